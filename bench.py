@@ -97,7 +97,16 @@ def parse():
     ap.add_argument("--no-host-canvas", action="store_true", help="N > 1: skip the shared-host-canvas record (every rank DMAs its bands over its own PCIe link)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary timed loops")
     ap.add_argument("--lean", action="store_true", help="= --no-cpu-baseline --no-dropin --no-secondary (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames the last one delivered to DIR/frames.npy (views x H x W x 3; a fixed "
+                         "sample of pixels when they exceed 64 MB), so that two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.profile_leg:
+        ap.error("--dump-outputs needs the timed steps, which --profile-leg does not run")
+    if a.dump_outputs and a.exchange == "none" and (a.gpus > 1 or a.force_group or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs with --exchange none: member 0 receives no frame")
     if a.lean:
         a.no_cpu_baseline = a.no_dropin = a.no_secondary = True
     a.pipeline = max(1, min(4, a.pipeline))
@@ -207,6 +216,30 @@ def timed(fn_step, fn_sync, steps, barrier=None):
 
 def ps(st):
     return st["rays_primary"] + st["rays_shadow"]
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, frames):
+    """Write `frames` (views, H, W, 3 on the device: what the last timed step delivered) to out_dir/frames.npy as float64
+    (float32 for 8-bit frames). Above DUMP_MAX_BYTES: DUMP_SAMPLE_PIXELS pixels drawn with seed 0 from the frames' shape alone
+    (the same pixels for the same arguments), as frames_sample.npy (pixels x 3) and their flat pixel indices in
+    frames_sample_index.npy."""
+    import numpy as np
+    import torch
+    frames = frames.to(torch.float64 if frames.dtype == torch.float64 else torch.float32)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    if frames.numel() * frames.element_size() <= DUMP_MAX_BYTES:
+        np.save(out / "frames.npy", frames.cpu().numpy())
+        return
+    npix = frames.numel() // 3
+    idx = np.sort(np.random.default_rng(0).choice(npix, DUMP_SAMPLE_PIXELS, replace=False))
+    pix = frames.reshape(npix, 3)[torch.from_numpy(idx).to(frames.device)]
+    np.save(out / "frames_sample.npy", pix.cpu().numpy())
+    np.save(out / "frames_sample_index.npy", idx.astype(np.float64))
 
 
 def main():
@@ -326,6 +359,9 @@ def run_single(args, rtc, np, torch, dev, dev_index, world, cam, cam_arr, wkey, 
     st = ctx.stats(extended=True)
     t_over = ctx.kernel_times_ms(1024)
     ctx.set_timing(0)
+    if args.dump_outputs:   # now: the legs below render into the same ring
+        last = ring[(state["i"] - 1) % R]
+        dump_outputs(args.dump_outputs, last.view(V, HP, W, 3)[:, :H] if V > 1 else last.unsqueeze(0))
     steps = max(1, args.steps)
     frames = steps * V
     k_ms, b_ms, n_solo = solo_leg(max(1, min(args.solo_launches, 64)))
@@ -490,6 +526,9 @@ def run_group(args, rtc, np, torch, dist, dev, dev_index, world, cam, cam_arr, w
     st = stats()
     times = ctx.kernel_times_ms(1024)
     ctx.set_timing(0)
+    if args.dump_outputs and rank == 0:   # now: the loops below render into the same canvases
+        b = (state["batch"] - 1) & 1
+        dump_outputs(args.dump_outputs, (canv[b] if args.exchange == "f64" else canv8[b])[:V])
     steps = max(1, args.steps)
     kernel_ms = float(np.mean(times)) if len(times) else 0.0
     info = ctx.last_launch_info()

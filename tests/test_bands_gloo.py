@@ -67,7 +67,9 @@ def _worker(rank, world_size, port, H, W, nframes, use_oracle, out_path):
                     ok = ok and rtc.group_row_owner(y, N) == (p, r)
         ok = ok and bool((seen == 1).all())
         np.save(out_path, np.array([ok]))
-    dist.barrier()
+    # the closing barrier as a CPU collective: dist.barrier() asks the HIP runtime for devices, which would open the GPU in
+    # every rank on a machine that has one
+    dist.all_reduce(torch.zeros(1))
     dist.destroy_process_group()
 
 

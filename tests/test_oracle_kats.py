@@ -1,6 +1,6 @@
 """Pin the CPU oracle against the reference's own known-answer tests.
 
-Every test here is a transcription (as data) of a #[test] in /root/reference/ch1/src/*.rs —
+Every test here is a transcription (as data) of a #[test] in the reference's ch1/src/*.rs —
 the name and file:line are in the docstring. Tolerance is the reference's own
 floats_equal: |a-b| < 1e-4 (lib.rs:13-15); `==` where the reference uses assert_eq!.
 No GPU is used; this is what makes the oracle trustworthy before it checks the HIP path.
