@@ -323,6 +323,15 @@ void        rtc_color_scale255(const double *components, size_t n, uint8_t *out)
  * f32 as the reference does), alpha 255. Canvas::new sets gamma = 1.0 (canvas.rs:30). `out` holds
  * width*height*4 bytes. Host. */
 void        rtc_canvas_to_rgba8(const double *rgb, uint32_t width, uint32_t height, float gamma, uint8_t *out);
+/* The quantisation table behind every DEVICE form of to_imgbuf (rtc_render_rgba8, rtc_render_views_rgba8,
+ * rtc_canvas_to_rgba8_device, rtc_group_render_host_rgba8). With e = (double)(1.0f / gamma) (color.rs:55-65),
+ * out[k-1] = T[k] for k = 1..255: the smallest double c >= +0 with Color::scale(pow(c, e), 255) >= k (+inf when only
+ * +inf gets there), found by bisection over the bit patterns of doubles with the host's own pow — the function
+ * rtc_canvas_to_rgba8 calls. The device then computes each channel as #{k : T[k] <= c} for c >= +0 (and follows pow's C99
+ * Annex F rules for NaN and inputs with the sign bit set), so its bytes are rtc_canvas_to_rgba8's, bit for bit, without
+ * evaluating pow. About 16 000 calls of pow per gamma; the device entries build a table once per gamma and context.
+ * RTC_ERR_ARG unless gamma is positive and finite. `out` holds 255 doubles. [host] */
+rtc_status  rtc_gamma_thresholds(float gamma, double *out);
 /* Canvas::write_to_file for a ".png" name (canvas.rs:80-84: to_imgbuf().save(path); the `image` crate encodes by
  * extension): an 8-bit PNG of `pixels` = height*width*channels bytes, channels = 4 (to_imgbuf's RGBA, colour type 6) or 3
  * (the device's Color::scale frame, colour type 2; a decoder supplies alpha 255, which is what to_imgbuf stores). PNG is
@@ -396,6 +405,30 @@ rtc_status  rtc_render(rtc_context *ctx, const rtc_world *w, const rtc_camera *c
  * canvas is not even written to HBM. Feed it to rtc_canvas_write_ppm_rgb8. Synchronous. `stats` may be NULL. */
 rtc_status  rtc_render_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam,
                             uint32_t mode, uint32_t flags, uint8_t *rgb8, rtc_stats *stats);
+/* Camera::render(&World) followed by canvas.set_gamma(gamma) and canvas.write_to_file(name) — to_imgbuf
+ * (canvas.rs:61-79): RGBA8, each channel Color::scale(c.powf(1/gamma), 255) with the reciprocal taken in f32
+ * (color.rs:55-65), alpha 255. Renders all rows, quantises them on the device in the render kernel's epilogue through the
+ * gamma's threshold table (rtc_gamma_thresholds) and copies only vsize*hsize*4 bytes into `rgba8`: byte for byte what
+ * rtc_canvas_to_rgba8 gives for the f64 canvas of rtc_render, which is never written to HBM. Feed it to
+ * rtc_canvas_write_png8 with channels = 4. gamma = 1.0 gives Color::scale's channels (rtc_render_rgb8's bytes) with alpha.
+ * RTC_ERR_ARG unless gamma is positive and finite. Synchronous. `stats` may be NULL. [device] */
+rtc_status  rtc_render_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                             float gamma, uint8_t *rgba8, rtc_stats *stats);
+/* rtc_render_views with to_imgbuf's RGBA at `gamma` as its only output: view v's rows land `v * view_rows` rows below
+ * view 0 in the DEVICE buffer d_rgba8, 4 bytes per pixel; rows, bands and views follow rtc_render_views' rules exactly
+ * (one view with first_band = 0, band_stride = 1 is a whole frame). Enqueues and returns; in a pipelined context the
+ * launches of different gammas may be in flight together (each gamma's table is uploaded once and never overwritten
+ * while a launch may read it). [device] */
+rtc_status  rtc_render_views_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
+                                   uint32_t first_band, uint32_t band_stride, float gamma, void *d_rgba8, uint32_t view_rows,
+                                   uint32_t flags);
+/* to_imgbuf (canvas.rs:61-79) of a canvas ALREADY IN DEVICE MEMORY — the reference's own order of calls, where the gamma
+ * is chosen after the render: `d_rgb` = rows*width*3 doubles (8-byte aligned), `d_rgba8` = rows*width*4 bytes; the same
+ * bytes as rtc_canvas_to_rgba8 on the host. Enqueued on the context's stream, in order with what the caller put there
+ * before (after launches of a pipelined context: rtc_context_fence first). RTC_ERR_ARG unless gamma is positive and
+ * finite. [device] */
+rtc_status  rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint32_t width, uint32_t rows, float gamma,
+                                       void *d_rgba8);
 /* render_lua (lua.rs:50-91) for an interpreted script: renders every job of `prog` in order — one launch per Render /
  * AddFrame call, 8-bit rows only (what the reference's file writers consume), a new device World whenever a job's world
  * differs from the previous one — and hands each frame (vsize*hsize*3 bytes, Color::scale, valid during the call only) to
@@ -539,6 +572,10 @@ rtc_status  rtc_group_render_host(rtc_group *g, const rtc_group_world *w, const 
 /* The same for the 8-bit frame (rtc_render_rgb8 across the group): `rgb8` = vsize*hsize*3 bytes. */
 rtc_status  rtc_group_render_host_rgb8(rtc_group *g, const rtc_group_world *w, const rtc_camera *cam, uint32_t mode,
                                        uint32_t flags, uint8_t *rgb8, rtc_stats *stats);
+/* The same for to_imgbuf's RGBA at `gamma` (rtc_render_rgba8 across the group, canvas.rs:61-79 / color.rs:55-65):
+ * `rgba8` = vsize*hsize*4 bytes. RTC_ERR_ARG unless gamma is positive and finite. */
+rtc_status  rtc_group_render_host_rgba8(rtc_group *g, const rtc_group_world *w, const rtc_camera *cam, uint32_t mode,
+                                        uint32_t flags, float gamma, uint8_t *rgba8, rtc_stats *stats);
 /* [host] The dealing of a frame's rows over the members (csrc/rtc_bands.h — the one definition rtc_group's tile sizes,
  * gather layout, host-canvas offsets and the un-deal kernel all use), for callers that lay out their own buffers:
  *   rtc_group_packed_rows          rows of one member's packed tile (= of one gather chunk per frame)

@@ -407,6 +407,14 @@ def to_rgba8(canvas: np.ndarray, gamma: float = 1.0) -> np.ndarray:
     return out
 
 
+def gamma_thresholds(gamma: float) -> np.ndarray:
+    """The 255 quantisation thresholds T[1..255] behind the device's to_imgbuf at `gamma` (rtc_gamma_thresholds): byte(c) =
+    #{k : T[k] <= c} for c >= +0. Raises RtcError (RTC_ERR_ARG) unless gamma is positive and finite."""
+    out = np.empty(255, dtype=np.float64)
+    _check(lib().rtc_gamma_thresholds(gamma, out.ctypes.data_as(C.POINTER(C.c_double))), "rtc_gamma_thresholds")
+    return out
+
+
 def color_scale255(rgb: np.ndarray) -> np.ndarray:
     """Color::scale(c, 255) (color.rs:100-114) element-wise on the host."""
     a = np.ascontiguousarray(rgb, dtype=np.float64)
@@ -568,6 +576,11 @@ class Context:
         _check(lib().rtc_binning_times_ms(self._h, buf, last, C.byref(n)), "rtc_binning_times_ms")
         return np.frombuffer(buf, dtype=np.float32, count=n.value).copy()
 
+    def canvas_to_rgba8_device(self, d_ptr: int, width: int, height: int, gamma: float, d_out: int) -> None:
+        """Canvas::to_imgbuf of an f64 canvas in DEVICE memory (address `d_ptr`, height x width x 3 doubles) into the device
+        buffer `d_out` (height x width x 4 bytes), enqueued on the context's stream (rtc_canvas_to_rgba8_device)."""
+        _check(lib().rtc_canvas_to_rgba8_device(self._h, d_ptr, width, height, gamma, d_out), "rtc_canvas_to_rgba8_device")
+
     def device_arith(self, op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.float64)
         bb = np.ascontiguousarray(b if b is not None else a, dtype=np.float64)
@@ -654,6 +667,30 @@ class DeviceWorld:
             return out, _stats_dict(st, cam.samples != 1)
         return out
 
+    def render_rgba8(self, cam: RtcCamera, gamma: float = 1.0, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False,
+                     out: np.ndarray | None = None):
+        """Camera::render + Canvas::set_gamma(gamma) + to_imgbuf: the (vsize, hsize, 4) uint8 RGBA frame, quantised on the
+        device — 4 bytes per pixel cross PCIe (rtc_render_rgba8). `out` as for render_rgb8 (host_canvas_rgba8: page-locked)."""
+        if out is None:
+            out = np.empty((cam.vsize, cam.hsize, 4), dtype=np.uint8)
+        elif out.shape != (cam.vsize, cam.hsize, 4) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous (vsize, hsize, 4) uint8 array")
+        st = RtcStats()
+        _check(lib().rtc_render_rgba8(self.ctx._h, self._h, C.byref(cam), mode, flags, gamma, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      C.byref(st) if with_stats else None), "rtc_render_rgba8")
+        if with_stats:
+            return out, _stats_dict(st, cam.samples != 1)
+        return out
+
+    def render_views_rgba8(self, cams, first_band: int, band_stride: int, d_ptr: int, view_rows: int, gamma: float = 1.0,
+                           mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+        """render_views with to_imgbuf's RGBA at `gamma` as the only output: DEVICE buffer `d_ptr`, 4 bytes per pixel
+        (rtc_render_views_rgba8)."""
+        arr = cams if isinstance(cams, C.Array) else (RtcCamera * len(cams))(*cams)
+        st = lib().rtc_render_views_rgba8(self.ctx._h, self._h, arr, len(arr), mode, first_band, band_stride, gamma, d_ptr, view_rows, flags)
+        if st != 0:
+            raise RtcError(st, "rtc_render_views_rgba8")
+
     def render_rows(self, cam: RtcCamera, y0: int, y1: int, d_ptr: int, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
                     d_ptr8: int | None = None) -> None:
         """Enqueue rows [y0, y1) into the DEVICE buffer at address `d_ptr` (no synchronisation);
@@ -694,6 +731,13 @@ class DeviceWorld:
 def host_canvas_rgb8(vsize: int, hsize: int) -> np.ndarray:
     """A zeroed (vsize, hsize, 3) uint8 frame in page-locked memory (rtc_host_alloc)."""
     arr = np.frombuffer(_Pinned(vsize * hsize * 3).buf, dtype=np.uint8).reshape(vsize, hsize, 3)
+    arr[...] = 0
+    return arr
+
+
+def host_canvas_rgba8(vsize: int, hsize: int) -> np.ndarray:
+    """A zeroed (vsize, hsize, 4) uint8 frame in page-locked memory (rtc_host_alloc), for render_rgba8's `out`."""
+    arr = np.frombuffer(_Pinned(vsize * hsize * 4).buf, dtype=np.uint8).reshape(vsize, hsize, 4)
     arr[...] = 0
     return arr
 
@@ -819,6 +863,17 @@ class GroupWorld:
                                                 C.byref(st) if with_stats else None), "rtc_group_render_host_rgb8")
         return (out, _stats_dict(st, cam.samples != 1)) if with_stats else out
 
+    def render_host_rgba8(self, cam: RtcCamera, out: np.ndarray, gamma: float = 1.0, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
+                          with_stats: bool = False):
+        """The same for to_imgbuf's RGBA at `gamma` ((vsize, hsize, 4) uint8; rtc_group_render_host_rgba8)."""
+        if out.shape != (cam.vsize, cam.hsize, 4) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous (vsize, hsize, 4) uint8 array")
+        st = RtcStats()
+        _check(lib().rtc_group_render_host_rgba8(self.group._h, self._h, C.byref(cam), mode, flags, gamma,
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st) if with_stats else None),
+               "rtc_group_render_host_rgba8")
+        return (out, _stats_dict(st, cam.samples != 1)) if with_stats else out
+
 
 # ---- [host] the dealing of rows over the members of a group (csrc/rtc_bands.h through the C-ABI) ------------------
 def group_packed_rows(vsize: int, nranks: int) -> int:
@@ -853,7 +908,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
 
 
 __all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "World", "camera", "ray_for_pixel",
-           "load_yaml", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
-           "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "format_ppm_rgb8", "write_ppm_rgb8",
+           "load_yaml", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
+           "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",
            "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcMaterial", "RtcShape", "RtcStats"]

@@ -118,6 +118,7 @@ PROTOTYPES = {
     "rtc_canvas_format_ppm": (C.c_size_t, [PD, U32, U32, C.c_char_p, C.c_size_t]),
     "rtc_color_scale255": (None, [PD, C.c_size_t, C.POINTER(C.c_uint8)]),
     "rtc_canvas_to_rgba8": (None, [PD, U32, U32, C.c_float, C.POINTER(C.c_uint8)]),
+    "rtc_gamma_thresholds": (C.c_int32, [C.c_float, PD]),
     "rtc_context_create": (C.c_int32, [C.c_int32, VP, C.POINTER(VP)]),
     "rtc_context_destroy": (None, [VP]),
     "rtc_context_synchronize": (C.c_int32, [VP]),
@@ -129,6 +130,9 @@ PROTOTYPES = {
     "rtc_render_views": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, U32, VP, VP, U32, U32]),
     "rtc_render": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, PD, C.POINTER(RtcStats)]),
     "rtc_render_rgb8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_render_rgba8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.c_float, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_render_views_rgba8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, U32, C.c_float, VP, U32, U32]),
+    "rtc_canvas_to_rgba8_device": (C.c_int32, [VP, VP, U32, U32, C.c_float, VP]),
     "rtc_canvas_write_ppm_rgb8": (C.c_int32, [C.c_char_p, C.POINTER(C.c_uint8), U32, U32]),
     "rtc_canvas_format_ppm_rgb8": (C.c_size_t, [C.POINTER(C.c_uint8), U32, U32, C.c_char_p, C.c_size_t]),
     "rtc_context_set_pipeline": (C.c_int32, [VP, U32]),
@@ -157,6 +161,7 @@ PROTOTYPES = {
     "rtc_group_render": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, U32, VP, VP]),
     "rtc_group_render_host": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, PD, C.POINTER(RtcStats)]),
     "rtc_group_render_host_rgb8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_group_render_host_rgba8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.c_float, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
     "rtc_group_packed_rows": (U32, [U32, U32]),
     "rtc_group_bands_owned": (U32, [U32, U32, U32]),
     "rtc_group_row_owner": (None, [U32, U32, C.POINTER(U32), C.POINTER(U32)]),

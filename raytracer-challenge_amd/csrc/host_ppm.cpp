@@ -5,6 +5,7 @@
 // codec by extension): PNG is lossless, so a decoder gives back exactly to_imgbuf's pixels whichever encoder wrote the
 // file. This one has no compressor: the zlib stream inside IDAT consists of stored blocks (RFC 1950 / 1951 §3.2.4).
 #include "rtc.h"
+#include "rtc_gamma.h"
 
 #include <cmath>
 #include <cstdio>
@@ -216,6 +217,69 @@ void rtc_canvas_to_rgba8(const double *rgb, uint32_t width, uint32_t height, flo
         for (int k = 0; k < 3; ++k) out[i * 4 + k] = static_cast<uint8_t>(scale255(std::pow(rgb[i * 3 + k], e)));
         out[i * 4 + 3] = 255; // std::u8::MAX canvas.rs:74
     }
+}
+
+// The threshold table of rtc_gamma.h for one gamma: T[k] by bisection on the bit patterns of non-negative doubles (their
+// order is the doubles' order), with this file's own pow and scale255 — the very functions rtc_canvas_to_rgba8 calls. T[k]
+// >= T[k-1], so each search starts where the previous one ended: about 255 x 64 calls of pow in all. Not part of
+// include/rtc.h: rtc_api.cpp fills the context's device tables with it.
+rtc_status rtc_gamma_build_table(float gamma, DevGamma *g) {
+    if (!g || !(gamma > 0.0f) || !std::isfinite(gamma)) return RTC_ERR_ARG;
+    const float ef = 1.0f / gamma; // Color::*_scaled_gamma: gamma.recip() in f32, widened (color.rs:55-65)
+    const double e = static_cast<double>(ef);
+    auto byte_of_bits = [e](uint64_t bits) {
+        double c;
+        std::memcpy(&c, &bits, sizeof c);
+        return scale255(std::pow(c, e));
+    };
+    const uint64_t inf_bits = 0x7ff0000000000000ull; // pow(+inf, e > 0) = +inf -> 255: every k is reached by +inf at the latest
+    uint64_t from = 0;
+    g->t[0] = 0.0;
+    for (int k = 1; k <= 255; ++k) {
+        uint64_t lo = from, hi = inf_bits; // smallest bit pattern in [lo, hi] whose byte is >= k
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (byte_of_bits(mid) >= k) hi = mid;
+            else lo = mid + 1;
+        }
+        std::memcpy(&g->t[k], &lo, sizeof lo);
+        from = lo;
+    }
+    g->e = ef;
+    if (std::isinf(e)) g->neg = RTC_GAMMA_NEG_ABS; // pow(x, +inf) depends on |x| only
+    else if (e == std::floor(e)) g->neg = std::fmod(e, 2.0) == 0.0 ? RTC_GAMMA_NEG_ABS : RTC_GAMMA_NEG_ZERO;
+    else g->neg = RTC_GAMMA_NEG_NAN;
+    g->_pad[0] = g->_pad[1] = 0;
+    return RTC_OK;
+}
+
+rtc_status rtc_gamma_thresholds(float gamma, double *out) {
+    if (!out) return RTC_ERR_ARG;
+    DevGamma g;
+    const rtc_status st = rtc_gamma_build_table(gamma, &g);
+    if (st != RTC_OK) return st;
+    std::memcpy(out, g.t + 1, sizeof(double) * 255);
+    return RTC_OK;
+}
+
+// Diagnostic (not part of include/rtc.h): rtc_gamma.h's lookup — the code the device runs — evaluated on the host for n
+// values, with the guess each value's own f32 estimate would give (`guess` = 0) or a deliberately wrong one (1: always 0,
+// so that every value takes the binary search). The CPU tests pin it against rtc_canvas_to_rgba8.
+rtc_status rtc_debug_gamma_lookup(float gamma, const double *c, size_t n, uint32_t guess, uint8_t *out) {
+    if (!c || !out) return RTC_ERR_ARG;
+    DevGamma g;
+    const rtc_status st = rtc_gamma_build_table(gamma, &g);
+    if (st != RTC_OK) return st;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t k = 0;
+        if (guess == 0) {
+            const float p = std::exp2(g.e * std::log2(static_cast<float>(std::fabs(c[i]))));
+            const float v = p * 255.0f;
+            k = v >= 1.0f ? (v < 255.0f ? static_cast<uint32_t>(v) : 255u) : 0u;
+        }
+        out[i] = static_cast<uint8_t>(rtc_gamma_byte_with(&g, c[i], k));
+    }
+    return RTC_OK;
 }
 
 rtc_status rtc_canvas_write_ppm(const char *path, const double *rgb, uint32_t width, uint32_t height) {

@@ -233,6 +233,49 @@ void fill_world(RenderParams &P, const rtc_world *w) {
     }
 }
 
+// The RGBA entries accept what Canvas::set_gamma can meaningfully hold: a positive, finite gamma.
+bool gamma_ok(float gamma) { return gamma > 0.f && std::isfinite(gamma); }
+
+// The device table of `gamma` (rtc_gamma.h), readable by work enqueued next on `stream` — stream bit `bit` of
+// rtc_context::GammaSlot::seen (lane l: l, the context's own stream: MAX_LANES). See rtc_context::gamma_slot.
+rtc_status gamma_table(rtc_context *ctx, float gamma, hipStream_t stream, uint32_t bit, const DevGamma **out) {
+    constexpr uint32_t NS = rtc_context::GAMMA_SLOTS;
+    if (!ctx->d_gamma) {
+        const hipError_t e = hipMalloc(&ctx->d_gamma, sizeof(DevGamma) * NS);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_gamma = nullptr;
+            return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE;
+        }
+    }
+    uint32_t s = 0;
+    while (s < NS && !(ctx->gamma_slot[s].used && ctx->gamma_slot[s].gamma == gamma)) ++s;
+    if (s == NS) { // a new gamma: a free slot, or — all taken — wait until nothing can read any table, then start afresh
+        s = 0;
+        while (s < NS && ctx->gamma_slot[s].used) ++s;
+        if (s == NS) {
+            HIP_TRY(drain_lanes(ctx));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            for (rtc_context::GammaSlot &sl : ctx->gamma_slot) { sl.used = false; sl.seen = 0; }
+            s = 0;
+        }
+        rtc_context::GammaSlot &sl = ctx->gamma_slot[s];
+        const rtc_status st = rtc_gamma_build_table(gamma, &sl.host);
+        if (st != RTC_OK) return st;
+        if (!sl.ready) HIP_TRY(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(ctx->d_gamma + s, &sl.host, sizeof(DevGamma), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(sl.ready, stream));
+        sl.used = true;
+        sl.gamma = gamma;
+        sl.seen = 1u << bit;
+    } else if (!(ctx->gamma_slot[s].seen & (1u << bit))) { // uploaded on another stream: wait for that copy once
+        HIP_TRY(hipStreamWaitEvent(stream, ctx->gamma_slot[s].ready, 0));
+        ctx->gamma_slot[s].seen |= 1u << bit;
+    }
+    *out = ctx->d_gamma + s;
+    return RTC_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -299,6 +342,9 @@ void rtc_context_destroy(rtc_context *ctx) {
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
     if (ctx->d_canvas) (void)hipFree(ctx->d_canvas);
     if (ctx->d_canvas8) (void)hipFree(ctx->d_canvas8);
+    if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
+    for (rtc_context::GammaSlot &sl : ctx->gamma_slot)
+        if (sl.ready) (void)hipEventDestroy(sl.ready);
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
     if (ctx->fence_ev) (void)hipEventDestroy(ctx->fence_ev);
     for (auto &pair : ctx->ev)
@@ -628,10 +674,11 @@ void rtc_world_destroy(rtc_world *w) {
     delete w;
 }
 
-// rows [y0, y1) in tile rows of 8, tile row k at image rows y0 + 8*k*band_stride; grid_y tile rows
+// rows [y0, y1) in tile rows of 8, tile row k at image rows y0 + 8*k*band_stride; grid_y tile rows. gamma > 0: d_rgb8
+// receives Canvas::to_imgbuf's RGBA at that gamma (4 B/pixel) instead of Color::scale's RGB.
 static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t y0,
                                 uint32_t y1, uint32_t band_stride, uint32_t grid_y, void *d_rgb, void *d_rgb8,
-                                uint32_t flags, uint32_t nviews = 1, uint32_t view_rows = 0) {
+                                uint32_t flags, uint32_t nviews = 1, uint32_t view_rows = 0, float gamma = 0.f) {
     HIP_TRY(hipSetDevice(ctx->device));
     RenderParams P;
     std::memset(&P, 0, sizeof P);
@@ -685,6 +732,10 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     const bool piped = ctx->lanes > 1;
     const uint32_t lane = piped ? ((src == SRC_CULL || src == SRC_CULL2) ? (uint32_t)(ctx->lane_next++ % ctx->lanes) : 0u) : 0u;
     hipStream_t stream = piped ? ctx->lane[lane] : ctx->stream;
+    if (gamma > 0.f) { // the table goes to the device on this launch's own stream (or is waited for there once)
+        const rtc_status gs = gamma_table(ctx, gamma, stream, piped ? lane : rtc_context::MAX_LANES, &P.gamma);
+        if (gs != RTC_OK) return gs;
+    }
     // the part of the frame this launch renders, in pixels (a rank's bands: its share)
     const unsigned long long launch_pixels = (unsigned long long)nviews * cam->hsize * std::min<unsigned long long>((unsigned long long)grid_y * 8u, cam->vsize);
     // binned primary pass (tile rows aligned with the image's): one small kernel puts every object on the list of each 8x8
@@ -999,9 +1050,10 @@ rtc_status rtc_last_kernel_ms(rtc_context *ctx, float *ms) {
 
 static_assert(RTC_MAX_VIEWS == RTC_MAX_VIEWS_PER_LAUNCH, "include/rtc.h and rtc_device.h disagree");
 
-rtc_status rtc_render_views(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
-                            uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t view_rows,
-                            uint32_t flags) {
+// rtc_render_views and rtc_render_views_rgba8 (gamma > 0: d_rgb8 holds RGBA, 4 B/pixel)
+static rtc_status render_views(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
+                               uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t view_rows,
+                               uint32_t flags, float gamma) {
     if (!ctx || !w || !cams || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
     if (nviews == 0 || nviews > RTC_MAX_VIEWS_PER_LAUNCH || band_stride == 0 || mode > RTC_MODE_RENDER_ASYNC) return RTC_ERR_ARG;
     if (cams[0].hsize == 0 || cams[0].vsize == 0) return RTC_ERR_ARG;
@@ -1022,14 +1074,27 @@ rtc_status rtc_render_views(rtc_context *ctx, const rtc_world *w, const rtc_came
         for (uint32_t v = 0; v < nviews; ++v) {
             const rtc_status st = render_launch(ctx, w, cams + v, mode, first_band * RTC_BAND_ROWS, cams[0].vsize, band_stride, mine,
                                                 d_rgb ? static_cast<double *>(d_rgb) + (size_t)v * view_rows * cams[0].hsize * 3u : nullptr,
-                                                d_rgb8 ? static_cast<unsigned char *>(d_rgb8) + (size_t)v * view_rows * cams[0].hsize * 3u : nullptr,
-                                                flags);
+                                                d_rgb8 ? static_cast<unsigned char *>(d_rgb8) + (size_t)v * view_rows * cams[0].hsize * (gamma > 0.f ? 4u : 3u) : nullptr,
+                                                flags, 1u, 0u, gamma);
             if (st != RTC_OK) return st;
         }
         return RTC_OK;
     }
     return render_launch(ctx, w, cams, mode, first_band * RTC_BAND_ROWS, cams[0].vsize, band_stride, mine, d_rgb, d_rgb8, flags,
-                         nviews, view_rows);
+                         nviews, view_rows, gamma);
+}
+
+rtc_status rtc_render_views(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
+                            uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t view_rows,
+                            uint32_t flags) {
+    return render_views(ctx, w, cams, nviews, mode, first_band, band_stride, d_rgb, d_rgb8, view_rows, flags, 0.f);
+}
+
+rtc_status rtc_render_views_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
+                                  uint32_t first_band, uint32_t band_stride, float gamma, void *d_rgba8, uint32_t view_rows,
+                                  uint32_t flags) {
+    if (!d_rgba8 || !gamma_ok(gamma)) return RTC_ERR_ARG;
+    return render_views(ctx, w, cams, nviews, mode, first_band, band_stride, nullptr, d_rgba8, view_rows, flags, gamma);
 }
 
 rtc_status rtc_render(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
@@ -1084,6 +1149,45 @@ rtc_status rtc_render_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camer
     if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
     if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
     return st;
+}
+
+rtc_status rtc_render_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, float gamma,
+                            uint8_t *rgba8, rtc_stats *stats) {
+    if (!ctx || !w || !cam || !rgba8 || w->ctx != ctx || !gamma_ok(gamma)) return RTC_ERR_ARG;
+    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || cam->samples > 255u) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)4 * cam->hsize * cam->vsize;
+    if (ctx->canvas8_bytes < bytes) { // the 8-bit scratch of rtc_render_rgb8, grown to 4 B/pixel
+        if (ctx->d_canvas8) (void)hipFree(ctx->d_canvas8);
+        ctx->d_canvas8 = nullptr;
+        ctx->canvas8_bytes = 0;
+        ++ctx->render_allocs;
+        const hipError_t e = hipMalloc(&ctx->d_canvas8, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
+        ctx->canvas8_bytes = bytes;
+    }
+    rtc_status st = RTC_OK;
+    if (stats) st = rtc_stats_reset(ctx);
+    // only the RGBA rows leave the kernel: no f64 canvas is written
+    if (st == RTC_OK)
+        st = render_launch(ctx, w, cam, mode, 0, cam->vsize, 1u, (cam->vsize + 7u) / 8u, nullptr, ctx->d_canvas8, flags, 1u, 0u, gamma);
+    if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE;
+    if (st == RTC_OK && hipMemcpyAsync(rgba8, ctx->d_canvas8, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
+    if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
+    if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
+    return st;
+}
+
+rtc_status rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint32_t width, uint32_t rows, float gamma, void *d_rgba8) {
+    if (!ctx || !d_rgb || !d_rgba8 || !gamma_ok(gamma) || ((size_t)d_rgb % sizeof(double)) != 0) return RTC_ERR_ARG;
+    const size_t n = (size_t)width * rows;
+    if (n == 0) return RTC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const DevGamma *g = nullptr;
+    const rtc_status st = gamma_table(ctx, gamma, ctx->stream, rtc_context::MAX_LANES, &g);
+    if (st != RTC_OK) return st;
+    HIP_TRY(rtc_launch_canvas_to_rgba8(static_cast<const double *>(d_rgb), n, g, static_cast<unsigned char *>(d_rgba8), ctx->stream));
+    return RTC_OK;
 }
 
 // render_lua (lua.rs:50-91) for a program rtc_lua_run has interpreted: every job is one render launch, 8-bit rows only. The

@@ -192,6 +192,8 @@ struct RenderParams {
     uint32_t nviews, view_rows;
     double *out;                 // rows x W x 3, rows = y1-y0 (band_stride 1) or 8*grid_y (packed bands)
     unsigned char *out8;         // optional: the same rows quantised by Color::scale(c, 255)
+    const struct DevGamma *gamma; // non-null: out8 receives Canvas::to_imgbuf's RGBA instead (4 B/pixel, alpha 255), each channel
+                                  // looked up in this gamma's threshold table (rtc_gamma.h); the tile is still staged at 3 B/pixel
     unsigned long long *counters; // CNT_N
     // probe mode (rtc_color_at): rays != nullptr
     const double *rays;

@@ -295,12 +295,14 @@ void rtc_group_world_destroy(rtc_group_world *w) {
 }
 
 // One launch per local member: its bands of `nframes` frames into tile buffer `b` (after the exchange that
-// last read that buffer); the member's exchange stream is made to wait for the launch.
+// last read that buffer); the member's exchange stream is made to wait for the launch. gamma > 0: the 8-bit tiles
+// hold RGBA at that gamma (rtc_render_views_rgba8, 4 B/pixel).
 static rtc_status render_members(rtc_group *g, const rtc_group_world *w, const rtc_camera *cams, uint32_t nframes, uint32_t mode,
-                                 uint32_t flags, bool want8, int b, bool want64 = true) {
+                                 uint32_t flags, bool want8, int b, bool want64 = true, float gamma = 0.f) {
     const uint32_t W = cams[0].hsize, H = cams[0].vsize, N = g->nranks;
     const uint32_t rows = packed_rows(H, N);
-    const size_t tile_bytes = (size_t)nframes * rows * W * 3u * sizeof(double), tile8_bytes = (size_t)nframes * rows * W * 3u;
+    const size_t tile_bytes = (size_t)nframes * rows * W * 3u * sizeof(double),
+                 tile8_bytes = (size_t)nframes * rows * W * (gamma > 0.f ? 4u : 3u);
     for (size_t i = 0; i < g->m.size(); ++i) {
         Member &mb = g->m[i];
         HIP_TRY(hipSetDevice(mb.device));
@@ -319,8 +321,10 @@ static rtc_status render_members(rtc_group *g, const rtc_group_world *w, const r
             mb.tile8_cap = tile8_bytes;
         }
         HIP_TRY(hipStreamWaitEvent(mb.s_render, mb.sent[b], 0)); // an event never recorded does not block
-        const rtc_status st = rtc_render_views(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, want64 ? mb.tile[b] : nullptr,
-                                               want8 ? mb.tile8[b] : nullptr, rows, flags);
+        const rtc_status st = gamma > 0.f
+                                  ? rtc_render_views_rgba8(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, gamma, mb.tile8[b], rows, flags)
+                                  : rtc_render_views(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, want64 ? mb.tile[b] : nullptr,
+                                                     want8 ? mb.tile8[b] : nullptr, rows, flags);
         if (st != RTC_OK) return st;
         HIP_TRY(hipEventRecord(mb.rendered[b], mb.s_render));
         HIP_TRY(hipStreamWaitEvent(mb.s_comm, mb.rendered[b], 0));
@@ -443,8 +447,9 @@ rtc_status rtc_group_render_host(rtc_group *g, const rtc_group_world *w, const r
     return st;
 }
 
-rtc_status rtc_group_render_host_rgb8(rtc_group *g, const rtc_group_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
-                                      uint8_t *rgb8, rtc_stats *stats) {
+// 3 B/pixel (gamma = 0: Color::scale) or 4 (gamma > 0: Canvas::to_imgbuf at that gamma)
+static rtc_status render_host8(rtc_group *g, const rtc_group_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                               uint8_t *rgb8, rtc_stats *stats, float gamma) {
     if (!g || !w || !cam || !rgb8 || w->g != g || w->w.size() != g->m.size()) return RTC_ERR_ARG;
     const uint32_t W = cam->hsize, H = cam->vsize, N = g->nranks;
     if (W == 0 || H == 0) return RTC_ERR_ARG;
@@ -452,10 +457,10 @@ rtc_status rtc_group_render_host_rgb8(rtc_group *g, const rtc_group_world *w, co
     const int b = (int)(g->batches & 1u);
     rtc_status st = RTC_OK;
     if (stats) st = rtc_group_stats_reset(g);
-    if (st == RTC_OK) st = render_members(g, w, cam, 1, mode, flags, true, b, false); // 8-bit rows only
+    if (st == RTC_OK) st = render_members(g, w, cam, 1, mode, flags, true, b, false, gamma); // 8-bit rows only
     if (st != RTC_OK) return st;
     ++g->batches;
-    const size_t row_bytes = (size_t)W * 3u, band_bytes = row_bytes * RTC_BAND_ROWS;
+    const size_t row_bytes = (size_t)W * (gamma > 0.f ? 4u : 3u), band_bytes = row_bytes * RTC_BAND_ROWS;
     const uint32_t nb = bands_of(H);
     for (Member &mb : g->m) { // band k of member r = image rows (r + k*N)*8 ..: one strided DMA per member, as for the f64 canvas
         if (mb.rank >= nb) continue;
@@ -474,6 +479,17 @@ rtc_status rtc_group_render_host_rgb8(rtc_group *g, const rtc_group_world *w, co
     st = rtc_group_synchronize(g);
     if (st == RTC_OK && stats) st = rtc_group_stats_read(g, stats);
     return st;
+}
+
+rtc_status rtc_group_render_host_rgb8(rtc_group *g, const rtc_group_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                      uint8_t *rgb8, rtc_stats *stats) {
+    return render_host8(g, w, cam, mode, flags, rgb8, stats, 0.f);
+}
+
+rtc_status rtc_group_render_host_rgba8(rtc_group *g, const rtc_group_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                       float gamma, uint8_t *rgba8, rtc_stats *stats) {
+    if (!(gamma > 0.f) || gamma == __builtin_inff()) return RTC_ERR_ARG; // positive and finite (NaN fails the first test)
+    return render_host8(g, w, cam, mode, flags, rgba8, stats, gamma);
 }
 
 rtc_status rtc_group_stats_read(rtc_group *g, rtc_stats *out) {

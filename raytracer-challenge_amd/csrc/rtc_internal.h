@@ -9,6 +9,7 @@
 
 #include "rtc.h"
 #include "rtc_device.h"
+#include "rtc_gamma.h"
 
 enum { SRC_SMEM = 0, SRC_LDS1 = 1, SRC_LDSN = 2, SRC_CULL = 3, SRC_CULL2 = 4 };
 
@@ -67,6 +68,21 @@ struct rtc_context {
     // ... and in a pipelined context (lanes > 1), where the binning kernel of launch i+1 runs beside launch i's render on the
     // other lane without any event: from this many pixels (RTC_BIN_SMALL_PIXELS_PIPELINED)
     unsigned long long bin_small_pixels_pipelined = 1500000ull;
+    // Gamma tables (rtc_gamma.h) of the RGBA entries: one slot of device memory per gamma, filled once — on the stream of
+    // the first launch that needs it — and never written again while the slot holds that gamma, so launches with different
+    // gammas may be in flight on different lanes at once. A stream that did not do the upload waits for it once (the
+    // slot's `ready` event; `seen`: bit l = lane l, bit MAX_LANES = `stream`). When every slot is taken the context waits
+    // for all its streams and starts the cache afresh.
+    static constexpr uint32_t GAMMA_SLOTS = 16;
+    struct GammaSlot {
+        bool used = false;
+        float gamma = 0.f;
+        uint32_t seen = 0;
+        hipEvent_t ready = nullptr;
+        DevGamma host{}; // the upload's source: stays put as long as the slot holds this gamma
+    };
+    DevGamma *d_gamma = nullptr; // GAMMA_SLOTS tables, allocated by the first RGBA call
+    GammaSlot gamma_slot[GAMMA_SLOTS];
 };
 
 struct rtc_world {
@@ -118,6 +134,8 @@ extern "C" hipError_t rtc_launch_binning(const DevCamera *views, uint32_t nviews
 enum { RTC_BIN_ROW_WORDS = 2 * RTC_MAX_VIEWS }; // a BinSet's tile_cnt buffer starts with the views' row words (RenderParams::tile_rows)
 extern "C" hipError_t rtc_launch_light_lists(uint32_t n, uint32_t cap, const DevBound *bound, const double light[3], double reach, DevTileBundle *cells,
                                              DevTileBundle *macros, uint32_t *cnt, uint32_t *list, hipStream_t stream);
+extern "C" rtc_status rtc_gamma_build_table(float gamma, DevGamma *g); // host_ppm.cpp
+extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
 extern "C" hipError_t rtc_launch_undeal(const void *staging, void *canvas, uint32_t nranks, uint32_t nframes, uint32_t H,
                                         uint32_t rows_max, size_t row_bytes, hipStream_t stream);
 

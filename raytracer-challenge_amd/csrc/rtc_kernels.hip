@@ -30,6 +30,7 @@
 #include "rtc.h"
 #include "rtc_bands.h"
 #include "rtc_device.h"
+#include "rtc_gamma.h"
 
 // Depth of the reflection / refraction frame stack. A frame is pushed only by a color_at call whose
 // `remaining` is not 0, and each level passes remaining - 1 on (shape.rs:730,735,752,765): a chain started with
@@ -1097,6 +1098,43 @@ DEVI unsigned char scale255(double c) {
     return (unsigned char)(int)v; // v_cvt_i32_f64 truncates toward zero
 }
 
+// Canvas::to_imgbuf's channel, scale255(c.powf(1/gamma)) (canvas.rs:61-79, color.rs:55-65), from the launch's threshold
+// table (rtc_gamma.h). The f32 estimate only picks which table entries to compare first; the byte is decided by the
+// comparisons (an 8-step binary search when the estimate missed), so it equals the host's bit for bit.
+DEVI unsigned char gamma_byte(const DevGamma *g, double c) {
+    const float cf = (float)__builtin_fabs(c);
+    const float v = __builtin_amdgcn_exp2f(g->e * __builtin_amdgcn_logf(cf)) * 255.0f; // v_log_f32 / v_exp_f32
+    const uint32_t guess = v >= 1.0f ? (v < 255.0f ? (uint32_t)v : 255u) : 0u;          // NaN -> 0
+    return (unsigned char)rtc_gamma_byte_with(g, c, guess);
+}
+
+// The RGBA form of a tile's 8-bit store (Canvas::to_imgbuf: R, G, B, alpha 255 — canvas.rs:74): `rows` x `cols` pixels of
+// the 3-byte staging (rows SRC_STRIDE bytes apart) to rows orow0.. / columns px0.. of `out8` (4 B/pixel, W pixels per row),
+// NT threads, this one number t. Whole rows of FULL pixels on a 4-byte aligned buffer: one dword per pixel, consecutive
+// threads on consecutive pixels; anything else byte by byte.
+template <uint32_t FULL, uint32_t SRC_STRIDE, uint32_t NT>
+DEVI void store_rgba(const unsigned char *src8, unsigned char *out8, uint32_t W, uint32_t orow0, uint32_t px0, uint32_t rows,
+                     uint32_t cols, uint32_t t) {
+    if (cols == FULL && ((size_t)out8 % 4u) == 0) {
+        for (uint32_t c = t; c < rows * FULL; c += NT) {
+            const uint32_t r = c / FULL, x = c % FULL;
+            const unsigned char *q = src8 + r * SRC_STRIDE + x * 3u;
+            const unsigned v = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | 0xff000000u;
+            RTC_CANVAS_STORE(reinterpret_cast<unsigned *>(out8 + ((size_t)(orow0 + r) * W + px0 + x) * 4u), v);
+        }
+    } else {
+        for (uint32_t c = t; c < rows * cols; c += NT) {
+            const uint32_t r = c / cols, x = c % cols;
+            const unsigned char *q = src8 + r * SRC_STRIDE + x * 3u;
+            unsigned char *d = out8 + ((size_t)(orow0 + r) * W + px0 + x) * 4u;
+            d[0] = q[0];
+            d[1] = q[1];
+            d[2] = q[2];
+            d[3] = 255u;
+        }
+    }
+}
+
 // Offsets of Camera::resample's extra rays (camera.rs:84-92). The reference draws them from
 // thread_rng; the documented counter-based stand-in (include/rtc.h, rtc_camera.samples): SplitMix64 of
 // ((y*hsize + x) << 16 | draw), top 53 bits -> [0, 1).
@@ -1117,7 +1155,9 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // ---- the kernel -------------------------------------------------------------------------
 // PROBE = true is the rtc_color_at flavour (arbitrary rays in, colours + hit records out); the
 // render flavour (PROBE = false) never carries the hit record's extra vectors in registers.
-template <int SRC, bool REFL, bool REFR, bool PROBE>
+// RGBA = true (render flavour only) is the launch with a gamma table (RenderParams::gamma): the 8-bit output is
+// Canvas::to_imgbuf's RGBA. Its own instantiation, so that the RGB kernels' code and resources stay exactly as they are.
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false>
 __global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
         const DevShade *__restrict__ t_shade, const DevPrim *__restrict__ t_prim, const DevBound *__restrict__ t_bound,
@@ -1990,9 +2030,16 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 const bool want8 = Po.out8 != nullptr;
                 if (want8) {
                     unsigned char *q = stage_u8 + (ty * TILE_W + tx) * 3u;
-                    q[0] = scale255(result.x);
-                    q[1] = scale255(result.y);
-                    q[2] = scale255(result.z);
+                    if constexpr (RGBA) { // Canvas::to_imgbuf's channels (rtc_gamma.h)
+                        const DevGamma *gt = Po.gamma;
+                        q[0] = gamma_byte(gt, result.x);
+                        q[1] = gamma_byte(gt, result.y);
+                        q[2] = gamma_byte(gt, result.z);
+                    } else {
+                        q[0] = scale255(result.x);
+                        q[1] = scale255(result.y);
+                        q[2] = scale255(result.z);
+                    }
                 }
 #ifdef RTC_DIAG_NO_STORE
                 if (Po.W == 0xffffffffu) // never true: keeps the code, skips the stores (diagnosis builds only)
@@ -2028,7 +2075,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         Po.out[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = src[r * (TILE_W * 3u) + k];
                     }
                 }
-                if (want8) {
+                if constexpr (RGBA) {
+                    if (want8) store_rgba<8u, TILE_W * 3u, 64u>(stage_u8 + wave * 24u, Po.out8, Po.W, orow0, px0, rows, cols, lane);
+                } else if (want8) {
                     const size_t row8 = (size_t)Po.W * 3u;
                     const unsigned char *src8 = stage_u8 + wave * 24u;
                     // 24 contiguous bytes per row: 3 pieces of 8 bytes
@@ -2071,7 +2120,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         Po.out[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = stage_f64[r * (TILE_W * 3u) + k];
                     }
                 }
-                if (want8) {
+                if constexpr (RGBA) {
+                    if (want8) store_rgba<TILE_W, TILE_W * 3u, BLOCK>(stage_u8, Po.out8, Po.W, orow0, px0, rows, cols, threadIdx.x);
+                } else if (want8) {
                     const size_t row8 = (size_t)Po.W * 3u;
                     // a tile row is 24 bytes per wave: 16-byte pieces for an even number of waves, 8-byte pieces for one
                     constexpr uint32_t PIECE = (TILE_W * 3u) % 16u == 0 ? 16u : 8u;
@@ -2511,25 +2562,52 @@ extern "C" hipError_t rtc_launch_undeal(const void *staging, void *canvas, uint3
     return hipGetLastError();
 }
 
+// Canvas::to_imgbuf (canvas.rs:61-79) of an f64 canvas already in device memory: `n` pixels of 24 bytes in, 4 bytes out
+// (alpha 255), every channel through the gamma's threshold table. One pixel per lane, grid-stride: consecutive lanes read
+// consecutive 24-byte pixels and write consecutive dwords.
+__global__ void __launch_bounds__(256) k_canvas_to_rgba8(const double *__restrict__ rgb, size_t n, const DevGamma *__restrict__ g,
+                                                         unsigned char *__restrict__ out, uint32_t aligned4) {
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
+        const double r = rgb[i * 3u], gr = rgb[i * 3u + 1u], b = rgb[i * 3u + 2u];
+        const unsigned v = (unsigned)gamma_byte(g, r) | ((unsigned)gamma_byte(g, gr) << 8) | ((unsigned)gamma_byte(g, b) << 16) | 0xff000000u;
+        if (aligned4) RTC_CANVAS_STORE(reinterpret_cast<unsigned *>(out + i * 4u), v);
+        else {
+            out[i * 4u] = (unsigned char)v;
+            out[i * 4u + 1u] = (unsigned char)(v >> 8);
+            out[i * 4u + 2u] = (unsigned char)(v >> 16);
+            out[i * 4u + 3u] = 255u;
+        }
+    }
+}
+
+extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t want = (n + 255u) / 256u;
+    const uint32_t blocks = (uint32_t)(want < 8192u ? want : 8192u); // at most 8192 workgroups (2M lanes); the loop strides over the rest
+    hipLaunchKernelGGL(k_canvas_to_rgba8, dim3(blocks), dim3(256), 0, stream, rgb, n, g, out, ((size_t)out % 4u) == 0 ? 1u : 0u);
+    return hipGetLastError();
+}
+
 // ---- launchers (called from rtc_api.cpp) --------------------------------------------------
-template <int SRC, bool REFL, bool REFR, bool PROBE>
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA>
 static hipError_t launch_kernel(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
                                 hipEvent_t e1) {
     if (lds_bytes > 48 * 1024) { // more dynamic LDS than the default limit: opt in (up to 160 KiB per CU on gfx950)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
     // e0/e1 (may be NULL) receive the dispatch's own begin/end timestamps: no marker packets on the stream
-    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
+    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
                           P.kind, P.shade, P.prim, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.idtab, P.pre, P.pre_s);
     return hipGetLastError();
 }
 template <int SRC, bool REFL, bool REFR>
 static hipError_t launch_one(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
                              hipEvent_t e1) {
-    if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true>(P, grid, lds_bytes, stream, e0, e1);
-    return launch_kernel<SRC, REFL, REFR, false>(P, grid, lds_bytes, stream, e0, e1);
+    if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false>(P, grid, lds_bytes, stream, e0, e1);
+    if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true>(P, grid, lds_bytes, stream, e0, e1);
+    return launch_kernel<SRC, REFL, REFR, false, false>(P, grid, lds_bytes, stream, e0, e1);
 }
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,

@@ -158,13 +158,36 @@ class Canvas { // canvas.rs:16-109
     // A Canvas returned by Camera::render_rgb8 / render_async_rgb8 holds ONLY what the reference's file writers read from a
     // Canvas — Color::scale(c, 255) of every component (canvas.rs:98-104, color.rs:100-114), evaluated on the device: 3 bytes
     // per pixel crossed PCIe instead of 24 and `pixels` is empty. write_to_file_simple writes the same file either way.
+    // Blind spot: those bytes are gamma 1's, so write_to_file of such a Canvas ignores `gamma` — a caller that sets a gamma
+    // renders with Camera::render_rgba8 instead.
     std::vector<uint8_t> rgb8;
+    // A Canvas returned by Camera::render_rgba8 / render_async_rgba8 holds to_imgbuf's RGBA (canvas.rs:61-79) at the gamma
+    // it was rendered with (`rgba8_gamma`, also set as `gamma`), quantised on the device: 4 bytes per pixel crossed PCIe,
+    // `pixels` and `rgb8` are empty. write_to_file writes it as it is and throws if `gamma` was changed after the render.
+    std::vector<uint8_t> rgba8;
+    float rgba8_gamma = 1.0f;
     Canvas(uint32_t w, uint32_t h) : width(w), height(h), pixels(static_cast<size_t>(w) * h * 3, 0.0) {} // BLACK canvas.rs:37-41
     static Canvas quantised(uint32_t w, uint32_t h) { Canvas c(0, 0); c.width = w; c.height = h; c.rgb8.assign(static_cast<size_t>(w) * h * 3, 0); return c; }
+    static Canvas imgbuf(uint32_t w, uint32_t h, float g) {
+        Canvas c(0, 0);
+        c.width = w; c.height = h;
+        c.rgba8.assign(static_cast<size_t>(w) * h * 4, 0);
+        c.gamma = c.rgba8_gamma = g;
+        return c;
+    }
     bool is_quantised() const { return pixels.empty() && !rgb8.empty(); }
+    bool is_imgbuf() const { return pixels.empty() && !rgba8.empty(); }
     void write_pixel(uint32_t x, uint32_t y, Color c) { double *p = at(x, y); p[0] = c.red; p[1] = c.green; p[2] = c.blue; }
     Color get_pixel(uint32_t x, uint32_t y) const { const double *p = const_cast<Canvas *>(this)->at(x, y); return {p[0], p[1], p[2]}; }
     void write_to_file_simple(const std::string &file_name) const { // canvas.rs:86-109
+        if (is_imgbuf()) { // the PPM is Color::scale's (gamma 1): only an RGBA frame of gamma 1 holds those bytes
+            if (rgba8_gamma != 1.0f) throw Panic(RTC_ERR_ARG, "Canvas::write_to_file_simple: the Canvas holds RGBA at gamma != 1 (Camera::render_rgba8)");
+            std::vector<uint8_t> rgb(static_cast<size_t>(width) * height * 3);
+            for (size_t i = 0; i < static_cast<size_t>(width) * height; ++i)
+                for (int k = 0; k < 3; ++k) rgb[i * 3 + k] = rgba8[i * 4 + k];
+            check(rtc_canvas_write_ppm_rgb8(file_name.c_str(), rgb.data(), width, height), "Canvas::write_to_file_simple");
+            return;
+        }
         if (is_quantised()) check(rtc_canvas_write_ppm_rgb8(file_name.c_str(), rgb8.data(), width, height), "Canvas::write_to_file_simple");
         else check(rtc_canvas_write_ppm(file_name.c_str(), pixels.data(), width, height), "Canvas::write_to_file_simple");
     }
@@ -175,6 +198,12 @@ class Canvas { // canvas.rs:16-109
         std::string ext = dot == std::string::npos ? std::string() : file_name.substr(dot + 1);
         for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
         if (ext != "png") throw Panic(RTC_ERR_ARG, "Canvas::write_to_file(" + file_name + "): only .png is written here (write_to_file_simple: PPM)");
+        if (is_imgbuf()) {
+            if (gamma != rgba8_gamma)
+                throw Panic(RTC_ERR_ARG, "Canvas::write_to_file(" + file_name + "): gamma was changed after Camera::render_rgba8 made this frame");
+            check(rtc_canvas_write_png8(file_name.c_str(), rgba8.data(), width, height, 4), "Canvas::write_to_file");
+            return;
+        }
         if (is_quantised()) { check(rtc_canvas_write_png8(file_name.c_str(), rgb8.data(), width, height, 3), "Canvas::write_to_file"); return; }
         std::vector<uint8_t> rgba(static_cast<size_t>(width) * height * 4);
         rtc_canvas_to_rgba8(pixels.data(), width, height, gamma, rgba.data());
@@ -183,7 +212,7 @@ class Canvas { // canvas.rs:16-109
     float gamma = 1.0f; // canvas.rs:30
   private:
     double *at(uint32_t x, uint32_t y) {
-        if (is_quantised()) throw std::logic_error("Canvas holds the 8-bit frame only (Camera::render_rgb8): render() for f64 pixels");
+        if (is_quantised() || is_imgbuf()) throw std::logic_error("Canvas holds the 8-bit frame only (Camera::render_rgb8 / render_rgba8): render() for f64 pixels");
         if (x >= width || y >= height) throw std::out_of_range("Canvas index out of bounds");
         return pixels.data() + (static_cast<size_t>(y) * width + x) * 3;
     }
@@ -314,6 +343,10 @@ class Camera { // camera.rs:17-160
     // comes back quantised (Canvas::rgb8), see Canvas.
     Canvas render_rgb8(const World &w) const { return run8(w, RTC_MODE_RENDER); }
     Canvas render_async_rgb8(const World &w) const { return run8(w, RTC_MODE_RENDER_ASYNC); }
+    // render + canvas.set_gamma(gamma) for a caller that then calls write_to_file (main.rs, lua.rs:67): the Canvas holds
+    // to_imgbuf's RGBA at that gamma (Canvas::rgba8), made on the device byte for byte as the host conversion makes it.
+    Canvas render_rgba8(const World &w, float gamma) const { return run_rgba8(w, RTC_MODE_RENDER, gamma); }
+    Canvas render_async_rgba8(const World &w, float gamma) const { return run_rgba8(w, RTC_MODE_RENDER_ASYNC, gamma); }
 
   private:
     Canvas run(const World &w, uint32_t mode) const {
@@ -330,6 +363,14 @@ class Camera { // camera.rs:17-160
         Canvas canvas = Canvas::quantised(hsize, vsize);
         World::Uploaded up(w);
         check(rtc_render_rgb8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
+        return canvas;
+    }
+    Canvas run_rgba8(const World &w, uint32_t mode, float gamma) const {
+        rtc_camera c = flat_;
+        c.samples = antialiasing_samples;
+        Canvas canvas = Canvas::imgbuf(hsize, vsize, gamma);
+        World::Uploaded up(w);
+        check(rtc_render_rgba8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, gamma, canvas.rgba8.data(), nullptr), "Camera::render_rgba8");
         return canvas;
     }
     rtc_camera flat_{};

@@ -19,8 +19,11 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     def g(k):
         m = re.search(k + r": (\d+)", blk)
         return m.group(1) if m else "?"
-    m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)E", name)
-    tag = "k_trace<%s,refl=%s,refr=%s,probe=%s>" % m.groups() if m else name[:44]
+    m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?", name)
+    if m:
+        tag = "k_trace<%s,refl=%s,refr=%s,probe=%s" % m.groups()[:4] + (",rgba>" if m.group(5) == "1" else ">")
+    else:
+        tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
     rows.append(f"{tag:44s} VGPR {g('VGPRs'):>4s} SGPR {g('SGPRs'):>4s} scratch {scratch:>5s} occupancy {occ:>2s} LDS {lds:>6s}")
 print("\n".join(sorted(rows)))
