@@ -454,7 +454,8 @@ rtc_status  rtc_stats_reset(rtc_context *ctx);
  * kernel is timed separately, rtc_binning_times_ms) unless rtc_context_set_timing says
  * otherwise. The context keeps the most recent 1024 pairs. rtc_kernel_times_ms writes the
  * durations (ms) of the latest min(cap, kept) launches, oldest first, and their number to *n; rtc_last_kernel_ms is the newest one alone
- * (RTC_ERR_ARG if nothing was launched yet). Both wait for the newest launch to finish. */
+ * (RTC_ERR_ARG if nothing was launched yet). Both wait for every launch they report to finish: on a pipelined context
+ * (rtc_context_set_pipeline) those launches may still run on several lanes. */
 rtc_status  rtc_kernel_times_ms(rtc_context *ctx, float *out, uint32_t cap, uint32_t *n);
 /* The same ring for the launches' BINNING kernels (k_bin_tiles: per-tile candidate lists, built per launch for large
  * launches; 0 for a launch that had none): out[k] belongs to the same launch as rtc_kernel_times_ms' out[k]. The render

@@ -1009,6 +1009,18 @@ rtc_status rtc_context_set_timing(rtc_context *ctx, uint32_t every) {
     return RTC_OK;
 }
 
+// Waits until the newest `take` timed launches have ended. In order on one stream the newest launch's end follows every
+// earlier one; a pipelined context's launches run on several lanes, so each pair's end is waited for (rtc_context_set_pipeline
+// drains the lanes, so pairs recorded before a switch back to depth 1 are complete already).
+static hipError_t wait_timed(rtc_context *ctx, uint64_t take) {
+    if (ctx->lanes <= 1) return hipEventSynchronize(ctx->ev[(ctx->timed - 1) % rtc_context::EV_RING][1]);
+    for (uint64_t k = 0; k < take; ++k) {
+        const hipError_t e = hipEventSynchronize(ctx->ev[(ctx->timed - take + k) % rtc_context::EV_RING][1]);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 rtc_status rtc_kernel_times_ms(rtc_context *ctx, float *out, uint32_t cap, uint32_t *n) {
     if (!ctx || !n || (cap && !out)) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1016,7 +1028,7 @@ rtc_status rtc_kernel_times_ms(rtc_context *ctx, float *out, uint32_t cap, uint3
     const uint64_t take = have < cap ? have : cap;
     *n = (uint32_t)take;
     if (take == 0) return RTC_OK;
-    HIP_TRY(hipEventSynchronize(ctx->ev[(ctx->timed - 1) % rtc_context::EV_RING][1]));
+    HIP_TRY(wait_timed(ctx, take));
     for (uint64_t k = 0; k < take; ++k) {
         hipEvent_t *pair = ctx->ev[(ctx->timed - take + k) % rtc_context::EV_RING];
         HIP_TRY(hipEventElapsedTime(&out[k], pair[0], pair[1]));
@@ -1031,7 +1043,7 @@ rtc_status rtc_binning_times_ms(rtc_context *ctx, float *out, uint32_t cap, uint
     const uint64_t take = have < cap ? have : cap;
     *n = (uint32_t)take;
     if (take == 0) return RTC_OK;
-    HIP_TRY(hipEventSynchronize(ctx->ev[(ctx->timed - 1) % rtc_context::EV_RING][1])); // the render kernel follows its binning
+    HIP_TRY(wait_timed(ctx, take)); // each render kernel follows its own binning
     for (uint64_t k = 0; k < take; ++k) {
         const uint64_t sl = (ctx->timed - take + k) % rtc_context::EV_RING;
         out[k] = 0.f;
