@@ -7,7 +7,7 @@
 //  * one thread per pixel; a wave owns an 8x8 pixel tile (coherent hit / miss / shadow
 //    decisions), a workgroup 2 such tiles side by side (1 for the frame-stack kernels, rtc_device.h);
 //    tile = workgroup id, which the hardware
-//    deals round-robin over the 8 XCDs (an even share of the image for each, RTC_TILE_ORDER).
+//    deals round-robin over the 8 XCDs (an even share of the image for each; see k_trace's tile loop).
 //  * every value is IEEE f64 evaluated in the reference's operation order; the file is
 //    compiled with -ffp-contract=off, so results are bit-identical to the CPU path apart
 //    from pow() (material.rs:355).
@@ -36,85 +36,6 @@
 // `remaining` is not 0, and each level passes remaining - 1 on (shape.rs:730,735,752,765): a chain started with
 // remaining = 5 (Camera::MAX_REFLECTIONS, camera.rs:31) suspends at most 5 shade_hit calls.
 #define RTC_MAX_STACK 5
-// Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x
-// 4 doubles x 64 lanes = 10 KB per wave, SoA ([level][component][lane]: lane-consecutive 8-byte accesses, no bank
-// conflicts). The scratch stack was HBM traffic: C4 wrote 941 MB and fetched 236 MB per frame against 453 MB
-// algorithmic (profiles/r02_a_c4_pmc.json). The output tile is staged in the same LDS (the stack is dead by then),
-// so a one-wave workgroup still fits 16 times in a CU's 160 KB. 0 = the scratch stack (A/B).
-#ifndef RTC_LDS_STACK
-#define RTC_LDS_STACK 1
-#endif
-// Tile output: true = each wave stores its own 8x8 part as soon as it is done, false = workgroup
-// barrier + cooperative store of the workgroup's whole tile (full 128-byte lines). Measured: the barrier
-// form wins for the flat kernel (0.0738 vs 0.0784 ms, 192-byte row pieces straddle lines), the
-// per-wave form for the frame-stack kernels, whose waves finish far apart (0.662 vs 0.690 ms).
-// Binned primary pass: request the tile's list at kernel entry, ahead of the ray generation (1), or where the pass needs
-// it (0). Measured: the early request is SLOWER (north star +3 %, C5 +4 %, where it also reads all 64 slots of a million
-// tiles; profiles/r02_exp_packed_tile_lists.log), so it is off.
-#ifndef RTC_BIN_HOIST
-#define RTC_BIN_HOIST 0
-#endif
-// Binned primary pass: the exact tests take the camera origin in object space and the sphere's c from the table the binning
-// kernel wrote for the view (1: closest_prim, 24 VALU instructions fewer per sphere test) or transform the origin again (0).
-#ifndef RTC_BIN_PRIM
-#define RTC_BIN_PRIM 1
-#endif
-// Canvas stores (written once, never read by the kernel): plain (0) or non-temporal (1).
-#ifndef RTC_NT_STORE
-#define RTC_NT_STORE 1
-#endif
-#if RTC_NT_STORE
-#define RTC_CANVAS_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define RTC_CANVAS_STORE(p, v) (*(p) = (v))
-#endif
-#ifndef RTC_WAVE_OUTPUT
-#define RTC_WAVE_OUTPUT(REFL) (REFL)
-#endif
-// Per-lane prefilter (ray_touches) in front of the exact test, beyond the incoherent secondary rays
-// that always get it. Shadow segments in large worlds (two-level cull): the wave-level bundle of a
-// dense world keeps ~17 candidates per pass of which each lane's own segment touches few — 1000
-// spheres 0.535 -> 0.423 ms, 10 000 spheres 0.560 -> 0.462 ms; at 100 objects (one-level cull, ~2
-// candidates per pass) the filter costs more than it saves (0.0754 -> 0.0767 ms). The frame-stack
-// kernels take it too: shadow segments from scattered secondary hits (6.7 exact tests per pass
-// without it), reflective 1080p 0.551 -> 0.536 ms.
-#ifndef RTC_SHADOW_LANE_FILTER
-#define RTC_SHADOW_LANE_FILTER(SRC, REFL) ((SRC) == SRC_CULL2 || (REFL))
-#endif
-// Apex of a secondary bundle: 0 = centroid of the origins (tighter origin spread), 1 = the axis lane's origin (four wave
-// reductions less per secondary pass: C4 -1.4 %, reflective 1080p -1 %; profiles/r03_exp_small_steps.log). Either is conservative: rho is
-// measured from whatever apex is chosen.
-#ifndef RTC_BUNDLE_APEX_LANE
-#define RTC_BUNDLE_APEX_LANE 1
-#endif
-#ifndef RTC_PRIMARY_LANE_FILTER
-#define RTC_PRIMARY_LANE_FILTER(SRC) false
-#endif
-// Shape of the cull walks. A round of the group level tests RTC_GROUP_SLOTS x 64 group spheres at once (ordered walks
-// then take the nearest key across the whole round), a round of the one-level cull RTC_OBJ_SLOTS x 64 object spheres,
-// and RTC_EXPAND_K surviving groups are expanded together. Measured on MI355X (ms per frame, 8 frames per launch):
-// slots/objslots/K = 1/1/1: C3 0.234, C5 5.07, north star 0.0696; 4/2/2: 0.259 / 5.63 / 0.0724; 4/4/4: 0.274 / 5.99 / 0.0718.
-// Batching the walks buys nothing: these kernels are bound by VALU issue slots, not by the length of the
-// load -> test -> ballot dependency chains, and the wider rounds cost instructions and registers. Defaults 1/1/1.
-#ifndef RTC_GROUP_SLOTS
-#define RTC_GROUP_SLOTS 1
-#endif
-#ifndef RTC_OBJ_SLOTS
-#define RTC_OBJ_SLOTS 1
-#endif
-#ifndef RTC_EXPAND_K
-#define RTC_EXPAND_K 1
-#endif
-#ifndef RTC_TILE_ORDER
-// Workgroup id -> tile. The hardware deals consecutive workgroup ids round-robin over the 8 XCDs.
-// 1 (default): tile = workgroup id, so every XCD gets every 8th tile of the image — an even share
-//    of sky, floor and spheres. 0: remap so that each XCD owns one contiguous band of rows (the
-//    usual "XCD-aware" advice, for L2 locality): here there is nothing to share (the scene is 50 KB,
-//    the canvas is write-once) and the bands are wildly uneven (sky above, everything below), so
-//    the top XCDs idle: north star 0.099 ms vs 0.073 ms, reflective 1.07 vs 0.69 ms, 10 000
-//    spheres 0.66 vs 0.54 ms. 2: round-robin, bottom rows first (no better than 1).
-#define RTC_TILE_ORDER 1
-#endif
 // 2nd argument of __launch_bounds__ = minimum waves per SIMD (caps VGPRs: 5 -> 96, 4 -> 128,
 // 3 -> 168, 2 -> 256). Measured on the north-star scene (culled flat kernel, 90 VGPRs):
 // 4 -> 0.0784 ms, 5 -> 0.0736 ms, 6 -> 0.0882 ms with 256-thread workgroups and one frame per launch; with
@@ -139,24 +60,6 @@ struct V3 {
 
 #define DEVI __device__ __forceinline__
 
-// Diagnostic build only (-DRTC_STAMPS): s_memtime stamps around the phases of k_trace, summed per
-// phase into counters CNT_STAMP0.. (read with rtc_debug_counters). Never enabled in the shipped
-// library; the stamped build's run time is not meaningful, only the shares are.
-#ifdef RTC_STAMPS
-#define DIAG(i, v) do { diag_c[i] += (v); } while (0)
-#define DIAG_FILTER(p) do { if (p) *(p) += 1u; } while (0)
-#define DIAG_PTR(i) (&diag_c[i])
-// STAMP(i): the time since the previous stamp (whichever it was) is added to phase i — summed over all passes of the wave in
-// stamp_t[i], and over its secondary passes only in stamp_t[8 + i].
-#define STAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-                      stamp_t[i] += now_ - stamp_last; if (stamp_secondary) stamp_t[8 + (i)] += now_ - stamp_last; stamp_last = now_; } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#define DIAG(i, v) do { } while (0)
-#define DIAG_FILTER(p) do { } while (0)
-#define DIAG_PTR(i) ((unsigned *)nullptr)
-#endif
-
 DEVI V3 mk(double x, double y, double z) { V3 v; v.x = x; v.y = y; v.z = z; return v; }
 DEVI V3 vadd(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 DEVI V3 vsub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -173,14 +76,11 @@ DEVI V3 vnormalize_plain(V3 a) {
 // The three IEEE divisions share their divisor. hipcc expands x / y (f64) into v_div_scale x2, v_rcp, four v_fma refining
 // 1/y, v_mul, v_fma, v_div_fmas, v_div_fixup (11 instructions); everything up to the refined reciprocal depends on y alone
 // as long as v_div_scale leaves y unscaled, which it does unless y, 1/y or x/y leave the normal range or x is tiny
-// (ISA: V_DIV_SCALE_F64). RTC_SHARED_NORMALIZE = 1 evaluates that part once when |mag| is in [2^-400, 2^400] and every
+// (ISA: V_DIV_SCALE_F64). vnormalize_shared evaluates that part once when |mag| is in [2^-400, 2^400] and every
 // component is +-0 or at least 2^-500 in magnitude (then no scaling happens, VCC is clear and v_div_fmas is a plain fma):
 // 5 + 3 x 4 instructions + the guards instead of 33, bit-identical (tests/test_gpu_round3.py: rtc_device_arith op 5 vs op 6
-// vs the host, 2 M triples). Measured (profiles/r03_exp_shared_normalize.log): no gain in k_trace (north star equal, C4 +1 %), so 0 there;
-// the binning kernel uses it (primary_dir).
-#ifndef RTC_SHARED_NORMALIZE
-#define RTC_SHARED_NORMALIZE 0
-#endif
+// vs the host, 2 M triples). The binning kernel uses it (primary_dir); k_trace keeps vnormalize_plain, where the shared form
+// measured no gain (north star equal, C4 +1 %, profiles/r03_exp_shared_normalize.log).
 DEVI V3 vnormalize_shared(V3 a) {
     const double mag = sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
     auto in_range = [](double v) { return __builtin_amdgcn_class(v, 0x060 /* +-0 */) || fabs(v) >= 0x1p-500; };
@@ -198,13 +98,6 @@ DEVI V3 vnormalize_shared(V3 a) {
         return mk(quot(a.x), quot(a.y), quot(a.z));
     }
     return mk(a.x / mag, a.y / mag, a.z / mag);
-}
-DEVI V3 vnormalize(V3 a) {
-#if RTC_SHARED_NORMALIZE
-    return vnormalize_shared(a);
-#else
-    return vnormalize_plain(a);
-#endif
 }
 // Vector::reflect vec.rs:106-108: self - n*(2*(self.n))
 DEVI V3 vreflect(V3 v, V3 n) { return vsub(v, vmul(n, 2. * vdot(v, n))); }
@@ -394,23 +287,9 @@ template <class P, class Q> DEVI void closest_prim(uint32_t kind, P m, Q pr, V3 
     }
 }
 
-// ---- wave64 reductions (DPP): inclusive scan inside each row of 16 lanes, then two row
-// broadcasts; the total lands in lane 63. All 64 lanes must execute these (converged code);
+// ---- wave64 reduction (DPP): inclusive scan inside each row of 16 lanes, then two row
+// broadcasts; the result lands in lane 63. All 64 lanes must execute it (converged code);
 // lanes that do not take part pass the identity.
-template <int CTRL, int ROW_MASK> DEVI float dpp_f32(float old, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src),
-                                                                 CTRL, ROW_MASK, 0xf, false));
-}
-DEVI float lane63(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)); }
-DEVI float wave_sum(float v) {
-    v += dpp_f32<0x111, 0xf>(0.f, v); // row_shr:1
-    v += dpp_f32<0x112, 0xf>(0.f, v); // row_shr:2
-    v += dpp_f32<0x114, 0xf>(0.f, v); // row_shr:4
-    v += dpp_f32<0x118, 0xf>(0.f, v); // row_shr:8
-    v += dpp_f32<0x142, 0xa>(0.f, v); // row_bcast:15 into rows 1,3
-    v += dpp_f32<0x143, 0xc>(0.f, v); // row_bcast:31 into rows 2,3
-    return lane63(v);
-}
 // Maximum of NON-NEGATIVE floats (NaN-free): their bit patterns order like unsigned integers, and
 // v_max_u32 with identity 0 folds into the DPP instruction (one instruction per step).
 template <int CTRL, int ROW_MASK> DEVI unsigned dpp_u32(unsigned src) {
@@ -464,8 +343,8 @@ DEVI double lane_f64(double x, uint32_t l) { // lane l's value in every lane (l 
 DEVI bool finite3(V3 v) { return fabs(v.x) < __builtin_inf() && fabs(v.y) < __builtin_inf() && fabs(v.z) < __builtin_inf(); }
 
 // SHARED: every active lane's ray starts at `apex` (the camera origin, or the light for shadow
-// segments walked backwards); otherwise the apex is the centroid of the lanes' origins and `rho`
-// their spread. REACH: the rays end after `reach` (shadow segments). The axis is the direction of
+// segments walked backwards); otherwise the apex is the origin of the axis lane and `rho` the
+// spread of the lanes' origins around it. REACH: the rays end after `reach` (shadow segments). The axis is the direction of
 // one active lane near the tile centre (no reduction needed); the half-angle is the largest
 // deviation from it.
 template <bool SHARED, bool REACH>
@@ -505,17 +384,11 @@ DEVI Bundle make_bundle(bool active, V3 apex, V3 o, V3 d, double reach) {
     if (!narrow) cmin = 1.f - wave_max_nonneg(good ? fmaxf(0.f, 1.f - dotv) : 0.f);
     float rho = 0.f;
     if constexpr (!SHARED) {
-#if RTC_BUNDLE_APEX_LANE
-        // apex = the origin of the axis lane (three readlanes) instead of the centroid of the origins (four wave sums)
+        // apex = the origin of the axis lane (three readlanes), not the centroid of the origins (four wave sums): C4 -1.4 %,
+        // reflective 1080p -1 % (profiles/r03_exp_small_steps.log). Either is conservative: rho is measured from the apex.
         const float mx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, (float)o.x), lane0));
         const float my = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, (float)o.y), lane0));
         const float mz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, (float)o.z), lane0));
-#else
-        const float cnt = fmaxf(wave_sum(good ? 1.f : 0.f), 1.f);
-        const float mx = wave_sum(good ? (float)o.x : 0.f) / cnt;
-        const float my = wave_sum(good ? (float)o.y : 0.f) / cnt;
-        const float mz = wave_sum(good ? (float)o.z : 0.f) / cnt;
-#endif
         apex = mk((double)mx, (double)my, (double)mz);
         float e2 = 0.f;
         if (good) {
@@ -677,13 +550,11 @@ DEVI unsigned long long ray_touches_pre_mask(V3 o, V3 d, double dd, const DevPre
     const double pm = fmax(wx * d.x + wy * d.y + wz * d.z, 0.);
     return __builtin_amdgcn_fcmp(ww * dd - pm * pm, (b.R2 + 1e-11 * ww) * dd, 13 /* ULE: !(lhs > rhs) */);
 }
-// Candidates of a per-lane-filtered walk are taken RTC_PRE_BATCH at a time: their records are requested together and their
+// Candidates of a per-lane-filtered walk are taken PRE_BATCH at a time: their records are requested together and their
 // prefilters evaluated back to back before any exact test, so that a pass over many candidates — a secondary pass whose bundle
 // cannot be bounded visits all 101 objects of the reflective north star — is not one scalar-load round trip per object
 // (profiles/r03_exp_unbounded_walks.log: those walks, 0.27 passes per wave, were a third of C4's kernel time).
-#ifndef RTC_PRE_BATCH
-#define RTC_PRE_BATCH 2
-#endif
+constexpr uint32_t PRE_BATCH = 2;
 
 // ---- wave-uniform object loop ------------------------------------------------------------
 // f(j, m, kind, prim) is called for objects j = 0..n-1 in insertion order (World::intersect,
@@ -755,10 +626,16 @@ DEVI int take_min_key(unsigned long long &mask, float key, float &kmin) {
     return sel;
 }
 
+// Shape of the cull walks: a round of the one-level cull tests OS x 64 object spheres, a round of the group level SLOTS x 64
+// group spheres (ordered walks then take the nearest key across the whole round), and K surviving groups are expanded
+// together. Measured on MI355X (ms per frame, 8 frames per launch): OS/SLOTS/K = 1/1/1: C3 0.234, C5 5.07, north star
+// 0.0696; 2/4/2: 0.259 / 5.63 / 0.0724; 4/4/4: 0.274 / 5.99 / 0.0718. Batching the walks buys nothing: these kernels are
+// bound by VALU issue slots, not by the length of the load -> test -> ballot dependency chains, so all three
+// are fixed at 1. The walks keep their batched form: written for width 1 they compile differently (one-level reflective
+// kernels +8..+29 instructions, C4 +0.65 % kernel time; ordered two-level kernels about +100 instructions).
 template <int SRC, bool LANE_FILTER = false, class PP, class F, class SK = NoSkip>
 DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool lane_needs, const Bundle &B, F &&f,
-                          V3 fro = V3{0., 0., 0.}, V3 frd = V3{0., 0., 0.}, SK skip = SK{}, unsigned *nfilt = nullptr,
-                          unsigned *ngrp = nullptr, unsigned *nobj = nullptr) {
+                          V3 fro = V3{0., 0., 0.}, V3 frd = V3{0., 0., 0.}, SK skip = SK{}) {
     constexpr bool ORDERED = !__is_same(SK, NoSkip);
     // per-lane prefilter: the pre-inflated records hold while every origin of the pass is within their limit
     bool pre_ok = false;
@@ -770,13 +647,13 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
     }
     if constexpr (SRC == SRC_CULL) {
         const unsigned long long needs_mask = ballot(lane_needs); // (lane_needs does not change during the walk)
-        // One-level cull (small worlds): up to RTC_OBJ_SLOTS x 64 objects per round, each lane tests one object's sphere of
+        // One-level cull (small worlds): up to OS x 64 objects per round, each lane tests one object's sphere of
         // every slot against the wave's bundle (the slots' loads are in flight together: one load -> test -> ballot
         // dependency chain per round instead of one per 64 objects); the ballot masks are walked in ascending
         // (= insertion) order and the survivors get the exact test, their records fetched by uniform index (scalar cache).
         if (ballot(lane_needs) == 0ull) return;
         const uint32_t lane = threadIdx.x & 63u;
-        constexpr uint32_t OS = RTC_OBJ_SLOTS;
+        constexpr uint32_t OS = 1; // (walk shape: see above)
         for (uint32_t base = 0; base < P.n; base += 64u * OS) {
             unsigned long long masks[OS];
 #pragma unroll
@@ -790,13 +667,13 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
             for (uint32_t sl = 0; sl < OS; ++sl) {
                 unsigned long long mask = masks[sl];
                 if constexpr (LANE_FILTER) {
-                    if (pre_ok) { // RTC_PRE_BATCH candidates at a time (see ray_touches_pre)
+                    if (pre_ok) { // PRE_BATCH candidates at a time (see ray_touches_pre)
                         while (mask) {
-                            uint32_t jx[RTC_PRE_BATCH];
-                            unsigned long long bx[RTC_PRE_BATCH];
+                            uint32_t jx[PRE_BATCH];
+                            unsigned long long bx[PRE_BATCH];
                             uint32_t cnt = 0;
 #pragma unroll
-                            for (uint32_t k = 0; k < RTC_PRE_BATCH; ++k) {
+                            for (uint32_t k = 0; k < PRE_BATCH; ++k) {
                                 jx[k] = k ? jx[0] : base + sl * 64u; // (slots past the last candidate repeat the first: a harmless second look)
                                 if (mask) {
                                     jx[k] = base + sl * 64u + (uint32_t)__builtin_ctzll(mask);
@@ -804,16 +681,15 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
                                     cnt = k + 1u;
                                 }
                             }
-                            DevPre q[RTC_PRE_BATCH]; // all requested before the first is used: one round trip for the batch
+                            DevPre q[PRE_BATCH]; // all requested before the first is used: one round trip for the batch
 #pragma unroll
-                            for (uint32_t k = 0; k < RTC_PRE_BATCH; ++k) q[k] = T.pre[jx[k]];
+                            for (uint32_t k = 0; k < PRE_BATCH; ++k) q[k] = T.pre[jx[k]];
 #pragma unroll
-                            for (uint32_t k = 0; k < RTC_PRE_BATCH; ++k) {
-                                DIAG_FILTER(nfilt);
+                            for (uint32_t k = 0; k < PRE_BATCH; ++k) {
                                 bx[k] = ray_touches_pre_mask(fro, frd, fdd, q[k]) & needs_mask; // (evaluated by every lane: no branch around the loads)
                             }
 #pragma unroll
-                            for (uint32_t k = 0; k < RTC_PRE_BATCH; ++k) {
+                            for (uint32_t k = 0; k < PRE_BATCH; ++k) {
                                 if (k >= cnt || bx[k] == 0ull) continue;
                                 const DevIsect rec = T.isect[jx[k]]; // record and kind requested together, ahead of the callback's branches
                                 const uint32_t kd = T.kind[jx[k]];
@@ -827,7 +703,6 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
                     const uint32_t jj = base + sl * 64u + (uint32_t)__builtin_ctzll(mask);
                     mask &= mask - 1ull;
                     if constexpr (LANE_FILTER) {
-                        DIAG_FILTER(nfilt);
                         if (ballot(lane_needs && ray_touches(fro, frd, T.bound[jj])) == 0ull) continue;
                     }
                     const DevIsect *rec = T.isect + jj;
@@ -838,12 +713,12 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
     } else if constexpr (SRC == SRC_CULL2) {
         // Two-level cull (large worlds) over the Morton-sorted tables. Level 1: group spheres against the wave's
         // bundle, one per lane and slot. Level 2: the 64 objects of surviving groups, one object sphere per lane —
-        // RTC_EXPAND_K groups per round, their bounds loaded and tested together (one dependency chain per round).
+        // K groups per round, their bounds loaded and tested together (one dependency chain per round).
         // Objects are not visited in insertion order here, so the callback receives the insertion index and the
         // tie-break compares it (closer()).
         if (ballot(lane_needs) == 0ull) return;
         const uint32_t lane = threadIdx.x & 63u;
-        constexpr uint32_t SLOTS = RTC_GROUP_SLOTS, K = RTC_EXPAND_K;
+        constexpr uint32_t SLOTS = 1, K = 1; // (walk shape: see above)
         // level 2 for the `cnt` (<= K) groups gidx[0..cnt); returns false when the walk is over (callback said so)
         auto expand = [&](const uint32_t (&gidx)[K], uint32_t cnt) -> bool {
             unsigned long long masks[K];
@@ -853,7 +728,6 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
                 bool cand = false;
                 okey[k] = 0.f;
                 if (k < cnt) {
-                    DIAG_FILTER(ngrp);
                     const uint32_t j = gidx[k] * 64u + lane;
                     if (j < P.n) cand = bundle_touches<ORDERED>(B, T.bound_s[j], &okey[k]);
                 }
@@ -873,9 +747,7 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
                         jj = base + (uint32_t)__builtin_ctzll(mask);
                         mask &= mask - 1ull;
                     }
-                    DIAG_FILTER(nobj);
                     if constexpr (LANE_FILTER) {
-                        DIAG_FILTER(nfilt);
                         if (ballot(lane_needs && (pre_ok ? ray_touches_pre(fro, frd, fdd, T.pre_s[jj]) : ray_touches(fro, frd, T.bound_s[jj]))) == 0ull) continue;
                     }
                     const DevIsect *rec = T.isect_s + jj;
@@ -1120,7 +992,7 @@ DEVI void store_rgba(const unsigned char *src8, unsigned char *out8, uint32_t W,
             const uint32_t r = c / FULL, x = c % FULL;
             const unsigned char *q = src8 + r * SRC_STRIDE + x * 3u;
             const unsigned v = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | 0xff000000u;
-            RTC_CANVAS_STORE(reinterpret_cast<unsigned *>(out8 + ((size_t)(orow0 + r) * W + px0 + x) * 4u), v);
+            __builtin_nontemporal_store(v, reinterpret_cast<unsigned *>(out8 + ((size_t)(orow0 + r) * W + px0 + x) * 4u));
         }
     } else {
         for (uint32_t c = t; c < rows * cols; c += NT) {
@@ -1167,7 +1039,22 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     constexpr uint32_t BLOCK = RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), TILE_W = RTC_TILE_W_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE);
     constexpr bool COMPACT = RTC_COMPACT_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE); // K3: two waves, live rays merged between bounces
     extern __shared__ double lds_raw[];
-    constexpr bool LDS_STACK = RTC_LDS_STACK && REFL && !REFR; // 32-byte frames in LDS (one wave per workgroup)
+    // Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x 4 doubles x
+    // 64 lanes = 10 KB per wave, SoA ([level][component][lane]: lane-consecutive 8-byte accesses, no bank conflicts). The
+    // scratch stack was HBM traffic: C4 wrote 941 MB and fetched 236 MB per frame against 453 MB algorithmic
+    // (profiles/r02_a_c4_pmc.json). The output tile is staged in the same LDS (the stack is dead by then), so a one-wave
+    // workgroup still fits 16 times in a CU's 160 KB.
+    constexpr bool LDS_STACK = REFL && !REFR;
+    // Tile output: each wave stores its own 8x8 part as soon as it is done (frame-stack kernels, whose waves finish far apart:
+    // 0.662 vs 0.690 ms), or a workgroup barrier + cooperative store of the whole tile in full 128-byte lines (flat kernels:
+    // 0.0738 vs 0.0784 ms, the per-wave 192-byte row pieces straddle lines).
+    constexpr bool WAVE_OUTPUT = REFL;
+    // Per-lane prefilter (ray_touches) in front of the shadow pass's exact tests (secondary closest passes always take it).
+    // Two-level cull: a dense world's shadow bundle keeps ~17 candidates per pass, of which each lane's own segment touches
+    // few: 1000 spheres 0.535 -> 0.423 ms, 10 000 spheres 0.560 -> 0.462 ms. Frame-stack kernels: shadow segments from
+    // scattered secondary hits (6.7 exact tests per pass without it), reflective 1080p 0.551 -> 0.536 ms. Not for the flat
+    // one-level cull: at 100 objects (~2 candidates per pass) it costs more than it saves (0.0754 -> 0.0767 ms).
+    constexpr bool SHADOW_LANE_FILTER = SRC == SRC_CULL2 || REFL;
     static_assert(!LDS_STACK || BLOCK == 64 || COMPACT, "the tile is staged over the LDS frame stack: one wave per workgroup, or a barrier first");
     // K3 exchange area: live counts per wave (double-buffered by pass parity) and up to 32 rays in transit
     __shared__ uint32_t k3_cnt[COMPACT ? 4 : 1];
@@ -1212,18 +1099,11 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     }
     const uint32_t reps = wg_reps;
     for (uint32_t rep = 0; rep < reps; ++rep) {
-    // workgroup id -> tile: see RTC_TILE_ORDER (XCD balance beats XCD locality here)
-    uint32_t bid = wg_base + rep * wg_stride;
+    // tile = workgroup id: the hardware deals consecutive ids round-robin over the 8 XCDs, so each XCD gets every 8th tile, an
+    // even share of sky, floor and spheres. Contiguous XCD bands (for L2 locality, of which there is none to gain: a 50 KB scene,
+    // a write-once canvas) measured 0.099 vs 0.073 ms on the north star, 1.07 vs 0.69 ms reflective.
+    const uint32_t bid = wg_base + rep * wg_stride;
     if (!PROBE && bid >= P.total_blocks) break; // (workgroup-uniform)
-#if RTC_TILE_ORDER == 0
-    {
-        const uint32_t nb = gridDim.x, q = nb / 8u, r = nb % 8u, xcd = bid % 8u, k = bid / 8u;
-        bid = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + k;
-    }
-#elif RTC_TILE_ORDER == 2
-    bid = gridDim.x - 1u - bid;
-#endif
-
     uint32_t px = 0, py = 0, ray_index = 0;
     uint32_t view = 0, tbid = bid; // which camera of the launch, and the tile's index inside that view
     bool in_range, traced;
@@ -1242,17 +1122,6 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         traced = in_range && !(P.mode == RTC_MODE_RENDER && (px + 1u >= P.W || py + 1u >= P.H));
     }
 
-#ifdef RTC_STAMPS
-    unsigned long long stamp_t[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-    bool stamp_secondary = false;
-    // per wave: [0] closest passes, [1] closest passes with an unbounded bundle, [2] exact tests in
-    // closest passes, [3] shadow passes, [4] shadow passes unbounded, [5] exact tests in shadow passes
-    // [8] groups expanded in closest passes, [9] in shadow passes, [10] object-level cull survivors (closest), [11] (shadow)
-    unsigned diag_c[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    STAMP(0);
-
     // Tile rows the binning kernel PROVED black for this view (k_bin_tiles, `rows`): no ray is generated, no pass is run, the
     // tile is stored as Canvas::new left it; the primary rays the reference would have cast are still counted (and reported
     // separately, rtc_stats::rays_primary_proven_miss). One-sample renders only.
@@ -1267,8 +1136,8 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     }
 
     // Binned primary pass: this wave's 8x8 tile has a list of the objects its primary rays can touch (k_bin_tiles): lane e
-    // holds entry e. (RTC_BIN_HOIST: the 64 entry slots of a tile always exist, the ones past the
-    // count hold garbage and are masked in the walk.)
+    // holds entry e. Requested where the pass needs it: a request at kernel entry, ahead of the ray generation, measured
+    // slower (north star +3 %, C5 +4 %; profiles/r02_exp_packed_tile_lists.log).
     bool binned = false;
     uint32_t bin_cnt = 0, bin_ent = 0xffffffffu;
     auto tile_lookup = [&]() {
@@ -1278,20 +1147,12 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             const uint32_t itx = (tbid % Pt.grid_x) * (TILE_W / 8u) + wv, ity = (Pt.y0 >> 3) + (tbid / Pt.grid_x) * Pt.band_stride;
             if (itx < Pt.tiles_x && ity < Pt.tiles_y) {
                 const size_t tile = (size_t)(view * Pt.tiles_y + ity) * Pt.tiles_x + itx;
-#if RTC_BIN_HOIST
-                bin_ent = Pt.tile_list[tile * RTC_TILE_LIST_CAP + lane];
-                bin_cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)Pt.tile_cnt[tile]);
-#else
                 bin_cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)Pt.tile_cnt[tile]);
                 if (lane < bin_cnt) bin_ent = Pt.tile_list[tile * RTC_TILE_LIST_CAP + lane];
-#endif
                 binned = bin_cnt <= RTC_TILE_LIST_CAP; // an overflowing list is incomplete: walk instead
             }
         }
     };
-#if RTC_BIN_HOIST
-    if constexpr (IS_CULL(SRC) && !PROBE) tile_lookup();
-#endif
 
     // render_pixel (camera.rs:94-114): one ray, or the 4 fixed sub-samples followed — for the pixels whose
     // samples differ by more than 0.01 from their mean — by `resample_n` more rays (Camera::resample)
@@ -1338,7 +1199,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             const double world_y = Pr.half_height - yoffset;
             const V3 pixel = xpoint(Pr.vinv, mk(world_x, world_y, -1.));
             ro = cam_origin;
-            rd = vnormalize(vsub(pixel, cam_origin));
+            rd = vnormalize_plain(vsub(pixel, cam_origin));
             shared_origin = true;
         }
 
@@ -1410,74 +1271,46 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 pass_again = false;
             }
 
-#ifdef RTC_STAMPS
-            stamp_secondary = !first; // [1] of a secondary pass = the previous pass's lighting + frame push
-#endif
-            STAMP(1); // ray generated
             // ---- World::intersect + get_hit (shape.rs:677-683, 220-232), streaming form ----
             double best = __builtin_inf();
             int hidx = -1, hroot = 0;
             Bundle B{}; // every field defined: an undefined field turns into a value carried around the pass loop
             B.off = true;
-#if !RTC_BIN_HOIST
             if constexpr (IS_CULL(SRC) && !PROBE) {
                 if (shared_origin && first) tile_lookup();
             }
-#endif
             const bool use_bins = binned && shared_origin && first; // (binned is false in the probe and brute-force variants)
             if constexpr (IS_CULL(SRC)) {
                 if (ballot(tracing) != 0ull && !use_bins) {
                     if (shared_origin && first) B = make_bundle<true, false>(tracing, cam_origin, ro, rd, 0.);
                     else B = make_bundle<false, false>(tracing, cam_origin, ro, rd, 0.);
-#ifdef RTC_NO_SECONDARY_CULL
-                    if (!(shared_origin && first)) B.off = true;
-#endif
-#ifdef RTC_NO_PRIMARY_CULL
-                    if (shared_origin && first) B.off = true;
-#endif
                 }
             }
-            STAMP(2); // primary bundle built
-            DIAG(0, ballot(tracing) != 0ull ? 1u : 0u);
-            DIAG(1, (ballot(tracing) != 0ull && B.off) ? 1u : 0u);
-            DIAG(12, (ballot(tracing) != 0ull && !first) ? 1u : 0u); // secondary closest passes
-#ifdef RTC_STAMPS
-            const unsigned diag_c2_before = diag_c[2], diag_c5_before = diag_c[5];
-            const bool diag_secondary = !first;
-#endif
             if (!IS_CULL(SRC) && shared_origin && first) {
                 for_each_object<SRC>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    DIAG(2, 1u);
                     if (tracing) closest_prim(kind, m, pr, rd, j, best, hidx, hroot);
                     return true;
                 });
-#ifndef RTC_NO_LANE_FILTER
-            } else if (IS_CULL(SRC) && ((REFL && !(shared_origin && first)) || RTC_PRIMARY_LANE_FILTER(SRC))) {
+            } else if (IS_CULL(SRC) && REFL && !(shared_origin && first)) {
                 // reflection / refraction rays: incoherent, per-lane prefilter before the exact test
-#ifdef RTC_EXP_SKIP_UNBOUNDED // (elimination build, profiles/r03_exp_unbounded_walks.log: wrong image, never shipped)
-                if (!B.off)
-#endif
                 for_each_object<SRC, true>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    DIAG(2, 1u);
                     if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
                     return true;
-                }, ro, rd, NoSkip{}, DIAG_PTR(6), DIAG_PTR(8), DIAG_PTR(10));
-#endif
+                }, ro, rd);
             } else if (IS_CULL(SRC) && !PROBE && use_bins) {
                 // binned primary pass: the unbounded objects, then the tile's own list (k_bin_tiles) — together
                 // every object this tile's rays can touch
                 // (the view's primary-ray constants come from the binning kernel's table: only the direction is transformed)
                 const auto &Pb = KP(P_arg);
                 const DevPrim *__restrict__ vprim = T.prim + (size_t)view * Pb.n;
-#if RTC_BIN_PRIM
-#define RTC_BINNED_TEST(KIND, M, J) closest_prim(KIND, M, reinterpret_cast<const double *>(vprim + (J)), rd, (int)(J), best, hidx, hroot)
-#else
-#define RTC_BINNED_TEST(KIND, M, J) closest_world(KIND, M, ro, rd, (int)(J), best, hidx, hroot)
-#endif
+                // closest_prim: the camera origin in object space and the sphere's c from that table, 24 VALU instructions
+                // fewer per sphere test than transforming the origin again (closest_world)
+                auto binned_test = [&](uint32_t kind, const double *m, uint32_t j) {
+                    closest_prim(kind, m, reinterpret_cast<const double *>(vprim + j), rd, (int)j, best, hidx, hroot);
+                };
                 for (uint32_t k = 0; k < Pb.n_unb; ++k) {
-                    DIAG(2, 1u);
                     const uint32_t jo = T.orig_s[k];
-                    if (tracing) RTC_BINNED_TEST(T.kind_s[k], T.isect_s[k].m, jo);
+                    if (tracing) binned_test(T.kind_s[k], T.isect_s[k].m, jo);
                 }
                 // the tile's list, nearest first: lane e holds entry e and the lower bound of the distance from the camera to
                 // its (inflated) bounding sphere — every intersection of that object has t >= key for these unit-direction
@@ -1493,8 +1326,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         if (ballot(tracing && !(best < (double)kmin)) == 0ull) break;
                         if (ent == e) ent = 0xffffffffu;
                         const uint32_t j = e & 0xffffu;
-                        DIAG(2, 1u);
-                        if (tracing) RTC_BINNED_TEST(T.kind[j], T.isect[j].m, j);
+                        if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
                     }
                 } else { // more than 65 536 objects: plain indices, keys from the bounds
                     uint32_t my_j = 0u;
@@ -1509,32 +1341,22 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         const int sel = take_min_key(lmask, my_key, kmin);
                         if (ballot(tracing && !(best < (double)kmin)) == 0ull) break;
                         const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)my_j, sel);
-                        DIAG(2, 1u);
-                        if (tracing) RTC_BINNED_TEST(T.kind[j], T.isect[j].m, j);
+                        if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
                     }
                 }
             } else if (SRC == SRC_CULL2 && !PROBE && shared_origin && first) {
                 // primary rays of a large world: start at the apex, unit direction -> ordered walk with early stop
                 for_each_object<SRC, false>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    DIAG(2, 1u);
                     if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
                     return true;
-                }, ro, rd, [&](float key) { return ballot(tracing && !(best < (double)key)) == 0ull; }, nullptr, DIAG_PTR(8), DIAG_PTR(10));
+                }, ro, rd, [&](float key) { return ballot(tracing && !(best < (double)key)) == 0ull; });
             } else {
                 for_each_object<SRC>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    DIAG(2, 1u);
                     if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
                     return true;
-                }, ro, rd, NoSkip{}, nullptr, DIAG_PTR(8), DIAG_PTR(10));
+                }, ro, rd);
             }
             const bool hit = tracing && hidx >= 0;
-#ifdef RTC_STAMPS
-            if (stamp_secondary && B.off) { // [8] (unused otherwise): closest-hit walks of secondary passes WITHOUT a bounded bundle (also part of [3])
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                stamp_t[8] += __builtin_amdgcn_s_memtime() - stamp_last;
-            }
-#endif
-            STAMP(3); // closest hit found
             const auto &Ph = KP(P_arg); // shading view: light
             const V3 lightp = mk(Ph.light_pos[0], Ph.light_pos[1], Ph.light_pos[2]);
 
@@ -1564,7 +1386,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     else ln = mk(0., 0., lp.z);
                 }
                 if (kind == RTC_PLANE) normal = mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]);
-                else normal = vnormalize(xvector3(S->nt, ln));
+                else normal = vnormalize_plain(xvector3(S->nt, ln));
                 inside = vdot(normal, eyev) < 0.0;
                 if (inside) normal = vneg(normal);
                 over = vadd(point, vmul(normal, RTC_EPSILON));
@@ -1649,11 +1471,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             }
 
             // ---- is_shadowed (shape.rs:712-727): any-hit with early exit ----------------------
-            STAMP(4); // hit record + shadow ray
             bool sh_pending = hit, shadowed = false;
-#ifdef RTC_EXP_SKIP_SECONDARY_SHADOW // (elimination build, as above)
-            if (!first) sh_pending = false;
-#endif
             c_shadow += popc64(ballot(hit));
             Bundle Bs{};
             Bs.off = true;
@@ -1690,7 +1508,6 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     }
                     if (listed) {
                         for (uint32_t k = 0; k < Pl.n_unb && ballot(sh_pending) != 0ull; ++k) { // unbounded objects: never listed
-                            DIAG(5, 1u);
                             if (sh_pending && occludes_world(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                         }
                         const uint32_t ci = lane >> 4, ei = lane & 15u;
@@ -1714,12 +1531,10 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                             unsigned long long &word = done[(j >> 6) & 3u];
                             if (word & bit) continue;
                             word |= bit;
-                            DIAG_FILTER(DIAG_PTR(7));
                             bool t;
                             if (pre_ok) { const DevPre q = T.pre[j]; t = ray_touches_pre(over, sdir, sdd, q); }
                             else t = ray_touches(over, sdir, T.bound[j]);
                             if (ballot(sh_pending & t) == 0ull) continue;
-                            DIAG(5, 1u);
                             const DevIsect rec = T.isect[j]; // record and kind requested together
                             const uint32_t kd = T.kind[j];
                             if (sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
@@ -1730,13 +1545,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             if constexpr (IS_CULL(SRC)) {
                 // the segment over_point -> light, walked from the light: apex = light (shared)
                 if (ballot(hit) != 0ull && !listed) Bs = make_bundle<true, true>(hit, lightp, lightp, vneg(sdir), sdist);
-#ifdef RTC_NO_SHADOW_CULL
-                Bs.off = true;
-#endif
             }
-            STAMP(5); // shadow bundle built
-            DIAG(3, ballot(hit) != 0ull ? 1u : 0u);
-            DIAG(4, (ballot(hit) != 0ull && Bs.off) ? 1u : 0u);
             // Light-space shadow lists (two-level worlds): instead of walking every group sphere, filter the lists of the
             // direction cells (around the light) this wave's segments fall in with the wave's own shadow bundle.
             if constexpr (SRC == SRC_CULL2) {
@@ -1747,7 +1556,6 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     listed = ballot(hit && ccnt > Pl.light_cap) == 0ull;       // a cell whose list overflowed is incomplete: walk instead
                     if (listed) {
                         for (uint32_t k = 0; k < Pl.n_unb && ballot(sh_pending) != 0ull; ++k) { // unbounded objects: never listed
-                            DIAG(5, 1u);
                             if (sh_pending && occludes_world(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                         }
                         bool pre_ok; // pre-inflated prefilter records hold while every origin is within their limit (DevPre)
@@ -1768,15 +1576,13 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                                 uint32_t idx = 0u;
                                 bool cand = false;
                                 if (e < nl) { idx = ll[e]; cand = bundle_touches(Bs, T.bound[idx]); }
-                                DIAG_FILTER(DIAG_PTR(9));
                                 unsigned long long mask = ballot(cand);
-                                while (mask && ballot(sh_pending) != 0ull) { // survivors two at a time (RTC_PRE_BATCH, as for_each_object)
+                                while (mask && ballot(sh_pending) != 0ull) { // survivors two at a time (PRE_BATCH, as for_each_object)
                                     const uint32_t j0 = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)__builtin_ctzll(mask));
                                     mask &= mask - 1ull;
                                     uint32_t j1 = j0;
                                     const bool two = mask != 0ull;
                                     if (two) { j1 = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)__builtin_ctzll(mask)); mask &= mask - 1ull; }
-                                    DIAG_FILTER(DIAG_PTR(11));
                                     unsigned long long b0, b1;
                                     if (pre_ok) {
                                         const DevPre q0 = T.pre[j0], q1 = T.pre[j1];
@@ -1788,13 +1594,11 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                                         b1 = two ? ballot(sh_pending && ray_touches(over, sdir, T.bound[j1])) : 0ull;
                                     }
                                     if (b0 != 0ull) {
-                                        DIAG(5, 1u);
                                         const DevIsect rec = T.isect[j0];
                                         const uint32_t kd = T.kind[j0];
                                         if (sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                                     }
                                     if (b1 != 0ull && ballot(sh_pending) != 0ull) {
-                                        DIAG(5, 1u);
                                         const DevIsect rec = T.isect[j1];
                                         const uint32_t kd = T.kind[j1];
                                         if (sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
@@ -1806,22 +1610,13 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 }
             }
             if (!listed)
-            for_each_object<SRC, RTC_SHADOW_LANE_FILTER(SRC, REFL)>(P, T, L, sh_pending, Bs, [&](int j, auto m, uint32_t kind, auto pr) {
-                DIAG(5, 1u);
+            for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, sh_pending, Bs, [&](int j, auto m, uint32_t kind, auto pr) {
                 if (sh_pending) {
                     if (occludes_world(kind, m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                 }
                 return ballot(sh_pending) != 0ull;
-            }, over, sdir, NoSkip{}, DIAG_PTR(7), DIAG_PTR(9), DIAG_PTR(11));
+            }, over, sdir);
 
-            STAMP(6); // shadow resolved
-#ifdef RTC_STAMPS
-            if (diag_secondary) { // [13] exact tests in secondary closest passes, [14] their shadow passes, [15] exact tests in those
-                diag_c[13] += diag_c[2] - diag_c2_before;
-                diag_c[14] += ballot(hit) != 0ull ? 1u : 0u;
-                diag_c[15] += diag_c[5] - diag_c5_before;
-            }
-#endif
             // keep the material / pattern loads of the lighting stage BELOW the shadow loop: hoisted
             // above it they stay live through the loop and cost a wave per SIMD in occupancy
             asm volatile("" ::: "memory");
@@ -2041,10 +1836,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         q[2] = scale255(result.z);
                     }
                 }
-#ifdef RTC_DIAG_NO_STORE
-                if (Po.W == 0xffffffffu) // never true: keeps the code, skips the stores (diagnosis builds only)
-#endif
-                if constexpr (RTC_WAVE_OUTPUT(REFL)) {
+                // Canvas stores are non-temporal (written once, never read by the kernel): north star -2.3 %, C3 -4.2 %,
+                // C5 -1.5 % (profiles/r02_exp_nt_stores.log).
+                if constexpr (WAVE_OUTPUT) {
                 // Each wave stores its own 8x8 part of the tile (no workgroup barrier: a wave that is
                 // done retires without waiting for the slowest of its three neighbours). Its LDS
                 // region is written and read by this wave only; LDS operations of one wave execute
@@ -2067,7 +1861,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         const uint32_t r = c / 12u, k = c % 12u;
                         const d2 v = *reinterpret_cast<const d2 *>(src + r * (TILE_W * 3u) + k * 2u);
                         char *dst = reinterpret_cast<char *>(Po.out) + (size_t)(orow0 + r) * row_bytes + (size_t)px0 * 24u + k * 16u;
-                        RTC_CANVAS_STORE(reinterpret_cast<d2 *>(dst), v);
+                        __builtin_nontemporal_store(v, reinterpret_cast<d2 *>(dst));
                     }
                 } else {
                     for (uint32_t c = lane; c < rows * cols * 3u; c += 64u) {
@@ -2087,7 +1881,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         for (uint32_t c = lane; c < rows * 3u; c += 64u) {
                             const uint32_t r = c / 3u, k = c % 3u;
                             const u2 v = *reinterpret_cast<const u2 *>(src8 + r * (TILE_W * 3u) + k * 8u);
-                            RTC_CANVAS_STORE(reinterpret_cast<u2 *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * 8u), v);
+                            __builtin_nontemporal_store(v, reinterpret_cast<u2 *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * 8u));
                         }
                     } else {
                         for (uint32_t c = lane; c < rows * cols * 3u; c += 64u) {
@@ -2112,7 +1906,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         const uint32_t r = c / (TILE_W * 3u / 2u), k = c % (TILE_W * 3u / 2u);
                         const d2 v = *reinterpret_cast<const d2 *>(stage_f64 + r * (TILE_W * 3u) + k * 2u);
                         char *dst = reinterpret_cast<char *>(Po.out) + (size_t)(orow0 + r) * row_bytes + (size_t)px0 * 24u + k * 16u;
-                        RTC_CANVAS_STORE(reinterpret_cast<d2 *>(dst), v);
+                        __builtin_nontemporal_store(v, reinterpret_cast<d2 *>(dst));
                     }
                 } else {
                     for (uint32_t c = threadIdx.x; c < rows * cols * 3u; c += BLOCK) {
@@ -2132,7 +1926,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         for (uint32_t c = threadIdx.x; c < rows * (TILE_W * 3u / PIECE); c += BLOCK) {
                             const uint32_t r = c / (TILE_W * 3u / PIECE), k = c % (TILE_W * 3u / PIECE);
                             const piece_t v = *reinterpret_cast<const piece_t *>(stage_u8 + r * (TILE_W * 3u) + k * PIECE);
-                            RTC_CANVAS_STORE(reinterpret_cast<piece_t *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * PIECE), v);
+                            __builtin_nontemporal_store(v, reinterpret_cast<piece_t *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * PIECE));
                         }
                     } else {
                         for (uint32_t c = threadIdx.x; c < rows * cols * 3u; c += BLOCK) {
@@ -2149,16 +1943,11 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     if (rep + 1u < reps) {
         // the next tile is staged over the same LDS: the workgroup's cooperative store must have read it (a wave's own LDS
         // operations are in order, so the per-wave output form needs nothing)
-        if constexpr (!PROBE && !RTC_WAVE_OUTPUT(REFL)) __syncthreads();
+        if constexpr (!PROBE && !WAVE_OUTPUT) __syncthreads();
     }
     } // rep
-    STAMP(7); // shaded, stored
     const auto &Pc = KP(P_arg);
-#ifdef RTC_DIAG_NO_COUNTERS
-    if (Pc.counters && Pc.W == 0xffffffffu) {
-#else
     if (Pc.counters) {
-#endif
         if (lane == 0) { // (rtc_stats::pixels is counted by the host, render_launch)
             unsigned long long *slot = Pc.counters + (size_t)((blockIdx.x * (BLOCK / 64u) + wave) % CNT_SLOTS) * CNT_N;
             if (c_primary) atomicAdd(slot + CNT_PRIMARY, (unsigned long long)c_primary);
@@ -2167,11 +1956,6 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             if (c_refract) atomicAdd(slot + CNT_REFRACT, (unsigned long long)c_refract);
             if (c_resample) atomicAdd(slot + CNT_RESAMPLE, (unsigned long long)c_resample);
             if (c_sky) atomicAdd(slot + CNT_SKY, (unsigned long long)c_sky);
-#ifdef RTC_STAMPS
-            for (int i = 0; i < 8; ++i) atomicAdd(slot + CNT_STAMP0 + i, stamp_t[i]);
-            for (int i = 0; i < 8; ++i) atomicAdd(slot + CNT_STAMP2 + i, stamp_t[8 + i]);
-            for (int i = 0; i < 16; ++i) atomicAdd(slot + CNT_DIAG0 + i, (unsigned long long)diag_c[i]);
-#endif
         }
     }
 }
@@ -2570,7 +2354,7 @@ __global__ void __launch_bounds__(256) k_canvas_to_rgba8(const double *__restric
     for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
         const double r = rgb[i * 3u], gr = rgb[i * 3u + 1u], b = rgb[i * 3u + 2u];
         const unsigned v = (unsigned)gamma_byte(g, r) | ((unsigned)gamma_byte(g, gr) << 8) | ((unsigned)gamma_byte(g, b) << 16) | 0xff000000u;
-        if (aligned4) RTC_CANVAS_STORE(reinterpret_cast<unsigned *>(out + i * 4u), v);
+        if (aligned4) __builtin_nontemporal_store(v, reinterpret_cast<unsigned *>(out + i * 4u));
         else {
             out[i * 4u] = (unsigned char)v;
             out[i * 4u + 1u] = (unsigned char)(v >> 8);

@@ -239,7 +239,7 @@ def test_forced_one_level_cull_beyond_256_objects(rtc, scenes):
 
 def test_shared_divisor_normalize_is_bit_identical(gpu):
     """Vector::normalize (vec.rs:65-76) with the three divisions sharing the divisor-only part of hipcc's f64 division
-    expansion (rtc_kernels.hip vnormalize_shared, behind RTC_SHARED_NORMALIZE; an experiment) must equal three IEEE divisions
+    expansion (rtc_kernels.hip vnormalize_shared, which the binning kernel uses) must equal three IEEE divisions
     bit for bit — and both must equal the host: ordinary directions, zeros and signed zeros, tiny and huge components (the
     guard's fall-back), denormals, infinities."""
     rng = np.random.default_rng(11)
