@@ -267,7 +267,8 @@ rtc_status  rtc_scene_load_yaml_file(const char *path, rtc_shape **shapes_out, u
  * shape-level color / pattern override; patterns "checks" / "stripes" / "grid"; lights[1] only; camera screenwidth /
  * screenheight / samples as Lua integers — and becomes one JOB: a world, a camera, the output file's name. The caller renders
  * the jobs in order (one rtc_render* launch each: an AddFrame loop is the one-camera-per-launch sequence a pipelined
- * context overlaps); encoding GIF / PNG / JPEG files is the `image` crate's business in the reference and nobody's here.
+ * context overlaps). The library writes PNG / PPM stills (rtc_canvas_write_png8, rtc_canvas_write_ppm_rgb8) and the
+ * animation's GIF (rtc_gif_format, rtc_gif_writer_*, rtc_lua_program_render_gif); JPEG is not rebuilt.
  * math.random is Lua 5.3's on POSIX (glibc random(), restated), so `math.randomseed(13)` worlds are reproducible.
  * A script runs under a step budget (`step_limit` statements / loop iterations / calls, 0 = 100 000 000), may nest 200 calls
  * (the interpreter recurses on the caller's stack: up to about 2 MB of it at that depth) and cannot touch
@@ -336,10 +337,47 @@ rtc_status  rtc_gamma_thresholds(float gamma, double *out);
  * extension): an 8-bit PNG of `pixels` = height*width*channels bytes, channels = 4 (to_imgbuf's RGBA, colour type 6) or 3
  * (the device's Color::scale frame, colour type 2; a decoder supplies alpha 255, which is what to_imgbuf stores). PNG is
  * lossless: decoding gives back exactly these pixels, as it does for the reference's file. No compressor is built in —
- * the zlib stream uses stored blocks, so the file is a little larger than the pixels. JPEG and GIF (lossy / palette
- * quantising third-party codecs in the reference) are not rebuilt. format: bytes needed; writes at most cap. Host. */
+ * the zlib stream uses stored blocks, so the file is a little larger than the pixels. JPEG (a lossy third-party codec in
+ * the reference) is not rebuilt; GIF is below. format: bytes needed; writes at most cap. Host. */
 rtc_status  rtc_canvas_write_png8(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels);
 size_t      rtc_canvas_format_png8(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint8_t *buf, size_t cap);
+/* Animated GIF: what StartAnimation(file) / enc:AddFrame(world, camera) write in the reference (lua.rs:17-45,75-79,
+ * Canvas::frame_to_file canvas.rs:53-59, the `image` crate's GIF encoder with a 75 ms delay per frame).
+ * LAYOUT PARITY UNPINNED: no copy of the reference's encoder is at hand; the layout below is what it is understood to emit,
+ * and the quantiser is this project's own (the reference uses NeuQuant, which learns one pixel at a time).
+ *   File:  "GIF89a"; logical screen = the first frame's width x height; no global colour table; no loop extension;
+ *          then one record per frame; trailer 0x3B.
+ *   Record: graphic control extension (disposal 0, no transparency, delay 7 cs = Delay 75 ms / 10, truncated); image
+ *          descriptor at (0,0) covering the frame, not interlaced, 256-entry local colour table; the table; LZW minimum
+ *          code size 8; the code stream in sub-blocks of at most 255 bytes; a 0-length block.
+ * Quantiser, on the frame's 8-bit RGB (Color::scale bytes, as rtc_render_rgb8 delivers them), deterministic:
+ *   Exact: a frame of at most 256 distinct colours gets those colours in ascending (r<<16)|(g<<8)|b order, padded with
+ *          black; lossless.
+ *   Median cut otherwise, over the 32768 bins (r>>3, g>>3, b>>3), each with its pixel count and sums of the 8-bit r, g, b.
+ *          A box is always shrunk to the bounding box of its occupied bins; the first is that of all of them. While there
+ *          are fewer than 256 boxes: among the boxes holding more than one occupied bin take the one with the most pixels
+ *          (ties: the box created first; none left: stop); split it along its longest axis in bins (ties: r, then g, then
+ *          b) after the first bin plane p at which 2 * (pixels in planes lo..p) >= the box's pixels, but at most at plane
+ *          hi-1; the lower part keeps the box's number, the upper part is the next box. Entry i = box i's mean over its
+ *          pixels, per channel (2*sum + n) / (2*n) in integers; entries past the last box are black.
+ *   Index: every pixel gets the argmin over all 256 entries of dr*dr + dg*dg + db*db, ties to the lowest index (in the exact
+ *          case that is the rank of its colour).
+ * Segmented LZW: the index stream is cut into segments of RTC_GIF_SEGMENT indices (the last may be shorter), each
+ * encoded on its own with a fresh dictionary — the stream is a clear code (256), segment 0's codes, a clear code, segment
+ * 1's codes, ..., the last segment's codes, EOI (257): each segment's terminator is written at that segment's final code
+ * width. Codes start at 9 bits; after a code is emitted the dictionary takes the next entry and the width grows by one
+ * when the next free code exceeds 2^width (at most 12 bits); when the dictionary holds 4096 codes, a clear code is emitted
+ * instead and the dictionary restarts at 9 bits. Segments are packed LSB-first into one stream. A segment of 4096
+ * indices keeps a whole frame's worth of encoders running at once (one wave each on the device, 507 for 1920x1080) and
+ * is long enough for noise to fill the dictionary inside it (3838 codes).
+ * rtc_gif_quantize: palette (768 bytes, 256 RGB entries) and one index per pixel; *used (may be NULL) = the entries that
+ * are distinct colours or boxes. rtc_gif_lzw: the packed code stream of `indices` (bytes needed; writes at most cap).
+ * rtc_gif_format: the whole file of `nframes` frames of width x height (rgb8, one after the other) — bytes needed, 0 for
+ * a size of 0 or above 65535; writes at most cap. Host. */
+enum { RTC_GIF_SEGMENT = 4096, RTC_GIF_DELAY_CS = 7 };
+rtc_status  rtc_gif_quantize(const uint8_t *rgb8, uint32_t width, uint32_t height, uint8_t *palette, uint8_t *indices, uint32_t *used);
+size_t      rtc_gif_lzw(const uint8_t *indices, size_t n, uint8_t *buf, size_t cap);
+size_t      rtc_gif_format(const uint8_t *frames, uint32_t nframes, uint32_t width, uint32_t height, uint8_t *buf, size_t cap);
 
 /* ==== [device] the hot path on one MI355X ========================================== */
 
@@ -439,6 +477,34 @@ rtc_status  rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint
 typedef int (*rtc_lua_frame_fn)(void *user, const rtc_lua_job *job, uint32_t job_index, const uint8_t *rgb8);
 rtc_status  rtc_lua_program_render(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
                                    rtc_lua_frame_fn fn, void *user, rtc_stats *stats);
+/* The GIF writer on the device: the same bytes as rtc_gif_format, frame by frame, with quantiser and LZW on the GPU
+ * (csrc/rtc_gif.hip) — only the compressed record of a frame crosses PCIe. A writer is bound to a context and owns its
+ * scratch (about 3 MB + 4 B per pixel, grow-only).
+ *   append_device: `d_rgb8` = height*width*3 bytes in device memory (rtc_render_rows' d_rgb8 rows), encoded on the
+ *     context's stream in order with what the caller put there before (after launches of a pipelined context:
+ *     rtc_context_fence first); blocks until the record is on the host.
+ *   render: renders `cam` through the rows path (8-bit rows only) into the writer's scratch and appends that frame; the
+ *     frame never leaves the device.
+ *   The first frame fixes the logical screen; a later frame of another size, or a size above 65535, is RTC_ERR_ARG.
+ *   bytes: the file so far with its trailer (bytes needed; writes at most cap; 0 before the first frame); write: the same
+ *     to `path`. [device] */
+typedef struct rtc_gif_writer rtc_gif_writer;
+rtc_status  rtc_gif_writer_create(rtc_context *ctx, rtc_gif_writer **out);
+rtc_status  rtc_gif_writer_append_device(rtc_gif_writer *g, const void *d_rgb8, uint32_t width, uint32_t height);
+rtc_status  rtc_gif_writer_render(rtc_gif_writer *g, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags);
+size_t      rtc_gif_writer_bytes(const rtc_gif_writer *g, uint8_t *buf, size_t cap);
+rtc_status  rtc_gif_writer_write(const rtc_gif_writer *g, const char *path);
+void        rtc_gif_writer_destroy(rtc_gif_writer *g);
+/* rtc_lua_program_render with the animations encoded on the device: the same launches, lanes and job order, but for an
+ * AddFrame job the frame is quantised and LZW-coded on the GPU behind its render (on the same lane) and `fn` receives that
+ * frame's GIF record (extension + descriptor + table + sub-blocks, nbytes of them) instead of the 8-bit rows; a Render
+ * job is delivered as by rtc_lua_program_render (rows, nbytes = vsize*hsize*3). A file is the 13-byte header of its first
+ * frame, its records in order, 0x3B. The record's size is known only on the device: its length (8 bytes) is copied
+ * behind each frame, and when the frame is delivered exactly that many bytes follow on a copy stream of this call — no
+ * worst-case buffer crosses PCIe, and the lanes keep rendering meanwhile. [device] */
+typedef int (*rtc_lua_gif_fn)(void *user, const rtc_lua_job *job, uint32_t job_index, const uint8_t *bytes, size_t nbytes);
+rtc_status  rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
+                                       rtc_lua_gif_fn fn, void *user, rtc_stats *stats);
 /* Page-locked host memory for canvases handed to rtc_render: a canvas from rtc_host_alloc is
  * filled by one DMA at link speed, ordinary (pageable) memory goes through the runtime's bounce
  * buffers and is several times slower. What the reference would use for Canvas.pixels

@@ -17,7 +17,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, PATTERNS, STATUS_NAMES, declare)
 
@@ -353,6 +353,70 @@ class LuaProgram:
         self.render(ctx, on_frame=on_frame, mode=mode, flags=flags)
         return paths
 
+    def render_gif(self, ctx: "Context", on_frame, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
+        """rtc_lua_program_render_gif: every job rendered as by render(); on_frame(job_index, data, outfile, kind) gets an
+        AddFrame job's GIF record (bytes, quantised and LZW-coded on the GPU) or a Render job's (vsize, hsize, 3) uint8 frame.
+        A true return value stops the run."""
+        raised = []
+
+        def cb(_user, jp, index, data, nbytes):
+            try:
+                j = jp.contents
+                outfile = (j.outfile or b"").decode(errors="replace")
+                if j.kind == 1:
+                    payload = C.string_at(data, nbytes)
+                else:
+                    payload = np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3))
+                return 1 if on_frame(index, payload, outfile, "AddFrame" if j.kind == 1 else "Render") else 0
+            except BaseException as e:  # never unwind through the C frames
+                raised.append(e)
+                return 1
+
+        st = RtcStats()
+        fn = LUA_GIF_FN(cb)
+        rc = lib().rtc_lua_program_render_gif(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
+        if raised:
+            raise raised[0]
+        _check(rc, "rtc_lua_program_render_gif")
+        return _stats_dict(st, True) if with_stats else None
+
+    def render_animations(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0, on_frame=None) -> list:
+        """render_lua with the reference's files: one out_dir/<basename>.gif per StartAnimation call (frames encoded on the
+        GPU, rtc_lua_program_render_gif), Render stills written exactly as render_to_files writes them. `on_frame` (optional,
+        same arguments as render_gif's) sees every job first; a true return value stops the run (files of the frames so
+        far are still written). Returns the paths: stills in job order, then the animations in StartAnimation order."""
+        out = Path(out_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        paths, anims = [], {}
+
+        def cb(index, data, outfile, kind):
+            stop = bool(on_frame(index, data, outfile, kind)) if on_frame is not None else False
+            name = Path(outfile).name or f"job{index}"
+            if kind == "AddFrame":
+                j = self.job(index)
+                a = anims.setdefault(j.animation, {"name": name, "size": (j.camera.hsize, j.camera.vsize), "records": []})
+                if (j.camera.hsize, j.camera.vsize) != a["size"]:
+                    raise RtcError(4, "render_animations", f"frame {j.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
+                a["records"].append(data)
+            else:
+                target = out / name if name.lower().endswith((".png", ".ppm")) else out / (name + ".png")
+                if target.suffix.lower() == ".ppm":
+                    write_ppm_rgb8(target, data)
+                else:
+                    write_png(target, data)
+                paths.append(target)
+            return stop
+
+        try:
+            self.render_gif(ctx, cb, mode=mode, flags=flags)
+        finally:
+            for k in sorted(anims):
+                a = anims[k]
+                target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
+                target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
+                paths.append(target)
+        return paths
+
     def close(self):
         if getattr(self, "_h", None):
             lib().rtc_lua_program_free(self._h)
@@ -460,6 +524,63 @@ def write_png(path, pixels: np.ndarray) -> None:
     if a.ndim != 3 or a.shape[2] not in (3, 4):
         raise ValueError("pixels must be (H, W, 3) or (H, W, 4) uint8")
     _check(lib().rtc_canvas_write_png8(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2]), "rtc_canvas_write_png8")
+
+
+def gif_file_header(width: int, height: int) -> bytes:
+    """The 13 bytes in front of a GIF's first frame (include/rtc.h): GIF89a, the logical screen, no global table."""
+    if not (0 < width <= 65535 and 0 < height <= 65535):
+        raise RtcError(4, "gif_file_header", f"{width}x{height}")
+    return b"GIF89a" + int(width).to_bytes(2, "little") + int(height).to_bytes(2, "little") + b"\0\0\0"
+
+
+def _frames_u8(frames) -> np.ndarray:
+    fs = [np.asarray(f) for f in frames]
+    if not fs:
+        raise ValueError("no frames")
+    for f in fs:
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+            raise ValueError("frames must be (H, W, 3) uint8")
+        if f.shape != fs[0].shape:
+            raise RtcError(4, "gif_encode", f"frame of {f.shape[1]}x{f.shape[0]} in a {fs[0].shape[1]}x{fs[0].shape[0]} animation")
+    return np.ascontiguousarray(np.stack(fs))
+
+
+def gif_quantize(frame: np.ndarray):
+    """The GIF quantiser of include/rtc.h on the host (rtc_gif_quantize): (palette (256, 3) uint8, indices (H, W) uint8,
+    used entries)."""
+    a = np.ascontiguousarray(frame, dtype=np.uint8)
+    h, w = a.shape[0], a.shape[1]
+    P8 = C.POINTER(C.c_uint8)
+    pal = np.empty((256, 3), dtype=np.uint8)
+    idx = np.empty((h, w), dtype=np.uint8)
+    used = C.c_uint32()
+    _check(lib().rtc_gif_quantize(a.ctypes.data_as(P8), w, h, pal.ctypes.data_as(P8), idx.ctypes.data_as(P8), C.byref(used)), "rtc_gif_quantize")
+    return pal, idx, used.value
+
+
+def gif_lzw(indices: np.ndarray) -> bytes:
+    """The segmented LZW code stream of include/rtc.h for an index stream (rtc_gif_lzw), before sub-blocking."""
+    a = np.ascontiguousarray(indices, dtype=np.uint8).ravel()
+    P8 = C.POINTER(C.c_uint8)
+    need = lib().rtc_gif_lzw(a.ctypes.data_as(P8), a.size, None, 0)
+    buf = np.empty(need, dtype=np.uint8)
+    lib().rtc_gif_lzw(a.ctypes.data_as(P8), a.size, buf.ctypes.data_as(P8), need)
+    return buf.tobytes()
+
+
+def gif_encode(frames) -> bytes:
+    """An animated GIF of equal-sized (H, W, 3) uint8 frames, encoded on the host (rtc_gif_format): what
+    StartAnimation / AddFrame write, by the rules of include/rtc.h. Frames of different sizes, or a side above 65535, raise
+    RtcError (RTC_ERR_ARG)."""
+    a = _frames_u8(frames)
+    n, h, w = a.shape[0], a.shape[1], a.shape[2]
+    P8 = C.POINTER(C.c_uint8)
+    need = lib().rtc_gif_format(a.ctypes.data_as(P8), n, w, h, None, 0)
+    if need == 0:
+        raise RtcError(4, "rtc_gif_format", f"{w}x{h}")
+    buf = np.empty(need, dtype=np.uint8)
+    lib().rtc_gif_format(a.ctypes.data_as(P8), n, w, h, buf.ctypes.data_as(P8), need)
+    return buf.tobytes()
 
 
 def write_ppm(path, rgb: np.ndarray) -> None:
@@ -726,6 +847,47 @@ class DeviceWorld:
         P = C.POINTER(C.c_double)
         _check(lib().rtc_color_at(self.ctx._h, self._h, r.ctypes.data_as(P), n, remaining, flags, rgb.ctypes.data_as(P), hits), "rtc_color_at")
         return (rgb, hits) if want_hits else rgb
+
+
+class GifWriter:
+    """An animated GIF encoded on the GPU (rtc_gif_writer): frames already in device memory or rendered straight into the
+    writer; only each frame's compressed record crosses PCIe. The bytes equal gif_encode's for the same frames."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(lib().rtc_gif_writer_create(ctx._h, C.byref(self._h)), "rtc_gif_writer_create")
+        ctx._worlds.append(weakref.ref(self))   # closed with the context
+
+    def append_device(self, d_ptr: int, width: int, height: int) -> None:
+        """Append the height x width x 3 uint8 frame at device address d_ptr (enqueued on the context's stream)."""
+        _check(lib().rtc_gif_writer_append_device(self._h, C.c_void_p(d_ptr), width, height), "rtc_gif_writer_append_device")
+
+    def render(self, world: "DeviceWorld", cam: RtcCamera, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+        """Render `cam` on the device and append the frame without copying it to the host."""
+        _check(lib().rtc_gif_writer_render(self._h, world._h, C.byref(cam), mode, flags), "rtc_gif_writer_render")
+
+    def bytes(self) -> bytes:
+        need = lib().rtc_gif_writer_bytes(self._h, None, 0)
+        if need == 0:
+            return b""
+        buf = np.empty(need, dtype=np.uint8)
+        lib().rtc_gif_writer_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
+        return buf.tobytes()
+
+    def write(self, path) -> None:
+        _check(lib().rtc_gif_writer_write(self._h, str(path).encode()), "rtc_gif_writer_write")
+
+    def close(self):
+        if self._h:
+            lib().rtc_gif_writer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def host_canvas_rgb8(vsize: int, hsize: int) -> np.ndarray:

@@ -63,6 +63,8 @@ class RtcLuaJob(C.Structure):
 
 
 LUA_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.POINTER(C.c_uint8))
+LUA_GIF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
+GIF_SEGMENT, GIF_DELAY_CS = 4096, 7
 
 SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute force, object table staged in LDS (one tile)",
                 2: "brute force, object table staged in LDS tiles", 3: "one-level per-wave cull", 4: "two-level per-wave cull"}
@@ -109,6 +111,16 @@ PROTOTYPES = {
     "rtc_lua_program_output": (C.c_char_p, [C.c_void_p]),
     "rtc_lua_program_free": (None, [C.c_void_p]),
     "rtc_lua_program_render": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, LUA_FRAME_FN, C.c_void_p, C.POINTER(RtcStats)]),
+    "rtc_lua_program_render_gif": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, LUA_GIF_FN, C.c_void_p, C.POINTER(RtcStats)]),
+    "rtc_gif_quantize": (C.c_int32, [C.POINTER(C.c_uint8), U32, U32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(U32)]),
+    "rtc_gif_lzw": (C.c_size_t, [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_gif_format": (C.c_size_t, [C.POINTER(C.c_uint8), U32, U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_gif_writer_create": (C.c_int32, [VP, C.POINTER(VP)]),
+    "rtc_gif_writer_append_device": (C.c_int32, [VP, VP, U32, U32]),
+    "rtc_gif_writer_render": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32]),
+    "rtc_gif_writer_bytes": (C.c_size_t, [VP, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_gif_writer_write": (C.c_int32, [VP, C.c_char_p]),
+    "rtc_gif_writer_destroy": (None, [VP]),
     "rtc_scene_load_lua": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_scene_load_lua_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
