@@ -268,7 +268,8 @@ rtc_status  rtc_scene_load_yaml_file(const char *path, rtc_shape **shapes_out, u
  * screenheight / samples as Lua integers — and becomes one JOB: a world, a camera, the output file's name. The caller renders
  * the jobs in order (one rtc_render* launch each: an AddFrame loop is the one-camera-per-launch sequence a pipelined
  * context overlaps). The library writes PNG / PPM stills (rtc_canvas_write_png8, rtc_canvas_write_ppm_rgb8) and the
- * animation's GIF (rtc_gif_format, rtc_gif_writer_*, rtc_lua_program_render_gif); JPEG is not rebuilt.
+ * animation's GIF (rtc_gif_format, rtc_gif_writer_*, rtc_lua_program_render_gif) and JPEG stills (rtc_jpeg_format,
+ * rtc_jpeg_encoder_*, rtc_lua_program_render_files).
  * math.random is Lua 5.3's on POSIX (glibc random(), restated), so `math.randomseed(13)` worlds are reproducible.
  * A script runs under a step budget (`step_limit` statements / loop iterations / calls, 0 = 100 000 000), may nest 200 calls
  * (the interpreter recurses on the caller's stack: up to about 2 MB of it at that depth) and cannot touch
@@ -337,8 +338,8 @@ rtc_status  rtc_gamma_thresholds(float gamma, double *out);
  * extension): an 8-bit PNG of `pixels` = height*width*channels bytes, channels = 4 (to_imgbuf's RGBA, colour type 6) or 3
  * (the device's Color::scale frame, colour type 2; a decoder supplies alpha 255, which is what to_imgbuf stores). PNG is
  * lossless: decoding gives back exactly these pixels, as it does for the reference's file. No compressor is built in —
- * the zlib stream uses stored blocks, so the file is a little larger than the pixels. JPEG (a lossy third-party codec in
- * the reference) is not rebuilt; GIF is below. format: bytes needed; writes at most cap. Host. */
+ * the zlib stream uses stored blocks, so the file is a little larger than the pixels. GIF and JPEG are below.
+ * format: bytes needed; writes at most cap. Host. */
 rtc_status  rtc_canvas_write_png8(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels);
 size_t      rtc_canvas_format_png8(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint8_t *buf, size_t cap);
 /* Animated GIF: what StartAnimation(file) / enc:AddFrame(world, camera) write in the reference (lua.rs:17-45,75-79,
@@ -378,6 +379,48 @@ enum { RTC_GIF_SEGMENT = 4096, RTC_GIF_DELAY_CS = 7 };
 rtc_status  rtc_gif_quantize(const uint8_t *rgb8, uint32_t width, uint32_t height, uint8_t *palette, uint8_t *indices, uint32_t *used);
 size_t      rtc_gif_lzw(const uint8_t *indices, size_t n, uint8_t *buf, size_t cap);
 size_t      rtc_gif_format(const uint8_t *frames, uint32_t nframes, uint32_t width, uint32_t height, uint8_t *buf, size_t cap);
+/* JPEG: what Canvas::write_to_file writes for a ".jpg" / ".jpeg" name (canvas.rs:80-84, the `image` crate's encoder at
+ * quality 75; Render(world, camera, "jamis.jpg") in jamis.lua).
+ * LAYOUT PARITY UNPINNED: no copy of the reference's encoder is at hand; what follows is what it is understood to emit, and
+ * byte parity with the reference's files is not claimed. Deterministic:
+ *   Input: `pixels` = height*width*channels bytes, channels 3 (Color::scale rows: rtc_render_rgb8, rtc_render_rows' d_rgb8)
+ *          or 4 (to_imgbuf's RGBA; alpha is ignored: the same RGB in 3 or 4 channels gives the same file). Width and height
+ *          1..65535, quality 1..100; anything else is RTC_ERR_ARG (0 bytes from rtc_jpeg_format).
+ *   File:  SOI; APP0 JFIF 1.02 (no density units, density 1:1, no thumbnail); DQT table 0 (luma) and DQT table 1 (chroma),
+ *          one segment each, 8-bit entries in zigzag order; SOF0 (baseline, 8-bit, components 1, 2, 3, each sampled 1x1 —
+ *          4:4:4 —, quantisation tables 0, 1, 1); four DHT segments with the Annex K.3 tables, DC0, AC0, DC1, AC1; SOS (one
+ *          interleaved scan of the three components, tables 0/0, 1/1, 1/1, Ss 0, Se 63, Ah Al 0); the entropy-coded data;
+ *          EOI. No restart markers. The 623 bytes in front of the data depend on the size and quality only.
+ *   Quantisation tables: libjpeg's scaling of the Annex K.1 tables: s = q < 50 ? 5000 / q : 200 - 2q, entry =
+ *          clamp((std * s + 50) / 100, 1, 255), integer arithmetic. rtc_jpeg_quant_tables gives both tables, natural order.
+ *   Colour, per pixel, in f32 with the coefficients the f32 quotients written here, evaluated exactly in this order (products
+ *          first, sums left to right, no fused multiply-add):
+ *              Y  = ((( 76.245/255)*r + (149.685/255)*g) + ( 29.07/255)*b)
+ *              Cb = ((((-43.0185/255)*r + (-84.4815/255)*g) + (127.5/255)*b) + 128)
+ *              Cr = ((((127.5/255)*r + (-106.7685/255)*g) + (-20.7315/255)*b) + 128)
+ *          each converted to a byte by truncation toward zero with saturation (Rust's `as u8`: NaN and negatives -> 0,
+ *          >= 255 -> 255).
+ *   Blocks: 8x8 per component, MCUs in raster order, each MCU the Y, Cb and Cr blocks of the same pixels; pixels past the
+ *          right or bottom edge replicate the last column / row.
+ *   DCT:   libjpeg's integer LLM forward DCT (ISLOW: CONST_BITS 13, PASS1_BITS 2, constants round(c * 2^13), DESCALE(x, n)
+ *          = (x + 2^(n-1)) >> n arithmetic) of the samples minus 128, rows then columns; the output is scaled by 8.
+ *          rtc_jpeg_fdct: that DCT of 64 samples (0..255, natural order, not level-shifted).
+ *   Quantised coefficient of DCT output d and table entry q: round(trunc(d / 8) / q) with halves away from zero, computed
+ *          as sign(t) * ((2|t| + q) / (2q)), t = trunc(d / 8) — the same number as the f32 ((d/8) as f32 / q as f32).round().
+ *          rtc_jpeg_coefficients: every MCU's three blocks of 64 (Y, Cb, Cr, natural order), MCUs in raster order.
+ *   Entropy coding: DC predicted per component from the previous MCU's (0 for the first); AC as runs of zeros with ZRL (0xF0)
+ *          for runs of 16 and EOB only when the block ends in zeros; bits MSB-first; the last byte padded with 1-bits; every
+ *          0xFF byte of the data, the padded one included, followed by 0x00.
+ * rtc_jpeg_format: the whole file — bytes needed (0 on bad arguments); writes at most cap. rtc_canvas_write_jpeg: the same to
+ * `path`. Host. */
+rtc_status  rtc_jpeg_quant_tables(int32_t quality, uint16_t *out);
+rtc_status  rtc_jpeg_fdct(const uint8_t *samples, int32_t *out);
+rtc_status  rtc_jpeg_coefficients(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, int32_t quality,
+                                  int16_t *out);
+size_t      rtc_jpeg_format(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, int32_t quality, uint8_t *buf,
+                            size_t cap);
+rtc_status  rtc_canvas_write_jpeg(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                                  int32_t quality);
 
 /* ==== [device] the hot path on one MI355X ========================================== */
 
@@ -505,6 +548,39 @@ void        rtc_gif_writer_destroy(rtc_gif_writer *g);
 typedef int (*rtc_lua_gif_fn)(void *user, const rtc_lua_job *job, uint32_t job_index, const uint8_t *bytes, size_t nbytes);
 rtc_status  rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
                                        rtc_lua_gif_fn fn, void *user, rtc_stats *stats);
+/* The JPEG writer on the device: the same bytes as rtc_jpeg_format for a frame already in device memory (csrc/rtc_jpeg.hip);
+ * only the finished file crosses PCIe. An encoder is bound to a context and owns its scratch, grow-only and sized from the
+ * worst case of a block (22 + 63 * 26 + 3 * 11 + 4 = 1697 entropy-coded bits, doubled by byte stuffing at most), so no input
+ * can overflow it: about 2.3 KB per 8x8 pixels (for 1920x1080, 75 MB).
+ *   encode_device: `d_pixels` = height*width*channels bytes in device memory (rtc_render_rows' d_rgb8 rows, channels 3, or
+ *     rtc_render_views_rgba8's frame, channels 4), encoded on the context's stream in order with what the caller put there
+ *     before (after launches of a pipelined context: rtc_context_fence first); blocks until the file is on the host.
+ *   render: Camera::render + set_gamma(gamma) + write_to_file("x.jpg"): at gamma 1 through the rows path (3 channels), at
+ *     any other gamma through rtc_render_views_rgba8 (4 channels), into the encoder's scratch; the frame never leaves the
+ *     device. The bytes equal rtc_jpeg_format of rtc_render_rgba8(..., gamma).
+ *   bytes: the last file (bytes needed; writes at most cap; 0 before the first); write: the same to `path`. [device] */
+typedef struct rtc_jpeg_encoder rtc_jpeg_encoder;
+rtc_status  rtc_jpeg_encoder_create(rtc_context *ctx, rtc_jpeg_encoder **out);
+rtc_status  rtc_jpeg_encoder_encode_device(rtc_jpeg_encoder *e, const void *d_pixels, uint32_t width, uint32_t height,
+                                           uint32_t channels, int32_t quality);
+rtc_status  rtc_jpeg_encoder_render(rtc_jpeg_encoder *e, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                    float gamma, int32_t quality);
+size_t      rtc_jpeg_encoder_bytes(const rtc_jpeg_encoder *e, uint8_t *buf, size_t cap);
+rtc_status  rtc_jpeg_encoder_write(const rtc_jpeg_encoder *e, const char *path);
+void        rtc_jpeg_encoder_destroy(rtc_jpeg_encoder *e);
+/* rtc_lua_program_render_gif with every file of the reference delivered: the same launches, lanes and job order; `fn`
+ * receives, per job, `format` and its bytes —
+ *   RTC_LUA_OUT_GIF_RECORD  an AddFrame job's GIF record (as rtc_lua_program_render_gif delivers it);
+ *   RTC_LUA_OUT_JPEG        a Render job whose file name ends in ".jpg" or ".jpeg" (any case): the whole JPEG file of its
+ *                           rows at `quality`, encoded on the GPU behind the render on the same lane (rtc_jpeg_format's bytes);
+ *   RTC_LUA_OUT_RGB8        any other Render job: the 8-bit rows, nbytes = vsize*hsize*3.
+ * Encoded outputs cross PCIe as their 8-byte length, then exactly that many bytes. RTC_ERR_ARG unless quality is 1..100.
+ * [device] */
+enum { RTC_LUA_OUT_RGB8 = 0u, RTC_LUA_OUT_GIF_RECORD = 1u, RTC_LUA_OUT_JPEG = 2u };
+typedef int (*rtc_lua_file_fn)(void *user, const rtc_lua_job *job, uint32_t job_index, uint32_t format, const uint8_t *bytes,
+                               size_t nbytes);
+rtc_status  rtc_lua_program_render_files(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
+                                         int32_t quality, rtc_lua_file_fn fn, void *user, rtc_stats *stats);
 /* Page-locked host memory for canvases handed to rtc_render: a canvas from rtc_host_alloc is
  * filled by one DMA at link speed, ordinary (pageable) memory goes through the runtime's bounce
  * buffers and is several times slower. What the reference would use for Canvas.pixels

@@ -17,7 +17,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, PATTERNS, STATUS_NAMES, declare)
 
@@ -328,8 +328,8 @@ class LuaProgram:
 
     def render_to_files(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> list:
         """render_lua with the files written: Render(world, camera, "x.png") -> out_dir/x.png, "x.ppm" -> the P3 file of
-        Canvas::write_to_file_simple; any other extension (the reference's JPEG / GIF codecs are not rebuilt) -> the name
-        + ".png". AddFrame frames of StartAnimation("a.gif") -> out_dir/a.gif.0000.png, a.gif.0001.png, ...
+        Canvas::write_to_file_simple; any other extension -> the name + ".png" (render_reference_files writes the JPEGs and
+        GIFs). AddFrame frames of StartAnimation("a.gif") -> out_dir/a.gif.0000.png, a.gif.0001.png, ...
         Only the file's base name is used. Returns the paths in job order."""
         out = Path(out_dir)
         out.mkdir(parents=True, exist_ok=True)
@@ -409,6 +409,76 @@ class LuaProgram:
 
         try:
             self.render_gif(ctx, cb, mode=mode, flags=flags)
+        finally:
+            for k in sorted(anims):
+                a = anims[k]
+                target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
+                target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
+                paths.append(target)
+        return paths
+
+    def render_files(self, ctx: "Context", on_output, quality: int = 75, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
+                     with_stats: bool = False):
+        """rtc_lua_program_render_files: every job rendered as by render(); on_output(job_index, fmt, data, outfile, kind) gets,
+        by `fmt`, an AddFrame job's GIF record ("gif", bytes), a .jpg / .jpeg Render job's whole JPEG file at `quality`
+        ("jpeg", bytes, encoded on the GPU) or any other Render job's (vsize, hsize, 3) uint8 rows ("rgb8").
+        A true return value stops the run."""
+        raised = []
+        names = {LUA_OUT_RGB8: "rgb8", LUA_OUT_GIF_RECORD: "gif", LUA_OUT_JPEG: "jpeg"}
+
+        def cb(_user, jp, index, fmt, data, nbytes):
+            try:
+                j = jp.contents
+                outfile = (j.outfile or b"").decode(errors="replace")
+                if fmt == LUA_OUT_RGB8:
+                    payload = np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3))
+                else:
+                    payload = C.string_at(data, nbytes)
+                return 1 if on_output(index, names[fmt], payload, outfile, "AddFrame" if j.kind == 1 else "Render") else 0
+            except BaseException as e:  # never unwind through the C frames
+                raised.append(e)
+                return 1
+
+        st = RtcStats()
+        fn = LUA_FILE_FN(cb)
+        rc = lib().rtc_lua_program_render_files(ctx._h, self._h, mode, flags, quality, fn, None, C.byref(st) if with_stats else None)
+        if raised:
+            raise raised[0]
+        _check(rc, "rtc_lua_program_render_files")
+        return _stats_dict(st, True) if with_stats else None
+
+    def render_reference_files(self, ctx: "Context", out_dir, quality: int = 75, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> list:
+        """render_lua with every file under the name the script gave it (only its base name is used): ".jpg" / ".jpeg"
+        stills as JPEG encoded on the GPU at `quality` (the reference's `save` uses 75), ".png" / ".ppm" as render_to_files
+        writes them, any other extension + ".png", and one GIF per StartAnimation call (+ ".gif" unless the name has it).
+        Returns the paths: stills in job order, then the animations in StartAnimation order."""
+        out = Path(out_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        paths, anims = [], {}
+
+        def cb(index, fmt, data, outfile, kind):
+            name = Path(outfile).name or f"job{index}"
+            if fmt == "gif":
+                j = self.job(index)
+                a = anims.setdefault(j.animation, {"name": name, "size": (j.camera.hsize, j.camera.vsize), "records": []})
+                if (j.camera.hsize, j.camera.vsize) != a["size"]:
+                    raise RtcError(4, "render_reference_files", f"frame {j.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
+                a["records"].append(data)
+                return False
+            if fmt == "jpeg":
+                target = out / name
+                target.write_bytes(data)
+            else:
+                target = out / name if name.lower().endswith((".png", ".ppm")) else out / (name + ".png")
+                if target.suffix.lower() == ".ppm":
+                    write_ppm_rgb8(target, data)
+                else:
+                    write_png(target, data)
+            paths.append(target)
+            return False
+
+        try:
+            self.render_files(ctx, cb, quality=quality, mode=mode, flags=flags)
         finally:
             for k in sorted(anims):
                 a = anims[k]
@@ -581,6 +651,61 @@ def gif_encode(frames) -> bytes:
     buf = np.empty(need, dtype=np.uint8)
     lib().rtc_gif_format(a.ctypes.data_as(P8), n, w, h, buf.ctypes.data_as(P8), need)
     return buf.tobytes()
+
+
+def _pixels_u8(pixels) -> np.ndarray:
+    a = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise ValueError("pixels must be an (H, W, 3) or (H, W, 4) uint8 array")
+    return a
+
+
+def jpeg_quant_tables(quality: int = 75) -> np.ndarray:
+    """The (2, 64) luma and chroma quantisation tables at `quality`, natural order (rtc_jpeg_quant_tables)."""
+    out = np.empty((2, 64), dtype=np.uint16)
+    _check(lib().rtc_jpeg_quant_tables(quality, out.ctypes.data_as(C.POINTER(C.c_uint16))), "rtc_jpeg_quant_tables", f"quality {quality}")
+    return out
+
+
+def jpeg_fdct(samples: np.ndarray) -> np.ndarray:
+    """The integer forward DCT of include/rtc.h (libjpeg's ISLOW, output scaled by 8) of an 8x8 block of samples 0..255
+    (rtc_jpeg_fdct): an (8, 8) int32 array, natural order."""
+    a = np.ascontiguousarray(samples, dtype=np.uint8).reshape(64)
+    out = np.empty(64, dtype=np.int32)
+    _check(lib().rtc_jpeg_fdct(a.ctypes.data_as(C.POINTER(C.c_uint8)), out.ctypes.data_as(C.POINTER(C.c_int32))), "rtc_jpeg_fdct")
+    return out.reshape(8, 8)
+
+
+def jpeg_coefficients(pixels: np.ndarray, quality: int = 75) -> np.ndarray:
+    """The quantised blocks of a JPEG of `pixels` (rtc_jpeg_coefficients): (MCUs, 3, 64) int16, MCUs in raster order, Y, Cb,
+    Cr per MCU, natural order."""
+    a = _pixels_u8(pixels)
+    h, w, c = a.shape
+    out = np.empty((((w + 7) // 8) * ((h + 7) // 8), 3, 64), dtype=np.int16)
+    _check(lib().rtc_jpeg_coefficients(a.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, c, quality, out.ctypes.data_as(C.POINTER(C.c_int16))),
+           "rtc_jpeg_coefficients", f"{w}x{h}x{c} quality {quality}")
+    return out
+
+
+def jpeg_encode(pixels: np.ndarray, quality: int = 75) -> bytes:
+    """A baseline 4:4:4 JPEG of an (H, W, 3) or (H, W, 4) uint8 frame, encoded on the host (rtc_jpeg_format): what
+    Canvas::write_to_file writes for a ".jpg" name (include/rtc.h; alpha ignored)."""
+    a = _pixels_u8(pixels)
+    h, w, c = a.shape
+    P8 = C.POINTER(C.c_uint8)
+    need = lib().rtc_jpeg_format(a.ctypes.data_as(P8), w, h, c, quality, None, 0)
+    if need == 0:
+        raise RtcError(4, "rtc_jpeg_format", f"{w}x{h}x{c} quality {quality}")
+    buf = np.empty(need, dtype=np.uint8)
+    lib().rtc_jpeg_format(a.ctypes.data_as(P8), w, h, c, quality, buf.ctypes.data_as(P8), need)
+    return buf.tobytes()
+
+
+def write_jpeg(path, pixels: np.ndarray, quality: int = 75) -> None:
+    """rtc_canvas_write_jpeg: jpeg_encode's bytes to `path`."""
+    a = _pixels_u8(pixels)
+    _check(lib().rtc_canvas_write_jpeg(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2], quality),
+           "rtc_canvas_write_jpeg")
 
 
 def write_ppm(path, rgb: np.ndarray) -> None:
@@ -881,6 +1006,51 @@ class GifWriter:
     def close(self):
         if self._h:
             lib().rtc_gif_writer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JpegEncoder:
+    """A JPEG encoder on the GPU (rtc_jpeg_encoder): frames already in device memory or rendered straight into the encoder;
+    only the finished file crosses PCIe. The bytes equal jpeg_encode's for the same pixels."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(lib().rtc_jpeg_encoder_create(ctx._h, C.byref(self._h)), "rtc_jpeg_encoder_create")
+        ctx._worlds.append(weakref.ref(self))   # closed with the context
+
+    def encode_device(self, d_ptr: int, width: int, height: int, channels: int = 3, quality: int = 75) -> bytes:
+        """Encode the height x width x channels uint8 frame at device address d_ptr (enqueued on the context's stream)."""
+        _check(lib().rtc_jpeg_encoder_encode_device(self._h, C.c_void_p(d_ptr), width, height, channels, quality),
+               "rtc_jpeg_encoder_encode_device")
+        return self.bytes()
+
+    def render(self, world: "DeviceWorld", cam: RtcCamera, gamma: float = 1.0, quality: int = 75, mode: int = MODE_RENDER_ASYNC,
+               flags: int = 0) -> bytes:
+        """Camera::render + set_gamma(gamma) + write_to_file("x.jpg"), the frame never leaving the device."""
+        _check(lib().rtc_jpeg_encoder_render(self._h, world._h, C.byref(cam), mode, flags, gamma, quality), "rtc_jpeg_encoder_render")
+        return self.bytes()
+
+    def bytes(self) -> bytes:
+        need = lib().rtc_jpeg_encoder_bytes(self._h, None, 0)
+        if need == 0:
+            return b""
+        buf = np.empty(need, dtype=np.uint8)
+        lib().rtc_jpeg_encoder_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
+        return buf.tobytes()
+
+    def write(self, path) -> None:
+        _check(lib().rtc_jpeg_encoder_write(self._h, str(path).encode()), "rtc_jpeg_encoder_write")
+
+    def close(self):
+        if self._h:
+            lib().rtc_jpeg_encoder_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

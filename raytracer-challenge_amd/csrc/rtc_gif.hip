@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -27,6 +28,7 @@
 #include "rtc.h"
 #include "rtc_gif.h"
 #include "rtc_internal.h"
+#include "rtc_jpeg.h"
 
 namespace {
 
@@ -613,10 +615,26 @@ rtc_status rtc_gif_writer_write(const rtc_gif_writer *g, const char *path) {
     return (std::fclose(f) == 0 && ok) ? RTC_OK : RTC_ERR_IO;
 }
 
-// rtc_lua_program_render's ring and lanes, with the GIF chain behind every AddFrame render on the same lane and only the
-// record's length copied behind it; the record itself follows at delivery, on this call's copy stream.
-rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_gif_fn fn,
-                                      void *user, rtc_stats *stats) {
+namespace {
+
+bool jpeg_name(const char *name) { // ".jpg" / ".jpeg", any case, as the `image` crate matches extensions
+    if (!name) return false;
+    const size_t n = std::strlen(name);
+    auto ends = [&](const char *ext) {
+        const size_t k = std::strlen(ext);
+        if (n < k) return false;
+        for (size_t i = 0; i < k; ++i)
+            if (std::tolower((unsigned char)name[n - k + i]) != ext[i]) return false;
+        return true;
+    };
+    return ends(".jpg") || ends(".jpeg");
+}
+
+// rtc_lua_program_render's ring and lanes, with the GIF chain behind every AddFrame render (and, when `jpeg`, the JPEG chain
+// behind every Render job of a .jpg / .jpeg name) on the same lane and only the encoded length copied behind it; the bytes
+// themselves follow at delivery, on this call's copy stream.
+rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, bool jpeg, int32_t quality,
+                              rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
     if (!ctx || !prog || mode > RTC_MODE_RENDER_ASYNC) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     constexpr uint32_t RING = rtc_context::MAX_LANES + 1u;
@@ -625,8 +643,11 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
         size_t cap = 0, hcap = 0;
         GifScratch sc;
         GifInfo *h_info = nullptr;          // page-locked: the record length lands here
+        JpegScratch *jsc = nullptr;
+        unsigned long long *h_len = nullptr; // page-locked: the JPEG data length lands here
         hipEvent_t done = nullptr;
         bool pending = false, gif = false;
+        uint32_t format = RTC_LUA_OUT_RGB8;
         uint32_t job = 0;
     } ring[RING];
     hipStream_t copy = nullptr;
@@ -659,8 +680,18 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
             if (hipMemcpyAsync(sl.h, sl.sc.record, nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
                 hipStreamSynchronize(copy) != hipSuccess)
                 return RTC_ERR_DEVICE;
+        } else if (sl.format == RTC_LUA_OUT_JPEG) {
+            const size_t len = (size_t)*sl.h_len;
+            if (len < 2 || len > rtc_jpeg_scratch_out_cap(sl.jsc)) return RTC_ERR_DEVICE;
+            nbytes = RTC_JPEG_HEADER_BYTES + len;
+            const rtc_status hb = host_buf(sl, nbytes);
+            if (hb != RTC_OK) return hb;
+            rtc_jpeg_header(job.camera.hsize, job.camera.vsize, quality, sl.h);
+            if (hipMemcpyAsync(sl.h + RTC_JPEG_HEADER_BYTES, rtc_jpeg_scratch_data(sl.jsc), len, hipMemcpyDeviceToHost, copy) != hipSuccess ||
+                hipStreamSynchronize(copy) != hipSuccess)
+                return RTC_ERR_DEVICE;
         }
-        if (fn && !stop && fn(user, &job, sl.job, sl.h, nbytes) != 0) stop = true;
+        if (fn && !stop && fn(user, &job, sl.job, sl.format, sl.h, nbytes) != 0) stop = true;
         return RTC_OK;
     };
     auto drain = [&](uint32_t next_job) -> rtc_status {
@@ -681,7 +712,9 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
         if (st != RTC_OK) break;
         const size_t bytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
         const bool gif = job.kind == RTC_LUA_JOB_ADD_FRAME;
-        if (bytes == 0 || (gif && (job.camera.hsize > 65535u || job.camera.vsize > 65535u))) { st = RTC_ERR_ARG; break; }
+        const uint32_t format = gif ? RTC_LUA_OUT_GIF_RECORD : (jpeg && jpeg_name(job.outfile)) ? RTC_LUA_OUT_JPEG : RTC_LUA_OUT_RGB8;
+        const bool encoded = format != RTC_LUA_OUT_RGB8;
+        if (bytes == 0 || (encoded && (job.camera.hsize > 65535u || job.camera.vsize > 65535u))) { st = RTC_ERR_ARG; break; }
         Slot &sl = ring[i % RING];
         st = deliver(sl);
         if (st != RTC_OK || stop) break;
@@ -702,7 +735,11 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
             if (e != hipSuccess) { (void)hipGetLastError(); st = e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; break; }
             sl.cap = bytes;
         }
-        if (!gif && (st = host_buf(sl, bytes)) != RTC_OK) break;
+        if (!encoded && (st = host_buf(sl, bytes)) != RTC_OK) break;
+        if (format == RTC_LUA_OUT_JPEG) {
+            if (!sl.jsc && !(sl.jsc = rtc_jpeg_scratch_new())) { st = RTC_ERR_NOMEM; break; }
+            if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
+        }
         if (!sl.h_info && hipHostMalloc(reinterpret_cast<void **>(&sl.h_info), sizeof(GifInfo), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
         if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
         st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, nullptr, sl.d, flags);
@@ -712,6 +749,10 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
             st = encode_frame(sl.sc, sl.d, job.camera.hsize, job.camera.vsize, s);
             if (st != RTC_OK) break;
             if (hipMemcpyAsync(sl.h_info, sl.sc.info, sizeof(GifInfo), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
+        } else if (format == RTC_LUA_OUT_JPEG) {
+            st = (rtc_status)rtc_jpeg_scratch_encode(sl.jsc, sl.d, job.camera.hsize, job.camera.vsize, 3, quality, s);
+            if (st != RTC_OK) break;
+            if (hipMemcpyAsync(sl.h_len, rtc_jpeg_scratch_length(sl.jsc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
         } else if (hipMemcpyAsync(sl.h, sl.d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
             st = RTC_ERR_DEVICE;
             break;
@@ -719,6 +760,7 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
         if (hipEventRecord(sl.done, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
         sl.pending = true;
         sl.gif = gif;
+        sl.format = format;
         sl.job = i;
     }
     {
@@ -733,6 +775,8 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
         if (sl.d) (void)hipFree(sl.d);
         if (sl.h) (void)hipHostFree(sl.h);
         if (sl.h_info) (void)hipHostFree(sl.h_info);
+        if (sl.h_len) (void)hipHostFree(sl.h_len);
+        rtc_jpeg_scratch_free(sl.jsc);
         sl.sc.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -743,4 +787,28 @@ rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *p
     }
     if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
     return st;
+}
+
+struct GifFnAdapter {
+    rtc_lua_gif_fn fn;
+    void *user;
+};
+
+int gif_fn_adapter(void *user, const rtc_lua_job *job, uint32_t job_index, uint32_t, const uint8_t *bytes, size_t nbytes) {
+    const GifFnAdapter *a = static_cast<const GifFnAdapter *>(user);
+    return a->fn ? a->fn(a->user, job, job_index, bytes, nbytes) : 0;
+}
+
+} // namespace
+
+rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_gif_fn fn,
+                                      void *user, rtc_stats *stats) {
+    GifFnAdapter a{fn, user};
+    return render_lua_outputs(ctx, prog, mode, flags, false, 75, gif_fn_adapter, &a, stats);
+}
+
+rtc_status rtc_lua_program_render_files(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, int32_t quality,
+                                        rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
+    if (quality < 1 || quality > 100) return RTC_ERR_ARG;
+    return render_lua_outputs(ctx, prog, mode, flags, true, quality, fn, user, stats);
 }

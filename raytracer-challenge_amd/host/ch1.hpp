@@ -209,6 +209,22 @@ class Canvas { // canvas.rs:16-109
         rtc_canvas_to_rgba8(pixels.data(), width, height, gamma, rgba.data());
         check(rtc_canvas_write_png8(file_name.c_str(), rgba.data(), width, height, 4), "Canvas::write_to_file");
     }
+    // Canvas::write_to_file for a ".jpg" / ".jpeg" name, as its own call (write_to_file itself keeps panicking on them):
+    // the same frame and gamma rules as write_to_file, encoded by the host JPEG writer (rtc_canvas_write_jpeg, include/rtc.h)
+    // at `quality` — the reference's `save` uses 75. The name's extension is not looked at.
+    void write_to_file_jpeg(const std::string &file_name, int32_t quality = 75) const {
+        const char *where = "Canvas::write_to_file_jpeg";
+        if (is_imgbuf()) {
+            if (gamma != rgba8_gamma)
+                throw Panic(RTC_ERR_ARG, "Canvas::write_to_file_jpeg(" + file_name + "): gamma was changed after Camera::render_rgba8 made this frame");
+            check(rtc_canvas_write_jpeg(file_name.c_str(), rgba8.data(), width, height, 4, quality), where);
+            return;
+        }
+        if (is_quantised()) { check(rtc_canvas_write_jpeg(file_name.c_str(), rgb8.data(), width, height, 3, quality), where); return; }
+        std::vector<uint8_t> rgba(static_cast<size_t>(width) * height * 4);
+        rtc_canvas_to_rgba8(pixels.data(), width, height, gamma, rgba.data());
+        check(rtc_canvas_write_jpeg(file_name.c_str(), rgba.data(), width, height, 4, quality), where);
+    }
     float gamma = 1.0f; // canvas.rs:30
   private:
     double *at(uint32_t x, uint32_t y) {
@@ -401,9 +417,9 @@ struct LuaSink {
 } // namespace detail
 
 // render_lua (lua.rs:50-91): run a scene script and render what it asks for. The reference writes each Render's Canvas
-// with `image` (PNG / JPEG by extension) and each animation as a GIF; those codecs are not rebuilt here, so the frames are
-// handed to `sink` instead — (Canvas holding the 8-bit frame, the file name the script gave, frame number inside its
-// animation or -1 for Render) — in the order the script made the calls. Returns what the script print()ed.
+// with `image` (PNG / JPEG by extension) and each animation as a GIF; here the frames are handed to `sink` instead —
+// (Canvas holding the 8-bit frame, the file name the script gave, frame number inside its animation or -1 for Render) — in
+// the order the script made the calls, for write_to_file (PNG) or write_to_file_jpeg. Returns what the script print()ed.
 template <class Sink>
 inline std::string render_lua(const std::string &script, Sink &&sink) {
     char err[512] = "";

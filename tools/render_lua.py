@@ -1,8 +1,9 @@
 """The reference's `render_lua(script)` (ch1/src/lua.rs:50-91) from the command line: run a Lua scene script through the
 library's interpreter, render every Render / AddFrame call on the GPU, write the frames (PNG; PPM for ".ppm" names).
-    python tools/render_lua.py [--gif] SCRIPT.lua [OUT_DIR]
+    python tools/render_lua.py [--gif | --jpeg] SCRIPT.lua [OUT_DIR]
 By default every AddFrame frame is a numbered PNG; with --gif each StartAnimation call becomes one animated GIF, encoded
-on the GPU.
+on the GPU; with --jpeg every file gets the name the script gave it: ".jpg" / ".jpeg" stills as JPEG (quality 75) and the
+animations as GIFs, both encoded on the GPU.
 Needs an MI355X (there is no CPU path); prints what the script printed and the files written."""
 import sys
 import time
@@ -14,8 +15,8 @@ from _bootstrap import package  # noqa: E402
 
 
 def main(argv):
-    gif = "--gif" in argv
-    argv = [a for a in argv if a != "--gif"]
+    gif, jpeg = "--gif" in argv, "--jpeg" in argv
+    argv = [a for a in argv if a not in ("--gif", "--jpeg")]
     if len(argv) < 2:
         print(__doc__)
         return 2
@@ -25,7 +26,10 @@ def main(argv):
     ctx = rtc.Context(0)
     t = time.perf_counter()
     out = argv[2] if len(argv) > 2 else "."
-    paths = prog.render_animations(ctx, out) if gif else prog.render_to_files(ctx, out)
+    if jpeg:
+        paths = prog.render_reference_files(ctx, out)
+    else:
+        paths = prog.render_animations(ctx, out) if gif else prog.render_to_files(ctx, out)
     dt = time.perf_counter() - t
     for p in paths:
         print(p)
