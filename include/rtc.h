@@ -268,8 +268,9 @@ rtc_status  rtc_scene_load_yaml_file(const char *path, rtc_shape **shapes_out, u
  * screenheight / samples as Lua integers — and becomes one JOB: a world, a camera, the output file's name. The caller renders
  * the jobs in order (one rtc_render* launch each: an AddFrame loop is the one-camera-per-launch sequence a pipelined
  * context overlaps). The library writes PNG / PPM stills (rtc_canvas_write_png8, rtc_canvas_write_ppm_rgb8) and the
- * animation's GIF (rtc_gif_format, rtc_gif_writer_*, rtc_lua_program_render_gif) and JPEG stills (rtc_jpeg_format,
- * rtc_jpeg_encoder_*, rtc_lua_program_render_files).
+ * animation's GIF (rtc_gif_format, rtc_gif_writer_*, rtc_lua_program_render_gif), JPEG stills (rtc_jpeg_format,
+ * rtc_jpeg_encoder_*, rtc_lua_program_render_files) and compressed PNGs (rtc_png_format, rtc_png_encoder_*,
+ * rtc_lua_program_render_png).
  * math.random is Lua 5.3's on POSIX (glibc random(), restated), so `math.randomseed(13)` worlds are reproducible.
  * A script runs under a step budget (`step_limit` statements / loop iterations / calls, 0 = 100 000 000), may nest 200 calls
  * (the interpreter recurses on the caller's stack: up to about 2 MB of it at that depth) and cannot touch
@@ -421,6 +422,48 @@ size_t      rtc_jpeg_format(const uint8_t *pixels, uint32_t width, uint32_t heig
                             size_t cap);
 rtc_status  rtc_canvas_write_jpeg(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
                                   int32_t quality);
+/* Compressed PNG: a filtered, deflate-coded 8-bit PNG of the same input as rtc_canvas_format_png8 (which stays the stored
+ * writer). LAYOUT PARITY UNPINNED: no copy of the reference's `png` / `deflate` crates is at hand, so byte parity with its
+ * files is not claimed; its pixels are pinned (PNG is lossless: decoding gives back exactly `pixels`). Deterministic:
+ *   Input: `pixels` = height*width*channels bytes, channels 3 (colour type 2) or 4 (colour type 6), bit depth 8, no
+ *          interlace; width and height 1..65535. Anything else is RTC_ERR_ARG (0 bytes from rtc_png_format).
+ *   Filters (ISO 15948 §9, bpp = channels): every row is filtered with None, Sub, Up, Average and Paeth (row 0's prior row
+ *          is zeros); the row takes the filter with the least sum of min(v, 256 - v) over its filtered bytes, ties to the
+ *          lower type. The filtered stream (n = height * (1 + width*channels) bytes) is, per row, the type byte and the row.
+ *   Segments: the stream is cut into segments of RTC_PNG_SEGMENT bytes (the last may be shorter). Each is one deflate
+ *          block; every segment but the last is followed by an empty stored block (a sync flush: 3 bits, zero bits to the
+ *          byte, 00 00 FF FF), so every segment starts on a byte; the last block has BFINAL = 1 and is padded with zero bits.
+ *   Matches: hash(p) = ((s[p] << 10) ^ (s[p+1] << 5) ^ s[p+2]) & 0x7fff, for p + 3 <= n. The candidates of p are the
+ *          RTC_PNG_CHAIN nearest q < p with p - q <= 32768 and hash(q) = hash(p) (every position counts, those inside matches
+ *          and in earlier segments included). A candidate's length is the common prefix of s[q..] and s[p..], capped at 258
+ *          and at the end of p's segment. L(p) = the longest length >= 3 (ties: the nearest candidate), else 0.
+ *   Parse: from the segment's start, at p: if L(p) >= 3 and not L(p+1) > L(p), the match (L(p), its distance) and p += L(p);
+ *          otherwise the literal s[p] and p += 1 (zlib's one-step lazy rule).
+ *   Block type: stored, fixed or dynamic Huffman, whichever has the fewest bits (exact, without padding or flush); ties go
+ *          to stored, then fixed. Stored: 3 bits, zero bits to the byte, LEN, NLEN, the bytes.
+ *   Dynamic codes: literal/length (symbols 0..285, end-of-block counted once) and distance codes limited to 15 bits, the
+ *          code-length code to 7, built by package-merge: symbols of non-zero count sorted by (count, symbol); the deepest
+ *          level lists the leaves, each level above merges the leaves with the pairs of the level below (a leaf first on
+ *          equal weight) and keeps its first 2m - 2 items (m symbols used); the top's first 2m - 2 items are taken, each
+ *          taken leaf adds one bit, each taken package takes two items of the level below. A code of fewer than two used
+ *          symbols gives length 1 to the used one and then to the lowest-numbered unused symbols until two have it (a block
+ *          without matches codes distances 0 and 1 with one bit each). Codes are canonical (RFC 1951 §3.2.2).
+ *          HLIT = max(257, 1 + the last literal/length symbol with a length), HDIST = max(1, 1 + the last distance symbol
+ *          with one), HCLEN = max(4, 1 + the last position of the code-length order with a length). The HLIT + HDIST lengths
+ *          are one sequence (runs cross from one code to the other); a run of r equal values v: v = 0: symbol 18 for
+ *          min(r, 138) while r >= 11, then 17 if r >= 3, else r zeros; v != 0: v once, then 16 for min(r, 6) while r >= 3,
+ *          then v for the rest.
+ *   Framing: signature, IHDR, one IDAT chunk per segment, IEND. The first IDAT also carries the zlib header 78 9C in front,
+ *          the last the Adler-32 of the filtered stream (big-endian) behind, so each chunk's CRC stands alone.
+ *   The file is never larger than n + 22 * segments + 51 bytes (every segment stored).
+ * rtc_png_filter: each row's filter type (`types`, height bytes) and the filtered stream (`filtered`, n bytes); either may be
+ * null. rtc_png_format: the whole file — bytes needed (0 on bad arguments); writes at most cap. rtc_canvas_write_png: the
+ * same to `path`. Host. */
+enum { RTC_PNG_SEGMENT = 32768, RTC_PNG_CHAIN = 8 };
+rtc_status  rtc_png_filter(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint8_t *types,
+                           uint8_t *filtered);
+size_t      rtc_png_format(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint8_t *buf, size_t cap);
+rtc_status  rtc_canvas_write_png(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels);
 
 /* ==== [device] the hot path on one MI355X ========================================== */
 
@@ -581,6 +624,30 @@ typedef int (*rtc_lua_file_fn)(void *user, const rtc_lua_job *job, uint32_t job_
                                size_t nbytes);
 rtc_status  rtc_lua_program_render_files(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
                                          int32_t quality, rtc_lua_file_fn fn, void *user, rtc_stats *stats);
+/* The compressed PNG writer on the device: the same bytes as rtc_png_format for a frame already in device memory
+ * (csrc/rtc_png.hip); only the finished file crosses PCIe. An encoder is bound to a context and owns its scratch, grow-only
+ * and sized from the input (no segment costs more than its stored form): about 11 bytes per filtered byte.
+ *   encode_device / render / bytes / write / destroy: as rtc_jpeg_encoder_* (render at gamma 1 through the rows path with
+ *     3 channels, at any other gamma through rtc_render_views_rgba8 with 4; its bytes equal rtc_png_format of
+ *     rtc_render_rgba8(..., gamma)). [device] */
+typedef struct rtc_png_encoder rtc_png_encoder;
+rtc_status  rtc_png_encoder_create(rtc_context *ctx, rtc_png_encoder **out);
+rtc_status  rtc_png_encoder_encode_device(rtc_png_encoder *e, const void *d_pixels, uint32_t width, uint32_t height,
+                                          uint32_t channels);
+rtc_status  rtc_png_encoder_render(rtc_png_encoder *e, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                   float gamma);
+size_t      rtc_png_encoder_bytes(const rtc_png_encoder *e, uint8_t *buf, size_t cap);
+rtc_status  rtc_png_encoder_write(const rtc_png_encoder *e, const char *path);
+void        rtc_png_encoder_destroy(rtc_png_encoder *e);
+/* rtc_lua_program_render with the files LuaProgram.render_to_files writes, the PNGs compressed on the GPU: the same
+ * launches, lanes and job order as rtc_lua_program_render_gif; `fn` receives, per job —
+ *   RTC_LUA_OUT_PNG   an AddFrame job, or a Render job whose file name does not end in ".ppm" (any case): the whole file
+ *                     (rtc_png_format's bytes of its rows, 3 channels), encoded behind the render on the same lane;
+ *   RTC_LUA_OUT_RGB8  a Render job named ".ppm": the 8-bit rows, nbytes = vsize*hsize*3.
+ * The file crosses PCIe as its 8-byte length, then exactly that many bytes. [device] */
+enum { RTC_LUA_OUT_PNG = 3u };
+rtc_status  rtc_lua_program_render_png(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
+                                       rtc_lua_file_fn fn, void *user, rtc_stats *stats);
 /* Page-locked host memory for canvases handed to rtc_render: a canvas from rtc_host_alloc is
  * filled by one DMA at link speed, ordinary (pageable) memory goes through the runtime's bounce
  * buffers and is several times slower. What the reference would use for Canvas.pixels

@@ -17,7 +17,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, PATTERNS, STATUS_NAMES, declare)
 
@@ -487,6 +487,42 @@ class LuaProgram:
                 paths.append(target)
         return paths
 
+    def render_png_files(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
+        """render_to_files' files under render_to_files' names, the PNGs compressed on the GPU behind each render
+        (rtc_lua_program_render_png: png_encode's bytes, only the file crossing PCIe); ".ppm" stills as render_to_files
+        writes them. Returns the paths in job order (and the stats with `with_stats`)."""
+        out = Path(out_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        paths, raised = [], []
+
+        def cb(_user, jp, index, fmt, data, nbytes):
+            try:
+                j = jp.contents
+                name = Path((j.outfile or b"").decode(errors="replace")).name or f"job{index}"
+                if j.kind == 1:
+                    target = out / f"{name}.{j.frame:04d}.png"
+                elif name.lower().endswith((".png", ".ppm")):
+                    target = out / name
+                else:
+                    target = out / (name + ".png")
+                if fmt == LUA_OUT_PNG:
+                    target.write_bytes(C.string_at(data, nbytes))
+                else:
+                    write_ppm_rgb8(target, np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3)))
+                paths.append(target)
+                return 0
+            except BaseException as e:  # never unwind through the C frames
+                raised.append(e)
+                return 1
+
+        st = RtcStats()
+        fn = LUA_FILE_FN(cb)
+        rc = lib().rtc_lua_program_render_png(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
+        if raised:
+            raise raised[0]
+        _check(rc, "rtc_lua_program_render_png")
+        return (paths, _stats_dict(st, True)) if with_stats else paths
+
     def close(self):
         if getattr(self, "_h", None):
             lib().rtc_lua_program_free(self._h)
@@ -706,6 +742,40 @@ def write_jpeg(path, pixels: np.ndarray, quality: int = 75) -> None:
     a = _pixels_u8(pixels)
     _check(lib().rtc_canvas_write_jpeg(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2], quality),
            "rtc_canvas_write_jpeg")
+
+
+def png_filter(pixels: np.ndarray):
+    """The row filters of the compressed PNG writer (rtc_png_filter): (types, filtered) — each row's filter type (H uint8)
+    and the filtered stream, H * (1 + W * C) uint8 (per row the type byte, then the filtered row)."""
+    a = _pixels_u8(pixels)
+    h, w, c = a.shape
+    P8 = C.POINTER(C.c_uint8)
+    types = np.empty(h, dtype=np.uint8)
+    filtered = np.empty(h * (1 + w * c), dtype=np.uint8)
+    _check(lib().rtc_png_filter(a.ctypes.data_as(P8), w, h, c, types.ctypes.data_as(P8), filtered.ctypes.data_as(P8)),
+           "rtc_png_filter", f"{w}x{h}x{c}")
+    return types, filtered
+
+
+def png_encode(pixels: np.ndarray) -> bytes:
+    """A filtered, deflate-compressed 8-bit PNG of an (H, W, 3) or (H, W, 4) uint8 frame, encoded on the host
+    (rtc_png_format): the bytes PngEncoder produces on the GPU. format_png stays the stored writer."""
+    a = _pixels_u8(pixels)
+    h, w, c = a.shape
+    P8 = C.POINTER(C.c_uint8)
+    need = lib().rtc_png_format(a.ctypes.data_as(P8), w, h, c, None, 0)
+    if need == 0:
+        raise RtcError(4, "rtc_png_format", f"{w}x{h}x{c}")
+    buf = np.empty(need, dtype=np.uint8)
+    lib().rtc_png_format(a.ctypes.data_as(P8), w, h, c, buf.ctypes.data_as(P8), need)
+    return buf.tobytes()
+
+
+def write_png_deflate(path, pixels: np.ndarray) -> None:
+    """rtc_canvas_write_png: png_encode's bytes to `path`."""
+    a = _pixels_u8(pixels)
+    _check(lib().rtc_canvas_write_png(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2]),
+           "rtc_canvas_write_png")
 
 
 def write_ppm(path, rgb: np.ndarray) -> None:
@@ -1051,6 +1121,49 @@ class JpegEncoder:
     def close(self):
         if self._h:
             lib().rtc_jpeg_encoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PngEncoder:
+    """A compressed PNG encoder on the GPU (rtc_png_encoder): frames already in device memory or rendered straight into the
+    encoder; only the finished file crosses PCIe. The bytes equal png_encode's for the same pixels."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(lib().rtc_png_encoder_create(ctx._h, C.byref(self._h)), "rtc_png_encoder_create")
+        ctx._worlds.append(weakref.ref(self))   # closed with the context
+
+    def encode_device(self, d_ptr: int, width: int, height: int, channels: int = 3) -> bytes:
+        """Encode the height x width x channels uint8 frame at device address d_ptr (enqueued on the context's stream)."""
+        _check(lib().rtc_png_encoder_encode_device(self._h, C.c_void_p(d_ptr), width, height, channels), "rtc_png_encoder_encode_device")
+        return self.bytes()
+
+    def render(self, world: "DeviceWorld", cam: RtcCamera, gamma: float = 1.0, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> bytes:
+        """Camera::render + set_gamma(gamma) + write_to_file("x.png"), the frame never leaving the device."""
+        _check(lib().rtc_png_encoder_render(self._h, world._h, C.byref(cam), mode, flags, gamma), "rtc_png_encoder_render")
+        return self.bytes()
+
+    def bytes(self) -> bytes:
+        need = lib().rtc_png_encoder_bytes(self._h, None, 0)
+        if need == 0:
+            return b""
+        buf = np.empty(need, dtype=np.uint8)
+        lib().rtc_png_encoder_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
+        return buf.tobytes()
+
+    def write(self, path) -> None:
+        _check(lib().rtc_png_encoder_write(self._h, str(path).encode()), "rtc_png_encoder_write")
+
+    def close(self):
+        if self._h:
+            lib().rtc_png_encoder_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

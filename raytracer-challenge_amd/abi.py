@@ -66,7 +66,8 @@ LUA_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32
 LUA_GIF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
 GIF_SEGMENT, GIF_DELAY_CS = 4096, 7
 LUA_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
-LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG = 0, 1, 2
+LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG = 0, 1, 2, 3
+PNG_SEGMENT, PNG_CHAIN = 32768, 8
 
 SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute force, object table staged in LDS (one tile)",
                 2: "brute force, object table staged in LDS tiles", 3: "one-level per-wave cull", 4: "two-level per-wave cull"}
@@ -135,6 +136,16 @@ PROTOTYPES = {
     "rtc_jpeg_encoder_write": (C.c_int32, [VP, C.c_char_p]),
     "rtc_jpeg_encoder_destroy": (None, [VP]),
     "rtc_lua_program_render_files": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, LUA_FILE_FN, C.c_void_p, C.POINTER(RtcStats)]),
+    "rtc_png_filter": (C.c_int32, [C.POINTER(C.c_uint8), U32, U32, U32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "rtc_png_format": (C.c_size_t, [C.POINTER(C.c_uint8), U32, U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_canvas_write_png": (C.c_int32, [C.c_char_p, C.POINTER(C.c_uint8), U32, U32, U32]),
+    "rtc_png_encoder_create": (C.c_int32, [VP, C.POINTER(VP)]),
+    "rtc_png_encoder_encode_device": (C.c_int32, [VP, VP, U32, U32, U32]),
+    "rtc_png_encoder_render": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.c_float]),
+    "rtc_png_encoder_bytes": (C.c_size_t, [VP, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_png_encoder_write": (C.c_int32, [VP, C.c_char_p]),
+    "rtc_png_encoder_destroy": (None, [VP]),
+    "rtc_lua_program_render_png": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, LUA_FILE_FN, C.c_void_p, C.POINTER(RtcStats)]),
     "rtc_scene_load_lua": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_scene_load_lua_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),

@@ -29,6 +29,7 @@
 #include "rtc_gif.h"
 #include "rtc_internal.h"
 #include "rtc_jpeg.h"
+#include "rtc_png.h"
 
 namespace {
 
@@ -630,11 +631,21 @@ bool jpeg_name(const char *name) { // ".jpg" / ".jpeg", any case, as the `image`
     return ends(".jpg") || ends(".jpeg");
 }
 
+bool ppm_name(const char *name) { // what render_to_files writes as a P3 file: ".ppm", any case
+    if (!name) return false;
+    const size_t n = std::strlen(name);
+    if (n < 4) return false;
+    const char *e = name + n - 4;
+    return e[0] == '.' && std::tolower((unsigned char)e[1]) == 'p' && std::tolower((unsigned char)e[2]) == 'p' &&
+           std::tolower((unsigned char)e[3]) == 'm';
+}
+
 // rtc_lua_program_render's ring and lanes, with the GIF chain behind every AddFrame render (and, when `jpeg`, the JPEG chain
 // behind every Render job of a .jpg / .jpeg name) on the same lane and only the encoded length copied behind it; the bytes
-// themselves follow at delivery, on this call's copy stream.
+// themselves follow at delivery, on this call's copy stream. When `png`, the compressed PNG chain takes the place of the GIF
+// chain and of the rows for every job but a Render named .ppm (render_to_files' PNG files).
 rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, bool jpeg, int32_t quality,
-                              rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
+                              bool png, rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
     if (!ctx || !prog || mode > RTC_MODE_RENDER_ASYNC) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     constexpr uint32_t RING = rtc_context::MAX_LANES + 1u;
@@ -644,7 +655,8 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         GifScratch sc;
         GifInfo *h_info = nullptr;          // page-locked: the record length lands here
         JpegScratch *jsc = nullptr;
-        unsigned long long *h_len = nullptr; // page-locked: the JPEG data length lands here
+        unsigned long long *h_len = nullptr; // page-locked: the JPEG data / PNG file length lands here
+        PngScratch *psc = nullptr;
         hipEvent_t done = nullptr;
         bool pending = false, gif = false;
         uint32_t format = RTC_LUA_OUT_RGB8;
@@ -690,6 +702,14 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
             if (hipMemcpyAsync(sl.h + RTC_JPEG_HEADER_BYTES, rtc_jpeg_scratch_data(sl.jsc), len, hipMemcpyDeviceToHost, copy) != hipSuccess ||
                 hipStreamSynchronize(copy) != hipSuccess)
                 return RTC_ERR_DEVICE;
+        } else if (sl.format == RTC_LUA_OUT_PNG) {
+            nbytes = (size_t)*sl.h_len;
+            if (nbytes == 0 || nbytes > rtc_png_scratch_out_cap(sl.psc)) return RTC_ERR_DEVICE;
+            const rtc_status hb = host_buf(sl, nbytes);
+            if (hb != RTC_OK) return hb;
+            if (hipMemcpyAsync(sl.h, rtc_png_scratch_data(sl.psc), nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
+                hipStreamSynchronize(copy) != hipSuccess)
+                return RTC_ERR_DEVICE;
         }
         if (fn && !stop && fn(user, &job, sl.job, sl.format, sl.h, nbytes) != 0) stop = true;
         return RTC_OK;
@@ -711,8 +731,10 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         st = rtc_lua_program_job(prog, i, &job);
         if (st != RTC_OK) break;
         const size_t bytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
-        const bool gif = job.kind == RTC_LUA_JOB_ADD_FRAME;
-        const uint32_t format = gif ? RTC_LUA_OUT_GIF_RECORD : (jpeg && jpeg_name(job.outfile)) ? RTC_LUA_OUT_JPEG : RTC_LUA_OUT_RGB8;
+        const bool add_frame = job.kind == RTC_LUA_JOB_ADD_FRAME;
+        const bool gif = add_frame && !png;
+        const uint32_t format = png ? ((add_frame || !ppm_name(job.outfile)) ? RTC_LUA_OUT_PNG : RTC_LUA_OUT_RGB8)
+                                    : gif ? RTC_LUA_OUT_GIF_RECORD : (jpeg && jpeg_name(job.outfile)) ? RTC_LUA_OUT_JPEG : RTC_LUA_OUT_RGB8;
         const bool encoded = format != RTC_LUA_OUT_RGB8;
         if (bytes == 0 || (encoded && (job.camera.hsize > 65535u || job.camera.vsize > 65535u))) { st = RTC_ERR_ARG; break; }
         Slot &sl = ring[i % RING];
@@ -740,6 +762,10 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
             if (!sl.jsc && !(sl.jsc = rtc_jpeg_scratch_new())) { st = RTC_ERR_NOMEM; break; }
             if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
         }
+        if (format == RTC_LUA_OUT_PNG) {
+            if (!sl.psc && !(sl.psc = rtc_png_scratch_new())) { st = RTC_ERR_NOMEM; break; }
+            if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
+        }
         if (!sl.h_info && hipHostMalloc(reinterpret_cast<void **>(&sl.h_info), sizeof(GifInfo), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
         if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
         st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, nullptr, sl.d, flags);
@@ -753,6 +779,10 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
             st = (rtc_status)rtc_jpeg_scratch_encode(sl.jsc, sl.d, job.camera.hsize, job.camera.vsize, 3, quality, s);
             if (st != RTC_OK) break;
             if (hipMemcpyAsync(sl.h_len, rtc_jpeg_scratch_length(sl.jsc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
+        } else if (format == RTC_LUA_OUT_PNG) {
+            st = (rtc_status)rtc_png_scratch_encode(sl.psc, sl.d, job.camera.hsize, job.camera.vsize, 3, s);
+            if (st != RTC_OK) break;
+            if (hipMemcpyAsync(sl.h_len, rtc_png_scratch_length(sl.psc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
         } else if (hipMemcpyAsync(sl.h, sl.d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
             st = RTC_ERR_DEVICE;
             break;
@@ -777,6 +807,7 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         if (sl.h_info) (void)hipHostFree(sl.h_info);
         if (sl.h_len) (void)hipHostFree(sl.h_len);
         rtc_jpeg_scratch_free(sl.jsc);
+        rtc_png_scratch_free(sl.psc);
         sl.sc.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -804,11 +835,16 @@ int gif_fn_adapter(void *user, const rtc_lua_job *job, uint32_t job_index, uint3
 rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_gif_fn fn,
                                       void *user, rtc_stats *stats) {
     GifFnAdapter a{fn, user};
-    return render_lua_outputs(ctx, prog, mode, flags, false, 75, gif_fn_adapter, &a, stats);
+    return render_lua_outputs(ctx, prog, mode, flags, false, 75, false, gif_fn_adapter, &a, stats);
 }
 
 rtc_status rtc_lua_program_render_files(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, int32_t quality,
                                         rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
     if (quality < 1 || quality > 100) return RTC_ERR_ARG;
-    return render_lua_outputs(ctx, prog, mode, flags, true, quality, fn, user, stats);
+    return render_lua_outputs(ctx, prog, mode, flags, true, quality, false, fn, user, stats);
+}
+
+rtc_status rtc_lua_program_render_png(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_file_fn fn,
+                                      void *user, rtc_stats *stats) {
+    return render_lua_outputs(ctx, prog, mode, flags, false, 75, true, fn, user, stats);
 }
