@@ -464,6 +464,63 @@ rtc_status  rtc_png_filter(const uint8_t *pixels, uint32_t width, uint32_t heigh
                            uint8_t *filtered);
 size_t      rtc_png_format(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint8_t *buf, size_t cap);
 rtc_status  rtc_canvas_write_png(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels);
+/* Save by file name: Canvas::write_to_file's `to_imgbuf().save(path)` (canvas.rs:80-84), where the `image` crate picks the
+ * codec from the extension. The extension is what follows the last '.' of the name's last component (after the last '/'),
+ * compared without regard to case; a component that starts with its only '.' (".png") has none, as in Rust's
+ * Path::extension. The table, one for every layer (host, device, Lua, Python, C++):
+ *   png                RTC_IMAGE_PNG       rtc_png_format's bytes of the RGB channels (3 channels, colour type 2)
+ *   jpg, jpeg          RTC_IMAGE_JPEG      rtc_jpeg_format's bytes at quality 75 (the crate's `save` default)
+ *   gif                RTC_IMAGE_GIF       rtc_gif_format's bytes for the one frame (what rtc_gif_writer writes for it)
+ *   ppm                RTC_IMAGE_PPM       rtc_canvas_format_ppm_rgb8's bytes (the P3 file of write_to_file_simple)
+ *   bmp                RTC_IMAGE_BMP       below
+ *   tga                RTC_IMAGE_TGA       below
+ *   tif, tiff          RTC_IMAGE_TIFF      below
+ *   ico                RTC_IMAGE_ICO       below
+ *   ff                 RTC_IMAGE_FARBFELD  below
+ *   pam                RTC_IMAGE_PAM       below
+ *   anything else, or no extension: RTC_ERR_UNSUPPORTED, and nothing is written.
+ * Input: `pixels` = height*width*channels bytes, channels 3 (Color::scale's rows, rtc_render_rgb8) or 4 (to_imgbuf's RGBA,
+ * rtc_render_rgba8). Every file is a function of the R, G, B bytes alone and stores alpha 255 where it has alpha (to_imgbuf
+ * stores nothing else), so the 3- and the 4-channel form of a frame give the same file, byte for byte. LAYOUT PARITY
+ * UNPINNED: the crate's encoders are not at hand, so byte parity with its files is not claimed; pixels are pinned (every
+ * format but JPEG, and GIF above 256 colours, is lossless: decoding gives back the R, G, B bytes with alpha 255). The new
+ * layouts (all integers little-endian unless stated; no field not listed is written):
+ *   BMP:  BITMAPFILEHEADER: "BM", file size (u32), 0 (u32), pixel offset 122 (u32). BITMAPV4HEADER: 108, width, height
+ *         (positive: rows stored bottom-up), planes 1 (u16), 32 bpp (u16), BI_BITFIELDS 3, pixel bytes 4*width*height,
+ *         resolution 0 and 0, colours used 0, important 0, masks R 0x00FF0000, G 0x0000FF00, B 0x000000FF, A 0xFF000000,
+ *         colour space 0x73524742 ("sRGB"), end points and gamma 0 (48 bytes). Pixels B,G,R,A, rows without padding.
+ *         Width and height 1..2^31-1; RTC_ERR_ARG when the file size does not fit in a u32.
+ *   TGA:  18 bytes: ID length 0, colour map type 0, image type 2, colour map spec 0 (5 bytes), origin 0,0 (u16 each), width,
+ *         height (u16), 32 bpp, descriptor 0x28 (8 alpha bits, top-left origin). Pixels B,G,R,A top row first; no ID, no
+ *         colour map, no footer. Width and height 1..65535.
+ *   TIFF: "II", 42, IFD offset 8; the IFD: 14 entries (u16 count, 12 bytes each, next-IFD offset 0) in tag order:
+ *         256 ImageWidth LONG, 257 ImageLength LONG, 258 BitsPerSample SHORT[4] = 8,8,8,8 (at 182), 259 Compression 1,
+ *         262 Photometric 2, 273 StripOffsets LONG[S], 277 SamplesPerPixel 4, 278 RowsPerStrip LONG R, 279 StripByteCounts
+ *         LONG[S], 282 XResolution RATIONAL 1/1 (at 190), 283 YResolution 1/1 (at 198), 284 PlanarConfiguration 1,
+ *         296 ResolutionUnit 1, 338 ExtraSamples 2 (unassociated alpha); SHORT values sit in the low half of the entry's
+ *         value field. R = max(1, floor(RTC_TIFF_STRIP_BYTES / (4*width))) rows per strip, S = ceil(height / R) strips, the
+ *         last strip holds the rest. S = 1: both arrays' one value is inline; S > 1: StripOffsets at 206, StripByteCounts at
+ *         206 + 4S. The strips follow the header (206 + (S > 1 ? 8S : 0) bytes) as one contiguous block of R,G,B,A rows,
+ *         top row first. Width and height >= 1; RTC_ERR_ARG when the file size does not fit in a u32.
+ *   ICO:  ICONDIR: 0, type 1, count 1 (u16 each); ICONDIRENTRY: width, height (one byte each, 0 = 256), colours 0,
+ *         reserved 0, planes 1, 32 bpp (u16 each), bytes of the PNG (u32), its offset 22 (u32); then rtc_png_format's file
+ *         of the RGBA frame (4 channels, colour type 6, alpha 255). Width and height 1..256.
+ *   farbfeld: "farbfeld", width, height (big-endian u32), then R,G,B,A of each pixel as big-endian u16 v * 257, top row first.
+ *   PAM:  "P7\nWIDTH w\nHEIGHT h\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n" (w, h in decimal), then R,G,B,A bytes.
+ *   PPM, farbfeld and PAM take any width and height >= 1 whose file size fits in 64 bits; PNG, JPEG and GIF keep their
+ *   own limits (1..65535).
+ * rtc_image_format_for_name: the table's format for `name` (RTC_ERR_UNSUPPORTED if none; RTC_ERR_ARG for NULL).
+ * rtc_image_format: the whole file of `format` — bytes needed (0 on bad arguments or an unknown format); writes at most cap.
+ * rtc_canvas_save: that file to `path`, the format from the name; RTC_ERR_UNSUPPORTED before anything is opened. Host. */
+enum {
+    RTC_IMAGE_PNG = 0, RTC_IMAGE_JPEG = 1, RTC_IMAGE_GIF = 2, RTC_IMAGE_PPM = 3, RTC_IMAGE_BMP = 4, RTC_IMAGE_TGA = 5,
+    RTC_IMAGE_TIFF = 6, RTC_IMAGE_ICO = 7, RTC_IMAGE_FARBFELD = 8, RTC_IMAGE_PAM = 9
+};
+enum { RTC_IMAGE_JPEG_QUALITY = 75, RTC_TIFF_STRIP_BYTES = 65536 };
+rtc_status  rtc_image_format_for_name(const char *name, uint32_t *format);
+size_t      rtc_image_format(uint32_t format, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                             uint8_t *buf, size_t cap);
+rtc_status  rtc_canvas_save(const char *path, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels);
 
 /* ==== [device] the hot path on one MI355X ========================================== */
 
@@ -648,6 +705,38 @@ void        rtc_png_encoder_destroy(rtc_png_encoder *e);
 enum { RTC_LUA_OUT_PNG = 3u };
 rtc_status  rtc_lua_program_render_png(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
                                        rtc_lua_file_fn fn, void *user, rtc_stats *stats);
+/* The save-by-name writer on the device: rtc_image_format's bytes for a frame already in device memory (csrc/rtc_image.hip);
+ * only the finished file crosses PCIe, in one copy behind its 8-byte length. BMP, TGA, TIFF, farbfeld and PAM are packed by
+ * one kernel (header computed on the host, written by the kernel with the pixels); ICO is the PNG chain (4 channels) behind
+ * its header; PNG, JPEG and GIF are their chains; PPM is the one text format, and its 3 bytes per pixel cross PCIe and are
+ * printed on the host (the P3 text is about four times as large). An encoder is bound to a context and owns its scratch,
+ * grow-only.
+ *   encode_device: `d_pixels` = height*width*channels bytes in device memory, channels 3 or 4, encoded as `format` on the
+ *     context's stream in order with what the caller put there before (after launches of a pipelined context:
+ *     rtc_context_fence first); blocks until the file is on the host.
+ *   render: Camera::render + set_gamma(gamma) + save: at gamma 1 through the rows path (3 channels), at any other gamma
+ *     through rtc_render_views_rgba8 (4 channels), into the encoder's scratch; the bytes equal rtc_image_format of
+ *     rtc_render_rgba8(..., gamma).
+ *   bytes: the last file (bytes needed; writes at most cap; 0 before the first); write: the same to `path`. [device] */
+typedef struct rtc_image_encoder rtc_image_encoder;
+rtc_status  rtc_image_encoder_create(rtc_context *ctx, rtc_image_encoder **out);
+rtc_status  rtc_image_encoder_encode_device(rtc_image_encoder *e, uint32_t format, const void *d_pixels, uint32_t width,
+                                            uint32_t height, uint32_t channels);
+rtc_status  rtc_image_encoder_render(rtc_image_encoder *e, uint32_t format, const rtc_world *w, const rtc_camera *cam,
+                                     uint32_t mode, uint32_t flags, float gamma);
+size_t      rtc_image_encoder_bytes(const rtc_image_encoder *e, uint8_t *buf, size_t cap);
+rtc_status  rtc_image_encoder_write(const rtc_image_encoder *e, const char *path);
+void        rtc_image_encoder_destroy(rtc_image_encoder *e);
+/* rtc_lua_program_render with every file of the script saved by its name: the same launches, lanes and job order as
+ * rtc_lua_program_render_gif; `fn` receives, per job —
+ *   RTC_LUA_OUT_FILE        a Render job: the whole file the save table gives its name (rtc_image_format's bytes of its
+ *                           rows), encoded on the GPU behind the render on the same lane (PPM: printed on the host);
+ *   RTC_LUA_OUT_GIF_RECORD  an AddFrame job: its GIF record, as rtc_lua_program_render_gif delivers it.
+ * Before the first launch every Render name is looked up (RTC_ERR_UNSUPPORTED) and every Render size checked against its
+ * format (RTC_ERR_ARG); then nothing is rendered. [device] */
+enum { RTC_LUA_OUT_FILE = 4u };
+rtc_status  rtc_lua_program_render_saved(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
+                                         rtc_lua_file_fn fn, void *user, rtc_stats *stats);
 /* Page-locked host memory for canvases handed to rtc_render: a canvas from rtc_host_alloc is
  * filled by one DMA at link speed, ordinary (pageable) memory goes through the runtime's bounce
  * buffers and is several times slower. What the reference would use for Canvas.pixels

@@ -17,7 +17,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, PATTERNS, STATUS_NAMES, declare)
 
@@ -523,6 +523,50 @@ class LuaProgram:
         _check(rc, "rtc_lua_program_render_png")
         return (paths, _stats_dict(st, True)) if with_stats else paths
 
+    def render_saved_files(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
+        """render_lua with every file saved as the reference saves it: each Render still under the base name the script gave
+        it, in the format its extension names (the save table of include/rtc.h: image_format_for_name), encoded on the GPU
+        behind its render (rtc_lua_program_render_saved); one GIF per StartAnimation call (+ ".gif" unless the name has it).
+        An unsupported name raises RtcError (RTC_ERR_UNSUPPORTED) before anything is rendered or written. Returns the paths:
+        stills in job order, then the animations in StartAnimation order (and the stats with `with_stats`)."""
+        out = Path(out_dir)
+        paths, anims, raised = [], {}, []
+
+        def cb(_user, jp, index, fmt, data, nbytes):
+            try:
+                j = jp.contents
+                name = Path((j.outfile or b"").decode(errors="replace")).name or f"job{index}"
+                if fmt == LUA_OUT_GIF_RECORD:
+                    a = anims.setdefault(j.animation, {"name": name, "size": (j.camera.hsize, j.camera.vsize), "records": []})
+                    if (j.camera.hsize, j.camera.vsize) != a["size"]:
+                        raise RtcError(4, "render_saved_files", f"frame {j.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
+                    a["records"].append(C.string_at(data, nbytes))
+                else:
+                    out.mkdir(parents=True, exist_ok=True)
+                    target = out / name
+                    target.write_bytes(C.string_at(data, nbytes))
+                    paths.append(target)
+                return 0
+            except BaseException as e:  # never unwind through the C frames
+                raised.append(e)
+                return 1
+
+        st = RtcStats()
+        fn = LUA_FILE_FN(cb)
+        try:
+            rc = lib().rtc_lua_program_render_saved(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
+            if raised:
+                raise raised[0]
+            _check(rc, "rtc_lua_program_render_saved")
+        finally:
+            for k in sorted(anims):
+                a = anims[k]
+                out.mkdir(parents=True, exist_ok=True)
+                target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
+                target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
+                paths.append(target)
+        return (paths, _stats_dict(st, True)) if with_stats else paths
+
     def close(self):
         if getattr(self, "_h", None):
             lib().rtc_lua_program_free(self._h)
@@ -776,6 +820,42 @@ def write_png_deflate(path, pixels: np.ndarray) -> None:
     a = _pixels_u8(pixels)
     _check(lib().rtc_canvas_write_png(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2]),
            "rtc_canvas_write_png")
+
+
+def image_format_for_name(name) -> int:
+    """The save table's format for a file name (rtc_image_format_for_name): one of IMAGE_FORMATS' values. The extension is
+    the last one of the name's last component, any case; an unsupported or missing one raises RtcError
+    (RTC_ERR_UNSUPPORTED)."""
+    f = C.c_uint32()
+    _check(lib().rtc_image_format_for_name(str(name).encode(), C.byref(f)), "rtc_image_format_for_name", str(name))
+    return f.value
+
+
+def _image_format(fmt) -> int:
+    return IMAGE_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+def image_encode(fmt, pixels: np.ndarray) -> bytes:
+    """The file of an (H, W, 3) or (H, W, 4) uint8 frame in format `fmt` (a name of IMAGE_FORMATS or its value), encoded on
+    the host (rtc_image_format): what Canvas::write_to_file saves for a name of that format, and what ImageEncoder makes on
+    the GPU. The 3- and the 4-channel form of a frame give the same bytes."""
+    a = _pixels_u8(pixels)
+    h, w, c = a.shape
+    f = _image_format(fmt)
+    P8 = C.POINTER(C.c_uint8)
+    need = lib().rtc_image_format(f, a.ctypes.data_as(P8), w, h, c, None, 0)
+    if need == 0:
+        raise RtcError(4, "rtc_image_format", f"format {fmt}, {w}x{h}x{c}")
+    buf = np.empty(need, dtype=np.uint8)
+    lib().rtc_image_format(f, a.ctypes.data_as(P8), w, h, c, buf.ctypes.data_as(P8), need)
+    return buf.tobytes()
+
+
+def save(path, pixels: np.ndarray) -> None:
+    """rtc_canvas_save: image_encode's bytes for the format `path`'s extension names, written to `path`."""
+    a = _pixels_u8(pixels)
+    _check(lib().rtc_canvas_save(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2]),
+           "rtc_canvas_save", str(path))
 
 
 def write_ppm(path, rgb: np.ndarray) -> None:
@@ -1164,6 +1244,51 @@ class PngEncoder:
     def close(self):
         if self._h:
             lib().rtc_png_encoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ImageEncoder:
+    """The save-by-name encoder on the GPU (rtc_image_encoder): frames already in device memory or rendered straight into
+    the encoder, any format of the save table; only the finished file crosses PCIe. The bytes equal image_encode's."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(lib().rtc_image_encoder_create(ctx._h, C.byref(self._h)), "rtc_image_encoder_create")
+        ctx._worlds.append(weakref.ref(self))   # closed with the context
+
+    def encode_device(self, fmt, d_ptr: int, width: int, height: int, channels: int = 3) -> bytes:
+        """Encode the height x width x channels uint8 frame at device address d_ptr as `fmt` (on the context's stream)."""
+        _check(lib().rtc_image_encoder_encode_device(self._h, _image_format(fmt), C.c_void_p(d_ptr), width, height, channels),
+               "rtc_image_encoder_encode_device", f"format {fmt}, {width}x{height}x{channels}")
+        return self.bytes()
+
+    def render(self, fmt, world: "DeviceWorld", cam: RtcCamera, gamma: float = 1.0, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> bytes:
+        """Camera::render + set_gamma(gamma) + write_to_file(name of format `fmt`), the frame never leaving the device."""
+        _check(lib().rtc_image_encoder_render(self._h, _image_format(fmt), world._h, C.byref(cam), mode, flags, gamma),
+               "rtc_image_encoder_render", f"format {fmt}")
+        return self.bytes()
+
+    def bytes(self) -> bytes:
+        need = lib().rtc_image_encoder_bytes(self._h, None, 0)
+        if need == 0:
+            return b""
+        buf = np.empty(need, dtype=np.uint8)
+        lib().rtc_image_encoder_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
+        return buf.tobytes()
+
+    def write(self, path) -> None:
+        _check(lib().rtc_image_encoder_write(self._h, str(path).encode()), "rtc_image_encoder_write")
+
+    def close(self):
+        if self._h:
+            lib().rtc_image_encoder_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -66,7 +66,11 @@ LUA_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32
 LUA_GIF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
 GIF_SEGMENT, GIF_DELAY_CS = 4096, 7
 LUA_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
-LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG = 0, 1, 2, 3
+LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE = 0, 1, 2, 3, 4
+IMAGE_FORMATS = {"png": 0, "jpeg": 1, "gif": 2, "ppm": 3, "bmp": 4, "tga": 5, "tiff": 6, "ico": 7, "farbfeld": 8, "pam": 9}
+(IMAGE_PNG, IMAGE_JPEG, IMAGE_GIF, IMAGE_PPM, IMAGE_BMP, IMAGE_TGA, IMAGE_TIFF, IMAGE_ICO, IMAGE_FARBFELD,
+ IMAGE_PAM) = range(10)
+IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES = 75, 65536
 PNG_SEGMENT, PNG_CHAIN = 32768, 8
 
 SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute force, object table staged in LDS (one tile)",
@@ -146,6 +150,16 @@ PROTOTYPES = {
     "rtc_png_encoder_write": (C.c_int32, [VP, C.c_char_p]),
     "rtc_png_encoder_destroy": (None, [VP]),
     "rtc_lua_program_render_png": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, LUA_FILE_FN, C.c_void_p, C.POINTER(RtcStats)]),
+    "rtc_image_format_for_name": (C.c_int32, [C.c_char_p, C.POINTER(U32)]),
+    "rtc_image_format": (C.c_size_t, [U32, C.POINTER(C.c_uint8), U32, U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_canvas_save": (C.c_int32, [C.c_char_p, C.POINTER(C.c_uint8), U32, U32, U32]),
+    "rtc_image_encoder_create": (C.c_int32, [VP, C.POINTER(VP)]),
+    "rtc_image_encoder_encode_device": (C.c_int32, [VP, U32, VP, U32, U32, U32]),
+    "rtc_image_encoder_render": (C.c_int32, [VP, U32, VP, C.POINTER(RtcCamera), U32, U32, C.c_float]),
+    "rtc_image_encoder_bytes": (C.c_size_t, [VP, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_image_encoder_write": (C.c_int32, [VP, C.c_char_p]),
+    "rtc_image_encoder_destroy": (None, [VP]),
+    "rtc_lua_program_render_saved": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, LUA_FILE_FN, C.c_void_p, C.POINTER(RtcStats)]),
     "rtc_scene_load_lua": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_scene_load_lua_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),

@@ -23,10 +23,12 @@
 #include <cctype>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include "rtc.h"
 #include "rtc_gif.h"
+#include "rtc_image.h"
 #include "rtc_internal.h"
 #include "rtc_jpeg.h"
 #include "rtc_png.h"
@@ -525,6 +527,24 @@ hipError_t drain_lanes(rtc_context *ctx) {
 
 } // namespace
 
+struct GifFrameScratch {
+    GifScratch sc;
+};
+
+GifFrameScratch *rtc_gif_scratch_new() { return new (std::nothrow) GifFrameScratch; }
+void rtc_gif_scratch_free(GifFrameScratch *g) {
+    if (!g) return;
+    g->sc.release();
+    delete g;
+}
+int rtc_gif_scratch_encode(GifFrameScratch *g, const void *d_rgb8, uint32_t width, uint32_t height, void *stream) {
+    if (!g || !d_rgb8 || width == 0 || height == 0 || width > 65535u || height > 65535u) return RTC_ERR_ARG;
+    return encode_frame(g->sc, static_cast<const uint8_t *>(d_rgb8), width, height, static_cast<hipStream_t>(stream));
+}
+const uint8_t *rtc_gif_scratch_record(const GifFrameScratch *g) { return g->sc.record; }
+size_t rtc_gif_scratch_record_cap(const GifFrameScratch *g) { return g->sc.record_cap; }
+const unsigned long long *rtc_gif_scratch_length(const GifFrameScratch *g) { return &g->sc.info->record_bytes; }
+
 struct rtc_gif_writer {
     rtc_context *ctx = nullptr;
     GifScratch sc;
@@ -643,10 +663,26 @@ bool ppm_name(const char *name) { // what render_to_files writes as a P3 file: "
 // rtc_lua_program_render's ring and lanes, with the GIF chain behind every AddFrame render (and, when `jpeg`, the JPEG chain
 // behind every Render job of a .jpg / .jpeg name) on the same lane and only the encoded length copied behind it; the bytes
 // themselves follow at delivery, on this call's copy stream. When `png`, the compressed PNG chain takes the place of the GIF
-// chain and of the rows for every job but a Render named .ppm (render_to_files' PNG files).
+// chain and of the rows for every job but a Render named .ppm (render_to_files' PNG files). When `saved`, every Render job's
+// file is made by the save table (rtc_image.hip's chain behind the render; PPM printed from the rows at delivery).
 rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, bool jpeg, int32_t quality,
-                              bool png, rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
+                              bool png, bool saved, rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
     if (!ctx || !prog || mode > RTC_MODE_RENDER_ASYNC) return RTC_ERR_ARG;
+    if (saved) // every name and size first: an unsupported one renders nothing
+        for (uint32_t i = 0, n = rtc_lua_program_jobs(prog); i < n; ++i) {
+            rtc_lua_job job;
+            const rtc_status js = rtc_lua_program_job(prog, i, &job);
+            if (js != RTC_OK) return js;
+            uint32_t f = 0;
+            if (job.kind == RTC_LUA_JOB_ADD_FRAME) {
+                if (job.camera.hsize == 0 || job.camera.vsize == 0 || job.camera.hsize > 65535u || job.camera.vsize > 65535u) return RTC_ERR_ARG;
+                continue;
+            }
+            const rtc_status fs = rtc_image_format_for_name(job.outfile, &f);
+            if (fs != RTC_OK) return fs == RTC_ERR_ARG ? RTC_ERR_UNSUPPORTED : fs;
+            if (!rtc_image_size_ok(f, job.camera.hsize, job.camera.vsize) || job.camera.hsize > 65535u || job.camera.vsize > 65535u)
+                return RTC_ERR_ARG;
+        }
     HIP_TRY(hipSetDevice(ctx->device));
     constexpr uint32_t RING = rtc_context::MAX_LANES + 1u;
     struct Slot {
@@ -657,9 +693,10 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         JpegScratch *jsc = nullptr;
         unsigned long long *h_len = nullptr; // page-locked: the JPEG data / PNG file length lands here
         PngScratch *psc = nullptr;
+        ImageScratch *isc = nullptr;
         hipEvent_t done = nullptr;
         bool pending = false, gif = false;
-        uint32_t format = RTC_LUA_OUT_RGB8;
+        uint32_t format = RTC_LUA_OUT_RGB8, image = 0; // image: a RTC_LUA_OUT_FILE's RTC_IMAGE_* format
         uint32_t job = 0;
     } ring[RING];
     hipStream_t copy = nullptr;
@@ -710,6 +747,20 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
             if (hipMemcpyAsync(sl.h, rtc_png_scratch_data(sl.psc), nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
                 hipStreamSynchronize(copy) != hipSuccess)
                 return RTC_ERR_DEVICE;
+        } else if (sl.format == RTC_LUA_OUT_FILE && sl.image == RTC_IMAGE_PPM) { // the rows are on the host: print them
+            std::vector<uint8_t> ppm(rtc_image_format(RTC_IMAGE_PPM, sl.h, job.camera.hsize, job.camera.vsize, 3, nullptr, 0));
+            rtc_image_format(RTC_IMAGE_PPM, sl.h, job.camera.hsize, job.camera.vsize, 3, ppm.data(), ppm.size());
+            if (ppm.empty()) return RTC_ERR_ARG;
+            if (fn && !stop && fn(user, &job, sl.job, sl.format, ppm.data(), ppm.size()) != 0) stop = true;
+            return RTC_OK;
+        } else if (sl.format == RTC_LUA_OUT_FILE) {
+            nbytes = (size_t)*sl.h_len;
+            if (nbytes == 0 || nbytes > rtc_image_scratch_out_cap(sl.isc)) return RTC_ERR_DEVICE;
+            const rtc_status hb = host_buf(sl, nbytes);
+            if (hb != RTC_OK) return hb;
+            if (hipMemcpyAsync(sl.h, rtc_image_scratch_data(sl.isc), nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
+                hipStreamSynchronize(copy) != hipSuccess)
+                return RTC_ERR_DEVICE;
         }
         if (fn && !stop && fn(user, &job, sl.job, sl.format, sl.h, nbytes) != 0) stop = true;
         return RTC_OK;
@@ -733,10 +784,14 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         const size_t bytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
         const bool add_frame = job.kind == RTC_LUA_JOB_ADD_FRAME;
         const bool gif = add_frame && !png;
+        uint32_t image = 0;
+        if (saved && !add_frame && (st = rtc_image_format_for_name(job.outfile, &image)) != RTC_OK) break;
         const uint32_t format = png ? ((add_frame || !ppm_name(job.outfile)) ? RTC_LUA_OUT_PNG : RTC_LUA_OUT_RGB8)
-                                    : gif ? RTC_LUA_OUT_GIF_RECORD : (jpeg && jpeg_name(job.outfile)) ? RTC_LUA_OUT_JPEG : RTC_LUA_OUT_RGB8;
-        const bool encoded = format != RTC_LUA_OUT_RGB8;
-        if (bytes == 0 || (encoded && (job.camera.hsize > 65535u || job.camera.vsize > 65535u))) { st = RTC_ERR_ARG; break; }
+                                : gif ? RTC_LUA_OUT_GIF_RECORD
+                                : saved ? RTC_LUA_OUT_FILE
+                                : (jpeg && jpeg_name(job.outfile)) ? RTC_LUA_OUT_JPEG : RTC_LUA_OUT_RGB8;
+        const bool rows_out = format == RTC_LUA_OUT_RGB8 || (format == RTC_LUA_OUT_FILE && image == RTC_IMAGE_PPM);
+        if (bytes == 0 || (!rows_out && (job.camera.hsize > 65535u || job.camera.vsize > 65535u))) { st = RTC_ERR_ARG; break; }
         Slot &sl = ring[i % RING];
         st = deliver(sl);
         if (st != RTC_OK || stop) break;
@@ -757,13 +812,17 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
             if (e != hipSuccess) { (void)hipGetLastError(); st = e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; break; }
             sl.cap = bytes;
         }
-        if (!encoded && (st = host_buf(sl, bytes)) != RTC_OK) break;
+        if (rows_out && (st = host_buf(sl, bytes)) != RTC_OK) break;
         if (format == RTC_LUA_OUT_JPEG) {
             if (!sl.jsc && !(sl.jsc = rtc_jpeg_scratch_new())) { st = RTC_ERR_NOMEM; break; }
             if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
         }
         if (format == RTC_LUA_OUT_PNG) {
             if (!sl.psc && !(sl.psc = rtc_png_scratch_new())) { st = RTC_ERR_NOMEM; break; }
+            if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
+        }
+        if (format == RTC_LUA_OUT_FILE && !rows_out) {
+            if (!sl.isc && !(sl.isc = rtc_image_scratch_new())) { st = RTC_ERR_NOMEM; break; }
             if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
         }
         if (!sl.h_info && hipHostMalloc(reinterpret_cast<void **>(&sl.h_info), sizeof(GifInfo), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
@@ -783,6 +842,10 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
             st = (rtc_status)rtc_png_scratch_encode(sl.psc, sl.d, job.camera.hsize, job.camera.vsize, 3, s);
             if (st != RTC_OK) break;
             if (hipMemcpyAsync(sl.h_len, rtc_png_scratch_length(sl.psc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
+        } else if (!rows_out) { // RTC_LUA_OUT_FILE
+            st = (rtc_status)rtc_image_scratch_encode(sl.isc, image, sl.d, job.camera.hsize, job.camera.vsize, 3, s);
+            if (st != RTC_OK) break;
+            if (hipMemcpyAsync(sl.h_len, rtc_image_scratch_length(sl.isc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
         } else if (hipMemcpyAsync(sl.h, sl.d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
             st = RTC_ERR_DEVICE;
             break;
@@ -791,6 +854,7 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         sl.pending = true;
         sl.gif = gif;
         sl.format = format;
+        sl.image = image;
         sl.job = i;
     }
     {
@@ -808,6 +872,7 @@ rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uin
         if (sl.h_len) (void)hipHostFree(sl.h_len);
         rtc_jpeg_scratch_free(sl.jsc);
         rtc_png_scratch_free(sl.psc);
+        rtc_image_scratch_free(sl.isc);
         sl.sc.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -835,16 +900,21 @@ int gif_fn_adapter(void *user, const rtc_lua_job *job, uint32_t job_index, uint3
 rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_gif_fn fn,
                                       void *user, rtc_stats *stats) {
     GifFnAdapter a{fn, user};
-    return render_lua_outputs(ctx, prog, mode, flags, false, 75, false, gif_fn_adapter, &a, stats);
+    return render_lua_outputs(ctx, prog, mode, flags, false, 75, false, false, gif_fn_adapter, &a, stats);
 }
 
 rtc_status rtc_lua_program_render_files(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, int32_t quality,
                                         rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
     if (quality < 1 || quality > 100) return RTC_ERR_ARG;
-    return render_lua_outputs(ctx, prog, mode, flags, true, quality, false, fn, user, stats);
+    return render_lua_outputs(ctx, prog, mode, flags, true, quality, false, false, fn, user, stats);
 }
 
 rtc_status rtc_lua_program_render_png(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_file_fn fn,
                                       void *user, rtc_stats *stats) {
-    return render_lua_outputs(ctx, prog, mode, flags, false, 75, true, fn, user, stats);
+    return render_lua_outputs(ctx, prog, mode, flags, false, 75, true, false, fn, user, stats);
+}
+
+rtc_status rtc_lua_program_render_saved(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_file_fn fn,
+                                        void *user, rtc_stats *stats) {
+    return render_lua_outputs(ctx, prog, mode, flags, false, RTC_IMAGE_JPEG_QUALITY, false, true, fn, user, stats);
 }

@@ -225,6 +225,22 @@ class Canvas { // canvas.rs:16-109
         rtc_canvas_to_rgba8(pixels.data(), width, height, gamma, rgba.data());
         check(rtc_canvas_write_jpeg(file_name.c_str(), rgba.data(), width, height, 4, quality), where);
     }
+    // Canvas::write_to_file with every codec of the save table (include/rtc.h, rtc_canvas_save): png, jpg / jpeg (quality
+    // 75), gif, ppm, bmp, tga, tif / tiff, ico, ff, pam by the name's last extension, any case; anything else panics with
+    // RTC_ERR_UNSUPPORTED and writes nothing. The same frame and gamma rules as write_to_file.
+    void save(const std::string &file_name) const {
+        const char *where = "Canvas::save";
+        if (is_imgbuf()) {
+            if (gamma != rgba8_gamma)
+                throw Panic(RTC_ERR_ARG, "Canvas::save(" + file_name + "): gamma was changed after Camera::render_rgba8 made this frame");
+            check(rtc_canvas_save(file_name.c_str(), rgba8.data(), width, height, 4), where);
+            return;
+        }
+        if (is_quantised()) { check(rtc_canvas_save(file_name.c_str(), rgb8.data(), width, height, 3), where); return; }
+        std::vector<uint8_t> rgba(static_cast<size_t>(width) * height * 4);
+        rtc_canvas_to_rgba8(pixels.data(), width, height, gamma, rgba.data());
+        check(rtc_canvas_save(file_name.c_str(), rgba.data(), width, height, 4), where);
+    }
     float gamma = 1.0f; // canvas.rs:30
   private:
     double *at(uint32_t x, uint32_t y) {
