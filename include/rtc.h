@@ -705,10 +705,11 @@ void        rtc_png_encoder_destroy(rtc_png_encoder *e);
 enum { RTC_LUA_OUT_PNG = 3u };
 rtc_status  rtc_lua_program_render_png(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags,
                                        rtc_lua_file_fn fn, void *user, rtc_stats *stats);
-/* The save-by-name writer on the device: rtc_image_format's bytes for a frame already in device memory (csrc/rtc_image.hip);
- * only the finished file crosses PCIe, in one copy behind its 8-byte length. BMP, TGA, TIFF, farbfeld and PAM are packed by
- * one kernel (header computed on the host, written by the kernel with the pixels); ICO is the PNG chain (4 channels) behind
- * its header; PNG, JPEG and GIF are their chains; PPM is the one text format, and its 3 bytes per pixel cross PCIe and are
+/* The save-by-name writer on the device: rtc_image_format's bytes for a frame already in device memory (csrc/rtc_image.hip,
+ * csrc/rtc_encode.cpp); only what the device made crosses PCIe, in one copy behind its 8-byte length. BMP, TGA, TIFF,
+ * farbfeld and PAM are packed by one kernel (header computed on the host, written by the kernel with the pixels); ICO is the
+ * PNG chain (4 channels) behind its header; PNG, JPEG and GIF are their chains (the JPEG and GIF headers, the GIF trailer
+ * and the ICO header are written on the host); PPM is the one text format, and its 3 bytes per pixel cross PCIe and are
  * printed on the host (the P3 text is about four times as large). An encoder is bound to a context and owns its scratch,
  * grow-only.
  *   encode_device: `d_pixels` = height*width*channels bytes in device memory, channels 3 or 4, encoded as `format` on the

@@ -269,6 +269,27 @@ class LuaJob:
             self.world.shapes.append(s)
 
 
+class _Animations:
+    """The GIF files of a run: each StartAnimation's records collected in order, written as header + records + 0x3B."""
+
+    def __init__(self, where: str):
+        self.where, self.anims = where, {}
+
+    def add(self, job, name: str, record: bytes) -> None:
+        a = self.anims.setdefault(job.animation, {"name": name, "size": (job.camera.hsize, job.camera.vsize), "records": []})
+        if (job.camera.hsize, job.camera.vsize) != a["size"]:
+            raise RtcError(4, self.where, f"frame {job.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
+        a["records"].append(record)
+
+    def write(self, out: Path, paths: list) -> None:
+        for k in sorted(self.anims):
+            a = self.anims[k]
+            out.mkdir(parents=True, exist_ok=True)
+            target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
+            target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
+            paths.append(target)
+
+
 class LuaProgram:
     """A scene script of the reference's Lua front-end, interpreted (rtc_lua_run: csrc/host_lua.cpp carries its own
     interpreter of the Lua 5.3 subset those scripts use): `jobs` = its Render / AddFrame calls in order, `output` = what it
@@ -297,34 +318,41 @@ class LuaProgram:
     def jobs(self):
         return [self.job(i) for i in range(len(self))]
 
-    def render(self, ctx: "Context", on_frame=None, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
-        """rtc_lua_program_render: returns the list of (vsize, hsize, 3) uint8 frames in job order — or, with `on_frame`
-        (called as on_frame(job_index, frame, outfile, kind); a true return value stops), nothing is kept."""
-        frames = []
+    def _run(self, ctx: "Context", entry: str, fn_type, cb, args, with_stats: bool):
+        """Run rtc_lua_program_<entry>(ctx, prog, *args, fn, NULL, stats) with `cb` (the C callback's arguments after
+        `user`) as its callback: a true return value stops the run; an exception stops it and is raised here."""
         raised = []
 
-        def cb(_user, jp, index, rgb8):
+        def trampoline(_user, *a):
             try:
-                cam = jp.contents.camera
-                frame = np.ctypeslib.as_array(rgb8, shape=(cam.vsize, cam.hsize, 3))
-                if on_frame is None:
-                    frames.append(frame.copy())
-                    return 0
-                j = jp.contents
-                return 1 if on_frame(index, frame, (j.outfile or b"").decode(errors="replace"), "AddFrame" if j.kind == 1 else "Render") else 0
+                return 1 if cb(*a) else 0
             except BaseException as e:  # never unwind through the C frames
                 raised.append(e)
                 return 1
 
         st = RtcStats()
-        fn = LUA_FRAME_FN(cb)
-        rc = lib().rtc_lua_program_render(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
+        rc = getattr(lib(), entry)(ctx._h, self._h, *args, fn_type(trampoline), None, C.byref(st) if with_stats else None)
         if raised:
             raise raised[0]
-        _check(rc, "rtc_lua_program_render")
-        if with_stats:
-            return frames, _stats_dict(st, True)
-        return frames
+        _check(rc, entry)
+        return _stats_dict(st, True) if with_stats else None
+
+    def render(self, ctx: "Context", on_frame=None, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
+        """rtc_lua_program_render: returns the list of (vsize, hsize, 3) uint8 frames in job order — or, with `on_frame`
+        (called as on_frame(job_index, frame, outfile, kind); a true return value stops), nothing is kept."""
+        frames = []
+
+        def cb(jp, index, rgb8):
+            cam = jp.contents.camera
+            frame = np.ctypeslib.as_array(rgb8, shape=(cam.vsize, cam.hsize, 3))
+            if on_frame is None:
+                frames.append(frame.copy())
+                return False
+            j = jp.contents
+            return on_frame(index, frame, (j.outfile or b"").decode(errors="replace"), "AddFrame" if j.kind == 1 else "Render")
+
+        st = self._run(ctx, "rtc_lua_program_render", LUA_FRAME_FN, cb, (mode, flags), with_stats)
+        return (frames, st) if with_stats else frames
 
     def render_to_files(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> list:
         """render_lua with the files written: Render(world, camera, "x.png") -> out_dir/x.png, "x.ppm" -> the P3 file of
@@ -357,28 +385,16 @@ class LuaProgram:
         """rtc_lua_program_render_gif: every job rendered as by render(); on_frame(job_index, data, outfile, kind) gets an
         AddFrame job's GIF record (bytes, quantised and LZW-coded on the GPU) or a Render job's (vsize, hsize, 3) uint8 frame.
         A true return value stops the run."""
-        raised = []
+        def cb(jp, index, data, nbytes):
+            j = jp.contents
+            outfile = (j.outfile or b"").decode(errors="replace")
+            if j.kind == 1:
+                payload = C.string_at(data, nbytes)
+            else:
+                payload = np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3))
+            return on_frame(index, payload, outfile, "AddFrame" if j.kind == 1 else "Render")
 
-        def cb(_user, jp, index, data, nbytes):
-            try:
-                j = jp.contents
-                outfile = (j.outfile or b"").decode(errors="replace")
-                if j.kind == 1:
-                    payload = C.string_at(data, nbytes)
-                else:
-                    payload = np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3))
-                return 1 if on_frame(index, payload, outfile, "AddFrame" if j.kind == 1 else "Render") else 0
-            except BaseException as e:  # never unwind through the C frames
-                raised.append(e)
-                return 1
-
-        st = RtcStats()
-        fn = LUA_GIF_FN(cb)
-        rc = lib().rtc_lua_program_render_gif(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
-        if raised:
-            raise raised[0]
-        _check(rc, "rtc_lua_program_render_gif")
-        return _stats_dict(st, True) if with_stats else None
+        return self._run(ctx, "rtc_lua_program_render_gif", LUA_GIF_FN, cb, (mode, flags), with_stats)
 
     def render_animations(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0, on_frame=None) -> list:
         """render_lua with the reference's files: one out_dir/<basename>.gif per StartAnimation call (frames encoded on the
@@ -387,17 +403,13 @@ class LuaProgram:
         far are still written). Returns the paths: stills in job order, then the animations in StartAnimation order."""
         out = Path(out_dir)
         out.mkdir(parents=True, exist_ok=True)
-        paths, anims = [], {}
+        paths, anims = [], _Animations("render_animations")
 
         def cb(index, data, outfile, kind):
             stop = bool(on_frame(index, data, outfile, kind)) if on_frame is not None else False
             name = Path(outfile).name or f"job{index}"
             if kind == "AddFrame":
-                j = self.job(index)
-                a = anims.setdefault(j.animation, {"name": name, "size": (j.camera.hsize, j.camera.vsize), "records": []})
-                if (j.camera.hsize, j.camera.vsize) != a["size"]:
-                    raise RtcError(4, "render_animations", f"frame {j.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
-                a["records"].append(data)
+                anims.add(self.job(index), name, data)
             else:
                 target = out / name if name.lower().endswith((".png", ".ppm")) else out / (name + ".png")
                 if target.suffix.lower() == ".ppm":
@@ -410,11 +422,7 @@ class LuaProgram:
         try:
             self.render_gif(ctx, cb, mode=mode, flags=flags)
         finally:
-            for k in sorted(anims):
-                a = anims[k]
-                target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
-                target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
-                paths.append(target)
+            anims.write(out, paths)
         return paths
 
     def render_files(self, ctx: "Context", on_output, quality: int = 75, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
@@ -423,29 +431,18 @@ class LuaProgram:
         by `fmt`, an AddFrame job's GIF record ("gif", bytes), a .jpg / .jpeg Render job's whole JPEG file at `quality`
         ("jpeg", bytes, encoded on the GPU) or any other Render job's (vsize, hsize, 3) uint8 rows ("rgb8").
         A true return value stops the run."""
-        raised = []
         names = {LUA_OUT_RGB8: "rgb8", LUA_OUT_GIF_RECORD: "gif", LUA_OUT_JPEG: "jpeg"}
 
-        def cb(_user, jp, index, fmt, data, nbytes):
-            try:
-                j = jp.contents
-                outfile = (j.outfile or b"").decode(errors="replace")
-                if fmt == LUA_OUT_RGB8:
-                    payload = np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3))
-                else:
-                    payload = C.string_at(data, nbytes)
-                return 1 if on_output(index, names[fmt], payload, outfile, "AddFrame" if j.kind == 1 else "Render") else 0
-            except BaseException as e:  # never unwind through the C frames
-                raised.append(e)
-                return 1
+        def cb(jp, index, fmt, data, nbytes):
+            j = jp.contents
+            outfile = (j.outfile or b"").decode(errors="replace")
+            if fmt == LUA_OUT_RGB8:
+                payload = np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3))
+            else:
+                payload = C.string_at(data, nbytes)
+            return on_output(index, names[fmt], payload, outfile, "AddFrame" if j.kind == 1 else "Render")
 
-        st = RtcStats()
-        fn = LUA_FILE_FN(cb)
-        rc = lib().rtc_lua_program_render_files(ctx._h, self._h, mode, flags, quality, fn, None, C.byref(st) if with_stats else None)
-        if raised:
-            raise raised[0]
-        _check(rc, "rtc_lua_program_render_files")
-        return _stats_dict(st, True) if with_stats else None
+        return self._run(ctx, "rtc_lua_program_render_files", LUA_FILE_FN, cb, (mode, flags, quality), with_stats)
 
     def render_reference_files(self, ctx: "Context", out_dir, quality: int = 75, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> list:
         """render_lua with every file under the name the script gave it (only its base name is used): ".jpg" / ".jpeg"
@@ -454,16 +451,12 @@ class LuaProgram:
         Returns the paths: stills in job order, then the animations in StartAnimation order."""
         out = Path(out_dir)
         out.mkdir(parents=True, exist_ok=True)
-        paths, anims = [], {}
+        paths, anims = [], _Animations("render_reference_files")
 
         def cb(index, fmt, data, outfile, kind):
             name = Path(outfile).name or f"job{index}"
             if fmt == "gif":
-                j = self.job(index)
-                a = anims.setdefault(j.animation, {"name": name, "size": (j.camera.hsize, j.camera.vsize), "records": []})
-                if (j.camera.hsize, j.camera.vsize) != a["size"]:
-                    raise RtcError(4, "render_reference_files", f"frame {j.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
-                a["records"].append(data)
+                anims.add(self.job(index), name, data)
                 return False
             if fmt == "jpeg":
                 target = out / name
@@ -480,11 +473,7 @@ class LuaProgram:
         try:
             self.render_files(ctx, cb, quality=quality, mode=mode, flags=flags)
         finally:
-            for k in sorted(anims):
-                a = anims[k]
-                target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
-                target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
-                paths.append(target)
+            anims.write(out, paths)
         return paths
 
     def render_png_files(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
@@ -493,35 +482,26 @@ class LuaProgram:
         writes them. Returns the paths in job order (and the stats with `with_stats`)."""
         out = Path(out_dir)
         out.mkdir(parents=True, exist_ok=True)
-        paths, raised = [], []
+        paths = []
 
-        def cb(_user, jp, index, fmt, data, nbytes):
-            try:
-                j = jp.contents
-                name = Path((j.outfile or b"").decode(errors="replace")).name or f"job{index}"
-                if j.kind == 1:
-                    target = out / f"{name}.{j.frame:04d}.png"
-                elif name.lower().endswith((".png", ".ppm")):
-                    target = out / name
-                else:
-                    target = out / (name + ".png")
-                if fmt == LUA_OUT_PNG:
-                    target.write_bytes(C.string_at(data, nbytes))
-                else:
-                    write_ppm_rgb8(target, np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3)))
-                paths.append(target)
-                return 0
-            except BaseException as e:  # never unwind through the C frames
-                raised.append(e)
-                return 1
+        def cb(jp, index, fmt, data, nbytes):
+            j = jp.contents
+            name = Path((j.outfile or b"").decode(errors="replace")).name or f"job{index}"
+            if j.kind == 1:
+                target = out / f"{name}.{j.frame:04d}.png"
+            elif name.lower().endswith((".png", ".ppm")):
+                target = out / name
+            else:
+                target = out / (name + ".png")
+            if fmt == LUA_OUT_PNG:
+                target.write_bytes(C.string_at(data, nbytes))
+            else:
+                write_ppm_rgb8(target, np.ctypeslib.as_array(data, shape=(j.camera.vsize, j.camera.hsize, 3)))
+            paths.append(target)
+            return False
 
-        st = RtcStats()
-        fn = LUA_FILE_FN(cb)
-        rc = lib().rtc_lua_program_render_png(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
-        if raised:
-            raise raised[0]
-        _check(rc, "rtc_lua_program_render_png")
-        return (paths, _stats_dict(st, True)) if with_stats else paths
+        st = self._run(ctx, "rtc_lua_program_render_png", LUA_FILE_FN, cb, (mode, flags), with_stats)
+        return (paths, st) if with_stats else paths
 
     def render_saved_files(self, ctx: "Context", out_dir, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False):
         """render_lua with every file saved as the reference saves it: each Render still under the base name the script gave
@@ -530,42 +510,25 @@ class LuaProgram:
         An unsupported name raises RtcError (RTC_ERR_UNSUPPORTED) before anything is rendered or written. Returns the paths:
         stills in job order, then the animations in StartAnimation order (and the stats with `with_stats`)."""
         out = Path(out_dir)
-        paths, anims, raised = [], {}, []
+        paths, anims = [], _Animations("render_saved_files")
 
-        def cb(_user, jp, index, fmt, data, nbytes):
-            try:
-                j = jp.contents
-                name = Path((j.outfile or b"").decode(errors="replace")).name or f"job{index}"
-                if fmt == LUA_OUT_GIF_RECORD:
-                    a = anims.setdefault(j.animation, {"name": name, "size": (j.camera.hsize, j.camera.vsize), "records": []})
-                    if (j.camera.hsize, j.camera.vsize) != a["size"]:
-                        raise RtcError(4, "render_saved_files", f"frame {j.frame} of {name} is not {a['size'][0]}x{a['size'][1]}")
-                    a["records"].append(C.string_at(data, nbytes))
-                else:
-                    out.mkdir(parents=True, exist_ok=True)
-                    target = out / name
-                    target.write_bytes(C.string_at(data, nbytes))
-                    paths.append(target)
-                return 0
-            except BaseException as e:  # never unwind through the C frames
-                raised.append(e)
-                return 1
-
-        st = RtcStats()
-        fn = LUA_FILE_FN(cb)
-        try:
-            rc = lib().rtc_lua_program_render_saved(ctx._h, self._h, mode, flags, fn, None, C.byref(st) if with_stats else None)
-            if raised:
-                raise raised[0]
-            _check(rc, "rtc_lua_program_render_saved")
-        finally:
-            for k in sorted(anims):
-                a = anims[k]
+        def cb(jp, index, fmt, data, nbytes):
+            j = jp.contents
+            name = Path((j.outfile or b"").decode(errors="replace")).name or f"job{index}"
+            if fmt == LUA_OUT_GIF_RECORD:
+                anims.add(j, name, C.string_at(data, nbytes))
+            else:
                 out.mkdir(parents=True, exist_ok=True)
-                target = out / (a["name"] if a["name"].lower().endswith(".gif") else a["name"] + ".gif")
-                target.write_bytes(gif_file_header(*a["size"]) + b"".join(a["records"]) + b"\x3b")
+                target = out / name
+                target.write_bytes(C.string_at(data, nbytes))
                 paths.append(target)
-        return (paths, _stats_dict(st, True)) if with_stats else paths
+            return False
+
+        try:
+            st = self._run(ctx, "rtc_lua_program_render_saved", LUA_FILE_FN, cb, (mode, flags), with_stats)
+        finally:
+            anims.write(out, paths)
+        return (paths, st) if with_stats else paths
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1124,38 +1087,33 @@ class DeviceWorld:
         return (rgb, hits) if want_hits else rgb
 
 
-class GifWriter:
-    """An animated GIF encoded on the GPU (rtc_gif_writer): frames already in device memory or rendered straight into the
-    writer; only each frame's compressed record crosses PCIe. The bytes equal gif_encode's for the same frames."""
+class _Encoder:
+    """What the device encoders share: an rtc_<kind>_* object bound to a context (closed with it), its file's bytes."""
+    _kind = ""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
         self._h = C.c_void_p()
-        _check(lib().rtc_gif_writer_create(ctx._h, C.byref(self._h)), "rtc_gif_writer_create")
+        _check(self._fn("create")(ctx._h, C.byref(self._h)), f"rtc_{self._kind}_create")
         ctx._worlds.append(weakref.ref(self))   # closed with the context
 
-    def append_device(self, d_ptr: int, width: int, height: int) -> None:
-        """Append the height x width x 3 uint8 frame at device address d_ptr (enqueued on the context's stream)."""
-        _check(lib().rtc_gif_writer_append_device(self._h, C.c_void_p(d_ptr), width, height), "rtc_gif_writer_append_device")
-
-    def render(self, world: "DeviceWorld", cam: RtcCamera, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
-        """Render `cam` on the device and append the frame without copying it to the host."""
-        _check(lib().rtc_gif_writer_render(self._h, world._h, C.byref(cam), mode, flags), "rtc_gif_writer_render")
+    def _fn(self, name: str):
+        return getattr(lib(), f"rtc_{self._kind}_{name}")
 
     def bytes(self) -> bytes:
-        need = lib().rtc_gif_writer_bytes(self._h, None, 0)
+        need = self._fn("bytes")(self._h, None, 0)
         if need == 0:
             return b""
         buf = np.empty(need, dtype=np.uint8)
-        lib().rtc_gif_writer_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
+        self._fn("bytes")(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
         return buf.tobytes()
 
     def write(self, path) -> None:
-        _check(lib().rtc_gif_writer_write(self._h, str(path).encode()), "rtc_gif_writer_write")
+        _check(self._fn("write")(self._h, str(path).encode()), f"rtc_{self._kind}_write")
 
     def close(self):
         if self._h:
-            lib().rtc_gif_writer_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -1165,15 +1123,24 @@ class GifWriter:
             pass
 
 
-class JpegEncoder:
+class GifWriter(_Encoder):
+    """An animated GIF encoded on the GPU (rtc_gif_writer): frames already in device memory or rendered straight into the
+    writer; only each frame's compressed record crosses PCIe. The bytes equal gif_encode's for the same frames."""
+    _kind = "gif_writer"
+
+    def append_device(self, d_ptr: int, width: int, height: int) -> None:
+        """Append the height x width x 3 uint8 frame at device address d_ptr (enqueued on the context's stream)."""
+        _check(lib().rtc_gif_writer_append_device(self._h, C.c_void_p(d_ptr), width, height), "rtc_gif_writer_append_device")
+
+    def render(self, world: "DeviceWorld", cam: RtcCamera, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+        """Render `cam` on the device and append the frame without copying it to the host."""
+        _check(lib().rtc_gif_writer_render(self._h, world._h, C.byref(cam), mode, flags), "rtc_gif_writer_render")
+
+
+class JpegEncoder(_Encoder):
     """A JPEG encoder on the GPU (rtc_jpeg_encoder): frames already in device memory or rendered straight into the encoder;
     only the finished file crosses PCIe. The bytes equal jpeg_encode's for the same pixels."""
-
-    def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self._h = C.c_void_p()
-        _check(lib().rtc_jpeg_encoder_create(ctx._h, C.byref(self._h)), "rtc_jpeg_encoder_create")
-        ctx._worlds.append(weakref.ref(self))   # closed with the context
+    _kind = "jpeg_encoder"
 
     def encode_device(self, d_ptr: int, width: int, height: int, channels: int = 3, quality: int = 75) -> bytes:
         """Encode the height x width x channels uint8 frame at device address d_ptr (enqueued on the context's stream)."""
@@ -1187,38 +1154,11 @@ class JpegEncoder:
         _check(lib().rtc_jpeg_encoder_render(self._h, world._h, C.byref(cam), mode, flags, gamma, quality), "rtc_jpeg_encoder_render")
         return self.bytes()
 
-    def bytes(self) -> bytes:
-        need = lib().rtc_jpeg_encoder_bytes(self._h, None, 0)
-        if need == 0:
-            return b""
-        buf = np.empty(need, dtype=np.uint8)
-        lib().rtc_jpeg_encoder_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
-        return buf.tobytes()
 
-    def write(self, path) -> None:
-        _check(lib().rtc_jpeg_encoder_write(self._h, str(path).encode()), "rtc_jpeg_encoder_write")
-
-    def close(self):
-        if self._h:
-            lib().rtc_jpeg_encoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PngEncoder:
+class PngEncoder(_Encoder):
     """A compressed PNG encoder on the GPU (rtc_png_encoder): frames already in device memory or rendered straight into the
     encoder; only the finished file crosses PCIe. The bytes equal png_encode's for the same pixels."""
-
-    def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self._h = C.c_void_p()
-        _check(lib().rtc_png_encoder_create(ctx._h, C.byref(self._h)), "rtc_png_encoder_create")
-        ctx._worlds.append(weakref.ref(self))   # closed with the context
+    _kind = "png_encoder"
 
     def encode_device(self, d_ptr: int, width: int, height: int, channels: int = 3) -> bytes:
         """Encode the height x width x channels uint8 frame at device address d_ptr (enqueued on the context's stream)."""
@@ -1230,38 +1170,11 @@ class PngEncoder:
         _check(lib().rtc_png_encoder_render(self._h, world._h, C.byref(cam), mode, flags, gamma), "rtc_png_encoder_render")
         return self.bytes()
 
-    def bytes(self) -> bytes:
-        need = lib().rtc_png_encoder_bytes(self._h, None, 0)
-        if need == 0:
-            return b""
-        buf = np.empty(need, dtype=np.uint8)
-        lib().rtc_png_encoder_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
-        return buf.tobytes()
 
-    def write(self, path) -> None:
-        _check(lib().rtc_png_encoder_write(self._h, str(path).encode()), "rtc_png_encoder_write")
-
-    def close(self):
-        if self._h:
-            lib().rtc_png_encoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ImageEncoder:
+class ImageEncoder(_Encoder):
     """The save-by-name encoder on the GPU (rtc_image_encoder): frames already in device memory or rendered straight into
     the encoder, any format of the save table; only the finished file crosses PCIe. The bytes equal image_encode's."""
-
-    def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self._h = C.c_void_p()
-        _check(lib().rtc_image_encoder_create(ctx._h, C.byref(self._h)), "rtc_image_encoder_create")
-        ctx._worlds.append(weakref.ref(self))   # closed with the context
+    _kind = "image_encoder"
 
     def encode_device(self, fmt, d_ptr: int, width: int, height: int, channels: int = 3) -> bytes:
         """Encode the height x width x channels uint8 frame at device address d_ptr as `fmt` (on the context's stream)."""
@@ -1274,28 +1187,6 @@ class ImageEncoder:
         _check(lib().rtc_image_encoder_render(self._h, _image_format(fmt), world._h, C.byref(cam), mode, flags, gamma),
                "rtc_image_encoder_render", f"format {fmt}")
         return self.bytes()
-
-    def bytes(self) -> bytes:
-        need = lib().rtc_image_encoder_bytes(self._h, None, 0)
-        if need == 0:
-            return b""
-        buf = np.empty(need, dtype=np.uint8)
-        lib().rtc_image_encoder_bytes(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), need)
-        return buf.tobytes()
-
-    def write(self, path) -> None:
-        _check(lib().rtc_image_encoder_write(self._h, str(path).encode()), "rtc_image_encoder_write")
-
-    def close(self):
-        if self._h:
-            lib().rtc_image_encoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def host_canvas_rgb8(vsize: int, hsize: int) -> np.ndarray:

@@ -1,6 +1,6 @@
 // rtc_gif.hip — [device] the GIF writer of include/rtc.h on gfx950: distinct-colour bitmap, bin histogram, median cut,
-// nearest-entry mapping and segmented LZW for a frame already in device memory, then the writer object and the Lua
-// AddFrame loop that use them. host_gif.cpp states the same bytes on the host.
+// nearest-entry mapping and segmented LZW for a frame already in device memory: one frame's record (rtc_encode.h).
+// host_gif.cpp states the same bytes on the host.
 //
 // Kernels of one frame, in stream order (all on the stream of the frame's render):
 //   k_gif_scan_pixels   pixel pass: presence bit of each 24-bit colour (global, tested before the atomic) and the
@@ -20,18 +20,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cctype>
-#include <cstdio>
 #include <cstring>
 #include <new>
-#include <vector>
 
 #include "rtc.h"
+#include "rtc_encode.h"
 #include "rtc_gif.h"
-#include "rtc_image.h"
-#include "rtc_internal.h"
-#include "rtc_jpeg.h"
-#include "rtc_png.h"
 
 namespace {
 
@@ -438,6 +432,8 @@ __global__ __launch_bounds__(256) void k_gif_pack(const uint8_t *seg, const unsi
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
+} // namespace
+
 struct GifScratch {
     size_t px_cap = 0;          // pixels the buffers below are sized for
     uint8_t *block = nullptr;   // one allocation: the parts cleared per frame first
@@ -490,11 +486,12 @@ struct GifScratch {
     }
 };
 
-// Enqueue the whole chain for a width x height frame at d_rgb8 on `s`; the record is then at sc.record, its length in
-// sc.info->record_bytes.
-rtc_status encode_frame(GifScratch &sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s) {
+// The whole chain for a width x height frame at d_rgb8 on `s`; the body is the frame's record (not the file), its length
+// info->record_bytes.
+rtc_status rtc_gif_enqueue(GifScratch *&sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s, RtcEncoded *e) {
+    if (!sc && !(sc = new (std::nothrow) GifScratch)) return RTC_ERR_NOMEM;
     const size_t n = (size_t)width * height;
-    const rtc_status r = sc.reserve(n);
+    const rtc_status r = sc->reserve(n);
     if (r != RTC_OK) return r;
     const uint32_t nseg = GifScratch::segments(n);
     const size_t px_threads = (n + PX_PER_THREAD - 1) / PX_PER_THREAD;
@@ -502,419 +499,26 @@ rtc_status encode_frame(GifScratch &sc, const uint8_t *d_rgb8, uint32_t width, u
     const uint32_t grid_sum = (uint32_t)std::min<size_t>(1024, (px_threads + 255) / 256);
     const uint32_t grid_map = (uint32_t)std::min<size_t>(2048, ((n + 3) / 4 + 255) / 256);
     const uint32_t grid_pack = (uint32_t)std::min<size_t>(2048, (nseg * (size_t)RTC_GIF_SEG_BYTES + 255) / 256);
-    HIP_TRY(hipMemsetAsync(sc.block, 0, sc.clear_bytes, s));
-    hipLaunchKernelGGL(k_gif_scan_pixels, dim3(grid_px), dim3(1024), 0, s, d_rgb8, n, sc.bitmap, sc.cnt);
-    hipLaunchKernelGGL(k_gif_bitmap_count, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc.bitmap, sc.blockcnt);
-    hipLaunchKernelGGL(k_gif_exact, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc.bitmap, sc.blockcnt, sc.pal32, sc.info);
-    hipLaunchKernelGGL(k_gif_median_cut, dim3(1), dim3(1024), 0, s, sc.cnt, sc.info, sc.lut);
-    hipLaunchKernelGGL(k_gif_box_sums, dim3(grid_sum), dim3(256), 0, s, d_rgb8, n, sc.info, sc.lut, sc.boxsum);
-    hipLaunchKernelGGL(k_gif_map, dim3(grid_map), dim3(256), 0, s, d_rgb8, n, sc.info, sc.pal32, sc.boxsum, sc.idx, sc.record);
-    hipLaunchKernelGGL(k_gif_lzw, dim3(nseg), dim3(64), 0, s, sc.idx, n, sc.seg, sc.seglen);
-    hipLaunchKernelGGL(k_gif_offsets, dim3(1), dim3(256), 0, s, sc.seglen, nseg, sc.segoff, sc.info, sc.record, width, height);
-    hipLaunchKernelGGL(k_gif_pack, dim3(grid_pack), dim3(256), 0, s, sc.seg, sc.segoff, nseg, sc.info, sc.record);
+    HIP_TRY(hipMemsetAsync(sc->block, 0, sc->clear_bytes, s));
+    hipLaunchKernelGGL(k_gif_scan_pixels, dim3(grid_px), dim3(1024), 0, s, d_rgb8, n, sc->bitmap, sc->cnt);
+    hipLaunchKernelGGL(k_gif_bitmap_count, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc->bitmap, sc->blockcnt);
+    hipLaunchKernelGGL(k_gif_exact, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc->bitmap, sc->blockcnt, sc->pal32, sc->info);
+    hipLaunchKernelGGL(k_gif_median_cut, dim3(1), dim3(1024), 0, s, sc->cnt, sc->info, sc->lut);
+    hipLaunchKernelGGL(k_gif_box_sums, dim3(grid_sum), dim3(256), 0, s, d_rgb8, n, sc->info, sc->lut, sc->boxsum);
+    hipLaunchKernelGGL(k_gif_map, dim3(grid_map), dim3(256), 0, s, d_rgb8, n, sc->info, sc->pal32, sc->boxsum, sc->idx, sc->record);
+    hipLaunchKernelGGL(k_gif_lzw, dim3(nseg), dim3(64), 0, s, sc->idx, n, sc->seg, sc->seglen);
+    hipLaunchKernelGGL(k_gif_offsets, dim3(1), dim3(256), 0, s, sc->seglen, nseg, sc->segoff, sc->info, sc->record, width, height);
+    hipLaunchKernelGGL(k_gif_pack, dim3(grid_pack), dim3(256), 0, s, sc->seg, sc->segoff, nseg, sc->info, sc->record);
     HIP_TRY(hipGetLastError());
+    e->d_body = sc->record;
+    e->d_len = &sc->info->record_bytes;
+    e->cap = sc->record_cap;
+    e->min_len = RTC_GIF_RECORD_HEADER + 1; // at least the header and the block terminator
     return RTC_OK;
 }
 
-hipError_t drain_lanes(rtc_context *ctx) {
-    for (uint32_t l = 0; l < rtc_context::MAX_LANES; ++l)
-        if (ctx->lane[l]) {
-            const hipError_t e = hipStreamSynchronize(ctx->lane[l]);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
-
-} // namespace
-
-struct GifFrameScratch {
-    GifScratch sc;
-};
-
-GifFrameScratch *rtc_gif_scratch_new() { return new (std::nothrow) GifFrameScratch; }
-void rtc_gif_scratch_free(GifFrameScratch *g) {
-    if (!g) return;
-    g->sc.release();
-    delete g;
-}
-int rtc_gif_scratch_encode(GifFrameScratch *g, const void *d_rgb8, uint32_t width, uint32_t height, void *stream) {
-    if (!g || !d_rgb8 || width == 0 || height == 0 || width > 65535u || height > 65535u) return RTC_ERR_ARG;
-    return encode_frame(g->sc, static_cast<const uint8_t *>(d_rgb8), width, height, static_cast<hipStream_t>(stream));
-}
-const uint8_t *rtc_gif_scratch_record(const GifFrameScratch *g) { return g->sc.record; }
-size_t rtc_gif_scratch_record_cap(const GifFrameScratch *g) { return g->sc.record_cap; }
-const unsigned long long *rtc_gif_scratch_length(const GifFrameScratch *g) { return &g->sc.info->record_bytes; }
-
-struct rtc_gif_writer {
-    rtc_context *ctx = nullptr;
-    GifScratch sc;
-    uint8_t *d_frame = nullptr; // render target of rtc_gif_writer_render
-    size_t frame_cap = 0;
-    uint32_t width = 0, height = 0;
-    std::vector<uint8_t> file; // header + records, without the trailer
-};
-
-rtc_status rtc_gif_writer_create(rtc_context *ctx, rtc_gif_writer **out) {
-    if (!ctx || !out) return RTC_ERR_ARG;
-    *out = new (std::nothrow) rtc_gif_writer;
-    if (!*out) return RTC_ERR_NOMEM;
-    (*out)->ctx = ctx;
-    return RTC_OK;
-}
-
-void rtc_gif_writer_destroy(rtc_gif_writer *g) {
-    if (!g) return;
-    if (hipSetDevice(g->ctx->device) == hipSuccess) {
-        (void)hipStreamSynchronize(g->ctx->stream);
-        g->sc.release();
-        if (g->d_frame) (void)hipFree(g->d_frame);
-    }
-    delete g;
-}
-
-rtc_status rtc_gif_writer_append_device(rtc_gif_writer *g, const void *d_rgb8, uint32_t width, uint32_t height) {
-    if (!g || !d_rgb8 || width == 0 || height == 0 || width > 65535u || height > 65535u) return RTC_ERR_ARG;
-    if (!g->file.empty() && (width != g->width || height != g->height)) return RTC_ERR_ARG;
-    rtc_context *ctx = g->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    rtc_status st = encode_frame(g->sc, static_cast<const uint8_t *>(d_rgb8), width, height, ctx->stream);
-    if (st != RTC_OK) return st;
-    GifInfo info{};
-    HIP_TRY(hipMemcpyAsync(&info, g->sc.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (g->file.empty()) {
-        g->file.resize(RTC_GIF_FILE_HEADER);
-        rtc_gif_file_header(g->file.data(), width, height);
-        g->width = width;
-        g->height = height;
-    }
-    const size_t at = g->file.size();
-    g->file.resize(at + info.record_bytes);
-    HIP_TRY(hipMemcpy(g->file.data() + at, g->sc.record, info.record_bytes, hipMemcpyDeviceToHost));
-    return RTC_OK;
-}
-
-rtc_status rtc_gif_writer_render(rtc_gif_writer *g, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags) {
-    if (!g || !w || !cam || w->ctx != g->ctx) return RTC_ERR_ARG;
-    if (cam->hsize > 65535u || cam->vsize > 65535u) return RTC_ERR_ARG;
-    if (!g->file.empty() && (cam->hsize != g->width || cam->vsize != g->height)) return RTC_ERR_ARG;
-    rtc_context *ctx = g->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)3 * cam->hsize * cam->vsize;
-    if (bytes == 0) return RTC_ERR_ARG;
-    if (g->frame_cap < bytes) {
-        if (g->d_frame) (void)hipFree(g->d_frame);
-        g->d_frame = nullptr;
-        g->frame_cap = 0;
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&g->d_frame), bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        g->frame_cap = bytes;
-    }
-    rtc_status st = rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, nullptr, g->d_frame, flags);
-    if (st == RTC_OK) st = rtc_context_fence(ctx); // a pipelined context rendered on a lane: the stream waits for it
-    if (st == RTC_OK) st = rtc_gif_writer_append_device(g, g->d_frame, cam->hsize, cam->vsize);
-    return st;
-}
-
-size_t rtc_gif_writer_bytes(const rtc_gif_writer *g, uint8_t *buf, size_t cap) {
-    if (!g || g->file.empty()) return 0;
-    const size_t need = g->file.size() + 1;
-    if (buf) {
-        const size_t k = std::min(cap, g->file.size());
-        std::memcpy(buf, g->file.data(), k);
-        if (cap >= need) buf[need - 1] = 0x3B;
-    }
-    return need;
-}
-
-rtc_status rtc_gif_writer_write(const rtc_gif_writer *g, const char *path) {
-    if (!g || !path || g->file.empty()) return RTC_ERR_ARG;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return RTC_ERR_IO;
-    const uint8_t trailer = 0x3B;
-    const bool ok = std::fwrite(g->file.data(), 1, g->file.size(), f) == g->file.size() && std::fwrite(&trailer, 1, 1, f) == 1;
-    return (std::fclose(f) == 0 && ok) ? RTC_OK : RTC_ERR_IO;
-}
-
-namespace {
-
-bool jpeg_name(const char *name) { // ".jpg" / ".jpeg", any case, as the `image` crate matches extensions
-    if (!name) return false;
-    const size_t n = std::strlen(name);
-    auto ends = [&](const char *ext) {
-        const size_t k = std::strlen(ext);
-        if (n < k) return false;
-        for (size_t i = 0; i < k; ++i)
-            if (std::tolower((unsigned char)name[n - k + i]) != ext[i]) return false;
-        return true;
-    };
-    return ends(".jpg") || ends(".jpeg");
-}
-
-bool ppm_name(const char *name) { // what render_to_files writes as a P3 file: ".ppm", any case
-    if (!name) return false;
-    const size_t n = std::strlen(name);
-    if (n < 4) return false;
-    const char *e = name + n - 4;
-    return e[0] == '.' && std::tolower((unsigned char)e[1]) == 'p' && std::tolower((unsigned char)e[2]) == 'p' &&
-           std::tolower((unsigned char)e[3]) == 'm';
-}
-
-// rtc_lua_program_render's ring and lanes, with the GIF chain behind every AddFrame render (and, when `jpeg`, the JPEG chain
-// behind every Render job of a .jpg / .jpeg name) on the same lane and only the encoded length copied behind it; the bytes
-// themselves follow at delivery, on this call's copy stream. When `png`, the compressed PNG chain takes the place of the GIF
-// chain and of the rows for every job but a Render named .ppm (render_to_files' PNG files). When `saved`, every Render job's
-// file is made by the save table (rtc_image.hip's chain behind the render; PPM printed from the rows at delivery).
-rtc_status render_lua_outputs(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, bool jpeg, int32_t quality,
-                              bool png, bool saved, rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
-    if (!ctx || !prog || mode > RTC_MODE_RENDER_ASYNC) return RTC_ERR_ARG;
-    if (saved) // every name and size first: an unsupported one renders nothing
-        for (uint32_t i = 0, n = rtc_lua_program_jobs(prog); i < n; ++i) {
-            rtc_lua_job job;
-            const rtc_status js = rtc_lua_program_job(prog, i, &job);
-            if (js != RTC_OK) return js;
-            uint32_t f = 0;
-            if (job.kind == RTC_LUA_JOB_ADD_FRAME) {
-                if (job.camera.hsize == 0 || job.camera.vsize == 0 || job.camera.hsize > 65535u || job.camera.vsize > 65535u) return RTC_ERR_ARG;
-                continue;
-            }
-            const rtc_status fs = rtc_image_format_for_name(job.outfile, &f);
-            if (fs != RTC_OK) return fs == RTC_ERR_ARG ? RTC_ERR_UNSUPPORTED : fs;
-            if (!rtc_image_size_ok(f, job.camera.hsize, job.camera.vsize) || job.camera.hsize > 65535u || job.camera.vsize > 65535u)
-                return RTC_ERR_ARG;
-        }
-    HIP_TRY(hipSetDevice(ctx->device));
-    constexpr uint32_t RING = rtc_context::MAX_LANES + 1u;
-    struct Slot {
-        uint8_t *d = nullptr, *h = nullptr; // the frame's rows (device), the delivered bytes (page-locked)
-        size_t cap = 0, hcap = 0;
-        GifScratch sc;
-        GifInfo *h_info = nullptr;          // page-locked: the record length lands here
-        JpegScratch *jsc = nullptr;
-        unsigned long long *h_len = nullptr; // page-locked: the JPEG data / PNG file length lands here
-        PngScratch *psc = nullptr;
-        ImageScratch *isc = nullptr;
-        hipEvent_t done = nullptr;
-        bool pending = false, gif = false;
-        uint32_t format = RTC_LUA_OUT_RGB8, image = 0; // image: a RTC_LUA_OUT_FILE's RTC_IMAGE_* format
-        uint32_t job = 0;
-    } ring[RING];
-    hipStream_t copy = nullptr;
-    const uint32_t njobs = rtc_lua_program_jobs(prog);
-    const uint32_t lanes_before = ctx->lanes;
-    rtc_world *world = nullptr;
-    rtc_status st = RTC_OK;
-    bool stop = false;
-    auto host_buf = [&](Slot &sl, size_t bytes) -> rtc_status {
-        if (sl.hcap >= bytes) return RTC_OK;
-        if (sl.h) (void)hipHostFree(sl.h);
-        sl.h = nullptr;
-        sl.hcap = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&sl.h), bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return RTC_ERR_NOMEM; }
-        sl.hcap = bytes;
-        return RTC_OK;
-    };
-    auto deliver = [&](Slot &sl) -> rtc_status {
-        if (!sl.pending) return RTC_OK;
-        sl.pending = false;
-        if (hipEventSynchronize(sl.done) != hipSuccess) return RTC_ERR_DEVICE;
-        rtc_lua_job job;
-        const rtc_status js = rtc_lua_program_job(prog, sl.job, &job);
-        if (js != RTC_OK) return js;
-        size_t nbytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
-        if (sl.gif) {
-            nbytes = (size_t)sl.h_info->record_bytes;
-            const rtc_status hb = host_buf(sl, nbytes);
-            if (hb != RTC_OK) return hb;
-            if (hipMemcpyAsync(sl.h, sl.sc.record, nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
-                hipStreamSynchronize(copy) != hipSuccess)
-                return RTC_ERR_DEVICE;
-        } else if (sl.format == RTC_LUA_OUT_JPEG) {
-            const size_t len = (size_t)*sl.h_len;
-            if (len < 2 || len > rtc_jpeg_scratch_out_cap(sl.jsc)) return RTC_ERR_DEVICE;
-            nbytes = RTC_JPEG_HEADER_BYTES + len;
-            const rtc_status hb = host_buf(sl, nbytes);
-            if (hb != RTC_OK) return hb;
-            rtc_jpeg_header(job.camera.hsize, job.camera.vsize, quality, sl.h);
-            if (hipMemcpyAsync(sl.h + RTC_JPEG_HEADER_BYTES, rtc_jpeg_scratch_data(sl.jsc), len, hipMemcpyDeviceToHost, copy) != hipSuccess ||
-                hipStreamSynchronize(copy) != hipSuccess)
-                return RTC_ERR_DEVICE;
-        } else if (sl.format == RTC_LUA_OUT_PNG) {
-            nbytes = (size_t)*sl.h_len;
-            if (nbytes == 0 || nbytes > rtc_png_scratch_out_cap(sl.psc)) return RTC_ERR_DEVICE;
-            const rtc_status hb = host_buf(sl, nbytes);
-            if (hb != RTC_OK) return hb;
-            if (hipMemcpyAsync(sl.h, rtc_png_scratch_data(sl.psc), nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
-                hipStreamSynchronize(copy) != hipSuccess)
-                return RTC_ERR_DEVICE;
-        } else if (sl.format == RTC_LUA_OUT_FILE && sl.image == RTC_IMAGE_PPM) { // the rows are on the host: print them
-            std::vector<uint8_t> ppm(rtc_image_format(RTC_IMAGE_PPM, sl.h, job.camera.hsize, job.camera.vsize, 3, nullptr, 0));
-            rtc_image_format(RTC_IMAGE_PPM, sl.h, job.camera.hsize, job.camera.vsize, 3, ppm.data(), ppm.size());
-            if (ppm.empty()) return RTC_ERR_ARG;
-            if (fn && !stop && fn(user, &job, sl.job, sl.format, ppm.data(), ppm.size()) != 0) stop = true;
-            return RTC_OK;
-        } else if (sl.format == RTC_LUA_OUT_FILE) {
-            nbytes = (size_t)*sl.h_len;
-            if (nbytes == 0 || nbytes > rtc_image_scratch_out_cap(sl.isc)) return RTC_ERR_DEVICE;
-            const rtc_status hb = host_buf(sl, nbytes);
-            if (hb != RTC_OK) return hb;
-            if (hipMemcpyAsync(sl.h, rtc_image_scratch_data(sl.isc), nbytes, hipMemcpyDeviceToHost, copy) != hipSuccess ||
-                hipStreamSynchronize(copy) != hipSuccess)
-                return RTC_ERR_DEVICE;
-        }
-        if (fn && !stop && fn(user, &job, sl.job, sl.format, sl.h, nbytes) != 0) stop = true;
-        return RTC_OK;
-    };
-    auto drain = [&](uint32_t next_job) -> rtc_status {
-        rtc_status r = RTC_OK;
-        for (uint32_t k = 0; k < RING; ++k) {
-            const rtc_status d = deliver(ring[(next_job + k) % RING]);
-            if (r == RTC_OK) r = d;
-        }
-        return r;
-    };
-    if (hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) != hipSuccess) return RTC_ERR_DEVICE;
-    if (stats) st = rtc_stats_reset(ctx);
-    if (st == RTC_OK && lanes_before == 1u && njobs > 1u) st = rtc_context_set_pipeline(ctx, 3u);
-    uint32_t i = 0;
-    for (; st == RTC_OK && !stop && i < njobs; ++i) {
-        rtc_lua_job job;
-        st = rtc_lua_program_job(prog, i, &job);
-        if (st != RTC_OK) break;
-        const size_t bytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
-        const bool add_frame = job.kind == RTC_LUA_JOB_ADD_FRAME;
-        const bool gif = add_frame && !png;
-        uint32_t image = 0;
-        if (saved && !add_frame && (st = rtc_image_format_for_name(job.outfile, &image)) != RTC_OK) break;
-        const uint32_t format = png ? ((add_frame || !ppm_name(job.outfile)) ? RTC_LUA_OUT_PNG : RTC_LUA_OUT_RGB8)
-                                : gif ? RTC_LUA_OUT_GIF_RECORD
-                                : saved ? RTC_LUA_OUT_FILE
-                                : (jpeg && jpeg_name(job.outfile)) ? RTC_LUA_OUT_JPEG : RTC_LUA_OUT_RGB8;
-        const bool rows_out = format == RTC_LUA_OUT_RGB8 || (format == RTC_LUA_OUT_FILE && image == RTC_IMAGE_PPM);
-        if (bytes == 0 || (!rows_out && (job.camera.hsize > 65535u || job.camera.vsize > 65535u))) { st = RTC_ERR_ARG; break; }
-        Slot &sl = ring[i % RING];
-        st = deliver(sl);
-        if (st != RTC_OK || stop) break;
-        if (!world || !job.same_world_as_previous) {
-            st = drain(i);
-            if (st == RTC_OK) st = rtc_context_synchronize(ctx);
-            if (st != RTC_OK || stop) break;
-            if (world) rtc_world_destroy(world);
-            world = nullptr;
-            st = rtc_world_create(ctx, job.shapes, job.n_shapes, &job.light, &world);
-            if (st != RTC_OK) break;
-        }
-        if (sl.cap < bytes) {
-            if (sl.d) (void)hipFree(sl.d);
-            sl.d = nullptr;
-            sl.cap = 0;
-            const hipError_t e = hipMalloc(reinterpret_cast<void **>(&sl.d), bytes);
-            if (e != hipSuccess) { (void)hipGetLastError(); st = e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; break; }
-            sl.cap = bytes;
-        }
-        if (rows_out && (st = host_buf(sl, bytes)) != RTC_OK) break;
-        if (format == RTC_LUA_OUT_JPEG) {
-            if (!sl.jsc && !(sl.jsc = rtc_jpeg_scratch_new())) { st = RTC_ERR_NOMEM; break; }
-            if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
-        }
-        if (format == RTC_LUA_OUT_PNG) {
-            if (!sl.psc && !(sl.psc = rtc_png_scratch_new())) { st = RTC_ERR_NOMEM; break; }
-            if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
-        }
-        if (format == RTC_LUA_OUT_FILE && !rows_out) {
-            if (!sl.isc && !(sl.isc = rtc_image_scratch_new())) { st = RTC_ERR_NOMEM; break; }
-            if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
-        }
-        if (!sl.h_info && hipHostMalloc(reinterpret_cast<void **>(&sl.h_info), sizeof(GifInfo), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
-        if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, nullptr, sl.d, flags);
-        if (st != RTC_OK) break;
-        hipStream_t s = ctx->lanes > 1u ? ctx->lane[ctx->last.lane] : ctx->stream;
-        if (gif) {
-            st = encode_frame(sl.sc, sl.d, job.camera.hsize, job.camera.vsize, s);
-            if (st != RTC_OK) break;
-            if (hipMemcpyAsync(sl.h_info, sl.sc.info, sizeof(GifInfo), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        } else if (format == RTC_LUA_OUT_JPEG) {
-            st = (rtc_status)rtc_jpeg_scratch_encode(sl.jsc, sl.d, job.camera.hsize, job.camera.vsize, 3, quality, s);
-            if (st != RTC_OK) break;
-            if (hipMemcpyAsync(sl.h_len, rtc_jpeg_scratch_length(sl.jsc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        } else if (format == RTC_LUA_OUT_PNG) {
-            st = (rtc_status)rtc_png_scratch_encode(sl.psc, sl.d, job.camera.hsize, job.camera.vsize, 3, s);
-            if (st != RTC_OK) break;
-            if (hipMemcpyAsync(sl.h_len, rtc_png_scratch_length(sl.psc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        } else if (!rows_out) { // RTC_LUA_OUT_FILE
-            st = (rtc_status)rtc_image_scratch_encode(sl.isc, image, sl.d, job.camera.hsize, job.camera.vsize, 3, s);
-            if (st != RTC_OK) break;
-            if (hipMemcpyAsync(sl.h_len, rtc_image_scratch_length(sl.isc), sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        } else if (hipMemcpyAsync(sl.h, sl.d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
-            st = RTC_ERR_DEVICE;
-            break;
-        }
-        if (hipEventRecord(sl.done, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        sl.pending = true;
-        sl.gif = gif;
-        sl.format = format;
-        sl.image = image;
-        sl.job = i;
-    }
-    {
-        const rtc_status d = drain(i);
-        if (st == RTC_OK) st = d;
-    }
-    const rtc_status sy = rtc_context_synchronize(ctx);
-    if (st == RTC_OK) st = sy;
-    (void)drain_lanes(ctx);
-    if (world) rtc_world_destroy(world);
-    for (Slot &sl : ring) {
-        if (sl.d) (void)hipFree(sl.d);
-        if (sl.h) (void)hipHostFree(sl.h);
-        if (sl.h_info) (void)hipHostFree(sl.h_info);
-        if (sl.h_len) (void)hipHostFree(sl.h_len);
-        rtc_jpeg_scratch_free(sl.jsc);
-        rtc_png_scratch_free(sl.psc);
-        rtc_image_scratch_free(sl.isc);
-        sl.sc.release();
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    (void)hipStreamDestroy(copy);
-    if (ctx->lanes != lanes_before) {
-        const rtc_status r = rtc_context_set_pipeline(ctx, lanes_before);
-        if (st == RTC_OK) st = r;
-    }
-    if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
-    return st;
-}
-
-struct GifFnAdapter {
-    rtc_lua_gif_fn fn;
-    void *user;
-};
-
-int gif_fn_adapter(void *user, const rtc_lua_job *job, uint32_t job_index, uint32_t, const uint8_t *bytes, size_t nbytes) {
-    const GifFnAdapter *a = static_cast<const GifFnAdapter *>(user);
-    return a->fn ? a->fn(a->user, job, job_index, bytes, nbytes) : 0;
-}
-
-} // namespace
-
-rtc_status rtc_lua_program_render_gif(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_gif_fn fn,
-                                      void *user, rtc_stats *stats) {
-    GifFnAdapter a{fn, user};
-    return render_lua_outputs(ctx, prog, mode, flags, false, 75, false, false, gif_fn_adapter, &a, stats);
-}
-
-rtc_status rtc_lua_program_render_files(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, int32_t quality,
-                                        rtc_lua_file_fn fn, void *user, rtc_stats *stats) {
-    if (quality < 1 || quality > 100) return RTC_ERR_ARG;
-    return render_lua_outputs(ctx, prog, mode, flags, true, quality, false, false, fn, user, stats);
-}
-
-rtc_status rtc_lua_program_render_png(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_file_fn fn,
-                                      void *user, rtc_stats *stats) {
-    return render_lua_outputs(ctx, prog, mode, flags, false, 75, true, false, fn, user, stats);
-}
-
-rtc_status rtc_lua_program_render_saved(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mode, uint32_t flags, rtc_lua_file_fn fn,
-                                        void *user, rtc_stats *stats) {
-    return render_lua_outputs(ctx, prog, mode, flags, false, RTC_IMAGE_JPEG_QUALITY, false, true, fn, user, stats);
+void rtc_gif_release(GifScratch *sc) {
+    if (!sc) return;
+    sc->release();
+    delete sc;
 }

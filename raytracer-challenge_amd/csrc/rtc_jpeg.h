@@ -193,15 +193,4 @@ RTC_JHD uint32_t rtc_jpeg_eob_code(int chroma, uint64_t *code) {
 // SOI .. SOS of a width x height file at `quality` (RTC_JPEG_HEADER_BYTES bytes): the part of the file the host writes
 extern "C" void rtc_jpeg_header(uint32_t width, uint32_t height, int32_t quality, uint8_t *hdr);
 
-// The device encoder's chain, for the Lua loop's lanes (rtc_gif.hip): scratch, grow-only; encode enqueues on `stream` (a
-// hipStream_t); the stuffed data + EOI are then at rtc_jpeg_scratch_data, their length (8 bytes) at rtc_jpeg_scratch_length.
-struct JpegScratch;
-JpegScratch *rtc_jpeg_scratch_new();
-void rtc_jpeg_scratch_free(JpegScratch *sc);
-int rtc_jpeg_scratch_encode(JpegScratch *sc, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels, int32_t quality,
-                            void *stream);
-const uint8_t *rtc_jpeg_scratch_data(const JpegScratch *sc);
-size_t rtc_jpeg_scratch_out_cap(const JpegScratch *sc);
-const unsigned long long *rtc_jpeg_scratch_length(const JpegScratch *sc);
-
 #endif

@@ -1,6 +1,5 @@
-// rtc_jpeg.hip — [device] the JPEG writer of include/rtc.h on gfx950 for a frame already in device memory, and the
-// encoder object that uses it. host_jpeg.cpp states the same bytes on the host; the per-block arithmetic of both is
-// rtc_jpeg.h. The host writes the 623 header bytes (fixed for a size and quality); the device produces the rest.
+// rtc_jpeg.hip — [device] the JPEG writer of include/rtc.h on gfx950 for a frame already in device memory (rtc_encode.h).
+// host_jpeg.cpp states the same bytes on the host; the per-block arithmetic of both is rtc_jpeg.h. The host writes the 623 header bytes (fixed for a size and quality); the device produces the rest.
 //
 // Kernels of one frame, in stream order:
 //   k_jpeg_blocks    one wave per MCU: colour (lane = pixel), the two DCT passes through LDS (one lane per row / column of
@@ -18,13 +17,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <vector>
 
 #include "rtc.h"
-#include "rtc_internal.h"
+#include "rtc_encode.h"
 #include "rtc_jpeg.h"
 
 namespace {
@@ -323,136 +319,42 @@ struct JpegScratch {
     }
 };
 
-namespace {
-
-bool encode_args_ok(const void *d, uint32_t w, uint32_t h, uint32_t channels, int32_t quality) {
-    return d && w >= 1 && w <= 65535u && h >= 1 && h <= 65535u && (channels == 3 || channels == 4) && quality >= 1 && quality <= 100;
-}
-
-// Enqueue the whole chain on `s`; the stuffed data + EOI are then at sc.out, their length in sc.info->out_bytes.
-rtc_status encode_frame(JpegScratch &sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, int32_t quality,
-                        hipStream_t s) {
+// The whole chain on `s`; the body is the stuffed data + EOI (what follows the header), its length info->out_bytes.
+rtc_status rtc_jpeg_enqueue(JpegScratch *&sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, int32_t quality,
+                            hipStream_t s, RtcEncoded *e) {
+    if (!sc && !(sc = new (std::nothrow) JpegScratch)) return RTC_ERR_NOMEM;
     const uint32_t mcu_w = (w + 7) / 8, mcu_h = (h + 7) / 8;
     const size_t nmcu = (size_t)mcu_w * mcu_h;
-    const rtc_status r = sc.reserve(nmcu);
+    const rtc_status r = sc->reserve(nmcu);
     if (r != RTC_OK) return r;
     JpegQuant q;
     for (int t = 0; t < 2; ++t)
         for (int i = 0; i < 64; ++i) q.q[64 * t + i] = (uint16_t)rtc_jpeg_quant_entry(quality, t, i);
     const uint32_t ngroups = (uint32_t)((nmcu + MCU_PER_GROUP - 1) / MCU_PER_GROUP);
     const uint32_t grid_mcu = (uint32_t)((nmcu + 3) / 4);
-    const size_t nchunks_max = (sc.data_max + CHUNK - 1) / CHUNK;
+    const size_t nchunks_max = (sc->data_max + CHUNK - 1) / CHUNK;
     const uint32_t grid_data = (uint32_t)std::min<size_t>(DATA_GRID_MAX, nchunks_max);
-    hipLaunchKernelGGL(k_jpeg_blocks, dim3(grid_mcu), dim3(256), 0, s, d_pixels, w, h, channels, mcu_w, (uint32_t)nmcu, q, sc.coef,
-                       sc.acbits, sc.dc);
-    hipLaunchKernelGGL(k_jpeg_mcu_scan, dim3(ngroups), dim3(MCU_PER_GROUP), 0, s, sc.acbits, sc.dc, (uint32_t)nmcu, sc.mcu_off, sc.group);
-    hipLaunchKernelGGL(k_jpeg_group_scan, dim3(1), dim3(1024), 0, s, sc.group, ngroups, sc.info);
-    hipLaunchKernelGGL(k_jpeg_clear, dim3(grid_data), dim3(256), 0, s, sc.words, sc.info);
-    hipLaunchKernelGGL(k_jpeg_pack, dim3(grid_mcu), dim3(256), 0, s, sc.coef, sc.dc, (uint32_t)nmcu, sc.mcu_off, sc.group, sc.info, sc.words,
-                       (unsigned long long)sc.nwords);
-    hipLaunchKernelGGL(k_jpeg_ffcount, dim3(grid_data), dim3(256), 0, s, sc.words, sc.info, sc.ffcnt);
-    hipLaunchKernelGGL(k_jpeg_ffscan, dim3(1), dim3(1024), 0, s, sc.ffcnt, sc.info, sc.chunk_off);
-    hipLaunchKernelGGL(k_jpeg_scatter, dim3(grid_data), dim3(256), 0, s, sc.words, sc.info, sc.chunk_off, sc.out,
-                       (unsigned long long)(2 * sc.data_max + 2));
+    const unsigned long long out_cap = 2 * sc->data_max + 2;
+    hipLaunchKernelGGL(k_jpeg_blocks, dim3(grid_mcu), dim3(256), 0, s, d_pixels, w, h, channels, mcu_w, (uint32_t)nmcu, q, sc->coef,
+                       sc->acbits, sc->dc);
+    hipLaunchKernelGGL(k_jpeg_mcu_scan, dim3(ngroups), dim3(MCU_PER_GROUP), 0, s, sc->acbits, sc->dc, (uint32_t)nmcu, sc->mcu_off, sc->group);
+    hipLaunchKernelGGL(k_jpeg_group_scan, dim3(1), dim3(1024), 0, s, sc->group, ngroups, sc->info);
+    hipLaunchKernelGGL(k_jpeg_clear, dim3(grid_data), dim3(256), 0, s, sc->words, sc->info);
+    hipLaunchKernelGGL(k_jpeg_pack, dim3(grid_mcu), dim3(256), 0, s, sc->coef, sc->dc, (uint32_t)nmcu, sc->mcu_off, sc->group, sc->info,
+                       sc->words, (unsigned long long)sc->nwords);
+    hipLaunchKernelGGL(k_jpeg_ffcount, dim3(grid_data), dim3(256), 0, s, sc->words, sc->info, sc->ffcnt);
+    hipLaunchKernelGGL(k_jpeg_ffscan, dim3(1), dim3(1024), 0, s, sc->ffcnt, sc->info, sc->chunk_off);
+    hipLaunchKernelGGL(k_jpeg_scatter, dim3(grid_data), dim3(256), 0, s, sc->words, sc->info, sc->chunk_off, sc->out, out_cap);
     HIP_TRY(hipGetLastError());
+    e->d_body = sc->out;
+    e->d_len = &sc->info->out_bytes;
+    e->cap = out_cap;
+    e->min_len = 2; // EOI
     return RTC_OK;
 }
 
-} // namespace
-
-JpegScratch *rtc_jpeg_scratch_new() { return new (std::nothrow) JpegScratch; }
-void rtc_jpeg_scratch_free(JpegScratch *sc) {
+void rtc_jpeg_release(JpegScratch *sc) {
     if (!sc) return;
     sc->release();
     delete sc;
-}
-int rtc_jpeg_scratch_encode(JpegScratch *sc, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels, int32_t quality,
-                            void *stream) {
-    if (!sc || !encode_args_ok(d_pixels, width, height, channels, quality)) return RTC_ERR_ARG;
-    return encode_frame(*sc, static_cast<const uint8_t *>(d_pixels), width, height, channels, quality, static_cast<hipStream_t>(stream));
-}
-const uint8_t *rtc_jpeg_scratch_data(const JpegScratch *sc) { return sc->out; }
-size_t rtc_jpeg_scratch_out_cap(const JpegScratch *sc) { return 2 * sc->data_max + 2; }
-const unsigned long long *rtc_jpeg_scratch_length(const JpegScratch *sc) { return &sc->info->out_bytes; }
-
-struct rtc_jpeg_encoder {
-    rtc_context *ctx = nullptr;
-    JpegScratch sc;
-    uint8_t *d_frame = nullptr; // render target of rtc_jpeg_encoder_render
-    size_t frame_cap = 0;
-    std::vector<uint8_t> file;
-};
-
-rtc_status rtc_jpeg_encoder_create(rtc_context *ctx, rtc_jpeg_encoder **out) {
-    if (!ctx || !out) return RTC_ERR_ARG;
-    *out = new (std::nothrow) rtc_jpeg_encoder;
-    if (!*out) return RTC_ERR_NOMEM;
-    (*out)->ctx = ctx;
-    return RTC_OK;
-}
-
-void rtc_jpeg_encoder_destroy(rtc_jpeg_encoder *e) {
-    if (!e) return;
-    if (hipSetDevice(e->ctx->device) == hipSuccess) {
-        (void)hipStreamSynchronize(e->ctx->stream);
-        e->sc.release();
-        if (e->d_frame) (void)hipFree(e->d_frame);
-    }
-    delete e;
-}
-
-rtc_status rtc_jpeg_encoder_encode_device(rtc_jpeg_encoder *e, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels,
-                                          int32_t quality) {
-    if (!e || !encode_args_ok(d_pixels, width, height, channels, quality)) return RTC_ERR_ARG;
-    rtc_context *ctx = e->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const rtc_status st = encode_frame(e->sc, static_cast<const uint8_t *>(d_pixels), width, height, channels, quality, ctx->stream);
-    if (st != RTC_OK) return st;
-    unsigned long long len = 0;
-    HIP_TRY(hipMemcpyAsync(&len, &e->sc.info->out_bytes, sizeof len, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (len < 2 || len > 2 * e->sc.data_max + 2) return RTC_ERR_DEVICE;
-    e->file.resize(RTC_JPEG_HEADER_BYTES + (size_t)len);
-    rtc_jpeg_header(width, height, quality, e->file.data());
-    HIP_TRY(hipMemcpy(e->file.data() + RTC_JPEG_HEADER_BYTES, e->sc.out, (size_t)len, hipMemcpyDeviceToHost));
-    return RTC_OK;
-}
-
-rtc_status rtc_jpeg_encoder_render(rtc_jpeg_encoder *e, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
-                                   float gamma, int32_t quality) {
-    if (!e || !w || !cam || w->ctx != e->ctx) return RTC_ERR_ARG;
-    if (cam->hsize == 0 || cam->vsize == 0 || cam->hsize > 65535u || cam->vsize > 65535u || quality < 1 || quality > 100) return RTC_ERR_ARG;
-    if (!(gamma > 0.0f) || !(gamma <= 3.4028235e38f)) return RTC_ERR_ARG;
-    rtc_context *ctx = e->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t channels = gamma == 1.0f ? 3u : 4u;
-    const uint32_t rows = channels == 3u ? cam->vsize : (cam->vsize + 7u) / 8u * 8u; // a view holds whole 8-row bands
-    const size_t bytes = (size_t)channels * cam->hsize * rows;
-    if (e->frame_cap < bytes) {
-        if (e->d_frame) (void)hipFree(e->d_frame);
-        e->d_frame = nullptr;
-        e->frame_cap = 0;
-        const hipError_t he = hipMalloc(reinterpret_cast<void **>(&e->d_frame), bytes);
-        if (he != hipSuccess) { (void)hipGetLastError(); return he == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        e->frame_cap = bytes;
-    }
-    rtc_status st = channels == 3u ? rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, nullptr, e->d_frame, flags)
-                                   : rtc_render_views_rgba8(ctx, w, cam, 1, mode, 0, 1, gamma, e->d_frame, rows, flags);
-    if (st == RTC_OK) st = rtc_context_fence(ctx); // a pipelined context rendered on a lane: the stream waits for it
-    if (st == RTC_OK) st = rtc_jpeg_encoder_encode_device(e, e->d_frame, cam->hsize, cam->vsize, channels, quality);
-    return st;
-}
-
-size_t rtc_jpeg_encoder_bytes(const rtc_jpeg_encoder *e, uint8_t *buf, size_t cap) {
-    if (!e || e->file.empty()) return 0;
-    if (buf) std::memcpy(buf, e->file.data(), std::min(cap, e->file.size()));
-    return e->file.size();
-}
-
-rtc_status rtc_jpeg_encoder_write(const rtc_jpeg_encoder *e, const char *path) {
-    if (!e || !path || e->file.empty()) return RTC_ERR_ARG;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return RTC_ERR_IO;
-    const bool ok = std::fwrite(e->file.data(), 1, e->file.size(), f) == e->file.size();
-    return (std::fclose(f) == 0 && ok) ? RTC_OK : RTC_ERR_IO;
 }

@@ -368,14 +368,4 @@ RTC_PHD void rtc_png_head(uint32_t width, uint32_t height, uint32_t channels, ui
     o[26] = o[27] = o[28] = 0;
 }
 
-// The device encoder's chain for the Lua loop's lanes (rtc_gif.hip): scratch, grow-only; encode enqueues on `stream` (a
-// hipStream_t); the file is then at rtc_png_scratch_data, its length (8 bytes) at rtc_png_scratch_length.
-struct PngScratch;
-PngScratch *rtc_png_scratch_new();
-void rtc_png_scratch_free(PngScratch *sc);
-int rtc_png_scratch_encode(PngScratch *sc, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels, void *stream);
-const uint8_t *rtc_png_scratch_data(const PngScratch *sc);
-size_t rtc_png_scratch_out_cap(const PngScratch *sc);
-const unsigned long long *rtc_png_scratch_length(const PngScratch *sc);
-
 #endif

@@ -1,5 +1,5 @@
-// rtc_png.hip — [device] the compressed PNG writer of include/rtc.h on gfx950 for a frame already in device memory, and the
-// encoder object that uses it. host_png.cpp states the same bytes on the host; the arithmetic of both is rtc_png.h.
+// rtc_png.hip — [device] the compressed PNG writer of include/rtc.h on gfx950 for a frame already in device memory
+// (rtc_encode.h). host_png.cpp states the same bytes on the host; the arithmetic of both is rtc_png.h.
 //
 // Kernels of one frame, in stream order (n = filtered bytes, one segment = RTC_PNG_SEGMENT of them):
 //   k_png_filter   one wave per row: the five filters' sums (lane = byte, wave reduction), then the chosen filter's row
@@ -20,13 +20,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <vector>
 
 #include "rtc.h"
-#include "rtc_internal.h"
+#include "rtc_encode.h"
 #include "rtc_png.h"
 
 namespace {
@@ -412,123 +409,33 @@ struct PngScratch {
     }
 };
 
-namespace {
-
-bool encode_args_ok(const void *d, uint32_t w, uint32_t h, uint32_t channels) {
-    return d && w >= 1 && w <= 65535u && h >= 1 && h <= 65535u && (channels == 3 || channels == 4);
-}
-
-// Enqueue the whole chain on `s`; the file is then at sc.out, its length in sc.pinfo->file_bytes.
-rtc_status encode_frame(PngScratch &sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, hipStream_t s) {
+// The whole chain on `s`; the body is the file, its length pinfo->file_bytes.
+rtc_status rtc_png_enqueue(PngScratch *&sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, hipStream_t s,
+                           RtcEncoded *e) {
+    if (!sc && !(sc = new (std::nothrow) PngScratch)) return RTC_ERR_NOMEM;
     const size_t n = ((size_t)w * channels + 1) * h;
-    const rtc_status r = sc.reserve(n);
+    const rtc_status r = sc->reserve(n);
     if (r != RTC_OK) return r;
     const uint32_t nseg = (uint32_t)((n + SEG - 1) / SEG);
-    const unsigned long long nn = n;
-    hipLaunchKernelGGL(k_png_filter, dim3((h + 3) / 4), dim3(256), 0, s, d_pixels, w, h, channels, sc.filt);
-    hipLaunchKernelGGL(k_png_prev, dim3(nseg), dim3(64), 0, s, sc.filt, nn, sc.prev);
-    hipLaunchKernelGGL(k_png_match, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sc.filt, nn, sc.prev, sc.M);
-    hipLaunchKernelGGL(k_png_parse, dim3(nseg), dim3(256), 0, s, sc.M, nn, sc.prev);
-    hipLaunchKernelGGL(k_png_segment, dim3(nseg), dim3(SEG_THREADS), 0, s, sc.filt, nn, sc.M, sc.prev, sc.words, sc.info);
-    hipLaunchKernelGGL(k_png_layout, dim3(1), dim3(1024), 0, s, sc.info, nseg, nn, w, h, channels, sc.chunk_off, sc.out,
-                       (unsigned long long)sc.out_cap, sc.pinfo);
-    hipLaunchKernelGGL(k_png_copy, dim3(nseg), dim3(256), 0, s, sc.words, sc.info, sc.chunk_off, sc.out, (unsigned long long)sc.out_cap);
-    hipLaunchKernelGGL(k_png_crc, dim3(nseg), dim3(256), 0, s, sc.info, nseg, sc.chunk_off, sc.out, (unsigned long long)sc.out_cap);
+    const unsigned long long nn = n, cap = sc->out_cap;
+    hipLaunchKernelGGL(k_png_filter, dim3((h + 3) / 4), dim3(256), 0, s, d_pixels, w, h, channels, sc->filt);
+    hipLaunchKernelGGL(k_png_prev, dim3(nseg), dim3(64), 0, s, sc->filt, nn, sc->prev);
+    hipLaunchKernelGGL(k_png_match, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sc->filt, nn, sc->prev, sc->M);
+    hipLaunchKernelGGL(k_png_parse, dim3(nseg), dim3(256), 0, s, sc->M, nn, sc->prev);
+    hipLaunchKernelGGL(k_png_segment, dim3(nseg), dim3(SEG_THREADS), 0, s, sc->filt, nn, sc->M, sc->prev, sc->words, sc->info);
+    hipLaunchKernelGGL(k_png_layout, dim3(1), dim3(1024), 0, s, sc->info, nseg, nn, w, h, channels, sc->chunk_off, sc->out, cap, sc->pinfo);
+    hipLaunchKernelGGL(k_png_copy, dim3(nseg), dim3(256), 0, s, sc->words, sc->info, sc->chunk_off, sc->out, cap);
+    hipLaunchKernelGGL(k_png_crc, dim3(nseg), dim3(256), 0, s, sc->info, nseg, sc->chunk_off, sc->out, cap);
     HIP_TRY(hipGetLastError());
+    e->d_body = sc->out;
+    e->d_len = &sc->pinfo->file_bytes;
+    e->cap = cap;
+    e->min_len = RTC_PNG_FILE_FIXED + RTC_PNG_CHUNK_OVERHEAD;
     return RTC_OK;
 }
 
-} // namespace
-
-PngScratch *rtc_png_scratch_new() { return new (std::nothrow) PngScratch; }
-void rtc_png_scratch_free(PngScratch *sc) {
+void rtc_png_release(PngScratch *sc) {
     if (!sc) return;
     sc->release();
     delete sc;
-}
-int rtc_png_scratch_encode(PngScratch *sc, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels, void *stream) {
-    if (!sc || !encode_args_ok(d_pixels, width, height, channels)) return RTC_ERR_ARG;
-    return encode_frame(*sc, static_cast<const uint8_t *>(d_pixels), width, height, channels, static_cast<hipStream_t>(stream));
-}
-const uint8_t *rtc_png_scratch_data(const PngScratch *sc) { return sc->out; }
-size_t rtc_png_scratch_out_cap(const PngScratch *sc) { return sc->out_cap; }
-const unsigned long long *rtc_png_scratch_length(const PngScratch *sc) { return &sc->pinfo->file_bytes; }
-
-struct rtc_png_encoder {
-    rtc_context *ctx = nullptr;
-    PngScratch sc;
-    uint8_t *d_frame = nullptr; // render target of rtc_png_encoder_render
-    size_t frame_cap = 0;
-    std::vector<uint8_t> file;
-};
-
-rtc_status rtc_png_encoder_create(rtc_context *ctx, rtc_png_encoder **out) {
-    if (!ctx || !out) return RTC_ERR_ARG;
-    *out = new (std::nothrow) rtc_png_encoder;
-    if (!*out) return RTC_ERR_NOMEM;
-    (*out)->ctx = ctx;
-    return RTC_OK;
-}
-
-void rtc_png_encoder_destroy(rtc_png_encoder *e) {
-    if (!e) return;
-    if (hipSetDevice(e->ctx->device) == hipSuccess) {
-        (void)hipStreamSynchronize(e->ctx->stream);
-        e->sc.release();
-        if (e->d_frame) (void)hipFree(e->d_frame);
-    }
-    delete e;
-}
-
-rtc_status rtc_png_encoder_encode_device(rtc_png_encoder *e, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels) {
-    if (!e || !encode_args_ok(d_pixels, width, height, channels)) return RTC_ERR_ARG;
-    rtc_context *ctx = e->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const rtc_status st = encode_frame(e->sc, static_cast<const uint8_t *>(d_pixels), width, height, channels, ctx->stream);
-    if (st != RTC_OK) return st;
-    unsigned long long len = 0;
-    HIP_TRY(hipMemcpyAsync(&len, &e->sc.pinfo->file_bytes, sizeof len, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (len < RTC_PNG_FILE_FIXED + RTC_PNG_CHUNK_OVERHEAD || len > e->sc.out_cap) return RTC_ERR_DEVICE;
-    e->file.resize((size_t)len);
-    HIP_TRY(hipMemcpy(e->file.data(), e->sc.out, (size_t)len, hipMemcpyDeviceToHost));
-    return RTC_OK;
-}
-
-rtc_status rtc_png_encoder_render(rtc_png_encoder *e, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, float gamma) {
-    if (!e || !w || !cam || w->ctx != e->ctx) return RTC_ERR_ARG;
-    if (cam->hsize == 0 || cam->vsize == 0 || cam->hsize > 65535u || cam->vsize > 65535u) return RTC_ERR_ARG;
-    if (!(gamma > 0.0f) || !(gamma <= 3.4028235e38f)) return RTC_ERR_ARG;
-    rtc_context *ctx = e->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t channels = gamma == 1.0f ? 3u : 4u;
-    const uint32_t rows = channels == 3u ? cam->vsize : (cam->vsize + 7u) / 8u * 8u; // a view holds whole 8-row bands
-    const size_t bytes = (size_t)channels * cam->hsize * rows;
-    if (e->frame_cap < bytes) {
-        if (e->d_frame) (void)hipFree(e->d_frame);
-        e->d_frame = nullptr;
-        e->frame_cap = 0;
-        const hipError_t he = hipMalloc(reinterpret_cast<void **>(&e->d_frame), bytes);
-        if (he != hipSuccess) { (void)hipGetLastError(); return he == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        e->frame_cap = bytes;
-    }
-    rtc_status st = channels == 3u ? rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, nullptr, e->d_frame, flags)
-                                   : rtc_render_views_rgba8(ctx, w, cam, 1, mode, 0, 1, gamma, e->d_frame, rows, flags);
-    if (st == RTC_OK) st = rtc_context_fence(ctx); // a pipelined context rendered on a lane: the stream waits for it
-    if (st == RTC_OK) st = rtc_png_encoder_encode_device(e, e->d_frame, cam->hsize, cam->vsize, channels);
-    return st;
-}
-
-size_t rtc_png_encoder_bytes(const rtc_png_encoder *e, uint8_t *buf, size_t cap) {
-    if (!e || e->file.empty()) return 0;
-    if (buf) std::memcpy(buf, e->file.data(), std::min(cap, e->file.size()));
-    return e->file.size();
-}
-
-rtc_status rtc_png_encoder_write(const rtc_png_encoder *e, const char *path) {
-    if (!e || !path || e->file.empty()) return RTC_ERR_ARG;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return RTC_ERR_IO;
-    const bool ok = std::fwrite(e->file.data(), 1, e->file.size(), f) == e->file.size();
-    return (std::fclose(f) == 0 && ok) ? RTC_OK : RTC_ERR_IO;
 }

@@ -431,6 +431,60 @@ def test_lua_program_render_orbit_animation(rtc, scenes, O):
     ctx.close()
 
 
+@pytest.mark.parametrize("entry", ["rtc_lua_program_render_png", "rtc_lua_program_render_saved"])
+def test_lua_file_entries_stop_and_keep_the_pipeline_depth(rtc, entry):
+    """What test_lua_program_render_orbit_animation checks for the rows entry, for two encoded entries whose Python wrappers
+    take no callback (through their ctypes entry points): outputs in job order, a non-zero callback return stops the run
+    after that job, an in-order context is in order again afterwards and a pipelined one keeps its depth."""
+    import ctypes as C
+    import torch
+    from pathlib import Path
+    data = Path(rtc.__file__).resolve().parent / "data"
+    text = "FRAMES = 5 BALLS = 9 WIDTH, HEIGHT = 96, 64\n" + (data / "orbit_animation.lua").read_text()
+    prog = rtc.LuaProgram(text=text, base_dir=data)
+    jobs = prog.jobs
+    assert [j.kind for j in jobs] == ["AddFrame"] * 5 + ["Render"] and jobs[5].outfile.endswith(".ppm")
+
+    def run(ctx, stop_at=None):
+        got = []
+
+        def cb(_user, jp, index, fmt, ptr, nbytes):
+            got.append((index, fmt, C.string_at(ptr, nbytes)))
+            return 1 if index == stop_at else 0
+
+        fn = rtc.LUA_FILE_FN(cb)
+        assert getattr(rtc.lib(), entry)(ctx._h, prog._h, rtc.MODE_RENDER_ASYNC, 0, fn, None, None) == 0
+        return got
+
+    def lanes(ctx, dw, n=4):
+        q = torch.zeros((64, 96, 3), dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        seen = []
+        for _ in range(n):
+            dw.render_rows(jobs[0].camera, 0, 64, None, d_ptr8=q.data_ptr())
+            seen.append(ctx.last_launch_info()["lane"])
+        ctx.synchronize()
+        return seen
+
+    ctx = rtc.Context(0)
+    try:
+        dw = ctx.upload(jobs[0].world)
+        full = run(ctx)
+        first = rtc.LUA_OUT_PNG if entry.endswith("_png") else rtc.LUA_OUT_GIF_RECORD
+        last = rtc.LUA_OUT_RGB8 if entry.endswith("_png") else rtc.LUA_OUT_FILE
+        assert [(i, f) for i, f, _ in full] == [(i, first) for i in range(5)] + [(5, last)]
+        assert lanes(ctx, dw) == [0, 0, 0, 0]                 # in order again
+        ctx.set_pipeline(2)
+        stopped = run(ctx, stop_at=2)
+        assert stopped == full[:3]
+        seen = lanes(ctx, dw)                                 # still two lanes, dealt in turn
+        assert sorted(set(seen)) == [0, 1] and all(a != b for a, b in zip(seen, seen[1:])), seen
+        assert run(ctx) == full
+        dw.close()
+    finally:
+        ctx.close()
+
+
 def test_guided_chunks_render_the_same_frames(rtc, scenes):
     """Guided chunks (RenderParams::chunk_wgs): a launch's first workgroups render eight, four, three, two tiles each and its last
     ones one — only the tile -> workgroup mapping changes, so canvases, 8-bit frames and ray counts must equal the one-tile-per-
