@@ -206,22 +206,22 @@ void fill_camera(RenderParams &P, const rtc_camera *cam, uint32_t view = 0) {
 }
 
 void fill_world(RenderParams &P, const rtc_world *w) {
-    P.isect = w->d_isect;
-    P.kind = w->d_kind;
-    P.shade = w->d_shade;
-    P.prim = w->d_prim;
-    P.bound = w->d_bound;
-    P.isect_s = w->d_isect_s;
-    P.kind_s = w->d_kind_s;
-    P.bound_s = w->d_bound_s;
-    P.orig_s = w->d_orig_s;
-    P.gbound = w->d_gbound;
-    P.idtab = w->d_idtab;
-    P.pre = w->d_pre;
-    P.pre_s = w->d_pre_s;
+    P.isect = w->d_isect.get();
+    P.kind = w->d_kind.get();
+    P.shade = w->d_shade.get();
+    P.prim = w->d_prim.get();
+    P.bound = w->d_bound.get();
+    P.isect_s = w->d_isect_s.get();
+    P.kind_s = w->d_kind_s.get();
+    P.bound_s = w->d_bound_s.get();
+    P.orig_s = w->d_orig_s.get();
+    P.gbound = w->d_gbound.get();
+    P.idtab = w->d_idtab.get();
+    P.pre = w->d_pre.get();
+    P.pre_s = w->d_pre_s.get();
     P.pre_limit = w->pre_limit;
-    P.light_cnt = w->d_light_cnt;
-    P.light_list = w->d_light_list;
+    P.light_cnt = w->d_light_cnt.get();
+    P.light_list = w->d_light_list.get();
     P.light_reach = w->light_reach;
     P.light_cap = w->light_cap;
     P.n_unb = w->n_unb;
@@ -240,14 +240,8 @@ bool gamma_ok(float gamma) { return gamma > 0.f && std::isfinite(gamma); }
 // rtc_context::GammaSlot::seen (lane l: l, the context's own stream: MAX_LANES). See rtc_context::gamma_slot.
 rtc_status gamma_table(rtc_context *ctx, float gamma, hipStream_t stream, uint32_t bit, const DevGamma **out) {
     constexpr uint32_t NS = rtc_context::GAMMA_SLOTS;
-    if (!ctx->d_gamma) {
-        const hipError_t e = hipMalloc(&ctx->d_gamma, sizeof(DevGamma) * NS);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->d_gamma = nullptr;
-            return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE;
-        }
-    }
+    const rtc_status as = ctx->d_gamma.reserve(NS);
+    if (as != RTC_OK) return as;
     uint32_t s = 0;
     while (s < NS && !(ctx->gamma_slot[s].used && ctx->gamma_slot[s].gamma == gamma)) ++s;
     if (s == NS) { // a new gamma: a free slot, or — all taken — wait until nothing can read any table, then start afresh
@@ -263,7 +257,7 @@ rtc_status gamma_table(rtc_context *ctx, float gamma, hipStream_t stream, uint32
         const rtc_status st = rtc_gamma_build_table(gamma, &sl.host);
         if (st != RTC_OK) return st;
         if (!sl.ready) HIP_TRY(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(ctx->d_gamma + s, &sl.host, sizeof(DevGamma), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(ctx->d_gamma.get() + s, &sl.host, sizeof(DevGamma), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipEventRecord(sl.ready, stream));
         sl.used = true;
         sl.gamma = gamma;
@@ -272,8 +266,20 @@ rtc_status gamma_table(rtc_context *ctx, float gamma, hipStream_t stream, uint32
         HIP_TRY(hipStreamWaitEvent(stream, ctx->gamma_slot[s].ready, 0));
         ctx->gamma_slot[s].seen |= 1u << bit;
     }
-    *out = ctx->d_gamma + s;
+    *out = ctx->d_gamma.get() + s;
     return RTC_OK;
+}
+
+// The context's timing event pairs [ev_created, upto) (rtc_context::ev, ev_bin).
+hipError_t create_events(rtc_context *ctx, uint32_t upto) {
+    for (uint32_t k = ctx->ev_created; k < upto; ++k) {
+        for (hipEvent_t *e : {&ctx->ev[k][0], &ctx->ev[k][1], &ctx->ev_bin[k][0], &ctx->ev_bin[k][1]}) {
+            const hipError_t r = hipEventCreate(e);
+            if (r != hipSuccess) return r;
+        }
+        ctx->ev_created = k + 1;
+    }
+    return hipSuccess;
 }
 
 } // namespace
@@ -294,8 +300,8 @@ rtc_status rtc_context_create(int32_t device, void *stream, rtc_context **out) {
     ctx->device = device;
     ctx->stream = static_cast<hipStream_t>(stream); // NULL = the device's default stream
 
-    if (hipMalloc(&ctx->d_counters, sizeof(unsigned long long) * CNT_N * CNT_SLOTS) != hipSuccess ||
-        hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N * CNT_SLOTS, ctx->stream) != hipSuccess) {
+    if (ctx->d_counters.reserve(CNT_N * CNT_SLOTS) != RTC_OK ||
+        hipMemsetAsync(ctx->d_counters.get(), 0, sizeof(unsigned long long) * CNT_N * CNT_SLOTS, ctx->stream) != hipSuccess) {
         rtc_context_destroy(ctx);
         return RTC_ERR_DEVICE;
     }
@@ -339,10 +345,6 @@ void rtc_context_destroy(rtc_context *ctx) {
     (void)drain_lanes(ctx);
     for (hipStream_t &l : ctx->lane)
         if (l) { (void)hipStreamDestroy(l); l = nullptr; }
-    if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->d_canvas) (void)hipFree(ctx->d_canvas);
-    if (ctx->d_canvas8) (void)hipFree(ctx->d_canvas8);
-    if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
     for (rtc_context::GammaSlot &sl : ctx->gamma_slot)
         if (sl.ready) (void)hipEventDestroy(sl.ready);
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
@@ -353,7 +355,7 @@ void rtc_context_destroy(rtc_context *ctx) {
     for (auto &pair : ctx->ev_bin)
         for (hipEvent_t e : pair)
             if (e) (void)hipEventDestroy(e);
-    delete ctx;
+    delete ctx; // its device buffers too: the device is current and its streams are idle
 }
 
 rtc_status rtc_context_synchronize(rtc_context *ctx) {
@@ -570,38 +572,28 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
     w->light = *light;
     w->any_refl = any_refl;
     w->any_refr = any_refr;
-    bool ok = hipMalloc(&w->d_isect, sizeof(DevIsect) * na) == hipSuccess &&
-              hipMalloc(&w->d_kind, sizeof(uint32_t) * na) == hipSuccess &&
-              hipMalloc(&w->d_shade, sizeof(DevShade) * na) == hipSuccess &&
-              hipMalloc(&w->d_prim, sizeof(DevPrim) * na) == hipSuccess &&
-              hipMalloc(&w->d_bound, sizeof(DevBound) * na) == hipSuccess &&
-              hipMalloc(&w->d_isect_s, sizeof(DevIsect) * na) == hipSuccess &&
-              hipMalloc(&w->d_kind_s, sizeof(uint32_t) * na) == hipSuccess &&
-              hipMalloc(&w->d_bound_s, sizeof(DevBound) * na) == hipSuccess &&
-              hipMalloc(&w->d_orig_s, sizeof(uint32_t) * na) == hipSuccess &&
-              hipMalloc(&w->d_gbound, sizeof(DevBound) * gbound.size()) == hipSuccess &&
-              hipMalloc(&w->d_idtab, sizeof(DevIdEntry) * na) == hipSuccess &&
-              hipMalloc(&w->d_pre, sizeof(DevPre) * na) == hipSuccess &&
-              hipMalloc(&w->d_pre_s, sizeof(DevPre) * na) == hipSuccess;
     for (uint32_t i = 0; i < n; ++i)
         if (!std::isfinite(bound_s[i].r)) w->n_unb = i + 1u; // unbounded objects sort first (key 0)
-    ok = ok && hipMemcpy(w->d_isect, isect.data(), sizeof(DevIsect) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_kind, kind.data(), sizeof(uint32_t) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_shade, shade.data(), sizeof(DevShade) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_bound, bound.data(), sizeof(DevBound) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_isect_s, isect_s.data(), sizeof(DevIsect) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_kind_s, kind_s.data(), sizeof(uint32_t) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_bound_s, bound_s.data(), sizeof(DevBound) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_orig_s, orig_s.data(), sizeof(uint32_t) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_gbound, gbound.data(), sizeof(DevBound) * gbound.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_idtab, idtab.data(), sizeof(DevIdEntry) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_pre, pre.data(), sizeof(DevPre) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(w->d_pre_s, pre_s.data(), sizeof(DevPre) * na, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(w->d_prim, 0, sizeof(DevPrim) * na) == hipSuccess;
+    rtc_status st = RTC_OK;
+    auto upload = [&st](auto &buf, const auto &host) { if (st == RTC_OK) st = buf.upload(host.data(), host.size()); };
+    upload(w->d_isect, isect);
+    upload(w->d_kind, kind);
+    upload(w->d_shade, shade);
+    upload(w->d_bound, bound);
+    upload(w->d_isect_s, isect_s);
+    upload(w->d_kind_s, kind_s);
+    upload(w->d_bound_s, bound_s);
+    upload(w->d_orig_s, orig_s);
+    upload(w->d_gbound, gbound);
+    upload(w->d_idtab, idtab);
+    upload(w->d_pre, pre);
+    upload(w->d_pre_s, pre_s);
+    if (st == RTC_OK) st = w->d_prim.reserve(na);
+    if (st == RTC_OK) st = rtc_status_of(hipMemset(w->d_prim.get(), 0, sizeof(DevPrim) * na));
     // light-space shadow lists: every shadow segment ends at the light, so the objects a segment can meet
     // are listed per direction cell of a cube map around the light, once per World. Reach = twice the far side of the
     // farthest bounded object as seen from the light (longer segments fall back to the group walk).
-    if (ok && n >= 32) { // (a handful of objects: one cull step is cheaper than finding the cells — Criterion scene 33.5 vs 37.8 us)
+    if (st == RTC_OK && n >= 32) { // (a handful of objects: one cull step is cheaper than finding the cells — Criterion scene 33.5 vs 37.8 us)
         double far = 0.;
         for (uint32_t i = 0; i < n; ++i)
             if (std::isfinite(bound[i].r)) {
@@ -615,28 +607,26 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
             w->light_cap = cap;
             const size_t cells = 6u * (size_t)RTC_LIGHT_R * RTC_LIGHT_R, macros = 6u * (size_t)(RTC_LIGHT_R / 8u) * (RTC_LIGHT_R / 8u);
             // the lists are an optimisation (the shadow pass walks without them): a failed allocation must not fail the upload
-            const bool got = hipMalloc(&w->d_light_cells, sizeof(DevTileBundle) * (cells + macros)) == hipSuccess &&
-                             hipMalloc(&w->d_light_cnt, sizeof(uint32_t) * cells) == hipSuccess &&
-                             hipMalloc(&w->d_light_list, sizeof(uint32_t) * cells * cap) == hipSuccess;
+            const bool got = w->d_light_cells.reserve(cells + macros) == RTC_OK && w->d_light_cnt.reserve(cells) == RTC_OK &&
+                             w->d_light_list.reserve(cells * cap) == RTC_OK;
             if (got) {
-                ok = rtc_launch_light_lists(n, cap, w->d_bound, light->position, reach, w->d_light_cells, w->d_light_cells + cells, w->d_light_cnt,
-                                            w->d_light_list, ctx->stream) == hipSuccess &&
-                     hipStreamSynchronize(ctx->stream) == hipSuccess;
+                DevTileBundle *cell = w->d_light_cells.get();
+                st = rtc_status_of(rtc_launch_light_lists(n, cap, w->d_bound.get(), light->position, reach, cell, cell + cells,
+                                                          w->d_light_cnt.get(), w->d_light_list.get(), ctx->stream));
+                if (st == RTC_OK) st = rtc_status_of(hipStreamSynchronize(ctx->stream));
                 w->light_reach = reach;
             } else {
-                (void)hipGetLastError();
-                if (w->d_light_cells) (void)hipFree(w->d_light_cells);
-                if (w->d_light_cnt) (void)hipFree(w->d_light_cnt);
-                if (w->d_light_list) (void)hipFree(w->d_light_list);
-                w->d_light_cells = nullptr; w->d_light_cnt = nullptr; w->d_light_list = nullptr;
+                w->d_light_cells.reset();
+                w->d_light_cnt.reset();
+                w->d_light_list.reset();
                 w->light_cap = 0;
             }
         }
     }
-    if (!ok) {
-        const hipError_t e = hipGetLastError();
+    if (st != RTC_OK) {
+        (void)hipGetLastError();
         rtc_world_destroy(w);
-        return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE;
+        return st;
     }
     *out = w;
     return RTC_OK;
@@ -648,30 +638,55 @@ void rtc_world_destroy(rtc_world *w) {
         (void)hipSetDevice(w->device);
         (void)hipDeviceSynchronize();
     }
-    if (w->d_isect) (void)hipFree(w->d_isect);
-    if (w->d_kind) (void)hipFree(w->d_kind);
-    if (w->d_shade) (void)hipFree(w->d_shade);
-    if (w->d_prim) (void)hipFree(w->d_prim);
-    if (w->d_bound) (void)hipFree(w->d_bound);
-    if (w->d_isect_s) (void)hipFree(w->d_isect_s);
-    if (w->d_kind_s) (void)hipFree(w->d_kind_s);
-    if (w->d_bound_s) (void)hipFree(w->d_bound_s);
-    if (w->d_orig_s) (void)hipFree(w->d_orig_s);
-    if (w->d_gbound) (void)hipFree(w->d_gbound);
-    if (w->d_idtab) (void)hipFree(w->d_idtab);
-    if (w->d_pre) (void)hipFree(w->d_pre);
-    if (w->d_pre_s) (void)hipFree(w->d_pre_s);
     for (rtc_world::BinSet &b : w->bin) {
-        if (b.tile_cnt) (void)hipFree(b.tile_cnt);
-        if (b.tile_list) (void)hipFree(b.tile_list);
-        if (b.prim) (void)hipFree(b.prim);
         if (b.binned) (void)hipEventDestroy(b.binned);
         if (b.traced) (void)hipEventDestroy(b.traced);
     }
-    if (w->d_light_cells) (void)hipFree(w->d_light_cells);
-    if (w->d_light_cnt) (void)hipFree(w->d_light_cnt);
-    if (w->d_light_list) (void)hipFree(w->d_light_list);
-    delete w;
+    delete w; // its device buffers too, the device current and idle
+}
+
+// Readies binning set S for a launch: tile lists for `tiles` (view, tile) entries, grown to `tiles_alloc` when they are
+// smaller, and primary-ray records for `prims` (object, view) pairs, grown to `prims_alloc`. A pipelined launch (`sync`)
+// first waits for its lane, which may still read the set. False when there is no memory for the lists: they are an
+// optimisation, and the launch walks instead (same pixels).
+static bool ready_binset(rtc_context *ctx, rtc_world::BinSet &S, size_t tiles, size_t tiles_alloc, size_t prims, size_t prims_alloc,
+                         bool sync, hipStream_t stream) {
+    if (S.tile_list.capacity() < tiles * RTC_TILE_LIST_CAP) {
+        if (sync) (void)hipStreamSynchronize(stream);
+        S.tile_cnt.reset(); // both old lists go before either new one is allocated
+        S.tile_list.reset();
+        if (S.tile_cnt.reserve(tiles_alloc + RTC_BIN_ROW_WORDS, &ctx->render_allocs) != RTC_OK ||
+            S.tile_list.reserve(tiles_alloc * RTC_TILE_LIST_CAP, &ctx->render_allocs) != RTC_OK) {
+            S.tile_cnt.reset();
+            return false;
+        }
+    }
+    if (S.prim.capacity() < prims) {
+        if (sync) (void)hipStreamSynchronize(stream);
+        if (S.prim.reserve(prims_alloc, &ctx->render_allocs) != RTC_OK) return false;
+    }
+    return true;
+}
+
+// k_bin_tiles of the launch's views into set B on `stream` (timed by the event pair `ev`, if any), and the render
+// parameters that read the set.
+static hipError_t bin_tiles(RenderParams &P, const rtc_world *w, const rtc_world::BinSet &B, bool sky_rows, hipStream_t stream,
+                            const hipEvent_t *ev) {
+    uint32_t *cnt = B.tile_cnt.get() + RTC_BIN_ROW_WORDS;
+    const hipError_t e = rtc_launch_binning(P.views, P.nviews, P.W, P.H, w->n, w->d_bound_s.get(), w->d_gbound.get(), w->d_orig_s.get(),
+                                            w->ngroups, cnt, B.tile_list.get(), P.y0 / 8u, P.band_stride, stream, ev ? ev[0] : nullptr,
+                                            ev ? ev[1] : nullptr, w->d_isect_s.get(), w->d_kind_s.get(), w->n_unb, B.tile_cnt.get(),
+                                            w->d_isect.get(), B.prim.get());
+    if (e != hipSuccess) return e;
+    P.prim = B.prim.get();
+    P.tile_rows = sky_rows ? B.tile_cnt.get() : nullptr;
+    P.tile_cnt = cnt;
+    P.tile_list = B.tile_list.get();
+    P.tiles_x = (P.W + 7u) / 8u;
+    P.tiles_y = (P.H + 7u) / 8u;
+    P.bin_packed = RTC_BIN_PACKED(w->n) ? 1u : 0u;
+    P.n_unb = w->n_unb;
+    return hipSuccess;
 }
 
 // rows [y0, y1) in tile rows of 8, tile row k at image rows y0 + 8*k*band_stride; grid_y tile rows. gamma > 0: d_rgb8
@@ -692,7 +707,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     P.mode = mode;
     P.out = static_cast<double *>(d_rgb);
     P.out8 = static_cast<unsigned char *>(d_rgb8);
-    P.counters = ctx->d_counters;
+    P.counters = ctx->d_counters.get();
     P.rays = nullptr;
     P.remaining = RTC_MAX_REFLECTIONS; // render_pixel passes Camera::MAX_REFLECTIONS camera.rs:98
     int src;
@@ -715,18 +730,9 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     // that are launch-bound sample every n-th launch instead (rtc_context_set_timing)
     const bool timed = ctx->time_every != 0 && ctx->launches % ctx->time_every == 0;
     const uint32_t slot = (uint32_t)(ctx->timed % rtc_context::EV_RING);
-    if (timed && slot >= ctx->ev_created) { // next chunk of the ring
-        const uint32_t upto = std::min<uint32_t>(rtc_context::EV_RING, ctx->ev_created + rtc_context::EV_CHUNK);
-        for (uint32_t k = ctx->ev_created; k < upto; ++k) {
-            HIP_TRY(hipEventCreate(&ctx->ev[k][0]));
-            HIP_TRY(hipEventCreate(&ctx->ev[k][1]));
-            HIP_TRY(hipEventCreate(&ctx->ev_bin[k][0]));
-            HIP_TRY(hipEventCreate(&ctx->ev_bin[k][1]));
-            ctx->ev_created = k + 1;
-        }
-    }
+    if (timed && slot >= ctx->ev_created) // next chunk of the ring
+        HIP_TRY(create_events(ctx, std::min<uint32_t>(rtc_context::EV_RING, ctx->ev_created + rtc_context::EV_CHUNK)));
     hipEvent_t *pair = ctx->ev[slot], *pair_bin = ctx->ev_bin[slot];
-    if (timed) ctx->bin_timed[slot] = false;
     // Which stream. A pipelined context deals the launches round-robin over its lanes; the brute-force variants share one
     // per-render table (w->d_prim) and stay in order on lane 0.
     const bool piped = ctx->lanes > 1;
@@ -755,44 +761,8 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         // lane-local lists: the binning kernel precedes the render kernel on the lane's own stream and runs beside the other
         // lanes' render kernels — no events. Sized for the largest launch seen (grow-only; growing waits for the lane).
         rtc_world::BinSet &B = w->bin[lane];
-        if (B.tiles_cap < tiles) {
-            (void)hipStreamSynchronize(stream);
-            if (B.tile_cnt) (void)hipFree(B.tile_cnt);
-            if (B.tile_list) (void)hipFree(B.tile_list);
-            B.tile_cnt = nullptr; B.tile_list = nullptr; B.tiles_cap = 0;
-            ++ctx->render_allocs;
-            const bool got = hipMalloc(&B.tile_cnt, sizeof(uint32_t) * (tiles + RTC_BIN_ROW_WORDS)) == hipSuccess &&
-                             (++ctx->render_allocs, hipMalloc(&B.tile_list, sizeof(uint32_t) * tiles * RTC_TILE_LIST_CAP) == hipSuccess);
-            if (got) B.tiles_cap = tiles;
-            else { // the lists are an optimisation: without memory for them the launch walks (same pixels)
-                if (B.tile_cnt) (void)hipFree(B.tile_cnt);
-                B.tile_cnt = nullptr; B.tile_list = nullptr;
-                (void)hipGetLastError();
-                bin_ok = false;
-            }
-        }
-        if (bin_ok && B.prim_cap < (size_t)w->n * nviews) {
-            (void)hipStreamSynchronize(stream);
-            if (B.prim) (void)hipFree(B.prim);
-            B.prim = nullptr; B.prim_cap = 0;
-            ++ctx->render_allocs;
-            if (hipMalloc(&B.prim, sizeof(DevPrim) * (size_t)w->n * nviews) == hipSuccess) B.prim_cap = (size_t)w->n * nviews;
-            else { (void)hipGetLastError(); bin_ok = false; }
-        }
-        if (bin_ok) {
-            HIP_TRY(rtc_launch_binning(P.views, nviews, cam->hsize, cam->vsize, w->n, w->d_bound_s, w->d_gbound, w->d_orig_s, w->ngroups,
-                                       B.tile_cnt + RTC_BIN_ROW_WORDS, B.tile_list, y0 / 8u, band_stride, stream, timed ? pair_bin[0] : nullptr,
-                                       timed ? pair_bin[1] : nullptr, w->d_isect_s, w->d_kind_s, w->n_unb, B.tile_cnt, w->d_isect, B.prim));
-            if (timed) ctx->bin_timed[slot] = true;
-            P.prim = B.prim;
-            P.tile_rows = ctx->sky_rows ? B.tile_cnt : nullptr;
-            P.tile_cnt = B.tile_cnt + RTC_BIN_ROW_WORDS;
-            P.tile_list = B.tile_list;
-            P.tiles_x = tiles_x;
-            P.tiles_y = tiles_y;
-            P.bin_packed = RTC_BIN_PACKED(w->n) ? 1u : 0u;
-            P.n_unb = w->n_unb;
-        }
+        bin_ok = ready_binset(ctx, B, tiles, tiles, (size_t)w->n * nviews, (size_t)w->n * nviews, true, stream);
+        if (bin_ok) HIP_TRY(bin_tiles(P, w, B, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
     } else if (bin_ok) {
         if (!ctx->side_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
         // Capacity. Both sets are made ready by the FIRST binned launch, and for RTC_MAX_VIEWS views while that stays within
@@ -809,30 +779,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
                 HIP_TRY(hipEventCreateWithFlags(&S.binned, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&S.traced, hipEventDisableTiming));
             }
-            if (S.tiles_cap < tiles) { // (hipFree waits for the device: nothing reads the old buffers any more)
-                if (S.tile_cnt) (void)hipFree(S.tile_cnt);
-                if (S.tile_list) (void)hipFree(S.tile_list);
-                S.tile_cnt = nullptr; S.tile_list = nullptr;
-                S.tiles_cap = 0;
-                ++ctx->render_allocs;
-                const bool got = hipMalloc(&S.tile_cnt, sizeof(uint32_t) * (tiles_alloc + RTC_BIN_ROW_WORDS)) == hipSuccess &&
-                                 (++ctx->render_allocs, hipMalloc(&S.tile_list, sizeof(uint32_t) * tiles_alloc * RTC_TILE_LIST_CAP) == hipSuccess);
-                if (got) S.tiles_cap = tiles_alloc;
-                else {
-                    if (S.tile_cnt) (void)hipFree(S.tile_cnt);
-                    S.tile_cnt = nullptr; S.tile_list = nullptr;
-                    (void)hipGetLastError();
-                    bin_ok = false;
-                }
-            }
-            if (bin_ok && S.prim_cap < (size_t)w->n * nviews) {
-                if (S.prim) (void)hipFree(S.prim);
-                S.prim = nullptr; S.prim_cap = 0;
-                ++ctx->render_allocs;
-                const size_t want = (size_t)w->n * std::max(alloc_views, nviews);
-                if (hipMalloc(&S.prim, sizeof(DevPrim) * want) == hipSuccess) S.prim_cap = want;
-                else { (void)hipGetLastError(); bin_ok = false; }
-            }
+            bin_ok = ready_binset(ctx, S, tiles, tiles_alloc, (size_t)w->n * nviews, (size_t)w->n * std::max(alloc_views, nviews), false, stream);
         }
     }
     if (bin_ok && !piped) {
@@ -841,24 +788,14 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         // to the side stream: it runs beside the PREVIOUS launch's render kernel, which still reads the other set. It must
         // wait for the render kernel that last read THIS set (two launches ago); the render stream waits for the binning.
         HIP_TRY(hipStreamWaitEvent(ctx->side_stream, B.traced, 0)); // never recorded: no wait
-        HIP_TRY(rtc_launch_binning(P.views, nviews, cam->hsize, cam->vsize, w->n, w->d_bound_s, w->d_gbound, w->d_orig_s, w->ngroups,
-                                   B.tile_cnt + RTC_BIN_ROW_WORDS, B.tile_list, y0 / 8u, band_stride, ctx->side_stream, timed ? pair_bin[0] : nullptr,
-                                   timed ? pair_bin[1] : nullptr, w->d_isect_s, w->d_kind_s, w->n_unb, B.tile_cnt, w->d_isect, B.prim));
-        if (timed) ctx->bin_timed[slot] = true;
-        P.prim = B.prim;
+        HIP_TRY(bin_tiles(P, w, B, ctx->sky_rows, ctx->side_stream, timed ? pair_bin : nullptr));
         HIP_TRY(hipEventRecord(B.binned, ctx->side_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, B.binned, 0));
-        P.tile_rows = ctx->sky_rows ? B.tile_cnt : nullptr;
-        P.tile_cnt = B.tile_cnt + RTC_BIN_ROW_WORDS;
-        P.tile_list = B.tile_list;
-        P.tiles_x = tiles_x;
-        P.tiles_y = tiles_y;
-        P.bin_packed = RTC_BIN_PACKED(w->n) ? 1u : 0u;
-        P.n_unb = w->n_unb;
         binset = &B;
     }
+    if (timed) ctx->bin_timed[slot] = P.tile_cnt != nullptr;
     // per-render prologue table of the brute-force variants (the culled kernels do not use it)
-    if (src != SRC_CULL && src != SRC_CULL2) HIP_TRY(rtc_launch_prep(w->d_isect, w->d_prim, w->n, P.views[0].vinv, stream));
+    if (src != SRC_CULL && src != SRC_CULL2) HIP_TRY(rtc_launch_prep(w->d_isect.get(), w->d_prim.get(), w->n, P.views[0].vinv, stream));
     P.total_blocks = P.grid_x * P.grid_y * nviews;
     P.reps = ctx->tiles_per_wg;
     // Guided chunks (RenderParams::chunk_wgs): with `slots` workgroups resident at once, the launch's last f x slots tiles go one
@@ -940,7 +877,7 @@ rtc_status rtc_stats_read(rtc_context *ctx, rtc_stats *out) {
     HIP_TRY(hipSetDevice(ctx->device));
     std::vector<unsigned long long> slots((size_t)CNT_N * CNT_SLOTS);
     HIP_TRY(drain_lanes(ctx));
-    HIP_TRY(hipMemcpyAsync(slots.data(), ctx->d_counters, sizeof(unsigned long long) * slots.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(slots.data(), ctx->d_counters.get(), sizeof(unsigned long long) * slots.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     unsigned long long h[CNT_N] = {0};
     for (int sl = 0; sl < CNT_SLOTS; ++sl)
@@ -969,7 +906,7 @@ rtc_status rtc_stats_reset(rtc_context *ctx) {
     if (!ctx) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(drain_lanes(ctx));
-    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N * CNT_SLOTS, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_counters.get(), 0, sizeof(unsigned long long) * CNT_N * CNT_SLOTS, ctx->stream));
     if (ctx->lanes > 1) HIP_TRY(hipStreamSynchronize(ctx->stream)); // the lanes are not ordered behind the stream
     ctx->pixels = 0;
     return RTC_OK;
@@ -979,14 +916,7 @@ rtc_status rtc_context_set_timing(rtc_context *ctx, uint32_t every) {
     if (!ctx) return RTC_ERR_ARG;
     if (every != 0) { // a caller that asks for timings gets the first 64 event pairs now, not 16 at a time in the middle of its timed loop
         HIP_TRY(hipSetDevice(ctx->device));
-        const uint32_t upto = std::min<uint32_t>(rtc_context::EV_RING, 64u);
-        for (uint32_t k = ctx->ev_created; k < upto; ++k) {
-            HIP_TRY(hipEventCreate(&ctx->ev[k][0]));
-            HIP_TRY(hipEventCreate(&ctx->ev[k][1]));
-            HIP_TRY(hipEventCreate(&ctx->ev_bin[k][0]));
-            HIP_TRY(hipEventCreate(&ctx->ev_bin[k][1]));
-            ctx->ev_created = k + 1;
-        }
+        HIP_TRY(create_events(ctx, std::min<uint32_t>(rtc_context::EV_RING, 64u)));
     }
     ctx->time_every = every;
     ctx->launches = 0; // the next launch is sampled (if any is), and the ring starts afresh
@@ -1094,85 +1024,45 @@ rtc_status rtc_render_views_rgba8(rtc_context *ctx, const rtc_world *w, const rt
     return render_views(ctx, w, cams, nviews, mode, first_band, band_stride, nullptr, d_rgba8, view_rows, flags, gamma);
 }
 
-rtc_status rtc_render(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
-                      double *rgb, rtc_stats *stats) {
-    if (!ctx || !w || !cam || !rgb || w->ctx != ctx) return RTC_ERR_ARG;
+// rtc_render, rtc_render_rgb8 and rtc_render_rgba8: the whole frame into the context's grow-only canvas (no hipMalloc /
+// hipFree, a device sync, per frame), then to `host`. f64: RGB doubles; else 8-bit rows, RGBA at `gamma` when gamma > 0
+// and Color::scale's RGB otherwise (only those rows leave the kernel: no f64 canvas is written).
+static rtc_status render_frame(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, bool f64,
+                               float gamma, void *host, rtc_stats *stats) {
+    if (!ctx || !w || !cam || !host || w->ctx != ctx) return RTC_ERR_ARG;
+    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || cam->samples > 255u) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * 3 * (size_t)cam->hsize * cam->vsize;
-    if (bytes == 0) return RTC_ERR_ARG;
-    if (ctx->canvas_bytes < bytes) { // grow-only scratch canvas: no hipMalloc/hipFree (a device sync) per frame
-        if (ctx->d_canvas) (void)hipFree(ctx->d_canvas);
-        ctx->d_canvas = nullptr;
-        ctx->canvas_bytes = 0;
-        ++ctx->render_allocs;
-        const hipError_t e = hipMalloc(&ctx->d_canvas, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        ctx->canvas_bytes = bytes;
-    }
-    double *d = ctx->d_canvas;
-    rtc_status st = RTC_OK;
+    const size_t px = (size_t)cam->hsize * cam->vsize, bytes = px * (f64 ? 3 * sizeof(double) : gamma > 0.f ? 4u : 3u);
+    rtc_status st = f64 ? ctx->d_canvas.reserve(3 * px, &ctx->render_allocs) : ctx->d_canvas8.reserve(bytes, &ctx->render_allocs);
+    if (st != RTC_OK) return st;
+    void *d = f64 ? (void *)ctx->d_canvas.get() : (void *)ctx->d_canvas8.get();
     if (stats) st = rtc_stats_reset(ctx);
-    if (st == RTC_OK) st = rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, d, nullptr, flags);
+    if (st == RTC_OK)
+        st = render_launch(ctx, w, cam, mode, 0, cam->vsize, 1u, (cam->vsize + 7u) / 8u, f64 ? d : nullptr, f64 ? nullptr : d, flags, 1u, 0u,
+                           gamma);
     if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE; // pipelined context: the copy below is on the stream
-    // `rgb` from rtc_host_alloc (page-locked) is filled by one DMA at link speed; pageable memory
+    // `host` from rtc_host_alloc (page-locked) is filled by one DMA at link speed; pageable memory
     // goes through the runtime's bounce buffers (several times slower)
-    if (st == RTC_OK && hipMemcpyAsync(rgb, d, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
+    if (st == RTC_OK && hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
     if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
     if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
     return st;
+}
+
+rtc_status rtc_render(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                      double *rgb, rtc_stats *stats) {
+    return render_frame(ctx, w, cam, mode, flags, true, 0.f, rgb, stats);
 }
 
 rtc_status rtc_render_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
                            uint8_t *rgb8, rtc_stats *stats) {
-    if (!ctx || !w || !cam || !rgb8 || w->ctx != ctx) return RTC_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)3 * cam->hsize * cam->vsize;
-    if (bytes == 0) return RTC_ERR_ARG;
-    if (ctx->canvas8_bytes < bytes) { // grow-only, like rtc_render's f64 scratch
-        if (ctx->d_canvas8) (void)hipFree(ctx->d_canvas8);
-        ctx->d_canvas8 = nullptr;
-        ctx->canvas8_bytes = 0;
-        ++ctx->render_allocs;
-        const hipError_t e = hipMalloc(&ctx->d_canvas8, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        ctx->canvas8_bytes = bytes;
-    }
-    rtc_status st = RTC_OK;
-    if (stats) st = rtc_stats_reset(ctx);
-    // only the 8-bit rows leave the kernel: no f64 canvas is written (d_rgb = NULL)
-    if (st == RTC_OK) st = rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, nullptr, ctx->d_canvas8, flags);
-    if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipMemcpyAsync(rgb8, ctx->d_canvas8, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
-    return st;
+    return render_frame(ctx, w, cam, mode, flags, false, 0.f, rgb8, stats);
 }
 
 rtc_status rtc_render_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, float gamma,
                             uint8_t *rgba8, rtc_stats *stats) {
-    if (!ctx || !w || !cam || !rgba8 || w->ctx != ctx || !gamma_ok(gamma)) return RTC_ERR_ARG;
-    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || cam->samples > 255u) return RTC_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)4 * cam->hsize * cam->vsize;
-    if (ctx->canvas8_bytes < bytes) { // the 8-bit scratch of rtc_render_rgb8, grown to 4 B/pixel
-        if (ctx->d_canvas8) (void)hipFree(ctx->d_canvas8);
-        ctx->d_canvas8 = nullptr;
-        ctx->canvas8_bytes = 0;
-        ++ctx->render_allocs;
-        const hipError_t e = hipMalloc(&ctx->d_canvas8, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        ctx->canvas8_bytes = bytes;
-    }
-    rtc_status st = RTC_OK;
-    if (stats) st = rtc_stats_reset(ctx);
-    // only the RGBA rows leave the kernel: no f64 canvas is written
-    if (st == RTC_OK)
-        st = render_launch(ctx, w, cam, mode, 0, cam->vsize, 1u, (cam->vsize + 7u) / 8u, nullptr, ctx->d_canvas8, flags, 1u, 0u, gamma);
-    if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipMemcpyAsync(rgba8, ctx->d_canvas8, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && stats) st = rtc_stats_read(ctx, stats);
-    return st;
+    if (!gamma_ok(gamma)) return RTC_ERR_ARG;
+    return render_frame(ctx, w, cam, mode, flags, false, gamma, rgba8, stats);
 }
 
 rtc_status rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint32_t width, uint32_t rows, float gamma, void *d_rgba8) {
@@ -1221,13 +1111,12 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
     if (remaining > RTC_MAX_REFLECTIONS) return RTC_ERR_ARG; // frame stack depth of the kernel = Camera::MAX_REFLECTIONS (camera.rs:31)
     if (n == 0) return RTC_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    double *d_rays = nullptr, *d_rgb = nullptr;
-    rtc_hit *d_hits = nullptr;
+    DevBuf<double> d_rays, d_rgb;
+    DevBuf<rtc_hit> d_hits;
     rtc_status st = RTC_OK;
-    if (hipMalloc(&d_rays, sizeof(double) * 6 * n) != hipSuccess || hipMalloc(&d_rgb, sizeof(double) * 3 * n) != hipSuccess ||
-        (hits && hipMalloc(&d_hits, sizeof(rtc_hit) * n) != hipSuccess))
+    if (d_rays.reserve((size_t)6 * n) != RTC_OK || d_rgb.reserve((size_t)3 * n) != RTC_OK || (hits && d_hits.reserve(n) != RTC_OK))
         st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipMemcpyAsync(d_rays, rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    if (st == RTC_OK && hipMemcpyAsync(d_rays.get(), rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;
     if (st == RTC_OK) {
         RenderParams P;
@@ -1235,12 +1124,12 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         fill_world(P, w);
         if (!ctx->light_lists) P.light_cnt = nullptr;
         P.W = n; P.H = 1; P.y0 = 0; P.y1 = 1; P.mode = RTC_MODE_RENDER_ASYNC; P.samples = 1;
-        P.out = d_rgb;
+        P.out = d_rgb.get();
         P.counters = nullptr;
-        P.rays = d_rays;
+        P.rays = d_rays.get();
         P.nrays = n;
         P.remaining = remaining;
-        P.hits = d_hits;
+        P.hits = d_hits.get();
         int src;
         size_t lds_bytes;
         choose_source(ctx, w->n, flags, &src, &P.tile_cap, &lds_bytes);
@@ -1256,14 +1145,11 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
                              nullptr) != hipSuccess)
             st = RTC_ERR_DEVICE;
     }
-    if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hits && hipMemcpyAsync(hits, d_hits, sizeof(rtc_hit) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    if (st == RTC_OK && hits && hipMemcpyAsync(hits, d_hits.get(), sizeof(rtc_hit) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (d_rays) (void)hipFree(d_rays);
-    if (d_rgb) (void)hipFree(d_rgb);
-    if (d_hits) (void)hipFree(d_hits);
     return st;
 }
 
@@ -1271,19 +1157,12 @@ rtc_status rtc_device_arith(rtc_context *ctx, uint32_t op, const double *a, cons
     if (!ctx || !a || !out || op > 6 || (op == 1 && !b) || (op == 2 && !b)) return RTC_ERR_ARG;
     if (n == 0) return RTC_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
+    DevBuf<double> da, db, dout;
     rtc_status st = RTC_OK;
-    const size_t bytes = sizeof(double) * n;
-    if (hipMalloc(&da, bytes) != hipSuccess || hipMalloc(&db, bytes) != hipSuccess || hipMalloc(&dout, bytes) != hipSuccess)
-        st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipMemcpy(da, a, bytes, hipMemcpyHostToDevice) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipMemcpy(db, b ? b : a, bytes, hipMemcpyHostToDevice) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && rtc_launch_arith(op, da, db, n, dout, ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
+    if (da.upload(a, n) != RTC_OK || db.upload(b ? b : a, n) != RTC_OK || dout.reserve(n) != RTC_OK) st = RTC_ERR_DEVICE;
+    if (st == RTC_OK && rtc_launch_arith(op, da.get(), db.get(), n, dout.get(), ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
     if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (st == RTC_OK && hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) != hipSuccess) st = RTC_ERR_DEVICE;
-    if (da) (void)hipFree(da);
-    if (db) (void)hipFree(db);
-    if (dout) (void)hipFree(dout);
+    if (st == RTC_OK && hipMemcpy(out, dout.get(), sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) st = RTC_ERR_DEVICE;
     return st;
 }
 

@@ -88,17 +88,6 @@ rtc_status RtcEncoder::enqueue(const RtcEncodeJob &job, const void *d_pixels, ui
     }
 }
 
-void RtcEncoder::release() {
-    rtc_gif_release(gif);
-    rtc_jpeg_release(jpeg);
-    rtc_png_release(png);
-    rtc_image_pack_release(pack);
-    gif = nullptr;
-    jpeg = nullptr;
-    png = nullptr;
-    pack = nullptr;
-}
-
 // ---- the encoder objects --------------------------------------------------------------------------------------------
 
 // What every encoder object is: bound to a context, its encoder's scratch, the render target of its render entry
@@ -106,8 +95,7 @@ void RtcEncoder::release() {
 struct RtcEncoderObject {
     rtc_context *ctx = nullptr;
     RtcEncoder enc;
-    uint8_t *d_frame = nullptr;
-    size_t frame_cap = 0;
+    DevBuf<uint8_t> d_frame;
     std::vector<uint8_t> file;
 };
 struct rtc_gif_writer : RtcEncoderObject {
@@ -131,12 +119,8 @@ rtc_status create(rtc_context *ctx, T **out) {
 template <typename T>
 void destroy(T *o) {
     if (!o) return;
-    if (hipSetDevice(o->ctx->device) == hipSuccess) {
-        (void)hipStreamSynchronize(o->ctx->stream);
-        o->enc.release();
-        if (o->d_frame) (void)hipFree(o->d_frame);
-    }
-    delete o;
+    if (hipSetDevice(o->ctx->device) == hipSuccess) (void)hipStreamSynchronize(o->ctx->stream);
+    delete o; // its device buffers too, after the stream that used them
 }
 
 // `job` for the frame at d_pixels on the context's stream; blocks until the file is on the host at file[at..] (file is
@@ -173,16 +157,10 @@ rtc_status render(RtcEncoderObject *o, const rtc_world *w, const rtc_camera *cam
     const uint32_t rows = *channels == 3u ? cam->vsize : (cam->vsize + 7u) / 8u * 8u; // a view holds whole 8-row bands
     const size_t bytes = (size_t)*channels * cam->hsize * rows;
     if (bytes == 0) return RTC_ERR_ARG;
-    if (o->frame_cap < bytes) {
-        if (o->d_frame) (void)hipFree(o->d_frame);
-        o->d_frame = nullptr;
-        o->frame_cap = 0;
-        const hipError_t he = hipMalloc(reinterpret_cast<void **>(&o->d_frame), bytes);
-        if (he != hipSuccess) { (void)hipGetLastError(); return he == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        o->frame_cap = bytes;
-    }
-    rtc_status st = *channels == 3u ? rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, nullptr, o->d_frame, flags)
-                                    : rtc_render_views_rgba8(ctx, w, cam, 1, mode, 0, 1, gamma, o->d_frame, rows, flags);
+    rtc_status st = o->d_frame.reserve(bytes);
+    if (st != RTC_OK) return st;
+    st = *channels == 3u ? rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, nullptr, o->d_frame.get(), flags)
+                         : rtc_render_views_rgba8(ctx, w, cam, 1, mode, 0, 1, gamma, o->d_frame.get(), rows, flags);
     if (st == RTC_OK) st = rtc_context_fence(ctx); // a pipelined context rendered on a lane: the stream waits for it
     return st;
 }
@@ -248,7 +226,7 @@ rtc_status rtc_gif_writer_render(rtc_gif_writer *g, const rtc_world *w, const rt
     if (!g->file.empty() && (cam->hsize != g->width || cam->vsize != g->height)) return RTC_ERR_ARG;
     uint32_t channels = 0;
     const rtc_status st = render(g, w, cam, mode, flags, 1.0f, &channels);
-    return st == RTC_OK ? rtc_gif_writer_append_device(g, g->d_frame, cam->hsize, cam->vsize) : st;
+    return st == RTC_OK ? rtc_gif_writer_append_device(g, g->d_frame.get(), cam->hsize, cam->vsize) : st;
 }
 
 size_t rtc_gif_writer_bytes(const rtc_gif_writer *g, uint8_t *buf, size_t cap) { return bytes_of(g, buf, cap, 0x3B); }
@@ -270,7 +248,7 @@ rtc_status rtc_jpeg_encoder_render(rtc_jpeg_encoder *e, const rtc_world *w, cons
     if (!gamma_ok(gamma)) return RTC_ERR_ARG;
     uint32_t channels = 0;
     const rtc_status st = render(e, w, cam, mode, flags, gamma, &channels);
-    return st == RTC_OK ? rtc_jpeg_encoder_encode_device(e, e->d_frame, cam->hsize, cam->vsize, channels, quality) : st;
+    return st == RTC_OK ? rtc_jpeg_encoder_encode_device(e, e->d_frame.get(), cam->hsize, cam->vsize, channels, quality) : st;
 }
 
 size_t rtc_jpeg_encoder_bytes(const rtc_jpeg_encoder *e, uint8_t *buf, size_t cap) { return bytes_of(e, buf, cap, 0); }
@@ -290,7 +268,7 @@ rtc_status rtc_png_encoder_render(rtc_png_encoder *e, const rtc_world *w, const 
     if (!gamma_ok(gamma)) return RTC_ERR_ARG;
     uint32_t channels = 0;
     const rtc_status st = render(e, w, cam, mode, flags, gamma, &channels);
-    return st == RTC_OK ? rtc_png_encoder_encode_device(e, e->d_frame, cam->hsize, cam->vsize, channels) : st;
+    return st == RTC_OK ? rtc_png_encoder_encode_device(e, e->d_frame.get(), cam->hsize, cam->vsize, channels) : st;
 }
 
 size_t rtc_png_encoder_bytes(const rtc_png_encoder *e, uint8_t *buf, size_t cap) { return bytes_of(e, buf, cap, 0); }
@@ -312,7 +290,7 @@ rtc_status rtc_image_encoder_render(rtc_image_encoder *e, uint32_t format, const
     if (!gamma_ok(gamma)) return RTC_ERR_ARG;
     uint32_t channels = 0;
     const rtc_status st = render(e, w, cam, mode, flags, gamma, &channels);
-    return st == RTC_OK ? rtc_image_encoder_encode_device(e, format, e->d_frame, cam->hsize, cam->vsize, channels) : st;
+    return st == RTC_OK ? rtc_image_encoder_encode_device(e, format, e->d_frame.get(), cam->hsize, cam->vsize, channels) : st;
 }
 
 size_t rtc_image_encoder_bytes(const rtc_image_encoder *e, uint8_t *buf, size_t cap) { return bytes_of(e, buf, cap, 0); }

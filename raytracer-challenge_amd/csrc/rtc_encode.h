@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rtc.h"
+#include "rtc_devmem.h"
 
 // What to produce from a frame in device memory.
 struct RtcEncodeJob {
@@ -49,36 +50,74 @@ struct RtcEncoded {
 const uint8_t *rtc_encode_finish(const RtcEncoded &e, unsigned long long len, uint8_t *file, std::vector<uint8_t> &text,
                                  size_t *nbytes);
 
-// Each file's chain: its scratch is created by the first enqueue (into `sc`) and grow-only; the arguments are checked by
-// the callers. The input is height*width*channels bytes (GIF: channels 3).
-struct GifScratch;
-struct JpegScratch;
-struct PngScratch;
-struct PackScratch;
-rtc_status rtc_gif_enqueue(GifScratch *&sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s, RtcEncoded *e);
-void rtc_gif_release(GifScratch *sc);
-rtc_status rtc_jpeg_enqueue(JpegScratch *&sc, const uint8_t *d_pixels, uint32_t width, uint32_t height, uint32_t channels,
-                            int32_t quality, hipStream_t s, RtcEncoded *e);
-void rtc_jpeg_release(JpegScratch *sc);
-rtc_status rtc_png_enqueue(PngScratch *&sc, const uint8_t *d_pixels, uint32_t width, uint32_t height, uint32_t channels,
-                           hipStream_t s, RtcEncoded *e);
-void rtc_png_release(PngScratch *sc);
-// k_image_pack: a packed file of the save table, or a raw R,G,B / R,G,B,255 packing (RTC_IMAGE_RAW_*)
-rtc_status rtc_image_pack_enqueue(PackScratch *&sc, uint32_t format, const uint8_t *d_pixels, uint32_t width, uint32_t height,
-                                  uint32_t channels, hipStream_t s, RtcEncoded *e);
-void rtc_image_pack_release(PackScratch *sc);
+// Each chain's grow-only scratch: one device block, carved by its reserve() (in the chain's file) when an enqueue needs
+// more. The info records are of the chain's own types.
+struct GifScratch {
+    size_t px_cap = 0;      // pixels the buffers below are sized for
+    DevBuf<uint8_t> block;  // the parts cleared per frame first
+    uint32_t *bitmap = nullptr, *cnt = nullptr, *pal32 = nullptr;
+    unsigned long long *boxsum = nullptr;
+    size_t clear_bytes = 0;
+    uint32_t *blockcnt = nullptr;
+    void *info = nullptr; // GifInfo
+    uint8_t *lut = nullptr, *idx = nullptr, *seg = nullptr, *record = nullptr;
+    uint32_t *seglen = nullptr;
+    unsigned long long *segoff = nullptr;
+    size_t record_cap = 0;
+    rtc_status reserve(size_t n);
+};
+struct JpegScratch {
+    size_t mcu_cap = 0;
+    DevBuf<uint8_t> block;
+    int16_t *coef = nullptr;
+    uint32_t *acbits = nullptr, *mcu_off = nullptr, *ffcnt = nullptr;
+    int32_t *dc = nullptr;
+    unsigned long long *group = nullptr, *words = nullptr, *chunk_off = nullptr;
+    void *info = nullptr; // JpegInfo
+    uint8_t *out = nullptr;
+    size_t nwords = 0, data_max = 0; // the packed stream's buffer: words, and its worst case in bytes
+    rtc_status reserve(size_t nmcu);
+};
+struct PngScratch {
+    size_t n_cap = 0;
+    DevBuf<uint8_t> block;
+    uint8_t *filt = nullptr, *out = nullptr;
+    uint16_t *prev = nullptr; // then T, the token flags
+    uint32_t *M = nullptr;
+    unsigned long long *words = nullptr, *chunk_off = nullptr;
+    void *info = nullptr, *pinfo = nullptr; // SegInfo[], PngInfo
+    size_t out_cap = 0;
+    rtc_status reserve(size_t n);
+};
+struct PackScratch {
+    DevBuf<uint8_t> out, d_hdr;
+    uint8_t *h_hdr = nullptr; // d_hdr's page-locked source (the upload is asynchronous; the source stays until the next file)
+    size_t hdr_cap = 0;
+    DevBuf<unsigned long long> d_len;
+    rtc_status header(size_t bytes);
+    ~PackScratch();
+};
 
-// The scratch of every chain, each created on first use, all released together (rtc_encode.cpp).
+// The chains, their arguments checked by the callers. The input is height*width*channels bytes (GIF: channels 3).
+rtc_status rtc_gif_enqueue(GifScratch &sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s, RtcEncoded *e);
+rtc_status rtc_jpeg_enqueue(JpegScratch &sc, const uint8_t *d_pixels, uint32_t width, uint32_t height, uint32_t channels,
+                            int32_t quality, hipStream_t s, RtcEncoded *e);
+rtc_status rtc_png_enqueue(PngScratch &sc, const uint8_t *d_pixels, uint32_t width, uint32_t height, uint32_t channels,
+                           hipStream_t s, RtcEncoded *e);
+// k_image_pack: a packed file of the save table, or a raw R,G,B / R,G,B,255 packing (RTC_IMAGE_RAW_*)
+rtc_status rtc_image_pack_enqueue(PackScratch &sc, uint32_t format, const uint8_t *d_pixels, uint32_t width, uint32_t height,
+                                  uint32_t channels, hipStream_t s, RtcEncoded *e);
+
+// The scratch of every chain. Its owner makes its device current and waits for its streams before letting it go.
 struct RtcEncoder {
-    GifScratch *gif = nullptr;
-    JpegScratch *jpeg = nullptr;
-    PngScratch *png = nullptr;
-    PackScratch *pack = nullptr;
+    GifScratch gif;
+    JpegScratch jpeg;
+    PngScratch png;
+    PackScratch pack;
 
     // enqueue `job` for the frame at d_pixels on `s`
     rtc_status enqueue(const RtcEncodeJob &job, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels, hipStream_t s,
                        RtcEncoded *e);
-    void release();
 };
 
 #endif

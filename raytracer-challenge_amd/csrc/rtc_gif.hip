@@ -21,7 +21,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 #include "rtc.h"
 #include "rtc_encode.h"
@@ -432,93 +431,69 @@ __global__ __launch_bounds__(256) void k_gif_pack(const uint8_t *seg, const unsi
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
+uint32_t segments(size_t n) { return (uint32_t)((n + RTC_GIF_SEGMENT - 1) / RTC_GIF_SEGMENT); }
+
 } // namespace
 
-struct GifScratch {
-    size_t px_cap = 0;          // pixels the buffers below are sized for
-    uint8_t *block = nullptr;   // one allocation: the parts cleared per frame first
-    uint32_t *bitmap = nullptr, *cnt = nullptr, *pal32 = nullptr;
-    unsigned long long *boxsum = nullptr;
-    size_t clear_bytes = 0;
-    uint32_t *blockcnt = nullptr;
-    GifInfo *info = nullptr;
-    uint8_t *lut = nullptr, *idx = nullptr, *seg = nullptr, *record = nullptr;
-    uint32_t *seglen = nullptr;
-    unsigned long long *segoff = nullptr;
-    size_t record_cap = 0;
-
-    static uint32_t segments(size_t n) { return (uint32_t)((n + RTC_GIF_SEGMENT - 1) / RTC_GIF_SEGMENT); }
-
-    rtc_status reserve(size_t n) {
-        if (n <= px_cap) return RTC_OK;
-        release();
-        const size_t nseg = segments(n);
-        const size_t dmax = nseg * (size_t)RTC_GIF_SEG_BYTES;
-        record_cap = RTC_GIF_RECORD_HEADER + dmax + (dmax + 254) / 255 + 1;
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_bitmap = 0, o_cnt = o_bitmap + up(4 * (size_t)BITMAP_WORDS), o_pal = o_cnt + up(4 * (size_t)RTC_GIF_BINS),
-                     o_box = o_pal + up(4 * 256), o_end_clear = o_box + up(8 * 256 * 4);
-        const size_t o_bc = o_end_clear, o_info = o_bc + up(4 * BITMAP_BLOCKS), o_lut = o_info + up(sizeof(GifInfo)),
-                     o_seglen = o_lut + up(RTC_GIF_BINS), o_segoff = o_seglen + up(4 * nseg), o_idx = o_segoff + up(8 * (nseg + 1)),
-                     o_seg = o_idx + up(n), o_rec = o_seg + up(nseg * (size_t)RTC_GIF_SEG_BYTES), total = o_rec + up(record_cap);
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&block), total);
-        if (e != hipSuccess) { (void)hipGetLastError(); block = nullptr; return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        bitmap = reinterpret_cast<uint32_t *>(block + o_bitmap);
-        cnt = reinterpret_cast<uint32_t *>(block + o_cnt);
-        pal32 = reinterpret_cast<uint32_t *>(block + o_pal);
-        boxsum = reinterpret_cast<unsigned long long *>(block + o_box);
-        clear_bytes = o_end_clear;
-        blockcnt = reinterpret_cast<uint32_t *>(block + o_bc);
-        info = reinterpret_cast<GifInfo *>(block + o_info);
-        lut = block + o_lut;
-        seglen = reinterpret_cast<uint32_t *>(block + o_seglen);
-        segoff = reinterpret_cast<unsigned long long *>(block + o_segoff);
-        idx = block + o_idx;
-        seg = block + o_seg;
-        record = block + o_rec;
-        px_cap = n;
-        return RTC_OK;
-    }
-    void release() {
-        if (block) (void)hipFree(block);
-        block = nullptr;
-        px_cap = 0;
-    }
-};
+rtc_status GifScratch::reserve(size_t n) {
+    if (n <= px_cap) return RTC_OK;
+    px_cap = 0;
+    const size_t nseg = segments(n);
+    const size_t dmax = nseg * (size_t)RTC_GIF_SEG_BYTES;
+    record_cap = RTC_GIF_RECORD_HEADER + dmax + (dmax + 254) / 255 + 1;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_bitmap = 0, o_cnt = o_bitmap + up(4 * (size_t)BITMAP_WORDS), o_pal = o_cnt + up(4 * (size_t)RTC_GIF_BINS),
+                 o_box = o_pal + up(4 * 256), o_end_clear = o_box + up(8 * 256 * 4);
+    const size_t o_bc = o_end_clear, o_info = o_bc + up(4 * BITMAP_BLOCKS), o_lut = o_info + up(sizeof(GifInfo)),
+                 o_seglen = o_lut + up(RTC_GIF_BINS), o_segoff = o_seglen + up(4 * nseg), o_idx = o_segoff + up(8 * (nseg + 1)),
+                 o_seg = o_idx + up(n), o_rec = o_seg + up(nseg * (size_t)RTC_GIF_SEG_BYTES), total = o_rec + up(record_cap);
+    const rtc_status st = this->block.reserve(total);
+    if (st != RTC_OK) return st;
+    uint8_t *block = this->block.get();
+    bitmap = reinterpret_cast<uint32_t *>(block + o_bitmap);
+    cnt = reinterpret_cast<uint32_t *>(block + o_cnt);
+    pal32 = reinterpret_cast<uint32_t *>(block + o_pal);
+    boxsum = reinterpret_cast<unsigned long long *>(block + o_box);
+    clear_bytes = o_end_clear;
+    blockcnt = reinterpret_cast<uint32_t *>(block + o_bc);
+    info = block + o_info;
+    lut = block + o_lut;
+    seglen = reinterpret_cast<uint32_t *>(block + o_seglen);
+    segoff = reinterpret_cast<unsigned long long *>(block + o_segoff);
+    idx = block + o_idx;
+    seg = block + o_seg;
+    record = block + o_rec;
+    px_cap = n;
+    return RTC_OK;
+}
 
 // The whole chain for a width x height frame at d_rgb8 on `s`; the body is the frame's record (not the file), its length
 // info->record_bytes.
-rtc_status rtc_gif_enqueue(GifScratch *&sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s, RtcEncoded *e) {
-    if (!sc && !(sc = new (std::nothrow) GifScratch)) return RTC_ERR_NOMEM;
+rtc_status rtc_gif_enqueue(GifScratch &sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s, RtcEncoded *e) {
     const size_t n = (size_t)width * height;
-    const rtc_status r = sc->reserve(n);
+    const rtc_status r = sc.reserve(n);
     if (r != RTC_OK) return r;
-    const uint32_t nseg = GifScratch::segments(n);
+    GifInfo *info = static_cast<GifInfo *>(sc.info);
+    const uint32_t nseg = segments(n);
     const size_t px_threads = (n + PX_PER_THREAD - 1) / PX_PER_THREAD;
     const uint32_t grid_px = (uint32_t)std::min<size_t>(PX_BLOCKS, (px_threads + 1023) / 1024);
     const uint32_t grid_sum = (uint32_t)std::min<size_t>(1024, (px_threads + 255) / 256);
     const uint32_t grid_map = (uint32_t)std::min<size_t>(2048, ((n + 3) / 4 + 255) / 256);
     const uint32_t grid_pack = (uint32_t)std::min<size_t>(2048, (nseg * (size_t)RTC_GIF_SEG_BYTES + 255) / 256);
-    HIP_TRY(hipMemsetAsync(sc->block, 0, sc->clear_bytes, s));
-    hipLaunchKernelGGL(k_gif_scan_pixels, dim3(grid_px), dim3(1024), 0, s, d_rgb8, n, sc->bitmap, sc->cnt);
-    hipLaunchKernelGGL(k_gif_bitmap_count, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc->bitmap, sc->blockcnt);
-    hipLaunchKernelGGL(k_gif_exact, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc->bitmap, sc->blockcnt, sc->pal32, sc->info);
-    hipLaunchKernelGGL(k_gif_median_cut, dim3(1), dim3(1024), 0, s, sc->cnt, sc->info, sc->lut);
-    hipLaunchKernelGGL(k_gif_box_sums, dim3(grid_sum), dim3(256), 0, s, d_rgb8, n, sc->info, sc->lut, sc->boxsum);
-    hipLaunchKernelGGL(k_gif_map, dim3(grid_map), dim3(256), 0, s, d_rgb8, n, sc->info, sc->pal32, sc->boxsum, sc->idx, sc->record);
-    hipLaunchKernelGGL(k_gif_lzw, dim3(nseg), dim3(64), 0, s, sc->idx, n, sc->seg, sc->seglen);
-    hipLaunchKernelGGL(k_gif_offsets, dim3(1), dim3(256), 0, s, sc->seglen, nseg, sc->segoff, sc->info, sc->record, width, height);
-    hipLaunchKernelGGL(k_gif_pack, dim3(grid_pack), dim3(256), 0, s, sc->seg, sc->segoff, nseg, sc->info, sc->record);
+    HIP_TRY(hipMemsetAsync(sc.block.get(), 0, sc.clear_bytes, s));
+    hipLaunchKernelGGL(k_gif_scan_pixels, dim3(grid_px), dim3(1024), 0, s, d_rgb8, n, sc.bitmap, sc.cnt);
+    hipLaunchKernelGGL(k_gif_bitmap_count, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc.bitmap, sc.blockcnt);
+    hipLaunchKernelGGL(k_gif_exact, dim3(BITMAP_BLOCKS), dim3(256), 0, s, sc.bitmap, sc.blockcnt, sc.pal32, info);
+    hipLaunchKernelGGL(k_gif_median_cut, dim3(1), dim3(1024), 0, s, sc.cnt, info, sc.lut);
+    hipLaunchKernelGGL(k_gif_box_sums, dim3(grid_sum), dim3(256), 0, s, d_rgb8, n, info, sc.lut, sc.boxsum);
+    hipLaunchKernelGGL(k_gif_map, dim3(grid_map), dim3(256), 0, s, d_rgb8, n, info, sc.pal32, sc.boxsum, sc.idx, sc.record);
+    hipLaunchKernelGGL(k_gif_lzw, dim3(nseg), dim3(64), 0, s, sc.idx, n, sc.seg, sc.seglen);
+    hipLaunchKernelGGL(k_gif_offsets, dim3(1), dim3(256), 0, s, sc.seglen, nseg, sc.segoff, info, sc.record, width, height);
+    hipLaunchKernelGGL(k_gif_pack, dim3(grid_pack), dim3(256), 0, s, sc.seg, sc.segoff, nseg, info, sc.record);
     HIP_TRY(hipGetLastError());
-    e->d_body = sc->record;
-    e->d_len = &sc->info->record_bytes;
-    e->cap = sc->record_cap;
+    e->d_body = sc.record;
+    e->d_len = &info->record_bytes;
+    e->cap = sc.record_cap;
     e->min_len = RTC_GIF_RECORD_HEADER + 1; // at least the header and the block terminator
     return RTC_OK;
-}
-
-void rtc_gif_release(GifScratch *sc) {
-    if (!sc) return;
-    sc->release();
-    delete sc;
 }

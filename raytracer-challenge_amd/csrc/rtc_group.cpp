@@ -76,9 +76,8 @@ struct Member {
     rtc_context *ctx = nullptr;
     ncclComm_t comm = nullptr;
     // two tile buffers: the exchange of batch j (s_comm) overlaps the render of batch j+1 (s_render)
-    double *tile[2] = {nullptr, nullptr};
-    unsigned char *tile8[2] = {nullptr, nullptr};
-    size_t tile_cap = 0, tile8_cap = 0; // bytes per buffer
+    DevBuf<double> tile[2];
+    DevBuf<unsigned char> tile8[2];
     hipEvent_t rendered[2] = {nullptr, nullptr}, sent[2] = {nullptr, nullptr};
 };
 
@@ -91,9 +90,8 @@ struct rtc_group {
     std::vector<Member> m; // local members, ascending rank
     uint64_t batches = 0;  // rtc_group_render calls so far (buffer parity)
     // member 0's gather destination: nranks chunks of one batch's packed tiles (grow-only)
-    double *staging = nullptr;
-    unsigned char *staging8 = nullptr;
-    size_t staging_cap = 0, staging8_cap = 0;
+    DevBuf<double> staging;
+    DevBuf<unsigned char> staging8;
     bool has_root() const { return !m.empty() && m[0].rank == 0; }
 };
 
@@ -124,26 +122,12 @@ void member_release(Member &mb) {
     if (mb.comm && rccl().ok) (void)rccl().CommDestroy(mb.comm);
     if (mb.ctx) rtc_context_destroy(mb.ctx);
     for (int b = 0; b < 2; ++b) {
-        if (mb.tile[b]) (void)hipFree(mb.tile[b]);
-        if (mb.tile8[b]) (void)hipFree(mb.tile8[b]);
         if (mb.rendered[b]) (void)hipEventDestroy(mb.rendered[b]);
         if (mb.sent[b]) (void)hipEventDestroy(mb.sent[b]);
     }
     if (mb.s_render) (void)hipStreamDestroy(mb.s_render);
     if (mb.s_comm) (void)hipStreamDestroy(mb.s_comm);
-    mb = Member{};
-}
-
-template <class T> rtc_status grow(T *&p, size_t &cap, size_t bytes) {
-    if (cap >= bytes) return RTC_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), bytes);
-    if (e == hipErrorOutOfMemory) return RTC_ERR_NOMEM;
-    if (e != hipSuccess) return RTC_ERR_DEVICE;
-    cap = bytes;
-    return RTC_OK;
+    mb = Member{}; // frees the tile buffers, the member's device current
 }
 
 static_assert(RTC_BANDS_ROWS == RTC_BAND_ROWS, "rtc_bands.h and include/rtc.h disagree");
@@ -167,9 +151,9 @@ rtc_status rtc_group_unique_id(uint8_t id[RTC_GROUP_ID_BYTES]) {
 
 void rtc_group_destroy(rtc_group *g) {
     if (!g) return;
+    const int root = g->m.empty() ? -1 : g->m[0].device;
     for (Member &mb : g->m) member_release(mb);
-    if (g->staging) (void)hipFree(g->staging);
-    if (g->staging8) (void)hipFree(g->staging8);
+    if (root >= 0) (void)hipSetDevice(root); // the staging buffers are member 0's
     delete g;
 }
 
@@ -301,30 +285,19 @@ static rtc_status render_members(rtc_group *g, const rtc_group_world *w, const r
                                  uint32_t flags, bool want8, int b, bool want64 = true, float gamma = 0.f) {
     const uint32_t W = cams[0].hsize, H = cams[0].vsize, N = g->nranks;
     const uint32_t rows = packed_rows(H, N);
-    const size_t tile_bytes = (size_t)nframes * rows * W * 3u * sizeof(double),
-                 tile8_bytes = (size_t)nframes * rows * W * (gamma > 0.f ? 4u : 3u);
+    const size_t tile_n = (size_t)nframes * rows * W * 3u, tile8_n = (size_t)nframes * rows * W * (gamma > 0.f ? 4u : 3u);
     for (size_t i = 0; i < g->m.size(); ++i) {
         Member &mb = g->m[i];
         HIP_TRY(hipSetDevice(mb.device));
-        if (want64 && mb.tile_cap < tile_bytes) { // both buffers grow together (hipFree waits for the device)
-            size_t c0 = mb.tile[0] ? mb.tile_cap : 0, c1 = mb.tile[1] ? mb.tile_cap : 0;
-            rtc_status st = grow(mb.tile[0], c0, tile_bytes);
-            if (st == RTC_OK) st = grow(mb.tile[1], c1, tile_bytes);
-            if (st != RTC_OK) return st;
-            mb.tile_cap = tile_bytes;
-        }
-        if (want8 && mb.tile8_cap < tile8_bytes) {
-            size_t c0 = mb.tile8[0] ? mb.tile8_cap : 0, c1 = mb.tile8[1] ? mb.tile8_cap : 0;
-            rtc_status st = grow(mb.tile8[0], c0, tile8_bytes);
-            if (st == RTC_OK) st = grow(mb.tile8[1], c1, tile8_bytes);
-            if (st != RTC_OK) return st;
-            mb.tile8_cap = tile8_bytes;
-        }
+        rtc_status grown = RTC_OK; // both buffers of a kind grow together (hipFree waits for the device)
+        for (int k = 0; k < 2 && want64 && grown == RTC_OK; ++k) grown = mb.tile[k].reserve(tile_n);
+        for (int k = 0; k < 2 && want8 && grown == RTC_OK; ++k) grown = mb.tile8[k].reserve(tile8_n);
+        if (grown != RTC_OK) return grown;
         HIP_TRY(hipStreamWaitEvent(mb.s_render, mb.sent[b], 0)); // an event never recorded does not block
         const rtc_status st = gamma > 0.f
-                                  ? rtc_render_views_rgba8(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, gamma, mb.tile8[b], rows, flags)
-                                  : rtc_render_views(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, want64 ? mb.tile[b] : nullptr,
-                                                     want8 ? mb.tile8[b] : nullptr, rows, flags);
+                                  ? rtc_render_views_rgba8(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, gamma, mb.tile8[b].get(), rows, flags)
+                                  : rtc_render_views(mb.ctx, w->w[i], cams, nframes, mode, mb.rank, N, want64 ? mb.tile[b].get() : nullptr,
+                                                     want8 ? mb.tile8[b].get() : nullptr, rows, flags);
         if (st != RTC_OK) return st;
         HIP_TRY(hipEventRecord(mb.rendered[b], mb.s_render));
         HIP_TRY(hipStreamWaitEvent(mb.s_comm, mb.rendered[b], 0));
@@ -361,8 +334,8 @@ rtc_status rtc_group_render(rtc_group *g, const rtc_group_world *w, const rtc_ca
     if (g->has_root()) {
         HIP_TRY(hipSetDevice(g->m[0].device));
         rtc_status st = RTC_OK;
-        if (f64) st = grow(g->staging, g->staging_cap, (size_t)N * tile_bytes);
-        if (st == RTC_OK && u8) st = grow(g->staging8, g->staging8_cap, (size_t)N * tile8_bytes);
+        if (f64) st = g->staging.reserve((size_t)N * tile_bytes / sizeof(double));
+        if (st == RTC_OK && u8) st = g->staging8.reserve((size_t)N * tile8_bytes);
         if (st != RTC_OK) return st;
     }
     if (g->exchange == RTC_EXCHANGE_RCCL) {
@@ -373,8 +346,8 @@ rtc_status rtc_group_render(rtc_group *g, const rtc_group_world *w, const rtc_ca
             bool ok = true;
             for (Member &mb : g->m) {
                 if (hipSetDevice(mb.device) != hipSuccess) ok = false;
-                void *recv = mb.rank == 0 ? (pass == 0 ? (void *)g->staging : (void *)g->staging8) : nullptr;
-                const void *send = pass == 0 ? (const void *)mb.tile[b] : (const void *)mb.tile8[b];
+                void *recv = mb.rank == 0 ? (pass == 0 ? (void *)g->staging.get() : (void *)g->staging8.get()) : nullptr;
+                const void *send = pass == 0 ? (const void *)mb.tile[b].get() : (const void *)mb.tile8[b].get();
                 const size_t count = pass == 0 ? tile_bytes / sizeof(double) : tile8_bytes;
                 if (R.Gather(send, recv, count, pass == 0 ? ncclDouble : ncclUint8, 0, mb.comm, mb.s_comm) != ncclSuccess) ok = false;
             }
@@ -388,10 +361,10 @@ rtc_status rtc_group_render(rtc_group *g, const rtc_group_world *w, const rtc_ca
             // the staging chunk may still be read by the previous batch's un-deal kernel (root's s_comm)
             if (mb.rank != 0) HIP_TRY(hipStreamWaitEvent(mb.s_comm, root.sent[b ^ 1], 0));
             if (f64)
-                HIP_TRY(hipMemcpyPeerAsync(reinterpret_cast<char *>(g->staging) + (size_t)mb.rank * tile_bytes, root.device, mb.tile[b],
+                HIP_TRY(hipMemcpyPeerAsync(reinterpret_cast<char *>(g->staging.get()) + (size_t)mb.rank * tile_bytes, root.device, mb.tile[b].get(),
                                            mb.device, tile_bytes, mb.s_comm));
             if (u8)
-                HIP_TRY(hipMemcpyPeerAsync(g->staging8 + (size_t)mb.rank * tile8_bytes, root.device, mb.tile8[b], mb.device, tile8_bytes,
+                HIP_TRY(hipMemcpyPeerAsync(g->staging8.get() + (size_t)mb.rank * tile8_bytes, root.device, mb.tile8[b].get(), mb.device, tile8_bytes,
                                            mb.s_comm));
             HIP_TRY(hipEventRecord(mb.sent[b], mb.s_comm));
         }
@@ -402,8 +375,8 @@ rtc_status rtc_group_render(rtc_group *g, const rtc_group_world *w, const rtc_ca
     if (g->has_root()) {
         Member &root = g->m[0];
         HIP_TRY(hipSetDevice(root.device));
-        if (f64) HIP_TRY(rtc_launch_undeal(g->staging, d_canvas, N, nframes, H, rows, row_bytes, root.s_comm));
-        if (u8) HIP_TRY(rtc_launch_undeal(g->staging8, d_rgb8, N, nframes, H, rows, row8, root.s_comm));
+        if (f64) HIP_TRY(rtc_launch_undeal(g->staging.get(), d_canvas, N, nframes, H, rows, row_bytes, root.s_comm));
+        if (u8) HIP_TRY(rtc_launch_undeal(g->staging8.get(), d_rgb8, N, nframes, H, rows, row8, root.s_comm));
     }
     for (Member &mb : g->m) {
         HIP_TRY(hipSetDevice(mb.device));
@@ -436,9 +409,9 @@ rtc_status rtc_group_render_host(rtc_group *g, const rtc_group_world *w, const r
         const uint32_t whole = last_short ? mine - 1u : mine;
         char *dst = reinterpret_cast<char *>(rgb) + (size_t)rtc_packed_row_to_image(mb.rank, 0u, N) * row_bytes; // = rank * band_bytes
         if (whole)
-            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)N * band_bytes, mb.tile[b], band_bytes, band_bytes, whole, hipMemcpyDeviceToHost, mb.s_comm));
+            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)N * band_bytes, mb.tile[b].get(), band_bytes, band_bytes, whole, hipMemcpyDeviceToHost, mb.s_comm));
         if (last_short)
-            HIP_TRY(hipMemcpyAsync(dst + (size_t)whole * N * band_bytes, reinterpret_cast<char *>(mb.tile[b]) + (size_t)whole * band_bytes,
+            HIP_TRY(hipMemcpyAsync(dst + (size_t)whole * N * band_bytes, reinterpret_cast<char *>(mb.tile[b].get()) + (size_t)whole * band_bytes,
                                    (size_t)(H % RTC_BAND_ROWS) * row_bytes, hipMemcpyDeviceToHost, mb.s_comm));
         HIP_TRY(hipEventRecord(mb.sent[b], mb.s_comm));
     }
@@ -470,9 +443,9 @@ static rtc_status render_host8(rtc_group *g, const rtc_group_world *w, const rtc
         const uint32_t whole = last_short ? mine - 1u : mine;
         unsigned char *dst = rgb8 + (size_t)mb.rank * band_bytes;
         if (whole)
-            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)N * band_bytes, mb.tile8[b], band_bytes, band_bytes, whole, hipMemcpyDeviceToHost, mb.s_comm));
+            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)N * band_bytes, mb.tile8[b].get(), band_bytes, band_bytes, whole, hipMemcpyDeviceToHost, mb.s_comm));
         if (last_short)
-            HIP_TRY(hipMemcpyAsync(dst + (size_t)whole * N * band_bytes, mb.tile8[b] + (size_t)whole * band_bytes,
+            HIP_TRY(hipMemcpyAsync(dst + (size_t)whole * N * band_bytes, mb.tile8[b].get() + (size_t)whole * band_bytes,
                                    (size_t)(H % RTC_BAND_ROWS) * row_bytes, hipMemcpyDeviceToHost, mb.s_comm));
         HIP_TRY(hipEventRecord(mb.sent[b], mb.s_comm));
     }

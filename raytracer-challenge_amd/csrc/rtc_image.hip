@@ -11,7 +11,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "rtc.h"
 #include "rtc_encode.h"
@@ -74,75 +73,47 @@ size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-struct PackScratch {
-    uint8_t *out = nullptr, *d_hdr = nullptr, *h_hdr = nullptr;
-    size_t out_cap = 0, hdr_cap = 0;
-    unsigned long long *d_len = nullptr;
+PackScratch::~PackScratch() {
+    if (h_hdr) (void)hipHostFree(h_hdr);
+}
 
-    static rtc_status dev(uint8_t *&p, size_t &cap, size_t bytes) {
-        if (bytes <= cap) return RTC_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        cap = bytes;
-        return RTC_OK;
-    }
-    // the header's device copy and its page-locked source (the upload is asynchronous; the source stays until the next file)
-    rtc_status header(size_t bytes) {
-        if (bytes <= hdr_cap) return RTC_OK;
-        if (h_hdr) (void)hipHostFree(h_hdr);
-        if (d_hdr) (void)hipFree(d_hdr);
-        h_hdr = d_hdr = nullptr;
-        hdr_cap = 0;
-        const size_t b = std::max<size_t>(bytes, 4096);
-        size_t dcap = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&h_hdr), b, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h_hdr = nullptr; return RTC_ERR_NOMEM; }
-        const rtc_status st = dev(d_hdr, dcap, b);
-        if (st != RTC_OK) return st;
-        hdr_cap = b;
-        return RTC_OK;
-    }
-    void release() {
-        if (out) (void)hipFree(out);
-        if (d_hdr) (void)hipFree(d_hdr);
-        if (h_hdr) (void)hipHostFree(h_hdr);
-        if (d_len) (void)hipFree(d_len);
-    }
-};
-
-// k_image_pack of `format` (a packed file or a raw packing) on `s`; the body is the file (RTC_IMAGE_RAW_*: the packed
-// pixels), its length written by the kernel.
-rtc_status rtc_image_pack_enqueue(PackScratch *&sc, uint32_t format, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels,
-                                  hipStream_t s, RtcEncoded *e) {
-    if (!sc && !(sc = new (std::nothrow) PackScratch)) return RTC_ERR_NOMEM;
-    if (!sc->d_len) {
-        const hipError_t he = hipMalloc(reinterpret_cast<void **>(&sc->d_len), sizeof(unsigned long long));
-        if (he != hipSuccess) { (void)hipGetLastError(); sc->d_len = nullptr; return RTC_ERR_DEVICE; }
-    }
-    RtcImageLayout L;
-    if (!rtc_image_layout(format, w, h, &L, nullptr)) return RTC_ERR_ARG;
-    rtc_status st = PackScratch::dev(sc->out, sc->out_cap, up16((size_t)L.file_bytes));
-    if (st == RTC_OK) st = sc->header(L.header);
+// the header's device copy and its page-locked source
+rtc_status PackScratch::header(size_t bytes) {
+    if (bytes <= hdr_cap) return RTC_OK;
+    if (h_hdr) (void)hipHostFree(h_hdr);
+    h_hdr = nullptr;
+    d_hdr.reset();
+    hdr_cap = 0;
+    const size_t b = std::max<size_t>(bytes, 4096);
+    if (hipHostMalloc(reinterpret_cast<void **>(&h_hdr), b, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h_hdr = nullptr; return RTC_ERR_NOMEM; }
+    const rtc_status st = d_hdr.reserve(b);
     if (st != RTC_OK) return st;
-    if (L.header) {
-        rtc_image_layout(format, w, h, &L, sc->h_hdr);
-        HIP_TRY(hipMemcpyAsync(sc->d_hdr, sc->h_hdr, L.header, hipMemcpyHostToDevice, s));
-    }
-    const unsigned long long threads = (L.file_bytes + 15) / 16;
-    const PackArgs a{d_pixels, sc->d_hdr, sc->out, sc->d_len, L.file_bytes, w, h, channels, L.header, L.bytes_per_pixel, L.bgr, L.flip};
-    hipLaunchKernelGGL(k_image_pack, dim3((uint32_t)((threads + PACK_THREADS - 1) / PACK_THREADS)), dim3(PACK_THREADS), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    e->d_body = sc->out;
-    e->d_len = sc->d_len;
-    e->cap = sc->out_cap;
-    e->min_len = 1;
+    hdr_cap = b;
     return RTC_OK;
 }
 
-void rtc_image_pack_release(PackScratch *sc) {
-    if (!sc) return;
-    sc->release();
-    delete sc;
+// k_image_pack of `format` (a packed file or a raw packing) on `s`; the body is the file (RTC_IMAGE_RAW_*: the packed
+// pixels), its length written by the kernel.
+rtc_status rtc_image_pack_enqueue(PackScratch &sc, uint32_t format, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels,
+                                  hipStream_t s, RtcEncoded *e) {
+    rtc_status st = sc.d_len.reserve(1);
+    if (st != RTC_OK) return st;
+    RtcImageLayout L;
+    if (!rtc_image_layout(format, w, h, &L, nullptr)) return RTC_ERR_ARG;
+    st = sc.out.reserve(up16((size_t)L.file_bytes));
+    if (st == RTC_OK) st = sc.header(L.header);
+    if (st != RTC_OK) return st;
+    if (L.header) {
+        rtc_image_layout(format, w, h, &L, sc.h_hdr);
+        HIP_TRY(hipMemcpyAsync(sc.d_hdr.get(), sc.h_hdr, L.header, hipMemcpyHostToDevice, s));
+    }
+    const unsigned long long threads = (L.file_bytes + 15) / 16;
+    const PackArgs a{d_pixels, sc.d_hdr.get(), sc.out.get(), sc.d_len.get(), L.file_bytes, w, h, channels, L.header, L.bytes_per_pixel, L.bgr, L.flip};
+    hipLaunchKernelGGL(k_image_pack, dim3((uint32_t)((threads + PACK_THREADS - 1) / PACK_THREADS)), dim3(PACK_THREADS), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    e->d_body = sc.out.get();
+    e->d_len = sc.d_len.get();
+    e->cap = sc.out.capacity();
+    e->min_len = 1;
+    return RTC_OK;
 }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rtc.h"
+#include "rtc_devmem.h"
 #include "rtc_device.h"
 #include "rtc_gamma.h"
 
@@ -18,7 +19,7 @@ struct rtc_context {
     unsigned long long render_allocs = 0; // hipMalloc calls made by render entry points (rtc_debug_render_allocs)
     unsigned long long pixels = 0; // rtc_stats::pixels of the launches since the last reset (counted by render_launch)
     hipStream_t stream = nullptr;
-    unsigned long long *d_counters = nullptr;
+    DevBuf<unsigned long long> d_counters;
     // ring of (begin, end) event pairs, one per timed k_trace launch. Created on demand, EV_CHUNK pairs
     // at a time (a context that never renders creates none; creating all 2048 up front made
     // rtc_context_create the slowest call of a one-frame render)
@@ -31,10 +32,8 @@ struct rtc_context {
     uint64_t timed = 0;    // ... of which carried an event pair (ring position)
     uint32_t time_every = 1; // rtc_context_set_timing
     // device canvas of rtc_render (host-canvas entry point): grow-only, reused between frames
-    double *d_canvas = nullptr;
-    size_t canvas_bytes = 0;
-    unsigned char *d_canvas8 = nullptr; // the same for rtc_render_rgb8 (3 B/pixel)
-    size_t canvas8_bytes = 0;
+    DevBuf<double> d_canvas;
+    DevBuf<unsigned char> d_canvas8; // the same for rtc_render_rgb8 (3 B/pixel) and rtc_render_rgba8 (4 B/pixel)
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -81,7 +80,7 @@ struct rtc_context {
         hipEvent_t ready = nullptr;
         DevGamma host{}; // the upload's source: stays put as long as the slot holds this gamma
     };
-    DevGamma *d_gamma = nullptr; // GAMMA_SLOTS tables, allocated by the first RGBA call
+    DevBuf<DevGamma> d_gamma; // GAMMA_SLOTS tables, allocated by the first RGBA call
     GammaSlot gamma_slot[GAMMA_SLOTS];
 };
 
@@ -89,34 +88,32 @@ struct rtc_world {
     rtc_context *ctx = nullptr; // identity check only; never dereferenced at destroy time
     int device = -1;
     uint32_t n = 0;
-    DevIsect *d_isect = nullptr;
-    uint32_t *d_kind = nullptr;
-    DevShade *d_shade = nullptr;
-    DevPrim *d_prim = nullptr;
-    DevBound *d_bound = nullptr;
-    DevIsect *d_isect_s = nullptr; // Morton-sorted copies for the two-level cull
-    uint32_t *d_kind_s = nullptr;
-    DevBound *d_bound_s = nullptr;
-    uint32_t *d_orig_s = nullptr;
-    DevBound *d_gbound = nullptr;
-    DevIdEntry *d_idtab = nullptr;
-    DevPre *d_pre = nullptr, *d_pre_s = nullptr; // per-lane prefilter records (insertion / sorted order)
+    DevBuf<DevIsect> d_isect;
+    DevBuf<uint32_t> d_kind;
+    DevBuf<DevShade> d_shade;
+    DevBuf<DevPrim> d_prim;
+    DevBuf<DevBound> d_bound;
+    DevBuf<DevIsect> d_isect_s; // Morton-sorted copies for the two-level cull
+    DevBuf<uint32_t> d_kind_s;
+    DevBuf<DevBound> d_bound_s;
+    DevBuf<uint32_t> d_orig_s;
+    DevBuf<DevBound> d_gbound;
+    DevBuf<DevIdEntry> d_idtab;
+    DevBuf<DevPre> d_pre, d_pre_s; // per-lane prefilter records (insertion / sorted order)
     double pre_limit = 0.;
     // binned primary pass: per-render scratch, grow-only, TWO sets — the binning of launch k+1 runs on the context's side
     // stream while launch k's render kernel still reads set k (rtc_render_* take the World as const: mutable)
     struct BinSet {
-        uint32_t *tile_cnt = nullptr, *tile_list = nullptr; // per (view, tile): entries used, RTC_TILE_LIST_CAP entry slots (tile_cnt: RTC_BIN_ROW_WORDS row words first)
-        size_t tiles_cap = 0;            // capacity in (view, tile) entries
-        DevPrim *prim = nullptr;         // per (view, object): the primary rays' constants, written by the set's binning kernel
-        size_t prim_cap = 0;             // capacity in records
+        DevBuf<uint32_t> tile_cnt, tile_list; // per (view, tile): entries used, RTC_TILE_LIST_CAP entry slots (tile_cnt: RTC_BIN_ROW_WORDS row words first)
+        DevBuf<DevPrim> prim;            // per (view, object): the primary rays' constants, written by the set's binning kernel
         hipEvent_t binned = nullptr;     // recorded on the side stream after the set's binning kernel
         hipEvent_t traced = nullptr;     // recorded on the render stream after the render kernel that read the set
     };
     mutable BinSet bin[rtc_context::MAX_LANES]; // in-order contexts alternate between [0] and [1]; a pipelined context's lane l owns [l]
     mutable uint32_t bin_next = 0;
     // light-space shadow lists (two-level worlds), built once at rtc_world_create
-    DevTileBundle *d_light_cells = nullptr;
-    uint32_t *d_light_cnt = nullptr, *d_light_list = nullptr;
+    DevBuf<DevTileBundle> d_light_cells;
+    DevBuf<uint32_t> d_light_cnt, d_light_list;
     double light_reach = 0.;
     uint32_t light_cap = 0;
     uint32_t n_unb = 0;               // unbounded objects: the first n_unb entries of the Morton-sorted tables

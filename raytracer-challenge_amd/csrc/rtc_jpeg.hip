@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "rtc.h"
 #include "rtc_encode.h"
@@ -274,87 +273,65 @@ __global__ __launch_bounds__(256) void k_jpeg_scatter(const unsigned long long *
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-struct JpegScratch {
-    size_t mcu_cap = 0;
-    uint8_t *block = nullptr;
-    int16_t *coef = nullptr;
-    uint32_t *acbits = nullptr, *mcu_off = nullptr, *ffcnt = nullptr;
-    int32_t *dc = nullptr;
-    unsigned long long *group = nullptr, *words = nullptr, *chunk_off = nullptr;
-    JpegInfo *info = nullptr;
-    uint8_t *out = nullptr;
-    size_t nwords = 0, data_max = 0; // the packed stream's buffer: words, and its worst case in bytes
-
-    rtc_status reserve(size_t nmcu) {
-        if (nmcu <= mcu_cap) return RTC_OK;
-        release();
-        const size_t ngroups = (nmcu + MCU_PER_GROUP - 1) / MCU_PER_GROUP;
-        nwords = (nmcu * 3 * (size_t)RTC_JPEG_BLOCK_BITS_MAX + 63) / 64 + 2; // + the padding's and a spare word
-        data_max = nwords * 8;
-        const size_t nchunks = (data_max + CHUNK - 1) / CHUNK;
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_coef = 0, o_ac = o_coef + up(nmcu * 192 * 2), o_dc = o_ac + up(nmcu * 3 * 4), o_off = o_dc + up(nmcu * 3 * 4),
-                     o_grp = o_off + up(nmcu * 4), o_info = o_grp + up(ngroups * 8), o_words = o_info + up(sizeof(JpegInfo)),
-                     o_ff = o_words + up(nwords * 8), o_co = o_ff + up(nchunks * 4), o_out = o_co + up(nchunks * 8),
-                     total = o_out + up(2 * data_max + 2);
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&block), total);
-        if (e != hipSuccess) { (void)hipGetLastError(); block = nullptr; return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        coef = reinterpret_cast<int16_t *>(block + o_coef);
-        acbits = reinterpret_cast<uint32_t *>(block + o_ac);
-        dc = reinterpret_cast<int32_t *>(block + o_dc);
-        mcu_off = reinterpret_cast<uint32_t *>(block + o_off);
-        group = reinterpret_cast<unsigned long long *>(block + o_grp);
-        info = reinterpret_cast<JpegInfo *>(block + o_info);
-        words = reinterpret_cast<unsigned long long *>(block + o_words);
-        ffcnt = reinterpret_cast<uint32_t *>(block + o_ff);
-        chunk_off = reinterpret_cast<unsigned long long *>(block + o_co);
-        out = block + o_out;
-        mcu_cap = nmcu;
-        return RTC_OK;
-    }
-    void release() {
-        if (block) (void)hipFree(block);
-        block = nullptr;
-        mcu_cap = 0;
-    }
-};
+rtc_status JpegScratch::reserve(size_t nmcu) {
+    if (nmcu <= mcu_cap) return RTC_OK;
+    mcu_cap = 0;
+    const size_t ngroups = (nmcu + MCU_PER_GROUP - 1) / MCU_PER_GROUP;
+    nwords = (nmcu * 3 * (size_t)RTC_JPEG_BLOCK_BITS_MAX + 63) / 64 + 2; // + the padding's and a spare word
+    data_max = nwords * 8;
+    const size_t nchunks = (data_max + CHUNK - 1) / CHUNK;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_coef = 0, o_ac = o_coef + up(nmcu * 192 * 2), o_dc = o_ac + up(nmcu * 3 * 4), o_off = o_dc + up(nmcu * 3 * 4),
+                 o_grp = o_off + up(nmcu * 4), o_info = o_grp + up(ngroups * 8), o_words = o_info + up(sizeof(JpegInfo)),
+                 o_ff = o_words + up(nwords * 8), o_co = o_ff + up(nchunks * 4), o_out = o_co + up(nchunks * 8),
+                 total = o_out + up(2 * data_max + 2);
+    const rtc_status st = this->block.reserve(total);
+    if (st != RTC_OK) return st;
+    uint8_t *block = this->block.get();
+    coef = reinterpret_cast<int16_t *>(block + o_coef);
+    acbits = reinterpret_cast<uint32_t *>(block + o_ac);
+    dc = reinterpret_cast<int32_t *>(block + o_dc);
+    mcu_off = reinterpret_cast<uint32_t *>(block + o_off);
+    group = reinterpret_cast<unsigned long long *>(block + o_grp);
+    info = block + o_info;
+    words = reinterpret_cast<unsigned long long *>(block + o_words);
+    ffcnt = reinterpret_cast<uint32_t *>(block + o_ff);
+    chunk_off = reinterpret_cast<unsigned long long *>(block + o_co);
+    out = block + o_out;
+    mcu_cap = nmcu;
+    return RTC_OK;
+}
 
 // The whole chain on `s`; the body is the stuffed data + EOI (what follows the header), its length info->out_bytes.
-rtc_status rtc_jpeg_enqueue(JpegScratch *&sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, int32_t quality,
+rtc_status rtc_jpeg_enqueue(JpegScratch &sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, int32_t quality,
                             hipStream_t s, RtcEncoded *e) {
-    if (!sc && !(sc = new (std::nothrow) JpegScratch)) return RTC_ERR_NOMEM;
     const uint32_t mcu_w = (w + 7) / 8, mcu_h = (h + 7) / 8;
     const size_t nmcu = (size_t)mcu_w * mcu_h;
-    const rtc_status r = sc->reserve(nmcu);
+    const rtc_status r = sc.reserve(nmcu);
     if (r != RTC_OK) return r;
+    JpegInfo *info = static_cast<JpegInfo *>(sc.info);
     JpegQuant q;
     for (int t = 0; t < 2; ++t)
         for (int i = 0; i < 64; ++i) q.q[64 * t + i] = (uint16_t)rtc_jpeg_quant_entry(quality, t, i);
     const uint32_t ngroups = (uint32_t)((nmcu + MCU_PER_GROUP - 1) / MCU_PER_GROUP);
     const uint32_t grid_mcu = (uint32_t)((nmcu + 3) / 4);
-    const size_t nchunks_max = (sc->data_max + CHUNK - 1) / CHUNK;
+    const size_t nchunks_max = (sc.data_max + CHUNK - 1) / CHUNK;
     const uint32_t grid_data = (uint32_t)std::min<size_t>(DATA_GRID_MAX, nchunks_max);
-    const unsigned long long out_cap = 2 * sc->data_max + 2;
-    hipLaunchKernelGGL(k_jpeg_blocks, dim3(grid_mcu), dim3(256), 0, s, d_pixels, w, h, channels, mcu_w, (uint32_t)nmcu, q, sc->coef,
-                       sc->acbits, sc->dc);
-    hipLaunchKernelGGL(k_jpeg_mcu_scan, dim3(ngroups), dim3(MCU_PER_GROUP), 0, s, sc->acbits, sc->dc, (uint32_t)nmcu, sc->mcu_off, sc->group);
-    hipLaunchKernelGGL(k_jpeg_group_scan, dim3(1), dim3(1024), 0, s, sc->group, ngroups, sc->info);
-    hipLaunchKernelGGL(k_jpeg_clear, dim3(grid_data), dim3(256), 0, s, sc->words, sc->info);
-    hipLaunchKernelGGL(k_jpeg_pack, dim3(grid_mcu), dim3(256), 0, s, sc->coef, sc->dc, (uint32_t)nmcu, sc->mcu_off, sc->group, sc->info,
-                       sc->words, (unsigned long long)sc->nwords);
-    hipLaunchKernelGGL(k_jpeg_ffcount, dim3(grid_data), dim3(256), 0, s, sc->words, sc->info, sc->ffcnt);
-    hipLaunchKernelGGL(k_jpeg_ffscan, dim3(1), dim3(1024), 0, s, sc->ffcnt, sc->info, sc->chunk_off);
-    hipLaunchKernelGGL(k_jpeg_scatter, dim3(grid_data), dim3(256), 0, s, sc->words, sc->info, sc->chunk_off, sc->out, out_cap);
+    const unsigned long long out_cap = 2 * sc.data_max + 2;
+    hipLaunchKernelGGL(k_jpeg_blocks, dim3(grid_mcu), dim3(256), 0, s, d_pixels, w, h, channels, mcu_w, (uint32_t)nmcu, q, sc.coef,
+                       sc.acbits, sc.dc);
+    hipLaunchKernelGGL(k_jpeg_mcu_scan, dim3(ngroups), dim3(MCU_PER_GROUP), 0, s, sc.acbits, sc.dc, (uint32_t)nmcu, sc.mcu_off, sc.group);
+    hipLaunchKernelGGL(k_jpeg_group_scan, dim3(1), dim3(1024), 0, s, sc.group, ngroups, info);
+    hipLaunchKernelGGL(k_jpeg_clear, dim3(grid_data), dim3(256), 0, s, sc.words, info);
+    hipLaunchKernelGGL(k_jpeg_pack, dim3(grid_mcu), dim3(256), 0, s, sc.coef, sc.dc, (uint32_t)nmcu, sc.mcu_off, sc.group, info,
+                       sc.words, (unsigned long long)sc.nwords);
+    hipLaunchKernelGGL(k_jpeg_ffcount, dim3(grid_data), dim3(256), 0, s, sc.words, info, sc.ffcnt);
+    hipLaunchKernelGGL(k_jpeg_ffscan, dim3(1), dim3(1024), 0, s, sc.ffcnt, info, sc.chunk_off);
+    hipLaunchKernelGGL(k_jpeg_scatter, dim3(grid_data), dim3(256), 0, s, sc.words, info, sc.chunk_off, sc.out, out_cap);
     HIP_TRY(hipGetLastError());
-    e->d_body = sc->out;
-    e->d_len = &sc->info->out_bytes;
+    e->d_body = sc.out;
+    e->d_len = &info->out_bytes;
     e->cap = out_cap;
     e->min_len = 2; // EOI
     return RTC_OK;
-}
-
-void rtc_jpeg_release(JpegScratch *sc) {
-    if (!sc) return;
-    sc->release();
-    delete sc;
 }

@@ -101,8 +101,9 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
     HIP_TRY(hipSetDevice(ctx->device));
     constexpr uint32_t RING = rtc_context::MAX_LANES + 1u; // a frame's buffers are reused only after `depth` later launches
     struct Slot {
-        uint8_t *d = nullptr, *h = nullptr; // the frame's rows (device), the delivered bytes (page-locked)
-        size_t cap = 0, hcap = 0;
+        DevBuf<uint8_t> d;     // the frame's rows
+        uint8_t *h = nullptr;  // the delivered bytes (page-locked)
+        size_t hcap = 0;
         RtcEncoder enc;
         unsigned long long *h_len = nullptr; // page-locked: an encoded body's length lands here
         hipEvent_t done = nullptr;
@@ -190,28 +191,21 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
             st = rtc_world_create(ctx, job.shapes, job.n_shapes, &job.light, &world);
             if (st != RTC_OK) break;
         }
-        if (sl.cap < bytes) {
-            if (sl.d) (void)hipFree(sl.d);
-            sl.d = nullptr;
-            sl.cap = 0;
-            const hipError_t e = hipMalloc(reinterpret_cast<void **>(&sl.d), bytes);
-            if (e != hipSuccess) { (void)hipGetLastError(); st = e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; break; }
-            sl.cap = bytes;
-        }
+        if ((st = sl.d.reserve(bytes)) != RTC_OK) break;
         if (!out.encoded && (st = host_buf(sl, bytes)) != RTC_OK) break;
         if (out.encoded) {
             if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
             if (!copy && hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) != hipSuccess) { copy = nullptr; st = RTC_ERR_DEVICE; break; }
         }
         if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, nullptr, sl.d, flags);
+        st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, nullptr, sl.d.get(), flags);
         if (st != RTC_OK) break;
         hipStream_t s = ctx->lanes > 1u ? ctx->lane[ctx->last.lane] : ctx->stream; // the stream that launch went to
         if (out.encoded) {
-            st = sl.enc.enqueue(out.job, sl.d, job.camera.hsize, job.camera.vsize, 3, s, &sl.e);
+            st = sl.enc.enqueue(out.job, sl.d.get(), job.camera.hsize, job.camera.vsize, 3, s, &sl.e);
             if (st != RTC_OK) break;
             if (hipMemcpyAsync(sl.h_len, sl.e.d_len, sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        } else if (hipMemcpyAsync(sl.h, sl.d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
+        } else if (hipMemcpyAsync(sl.h, sl.d.get(), bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
             st = RTC_ERR_DEVICE;
             break;
         }
@@ -229,11 +223,9 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
     for (hipStream_t lane : ctx->lane) // whatever failed above, nothing may still use the slots' buffers
         if (lane) (void)hipStreamSynchronize(lane);
     if (world) rtc_world_destroy(world);
-    for (Slot &sl : ring) {
-        if (sl.d) (void)hipFree(sl.d);
+    for (Slot &sl : ring) { // (the slots' device buffers are freed when the ring goes out of scope, after these syncs)
         if (sl.h) (void)hipHostFree(sl.h);
         if (sl.h_len) (void)hipHostFree(sl.h_len);
-        sl.enc.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (copy) (void)hipStreamDestroy(copy);

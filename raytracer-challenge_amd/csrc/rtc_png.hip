@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "rtc.h"
 #include "rtc_encode.h"
@@ -368,74 +367,53 @@ __global__ __launch_bounds__(256) void k_png_crc(const SegInfo *info, uint32_t n
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-struct PngScratch {
-    size_t n_cap = 0;
-    uint8_t *block = nullptr;
-    uint8_t *filt = nullptr, *out = nullptr;
-    uint16_t *prev = nullptr; // then T, the token flags
-    uint32_t *M = nullptr;
-    unsigned long long *words = nullptr, *chunk_off = nullptr;
-    SegInfo *info = nullptr;
-    PngInfo *pinfo = nullptr;
-    size_t out_cap = 0;
-
-    rtc_status reserve(size_t n) {
-        if (n <= n_cap) return RTC_OK;
-        release();
-        const size_t nseg = (n + SEG - 1) / SEG;
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t ocap = n + RTC_PNG_CHUNK_OVERHEAD * 2 * nseg + RTC_PNG_FILE_FIXED; // the stored bound, with room to spare
-        const size_t o_filt = 0, o_prev = o_filt + up(n + 8), o_m = o_prev + up(2 * n), o_words = o_m + up(4 * n),
-                     o_info = o_words + up(nseg * SEG_WORDS * 8), o_off = o_info + up(nseg * sizeof(SegInfo)), o_p = o_off + up(nseg * 8),
-                     o_out = o_p + up(sizeof(PngInfo)), total = o_out + up(ocap);
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&block), total);
-        if (e != hipSuccess) { (void)hipGetLastError(); block = nullptr; return e == hipErrorOutOfMemory ? RTC_ERR_NOMEM : RTC_ERR_DEVICE; }
-        filt = block + o_filt;
-        prev = reinterpret_cast<uint16_t *>(block + o_prev);
-        M = reinterpret_cast<uint32_t *>(block + o_m);
-        words = reinterpret_cast<unsigned long long *>(block + o_words);
-        info = reinterpret_cast<SegInfo *>(block + o_info);
-        chunk_off = reinterpret_cast<unsigned long long *>(block + o_off);
-        pinfo = reinterpret_cast<PngInfo *>(block + o_p);
-        out = block + o_out;
-        out_cap = ocap;
-        n_cap = n;
-        return RTC_OK;
-    }
-    void release() {
-        if (block) (void)hipFree(block);
-        block = nullptr;
-        n_cap = 0;
-    }
-};
-
-// The whole chain on `s`; the body is the file, its length pinfo->file_bytes.
-rtc_status rtc_png_enqueue(PngScratch *&sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, hipStream_t s,
-                           RtcEncoded *e) {
-    if (!sc && !(sc = new (std::nothrow) PngScratch)) return RTC_ERR_NOMEM;
-    const size_t n = ((size_t)w * channels + 1) * h;
-    const rtc_status r = sc->reserve(n);
-    if (r != RTC_OK) return r;
-    const uint32_t nseg = (uint32_t)((n + SEG - 1) / SEG);
-    const unsigned long long nn = n, cap = sc->out_cap;
-    hipLaunchKernelGGL(k_png_filter, dim3((h + 3) / 4), dim3(256), 0, s, d_pixels, w, h, channels, sc->filt);
-    hipLaunchKernelGGL(k_png_prev, dim3(nseg), dim3(64), 0, s, sc->filt, nn, sc->prev);
-    hipLaunchKernelGGL(k_png_match, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sc->filt, nn, sc->prev, sc->M);
-    hipLaunchKernelGGL(k_png_parse, dim3(nseg), dim3(256), 0, s, sc->M, nn, sc->prev);
-    hipLaunchKernelGGL(k_png_segment, dim3(nseg), dim3(SEG_THREADS), 0, s, sc->filt, nn, sc->M, sc->prev, sc->words, sc->info);
-    hipLaunchKernelGGL(k_png_layout, dim3(1), dim3(1024), 0, s, sc->info, nseg, nn, w, h, channels, sc->chunk_off, sc->out, cap, sc->pinfo);
-    hipLaunchKernelGGL(k_png_copy, dim3(nseg), dim3(256), 0, s, sc->words, sc->info, sc->chunk_off, sc->out, cap);
-    hipLaunchKernelGGL(k_png_crc, dim3(nseg), dim3(256), 0, s, sc->info, nseg, sc->chunk_off, sc->out, cap);
-    HIP_TRY(hipGetLastError());
-    e->d_body = sc->out;
-    e->d_len = &sc->pinfo->file_bytes;
-    e->cap = cap;
-    e->min_len = RTC_PNG_FILE_FIXED + RTC_PNG_CHUNK_OVERHEAD;
+rtc_status PngScratch::reserve(size_t n) {
+    if (n <= n_cap) return RTC_OK;
+    n_cap = 0;
+    const size_t nseg = (n + SEG - 1) / SEG;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t ocap = n + RTC_PNG_CHUNK_OVERHEAD * 2 * nseg + RTC_PNG_FILE_FIXED; // the stored bound, with room to spare
+    const size_t o_filt = 0, o_prev = o_filt + up(n + 8), o_m = o_prev + up(2 * n), o_words = o_m + up(4 * n),
+                 o_info = o_words + up(nseg * SEG_WORDS * 8), o_off = o_info + up(nseg * sizeof(SegInfo)), o_p = o_off + up(nseg * 8),
+                 o_out = o_p + up(sizeof(PngInfo)), total = o_out + up(ocap);
+    const rtc_status st = this->block.reserve(total);
+    if (st != RTC_OK) return st;
+    uint8_t *block = this->block.get();
+    filt = block + o_filt;
+    prev = reinterpret_cast<uint16_t *>(block + o_prev);
+    M = reinterpret_cast<uint32_t *>(block + o_m);
+    words = reinterpret_cast<unsigned long long *>(block + o_words);
+    info = block + o_info;
+    chunk_off = reinterpret_cast<unsigned long long *>(block + o_off);
+    pinfo = block + o_p;
+    out = block + o_out;
+    out_cap = ocap;
+    n_cap = n;
     return RTC_OK;
 }
 
-void rtc_png_release(PngScratch *sc) {
-    if (!sc) return;
-    sc->release();
-    delete sc;
+// The whole chain on `s`; the body is the file, its length pinfo->file_bytes.
+rtc_status rtc_png_enqueue(PngScratch &sc, const uint8_t *d_pixels, uint32_t w, uint32_t h, uint32_t channels, hipStream_t s,
+                           RtcEncoded *e) {
+    const size_t n = ((size_t)w * channels + 1) * h;
+    const rtc_status r = sc.reserve(n);
+    if (r != RTC_OK) return r;
+    SegInfo *info = static_cast<SegInfo *>(sc.info);
+    PngInfo *pinfo = static_cast<PngInfo *>(sc.pinfo);
+    const uint32_t nseg = (uint32_t)((n + SEG - 1) / SEG);
+    const unsigned long long nn = n, cap = sc.out_cap;
+    hipLaunchKernelGGL(k_png_filter, dim3((h + 3) / 4), dim3(256), 0, s, d_pixels, w, h, channels, sc.filt);
+    hipLaunchKernelGGL(k_png_prev, dim3(nseg), dim3(64), 0, s, sc.filt, nn, sc.prev);
+    hipLaunchKernelGGL(k_png_match, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sc.filt, nn, sc.prev, sc.M);
+    hipLaunchKernelGGL(k_png_parse, dim3(nseg), dim3(256), 0, s, sc.M, nn, sc.prev);
+    hipLaunchKernelGGL(k_png_segment, dim3(nseg), dim3(SEG_THREADS), 0, s, sc.filt, nn, sc.M, sc.prev, sc.words, info);
+    hipLaunchKernelGGL(k_png_layout, dim3(1), dim3(1024), 0, s, info, nseg, nn, w, h, channels, sc.chunk_off, sc.out, cap, pinfo);
+    hipLaunchKernelGGL(k_png_copy, dim3(nseg), dim3(256), 0, s, sc.words, info, sc.chunk_off, sc.out, cap);
+    hipLaunchKernelGGL(k_png_crc, dim3(nseg), dim3(256), 0, s, info, nseg, sc.chunk_off, sc.out, cap);
+    HIP_TRY(hipGetLastError());
+    e->d_body = sc.out;
+    e->d_len = &pinfo->file_bytes;
+    e->cap = cap;
+    e->min_len = RTC_PNG_FILE_FIXED + RTC_PNG_CHUNK_OVERHEAD;
+    return RTC_OK;
 }

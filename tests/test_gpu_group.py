@@ -322,7 +322,8 @@ def test_render_paths_stop_allocating_after_the_first_launch(rtc, scenes):
     middle of a sequence). The case that did: a launch of FEWER views (a 5-frame warm-up) between launches of 8 left one of
     the two binning sets too small, and the next 8-view launch re-allocated it inside the timed region of
     `bench.py --steps 20 --warmup 5` (0.09-0.22 ms per frame instead of 0.07). Both sets are now made ready by the first
-    binned launch, for RTC_MAX_VIEWS views. rtc_render's scratch canvas: allocated once."""
+    binned launch, for RTC_MAX_VIEWS views. A pipelined context's lane sets: sized by each lane's first launch. The scratch
+    canvases of rtc_render, rtc_render_rgb8 and rtc_render_rgba8: allocated once."""
     import ctypes as C
     import torch
     lib = rtc.lib()
@@ -347,10 +348,27 @@ def test_render_paths_stop_allocating_after_the_first_launch(rtc, scenes):
             dw.render_views([cam] * views, 0, 1, buf.data_ptr(), 184)
         ctx.synchronize()
         assert allocs(ctx) == first, (n, first, allocs(ctx))
-        a = dw.render(cam)
-        mid = allocs(ctx)
-        b = dw.render(cam)
-        assert allocs(ctx) == mid and np.array_equal(a, b)
+        for render in (dw.render, dw.render_rgb8, dw.render_rgba8):
+            a = render(cam)
+            mid = allocs(ctx)
+            b = render(cam)
+            assert allocs(ctx) == mid and np.array_equal(a, b), render.__name__
+        ctx.close()
+        # pipelined: three 8-view launches, one per lane, then the same sequence; consecutive launches never share outputs
+        ctx = _ctx_env(rtc, RTC_BIN_SMALL_PIXELS=0, RTC_BIN_SMALL_PIXELS_PIPELINED=0)
+        ctx.set_pipeline(3)
+        dw = ctx.upload(w)
+        bufs = [buf] + [torch.zeros_like(buf) for _ in range(2)]
+        torch.cuda.synchronize()
+        for k in range(3):
+            dw.render_views([cam] * 8, 0, 1, bufs[k].data_ptr(), 184)
+        ctx.synchronize()
+        first = allocs(ctx)
+        assert first > 0
+        for k, views in enumerate((8, 5, 8, 8, 1, 8, 4, 8)):
+            dw.render_views([cam] * views, 0, 1, bufs[k % 3].data_ptr(), 184)
+        ctx.synchronize()
+        assert allocs(ctx) == first, (n, "pipelined", first, allocs(ctx))
         ctx.close()
 
 
