@@ -79,7 +79,7 @@ def parse_gif(b: bytes) -> dict:
         p += 1
         idx = np.frombuffer(b"".join(lzw_decode(bytes(data), min_size)), dtype=np.uint8)
         frames.append({"gce": gce, "rect": (left, top, fw, fh), "packed": fp, "table": table, "min_size": min_size,
-                       "indices": idx, "blocks_ok": True})
+                       "indices": idx, "blocks_ok": True, "data": bytes(data)})
         gce = None
     return {"size": (w, h), "frames": frames}
 
@@ -163,9 +163,7 @@ def test_exact_palette_is_lossless_and_sorted(rtc):
 
 
 def test_exact_palette_256_with_black(rtc):
-    v = np.arange(256, dtype=np.uint8)
-    frame = np.stack([v, v[::-1], v], -1).reshape(16, 16, 3)
-    frame[0, 0] = 0   # black replaces one colour: 256 -> 256 distinct still (0,255,0) gone, (0,0,0) in
+    frame = exact_256_with_black_frame()
     pal, idx, used = rtc.gif_quantize(frame)
     assert used == len(np.unique(frame.reshape(-1, 3), axis=0))
     _, _, dec = check_roundtrip(rtc, [frame])
@@ -182,9 +180,8 @@ def test_mapping_is_nearest_entry_with_lowest_index_ties(rtc, shape):
     assert np.array_equal(dec[0], pal[idx])
 
 
-def test_median_cut_rules_on_a_small_frame(rtc):
-    """Two flat colours plus a sprinkle: 300 distinct colours in few bins, so boxes run out before 256 and the unused
-    entries are black; every box mean is the rounded mean of its pixels."""
+def small_median_cut_frame():
+    """Two flat colours plus a sprinkle of 300 colours in one bin."""
     rng = np.random.default_rng(2)
     frame = np.zeros((30, 30, 3), dtype=np.uint8)
     frame[:, :15] = (200, 40, 40)
@@ -192,6 +189,20 @@ def test_median_cut_rules_on_a_small_frame(rtc):
     i = np.arange(300)
     pos = rng.permutation(900)[:300]
     frame.reshape(-1, 3)[pos] = np.stack([200 + (i & 7), 40 + ((i >> 3) & 7), 40 + ((i >> 6) & 7)], -1)   # one bin
+    return frame
+
+
+def exact_256_with_black_frame():
+    v = np.arange(256, dtype=np.uint8)
+    frame = np.stack([v, v[::-1], v], -1).reshape(16, 16, 3)
+    frame[0, 0] = 0   # black replaces one colour: 256 -> 256 distinct still (0,255,0) gone, (0,0,0) in
+    return frame
+
+
+def test_median_cut_rules_on_a_small_frame(rtc):
+    """Two flat colours plus a sprinkle: 300 distinct colours in few bins, so boxes run out before 256 and the unused
+    entries are black; every box mean is the rounded mean of its pixels."""
+    frame = small_median_cut_frame()
     assert len(np.unique(frame.reshape(-1, 3), axis=0)) > 256
     pal, idx, used = rtc.gif_quantize(frame)
     assert used == 2 and not pal[used:].any()

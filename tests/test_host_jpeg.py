@@ -277,30 +277,39 @@ def test_decoder_recovers_coefficients(rtc):
     _roundtrip(rtc, np.full((20, 30, 3), (200, 10, 99), dtype=np.uint8), 75)
 
 
+def stuffing_frames(rtc):
+    """The q = 100 noise frame that stuffs many 0xFF bytes, and the first 8 x 8 noise frame whose last data byte is 0xFF
+    made by the 1-bit padding (None if the search finds none)."""
+    many = np.random.default_rng(11).integers(0, 256, (64, 64, 3), dtype=np.uint8)
+    for seed in range(400):
+        img = np.random.default_rng(seed).integers(0, 256, (8, 8, 3), dtype=np.uint8)
+        if parse_jpeg(rtc.jpeg_encode(img, 100))["data"].endswith(b"\xff\x00"):
+            return many, img
+    return many, None
+
+
 def test_noise_stuffs_0xff_including_the_padded_byte(rtc):
-    rng = np.random.default_rng(11)
-    img = rng.integers(0, 256, (64, 64, 3), dtype=np.uint8)
+    img, last = stuffing_frames(rtc)
     b = _roundtrip(rtc, img, 100)
     data = parse_jpeg(b)["data"]
     assert data.count(b"\xff\x00") > 10
-    found = False
-    for seed in range(400):   # a frame whose last data byte is 0xFF made by the 1-bit padding
-        img = np.random.default_rng(seed).integers(0, 256, (8, 8, 3), dtype=np.uint8)
-        d = parse_jpeg(rtc.jpeg_encode(img, 100))["data"]
-        if d.endswith(b"\xff\x00"):
-            _roundtrip(rtc, img, 100)
-            found = True
-            break
-    assert found
+    assert last is not None
+    _roundtrip(rtc, last, 100)
+
+
+def flat_blocks_frame():
+    """4000 flat 8 x 8 blocks of random colours, one above the other: (colours, frame)."""
+    rng = np.random.default_rng(3)
+    cols = rng.integers(0, 256, (4000, 3))
+    img = np.repeat(cols[:, None, :], 8, axis=1).reshape(4000, 8, 3)
+    img = np.repeat(img[:, None], 8, axis=1).reshape(4000 * 8, 8, 3).astype(np.uint8)
+    return cols, img
 
 
 def test_flat_block_dc_matches_bt601(rtc):
     """The DC of a flat block at q = 100 (every divisor 1) is 8 * (sample - 128): the converted sample, checked against
     float64 BT.601 to +-1."""
-    rng = np.random.default_rng(3)
-    cols = rng.integers(0, 256, (4000, 3))
-    img = np.repeat(cols[:, None, :], 8, axis=1).reshape(4000, 8, 3)
-    img = np.repeat(img[:, None], 8, axis=1).reshape(4000 * 8, 8, 3).astype(np.uint8)
+    cols, img = flat_blocks_frame()
     co = rtc.jpeg_coefficients(img, 100)
     assert np.all(co[:, :, 1:] == 0)
     assert np.all(co[:, :, 0] % 8 == 0)

@@ -200,10 +200,11 @@ def inflate_blocks(zdata: bytes):
 
 
 # ---- restatements ------------------------------------------------------------------------------------------------------
-def filters_numpy(px: np.ndarray):
+def filter_sums(px: np.ndarray):
+    """Per row, the five filters' sums of min(v, 256 - v) over the filtered bytes (the choice heuristic of include/rtc.h)."""
     h, w, c = px.shape
     a = px.reshape(h, w * c).astype(np.int32)
-    types = []
+    out = []
     for y in range(h):
         cur = a[y]
         up = a[y - 1] if y else np.zeros_like(cur)
@@ -213,9 +214,13 @@ def filters_numpy(px: np.ndarray):
         pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - ul)
         paeth = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, ul))
         cands = [cur, cur - left, cur - up, cur - ((left + up) >> 1), cur - paeth]
-        sums = [int(np.minimum(v & 255, 256 - (v & 255)).sum()) for v in cands]
-        types.append(int(np.argmin(sums)))   # argmin takes the first of equal sums
-    return np.array(types, dtype=np.uint8)
+        out.append([int(np.minimum(v & 255, 256 - (v & 255)).sum()) for v in cands])
+    return out
+
+
+def filters_numpy(px: np.ndarray):
+    # argmin takes the first of equal sums
+    return np.array([int(np.argmin(sums)) for sums in filter_sums(px)], dtype=np.uint8)
 
 
 def hash3(s, p):
@@ -471,9 +476,12 @@ def test_filter_choice(c):
         np.testing.assert_array_equal(unfilter(filtered.tobytes(), w, h, c), px)
 
 
-@pytest.mark.parametrize("px", [mixed(), mixed(90, 130, 4), gradient(100, 150, 3)], ids=["mixed", "mixed4", "gradient"])
-def test_stream_structure(px):
-    png = rtc.png_encode(px)
+def check_stream(png: bytes, px: np.ndarray) -> list:
+    """The per-segment structure of a compressed PNG of `px`, checked against this file's restatements: one block per
+    segment and an empty stored block after each but the last, IDAT chunks on the segment boundaries, each block's type
+    the cheapest by plan(), its tokens those of lengths_all / parse, its bit count exact, a dynamic block's code lengths,
+    run-length codes and costs those of package-merge within 15 and 7 bits. Returns one dict per segment: the block, its
+    tokens and bounds, and the plan's bits and parts."""
     _, raw, idat = decode(png)
     n = len(raw)
     nseg = -(-n // SEG)
@@ -493,19 +501,19 @@ def test_stream_structure(px):
             f = blocks[2 * g + 1]
             assert (f["type"], f["final"], f["out0"], f["out1"]) == (0, 0, b["out1"], b["out1"])
     # each IDAT chunk is its segment's bytes: the chunk boundaries fall on the segment boundaries
-    zdata = b"".join(idat)
     at = 0
     for g, d in enumerate(idat):
         at += len(d)
         if g + 1 < nseg:
             assert blocks[2 * g + 1]["end"] == 8 * (at - 2)
     L, D = lengths_all(raw)
-    counted = set()
+    segs = []
     for g in range(nseg):
         b = blocks[2 * g]
         s0, end = g * SEG, min(n, (g + 1) * SEG)
         toks = parse(raw, L, D, s0, end)
         bits, pl = plan(toks, end - s0)
+        segs.append({"block": b, "s0": s0, "end": end, "toks": toks, "bits": bits, "plan": pl, "L": L, "D": D, "raw": raw})
         best = min(range(3), key=lambda t: (bits[t], t))
         assert b["type"] == best, (g, bits)
         if b["type"] == 0:
@@ -520,7 +528,6 @@ def test_stream_structure(px):
             else:
                 pos += 1
         assert b["end"] - b["start"] == bits[b["type"]]
-        counted.add(b["type"])
         if b["type"] == 2:
             assert b["lit"] == pl["lit"] and b["dist"] == pl["dist"] and b["cl"] == pl["cl"] and b["hclen"] == pl["hclen"]
             assert b["rle"] == [(s, r if s >= 16 else 0) for s, r in pl["rle"]]
@@ -531,7 +538,13 @@ def test_stream_structure(px):
                 assert sum(f * l for f, l in zip(dist, b["dist"] + [0] * 30)) == optimal_cost(dist, 15)
             if sum(1 for f in pl["clf"] if f) >= 2:
                 assert sum(f * l for f, l in zip(pl["clf"], b["cl"])) == optimal_cost(pl["clf"], 7)
-    assert counted, "no compressed block to check"
+    return segs
+
+
+@pytest.mark.parametrize("px", [mixed(), mixed(90, 130, 4), gradient(100, 150, 3)], ids=["mixed", "mixed4", "gradient"])
+def test_stream_structure(px):
+    segs = check_stream(rtc.png_encode(px), px)
+    assert any(s["block"]["type"] != 0 for s in segs), "no compressed block to check"
 
 
 def test_package_merge_limits():
