@@ -123,14 +123,11 @@ enum { RTC_MAX_VIEWS = 8 };
 #ifndef RTC_BLOCK_STACK
 #define RTC_BLOCK_STACK 64
 #endif
-// K3, ray compaction between bounces (rtc_kernels.hip, COMPACT): reflection-only Worlds on the culled variants render with
-// TWO waves per workgroup, which merge their live rays into one wave once they fit (RTC_COMPACT = 1); 0 = one wave per
-// workgroup, no merging. Host grid and kernel must agree on the workgroup size: RTC_BLOCK_FOR.
-#ifndef RTC_COMPACT
-#define RTC_COMPACT 0
-#endif
-#define RTC_COMPACT_FOR(cull, refl, refr, probe) (RTC_COMPACT && (cull) && (refl) && !(refr) && !(probe))
-// `cull` is the cull level of the variant: 0 = none, 1 = one level (n <= 256), 2 = two levels (RTC_CULL_LEVEL).
+// Where a render variant takes its object records from (k_trace's SRC, chosen by the host's choose_source), and the
+// variant's cull level: 0 = none (brute force), 1 = one level (n <= 256), 2 = two levels.
+enum { SRC_SMEM = 0, SRC_LDS1 = 1, SRC_LDSN = 2, SRC_CULL = 3, SRC_CULL2 = 4 };
+#define CULL_LEVEL(S) ((S) == SRC_CULL2 ? 2 : (S) == SRC_CULL ? 1 : 0)
+// Host grid and kernel must agree on the workgroup size: RTC_BLOCK_FOR(CULL_LEVEL(src), ...) on both sides.
 #ifndef RTC_BLOCK_CULL2
 #define RTC_BLOCK_CULL2 64 // large worlds, flat kernel: C3 0.106 -> 0.102 ms against 128 (profiles/r02_exp_block_size.log)
 #endif
@@ -139,8 +136,7 @@ enum { RTC_MAX_VIEWS = 8 };
                            // 0.0576 -> 0.0561 ms pipelined, 0.0581 -> 0.0566 solo against 128 (north star; C2 -2.4 %); before the chunks: -1 %
 #endif
 #define RTC_BLOCK_FOR(cull, refl, refr, probe) \
-    (((refl) || (refr)) ? (RTC_COMPACT_FOR(cull, refl, refr, probe) ? 128 : RTC_BLOCK_STACK) \
-                        : ((cull) == 2 && !(probe) ? RTC_BLOCK_CULL2 : ((cull) == 1 && !(probe) ? RTC_BLOCK_CULL1 : RTC_BLOCK)))
+    (((refl) || (refr)) ? RTC_BLOCK_STACK : ((cull) == 2 && !(probe) ? RTC_BLOCK_CULL2 : ((cull) == 1 && !(probe) ? RTC_BLOCK_CULL1 : RTC_BLOCK)))
 #define RTC_TILE_W_FOR(cull, refl, refr, probe) ((RTC_BLOCK_FOR(cull, refl, refr, probe) / 64u) * 8u)
 
 // Tile-list entries hold (key >> 16) << 16 | index while every index fits 16 bits

@@ -12,8 +12,6 @@
 #include "rtc_device.h"
 #include "rtc_gamma.h"
 
-enum { SRC_SMEM = 0, SRC_LDS1 = 1, SRC_LDSN = 2, SRC_CULL = 3, SRC_CULL2 = 4 };
-
 struct rtc_context {
     int device = -1;
     unsigned long long render_allocs = 0; // hipMalloc calls made by render entry points (rtc_debug_render_allocs)
