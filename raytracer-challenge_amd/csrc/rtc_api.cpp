@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -565,6 +566,8 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
     rtc_world *w = new (std::nothrow) rtc_world;
     if (!w) return RTC_ERR_NOMEM;
     w->ctx = ctx;
+    static std::atomic<uint64_t> uploads{0};
+    w->serial = ++uploads;
     w->pre_limit = std::isfinite(pre_limit) ? pre_limit : 0.;
     w->ngroups = ngroups;
     w->device = ctx->device;
@@ -754,6 +757,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
                           (src == SRC_CULL && (piped ? launch_pixels >= ctx->bin_small_pixels_pipelined
                                                      : launch_pixels >= ctx->bin_small_pixels));
     rtc_world::BinSet *binset = nullptr;
+    int bin_set = -1; // which of w->bin this launch's lists are in (rtc_debug_tile_counts)
     bool bin_ok = bin_this && ctx->binning && (y0 % 8u) == 0u && w->n != 0u;
     const uint32_t tiles_x = (cam->hsize + 7u) / 8u, tiles_y = (cam->vsize + 7u) / 8u;
     const size_t tiles = (size_t)tiles_x * tiles_y * nviews;
@@ -763,6 +767,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         rtc_world::BinSet &B = w->bin[lane];
         bin_ok = ready_binset(ctx, B, tiles, tiles, (size_t)w->n * nviews, (size_t)w->n * nviews, true, stream);
         if (bin_ok) HIP_TRY(bin_tiles(P, w, B, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
+        if (bin_ok) bin_set = (int)lane;
     } else if (bin_ok) {
         if (!ctx->side_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
         // Capacity. Both sets are made ready by the FIRST binned launch, and for RTC_MAX_VIEWS views while that stays within
@@ -783,6 +788,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         }
     }
     if (bin_ok && !piped) {
+        bin_set = (int)(w->bin_next & 1u);
         rtc_world::BinSet &B = w->bin[w->bin_next++ & 1u];
         // The binning depends on the World (resident since rtc_world_create) and on this launch's cameras only, so it goes
         // to the side stream: it runs beside the PREVIOUS launch's render kernel, which still reads the other set. It must
@@ -833,6 +839,8 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     ctx->last = rtc_launch_info{(uint32_t)src, (w->any_refl || w->any_refr) ? 1u : 0u, w->any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
                                 P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], {0u, 0u}};
     ++ctx->launches_total;
+    ctx->last_bin = rtc_context::LastBin{};
+    if (P.tile_cnt && bin_set >= 0) ctx->last_bin = rtc_context::LastBin{w->serial, (uint32_t)bin_set, nviews, tiles_x, tiles_y};
     // rtc_stats::pixels is known here (the kernel traces exactly the pixels of this launch's rows; Camera::render leaves the
     // last row and column alone, camera.rs:120-121): counted on the host, one atomic per wave less
     {
@@ -899,6 +907,49 @@ rtc_status rtc_stats_read(rtc_context *ctx, rtc_stats *out) {
 extern "C" rtc_status rtc_debug_render_allocs(rtc_context *ctx, unsigned long long *out) {
     if (!ctx || !out) return RTC_ERR_ARG;
     *out = ctx->render_allocs;
+    return RTC_OK;
+}
+
+// Diagnostic (not part of include/rtc.h): what rtc_world_create derived for the candidate lists of `w`. info = {n_unb,
+// ngroups, light_cap (0: no light lists), n}; *light_reach; cell_counts (optional): the 6 * RTC_LIGHT_R * RTC_LIGHT_R
+// per-cell counters of the light lists (a counter above light_cap: that cell's list overflowed), untouched when the World
+// has no lists; bounds (optional): the n DevBound records {cx, cy, cz, r, k, cn} in insertion order. Copies only.
+extern "C" rtc_status rtc_debug_world_lists(const rtc_world *w, uint32_t info[4], double *light_reach, uint32_t *cell_counts, double *bounds) {
+    if (!w || !info || !light_reach) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(w->device));
+    HIP_TRY(hipDeviceSynchronize());
+    info[0] = w->n_unb; info[1] = w->ngroups; info[2] = w->d_light_cnt.get() ? w->light_cap : 0u; info[3] = w->n;
+    *light_reach = w->light_reach;
+    static_assert(sizeof(DevBound) == 6 * sizeof(double), "bounds are read back as six doubles per object");
+    if (cell_counts && w->d_light_cnt.get())
+        HIP_TRY(hipMemcpy(cell_counts, w->d_light_cnt.get(), sizeof(uint32_t) * 6u * RTC_LIGHT_R * RTC_LIGHT_R, hipMemcpyDeviceToHost));
+    if (bounds && w->n) HIP_TRY(hipMemcpy(bounds, w->d_bound.get(), sizeof(DevBound) * w->n, hipMemcpyDeviceToHost));
+    return RTC_OK;
+}
+
+// Diagnostic (not part of include/rtc.h): the tile lists of the context's most recent render launch, which must have been a
+// launch of `w`. dims = {binned, nviews, tiles_x, tiles_y}; binned == 0 ("none": that launch read no tile lists) leaves the
+// rest untouched. counts (optional, `counts_cap` words, at least nviews * tiles_y * tiles_x): per (view, tile) the list
+// count k_bin_tiles wrote, tile (tx, ty) of view v at (v * tiles_y + ty) * tiles_x + tx (above RTC_TILE_LIST_CAP: the list
+// overflowed; tile rows the launch did not render hold stale words). rows (optional, `rows_cap` words, at least 2 * nviews):
+// per view the two row words. Waits for the context's work first. Copies only.
+extern "C" rtc_status rtc_debug_tile_counts(rtc_context *ctx, const rtc_world *w, uint32_t dims[4], uint32_t *counts, size_t counts_cap,
+                                            uint32_t *rows, size_t rows_cap) {
+    if (!ctx || !w || !dims || w->ctx != ctx) return RTC_ERR_ARG;
+    dims[0] = dims[1] = dims[2] = dims[3] = 0u;
+    const rtc_context::LastBin &L = ctx->last_bin;
+    if (L.world_serial == 0 || L.world_serial != w->serial) return RTC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(drain_lanes(ctx));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->side_stream) HIP_TRY(hipStreamSynchronize(ctx->side_stream));
+    const rtc_world::BinSet &B = w->bin[L.set];
+    const size_t tiles = (size_t)L.nviews * L.tiles_x * L.tiles_y;
+    if (!B.tile_cnt.get() || B.tile_cnt.capacity() < RTC_BIN_ROW_WORDS + tiles) return RTC_ERR_ARG;
+    if ((counts && counts_cap < tiles) || (rows && rows_cap < 2u * (size_t)L.nviews)) return RTC_ERR_ARG;
+    dims[0] = 1u; dims[1] = L.nviews; dims[2] = L.tiles_x; dims[3] = L.tiles_y;
+    if (counts) HIP_TRY(hipMemcpy(counts, B.tile_cnt.get() + RTC_BIN_ROW_WORDS, sizeof(uint32_t) * tiles, hipMemcpyDeviceToHost));
+    if (rows) HIP_TRY(hipMemcpy(rows, B.tile_cnt.get(), sizeof(uint32_t) * 2u * L.nviews, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 

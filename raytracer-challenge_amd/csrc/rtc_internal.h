@@ -50,6 +50,12 @@ struct rtc_context {
     // the source / lists the most recent render launch ran with (rtc_context_last_launch_info)
     rtc_launch_info last{};
     uint64_t launches_total = 0; // render launches since the context was created (never reset)
+    // the tile lists the most recent render launch read, if it was binned (rtc_debug_tile_counts): the World's upload serial
+    // (a World created later at the same address has another), which of its sets, and the launch's grid
+    struct LastBin {
+        uint64_t world_serial = 0; // 0: the last launch was not binned
+        uint32_t set = 0, nviews = 0, tiles_x = 0, tiles_y = 0;
+    } last_bin;
     hipEvent_t fence_ev = nullptr; // rtc_context_fence
     bool light_lists = true; // RTC_LIGHT_LISTS=0: shadow passes of two-level worlds walk the groups (A/B)
     bool binning = true;  // RTC_BINNING=0: primary rays take the wave-level cull / group walk too (A/B)
@@ -85,6 +91,7 @@ struct rtc_context {
 struct rtc_world {
     rtc_context *ctx = nullptr; // identity check only; never dereferenced at destroy time
     int device = -1;
+    uint64_t serial = 0; // 1, 2, ... in order of rtc_world_create, process-wide: never reused
     uint32_t n = 0;
     DevBuf<DevIsect> d_isect;
     DevBuf<uint32_t> d_kind;

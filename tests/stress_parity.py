@@ -17,6 +17,7 @@ from _bootstrap import package  # noqa: E402
 
 rtc = package()
 from test_gpu_parity import adversarial_scene  # noqa: E402
+import candidate_list_cases as K  # noqa: E402
 
 n_worlds = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 5000
@@ -104,6 +105,12 @@ def mirror_world(seed):
     return w, cam
 
 
+def list_family(seed):
+    """candidate_list_cases.list_world: 32..1500 objects, planes in arbitrary poses, the light and the camera in odd places."""
+    shapes, lgt, cam = K.list_world(seed, "small" if seed % 2 else "large")
+    return K.as_world(rtc, shapes, lgt), cam
+
+
 ctx = rtc.Context(0)
 if pipeline > 1:
     ctx.set_pipeline(pipeline)
@@ -111,7 +118,7 @@ bad = 0
 t0 = time.time()
 for k in range(n_worlds):
     seed = seed0 + k
-    w, cam = mirror_world(seed) if k % 5 == 4 else (far_world(seed) if k % 4 == 3 else (big_world(seed) if k % 3 == 2 else adversarial_scene(rtc, seed)))
+    w, cam = list_family(seed) if k % 7 == 6 else mirror_world(seed) if k % 5 == 4 else (far_world(seed) if k % 4 == 3 else (big_world(seed) if k % 3 == 2 else adversarial_scene(rtc, seed)))
     dw = ctx.upload(w)
     got, st = dw.render(cam, rtc.MODE_RENDER_ASYNC, with_stats=True)
     brute, sb = dw.render(cam, rtc.MODE_RENDER_ASYNC, flags=1, with_stats=True)
