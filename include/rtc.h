@@ -538,6 +538,22 @@ rtc_status  rtc_context_device_info(rtc_context *ctx, char *name, size_t cap,
  * stays resident in HBM across renders. Validates materials (RTC_ERR_NO_COLOR). */
 rtc_status  rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t n_shapes,
                              const rtc_light *light, rtc_world **out);
+/* Replace the contents of a resident World of `ctx`: shapes, materials, light and n_shapes may all
+ * change. Validates as rtc_world_create does (plus RTC_ERR_ARG for a World of another context); a
+ * rejected call leaves the World as it was. Ordered like a launch: every render launched before the
+ * call sees the old contents, on whichever lane it runs, every render launched after it the new
+ * ones. `shapes` may be freed on return. The derived tables (bounds, Morton order, group spheres,
+ * prefilter records, light lists) are rebuilt on the device beside the renders in flight, with the
+ * bits a fresh World would hold. The call waits for no render kernel and, while n_shapes is no
+ * larger than the World has held and its light lists no larger (the 32 / 256 shape thresholds),
+ * allocates no device memory; a growing World waits for the context and reallocates first, and if
+ * that fails (RTC_ERR_NOMEM) the World has no contents: renders of it return RTC_ERR_NOMEM until
+ * an update succeeds. The first update of a World also creates its build stream, its events and
+ * one page-locked staging block. Three scalars of the build are kernel arguments of the render
+ * kernels, so the FIRST render launch after an update blocks the host until the build kernels of
+ * that update (not any render kernel) have finished and their 32-byte header has arrived. */
+rtc_status  rtc_world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes,
+                             uint32_t n_shapes, const rtc_light *light);
 void        rtc_world_destroy(rtc_world *w);
 
 /* Camera::render / render_async for canvas rows [y0, y1) into a DEVICE buffer of

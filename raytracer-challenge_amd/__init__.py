@@ -985,6 +985,13 @@ class DeviceWorld:
         self.n = len(world.shapes)
         ctx._worlds.append(weakref.ref(self))
 
+    def update(self, world: World) -> None:
+        """Replace the resident World's contents by `world` (rtc_world_update): ordered like a launch, rebuilt on the
+        device, no allocation while the World does not grow."""
+        arr = world.array()
+        _check(lib().rtc_world_update(self.ctx._h, self._h, arr, len(world.shapes), C.byref(world.light)), "rtc_world_update")
+        self.n = len(world.shapes)
+
     def close(self):
         if self._h:
             lib().rtc_world_destroy(self._h)

@@ -175,6 +175,7 @@ PROTOTYPES = {
     "rtc_context_synchronize": (C.c_int32, [VP]),
     "rtc_context_device_info": (C.c_int32, [VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rtc_world_create": (C.c_int32, [VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight), C.POINTER(VP)]),
+    "rtc_world_update": (C.c_int32, [VP, VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight)]),
     "rtc_world_destroy": (None, [VP]),
     "rtc_render_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),
     "rtc_render_bands": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "rtc.h"
@@ -80,6 +81,8 @@ uint64_t spread21(uint64_t v) {
     v = (v | (v << 2)) & 0x1249249249249249ULL;
     return v;
 }
+constexpr size_t LIGHT_CELLS = 6u * (size_t)RTC_LIGHT_R * RTC_LIGHT_R, LIGHT_MACROS = 6u * (size_t)(RTC_LIGHT_R / 8u) * (RTC_LIGHT_R / 8u);
+
 uint64_t morton_key(const DevBound &b, const double lo[3], const double hi[3]) {
     uint64_t k = 0;
     const double c[3] = {b.cx, b.cy, b.cz};
@@ -206,32 +209,204 @@ void fill_camera(RenderParams &P, const rtc_camera *cam, uint32_t view = 0) {
     std::memcpy(c.vinv, cam->view_inv, sizeof(double) * 12);
 }
 
-void fill_world(RenderParams &P, const rtc_world *w) {
-    P.isect = w->d_isect.get();
-    P.kind = w->d_kind.get();
-    P.shade = w->d_shade.get();
-    P.prim = w->d_prim.get();
-    P.bound = w->d_bound.get();
-    P.isect_s = w->d_isect_s.get();
-    P.kind_s = w->d_kind_s.get();
-    P.bound_s = w->d_bound_s.get();
-    P.orig_s = w->d_orig_s.get();
-    P.gbound = w->d_gbound.get();
-    P.idtab = w->d_idtab.get();
-    P.pre = w->d_pre.get();
-    P.pre_s = w->d_pre_s.get();
-    P.pre_limit = w->pre_limit;
-    P.light_cnt = w->d_light_cnt.get();
-    P.light_list = w->d_light_list.get();
-    P.light_reach = w->light_reach;
-    P.light_cap = w->light_cap;
-    P.n_unb = w->n_unb;
-    P.ngroups = w->ngroups;
-    P.n = w->n;
+void fill_world(RenderParams &P, const rtc_world::Gen &G) {
+    P.isect = G.isect;
+    P.kind = G.kind;
+    P.shade = G.shade;
+    P.bound = G.bound;
+    P.isect_s = G.isect_s;
+    P.kind_s = G.kind_s;
+    P.bound_s = G.bound_s;
+    P.orig_s = G.orig_s;
+    P.gbound = G.gbound;
+    P.idtab = G.idtab;
+    P.pre = G.pre;
+    P.pre_s = G.pre_s;
+    P.pre_limit = G.pre_limit;
+    P.light_cnt = G.light_cap ? G.lights : nullptr;
+    P.light_list = G.light_cap ? G.lights + LIGHT_CELLS : nullptr;
+    P.light_reach = G.light_reach;
+    P.light_cap = G.light_cap;
+    P.n_unb = G.n_unb;
+    P.ngroups = G.ngroups;
+    P.n = G.n;
     for (int i = 0; i < 3; ++i) {
-        P.light_pos[i] = w->light.position[i];
-        P.light_int[i] = w->light.intensity[i];
+        P.light_pos[i] = G.light.position[i];
+        P.light_int[i] = G.light.intensity[i];
     }
+}
+
+// ---- generations (rtc_world::Gen)
+
+// Which of a context's streams: lane l, the context's own stream, its side stream (bits of Gen::ordered; the first
+// MAX_LANES + 1 index Gen::read).
+constexpr uint32_t BIT_STREAM = rtc_context::MAX_LANES, BIT_SIDE = rtc_context::MAX_LANES + 1u;
+
+// Entries per cell of the light lists of a World of n shapes (0: none) — the sizing half of rtc_world_create's rules; the
+// other half, a usable reach, is known only once the bounds are.
+uint32_t light_cap_for(uint32_t n) { return n >= 32u ? (n > 256u ? RTC_LIGHT_LIST_CAP : RTC_LIGHT_LIST_CAP_SMALL) : 0u; }
+
+// Points G's tables into its slab for a World of n shapes and returns the bytes they take. isect, shade, idtab and kind —
+// what the host flattens — come first, `*staged` bytes in all: an update stages them in the same layout and copies them at once.
+size_t carve_gen(rtc_world::Gen &G, uint32_t n, size_t *staged) {
+    const size_t na = n ? n : 1u, ng = n ? (n + 63u) / 64u : 1u, npad = rtc_world_build_npad(n);
+    unsigned char *base = G.slab;
+    size_t off = 0;
+    auto take = [&](auto *&p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+        off += (count * sizeof(*p) + 255u) & ~(size_t)255u;
+    };
+    take(G.isect, na);
+    take(G.shade, na);
+    take(G.idtab, na);
+    take(G.kind, na);
+    if (staged) *staged = off;
+    take(G.bound, na);
+    take(G.isect_s, na);
+    take(G.kind_s, na);
+    take(G.bound_s, na);
+    take(G.orig_s, na);
+    take(G.gbound, ng);
+    take(G.pre, na);
+    take(G.pre_s, na);
+    take(G.partial, ng * RTC_WB_PARTIALS);
+    take(G.key, npad);
+    take(G.idx, npad);
+    take(G.d_hdr, 1);
+    return off;
+}
+
+// Room in every generation for `cap_n` shapes and light lists of `light_cap` entries per cell, and the brute-force
+// variants' scratch. Grow-only; what grows is freed first, so nothing may be in flight. The lists are an optimisation (the
+// shadow pass walks without them): when there is no memory for them the World has none.
+rtc_status reserve_generations(rtc_world *w, uint32_t cap_n, uint32_t light_cap) {
+    rtc_world::Gen sizing;
+    const size_t bytes = carve_gen(sizing, std::max(cap_n, w->cap_n), nullptr);
+    if (w->slabs.capacity() < bytes * rtc_world::GENS) {
+        const rtc_status st = w->slabs.reserve(bytes * rtc_world::GENS, &w->allocs);
+        for (uint32_t g = 0; g < rtc_world::GENS; ++g) w->gen[g].slab = st == RTC_OK ? w->slabs.get() + bytes * g : nullptr;
+        if (st != RTC_OK) return st;
+    }
+    if (cap_n > w->cap_n) w->cap_n = cap_n;
+    const size_t na = cap_n ? cap_n : 1u;
+    if (w->d_prim.capacity() < na) {
+        const rtc_status st = w->d_prim.reserve(na, &w->allocs);
+        if (st != RTC_OK) return st;
+        if (hipMemset(w->d_prim.get(), 0, sizeof(DevPrim) * na) != hipSuccess) return RTC_ERR_DEVICE;
+    }
+    if (light_cap > w->light_cap_alloc) {
+        const size_t per = LIGHT_CELLS * (1u + (size_t)light_cap);
+        const bool got = w->d_light_cells.reserve(LIGHT_CELLS + LIGHT_MACROS, &w->allocs) == RTC_OK &&
+                         w->lights.reserve(per * rtc_world::GENS, &w->allocs) == RTC_OK;
+        if (!got) w->lights.reset();
+        for (uint32_t g = 0; g < rtc_world::GENS; ++g) w->gen[g].lights = got ? w->lights.get() + per * g : nullptr;
+        w->light_cap_alloc = got ? light_cap : 0u;
+    }
+    return RTC_OK;
+}
+
+// rtc_world_create's and rtc_world_update's checks of the shapes.
+rtc_status check_shapes(const rtc_shape *shapes, uint32_t n) {
+    // Material::lighting panics when a material has neither colour nor pattern (material.rs:328-331)
+    for (uint32_t i = 0; i < n; ++i) {
+        if (shapes[i].kind > RTC_CUBE || shapes[i].material.pattern_kind > RTC_PATTERN_GRID) return RTC_ERR_ARG;
+        if (shapes[i].material.pattern_kind == RTC_PATTERN_NONE && !shapes[i].material.has_color) return RTC_ERR_NO_COLOR;
+    }
+    return RTC_OK;
+}
+
+// The shapes as the kernels read them: max(n, 1) records each of isect, kind, shade and idtab (zero beyond n).
+void flatten_shapes(const rtc_shape *shapes, uint32_t n, DevIsect *isect, uint32_t *kind, DevShade *shade, DevIdEntry *idtab, bool *refl,
+                    bool *refr) {
+    const uint32_t na = n ? n : 1;
+    std::memset(isect, 0, sizeof(DevIsect) * na);
+    std::memset(kind, 0, sizeof(uint32_t) * na);
+    std::memset(shade, 0, sizeof(DevShade) * na);
+    bool any_refl = false, any_refr = false;
+    // World::add_shape numbers the shapes last_world_id + 1 (shape.rs:661-667). A caller that leaves every id
+    // 0 (rtc_shape_init does) gets exactly that numbering; ids that were given are honoured as they are —
+    // equal ids are ONE container to compute_refractive (shape.rs:127), which is also what the reference's
+    // own u8 ids do beyond 255 shapes.
+    bool all_zero = true;
+    for (uint32_t i = 0; i < n; ++i) all_zero = all_zero && shapes[i].world_id == 0u;
+    idtab[0] = DevIdEntry{0u, 0u};
+    for (uint32_t i = 0; i < n; ++i) idtab[i] = DevIdEntry{i, all_zero ? i + 1u : shapes[i].world_id};
+    std::stable_sort(idtab, idtab + n, [](const DevIdEntry &a, const DevIdEntry &b) { return a.id < b.id; });
+    for (uint32_t i = 0; i < n; ++i) {
+        const rtc_shape &s = shapes[i];
+        const rtc_material &m = s.material;
+        std::memcpy(isect[i].m, s.inv, sizeof(double) * 12);
+        kind[i] = s.kind;
+        DevShade &d = shade[i];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                // Shape::normal_at uses transform_transpose (shape.rs:38); Cube::normal_at
+                // transposes its inverse on the fly (shape.rs:627)
+                d.nt[r * 3 + c] = (s.kind == RTC_CUBE) ? s.inv[c * 4 + r] : s.inv_t[r * 4 + c];
+        for (int c = 0; c < 3; ++c) {
+            d.color[c] = m.color[c];
+            d.pat_a[c] = m.pat_a[c];
+            d.pat_b[c] = m.pat_b[c];
+        }
+        d.ambient = m.ambient;
+        d.diffuse = m.diffuse;
+        d.specular = m.specular;
+        d.shininess = m.shininess;
+        d.reflective = m.reflective;
+        d.transparency = m.transparency;
+        d.refractive_index = m.refractive_index;
+        std::memcpy(d.pat_inv, m.pat_inv, sizeof(double) * 12);
+        if (s.kind == RTC_PLANE) {
+            // world_normal = local_normal.transform(inverse_transpose).normalize() with local_normal
+            // (0,1,0) (shape.rs:37-39, 481-483; transform.rs:114-117; vec.rs:65-76): mul/add/sqrt/div
+            // in the reference's order, correctly rounded on the host exactly as on the device
+            // (this file is compiled with -ffp-contract=off)
+            const double *t = d.nt;
+            const double wx = t[0] * 0. + t[1] * 1. + t[2] * 0.;
+            const double wy = t[3] * 0. + t[4] * 1. + t[5] * 0.;
+            const double wz = t[6] * 0. + t[7] * 1. + t[8] * 0.;
+            const double mag = std::sqrt(wx * wx + wy * wy + wz * wz);
+            d.plane_n[0] = wx / mag;
+            d.plane_n[1] = wy / mag;
+            d.plane_n[2] = wz / mag;
+        }
+        d.kind = s.kind;
+        d.pattern_kind = m.pattern_kind;
+        d.world_id = all_zero ? i + 1u : s.world_id;
+        if (m.reflective > 0.) any_refl = true;     // reflected_color shape.rs:730
+        if (m.transparency != 0.0) any_refr = true; // refracted_color shape.rs:752
+    }
+    *refl = any_refl;
+    *refr = any_refr;
+}
+
+// The generation a launch made now renders, its header read (Gen::hdr_pending): the one host wait of an update's
+// consumer — for the build kernels only, which nothing but the previous update precedes on their stream.
+rtc_status current_gen(const rtc_world *w, rtc_world::Gen **out) {
+    if (!w->valid) return RTC_ERR_NOMEM; // a growing update failed half way: no contents until an update succeeds
+    rtc_world::Gen &G = w->gen[w->cur];
+    if (G.hdr_pending) {
+        HIP_TRY(hipEventSynchronize(G.built));
+        G.n_unb = G.h_hdr->n_unb;
+        G.pre_limit = G.h_hdr->pre_limit;
+        G.light_reach = G.h_hdr->light_reach;
+        G.light_cap = G.light_reach > 0. ? G.light_cap_want : 0u;
+        G.hdr_pending = false;
+    }
+    *out = &G;
+    return RTC_OK;
+}
+// Orders work enqueued next on `stream` (stream `bit`) behind G's build, once per stream.
+hipError_t order_behind_build(rtc_world::Gen &G, hipStream_t stream, uint32_t bit) {
+    if (!G.device_built || (G.ordered & (1u << bit))) return hipSuccess; // (a host build was complete before rtc_world_create returned)
+    G.ordered |= 1u << bit;
+    return hipStreamWaitEvent(stream, G.built, 0);
+}
+// A launch on `stream` (lane l, or BIT_STREAM) has read G: the update that writes G next waits for it on its own stream.
+hipError_t record_read(const rtc_world *w, rtc_world::Gen &G, hipStream_t stream, uint32_t bit) {
+    if (!w->updated) return hipSuccess; // the first update records for everything launched before it
+    G.read_mask |= 1u << bit;
+    return hipEventRecord(G.read[bit], stream);
 }
 
 // The RGBA entries accept what Canvas::set_gamma can meaningfully hold: a positive, finite gamma.
@@ -312,6 +487,7 @@ rtc_status rtc_context_create(int32_t device, void *stream, rtc_context **out) {
     }
     if (const char *e = std::getenv("RTC_BINNING")) ctx->binning = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_LIGHT_LISTS")) ctx->light_lists = std::atoi(e) != 0;
+    if (const char *e = std::getenv("RTC_WORLD_UPDATE")) ctx->world_update = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_SKY_ROWS")) ctx->sky_rows = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS")) ctx->bin_small_pixels = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS_PIPELINED")) ctx->bin_small_pixels_pipelined = std::strtoull(e, nullptr, 10);
@@ -417,74 +593,18 @@ rtc_status rtc_context_device_info(rtc_context *ctx, char *name, size_t cap, int
 rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *light, rtc_world **out) {
     if (!ctx || !out || !light || (n && !shapes)) return RTC_ERR_ARG;
     *out = nullptr;
-    // Material::lighting panics when a material has neither colour nor pattern (material.rs:328-331)
-    for (uint32_t i = 0; i < n; ++i) {
-        if (shapes[i].kind > RTC_CUBE || shapes[i].material.pattern_kind > RTC_PATTERN_GRID) return RTC_ERR_ARG;
-        if (shapes[i].material.pattern_kind == RTC_PATTERN_NONE && !shapes[i].material.has_color) return RTC_ERR_NO_COLOR;
-    }
+    const rtc_status cs = check_shapes(shapes, n);
+    if (cs != RTC_OK) return cs;
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t na = n ? n : 1;
     std::vector<DevIsect> isect(na);
     std::vector<uint32_t> kind(na, 0);
     std::vector<DevShade> shade(na);
     std::vector<DevBound> bound(na);
-    std::memset(isect.data(), 0, sizeof(DevIsect) * na);
-    std::memset(shade.data(), 0, sizeof(DevShade) * na);
-    bool any_refl = false, any_refr = false;
-    // World::add_shape numbers the shapes last_world_id + 1 (shape.rs:661-667). A caller that leaves every id
-    // 0 (rtc_shape_init does) gets exactly that numbering; ids that were given are honoured as they are —
-    // equal ids are ONE container to compute_refractive (shape.rs:127), which is also what the reference's
-    // own u8 ids do beyond 255 shapes.
-    bool all_zero = true;
-    for (uint32_t i = 0; i < n; ++i) all_zero = all_zero && shapes[i].world_id == 0u;
     std::vector<DevIdEntry> idtab(na, DevIdEntry{0u, 0u});
-    for (uint32_t i = 0; i < n; ++i) idtab[i] = DevIdEntry{i, all_zero ? i + 1u : shapes[i].world_id};
-    std::stable_sort(idtab.begin(), idtab.begin() + n, [](const DevIdEntry &a, const DevIdEntry &b) { return a.id < b.id; });
-    for (uint32_t i = 0; i < n; ++i) {
-        const rtc_shape &s = shapes[i];
-        const rtc_material &m = s.material;
-        std::memcpy(isect[i].m, s.inv, sizeof(double) * 12);
-        kind[i] = s.kind;
-        DevShade &d = shade[i];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c)
-                // Shape::normal_at uses transform_transpose (shape.rs:38); Cube::normal_at
-                // transposes its inverse on the fly (shape.rs:627)
-                d.nt[r * 3 + c] = (s.kind == RTC_CUBE) ? s.inv[c * 4 + r] : s.inv_t[r * 4 + c];
-        for (int c = 0; c < 3; ++c) {
-            d.color[c] = m.color[c];
-            d.pat_a[c] = m.pat_a[c];
-            d.pat_b[c] = m.pat_b[c];
-        }
-        d.ambient = m.ambient;
-        d.diffuse = m.diffuse;
-        d.specular = m.specular;
-        d.shininess = m.shininess;
-        d.reflective = m.reflective;
-        d.transparency = m.transparency;
-        d.refractive_index = m.refractive_index;
-        std::memcpy(d.pat_inv, m.pat_inv, sizeof(double) * 12);
-        if (s.kind == RTC_PLANE) {
-            // world_normal = local_normal.transform(inverse_transpose).normalize() with local_normal
-            // (0,1,0) (shape.rs:37-39, 481-483; transform.rs:114-117; vec.rs:65-76): mul/add/sqrt/div
-            // in the reference's order, correctly rounded on the host exactly as on the device
-            // (this file is compiled with -ffp-contract=off)
-            const double *t = d.nt;
-            const double wx = t[0] * 0. + t[1] * 1. + t[2] * 0.;
-            const double wy = t[3] * 0. + t[4] * 1. + t[5] * 0.;
-            const double wz = t[6] * 0. + t[7] * 1. + t[8] * 0.;
-            const double mag = std::sqrt(wx * wx + wy * wy + wz * wz);
-            d.plane_n[0] = wx / mag;
-            d.plane_n[1] = wy / mag;
-            d.plane_n[2] = wz / mag;
-        }
-        d.kind = s.kind;
-        d.pattern_kind = m.pattern_kind;
-        d.world_id = all_zero ? i + 1u : s.world_id;
-        if (m.reflective > 0.) any_refl = true;     // reflected_color shape.rs:730
-        if (m.transparency != 0.0) any_refr = true; // refracted_color shape.rs:752
-        bound[i] = bound_of(s);
-    }
+    bool any_refl = false, any_refr = false;
+    flatten_shapes(shapes, n, isect.data(), kind.data(), shade.data(), idtab.data(), &any_refl, &any_refr);
+    for (uint32_t i = 0; i < n; ++i) bound[i] = bound_of(shapes[i]);
     // ---- two-level cull tables: unbounded objects first, the rest in Morton order of their centres;
     // groups of 64 consecutive entries get a sphere around their members (inf if any is unbounded)
     std::vector<uint32_t> order(na, 0);
@@ -568,35 +688,37 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
     w->ctx = ctx;
     static std::atomic<uint64_t> uploads{0};
     w->serial = ++uploads;
-    w->pre_limit = std::isfinite(pre_limit) ? pre_limit : 0.;
-    w->ngroups = ngroups;
     w->device = ctx->device;
-    w->n = n;
-    w->light = *light;
-    w->any_refl = any_refl;
-    w->any_refr = any_refr;
+    rtc_world::Gen &G = w->gen[0]; // the host build fills generation 0; the others wait for updates
+    G.pre_limit = std::isfinite(pre_limit) ? pre_limit : 0.;
+    G.ngroups = ngroups;
+    G.n = n;
+    G.light = *light;
+    G.any_refl = any_refl;
+    G.any_refr = any_refr;
     for (uint32_t i = 0; i < n; ++i)
-        if (!std::isfinite(bound_s[i].r)) w->n_unb = i + 1u; // unbounded objects sort first (key 0)
-    rtc_status st = RTC_OK;
-    auto upload = [&st](auto &buf, const auto &host) { if (st == RTC_OK) st = buf.upload(host.data(), host.size()); };
-    upload(w->d_isect, isect);
-    upload(w->d_kind, kind);
-    upload(w->d_shade, shade);
-    upload(w->d_bound, bound);
-    upload(w->d_isect_s, isect_s);
-    upload(w->d_kind_s, kind_s);
-    upload(w->d_bound_s, bound_s);
-    upload(w->d_orig_s, orig_s);
-    upload(w->d_gbound, gbound);
-    upload(w->d_idtab, idtab);
-    upload(w->d_pre, pre);
-    upload(w->d_pre_s, pre_s);
-    if (st == RTC_OK) st = w->d_prim.reserve(na);
-    if (st == RTC_OK) st = rtc_status_of(hipMemset(w->d_prim.get(), 0, sizeof(DevPrim) * na));
+        if (!std::isfinite(bound_s[i].r)) G.n_unb = i + 1u; // unbounded objects sort first (key 0)
+    rtc_status st = reserve_generations(w, n, light_cap_for(n));
+    if (st == RTC_OK) carve_gen(G, n, nullptr);
+    auto upload = [&st](auto *dst, const auto &host) {
+        if (st == RTC_OK) st = rtc_status_of(hipMemcpy(dst, host.data(), host.size() * sizeof(*dst), hipMemcpyHostToDevice));
+    };
+    upload(G.isect, isect);
+    upload(G.kind, kind);
+    upload(G.shade, shade);
+    upload(G.bound, bound);
+    upload(G.isect_s, isect_s);
+    upload(G.kind_s, kind_s);
+    upload(G.bound_s, bound_s);
+    upload(G.orig_s, orig_s);
+    upload(G.gbound, gbound);
+    upload(G.idtab, idtab);
+    upload(G.pre, pre);
+    upload(G.pre_s, pre_s);
     // light-space shadow lists: every shadow segment ends at the light, so the objects a segment can meet
     // are listed per direction cell of a cube map around the light, once per World. Reach = twice the far side of the
     // farthest bounded object as seen from the light (longer segments fall back to the group walk).
-    if (st == RTC_OK && n >= 32) { // (a handful of objects: one cull step is cheaper than finding the cells — Criterion scene 33.5 vs 37.8 us)
+    if (st == RTC_OK && w->light_cap_alloc) { // (a handful of objects, n < 32: one cull step is cheaper than finding the cells — Criterion scene 33.5 vs 37.8 us)
         double far = 0.;
         for (uint32_t i = 0; i < n; ++i)
             if (std::isfinite(bound[i].r)) {
@@ -606,24 +728,13 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
         const double reach = 2. * far;
         if (std::isfinite(reach) && reach > 0. && reach < 1e30 && std::isfinite(light->position[0]) && std::isfinite(light->position[1]) &&
             std::isfinite(light->position[2])) {
-            const uint32_t cap = n > 256 ? RTC_LIGHT_LIST_CAP : RTC_LIGHT_LIST_CAP_SMALL;
-            w->light_cap = cap;
-            const size_t cells = 6u * (size_t)RTC_LIGHT_R * RTC_LIGHT_R, macros = 6u * (size_t)(RTC_LIGHT_R / 8u) * (RTC_LIGHT_R / 8u);
-            // the lists are an optimisation (the shadow pass walks without them): a failed allocation must not fail the upload
-            const bool got = w->d_light_cells.reserve(cells + macros) == RTC_OK && w->d_light_cnt.reserve(cells) == RTC_OK &&
-                             w->d_light_list.reserve(cells * cap) == RTC_OK;
-            if (got) {
-                DevTileBundle *cell = w->d_light_cells.get();
-                st = rtc_status_of(rtc_launch_light_lists(n, cap, w->d_bound.get(), light->position, reach, cell, cell + cells,
-                                                          w->d_light_cnt.get(), w->d_light_list.get(), ctx->stream));
-                if (st == RTC_OK) st = rtc_status_of(hipStreamSynchronize(ctx->stream));
-                w->light_reach = reach;
-            } else {
-                w->d_light_cells.reset();
-                w->d_light_cnt.reset();
-                w->d_light_list.reset();
-                w->light_cap = 0;
-            }
+            G.light_cap = light_cap_for(n);
+            DevTileBundle *cell = w->d_light_cells.get();
+            st = rtc_status_of(rtc_launch_light_lists(n, G.light_cap, G.bound, light->position, reach, cell, cell + LIGHT_CELLS, G.lights,
+                                                      G.lights + LIGHT_CELLS, ctx->stream));
+            if (st == RTC_OK) st = rtc_status_of(hipStreamSynchronize(ctx->stream));
+            G.light_reach = reach;
+            w->light_cells_ready = true;
         }
     }
     if (st != RTC_OK) {
@@ -632,6 +743,122 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
         return st;
     }
     *out = w;
+    return RTC_OK;
+}
+
+// The streams, events and page-locked memory updates need: the first update makes them, a growing one the memory again.
+static rtc_status ready_update(rtc_world *w) {
+    if (!w->build_stream) HIP_TRY(hipStreamCreateWithFlags(&w->build_stream, hipStreamNonBlocking));
+    for (rtc_world::Gen &G : w->gen) {
+        if (!G.built) HIP_TRY(hipEventCreateWithFlags(&G.built, hipEventDisableTiming));
+        for (hipEvent_t &e : G.read)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    rtc_world::Gen sizing;
+    size_t staged = 0;
+    carve_gen(sizing, w->cap_n, &staged);
+    const size_t slot = staged + 256u; // + the header
+    if (w->pinned && w->gen[1].stage == w->pinned + slot) return RTC_OK; // laid out for this capacity already
+    if (w->pinned) (void)hipHostFree(w->pinned);
+    w->pinned = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&w->pinned), slot * rtc_world::GENS, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return RTC_ERR_NOMEM;
+    }
+    for (uint32_t g = 0; g < rtc_world::GENS; ++g) {
+        w->gen[g].stage = w->pinned + slot * g;
+        w->gen[g].h_hdr = reinterpret_cast<DevWorldHeader *>(w->gen[g].stage + staged);
+    }
+    return RTC_OK;
+}
+
+// Replaces the contents of a resident World, ordered like a launch. The host flattens the shapes into the page-locked
+// stage of the next generation of the ring; the copy and the build kernels (rtc_world_build.h, then the light lists) go
+// to the World's build stream, behind the read events of the launches that last used that generation — a wait on the
+// stream, never on the host — and run beside the renders in flight, which read other generations. Launches made after
+// the call are given the new generation and wait, on their stream, for its `built` event.
+//
+// k_trace and k_bin_tiles take n_unb, pre_limit and light_reach by argument, and only the build knows them: the first
+// render launch after an update therefore waits ON THE HOST for the generation's header, which is copied into a pinned
+// 32-byte slot right behind the build (current_gen). That wait is for the small build kernels alone, which run beside
+// the previous frame's render; it never waits for a render kernel.
+//
+// No hipMalloc, hipFree or hipDeviceSynchronize while the World's capacity suffices: n <= the largest count it has held,
+// and light lists no larger than it has (the n >= 32 / n > 256 rules). Otherwise the slow path: wait for everything the
+// context has in flight, grow every generation, go on as above; a World whose growing fails (RTC_ERR_NOMEM) has lost its
+// contents: until an update succeeds every render of it returns RTC_ERR_NOMEM (rtc_world::valid). (The first update also creates the build stream, the events and the
+// page-locked block.)
+rtc_status rtc_world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n, const rtc_light *light) {
+    if (!ctx || !w || !light || (n && !shapes) || w->ctx != ctx) return RTC_ERR_ARG;
+    const rtc_status cs = check_shapes(shapes, n);
+    if (cs != RTC_OK) return cs;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t light_cap = light_cap_for(n);
+    if (n > w->cap_n || light_cap > w->light_cap_alloc) { // (a World that could not get its lists tries again each time it is updated)
+        HIP_TRY(drain_lanes(ctx));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->side_stream) HIP_TRY(hipStreamSynchronize(ctx->side_stream));
+        if (w->build_stream) HIP_TRY(hipStreamSynchronize(w->build_stream));
+        w->valid = false; // the slabs are freed and allocated again: until this call has succeeded the World has no contents
+        const rtc_status rs = reserve_generations(w, std::max(n, w->cap_n), std::max(light_cap, w->light_cap_alloc));
+        if (rs != RTC_OK) return rs;
+        for (rtc_world::Gen &G : w->gen) G.read_mask = 0; // nothing is in flight any more
+    }
+    const rtc_status us = ready_update(w);
+    if (us != RTC_OK) return us;
+    hipStream_t bs = w->build_stream;
+    if (!w->updated) { // launches so far recorded nothing: one event per stream stands for all of them
+        rtc_world::Gen &C = w->gen[w->cur];
+        for (uint32_t l = 0; l < rtc_context::MAX_LANES; ++l)
+            if (ctx->lane[l]) { HIP_TRY(hipEventRecord(C.read[l], ctx->lane[l])); C.read_mask |= 1u << l; }
+        HIP_TRY(hipEventRecord(C.read[BIT_STREAM], ctx->stream));
+        C.read_mask |= 1u << BIT_STREAM;
+        w->updated = true;
+    }
+    const uint32_t g = (w->cur + 1u) % rtc_world::GENS;
+    rtc_world::Gen &G = w->gen[g];
+    if (G.device_built) HIP_TRY(hipEventSynchronize(G.built)); // its stage may still be the source of the copy of GENS updates ago
+    for (uint32_t b = 0; b <= rtc_context::MAX_LANES; ++b)
+        if (G.read_mask & (1u << b)) HIP_TRY(hipStreamWaitEvent(bs, G.read[b], 0));
+    G.read_mask = 0;
+    size_t staged = 0;
+    carve_gen(G, n, &staged);
+    unsigned char *const base = G.slab;
+    auto staged_at = [&](auto *p) { return reinterpret_cast<decltype(p)>(G.stage + (reinterpret_cast<unsigned char *>(p) - base)); };
+    flatten_shapes(shapes, n, staged_at(G.isect), staged_at(G.kind), staged_at(G.shade), staged_at(G.idtab), &G.any_refl, &G.any_refr);
+    G.n = n;
+    G.ngroups = (n + 63u) / 64u;
+    G.light = *light;
+    G.light_cap = 0;
+    G.light_cap_want = light_cap;
+    HIP_TRY(hipMemcpyAsync(base, G.stage, staged, hipMemcpyHostToDevice, bs));
+    WorldBuildArgs a{};
+    a.n = n;
+    a.npad = rtc_world_build_npad(n);
+    a.light_on = light_cap && w->light_cap_alloc && std::isfinite(light->position[0]) && std::isfinite(light->position[1]) &&
+                 std::isfinite(light->position[2]);
+    for (int i = 0; i < 3; ++i) a.light[i] = light->position[i];
+    a.isect = G.isect; a.kind = G.kind; a.bound = G.bound; a.isect_s = G.isect_s; a.kind_s = G.kind_s; a.bound_s = G.bound_s;
+    a.orig_s = G.orig_s; a.gbound = G.gbound; a.pre = G.pre; a.pre_s = G.pre_s; a.hdr = G.d_hdr; a.partial = G.partial;
+    a.key = G.key; a.idx = G.idx;
+    HIP_TRY(rtc_launch_world_build(&a, bs));
+    if (a.light_on) {
+        DevTileBundle *cell = w->d_light_cells.get();
+        if (!w->light_cells_ready) { // no generation has had lists yet: nothing reads the cone tables
+            HIP_TRY(rtc_launch_light_lists(0u, light_cap, G.bound, light->position, 0., cell, cell + LIGHT_CELLS, G.lights,
+                                           G.lights + LIGHT_CELLS, bs));
+            w->light_cells_ready = true;
+        }
+        HIP_TRY(rtc_launch_light_lists_built(n, light_cap, G.bound, light->position, G.d_hdr, cell, cell + LIGHT_CELLS, G.lights,
+                                             G.lights + LIGHT_CELLS, bs));
+    }
+    HIP_TRY(hipMemcpyAsync(G.h_hdr, G.d_hdr, sizeof(DevWorldHeader), hipMemcpyDeviceToHost, bs));
+    HIP_TRY(hipEventRecord(G.built, bs));
+    G.hdr_pending = true;
+    G.device_built = true;
+    G.ordered = 0;
+    w->cur = g;
+    w->valid = true;
     return RTC_OK;
 }
 
@@ -645,6 +872,13 @@ void rtc_world_destroy(rtc_world *w) {
         if (b.binned) (void)hipEventDestroy(b.binned);
         if (b.traced) (void)hipEventDestroy(b.traced);
     }
+    for (rtc_world::Gen &G : w->gen) {
+        if (G.built) (void)hipEventDestroy(G.built);
+        for (hipEvent_t e : G.read)
+            if (e) (void)hipEventDestroy(e);
+    }
+    if (w->build_stream) (void)hipStreamDestroy(w->build_stream);
+    if (w->pinned) (void)hipHostFree(w->pinned);
     delete w; // its device buffers too, the device current and idle
 }
 
@@ -673,13 +907,13 @@ static bool ready_binset(rtc_context *ctx, rtc_world::BinSet &S, size_t tiles, s
 
 // k_bin_tiles of the launch's views into set B on `stream` (timed by the event pair `ev`, if any), and the render
 // parameters that read the set.
-static hipError_t bin_tiles(RenderParams &P, const rtc_world *w, const rtc_world::BinSet &B, bool sky_rows, hipStream_t stream,
+static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_world::BinSet &B, bool sky_rows, hipStream_t stream,
                             const hipEvent_t *ev) {
     uint32_t *cnt = B.tile_cnt.get() + RTC_BIN_ROW_WORDS;
-    const hipError_t e = rtc_launch_binning(P.views, P.nviews, P.W, P.H, w->n, w->d_bound_s.get(), w->d_gbound.get(), w->d_orig_s.get(),
-                                            w->ngroups, cnt, B.tile_list.get(), P.y0 / 8u, P.band_stride, stream, ev ? ev[0] : nullptr,
-                                            ev ? ev[1] : nullptr, w->d_isect_s.get(), w->d_kind_s.get(), w->n_unb, B.tile_cnt.get(),
-                                            w->d_isect.get(), B.prim.get());
+    const hipError_t e = rtc_launch_binning(P.views, P.nviews, P.W, P.H, G.n, G.bound_s, G.gbound, G.orig_s,
+                                            G.ngroups, cnt, B.tile_list.get(), P.y0 / 8u, P.band_stride, stream, ev ? ev[0] : nullptr,
+                                            ev ? ev[1] : nullptr, G.isect_s, G.kind_s, G.n_unb, B.tile_cnt.get(),
+                                            G.isect, B.prim.get());
     if (e != hipSuccess) return e;
     P.prim = B.prim.get();
     P.tile_rows = sky_rows ? B.tile_cnt.get() : nullptr;
@@ -687,8 +921,8 @@ static hipError_t bin_tiles(RenderParams &P, const rtc_world *w, const rtc_world
     P.tile_list = B.tile_list.get();
     P.tiles_x = (P.W + 7u) / 8u;
     P.tiles_y = (P.H + 7u) / 8u;
-    P.bin_packed = RTC_BIN_PACKED(w->n) ? 1u : 0u;
-    P.n_unb = w->n_unb;
+    P.bin_packed = RTC_BIN_PACKED(G.n) ? 1u : 0u;
+    P.n_unb = G.n_unb;
     return hipSuccess;
 }
 
@@ -698,9 +932,14 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
                                 uint32_t y1, uint32_t band_stride, uint32_t grid_y, void *d_rgb, void *d_rgb8,
                                 uint32_t flags, uint32_t nviews = 1, uint32_t view_rows = 0, float gamma = 0.f) {
     HIP_TRY(hipSetDevice(ctx->device));
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status hs = current_gen(w, &gen);
+    if (hs != RTC_OK) return hs;
+    rtc_world::Gen &G = *gen;
     RenderParams P;
     std::memset(&P, 0, sizeof P);
-    fill_world(P, w);
+    fill_world(P, G);
+    P.prim = w->d_prim.get();
     if (!ctx->light_lists) P.light_cnt = nullptr;
     for (uint32_t v = 0; v < nviews; ++v) fill_camera(P, cam + v, v);
     P.nviews = nviews;
@@ -715,10 +954,10 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     P.remaining = RTC_MAX_REFLECTIONS; // render_pixel passes Camera::MAX_REFLECTIONS camera.rs:98
     int src;
     size_t lds_bytes;
-    choose_source(ctx, w->n, flags, &src, &P.tile_cap, &lds_bytes);
+    choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes);
     const int cull = CULL_LEVEL(src);
-    const bool refl = w->any_refl || w->any_refr;
-    const uint32_t block = RTC_BLOCK_FOR(cull, refl, w->any_refr, false), tile_w = RTC_TILE_W_FOR(cull, refl, w->any_refr, false);
+    const bool refl = G.any_refl || G.any_refr;
+    const uint32_t block = RTC_BLOCK_FOR(cull, refl, G.any_refr, false), tile_w = RTC_TILE_W_FOR(cull, refl, G.any_refr, false);
     P.grid_x = (cam->hsize + tile_w - 1u) / tile_w;
     P.grid_y = grid_y;
     P.band_stride = band_stride;
@@ -741,6 +980,8 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     const bool piped = ctx->lanes > 1;
     const uint32_t lane = piped ? ((src == SRC_CULL || src == SRC_CULL2) ? (uint32_t)(ctx->lane_next++ % ctx->lanes) : 0u) : 0u;
     hipStream_t stream = piped ? ctx->lane[lane] : ctx->stream;
+    const uint32_t stream_bit = piped ? lane : BIT_STREAM;
+    HIP_TRY(order_behind_build(G, stream, stream_bit));
     if (gamma > 0.f) { // the table goes to the device on this launch's own stream (or is waited for there once)
         const rtc_status gs = gamma_table(ctx, gamma, stream, piped ? lane : rtc_context::MAX_LANES, &P.gamma);
         if (gs != RTC_OK) return gs;
@@ -758,15 +999,15 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
                                                      : launch_pixels >= ctx->bin_small_pixels));
     rtc_world::BinSet *binset = nullptr;
     int bin_set = -1; // which of w->bin this launch's lists are in (rtc_debug_tile_counts)
-    bool bin_ok = bin_this && ctx->binning && (y0 % 8u) == 0u && w->n != 0u;
+    bool bin_ok = bin_this && ctx->binning && (y0 % 8u) == 0u && G.n != 0u;
     const uint32_t tiles_x = (cam->hsize + 7u) / 8u, tiles_y = (cam->vsize + 7u) / 8u;
     const size_t tiles = (size_t)tiles_x * tiles_y * nviews;
     if (bin_ok && piped) {
         // lane-local lists: the binning kernel precedes the render kernel on the lane's own stream and runs beside the other
         // lanes' render kernels — no events. Sized for the largest launch seen (grow-only; growing waits for the lane).
         rtc_world::BinSet &B = w->bin[lane];
-        bin_ok = ready_binset(ctx, B, tiles, tiles, (size_t)w->n * nviews, (size_t)w->n * nviews, true, stream);
-        if (bin_ok) HIP_TRY(bin_tiles(P, w, B, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
+        bin_ok = ready_binset(ctx, B, tiles, tiles, (size_t)G.n * nviews, (size_t)G.n * nviews, true, stream);
+        if (bin_ok) HIP_TRY(bin_tiles(P, G, B, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
         if (bin_ok) bin_set = (int)lane;
     } else if (bin_ok) {
         if (!ctx->side_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
@@ -784,7 +1025,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
                 HIP_TRY(hipEventCreateWithFlags(&S.binned, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&S.traced, hipEventDisableTiming));
             }
-            bin_ok = ready_binset(ctx, S, tiles, tiles_alloc, (size_t)w->n * nviews, (size_t)w->n * std::max(alloc_views, nviews), false, stream);
+            bin_ok = ready_binset(ctx, S, tiles, tiles_alloc, (size_t)G.n * nviews, (size_t)G.n * std::max(alloc_views, nviews), false, stream);
         }
     }
     if (bin_ok && !piped) {
@@ -794,14 +1035,15 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         // to the side stream: it runs beside the PREVIOUS launch's render kernel, which still reads the other set. It must
         // wait for the render kernel that last read THIS set (two launches ago); the render stream waits for the binning.
         HIP_TRY(hipStreamWaitEvent(ctx->side_stream, B.traced, 0)); // never recorded: no wait
-        HIP_TRY(bin_tiles(P, w, B, ctx->sky_rows, ctx->side_stream, timed ? pair_bin : nullptr));
+        HIP_TRY(order_behind_build(G, ctx->side_stream, BIT_SIDE));
+        HIP_TRY(bin_tiles(P, G, B, ctx->sky_rows, ctx->side_stream, timed ? pair_bin : nullptr));
         HIP_TRY(hipEventRecord(B.binned, ctx->side_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, B.binned, 0));
         binset = &B;
     }
     if (timed) ctx->bin_timed[slot] = P.tile_cnt != nullptr;
     // per-render prologue table of the brute-force variants (the culled kernels do not use it)
-    if (src != SRC_CULL && src != SRC_CULL2) HIP_TRY(rtc_launch_prep(w->d_isect.get(), w->d_prim.get(), w->n, P.views[0].vinv, stream));
+    if (src != SRC_CULL && src != SRC_CULL2) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
     P.total_blocks = P.grid_x * P.grid_y * nviews;
     P.reps = ctx->tiles_per_wg;
     // Guided chunks (RenderParams::chunk_wgs): with `slots` workgroups resident at once, the launch's last f x slots tiles go one
@@ -811,14 +1053,14 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     uint32_t grid_wgs = (P.total_blocks + P.reps - 1u) / P.reps;
     {
         static const uint32_t sizes[5] = {1u, 2u, 3u, 4u, 8u}; // chunk sizes from the END of the launch backwards
-        const uint32_t slots = ctx->tiles_slots ? ctx->tiles_slots : (1024u * ((w->any_refl || w->any_refr) ? 4u : 5u) / std::max(1u, block / 64u));
+        const uint32_t slots = ctx->tiles_slots ? ctx->tiles_slots : (1024u * ((G.any_refl || G.any_refr) ? 4u : 5u) / std::max(1u, block / 64u));
         const unsigned long long per_level = (unsigned long long)slots * ctx->tiles_guided_tenths / 10u;
         uint32_t nlevels = 1;
         while (nlevels < 5u && sizes[nlevels] <= ctx->tiles_kmax) ++nlevels;
         // Not for a large world on a small frame (C3: 10 000 spheres at 1080p): there the NEXT launch's binning kernel is as long
         // as this render kernel, and its few waves wait for slots that long-lived workgroups free late — the solo kernel gains
         // 6 %, the pipelined frame loses 9 % (profiles/r03_exp_tiles_per_workgroup.log).
-        const bool heavy_binning = w->n > 4096u && launch_pixels < 8000000ull;
+        const bool heavy_binning = G.n > 4096u && launch_pixels < 8000000ull;
         if (P.reps == 1u && per_level != 0u && nlevels > 1u && P.total_blocks >= 3u * slots && !heavy_binning) {
             unsigned long long rest = P.total_blocks, tiles[5] = {0, 0, 0, 0, 0};
             for (uint32_t l = 0; l < nlevels && rest; ++l) {
@@ -833,10 +1075,11 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
             grid_wgs = P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3] + (uint32_t)tiles[0];
         }
     }
-    HIP_TRY(rtc_launch_trace(&P, src, w->any_refl || w->any_refr, w->any_refr, grid_wgs, lds_bytes, stream,
+    HIP_TRY(rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, grid_wgs, lds_bytes, stream,
                              timed ? pair[0] : nullptr, timed ? pair[1] : nullptr));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
-    ctx->last = rtc_launch_info{(uint32_t)src, (w->any_refl || w->any_refr) ? 1u : 0u, w->any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
+    HIP_TRY(record_read(w, G, stream, stream_bit));
+    ctx->last = rtc_launch_info{(uint32_t)src, (G.any_refl || G.any_refr) ? 1u : 0u, G.any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
                                 P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], {0u, 0u}};
     ++ctx->launches_total;
     ctx->last_bin = rtc_context::LastBin{};
@@ -918,13 +1161,47 @@ extern "C" rtc_status rtc_debug_world_lists(const rtc_world *w, uint32_t info[4]
     if (!w || !info || !light_reach) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(w->device));
     HIP_TRY(hipDeviceSynchronize());
-    info[0] = w->n_unb; info[1] = w->ngroups; info[2] = w->d_light_cnt.get() ? w->light_cap : 0u; info[3] = w->n;
-    *light_reach = w->light_reach;
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status hs = current_gen(w, &gen);
+    if (hs != RTC_OK) return hs;
+    rtc_world::Gen &G = *gen;
+    info[0] = G.n_unb; info[1] = G.ngroups; info[2] = G.light_cap; info[3] = G.n;
+    *light_reach = G.light_reach;
     static_assert(sizeof(DevBound) == 6 * sizeof(double), "bounds are read back as six doubles per object");
-    if (cell_counts && w->d_light_cnt.get())
-        HIP_TRY(hipMemcpy(cell_counts, w->d_light_cnt.get(), sizeof(uint32_t) * 6u * RTC_LIGHT_R * RTC_LIGHT_R, hipMemcpyDeviceToHost));
-    if (bounds && w->n) HIP_TRY(hipMemcpy(bounds, w->d_bound.get(), sizeof(DevBound) * w->n, hipMemcpyDeviceToHost));
+    if (cell_counts && G.light_cap)
+        HIP_TRY(hipMemcpy(cell_counts, G.lights, sizeof(uint32_t) * 6u * RTC_LIGHT_R * RTC_LIGHT_R, hipMemcpyDeviceToHost));
+    if (bounds && G.n) HIP_TRY(hipMemcpy(bounds, G.bound, sizeof(DevBound) * G.n, hipMemcpyDeviceToHost));
     return RTC_OK;
+}
+
+// Diagnostic (not part of include/rtc.h): the tables and scalars of the World's current contents, however they were built.
+// info = {n, n_unb, ngroups, light_cap (0: no light lists), any_refl, any_refr}; scalars = {pre_limit, light_reach}; *allocs:
+// device allocations made for the World since it was created. Every table pointer is optional and receives max(n, 1) records
+// (gbound: max(ngroups, 1); light_cnt: 6 * RTC_LIGHT_R^2 counters and light_list light_cap entries per cell, both only when
+// light_cap != 0). Waits for the device first. Copies only.
+extern "C" rtc_status rtc_debug_world_tables(const rtc_world *w, uint32_t info[6], double scalars[2], unsigned long long *allocs, void *bound,
+                                             void *bound_s, uint32_t *orig_s, uint32_t *kind_s, void *isect_s, void *gbound, void *pre,
+                                             void *pre_s, void *idtab, uint32_t *light_cnt, uint32_t *light_list) {
+    if (!w || !info || !scalars || !allocs) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(w->device));
+    HIP_TRY(hipDeviceSynchronize());
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status hs = current_gen(w, &gen);
+    if (hs != RTC_OK) return hs;
+    rtc_world::Gen &G = *gen;
+    info[0] = G.n; info[1] = G.n_unb; info[2] = G.ngroups; info[3] = G.light_cap; info[4] = G.any_refl; info[5] = G.any_refr;
+    scalars[0] = G.pre_limit; scalars[1] = G.light_reach;
+    *allocs = w->allocs;
+    const size_t na = G.n ? G.n : 1u, ng = G.ngroups ? G.ngroups : 1u;
+    auto copy = [](void *dst, const void *src, size_t bytes) { return !dst || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    bool ok = copy(bound, G.bound, sizeof(DevBound) * na) && copy(bound_s, G.bound_s, sizeof(DevBound) * na) &&
+              copy(orig_s, G.orig_s, sizeof(uint32_t) * na) && copy(kind_s, G.kind_s, sizeof(uint32_t) * na) &&
+              copy(isect_s, G.isect_s, sizeof(DevIsect) * na) && copy(gbound, G.gbound, sizeof(DevBound) * ng) &&
+              copy(pre, G.pre, sizeof(DevPre) * na) && copy(pre_s, G.pre_s, sizeof(DevPre) * na) && copy(idtab, G.idtab, sizeof(DevIdEntry) * na);
+    if (G.light_cap)
+        ok = ok && copy(light_cnt, G.lights, sizeof(uint32_t) * LIGHT_CELLS) &&
+             copy(light_list, G.lights + LIGHT_CELLS, sizeof(uint32_t) * LIGHT_CELLS * G.light_cap);
+    return ok ? RTC_OK : RTC_ERR_DEVICE;
 }
 
 // Diagnostic (not part of include/rtc.h): the tile lists of the context's most recent render launch, which must have been a
@@ -1046,7 +1323,7 @@ static rtc_status render_views(rtc_context *ctx, const rtc_world *w, const rtc_c
     int src;
     uint32_t cap;
     size_t lds;
-    choose_source(ctx, w->n, flags, &src, &cap, &lds);
+    choose_source(ctx, w->gen[w->cur].n, flags, &src, &cap, &lds);
     if (src != SRC_CULL && src != SRC_CULL2) {
         // the brute-force variants keep a per-render table of the camera origin in object space: one view per launch
         for (uint32_t v = 0; v < nviews; ++v) {
@@ -1164,7 +1441,11 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
     HIP_TRY(hipSetDevice(ctx->device));
     DevBuf<double> d_rays, d_rgb;
     DevBuf<rtc_hit> d_hits;
-    rtc_status st = RTC_OK;
+    rtc_world::Gen *gen = nullptr;
+    rtc_status st = current_gen(w, &gen);
+    if (st != RTC_OK) return st;
+    rtc_world::Gen &G = *gen;
+    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
     if (d_rays.reserve((size_t)6 * n) != RTC_OK || d_rgb.reserve((size_t)3 * n) != RTC_OK || (hits && d_hits.reserve(n) != RTC_OK))
         st = RTC_ERR_DEVICE;
     if (st == RTC_OK && hipMemcpyAsync(d_rays.get(), rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
@@ -1172,7 +1453,8 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
     if (st == RTC_OK) {
         RenderParams P;
         std::memset(&P, 0, sizeof P);
-        fill_world(P, w);
+        fill_world(P, G);
+        P.prim = w->d_prim.get();
         if (!ctx->light_lists) P.light_cnt = nullptr;
         P.W = n; P.H = 1; P.y0 = 0; P.y1 = 1; P.mode = RTC_MODE_RENDER_ASYNC; P.samples = 1;
         P.out = d_rgb.get();
@@ -1183,8 +1465,8 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.hits = d_hits.get();
         int src;
         size_t lds_bytes;
-        choose_source(ctx, w->n, flags, &src, &P.tile_cap, &lds_bytes);
-        const uint32_t blk = RTC_BLOCK_FOR(CULL_LEVEL(src), w->any_refl || w->any_refr, w->any_refr, true);
+        choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes);
+        const uint32_t blk = RTC_BLOCK_FOR(CULL_LEVEL(src), G.any_refl || G.any_refr, G.any_refr, true);
         P.grid_x = (n + blk - 1u) / blk;
         P.grid_y = 1;
         P.band_stride = 1;
@@ -1192,7 +1474,7 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.total_blocks = P.grid_x;
         P.reps = 1;
         P.chunk_wgs[0] = P.chunk_wgs[1] = P.chunk_wgs[2] = P.chunk_wgs[3] = 0;
-        if (rtc_launch_trace(&P, src, w->any_refl || w->any_refr, w->any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
+        if (rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
                              nullptr) != hipSuccess)
             st = RTC_ERR_DEVICE;
     }

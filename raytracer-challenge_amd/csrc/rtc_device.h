@@ -1,7 +1,8 @@
 // rtc_device.h — layout of the flattened World in HBM and the kernel parameter block.
 // Shared by rtc_api.cpp (host side of the C-ABI) and rtc_kernels.hip.
 //
-// HBM layout (all f64, written once per rtc_world_create, read-only afterwards):
+// HBM layout (all f64, written once per rtc_world_create or rtc_world_update — a generation, rtc_internal.h — and read-only
+// until an update reuses the generation):
 //   isect[n]  96 B  rows 0..2 of the shape's stored inverse transform — everything
 //                   Shape::intersect needs (vec.rs:211-214, transform.rs:107-128);
 //                   read wave-uniformly through the scalar cache (or staged in LDS tiles).

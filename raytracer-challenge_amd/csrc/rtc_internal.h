@@ -11,6 +11,7 @@
 #include "rtc_devmem.h"
 #include "rtc_device.h"
 #include "rtc_gamma.h"
+#include "rtc_world_build.h"
 
 struct rtc_context {
     int device = -1;
@@ -58,6 +59,7 @@ struct rtc_context {
     } last_bin;
     hipEvent_t fence_ev = nullptr; // rtc_context_fence
     bool light_lists = true; // RTC_LIGHT_LISTS=0: shadow passes of two-level worlds walk the groups (A/B)
+    bool world_update = true; // RTC_WORLD_UPDATE=0: render_lua destroys and recreates the World when a job's differs (A/B)
     bool binning = true;  // RTC_BINNING=0: primary rays take the wave-level cull / group walk too (A/B)
     bool sky_rows = true; // RTC_SKY_ROWS=0: tile rows the binning kernel proved black are traced like any other (A/B)
     // one-level worlds (<= 256 objects) are binned only in launches of at least this many views (RTC_BIN_SMALL_VIEWS): the
@@ -92,20 +94,63 @@ struct rtc_world {
     rtc_context *ctx = nullptr; // identity check only; never dereferenced at destroy time
     int device = -1;
     uint64_t serial = 0; // 1, 2, ... in order of rtc_world_create, process-wide: never reused
-    uint32_t n = 0;
-    DevBuf<DevIsect> d_isect;
-    DevBuf<uint32_t> d_kind;
-    DevBuf<DevShade> d_shade;
-    DevBuf<DevPrim> d_prim;
-    DevBuf<DevBound> d_bound;
-    DevBuf<DevIsect> d_isect_s; // Morton-sorted copies for the two-level cull
-    DevBuf<uint32_t> d_kind_s;
-    DevBuf<DevBound> d_bound_s;
-    DevBuf<uint32_t> d_orig_s;
-    DevBuf<DevBound> d_gbound;
-    DevBuf<DevIdEntry> d_idtab;
-    DevBuf<DevPre> d_pre, d_pre_s; // per-lane prefilter records (insertion / sorted order)
-    double pre_limit = 0.;
+    // One generation of the World's contents: every table a launch is pointed at (fill_world) and the scalars that go with
+    // them. rtc_world_create fills generation 0 from its host build; rtc_world_update builds the next one of the ring on the
+    // device (rtc_world_build.h) while launches made earlier still read theirs. A generation is written again GENS updates
+    // later, behind the `read` events of the launches that used it.
+    struct Gen {
+        unsigned char *slab = nullptr; // its share of rtc_world::slabs: the tables below and the build's scratch, laid out by carve_gen (rtc_api.cpp)
+        uint32_t *lights = nullptr;    // its share of rtc_world::lights: the cells' counters, then light_cap_alloc entries per cell
+        DevIsect *isect = nullptr;
+        DevShade *shade = nullptr;
+        DevIdEntry *idtab = nullptr;
+        uint32_t *kind = nullptr; // isect .. kind: what the host flattens; the rest is derived from them
+        DevBound *bound = nullptr;
+        DevIsect *isect_s = nullptr; // Morton-sorted copies for the two-level cull
+        uint32_t *kind_s = nullptr;
+        DevBound *bound_s = nullptr;
+        uint32_t *orig_s = nullptr;
+        DevBound *gbound = nullptr;
+        DevPre *pre = nullptr, *pre_s = nullptr; // per-lane prefilter records (insertion / sorted order)
+        double *partial = nullptr;               // build scratch (WorldBuildArgs)
+        unsigned long long *key = nullptr;
+        uint32_t *idx = nullptr;
+        DevWorldHeader *d_hdr = nullptr;
+        uint32_t n = 0;
+        uint32_t ngroups = 0;
+        rtc_light light{};
+        bool any_refl = false, any_refr = false;
+        uint32_t light_cap = 0;  // entries per cell of this generation's lists; 0: it has none
+        // known to the host build at once; after a device build only once the header has arrived (hdr_pending)
+        uint32_t n_unb = 0; // unbounded objects: the first n_unb entries of the Morton-sorted tables
+        double pre_limit = 0.;
+        double light_reach = 0.;
+        // update bookkeeping
+        bool hdr_pending = false;    // the first launch waits for `built` on the host and reads *h_hdr
+        uint32_t light_cap_want = 0; // ... and light_cap becomes this if the header reports a reach
+        hipEvent_t built = nullptr;  // recorded on the build stream behind the header copy
+        bool device_built = false;   // written by an update (`built` has been recorded), not by rtc_world_create's host build
+        uint32_t ordered = 0;        // device_built: the streams that are ordered behind `built` already (bit: stream_bit, rtc_api.cpp)
+        hipEvent_t read[rtc_context::MAX_LANES + 1] = {}; // per render stream: behind its latest launch that used this generation
+        uint32_t read_mask = 0;                           // ... which of them have been recorded since the generation was built
+        unsigned char *stage = nullptr; // page-locked: the flattened shapes of the update that builds this generation
+        DevWorldHeader *h_hdr = nullptr; // page-locked: where the header lands
+    };
+    static constexpr uint32_t GENS = rtc_context::MAX_LANES + 1u; // as many as output slots can be in flight (the idea of BinSet)
+    mutable Gen gen[GENS]; // (rtc_render_* take the World as const)
+    // ONE allocation each for every generation's tables and for every generation's light lists: rtc_world_create pays for two
+    // hipMalloc calls however many generations there are (a World that is destroyed and created per frame must not pay per generation)
+    DevBuf<unsigned char> slabs;
+    DevBuf<uint32_t> lights;
+    uint32_t cur = 0;      // the generation launches made now are given
+    bool valid = true;     // false after a growing update that failed: gen[cur] points nowhere, renders are refused
+    uint32_t cap_n = 0;           // objects every generation has room for
+    uint32_t light_cap_alloc = 0; // entries per cell every generation's `lights` has room for (0: no lists)
+    unsigned long long allocs = 0; // hipMalloc calls made for this World so far (rtc_debug_world_tables)
+    mutable bool updated = false;   // since the first update every launch records a read event
+    hipStream_t build_stream = nullptr; // created by the first update: uploads and build kernels, beside the renders
+    unsigned char *pinned = nullptr;    // one page-locked block: every generation's stage and header slot
+    DevBuf<DevPrim> d_prim; // per-render scratch of the brute-force variants
     // binned primary pass: per-render scratch, grow-only, TWO sets — the binning of launch k+1 runs on the context's side
     // stream while launch k's render kernel still reads set k (rtc_render_* take the World as const: mutable)
     struct BinSet {
@@ -116,15 +161,8 @@ struct rtc_world {
     };
     mutable BinSet bin[rtc_context::MAX_LANES]; // in-order contexts alternate between [0] and [1]; a pipelined context's lane l owns [l]
     mutable uint32_t bin_next = 0;
-    // light-space shadow lists (two-level worlds), built once at rtc_world_create
-    DevBuf<DevTileBundle> d_light_cells;
-    DevBuf<uint32_t> d_light_cnt, d_light_list;
-    double light_reach = 0.;
-    uint32_t light_cap = 0;
-    uint32_t n_unb = 0;               // unbounded objects: the first n_unb entries of the Morton-sorted tables
-    uint32_t ngroups = 0;
-    rtc_light light{};
-    bool any_refl = false, any_refr = false;
+    DevBuf<DevTileBundle> d_light_cells; // the lists' cone tables: the same for every World, written once
+    bool light_cells_ready = false;
 };
 
 
@@ -136,6 +174,9 @@ extern "C" hipError_t rtc_launch_binning(const DevCamera *views, uint32_t nviews
 enum { RTC_BIN_ROW_WORDS = 2 * RTC_MAX_VIEWS }; // a BinSet's tile_cnt buffer starts with the views' row words (RenderParams::tile_rows)
 extern "C" hipError_t rtc_launch_light_lists(uint32_t n, uint32_t cap, const DevBound *bound, const double light[3], double reach, DevTileBundle *cells,
                                              DevTileBundle *macros, uint32_t *cnt, uint32_t *list, hipStream_t stream);
+extern "C" hipError_t rtc_launch_light_lists_built(uint32_t n, uint32_t cap, const DevBound *bound, const double light[3], const DevWorldHeader *hdr,
+                                                   const DevTileBundle *cells, const DevTileBundle *macros, uint32_t *cnt, uint32_t *list,
+                                                   hipStream_t stream);
 extern "C" rtc_status rtc_gamma_build_table(float gamma, DevGamma *g); // host_ppm.cpp
 extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
 extern "C" hipError_t rtc_launch_undeal(const void *staging, void *canvas, uint32_t nranks, uint32_t nframes, uint32_t H,

@@ -31,6 +31,7 @@
 #include "rtc_bands.h"
 #include "rtc_device.h"
 #include "rtc_gamma.h"
+#include "rtc_world_build.h"
 
 // Depth of the reflection / refraction frame stack. A frame is pushed only by a color_at call whose
 // `remaining` is not 0, and each level passes remaining - 1 on (shape.rs:730,735,752,765): a chain started with
@@ -2208,9 +2209,9 @@ DEVI Bundle light_bundle_of(const DevTileBundle &t, V3 apex, double reach) { // 
     return B;
 }
 // One wave per object: macro cells (8x8 cells) 64 per step, then the cells of the touched macro cells.
-__global__ void __launch_bounds__(64) k_light_bin(uint32_t n, uint32_t cap, const DevBound *__restrict__ bound, double lx, double ly, double lz, double reach,
-                                                   const DevTileBundle *__restrict__ cells, const DevTileBundle *__restrict__ macros,
-                                                   uint32_t *__restrict__ cnt, uint32_t *__restrict__ list) {
+DEVI void light_bin(uint32_t n, uint32_t cap, const DevBound *__restrict__ bound, double lx, double ly, double lz, double reach,
+                    const DevTileBundle *__restrict__ cells, const DevTileBundle *__restrict__ macros,
+                    uint32_t *__restrict__ cnt, uint32_t *__restrict__ list) {
     constexpr uint32_t R = RTC_LIGHT_R, M = RTC_LIGHT_R / 8u;
     const uint32_t j = blockIdx.x, lane = threadIdx.x;
     if (j >= n) return;
@@ -2234,6 +2235,18 @@ __global__ void __launch_bounds__(64) k_light_bin(uint32_t n, uint32_t cap, cons
         }
     }
 }
+__global__ void __launch_bounds__(64) k_light_bin(uint32_t n, uint32_t cap, const DevBound *__restrict__ bound, double lx, double ly, double lz, double reach,
+                                                   const DevTileBundle *__restrict__ cells, const DevTileBundle *__restrict__ macros,
+                                                   uint32_t *__restrict__ cnt, uint32_t *__restrict__ list) {
+    light_bin(n, cap, bound, lx, ly, lz, reach, cells, macros, cnt, list);
+}
+// The same for a World built on the device (rtc_world_build.h): the reach is in the build's header, 0 when the World gets no lists.
+__global__ void __launch_bounds__(64) k_light_bin_built(uint32_t n, uint32_t cap, const DevBound *__restrict__ bound, double lx, double ly, double lz,
+                                                         const DevWorldHeader *__restrict__ hdr, const DevTileBundle *__restrict__ cells,
+                                                         const DevTileBundle *__restrict__ macros, uint32_t *__restrict__ cnt, uint32_t *__restrict__ list) {
+    const double reach = hdr->light_reach;
+    if (reach > 0.) light_bin(n, cap, bound, lx, ly, lz, reach, cells, macros, cnt, list);
+}
 
 extern "C" hipError_t rtc_launch_light_lists(uint32_t n, uint32_t cap, const DevBound *bound, const double light[3], double reach, DevTileBundle *cells,
                                              DevTileBundle *macros, uint32_t *cnt, uint32_t *list, hipStream_t stream) {
@@ -2241,6 +2254,17 @@ extern "C" hipError_t rtc_launch_light_lists(uint32_t n, uint32_t cap, const Dev
     hipLaunchKernelGGL(k_light_cells, dim3((6u * R * R + 6u * M * M + 255u) / 256u), dim3(256), 0, stream, cells, macros, cnt);
     if (n) hipLaunchKernelGGL(k_light_bin, dim3(n), dim3(64), 0, stream, n, cap, bound, light[0], light[1], light[2], reach, (const DevTileBundle *)cells,
                               (const DevTileBundle *)macros, cnt, list);
+    return hipGetLastError();
+}
+
+// The lists of a World whose tables the device has just built on `stream`: clears the counters and bins with the header's
+// reach. `cells` and `macros` are the World's cone tables as rtc_launch_light_lists left them (they do not depend on the World).
+extern "C" hipError_t rtc_launch_light_lists_built(uint32_t n, uint32_t cap, const DevBound *bound, const double light[3], const DevWorldHeader *hdr,
+                                                   const DevTileBundle *cells, const DevTileBundle *macros, uint32_t *cnt, uint32_t *list,
+                                                   hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * 6u * RTC_LIGHT_R * RTC_LIGHT_R, stream);
+    if (e != hipSuccess) return e;
+    if (n) hipLaunchKernelGGL(k_light_bin_built, dim3(n), dim3(64), 0, stream, n, cap, bound, light[0], light[1], light[2], hdr, cells, macros, cnt, list);
     return hipGetLastError();
 }
 

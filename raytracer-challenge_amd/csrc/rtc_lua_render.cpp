@@ -182,11 +182,19 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
         Slot &sl = ring[i % RING];
         st = deliver(sl);
         if (st != RTC_OK || stop) break;
-        if (!world || !job.same_world_as_previous) { // a new World: nothing may still read the old one
+        if (!world) { // the program's first job
+            st = rtc_world_create(ctx, job.shapes, job.n_shapes, &job.light, &world);
+            if (st != RTC_OK) break;
+        } else if (!job.same_world_as_previous && ctx->world_update) {
+            // other contents for the resident World, ordered like a launch: the frames in flight keep theirs, and the
+            // outputs' ring is safe as it is (a slot is reused only after `depth` later launches)
+            st = rtc_world_update(ctx, world, job.shapes, job.n_shapes, &job.light);
+            if (st != RTC_OK) break;
+        } else if (!job.same_world_as_previous) { // RTC_WORLD_UPDATE=0, a new World: nothing may still read the old one
             st = drain(i);
             if (st == RTC_OK) st = rtc_context_synchronize(ctx);
             if (st != RTC_OK || stop) break;
-            if (world) rtc_world_destroy(world);
+            rtc_world_destroy(world);
             world = nullptr;
             st = rtc_world_create(ctx, job.shapes, job.n_shapes, &job.light, &world);
             if (st != RTC_OK) break;

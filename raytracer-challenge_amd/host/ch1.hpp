@@ -133,6 +133,14 @@ struct Shape {
     }
     Material &get_material_mut() { return material; }
     const Material &get_material() const { return material; }
+    // Sphere::set_transform (shape.rs:319-322). Plane's and Cube's transpose their OLD transpose instead of the new inverse
+    // (shape.rs:446-449, 535-538): kept.
+    void set_transform(const Matrix &m) {
+        check(rtc_matrix_inverse(m.m.data(), flat.inv), "Shape::set_transform");
+        double t[16];
+        rtc_matrix_transpose(flat.kind == RTC_SPHERE ? flat.inv : flat.inv_t, t);
+        std::memcpy(flat.inv_t, t, sizeof t);
+    }
 };
 struct Sphere {
     static Shape new_() { return Shape::make(RTC_SPHERE, Matrix::identity(), Material::default_()); }
@@ -328,14 +336,19 @@ class World { // shape.rs:633-795
             const bool same = w_ != nullptr && flat.size() == flat_.size() && std::memcmp(&l, &light_, sizeof l) == 0 &&
                               (flat.empty() || std::memcmp(flat.data(), flat_.data(), flat.size() * sizeof(rtc_shape)) == 0);
             if (!same) {
-                if (w_) rtc_world_destroy(w_);
-                w_ = nullptr;
-                check(rtc_world_create(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), &l, &w_), "World upload");
+                // other contents for the World that is resident already (rtc_world_update: no destroy, no allocation while
+                // it does not grow); a rejected update leaves it as it was, and so does this cache
+                if (w_) {
+                    const rtc_status st = rtc_world_update(Device::get(), w_, flat.data(), static_cast<uint32_t>(flat.size()), &l);
+                    if (st == RTC_ERR_NOMEM || st == RTC_ERR_DEVICE) flat_.clear(), light_ = rtc_light{}; // a failed growing update: nothing is resident
+                    check(st, "World update");
+                } else check(rtc_world_create(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), &l, &w_), "World upload");
                 flat_ = std::move(flat);
                 light_ = l;
             }
             return w_;
         }
+        rtc_world *resident() const { return w_; } // (tests: the handle stays the same across updates)
       private:
         Resident() { (void)Device::get(); } // the context outlives this cache (constructed first, destroyed last)
         ~Resident() { if (w_) rtc_world_destroy(w_); }

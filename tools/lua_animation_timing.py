@@ -1,5 +1,11 @@
 """Time lua.rs's render_lua on the GPU for the orbit script (rtc_lua_program_render: one launch per AddFrame, pipelined,
-frames copied to the host) against the same jobs rendered one by one through rtc_render_rgb8. python tools/lua_animation_timing.py"""
+frames copied to the host) against the same jobs rendered one by one through rtc_render_rgb8. python tools/lua_animation_timing.py
+
+python tools/lua_animation_timing.py moving [rounds]: the moving-world loops instead — bouncing_animation.lua (120 frames,
+1080p, every frame another world), the same script among 9 997 bystanders (10 001 shapes, two balls and the light moving)
+and with ONE moving sphere among them — under
+RTC_WORLD_UPDATE=0 (destroy and create per frame) and =1 (rtc_world_update), the two settings interleaved, and the orbit
+loop (one world) both ways as the control. Prints ms per delivered frame of every round and the medians."""
 import sys
 import time
 from pathlib import Path
@@ -11,6 +17,39 @@ from _bootstrap import package  # noqa: E402
 rtc = package()
 data = Path(rtc.__file__).resolve().parent / "data"
 rtc.LuaProgram(text="x = 1")   # (loads the library)
+
+
+def moving(rounds):
+    import os
+    import statistics
+    cases = (("bouncing 4 shapes", "bouncing_animation.lua", "FRAMES = 120 WIDTH, HEIGHT = 1920, 1080\n"),
+             ("bouncing 10001 shapes", "bouncing_animation.lua", "FRAMES = 120 BALLS = 9997 WIDTH, HEIGHT = 1920, 1080\n"),
+             ("one moving sphere of 10001 shapes", "bouncing_animation.lua", "FRAMES = 120 BALLS = 9997 ONLY_RED = true WIDTH, HEIGHT = 1920, 1080\n"),
+             ("orbit 102 shapes (one world)", "orbit_animation.lua", "FRAMES = 120 BALLS = 100 WIDTH, HEIGHT = 1920, 1080\n"))
+    for name, script, head in cases:
+        prog = rtc.LuaProgram(text=head + (data / script).read_text(), base_dir=data)
+        ctxs = {}
+        for setting in ("0", "1"):
+            os.environ["RTC_WORLD_UPDATE"] = setting
+            ctxs[setting] = rtc.Context(0)
+            prog.render(ctxs[setting], on_frame=lambda *a: None)     # warm
+        del os.environ["RTC_WORLD_UPDATE"]
+        ms = {"0": [], "1": []}
+        for _ in range(rounds):
+            for setting in ("0", "1"):   # interleaved
+                t = time.perf_counter()
+                prog.render(ctxs[setting], on_frame=lambda *a: None)
+                ms[setting].append((time.perf_counter() - t) / len(prog) * 1e3)
+        m0, m1 = statistics.median(ms["0"]), statistics.median(ms["1"])
+        print(f"{name}, {len(prog)} jobs, 1920x1080 rgb8 delivered, ms per frame: RTC_WORLD_UPDATE=0 {' '.join('%.3f' % v for v in ms['0'])} (median {m0:.3f}); "
+              f"=1 {' '.join('%.3f' % v for v in ms['1'])} (median {m1:.3f}); ratio =0/=1 {m0 / m1:.2f}", flush=True)
+        for c in ctxs.values():
+            c.close()
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "moving":
+    moving(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
+    sys.exit(0)
 for frames, balls, w, h in ((120, 100, 1920, 1080), (120, 24, 600, 400)):
     text = f"FRAMES = {frames} BALLS = {balls} WIDTH, HEIGHT = {w}, {h}\n" + (data / "orbit_animation.lua").read_text()
     t = time.perf_counter()
