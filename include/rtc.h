@@ -247,7 +247,7 @@ void        rtc_light_default(rtc_light *out);
  * applies transform lists in listed order (transform.rs:53-69 left-multiplication), starts
  * materials from Material::default() (lua.rs:187) and assigns world ids like
  * World::add_shape. On success *shapes_out is a malloc'ed array the caller releases with
- * rtc_free. Only the first light is used (lua.rs:148-150). */
+ * rtc_free. Returns the first light (lua.rs:148-150); rtc_scene_load_yaml_lights returns all of them. */
 rtc_status  rtc_scene_load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
                                 rtc_light *light_out, rtc_camera *camera_out,
                                 char *errbuf, size_t errbuf_len);
@@ -264,7 +264,8 @@ rtc_status  rtc_scene_load_yaml_file(const char *path, rtc_shape **shapes_out, u
  * Every Render / AddFrame call converts its tables AT THE CALL by lua.rs's own rules — transform_from_table's fixed order
  * rotate_x, rotate_y, rotate_z, scale, position; materials from Material::default() with the keys ambient, diffuse,
  * specular, shininess, reflectiveness, transparency, refractive_index, color, pattern (anything else is an error) and the
- * shape-level color / pattern override; patterns "checks" / "stripes" / "grid"; lights[1] only; camera screenwidth /
+ * shape-level color / pattern override; patterns "checks" / "stripes" / "grid"; every light of world.lights (the job's
+ * `light` field is lights[1], rtc_lua_program_job_lights hands out all); camera screenwidth /
  * screenheight / samples as Lua integers — and becomes one JOB: a world, a camera, the output file's name. The caller renders
  * the jobs in order (one rtc_render* launch each: an AddFrame loop is the one-camera-per-launch sequence a pipelined
  * context overlaps). The library writes PNG / PPM stills (rtc_canvas_write_png8, rtc_canvas_write_ppm_rgb8) and the
@@ -288,7 +289,7 @@ typedef struct rtc_lua_job {
     const char      *outfile;         /* Render's third argument / the animation's file name; owned by the program     */
     uint32_t         animation;       /* AddFrame: which StartAnimation call (0, 1, ...) the encoder came from         */
     uint32_t         frame;           /* AddFrame: index of the frame inside that animation                            */
-    uint32_t         same_world_as_previous; /* 1: shapes and light equal the previous job's byte for byte (same arrays) */
+    uint32_t         same_world_as_previous; /* 1: shapes and ALL lights equal the previous job's byte for byte (same arrays) */
     uint32_t         line;            /* script line of the call                                                      */
 } rtc_lua_job;
 rtc_status  rtc_lua_run(const char *text, const char *base_dir, uint64_t step_limit, rtc_lua_program **out,
@@ -307,6 +308,27 @@ rtc_status  rtc_scene_load_lua(const char *text, uint32_t render_index, rtc_shap
 rtc_status  rtc_scene_load_lua_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
                                     rtc_light *light_out, rtc_camera *camera_out, char *outfile, size_t outfile_len,
                                     uint32_t *renders_out, char *errbuf, size_t errbuf_len);
+/* All lights of a scene. The _lights forms of the loaders return every `add: light` entry (YAML, file order) / every
+ * element of world.lights (Lua, index order) in lights_out[0..*n_lights_out); the forms above keep returning the first.
+ * `lights_cap` is the room in lights_out: a scene with more lights than that is RTC_ERR_ARG, one with more than
+ * RTC_MAX_LIGHTS is RTC_ERR_PARSE with a message, whichever entry loads it. */
+rtc_status  rtc_scene_load_yaml_lights(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                       rtc_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                       rtc_camera *camera_out, char *errbuf, size_t errbuf_len);
+rtc_status  rtc_scene_load_yaml_lights_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                            rtc_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                            rtc_camera *camera_out, char *errbuf, size_t errbuf_len);
+rtc_status  rtc_scene_load_lua_lights(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                                      rtc_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                      rtc_camera *camera_out, char *outfile, size_t outfile_len,
+                                      uint32_t *renders_out, char *errbuf, size_t errbuf_len);
+rtc_status  rtc_scene_load_lua_lights_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                                           rtc_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                           rtc_camera *camera_out, char *outfile, size_t outfile_len,
+                                           uint32_t *renders_out, char *errbuf, size_t errbuf_len);
+/* Every light of job `index` (rtc_lua_job::light is lights_out[0]). RTC_ERR_ARG when cap is too small. */
+rtc_status  rtc_lua_program_job_lights(const rtc_lua_program *prog, uint32_t index, rtc_light *lights_out, uint32_t cap,
+                                       uint32_t *n_out);
 void        rtc_free(void *p);
 
 /* Canvas::write_to_file_simple: ASCII PPM P3 (canvas.rs:86-109) with Color::scale's
@@ -555,6 +577,29 @@ rtc_status  rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t
 rtc_status  rtc_world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes,
                              uint32_t n_shapes, const rtc_light *light);
 void        rtc_world_destroy(rtc_world *w);
+
+/* Worlds with several lights. The reference's World holds a list of lights, and its shade_hit uses the first and marks
+ * the rest `FIXME -- multiple lights` (shape.rs:642-650, 686). Here a World of lights L[0..n), 1 <= n <= RTC_MAX_LIGHTS,
+ * shades with
+ *     surface = lighting(L[0], .., is_shadowed_by_light(over_point, L[0]))
+ *     for i in 1..n:  surface = surface + lighting(L[i], .., is_shadowed_by_light(over_point, L[i]))    (shape.rs:716)
+ * added in f64 in light order; every term carries its own ambient part (the book's multi-light form). Everything after
+ * `surface` (reflected_color, refracted_color, the Schlick branch) is as for one light, and n == 1 IS the one-light
+ * arithmetic, kernels included: rtc_world_create / rtc_world_update are these calls with n_lights == 1.
+ * rtc_stats::rays_shadow counts one ray per light per shade_hit; rtc_hit::shadowed stays L[0]'s. Every render entry
+ * takes such a World unchanged (rtc_render*, the rgb8 / rgba8 forms, rtc_render_views*, rtc_color_at, the encoders'
+ * _render entries, RTC_FLAG_NO_CULL included, culled and brute-force frames bit-identical). Only L[0] has light-space
+ * shadow lists; the further lights' shadow passes take the bundle cull. With n_lights > 1 the measurement-only
+ * RTC_FLAG_LDS_TABLE path (and an RTC_SRC override naming an LDS source) is RTC_ERR_UNSUPPORTED. rtc_group_world_*
+ * stays single-light. n_lights == 0, n_lights > RTC_MAX_LIGHTS or lights == NULL: RTC_ERR_ARG.
+ * rtc_world_update_lights has rtc_world_update's ordering and no-allocation promises; n_lights may change between
+ * updates. */
+#define RTC_MAX_LIGHTS 8u
+rtc_status  rtc_world_create_lights(rtc_context *ctx, const rtc_shape *shapes, uint32_t n_shapes,
+                                    const rtc_light *lights, uint32_t n_lights, rtc_world **out);
+rtc_status  rtc_world_update_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n_shapes,
+                                    const rtc_light *lights, uint32_t n_lights);
+uint32_t    rtc_world_light_count(const rtc_world *w); /* 0 for NULL */
 
 /* Camera::render / render_async for canvas rows [y0, y1) into a DEVICE buffer of
  * (y1-y0)*hsize*3 doubles (row y0 first). Enqueues on the context stream and returns

@@ -19,7 +19,7 @@ import numpy as np
 
 from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
-                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, PATTERNS, STATUS_NAMES, declare)
+                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, PATTERNS, STATUS_NAMES, declare)
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librtc.so"
@@ -183,12 +183,36 @@ def light(position=(-10.0, 10.0, -10.0), intensity=(1.0, 1.0, 1.0)) -> RtcLight:
 
 
 class World:
-    """World (shape.rs:633-637): host-side list of shapes + one light; `add_shape` assigns
-    world ids like the reference (shape.rs:661-667)."""
+    """World (shape.rs:633-637): host-side list of shapes + 1..MAX_LIGHTS lights (one RtcLight or a list of them);
+    `add_shape` assigns world ids like the reference (shape.rs:661-667). `light` is `lights[0]`, the one the reference
+    shades with; a DeviceWorld shades with all of them (rtc_world_create_lights)."""
 
-    def __init__(self, lgt: RtcLight | None = None):
-        self.light = lgt if lgt is not None else light()
+    def __init__(self, lgt=None):
+        if lgt is None:
+            self.lights: list[RtcLight] = [light()]
+        elif isinstance(lgt, RtcLight):
+            self.lights = [lgt]
+        else:
+            self.lights = list(lgt)
         self.shapes: list[RtcShape] = []
+
+    @property
+    def light(self) -> RtcLight:
+        return self.lights[0]
+
+    @light.setter
+    def light(self, lgt: RtcLight) -> None:
+        self.lights[0] = lgt
+
+    def add_light(self, lgt: RtcLight) -> "World":
+        self.lights.append(lgt)
+        return self
+
+    def light_array(self):
+        arr = (RtcLight * max(1, len(self.lights)))()
+        for i, l in enumerate(self.lights):
+            arr[i] = l
+        return arr
 
     def add_shape(self, s: RtcShape) -> "World":
         s.world_id = len(self.shapes) + 1
@@ -228,18 +252,27 @@ def ray_for_pixel(cam: RtcCamera, x: int, y: int, xo: float = 0.5, yo: float = 0
     return np.array(list(out))
 
 
+def _copy_lights(arr, n: int) -> list:
+    out = []
+    for i in range(n):
+        l = RtcLight()
+        C.memmove(C.byref(l), C.byref(arr[i]), C.sizeof(RtcLight))
+        out.append(l)
+    return out
+
+
 def load_yaml(text: str | None = None, path: str | None = None):
-    """jamis.yml-vocabulary loader -> (World, RtcCamera)."""
+    """jamis.yml-vocabulary loader -> (World, RtcCamera); the World holds every `add: light` of the file."""
     shapes = C.POINTER(RtcShape)()
     n = C.c_uint32(0)
-    lgt, cam = RtcLight(), RtcCamera()
+    lgts, nl, cam = (RtcLight * MAX_LIGHTS)(), C.c_uint32(0), RtcCamera()
     err = C.create_string_buffer(512)
     if path is not None:
-        st = lib().rtc_scene_load_yaml_file(str(path).encode(), C.byref(shapes), C.byref(n), C.byref(lgt), C.byref(cam), err, 512)
+        st = lib().rtc_scene_load_yaml_lights_file(str(path).encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl), C.byref(cam), err, 512)
     else:
-        st = lib().rtc_scene_load_yaml(text.encode(), C.byref(shapes), C.byref(n), C.byref(lgt), C.byref(cam), err, 512)
+        st = lib().rtc_scene_load_yaml_lights(text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl), C.byref(cam), err, 512)
     _check(st, "rtc_scene_load_yaml", err.value.decode(errors="replace"))
-    w = World(lgt)
+    w = World(_copy_lights(lgts, nl.value))
     for i in range(n.value):
         s = RtcShape()
         C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
@@ -252,7 +285,7 @@ class LuaJob:
     """One Render(world, camera, file) or encoder:AddFrame(world, camera) call of a script (rtc_lua_job), converted by
     lua.rs's *_from_table rules at the moment of the call."""
 
-    def __init__(self, j: RtcLuaJob, index: int):
+    def __init__(self, j: RtcLuaJob, index: int, lights=None):
         self.index = index
         self.kind = "AddFrame" if j.kind == 1 else "Render"
         self.outfile = (j.outfile or b"").decode(errors="replace")
@@ -262,7 +295,8 @@ class LuaJob:
         C.memmove(C.byref(self.camera), C.byref(j.camera), C.sizeof(RtcCamera))
         lgt = RtcLight()
         C.memmove(C.byref(lgt), C.byref(j.light), C.sizeof(RtcLight))
-        self.world = World(lgt)
+        self.lights = list(lights) if lights else [lgt]  # every light of the job's world; lights[0] is rtc_lua_job.light
+        self.world = World(self.lights)
         for i in range(j.n_shapes):
             s = RtcShape()
             C.memmove(C.byref(s), C.byref(j.shapes[i]), C.sizeof(RtcShape))
@@ -312,7 +346,9 @@ class LuaProgram:
     def job(self, index: int) -> LuaJob:
         j = RtcLuaJob()
         _check(lib().rtc_lua_program_job(self._h, index, C.byref(j)), "rtc_lua_program_job")
-        return LuaJob(j, index)
+        lgts, nl = (RtcLight * MAX_LIGHTS)(), C.c_uint32(0)
+        _check(lib().rtc_lua_program_job_lights(self._h, index, lgts, MAX_LIGHTS, C.byref(nl)), "rtc_lua_program_job_lights")
+        return LuaJob(j, index, _copy_lights(lgts, nl.value))
 
     @property
     def jobs(self):
@@ -546,16 +582,16 @@ def load_lua(text: str | None = None, path: str | None = None, render_index: int
     """One job of a Lua scene script (rtc_scene_load_lua) -> (World, RtcCamera, outfile, n_jobs)."""
     shapes = C.POINTER(RtcShape)()
     n, renders = C.c_uint32(0), C.c_uint32(0)
-    lgt, cam = RtcLight(), RtcCamera()
+    lgts, nl, cam = (RtcLight * MAX_LIGHTS)(), C.c_uint32(0), RtcCamera()
     err, outfile = C.create_string_buffer(512), C.create_string_buffer(512)
     if path is not None:
-        st = lib().rtc_scene_load_lua_file(str(path).encode(), render_index, C.byref(shapes), C.byref(n), C.byref(lgt), C.byref(cam), outfile, 512,
-                                           C.byref(renders), err, 512)
+        st = lib().rtc_scene_load_lua_lights_file(str(path).encode(), render_index, C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl),
+                                                  C.byref(cam), outfile, 512, C.byref(renders), err, 512)
     else:
-        st = lib().rtc_scene_load_lua(text.encode(), render_index, C.byref(shapes), C.byref(n), C.byref(lgt), C.byref(cam), outfile, 512,
-                                      C.byref(renders), err, 512)
+        st = lib().rtc_scene_load_lua_lights(text.encode(), render_index, C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl),
+                                             C.byref(cam), outfile, 512, C.byref(renders), err, 512)
     _check(st, "rtc_scene_load_lua", err.value.decode(errors="replace"))
-    w = World(lgt)
+    w = World(_copy_lights(lgts, nl.value))
     for i in range(n.value):
         s = RtcShape()
         C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
@@ -981,7 +1017,8 @@ class DeviceWorld:
         self.ctx = ctx
         self._h = C.c_void_p()
         arr = world.array()
-        _check(lib().rtc_world_create(ctx._h, arr, len(world.shapes), C.byref(world.light), C.byref(self._h)), "rtc_world_create")
+        _check(lib().rtc_world_create_lights(ctx._h, arr, len(world.shapes), world.light_array(), len(world.lights), C.byref(self._h)),
+               "rtc_world_create_lights")
         self.n = len(world.shapes)
         ctx._worlds.append(weakref.ref(self))
 
@@ -989,7 +1026,8 @@ class DeviceWorld:
         """Replace the resident World's contents by `world` (rtc_world_update): ordered like a launch, rebuilt on the
         device, no allocation while the World does not grow."""
         arr = world.array()
-        _check(lib().rtc_world_update(self.ctx._h, self._h, arr, len(world.shapes), C.byref(world.light)), "rtc_world_update")
+        _check(lib().rtc_world_update_lights(self.ctx._h, self._h, arr, len(world.shapes), world.light_array(), len(world.lights)),
+               "rtc_world_update_lights")
         self.n = len(world.shapes)
 
     def close(self):

@@ -12,6 +12,7 @@ FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE = 0, 1, 2, 4
 EXCHANGE_RCCL, EXCHANGE_P2P = 0, 1
 GATHER_NONE, GATHER_F64, GATHER_U8 = 0, 1, 2
 GROUP_ID_BYTES = 128
+MAX_LIGHTS = 8
 PATTERNS = {"none": 0, "test": 1, "stripe": 2, "stripes": 2, "gradient": 3, "ring": 4, "checker": 5, "checkers": 5, "grid": 6}
 STATUS_NAMES = {0: "RTC_OK", 1: "RTC_ERR_SINGULAR", 2: "RTC_ERR_NO_COLOR", 3: "RTC_ERR_DEVICE", 4: "RTC_ERR_ARG",
                 5: "RTC_ERR_PARSE", 6: "RTC_ERR_IO", 7: "RTC_ERR_NOMEM", 8: "RTC_ERR_UNSUPPORTED"}
@@ -164,6 +165,15 @@ PROTOTYPES = {
                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_scene_load_lua_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
                                             C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_yaml_lights": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
+                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_yaml_lights_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
+                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_lua_lights": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
+                                              C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_lua_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
+                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_lua_program_job_lights": (C.c_int32, [C.c_void_p, U32, C.POINTER(RtcLight), U32, C.POINTER(U32)]),
     "rtc_free": (None, [VP]),
     "rtc_canvas_write_ppm": (C.c_int32, [C.c_char_p, PD, U32, U32]),
     "rtc_canvas_format_ppm": (C.c_size_t, [PD, U32, U32, C.c_char_p, C.c_size_t]),
@@ -176,6 +186,9 @@ PROTOTYPES = {
     "rtc_context_device_info": (C.c_int32, [VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rtc_world_create": (C.c_int32, [VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight), C.POINTER(VP)]),
     "rtc_world_update": (C.c_int32, [VP, VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight)]),
+    "rtc_world_create_lights": (C.c_int32, [VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight), U32, C.POINTER(VP)]),
+    "rtc_world_update_lights": (C.c_int32, [VP, VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight), U32]),
+    "rtc_world_light_count": (U32, [VP]),
     "rtc_world_destroy": (None, [VP]),
     "rtc_render_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),
     "rtc_render_bands": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),

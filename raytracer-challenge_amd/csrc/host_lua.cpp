@@ -35,7 +35,8 @@
 //     ("Invalid material property"); then a shape-level `color` (or else `pattern`) overrides, silently ignored when malformed;
 //   * pattern_from_table (lua.rs:109-143): "checks" / "stripes" with color_a, color_b; "grid" = white on black; the pattern
 //     table's own rotate_* / scale / position are its transform;
-//   * lights: only lights[1] (lua.rs:148-150); camera: screenwidth, screenheight (Lua INTEGERS, lua.rs:158-170), position,
+//   * lights: every element of world.lights, at most RTC_MAX_LIGHTS (the reference converts the list and shades with lights[1]
+//     only, lua.rs:148-150, shape.rs:686); camera: screenwidth, screenheight (Lua INTEGERS, lua.rs:158-170), position,
 //     lookat, up, fov, optional samples (integer 0..255, lua.rs:172-183);
 //   * shapes: "sphere" | "plane" | "cube" through *::new_with_transform_and_material, world ids as World::add_shape.
 // A Lua error — syntax, runtime, or a table lua.rs would reject — is RTC_ERR_PARSE with the message (the reference
@@ -824,7 +825,8 @@ struct Function {
 
 struct SceneData {
     std::vector<rtc_shape> shapes;
-    rtc_light light;
+    rtc_light light;               // lights[1]
+    std::vector<rtc_light> lights; // every element of world.lights, lights[1] first
 };
 struct Job {
     std::shared_ptr<SceneData> scene; // shared with the previous job when the converted world is identical
@@ -1586,7 +1588,8 @@ struct Interp {
         camera_from_table(*camera.t, j.camera, line);
         if (!jobs.empty()) { // an animation usually renders one world from many cameras: keep one copy
             const SceneData &prev = *jobs.back().scene;
-            if (prev.shapes.size() == sc->shapes.size() && std::memcmp(&prev.light, &sc->light, sizeof(rtc_light)) == 0 &&
+            if (prev.shapes.size() == sc->shapes.size() && prev.lights.size() == sc->lights.size() &&
+                std::memcmp(prev.lights.data(), sc->lights.data(), sizeof(rtc_light) * sc->lights.size()) == 0 &&
                 (sc->shapes.empty() || std::memcmp(prev.shapes.data(), sc->shapes.data(), sizeof(rtc_shape) * sc->shapes.size()) == 0)) {
                 sc = jobs.back().scene;
                 j.same_world = true;
@@ -2037,10 +2040,19 @@ void camera_from_table(const Table &t, rtc_camera &cam, int line) { // lua.rs:24
 
 void world_from_table(const Table &t, SceneData &sc, int line) { // lua.rs:293-330
     const Table &lights = table_of(t.get("lights"), "world.lights", line);
-    const Table &l1 = table_of(lights.at(1), "world.lights[1]", line); // lights_from_table: only the first
-    std::memset(&sc.light, 0, sizeof sc.light);
-    xyz(table_of(l1.get("color"), "light color", line), "r", "g", "b", sc.light.intensity, "light color", line);
-    xyz(table_of(l1.get("position"), "light position", line), "x", "y", "z", sc.light.position, "light position", line);
+    // lights_from_table converts the sequence; the reference then shades with the first only (shape.rs:686), this library with all
+    for (long long k = 1;; ++k) {
+        const Value *lv = lights.at(k);
+        if (!lv && k > 1) break;
+        const Table &lt = table_of(lv, k == 1 ? "world.lights[1]" : "a light", line);
+        if (sc.lights.size() == RTC_MAX_LIGHTS) fail(line, "too many lights: a world holds at most " + std::to_string(RTC_MAX_LIGHTS));
+        rtc_light l;
+        std::memset(&l, 0, sizeof l);
+        xyz(table_of(lt.get("color"), "light color", line), "r", "g", "b", l.intensity, "light color", line);
+        xyz(table_of(lt.get("position"), "light position", line), "x", "y", "z", l.position, "light position", line);
+        sc.lights.push_back(l);
+    }
+    sc.light = sc.lights[0];
     const Table &shapes = table_of(t.get("shapes"), "world.shapes", line);
     for (long long k = 1;; ++k) { // sequence_values: 1, 2, ... until the first nil
         const Value *sv = shapes.at(k);
@@ -2159,13 +2171,24 @@ rtc_status rtc_lua_program_job(const rtc_lua_program *prog, uint32_t index, rtc_
     return RTC_OK;
 }
 
+rtc_status rtc_lua_program_job_lights(const rtc_lua_program *prog, uint32_t index, rtc_light *lights_out, uint32_t cap, uint32_t *n_out) {
+    if (!prog || !lights_out || !n_out || index >= prog->in.jobs.size()) return RTC_ERR_ARG;
+    const std::vector<rtc_light> &l = prog->in.jobs[index].scene->lights;
+    *n_out = 0;
+    if (l.size() > cap) return RTC_ERR_ARG;
+    for (size_t i = 0; i < l.size(); ++i) lights_out[i] = l[i];
+    *n_out = static_cast<uint32_t>(l.size());
+    return RTC_OK;
+}
+
 const char *rtc_lua_program_output(const rtc_lua_program *prog) { return prog ? prog->in.output.c_str() : ""; }
 
 void rtc_lua_program_free(rtc_lua_program *prog) { delete prog; }
 
 // The single-scene form: run the script, hand out one of its jobs as malloc'ed arrays.
+// lights_cap == 0: the single-light form, *light_out = lights[1]
 static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *light_out,
-                           rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
+                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
     std::unique_ptr<rtc_lua_program> own(prog);
     Interp &in = prog->in;
     try {
@@ -2180,13 +2203,19 @@ static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_sha
         }
         const Job &j = in.jobs[render_index];
         if (outfile && outfile_len) std::snprintf(outfile, outfile_len, "%s", j.outfile.c_str());
+        if (lights_cap && j.scene->lights.size() > lights_cap) return RTC_ERR_ARG;
         const size_t count = j.scene->shapes.size();
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(sizeof(rtc_shape) * (count ? count : 1)));
         if (!arr) return RTC_ERR_NOMEM;
         if (count) std::memcpy(arr, j.scene->shapes.data(), sizeof(rtc_shape) * count);
         *shapes_out = arr;
         *n_out = static_cast<uint32_t>(count);
-        *light_out = j.scene->light;
+        if (lights_cap) {
+            for (size_t i = 0; i < j.scene->lights.size(); ++i) light_out[i] = j.scene->lights[i];
+            *n_lights_out = static_cast<uint32_t>(j.scene->lights.size());
+        } else {
+            *light_out = j.scene->light;
+        }
         *camera_out = j.camera;
         return RTC_OK;
     } catch (const LuaError &e) {
@@ -2208,7 +2237,7 @@ rtc_status rtc_scene_load_lua(const char *text, uint32_t render_index, rtc_shape
     rtc_lua_program *prog = nullptr;
     const rtc_status st = rtc_lua_run(text, nullptr, 0, &prog, errbuf, errbuf_len);
     if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, light_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+    return load_one(prog, render_index, shapes_out, n_out, light_out, 0u, nullptr, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
 }
 
 rtc_status rtc_scene_load_lua_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *light_out,
@@ -2222,7 +2251,37 @@ rtc_status rtc_scene_load_lua_file(const char *path, uint32_t render_index, rtc_
     rtc_lua_program *prog = nullptr;
     const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
     if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, light_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+    return load_one(prog, render_index, shapes_out, n_out, light_out, 0u, nullptr, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+}
+
+rtc_status rtc_scene_load_lua_lights(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out,
+                                     uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len,
+                                     uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
+    if (!text || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
+    *shapes_out = nullptr;
+    *n_out = 0;
+    *n_lights_out = 0;
+    if (renders_out) *renders_out = 0;
+    if (outfile && outfile_len) outfile[0] = 0;
+    rtc_lua_program *prog = nullptr;
+    const rtc_status st = rtc_lua_run(text, nullptr, 0, &prog, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return load_one(prog, render_index, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+}
+
+rtc_status rtc_scene_load_lua_lights_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out,
+                                          uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len,
+                                          uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
+    if (!path || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
+    *shapes_out = nullptr;
+    *n_out = 0;
+    *n_lights_out = 0;
+    if (renders_out) *renders_out = 0;
+    if (outfile && outfile_len) outfile[0] = 0;
+    rtc_lua_program *prog = nullptr;
+    const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return load_one(prog, render_index, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
 }
 
 } // extern "C"

@@ -339,8 +339,7 @@ void build_material(const Defs &defs, const Node *n, rtc_material &mat) {
 
 struct Scene {
     std::vector<rtc_shape> shapes;
-    rtc_light light;
-    bool have_light = false;
+    std::vector<rtc_light> lights; // every `add: light`, in file order
     rtc_camera camera;
     bool have_camera = false;
 };
@@ -392,7 +391,8 @@ void interpret(const Node &root, Scene &sc) {
             rtc_light l;
             as_triple(e.get("at"), "at", l.position);
             as_triple(e.get("intensity"), "intensity", l.intensity);
-            if (!sc.have_light) { sc.light = l; sc.have_light = true; } // lights[1] only, lua.rs:148-150
+            if (sc.lights.size() == RTC_MAX_LIGHTS) fail(e.line, "too many lights: a scene holds at most " + std::to_string(RTC_MAX_LIGHTS));
+            sc.lights.push_back(l); // (the reference uses lights[1] only, lua.rs:148-150: the single-light entries return that one)
         } else if (what == "sphere" || what == "plane" || what == "cube") {
             const uint32_t kind = what == "sphere" ? RTC_SPHERE : what == "plane" ? RTC_PLANE : RTC_CUBE;
             double xf[16];
@@ -409,7 +409,7 @@ void interpret(const Node &root, Scene &sc) {
             fail(add->line, "Invalid shape type: " + what); // lua.rs:322-326
         }
     }
-    if (!sc.have_light) fail(root.line, "scene has no light");
+    if (sc.lights.empty()) fail(root.line, "scene has no light");
     if (!sc.have_camera) fail(root.line, "scene has no camera");
 }
 
@@ -423,12 +423,13 @@ void set_err(char *errbuf, size_t len, const std::string &msg) {
 
 extern "C" {
 
-rtc_status rtc_scene_load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
-                               rtc_light *light_out, rtc_camera *camera_out, char *errbuf,
-                               size_t errbuf_len) {
-    if (!text || !shapes_out || !n_out || !light_out || !camera_out) return RTC_ERR_ARG;
+// first_only: the single-light entries' form — lights_out receives lights[1] alone, however many the scene has
+static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out, uint32_t lights_cap,
+                            uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only) {
+    if (!text || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
+    *n_lights_out = 0;
     try {
         Parser p;
         p.lines = split_lines(text);
@@ -437,13 +438,16 @@ rtc_status rtc_scene_load_yaml(const char *text, rtc_shape **shapes_out, uint32_
         if (p.pos != p.lines.size()) fail(p.lines[p.pos].number, "unexpected content");
         Scene sc;
         interpret(*root, sc);
+        if (!first_only && sc.lights.size() > lights_cap) return RTC_ERR_ARG;
         const size_t bytes = sizeof(rtc_shape) * (sc.shapes.empty() ? 1 : sc.shapes.size());
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(bytes));
         if (!arr) return RTC_ERR_NOMEM;
         if (!sc.shapes.empty()) std::memcpy(arr, sc.shapes.data(), sizeof(rtc_shape) * sc.shapes.size());
         *shapes_out = arr;
         *n_out = static_cast<uint32_t>(sc.shapes.size());
-        *light_out = sc.light;
+        const uint32_t nl = first_only ? 1u : static_cast<uint32_t>(sc.lights.size());
+        for (uint32_t i = 0; i < nl; ++i) lights_out[i] = sc.lights[i];
+        *n_lights_out = nl;
         *camera_out = sc.camera;
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -457,18 +461,46 @@ rtc_status rtc_scene_load_yaml(const char *text, rtc_shape **shapes_out, uint32_
     }
 }
 
-rtc_status rtc_scene_load_yaml_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
-                                    rtc_light *light_out, rtc_camera *camera_out, char *errbuf,
-                                    size_t errbuf_len) {
+rtc_status rtc_scene_load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                               rtc_light *light_out, rtc_camera *camera_out, char *errbuf,
+                               size_t errbuf_len) {
+    uint32_t one = 0u;
+    return load_yaml(text, shapes_out, n_out, light_out, 1u, &one, camera_out, errbuf, errbuf_len, true);
+}
+
+rtc_status rtc_scene_load_yaml_lights(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out,
+                                      uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                      size_t errbuf_len) {
+    return load_yaml(text, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false);
+}
+
+static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
     if (!path) return RTC_ERR_ARG;
     std::FILE *f = std::fopen(path, "rb");
     if (!f) { set_err(errbuf, errbuf_len, std::string("cannot open ") + path); return RTC_ERR_IO; }
-    std::string text;
     char buf[4096];
     size_t n;
     while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
     std::fclose(f);
+    return RTC_OK;
+}
+
+rtc_status rtc_scene_load_yaml_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                    rtc_light *light_out, rtc_camera *camera_out, char *errbuf,
+                                    size_t errbuf_len) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
     return rtc_scene_load_yaml(text.c_str(), shapes_out, n_out, light_out, camera_out, errbuf, errbuf_len);
+}
+
+rtc_status rtc_scene_load_yaml_lights_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out,
+                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                           size_t errbuf_len) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_lights(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len);
 }
 
 } // extern "C"

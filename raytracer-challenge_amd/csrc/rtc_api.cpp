@@ -19,7 +19,7 @@
 #include "rtc_internal.h"
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
-                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1);
+                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl);
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],
                                       hipStream_t stream);
 extern "C" hipError_t rtc_launch_arith(uint32_t op, const double *a, const double *b, uint32_t n, double *out,
@@ -47,7 +47,10 @@ hipError_t drain_lanes(rtc_context *ctx) {
     return hipSuccess;
 }
 
-void choose_source(const rtc_context *ctx, uint32_t n, uint32_t flags, int *src, uint32_t *tile_cap, size_t *lds_bytes) {
+// `multi`: a World with several lights. Its kernels exist for SRC_SMEM, SRC_CULL and SRC_CULL2 only, so the brute-force
+// choice is SRC_SMEM at every size; an LDS source can then only come out of RTC_FLAG_LDS_TABLE or an RTC_SRC override,
+// which the callers refuse (lights_of).
+void choose_source(const rtc_context *ctx, uint32_t n, uint32_t flags, int *src, uint32_t *tile_cap, size_t *lds_bytes, bool multi = false) {
     // per object in LDS: 96 B inverse rows + 32 B primary prologue + 4 B kind
     const uint32_t per_obj = 96 + 32 + 4;
     int s;
@@ -55,7 +58,7 @@ void choose_source(const rtc_context *ctx, uint32_t n, uint32_t flags, int *src,
     else if (!(flags & RTC_FLAG_NO_CULL)) s = (n > 256) ? SRC_CULL2 : SRC_CULL; // default: per-wave conservative cull,
                                                                               // two-level above 4 groups of 64
     else if (flags & RTC_FLAG_LDS_TABLE) s = SRC_LDS1; // brute force over the LDS-staged object table (LDS tiles when it does not fit)
-    else if (n <= 128) s = SRC_SMEM;
+    else if (n <= 128 || multi) s = SRC_SMEM;
     else if (n <= 448) s = SRC_LDS1;
     else s = SRC_LDSN;
     uint32_t cap = 0;
@@ -234,6 +237,30 @@ void fill_world(RenderParams &P, const rtc_world::Gen &G) {
         P.light_pos[i] = G.light.position[i];
         P.light_int[i] = G.light.intensity[i];
     }
+}
+
+// The further lights of generation G as k_trace's trailing argument; *xl = nullptr for a one-light World (the kernels
+// without that argument). RTC_ERR_UNSUPPORTED when the launch's source has no multi-light kernels.
+rtc_status lights_of(const rtc_world::Gen &G, int src, DevExtraLights &X, const DevExtraLights **xl) {
+    *xl = nullptr;
+    if (G.n_lights <= 1u) return RTC_OK;
+    if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED;
+    std::memset(&X, 0, sizeof X);
+    X.n = G.n_lights - 1u;
+    for (uint32_t i = 0; i < X.n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            X.pos[i][k] = G.more[i].position[k];
+            X.inten[i][k] = G.more[i].intensity[k];
+        }
+    *xl = &X;
+    return RTC_OK;
+}
+
+// L[0] and L[1..n) of a generation, from the caller's array
+void set_lights(rtc_world::Gen &G, const rtc_light *lights, uint32_t n_lights) {
+    G.light = lights[0];
+    G.n_lights = n_lights;
+    for (uint32_t i = 1; i < n_lights; ++i) G.more[i - 1u] = lights[i];
 }
 
 // ---- generations (rtc_world::Gen)
@@ -590,8 +617,17 @@ rtc_status rtc_context_device_info(rtc_context *ctx, char *name, size_t cap, int
     return RTC_OK;
 }
 
+static_assert(RTC_DEV_MAX_LIGHTS == RTC_MAX_LIGHTS, "include/rtc.h and rtc_device.h disagree");
+
 rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *light, rtc_world **out) {
-    if (!ctx || !out || !light || (n && !shapes)) return RTC_ERR_ARG;
+    return rtc_world_create_lights(ctx, shapes, n, light, 1u, out);
+}
+
+// (the light-space lists are L[0]'s: `light` below)
+rtc_status rtc_world_create_lights(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *lights, uint32_t n_lights,
+                                   rtc_world **out) {
+    if (!ctx || !out || !lights || (n && !shapes) || n_lights == 0u || n_lights > RTC_MAX_LIGHTS) return RTC_ERR_ARG;
+    const rtc_light *light = lights;
     *out = nullptr;
     const rtc_status cs = check_shapes(shapes, n);
     if (cs != RTC_OK) return cs;
@@ -693,7 +729,7 @@ rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t 
     G.pre_limit = std::isfinite(pre_limit) ? pre_limit : 0.;
     G.ngroups = ngroups;
     G.n = n;
-    G.light = *light;
+    set_lights(G, lights, n_lights);
     G.any_refl = any_refl;
     G.any_refr = any_refr;
     for (uint32_t i = 0; i < n; ++i)
@@ -789,7 +825,17 @@ static rtc_status ready_update(rtc_world *w) {
 // contents: until an update succeeds every render of it returns RTC_ERR_NOMEM (rtc_world::valid). (The first update also creates the build stream, the events and the
 // page-locked block.)
 rtc_status rtc_world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n, const rtc_light *light) {
-    if (!ctx || !w || !light || (n && !shapes) || w->ctx != ctx) return RTC_ERR_ARG;
+    return rtc_world_update_lights(ctx, w, shapes, n, light, 1u);
+}
+
+uint32_t rtc_world_light_count(const rtc_world *w) { return w ? w->gen[w->cur].n_lights : 0u; }
+
+// (the lights are host-side state of the generation: they reach the device in each launch's arguments, so a changed count
+// costs nothing here)
+rtc_status rtc_world_update_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n, const rtc_light *lights,
+                                   uint32_t n_lights) {
+    if (!ctx || !w || !lights || (n && !shapes) || w->ctx != ctx || n_lights == 0u || n_lights > RTC_MAX_LIGHTS) return RTC_ERR_ARG;
+    const rtc_light *light = lights;
     const rtc_status cs = check_shapes(shapes, n);
     if (cs != RTC_OK) return cs;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -828,7 +874,7 @@ rtc_status rtc_world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *sha
     flatten_shapes(shapes, n, staged_at(G.isect), staged_at(G.kind), staged_at(G.shade), staged_at(G.idtab), &G.any_refl, &G.any_refr);
     G.n = n;
     G.ngroups = (n + 63u) / 64u;
-    G.light = *light;
+    set_lights(G, lights, n_lights);
     G.light_cap = 0;
     G.light_cap_want = light_cap;
     HIP_TRY(hipMemcpyAsync(base, G.stage, staged, hipMemcpyHostToDevice, bs));
@@ -954,7 +1000,11 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     P.remaining = RTC_MAX_REFLECTIONS; // render_pixel passes Camera::MAX_REFLECTIONS camera.rs:98
     int src;
     size_t lds_bytes;
-    choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes);
+    choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u);
+    DevExtraLights extra;
+    const DevExtraLights *xl = nullptr;
+    const rtc_status ls = lights_of(G, src, extra, &xl);
+    if (ls != RTC_OK) return ls;
     const int cull = CULL_LEVEL(src);
     const bool refl = G.any_refl || G.any_refr;
     const uint32_t block = RTC_BLOCK_FOR(cull, refl, G.any_refr, false), tile_w = RTC_TILE_W_FOR(cull, refl, G.any_refr, false);
@@ -1076,7 +1126,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         }
     }
     HIP_TRY(rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, grid_wgs, lds_bytes, stream,
-                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr));
+                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, xl));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
     HIP_TRY(record_read(w, G, stream, stream_bit));
     ctx->last = rtc_launch_info{(uint32_t)src, (G.any_refl || G.any_refr) ? 1u : 0u, G.any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
@@ -1465,7 +1515,10 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.hits = d_hits.get();
         int src;
         size_t lds_bytes;
-        choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes);
+        choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u);
+        DevExtraLights extra;
+        const DevExtraLights *xl = nullptr;
+        st = lights_of(G, src, extra, &xl);
         const uint32_t blk = RTC_BLOCK_FOR(CULL_LEVEL(src), G.any_refl || G.any_refr, G.any_refr, true);
         P.grid_x = (n + blk - 1u) / blk;
         P.grid_y = 1;
@@ -1474,8 +1527,8 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.total_blocks = P.grid_x;
         P.reps = 1;
         P.chunk_wgs[0] = P.chunk_wgs[1] = P.chunk_wgs[2] = P.chunk_wgs[3] = 0;
-        if (rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
-                             nullptr) != hipSuccess)
+        if (st == RTC_OK && rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
+                                             nullptr, xl) != hipSuccess)
             st = RTC_ERR_DEVICE;
     }
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)

@@ -143,6 +143,16 @@ enum { SRC_SMEM = 0, SRC_LDS1 = 1, SRC_LDSN = 2, SRC_CULL = 3, SRC_CULL2 = 4 };
 // Tile-list entries hold (key >> 16) << 16 | index while every index fits 16 bits
 #define RTC_BIN_PACKED(n) ((n) <= 65536u)
 
+// Lights 1..n-1 of a World with several lights (light 0 is RenderParams::light_pos / light_int, as for every World). The
+// multi-light instantiations of k_trace take this block as their LAST argument, behind the table pointers; the one-light
+// kernels have no such argument, so their kernarg segment is what it always was.
+enum { RTC_DEV_MAX_LIGHTS = 8 }; // == RTC_MAX_LIGHTS (include/rtc.h)
+struct DevExtraLights {
+    uint32_t n, _pad;                          // how many follow the first: 1 .. RTC_DEV_MAX_LIGHTS - 1
+    double pos[RTC_DEV_MAX_LIGHTS - 1][3];     // PointLight::position
+    double inten[RTC_DEV_MAX_LIGHTS - 1][3];   // PointLight::intensity
+};
+
 struct RenderParams {
     const DevIsect *isect;
     const uint32_t *kind;

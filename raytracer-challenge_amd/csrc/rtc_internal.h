@@ -118,7 +118,9 @@ struct rtc_world {
         DevWorldHeader *d_hdr = nullptr;
         uint32_t n = 0;
         uint32_t ngroups = 0;
-        rtc_light light{};
+        rtc_light light{};                     // L[0]: the light with the light-space lists
+        uint32_t n_lights = 1;                 // 1 .. RTC_MAX_LIGHTS
+        rtc_light more[RTC_MAX_LIGHTS - 1]{};  // L[1 .. n_lights)
         bool any_refl = false, any_refr = false;
         uint32_t light_cap = 0;  // entries per cell of this generation's lists; 0: it has none
         // known to the host build at once; after a device build only once the header has arrived (hdr_pending)

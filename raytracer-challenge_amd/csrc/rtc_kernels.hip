@@ -910,6 +910,12 @@ DEVI V3 lighting(const PP &P, const DevShade *S, const double *m_obj, V3 point, 
     return vadd(vadd(ambient, diffuse), specular);
 }
 
+// lighting()'s view of a light that is not the parameter block's own (lights 1..n-1 of a multi-light World)
+struct LightInt {
+    double light_int[3];
+};
+template <class T> DEVI const T &first_of(const T &t) { return t; }
+
 // World::reflectance (Schlick) shape.rs:768-781
 DEVI double reflectance(V3 eyev, V3 normal, double n1, double n2) {
     double cosv = vdot(eyev, normal);
@@ -1028,13 +1034,20 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // render flavour (PROBE = false) never carries the hit record's extra vectors in registers.
 // RGBA = true (render flavour only) is the launch with a gamma table (RenderParams::gamma): the 8-bit output is
 // Canvas::to_imgbuf's RGBA. Its own instantiation, so that the RGB kernels' code and resources stay exactly as they are.
-template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false>
+// XL: empty for a World with one light — the kernels as they always were, argument list included. One DevExtraLights
+// (rtc_device.h) for a World with several (MULTI): lights 1..n-1 ride behind the tables in the kernarg segment, and the
+// shadow and lighting stages loop over them (shade_hit with the FIXME at shape.rs:686 filled in: the sum of every light's
+// lighting(), each with its own is_shadowed_by_light, shape.rs:716). Instantiated only for the sources a multi-light launch
+// takes (SRC_SMEM, SRC_CULL, SRC_CULL2).
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, class... XL>
 __global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
         const DevShade *__restrict__ t_shade, const DevPrim *__restrict__ t_prim, const DevBound *__restrict__ t_bound,
         const DevIsect *__restrict__ t_isect_s, const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s,
         const uint32_t *__restrict__ t_orig_s, const DevBound *__restrict__ t_gbound, const DevIdEntry *__restrict__ t_idtab,
-        const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s) {
+        const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
+    constexpr bool MULTI = sizeof...(XL) != 0;
+    static_assert(sizeof...(XL) <= 1, "at most one block of further lights");
     constexpr uint32_t BLOCK = RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), TILE_W = RTC_TILE_W_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE);
     extern __shared__ double lds_raw[];
     // Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x 4 doubles x
@@ -1580,6 +1593,47 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 H->n1 = n1; H->n2 = n2;
             }
 
+            // ---- several lights (MULTI): surface = lighting(L[0]) + lighting(L[1]) + ..., in light order ----
+            // The first light's term (its shadow bit comes from the passes above, lists included), then per further light
+            // the shadow ray's set-up (shape.rs:717-719), the any-hit pass and lighting(). The further lights have no
+            // light-space lists: their segments take the bundle walk, apex = that light. Kept out of the divergent
+            // branch below: the walks are wave-level code (ballots, DPP reductions).
+            V3 surface_all = mk(0., 0., 0.);
+            if constexpr (MULTI) {
+                static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "multi-light launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
+                const DevExtraLights &X = first_of(xl_arg...);
+                if (hit) surface_all = lighting(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
+                const uint32_t n_extra = X.n;
+                for (uint32_t li = 0; li < n_extra; ++li) {
+                    const V3 lp = mk(X.pos[li][0], X.pos[li][1], X.pos[li][2]);
+                    V3 ldir = mk(0, 0, 0);
+                    double ldist = 0.;
+                    if (hit) { // is_shadowed_by_light shape.rs:716-720
+                        const V3 v = vsub(lp, over);
+                        ldist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
+                        ldir = mk(v.x / ldist, v.y / ldist, v.z / ldist);
+                    }
+                    bool l_pending = hit, l_shadowed = false;
+                    c_shadow += popc64(ballot(hit));
+                    Bundle Bl{};
+                    Bl.off = true;
+                    if constexpr (IS_CULL(SRC)) {
+                        if (ballot(hit) != 0ull) Bl = make_bundle<true, true>(hit, lp, lp, vneg(ldir), ldist);
+                    }
+                    for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, l_pending, Bl, [&](int j, auto m, uint32_t kind, auto pr) {
+                        if (l_pending) {
+                            if (occludes_world(kind, m, over, ldir, ldist)) { l_shadowed = true; l_pending = false; }
+                        }
+                        return ballot(l_pending) != 0ull;
+                    }, over, ldir);
+                    asm volatile("" ::: "memory"); // as above: the material loads stay below the walk
+                    if (hit) {
+                        const LightInt I{{X.inten[li][0], X.inten[li][1], X.inten[li][2]}};
+                        surface_all = vadd(surface_all, lighting(I, S, m_obj, over, eyev, normal, ldir, l_shadowed));
+                    }
+                }
+            }
+
             // ---- shade_hit (shape.rs:685-700) ------------------------------------------------
             V3 val = mk(0., 0., 0.); // value returned by the color_at call that just finished
             bool have_val = false;
@@ -1587,7 +1641,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             if (tracing && !hit) { // background_color: BLACK shape.rs:652-653
                 have_val = true;
             } else if (hit) {
-                const V3 surface = lighting(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
+                V3 surface;
+                if constexpr (MULTI) surface = surface_all;
+                else surface = lighting(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
                 bool want_refl = false, want_refr = false;
                 V3 fr_o = mk(0, 0, 0), fr_d = mk(0, 0, 0);
                 if constexpr (REFL) want_refl = (rem != 0) && (m_kr > 0.); // reflected_color shape.rs:730
@@ -2329,35 +2385,44 @@ extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, co
 }
 
 // ---- launchers (called from rtc_api.cpp) --------------------------------------------------
-template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA>
+// XL: nothing (one light), or the World's further lights (k_trace's trailing argument)
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA, class... XL>
 static hipError_t launch_kernel(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
-                                hipEvent_t e1) {
+                                hipEvent_t e1, const XL &...xl) {
     if (lds_bytes > 48 * 1024) { // more dynamic LDS than the default limit: opt in (up to 160 KiB per CU on gfx950)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA, XL...>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
     // e0/e1 (may be NULL) receive the dispatch's own begin/end timestamps: no marker packets on the stream
-    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
-                          P.kind, P.shade, P.prim, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.idtab, P.pre, P.pre_s);
+    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA, XL...>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
+                          P.kind, P.shade, P.prim, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.idtab, P.pre, P.pre_s, xl...);
     return hipGetLastError();
 }
-template <int SRC, bool REFL, bool REFR>
+template <int SRC, bool REFL, bool REFR, class... XL>
 static hipError_t launch_one(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
-                             hipEvent_t e1) {
-    if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false>(P, grid, lds_bytes, stream, e0, e1);
-    if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true>(P, grid, lds_bytes, stream, e0, e1);
-    return launch_kernel<SRC, REFL, REFR, false, false>(P, grid, lds_bytes, stream, e0, e1);
+                             hipEvent_t e1, const XL &...xl) {
+    if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
+    if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true>(P, grid, lds_bytes, stream, e0, e1, xl...);
+    return launch_kernel<SRC, REFL, REFR, false, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
 }
 
+// `xl`: NULL for a World with one light; else its lights 1..n-1 (xl->n >= 1), and src one of SRC_SMEM, SRC_CULL, SRC_CULL2.
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
-                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl) {
     const dim3 grid(nblocks);
-#define RTC_CASE(S)                                                                            \
+#define RTC_CASE(S, ...)                                                                            \
     if (src == S) {                                                                            \
-        if (refr) return launch_one<S, true, true>(*P, grid, lds_bytes, stream, e0, e1);               \
-        if (refl) return launch_one<S, true, false>(*P, grid, lds_bytes, stream, e0, e1);              \
-        return launch_one<S, false, false>(*P, grid, lds_bytes, stream, e0, e1);                       \
+        if (refr) return launch_one<S, true, true>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);               \
+        if (refl) return launch_one<S, true, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);              \
+        return launch_one<S, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);                       \
+    }
+    if (xl != nullptr) {
+        if (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u) return hipErrorInvalidValue;
+        RTC_CASE(SRC_SMEM, *xl)
+        RTC_CASE(SRC_CULL, *xl)
+        RTC_CASE(SRC_CULL2, *xl)
+        return hipErrorInvalidValue;
     }
     RTC_CASE(SRC_SMEM)
     RTC_CASE(SRC_LDS1)

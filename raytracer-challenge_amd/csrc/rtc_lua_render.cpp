@@ -175,6 +175,9 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
         rtc_lua_job job;
         st = rtc_lua_program_job(prog, i, &job);
         if (st != RTC_OK) break;
+        rtc_light lights[RTC_MAX_LIGHTS]; // every light of the job's world (job.light is lights[0])
+        uint32_t n_lights = 0;
+        if ((st = rtc_lua_program_job_lights(prog, i, lights, RTC_MAX_LIGHTS, &n_lights)) != RTC_OK) break;
         const size_t bytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
         Output out;
         if ((st = choose(entry, job, quality, &out)) != RTC_OK) break;
@@ -183,12 +186,12 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
         st = deliver(sl);
         if (st != RTC_OK || stop) break;
         if (!world) { // the program's first job
-            st = rtc_world_create(ctx, job.shapes, job.n_shapes, &job.light, &world);
+            st = rtc_world_create_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
             if (st != RTC_OK) break;
         } else if (!job.same_world_as_previous && ctx->world_update) {
             // other contents for the resident World, ordered like a launch: the frames in flight keep theirs, and the
             // outputs' ring is safe as it is (a slot is reused only after `depth` later launches)
-            st = rtc_world_update(ctx, world, job.shapes, job.n_shapes, &job.light);
+            st = rtc_world_update_lights(ctx, world, job.shapes, job.n_shapes, lights, n_lights);
             if (st != RTC_OK) break;
         } else if (!job.same_world_as_previous) { // RTC_WORLD_UPDATE=0, a new World: nothing may still read the old one
             st = drain(i);
@@ -196,7 +199,7 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
             if (st != RTC_OK || stop) break;
             rtc_world_destroy(world);
             world = nullptr;
-            st = rtc_world_create(ctx, job.shapes, job.n_shapes, &job.light, &world);
+            st = rtc_world_create_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
             if (st != RTC_OK) break;
         }
         if ((st = sl.d.reserve(bytes)) != RTC_OK) break;

@@ -10,7 +10,7 @@ SHINY = { ambient = 0.05, diffuse = 0.6, specular = 0.8, shininess = 120, reflec
 scene = {
    lights = {
       { color = { r = 1, g = 0.9, b = 0.8 }, position = { x = -6, y = 8.5, z = -4 } },
-      { color = { r = 1, g = 0, b = 0 }, position = { x = 5, y = 10, z = 10 } },   -- ignored: only lights[1] is read
+      { color = { r = 1, g = 0, b = 0 }, position = { x = 5, y = 10, z = 10 } },   -- the reference reads lights[1] only; rtc_lua_program_render shades with both
    },
    shapes = {
       { type = "plane",

@@ -288,6 +288,18 @@ class World { // shape.rs:633-795
         shapes.push_back(std::move(s));
         return *this;
     }
+    // Further lights (the reference's World holds a list and shades with the first, shape.rs:636,686; here every light
+    // contributes: rtc_world_create_lights). `light` stays the first; at most RTC_MAX_LIGHTS in all.
+    World &add_light(Light l) {
+        if (more_lights.size() + 2 > RTC_MAX_LIGHTS) check(RTC_ERR_ARG, "World::add_light");
+        more_lights.push_back(l);
+        return *this;
+    }
+    std::vector<Light> lights() const {
+        std::vector<Light> all{light};
+        all.insert(all.end(), more_lights.begin(), more_lights.end());
+        return all;
+    }
     Shape &get_shape_mut(size_t i) { dirty_ = true; return shapes.at(i); }
     const Shape &get_shape(size_t i) const { return shapes.at(i); }
 
@@ -301,6 +313,7 @@ class World { // shape.rs:633-795
     }
 
     Light light;
+    std::vector<Light> more_lights; // lights()[1..]
     std::vector<Shape> shapes;
     uint32_t last_world_id = 0;
 
@@ -318,10 +331,14 @@ class World { // shape.rs:633-795
                 f.material = s.material.flatten();
                 flat.push_back(f);
             }
-            rtc_light l;
-            l.intensity[0] = world.light.intensity.red; l.intensity[1] = world.light.intensity.green; l.intensity[2] = world.light.intensity.blue;
-            l.position[0] = world.light.position.x; l.position[1] = world.light.position.y; l.position[2] = world.light.position.z;
-            w = Resident::instance().get(std::move(flat), l);
+            std::vector<rtc_light> ls;
+            for (const Light &wl : world.lights()) {
+                rtc_light l;
+                l.intensity[0] = wl.intensity.red; l.intensity[1] = wl.intensity.green; l.intensity[2] = wl.intensity.blue;
+                l.position[0] = wl.position.x; l.position[1] = wl.position.y; l.position[2] = wl.position.z;
+                ls.push_back(l);
+            }
+            w = Resident::instance().get(std::move(flat), ls);
         }
         Uploaded(const Uploaded &) = delete;
         Uploaded &operator=(const Uploaded &) = delete;
@@ -332,19 +349,22 @@ class World { // shape.rs:633-795
             static Resident r;
             return r;
         }
-        rtc_world *get(std::vector<rtc_shape> &&flat, const rtc_light &l) {
-            const bool same = w_ != nullptr && flat.size() == flat_.size() && std::memcmp(&l, &light_, sizeof l) == 0 &&
+        rtc_world *get(std::vector<rtc_shape> &&flat, const rtc_light &l) { return get(std::move(flat), std::vector<rtc_light>{l}); }
+        rtc_world *get(std::vector<rtc_shape> &&flat, const std::vector<rtc_light> &ls) {
+            const uint32_t nl = static_cast<uint32_t>(ls.size());
+            const bool same = w_ != nullptr && flat.size() == flat_.size() && ls.size() == lights_.size() &&
+                              std::memcmp(ls.data(), lights_.data(), ls.size() * sizeof(rtc_light)) == 0 &&
                               (flat.empty() || std::memcmp(flat.data(), flat_.data(), flat.size() * sizeof(rtc_shape)) == 0);
             if (!same) {
                 // other contents for the World that is resident already (rtc_world_update: no destroy, no allocation while
                 // it does not grow); a rejected update leaves it as it was, and so does this cache
                 if (w_) {
-                    const rtc_status st = rtc_world_update(Device::get(), w_, flat.data(), static_cast<uint32_t>(flat.size()), &l);
-                    if (st == RTC_ERR_NOMEM || st == RTC_ERR_DEVICE) flat_.clear(), light_ = rtc_light{}; // a failed growing update: nothing is resident
+                    const rtc_status st = rtc_world_update_lights(Device::get(), w_, flat.data(), static_cast<uint32_t>(flat.size()), ls.data(), nl);
+                    if (st == RTC_ERR_NOMEM || st == RTC_ERR_DEVICE) flat_.clear(), lights_.clear(); // a failed growing update: nothing is resident
                     check(st, "World update");
-                } else check(rtc_world_create(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), &l, &w_), "World upload");
+                } else check(rtc_world_create_lights(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), ls.data(), nl, &w_), "World upload");
                 flat_ = std::move(flat);
-                light_ = l;
+                lights_ = ls;
             }
             return w_;
         }
@@ -354,7 +374,7 @@ class World { // shape.rs:633-795
         ~Resident() { if (w_) rtc_world_destroy(w_); }
         rtc_world *w_ = nullptr;
         std::vector<rtc_shape> flat_;
-        rtc_light light_{};
+        std::vector<rtc_light> lights_;
     };
   private:
     bool dirty_ = false;

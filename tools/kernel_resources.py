@@ -21,7 +21,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         return m.group(1) if m else "?"
     m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?", name)
     if m:
-        tag = "k_trace<%s,refl=%s,refr=%s,probe=%s" % m.groups()[:4] + (",rgba>" if m.group(5) == "1" else ">")
+        tag = "k_trace<%s,refl=%s,refr=%s,probe=%s" % m.groups()[:4] + (",rgba" if m.group(5) == "1" else "")
+        tag += ",multi>" if "DevExtraLights" in name else ">"  # the instantiations for Worlds with several lights
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
