@@ -554,6 +554,14 @@ DEVI unsigned long long ray_touches_pre_mask(V3 o, V3 d, double dd, const DevPre
 // cannot be bounded visits all 101 objects of the reflective north star — is not one scalar-load round trip per object
 // (profiles/r03_exp_unbounded_walks.log: those walks, 0.27 passes per wave, were a third of C4's kernel time).
 constexpr uint32_t PRE_BATCH = 2;
+// The one-level listed shadow pass (k_trace) takes this many entries of a lane's own cell list per step, their prefilter records
+// requested together. Measured 1 / 2 / 4 (profiles/r03_exp_lane_lists.log): 2 and 4 keep 16 / 32 more VGPRs of records live and
+// spill in the flat kernel (12 / 24 B per lane) — rejected for that alone — and are 2 % / 5 % slower on the north star, whose cells
+// list 0-2 objects; on C4 and the reflective 1080p frame 1 and 2 measure the same.
+#ifndef RTC_LANE_LIST_BATCH
+#define RTC_LANE_LIST_BATCH 1
+#endif
+constexpr uint32_t LANE_LIST_BATCH = RTC_LANE_LIST_BATCH;
 
 // ---- wave-uniform object loop ------------------------------------------------------------
 // f(j, m, kind, prim) is called for objects j = 0..n-1 in insertion order (World::intersect,
@@ -1433,45 +1441,24 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             Bundle Bs{};
             Bs.off = true;
             // Light-space shadow lists, small worlds (one-level cull): the cells' lists are a handful of objects, so they
-            // are the candidates themselves — no shadow bundle, no bound tests: per listed object (each once: a 256-bit
-            // wave-uniform "done" set, cells next to each other list the same objects) the per-lane prefilter and the
-            // exact test.
+            // are the candidates themselves — no shadow bundle, no bound tests. Every lane walks the list of ITS OWN cell
+            // (per-lane loads of the entries and of their prefilter records, LANE_LIST_BATCH at a time); only the exact
+            // test of a survivor is wave-level, its record fetched by uniform index.
             bool listed = false;
             if constexpr (SRC == SRC_CULL) {
                 const auto &Pl = KP(P_arg);
-                // (Pl.n <= 256: the "done" set below has one bit per object; a larger World only gets here with the one-level
-                // cull FORCED, RTC_SRC=3, and then takes the bundle walk)
-                if (Pl.light_cnt != nullptr && Pl.n <= 256u && ballot(hit) != 0ull && ballot(hit && !(sdist <= Pl.light_reach)) == 0ull) {
-                    static_assert(RTC_LIGHT_LIST_CAP_SMALL <= 16u, "a quarter of the wave holds one cell's list");
-                    // Round trips, not instructions, are what this path costs: the cells' counters come with ONE
-                    // per-lane load (every lane asks for its own cell's), the lists of up to four distinct cells with ONE more
-                    // (lanes 16c..16c+15 hold cell c's entries); only the listed objects' own records are fetched one by one.
+                // (light_cap == RTC_LIGHT_LIST_CAP_SMALL: a one-level World's own lists; a larger World only gets here with the
+                // one-level cull FORCED, RTC_SRC=3 — its 128-entry lists feed a filter step — and takes the bundle walk)
+                if (Pl.light_cnt != nullptr && Pl.light_cap == RTC_LIGHT_LIST_CAP_SMALL && ballot(hit) != 0ull && ballot(hit && !(sdist <= Pl.light_reach)) == 0ull) {
+                    constexpr uint32_t LB = LANE_LIST_BATCH;
+                    static_assert((LB == 1u || LB == 2u || LB == 4u) && RTC_LIGHT_LIST_CAP_SMALL % LB == 0u, "a batch of entries is one aligned vector load");
                     const uint32_t cid = hit ? light_cell(vneg(sdir)) : 0u;
-                    const uint32_t ccnt = hit ? Pl.light_cnt[cid] : 0u;
-                    // a cell whose list overflowed is incomplete; hit points scattered over more than four cells (shadow rays
-                    // of secondary hits) are served better by the bundle cull: fall back
-                    listed = ballot(hit && ccnt > Pl.light_cap) == 0ull && Pl.light_cap <= 16u;
-                    uint32_t cells[4] = {0u, 0u, 0u, 0u}, cnts[4] = {0u, 0u, 0u, 0u}, ncells = 0;
-                    for (unsigned long long todo = ballot(hit); todo && listed;) {
-                        const int l = (int)__builtin_ctzll(todo);
-                        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cid, l);
-                        todo &= ~ballot(hit && cid == c);
-                        if (ncells == 4u) { listed = false; break; }
-                        const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)ccnt, l);
-#pragma unroll
-                        for (uint32_t k = 0; k < 4u; ++k)
-                            if (k == ncells) { cells[k] = c; cnts[k] = cn; }
-                        ++ncells;
-                    }
+                    const uint32_t ccnt = hit ? Pl.light_cnt[cid] : 0u; // every lane its own cell's counter: one round trip
+                    listed = ballot(ccnt > Pl.light_cap) == 0ull;      // a cell whose list overflowed is incomplete: fall back
                     if (listed) {
                         for (uint32_t k = 0; k < Pl.n_unb && ballot(sh_pending) != 0ull; ++k) { // unbounded objects: never listed
                             if (sh_pending && occludes_world(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                         }
-                        const uint32_t ci = lane >> 4, ei = lane & 15u;
-                        const uint32_t myc = ci == 0u ? cells[0] : ci == 1u ? cells[1] : ci == 2u ? cells[2] : cells[3];
-                        const uint32_t mycnt = ci == 0u ? cnts[0] : ci == 1u ? cnts[1] : ci == 2u ? cnts[2] : cnts[3];
-                        const bool have = ci < ncells && ei < mycnt;
-                        const uint32_t ent = have ? Pl.light_list[(size_t)myc * Pl.light_cap + ei] : 0u;
                         // pre-inflated prefilter records hold while every origin is within their limit (DevPre)
                         bool pre_ok;
                         double sdd;
@@ -1480,21 +1467,54 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                             pre_ok = ballot(hit && !(fabs(over.x) + fabs(over.y) + fabs(over.z) <= Pl.pre_limit)) == 0ull;
                             sdd = sdir.x * sdir.x + sdir.y * sdir.y + sdir.z * sdir.z;
                         }
-                        unsigned long long done[4] = {0ull, 0ull, 0ull, 0ull}; // one bit per object (n <= 256): neighbouring cells list the same objects
-                        for (unsigned long long vm = ballot(have); vm && ballot(sh_pending) != 0ull;) {
-                            const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)ent, (int)__builtin_ctzll(vm));
-                            vm &= vm - 1ull;
-                            const unsigned long long bit = 1ull << (j & 63u);
-                            unsigned long long &word = done[(j >> 6) & 3u];
-                            if (word & bit) continue;
-                            word |= bit;
-                            bool t;
-                            if (pre_ok) { const DevPre q = T.pre[j]; t = ray_touches_pre(over, sdir, sdd, q); }
-                            else t = ray_touches(over, sdir, T.bound[j]);
-                            if (ballot(sh_pending & t) == 0ull) continue;
-                            const DevIsect rec = T.isect[j]; // record and kind requested together
-                            const uint32_t kd = T.kind[j];
-                            if (sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                        // Why the shadow bit is what the union walk over all the wave's cells gave: it is an any-hit; a cell's
+                        // list is conservative for EVERY segment of that cell (k_light_cells' cones), so an object that is not on
+                        // a lane's own list cannot occlude that lane, and the prefilter — the same conservative function on the
+                        // same operands — only drops objects the exact test would miss. Restricting the unchanged exact test of
+                        // object j to the lanes whose own list names j and whose prefilter keeps it therefore drops only tests
+                        // that cannot hit. A lane's list holds each object once: no "done" set, no limit on the number of cells.
+                        const uint32_t *mylist = Pl.light_list + (size_t)cid * RTC_LIGHT_LIST_CAP_SMALL;
+                        for (uint32_t k0 = 0; ballot(sh_pending && k0 < ccnt) != 0ull; k0 += LB) {
+                            uint32_t ent[LB]; // (all lanes load: k0 + LB <= the cap, no branch around the loads; entries past the counter are masked)
+                            if constexpr (LB == 4u) { const uint4 v = *reinterpret_cast<const uint4 *>(mylist + k0); ent[0] = v.x; ent[1] = v.y; ent[2] = v.z; ent[3] = v.w; }
+                            else if constexpr (LB == 2u) { const uint2 v = *reinterpret_cast<const uint2 *>(mylist + k0); ent[0] = v.x; ent[1] = v.y; }
+                            else ent[0] = mylist[k0];
+                            bool todo[LB];
+#pragma unroll
+                            for (uint32_t b = 0; b < LB; ++b) {
+                                todo[b] = sh_pending && k0 + b < ccnt;
+                                if (!todo[b]) ent[b] = 0u;
+                            }
+                            if (pre_ok) {
+                                DevPre q[LB]; // the records of the batch are requested together, ahead of the tests
+#pragma unroll
+                                for (uint32_t b = 0; b < LB; ++b) q[b] = T.pre[ent[b]];
+#pragma unroll
+                                for (uint32_t b = 0; b < LB; ++b) todo[b] = todo[b] && ray_touches_pre(over, sdir, sdd, q[b]);
+                            } else {
+#pragma unroll
+                                for (uint32_t b = 0; b < LB; ++b) todo[b] = todo[b] && ray_touches(over, sdir, T.bound[ent[b]]);
+                            }
+                            // survivors: one object at a time, for every lane of the batch that still has it to test
+                            for (;;) {
+                                bool any = false;
+                                uint32_t mine = 0u;
+#pragma unroll
+                                for (uint32_t b = LB; b-- > 0u;) {
+                                    if (todo[b]) { any = true; mine = ent[b]; }
+                                }
+                                const unsigned long long m = ballot(any && sh_pending);
+                                if (m == 0ull) break;
+                                const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)__builtin_ctzll(m));
+                                const DevIsect rec = T.isect[j]; // record and kind requested together
+                                const uint32_t kd = T.kind[j];
+                                bool sel = false;
+#pragma unroll
+                                for (uint32_t b = 0; b < LB; ++b) {
+                                    if (todo[b] && ent[b] == j) { sel = true; todo[b] = false; }
+                                }
+                                if (sel && sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                            }
                         }
                     }
                 }
