@@ -326,9 +326,36 @@ rtc_status  rtc_scene_load_lua_lights_file(const char *path, uint32_t render_ind
                                            rtc_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
                                            rtc_camera *camera_out, char *outfile, size_t outfile_len,
                                            uint32_t *renders_out, char *errbuf, size_t errbuf_len);
-/* Every light of job `index` (rtc_lua_job::light is lights_out[0]). RTC_ERR_ARG when cap is too small. */
+/* Every light of job `index` (rtc_lua_job::light is lights_out[0]). RTC_ERR_ARG when cap is too small. RTC_ERR_PARSE
+ * (there is no message buffer here) when the job's world has an area light: rtc_lua_program_job_area_lights hands those
+ * out; rtc_lua_job::light is then the area light's first sample. */
 rtc_status  rtc_lua_program_job_lights(const rtc_lua_program *prog, uint32_t index, rtc_light *lights_out, uint32_t cap,
                                        uint32_t *n_out);
+/* Scenes with area lights (struct rtc_area_light, below). YAML: an `add: light` entry with corner / uvec / vvec / usteps
+ * / vsteps / intensity (the book's vocabulary; `jitter: false` is accepted, `jitter: true` is RTC_ERR_PARSE: not
+ * supported; `at` together with `corner` is a parse error). Lua: an element of world.lights with the keys corner, uvec,
+ * vvec, usteps, vsteps (Lua integers, by the rules of the camera's `samples`) beside `color`. These entries return every
+ * light as an rtc_area_light, point lights as the degenerate case; a scene with an area light may hold up to
+ * RTC_MAX_LIGHT_SAMPLES samples (more: RTC_ERR_PARSE with a message), one of point lights only RTC_MAX_LIGHTS lights as
+ * before. The entries above return RTC_ERR_PARSE for a scene with an area light, with a message naming these. */
+struct rtc_area_light;
+rtc_status  rtc_scene_load_yaml_area_lights(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                            struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                            rtc_camera *camera_out, char *errbuf, size_t errbuf_len);
+rtc_status  rtc_scene_load_yaml_area_lights_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                                 struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                                 rtc_camera *camera_out, char *errbuf, size_t errbuf_len);
+rtc_status  rtc_scene_load_lua_area_lights(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                                           struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                           rtc_camera *camera_out, char *outfile, size_t outfile_len,
+                                           uint32_t *renders_out, char *errbuf, size_t errbuf_len);
+rtc_status  rtc_scene_load_lua_area_lights_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                                                struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                                rtc_camera *camera_out, char *outfile, size_t outfile_len,
+                                                uint32_t *renders_out, char *errbuf, size_t errbuf_len);
+/* Every light of job `index` as an area light. RTC_ERR_ARG when cap is too small. */
+rtc_status  rtc_lua_program_job_area_lights(const rtc_lua_program *prog, uint32_t index, struct rtc_area_light *lights_out,
+                                            uint32_t cap, uint32_t *n_out);
 void        rtc_free(void *p);
 
 /* Canvas::write_to_file_simple: ASCII PPM P3 (canvas.rs:86-109) with Color::scale's
@@ -599,7 +626,49 @@ rtc_status  rtc_world_create_lights(rtc_context *ctx, const rtc_shape *shapes, u
                                     const rtc_light *lights, uint32_t n_lights, rtc_world **out);
 rtc_status  rtc_world_update_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n_shapes,
                                     const rtc_light *lights, uint32_t n_lights);
-uint32_t    rtc_world_light_count(const rtc_world *w); /* 0 for NULL */
+uint32_t    rtc_world_light_count(const rtc_world *w); /* 0 for NULL; the number of SAMPLES of a World of area lights */
+
+/* Area lights: soft shadows. An area light is a rectangle (`corner`, full edge vectors `uvec`, `vvec`) sampled at the
+ * centres of a usteps x vsteps grid of cells — the book's area light, written in scene files as corner / uvec / vvec /
+ * usteps / vsteps / intensity. It IS exactly usteps*vsteps point lights in the multi-light semantics above: every term
+ * carries its own ambient part, terms are summed in f64 in sample order. The arithmetic is f64 without fused
+ * multiply-add, in this order, per component:
+ *     ucell = uvec / (double)usteps          vcell = vvec / (double)vsteps
+ *     for v in 0..vsteps { for u in 0..usteps {
+ *         position  = (corner + ucell*(u + 0.5)) + vcell*(v + 0.5)
+ *         intensity = intensity / (double)(usteps*vsteps) } }
+ * A point light is the degenerate case corner = position, uvec = vvec = 0, 1x1: its single sample is that point light
+ * bit for bit. A World's lights are a list of rtc_area_light; its sample list is the concatenation of the expansions in
+ * list order, 1..RTC_MAX_LIGHT_SAMPLES samples in all. rtc_area_light_expand is the normative sample list.
+ * NO JITTER: samples sit at the cell centres. (The book's jittered form draws a random offset per hit; that is not
+ * expressible through the single-light oracle the frames are checked against, and is out of scope.) */
+typedef struct rtc_area_light {
+    double   intensity[3];
+    double   corner[3], uvec[3], vvec[3];   /* full edge vectors of the rectangle */
+    uint32_t usteps, vsteps;                /* >= 1 each */
+} rtc_area_light;
+#define RTC_MAX_LIGHT_SAMPLES 256u
+/* [host] The degenerate area light of a point light. */
+rtc_status  rtc_area_light_from_point(const rtc_light *light, rtc_area_light *out);
+/* [host] The sample list of lights[0..n) into out[0..*n_out). RTC_ERR_ARG (and *n_out = 0): a NULL pointer, n == 0, a
+ * step count of 0, more than RTC_MAX_LIGHT_SAMPLES samples in all, or more than `cap`. */
+rtc_status  rtc_area_light_expand(const rtc_area_light *lights, uint32_t n, rtc_light *out, uint32_t cap, uint32_t *n_out);
+/* [device] rtc_world_create_lights / rtc_world_update_lights for a list of area lights: the same validation (plus
+ * rtc_area_light_expand's), ordering and no-allocation promises; the number of samples may change between updates.
+ * An expansion of at most RTC_MAX_LIGHTS samples IS the rtc_world_create_lights World of the expanded list: the same
+ * kernels, the same kernel-argument path, the same bytes. Above that, samples 1..n-1 live in a device table of 6 doubles
+ * per sample — one per World generation, sized for RTC_MAX_LIGHT_SAMPLES when the World is created and written in stream
+ * order with the World's other tables — which k_trace's light loop reads instead of its kernel arguments
+ * (rtc_launch_info::light_table). Sample 0 keeps the World's light-space shadow lists; rtc_hit::shadowed stays sample
+ * 0's; rtc_stats::rays_shadow counts one ray per sample per shade_hit. Every render entry takes such a World unchanged
+ * (as above); RTC_FLAG_LDS_TABLE is RTC_ERR_UNSUPPORTED, RTC_FLAG_NO_CULL renders it through the scalar-cache brute
+ * force, bit-identical to the culled frame. rtc_group_world_* stays single-light. The environment switch
+ * RTC_LIGHT_TABLE=1 (measurement only, read at rtc_context_create) sends Worlds of 2..RTC_MAX_LIGHTS lights through the
+ * table kernels too. */
+rtc_status  rtc_world_create_area_lights(rtc_context *ctx, const rtc_shape *shapes, uint32_t n_shapes,
+                                         const rtc_area_light *lights, uint32_t n_lights, rtc_world **out);
+rtc_status  rtc_world_update_area_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n_shapes,
+                                         const rtc_area_light *lights, uint32_t n_lights);
 
 /* Camera::render / render_async for canvas rows [y0, y1) into a DEVICE buffer of
  * (y1-y0)*hsize*3 doubles (row y0 first). Enqueues on the context stream and returns
@@ -858,7 +927,9 @@ typedef struct rtc_launch_info {
                                      then two tiles each (a tile's stores drain under the next one) and the launch ends with
                                      single-tile workgroups (a short tail); this many render more than one. 0: none
                                      (RTC_TILES_GUIDED, RTC_TILES_KMAX)                                                  */
-    uint32_t _reserved[2];
+    uint32_t light_table; /* 1: the launch read lights 1..n-1 from the World's device table (more than RTC_MAX_LIGHTS
+                             samples, or RTC_LIGHT_TABLE=1), 0: from its kernel arguments / a one-light World           */
+    uint32_t _reserved[1];
 } rtc_launch_info;
 rtc_status  rtc_context_last_launch_info(rtc_context *ctx, rtc_launch_info *out);
 

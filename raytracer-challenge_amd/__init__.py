@@ -17,9 +17,9 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
-                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, PATTERNS, STATUS_NAMES, declare)
+                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, PATTERNS, STATUS_NAMES, declare)
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librtc.so"
@@ -182,15 +182,35 @@ def light(position=(-10.0, 10.0, -10.0), intensity=(1.0, 1.0, 1.0)) -> RtcLight:
     return l
 
 
+def area_light(corner, uvec, vvec, usteps: int, vsteps: int, intensity=(1.0, 1.0, 1.0)) -> RtcAreaLight:
+    """The book's area light: the rectangle corner + s*uvec + t*vvec sampled at the centres of usteps x vsteps cells
+    (rtc_area_light, include/rtc.h; no jitter)."""
+    a = RtcAreaLight()
+    for i in range(3):
+        a.corner[i], a.uvec[i], a.vvec[i], a.intensity[i] = float(corner[i]), float(uvec[i]), float(vvec[i]), float(intensity[i])
+    a.usteps, a.vsteps = int(usteps), int(vsteps)
+    return a
+
+
+def _copy_light(l):
+    """A loader's light as the binding's: the degenerate 1x1 area light of a point light becomes an RtcLight."""
+    if l.usteps == 1 and l.vsteps == 1 and not any(l.uvec) and not any(l.vvec):
+        return light(position=tuple(l.corner), intensity=tuple(l.intensity))
+    a = RtcAreaLight()
+    C.memmove(C.byref(a), C.byref(l), C.sizeof(RtcAreaLight))
+    return a
+
+
 class World:
-    """World (shape.rs:633-637): host-side list of shapes + 1..MAX_LIGHTS lights (one RtcLight or a list of them);
-    `add_shape` assigns world ids like the reference (shape.rs:661-667). `light` is `lights[0]`, the one the reference
-    shades with; a DeviceWorld shades with all of them (rtc_world_create_lights)."""
+    """World (shape.rs:633-637): host-side list of shapes + lights (one light or a list of them, RtcLight point lights and
+    RtcAreaLight area lights in any mix, 1..MAX_LIGHT_SAMPLES samples in all); `add_shape` assigns world ids like the
+    reference (shape.rs:661-667). `light` is `lights[0]`, the one the reference shades with; a DeviceWorld shades with
+    all of them (rtc_world_create_lights / rtc_world_create_area_lights)."""
 
     def __init__(self, lgt=None):
         if lgt is None:
             self.lights: list[RtcLight] = [light()]
-        elif isinstance(lgt, RtcLight):
+        elif isinstance(lgt, (RtcLight, RtcAreaLight)):
             self.lights = [lgt]
         else:
             self.lights = list(lgt)
@@ -213,6 +233,26 @@ class World:
         for i, l in enumerate(self.lights):
             arr[i] = l
         return arr
+
+    def needs_area_entries(self) -> bool:
+        """An area light, or more point lights than rtc_world_create_lights takes."""
+        return len(self.lights) > MAX_LIGHTS or any(isinstance(l, RtcAreaLight) for l in self.lights)
+
+    def area_light_array(self):
+        """Every light as an rtc_area_light (point lights: the degenerate 1x1 case)."""
+        arr = (RtcAreaLight * max(1, len(self.lights)))()
+        for i, l in enumerate(self.lights):
+            if isinstance(l, RtcAreaLight):
+                arr[i] = l
+            else:
+                _check(lib().rtc_area_light_from_point(C.byref(l), C.byref(arr[i])), "rtc_area_light_from_point")
+        return arr
+
+    def samples(self) -> list:
+        """The World's sample list: the point lights a DeviceWorld shades with (rtc_area_light_expand)."""
+        out, n = (RtcLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0)
+        _check(lib().rtc_area_light_expand(self.area_light_array(), len(self.lights), out, MAX_LIGHT_SAMPLES, C.byref(n)), "rtc_area_light_expand")
+        return _copy_lights(out, n.value)
 
     def add_shape(self, s: RtcShape) -> "World":
         s.world_id = len(self.shapes) + 1
@@ -265,14 +305,14 @@ def load_yaml(text: str | None = None, path: str | None = None):
     """jamis.yml-vocabulary loader -> (World, RtcCamera); the World holds every `add: light` of the file."""
     shapes = C.POINTER(RtcShape)()
     n = C.c_uint32(0)
-    lgts, nl, cam = (RtcLight * MAX_LIGHTS)(), C.c_uint32(0), RtcCamera()
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
     err = C.create_string_buffer(512)
     if path is not None:
-        st = lib().rtc_scene_load_yaml_lights_file(str(path).encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl), C.byref(cam), err, 512)
+        st = lib().rtc_scene_load_yaml_area_lights_file(str(path).encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512)
     else:
-        st = lib().rtc_scene_load_yaml_lights(text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl), C.byref(cam), err, 512)
+        st = lib().rtc_scene_load_yaml_area_lights(text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512)
     _check(st, "rtc_scene_load_yaml", err.value.decode(errors="replace"))
-    w = World(_copy_lights(lgts, nl.value))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
     for i in range(n.value):
         s = RtcShape()
         C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
@@ -346,9 +386,9 @@ class LuaProgram:
     def job(self, index: int) -> LuaJob:
         j = RtcLuaJob()
         _check(lib().rtc_lua_program_job(self._h, index, C.byref(j)), "rtc_lua_program_job")
-        lgts, nl = (RtcLight * MAX_LIGHTS)(), C.c_uint32(0)
-        _check(lib().rtc_lua_program_job_lights(self._h, index, lgts, MAX_LIGHTS, C.byref(nl)), "rtc_lua_program_job_lights")
-        return LuaJob(j, index, _copy_lights(lgts, nl.value))
+        lgts, nl = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0)
+        _check(lib().rtc_lua_program_job_area_lights(self._h, index, lgts, MAX_LIGHT_SAMPLES, C.byref(nl)), "rtc_lua_program_job_area_lights")
+        return LuaJob(j, index, [_copy_light(lgts[i]) for i in range(nl.value)])
 
     @property
     def jobs(self):
@@ -582,16 +622,16 @@ def load_lua(text: str | None = None, path: str | None = None, render_index: int
     """One job of a Lua scene script (rtc_scene_load_lua) -> (World, RtcCamera, outfile, n_jobs)."""
     shapes = C.POINTER(RtcShape)()
     n, renders = C.c_uint32(0), C.c_uint32(0)
-    lgts, nl, cam = (RtcLight * MAX_LIGHTS)(), C.c_uint32(0), RtcCamera()
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
     err, outfile = C.create_string_buffer(512), C.create_string_buffer(512)
     if path is not None:
-        st = lib().rtc_scene_load_lua_lights_file(str(path).encode(), render_index, C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl),
-                                                  C.byref(cam), outfile, 512, C.byref(renders), err, 512)
+        st = lib().rtc_scene_load_lua_area_lights_file(str(path).encode(), render_index, C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl),
+                                                       C.byref(cam), outfile, 512, C.byref(renders), err, 512)
     else:
-        st = lib().rtc_scene_load_lua_lights(text.encode(), render_index, C.byref(shapes), C.byref(n), lgts, MAX_LIGHTS, C.byref(nl),
-                                             C.byref(cam), outfile, 512, C.byref(renders), err, 512)
+        st = lib().rtc_scene_load_lua_area_lights(text.encode(), render_index, C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl),
+                                                  C.byref(cam), outfile, 512, C.byref(renders), err, 512)
     _check(st, "rtc_scene_load_lua", err.value.decode(errors="replace"))
-    w = World(_copy_lights(lgts, nl.value))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
     for i in range(n.value):
         s = RtcShape()
         C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
@@ -962,7 +1002,8 @@ class Context:
         return {"source": i.source, "source_name": SOURCE_NAMES.get(i.source, "?"), "reflective": bool(i.reflective),
                 "refractive": bool(i.refractive), "binned_primary_pass": bool(i.binned), "light_lists": bool(i.light_lists),
                 "lane": i.lane, "threads_per_workgroup": i.block, "dynamic_lds_bytes": i.lds_bytes,
-                "tiles_per_workgroup": i.tiles_per_workgroup, "multi_tile_workgroups": i.multi_tile_workgroups}
+                "tiles_per_workgroup": i.tiles_per_workgroup, "multi_tile_workgroups": i.multi_tile_workgroups,
+                "light_table": bool(i.light_table)}
 
     def binning_times_ms(self, last: int = 1024) -> np.ndarray:
         """Durations (ms) of the binning kernels of the most recent `last` timed launches (0 where a launch had none)."""
@@ -1017,8 +1058,12 @@ class DeviceWorld:
         self.ctx = ctx
         self._h = C.c_void_p()
         arr = world.array()
-        _check(lib().rtc_world_create_lights(ctx._h, arr, len(world.shapes), world.light_array(), len(world.lights), C.byref(self._h)),
-               "rtc_world_create_lights")
+        if world.needs_area_entries():
+            _check(lib().rtc_world_create_area_lights(ctx._h, arr, len(world.shapes), world.area_light_array(), len(world.lights), C.byref(self._h)),
+                   "rtc_world_create_area_lights")
+        else:
+            _check(lib().rtc_world_create_lights(ctx._h, arr, len(world.shapes), world.light_array(), len(world.lights), C.byref(self._h)),
+                   "rtc_world_create_lights")
         self.n = len(world.shapes)
         ctx._worlds.append(weakref.ref(self))
 
@@ -1026,8 +1071,12 @@ class DeviceWorld:
         """Replace the resident World's contents by `world` (rtc_world_update): ordered like a launch, rebuilt on the
         device, no allocation while the World does not grow."""
         arr = world.array()
-        _check(lib().rtc_world_update_lights(self.ctx._h, self._h, arr, len(world.shapes), world.light_array(), len(world.lights)),
-               "rtc_world_update_lights")
+        if world.needs_area_entries():
+            _check(lib().rtc_world_update_area_lights(self.ctx._h, self._h, arr, len(world.shapes), world.area_light_array(), len(world.lights)),
+                   "rtc_world_update_area_lights")
+        else:
+            _check(lib().rtc_world_update_lights(self.ctx._h, self._h, arr, len(world.shapes), world.light_array(), len(world.lights)),
+                   "rtc_world_update_lights")
         self.n = len(world.shapes)
 
     def close(self):
@@ -1327,6 +1376,8 @@ class GroupWorld:
     def __init__(self, group: Group, world: World):
         self.group = group
         self._h = C.c_void_p()
+        if not isinstance(world.light, RtcLight):
+            raise ValueError("group worlds are lit by a single point light: world.light is an area light (rtc_group_world_* stays single-light)")
         _check(lib().rtc_group_world_create(group._h, world.array(), len(world.shapes), C.byref(world.light), C.byref(self._h)),
                "rtc_group_world_create")
         group._worlds.append(weakref.ref(self))
@@ -1413,8 +1464,8 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "World", "camera", "ray_for_pixel",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel",
            "load_yaml", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",
-           "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcMaterial", "RtcShape", "RtcStats"]
+           "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcMaterial", "RtcShape", "RtcStats"]

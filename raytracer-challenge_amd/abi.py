@@ -13,6 +13,7 @@ EXCHANGE_RCCL, EXCHANGE_P2P = 0, 1
 GATHER_NONE, GATHER_F64, GATHER_U8 = 0, 1, 2
 GROUP_ID_BYTES = 128
 MAX_LIGHTS = 8
+MAX_LIGHT_SAMPLES = 256
 PATTERNS = {"none": 0, "test": 1, "stripe": 2, "stripes": 2, "gradient": 3, "ring": 4, "checker": 5, "checkers": 5, "grid": 6}
 STATUS_NAMES = {0: "RTC_OK", 1: "RTC_ERR_SINGULAR", 2: "RTC_ERR_NO_COLOR", 3: "RTC_ERR_DEVICE", 4: "RTC_ERR_ARG",
                 5: "RTC_ERR_PARSE", 6: "RTC_ERR_IO", 7: "RTC_ERR_NOMEM", 8: "RTC_ERR_UNSUPPORTED"}
@@ -31,6 +32,10 @@ class RtcShape(C.Structure):
 
 class RtcLight(C.Structure):
     _fields_ = [("intensity", Vec3), ("position", Vec3)]
+
+
+class RtcAreaLight(C.Structure):
+    _fields_ = [("intensity", Vec3), ("corner", Vec3), ("uvec", Vec3), ("vvec", Vec3), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
 
 
 class RtcCamera(C.Structure):
@@ -54,7 +59,7 @@ class RtcHit(C.Structure):
 class RtcLaunchInfo(C.Structure):
     _fields_ = [("source", C.c_uint32), ("reflective", C.c_uint32), ("refractive", C.c_uint32), ("binned", C.c_uint32),
                 ("light_lists", C.c_uint32), ("lane", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint32),
-                ("tiles_per_workgroup", C.c_uint32), ("multi_tile_workgroups", C.c_uint32), ("_reserved", C.c_uint32 * 2)]
+                ("tiles_per_workgroup", C.c_uint32), ("multi_tile_workgroups", C.c_uint32), ("light_table", C.c_uint32), ("_reserved", C.c_uint32 * 1)]
 
 
 class RtcLuaJob(C.Structure):
@@ -78,6 +83,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
                 2: "brute force, object table staged in LDS tiles", 3: "one-level per-wave cull", 4: "two-level per-wave cull"}
 
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
+assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -174,6 +180,17 @@ PROTOTYPES = {
     "rtc_scene_load_lua_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_lua_program_job_lights": (C.c_int32, [C.c_void_p, U32, C.POINTER(RtcLight), U32, C.POINTER(U32)]),
+    "rtc_area_light_from_point": (C.c_int32, [C.POINTER(RtcLight), C.POINTER(RtcAreaLight)]),
+    "rtc_area_light_expand": (C.c_int32, [C.POINTER(RtcAreaLight), U32, C.POINTER(RtcLight), U32, C.POINTER(U32)]),
+    "rtc_scene_load_yaml_area_lights": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_yaml_area_lights_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                         C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_lua_area_lights": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_lua_area_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_lua_program_job_area_lights": (C.c_int32, [C.c_void_p, U32, C.POINTER(RtcAreaLight), U32, C.POINTER(U32)]),
     "rtc_free": (None, [VP]),
     "rtc_canvas_write_ppm": (C.c_int32, [C.c_char_p, PD, U32, U32]),
     "rtc_canvas_format_ppm": (C.c_size_t, [PD, U32, U32, C.c_char_p, C.c_size_t]),
@@ -189,6 +206,8 @@ PROTOTYPES = {
     "rtc_world_create_lights": (C.c_int32, [VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight), U32, C.POINTER(VP)]),
     "rtc_world_update_lights": (C.c_int32, [VP, VP, C.POINTER(RtcShape), U32, C.POINTER(RtcLight), U32]),
     "rtc_world_light_count": (U32, [VP]),
+    "rtc_world_create_area_lights": (C.c_int32, [VP, C.POINTER(RtcShape), U32, C.POINTER(RtcAreaLight), U32, C.POINTER(VP)]),
+    "rtc_world_update_area_lights": (C.c_int32, [VP, VP, C.POINTER(RtcShape), U32, C.POINTER(RtcAreaLight), U32]),
     "rtc_world_destroy": (None, [VP]),
     "rtc_render_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),
     "rtc_render_bands": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),

@@ -35,7 +35,7 @@
 //     ("Invalid material property"); then a shape-level `color` (or else `pattern`) overrides, silently ignored when malformed;
 //   * pattern_from_table (lua.rs:109-143): "checks" / "stripes" with color_a, color_b; "grid" = white on black; the pattern
 //     table's own rotate_* / scale / position are its transform;
-//   * lights: every element of world.lights, at most RTC_MAX_LIGHTS (the reference converts the list and shades with lights[1]
+//   * lights: every element of world.lights, point or area lights (rtc_area_light, include/rtc.h), at most RTC_MAX_LIGHTS point lights (the reference converts the list and shades with lights[1]
 //     only, lua.rs:148-150, shape.rs:686); camera: screenwidth, screenheight (Lua INTEGERS, lua.rs:158-170), position,
 //     lookat, up, fov, optional samples (integer 0..255, lua.rs:172-183);
 //   * shapes: "sphere" | "plane" | "cube" through *::new_with_transform_and_material, world ids as World::add_shape.
@@ -825,8 +825,9 @@ struct Function {
 
 struct SceneData {
     std::vector<rtc_shape> shapes;
-    rtc_light light;               // lights[1]
-    std::vector<rtc_light> lights; // every element of world.lights, lights[1] first
+    rtc_light light;               // lights[1] (an area light: its first sample)
+    std::vector<rtc_area_light> lights; // every element of world.lights, lights[1] first; a point light is the degenerate 1x1 area light
+    bool any_area = false;         // some element has the area light's keys (corner, uvec, vvec, usteps, vsteps)
 };
 struct Job {
     std::shared_ptr<SceneData> scene; // shared with the previous job when the converted world is identical
@@ -1589,7 +1590,7 @@ struct Interp {
         if (!jobs.empty()) { // an animation usually renders one world from many cameras: keep one copy
             const SceneData &prev = *jobs.back().scene;
             if (prev.shapes.size() == sc->shapes.size() && prev.lights.size() == sc->lights.size() &&
-                std::memcmp(prev.lights.data(), sc->lights.data(), sizeof(rtc_light) * sc->lights.size()) == 0 &&
+                std::memcmp(prev.lights.data(), sc->lights.data(), sizeof(rtc_area_light) * sc->lights.size()) == 0 &&
                 (sc->shapes.empty() || std::memcmp(prev.shapes.data(), sc->shapes.data(), sizeof(rtc_shape) * sc->shapes.size()) == 0)) {
                 sc = jobs.back().scene;
                 j.same_world = true;
@@ -2041,18 +2042,45 @@ void camera_from_table(const Table &t, rtc_camera &cam, int line) { // lua.rs:24
 void world_from_table(const Table &t, SceneData &sc, int line) { // lua.rs:293-330
     const Table &lights = table_of(t.get("lights"), "world.lights", line);
     // lights_from_table converts the sequence; the reference then shades with the first only (shape.rs:686), this library with all
+    // a world of point lights holds RTC_MAX_LIGHTS of them, as ever; one with an area light RTC_MAX_LIGHT_SAMPLES samples
+    for (long long k = 1;; ++k) {
+        const Value *lv = lights.at(k);
+        if (!lv) break;
+        if (lv->kind == Value::Tab && lv->t->get("corner")) sc.any_area = true;
+    }
+    unsigned long long samples = 0;
     for (long long k = 1;; ++k) {
         const Value *lv = lights.at(k);
         if (!lv && k > 1) break;
         const Table &lt = table_of(lv, k == 1 ? "world.lights[1]" : "a light", line);
-        if (sc.lights.size() == RTC_MAX_LIGHTS) fail(line, "too many lights: a world holds at most " + std::to_string(RTC_MAX_LIGHTS));
-        rtc_light l;
+        if (!sc.any_area && sc.lights.size() == RTC_MAX_LIGHTS) fail(line, "too many lights: a world holds at most " + std::to_string(RTC_MAX_LIGHTS));
+        rtc_area_light l;
         std::memset(&l, 0, sizeof l);
+        l.usteps = l.vsteps = 1u;
         xyz(table_of(lt.get("color"), "light color", line), "r", "g", "b", l.intensity, "light color", line);
-        xyz(table_of(lt.get("position"), "light position", line), "x", "y", "z", l.position, "light position", line);
+        if (lt.get("corner")) { // the book's area light; the steps are Lua integers (the rules of the camera's `samples`)
+            if (lt.get("position")) fail(line, "a light has either 'position' (point light) or 'corner' (area light), not both");
+            xyz(table_of(lt.get("corner"), "light corner", line), "x", "y", "z", l.corner, "light corner", line);
+            xyz(table_of(lt.get("uvec"), "light uvec", line), "x", "y", "z", l.uvec, "light uvec", line);
+            xyz(table_of(lt.get("vvec"), "light vvec", line), "x", "y", "z", l.vvec, "light vvec", line);
+            l.usteps = static_cast<uint32_t>(integer_value(lt.get("usteps"), "usteps", 1, RTC_MAX_LIGHT_SAMPLES, line));
+            l.vsteps = static_cast<uint32_t>(integer_value(lt.get("vsteps"), "vsteps", 1, RTC_MAX_LIGHT_SAMPLES, line));
+            if (const Value *j = lt.get("jitter"))
+                if (j->kind != Value::Bool || j->b) fail(line, "jitter is not supported: area light samples sit at the cell centres");
+        } else {
+            xyz(table_of(lt.get("position"), "light position", line), "x", "y", "z", l.corner, "light position", line);
+        }
+        samples += static_cast<unsigned long long>(l.usteps) * l.vsteps;
+        if (samples > RTC_MAX_LIGHT_SAMPLES)
+            fail(line, "too many light samples: a world holds at most " + std::to_string(RTC_MAX_LIGHT_SAMPLES) + " (usteps x vsteps, summed over its lights)");
         sc.lights.push_back(l);
     }
-    sc.light = sc.lights[0];
+    {
+        rtc_light first[RTC_MAX_LIGHT_SAMPLES];
+        uint32_t nf = 0;
+        if (rtc_area_light_expand(sc.lights.data(), 1u, first, RTC_MAX_LIGHT_SAMPLES, &nf) != RTC_OK) fail(line, "world.lights[1] cannot be sampled");
+        sc.light = first[0];
+    }
     const Table &shapes = table_of(t.get("shapes"), "world.shapes", line);
     for (long long k = 1;; ++k) { // sequence_values: 1, 2, ... until the first nil
         const Value *sv = shapes.at(k);
@@ -2171,9 +2199,28 @@ rtc_status rtc_lua_program_job(const rtc_lua_program *prog, uint32_t index, rtc_
     return RTC_OK;
 }
 
+static rtc_light point_of(const rtc_area_light &a) { // a point light: corner = position, 1x1
+    rtc_light l;
+    for (int k = 0; k < 3; ++k) { l.position[k] = a.corner[k]; l.intensity[k] = a.intensity[k]; }
+    return l;
+}
+
+// (a job whose world has an area light: RTC_ERR_PARSE — rtc_lua_program_job_area_lights hands its lights out)
 rtc_status rtc_lua_program_job_lights(const rtc_lua_program *prog, uint32_t index, rtc_light *lights_out, uint32_t cap, uint32_t *n_out) {
     if (!prog || !lights_out || !n_out || index >= prog->in.jobs.size()) return RTC_ERR_ARG;
-    const std::vector<rtc_light> &l = prog->in.jobs[index].scene->lights;
+    const std::vector<rtc_area_light> &l = prog->in.jobs[index].scene->lights;
+    *n_out = 0;
+    if (prog->in.jobs[index].scene->any_area) return RTC_ERR_PARSE;
+    if (l.size() > cap) return RTC_ERR_ARG;
+    for (size_t i = 0; i < l.size(); ++i) lights_out[i] = point_of(l[i]);
+    *n_out = static_cast<uint32_t>(l.size());
+    return RTC_OK;
+}
+
+rtc_status rtc_lua_program_job_area_lights(const rtc_lua_program *prog, uint32_t index, rtc_area_light *lights_out, uint32_t cap,
+                                           uint32_t *n_out) {
+    if (!prog || !lights_out || !n_out || index >= prog->in.jobs.size()) return RTC_ERR_ARG;
+    const std::vector<rtc_area_light> &l = prog->in.jobs[index].scene->lights;
     *n_out = 0;
     if (l.size() > cap) return RTC_ERR_ARG;
     for (size_t i = 0; i < l.size(); ++i) lights_out[i] = l[i];
@@ -2186,9 +2233,10 @@ const char *rtc_lua_program_output(const rtc_lua_program *prog) { return prog ? 
 void rtc_lua_program_free(rtc_lua_program *prog) { delete prog; }
 
 // The single-scene form: run the script, hand out one of its jobs as malloc'ed arrays.
-// lights_cap == 0: the single-light form, *light_out = lights[1]
+// lights_cap == 0: the single-light form, *light_out = lights[1]. area_out (instead of light_out): every light as an rtc_area_light
 static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *light_out,
-                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
+                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len,
+                           rtc_area_light *area_out = nullptr) {
     std::unique_ptr<rtc_lua_program> own(prog);
     Interp &in = prog->in;
     try {
@@ -2203,6 +2251,7 @@ static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_sha
         }
         const Job &j = in.jobs[render_index];
         if (outfile && outfile_len) std::snprintf(outfile, outfile_len, "%s", j.outfile.c_str());
+        if (j.scene->any_area && !area_out) fail(j.line, "the world has an area light: load it with rtc_scene_load_lua_area_lights");
         if (lights_cap && j.scene->lights.size() > lights_cap) return RTC_ERR_ARG;
         const size_t count = j.scene->shapes.size();
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(sizeof(rtc_shape) * (count ? count : 1)));
@@ -2211,7 +2260,10 @@ static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_sha
         *shapes_out = arr;
         *n_out = static_cast<uint32_t>(count);
         if (lights_cap) {
-            for (size_t i = 0; i < j.scene->lights.size(); ++i) light_out[i] = j.scene->lights[i];
+            for (size_t i = 0; i < j.scene->lights.size(); ++i) {
+                if (area_out) area_out[i] = j.scene->lights[i];
+                else light_out[i] = point_of(j.scene->lights[i]);
+            }
             *n_lights_out = static_cast<uint32_t>(j.scene->lights.size());
         } else {
             *light_out = j.scene->light;
@@ -2282,6 +2334,38 @@ rtc_status rtc_scene_load_lua_lights_file(const char *path, uint32_t render_inde
     const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
     if (st != RTC_OK) return st;
     return load_one(prog, render_index, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+}
+
+rtc_status rtc_scene_load_lua_area_lights(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                                          rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out,
+                                          char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
+    if (!text || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
+    *shapes_out = nullptr;
+    *n_out = 0;
+    *n_lights_out = 0;
+    if (renders_out) *renders_out = 0;
+    if (outfile && outfile_len) outfile[0] = 0;
+    rtc_lua_program *prog = nullptr;
+    const rtc_status st = rtc_lua_run(text, nullptr, 0, &prog, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return load_one(prog, render_index, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len,
+                    lights_out);
+}
+
+rtc_status rtc_scene_load_lua_area_lights_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                                               rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out,
+                                               char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
+    if (!path || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
+    *shapes_out = nullptr;
+    *n_out = 0;
+    *n_lights_out = 0;
+    if (renders_out) *renders_out = 0;
+    if (outfile && outfile_len) outfile[0] = 0;
+    rtc_lua_program *prog = nullptr;
+    const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return load_one(prog, render_index, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len,
+                    lights_out);
 }
 
 } // extern "C"

@@ -266,6 +266,49 @@ void rtc_light_default(rtc_light *out) { // material.rs:26-31
     out->position[2] = -10.;
 }
 
+rtc_status rtc_area_light_from_point(const rtc_light *light, rtc_area_light *out) {
+    if (!light || !out) return RTC_ERR_ARG;
+    std::memset(out, 0, sizeof *out);
+    for (int k = 0; k < 3; ++k) {
+        out->intensity[k] = light->intensity[k];
+        out->corner[k] = light->position[k];
+    }
+    out->usteps = out->vsteps = 1u;
+    return RTC_OK;
+}
+
+// The normative sample list (include/rtc.h): cell centres, v outer, u inner; mul, add and div in the stated order (this
+// file is compiled with -ffp-contract=off).
+rtc_status rtc_area_light_expand(const rtc_area_light *lights, uint32_t n, rtc_light *out, uint32_t cap, uint32_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!lights || !out || !n_out || n == 0u) return RTC_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (lights[i].usteps == 0u || lights[i].vsteps == 0u) return RTC_ERR_ARG;
+        total += (uint64_t)lights[i].usteps * lights[i].vsteps; // each product < 2^64; the running sum is checked at once
+        if (total > RTC_MAX_LIGHT_SAMPLES) return RTC_ERR_ARG;
+    }
+    if (total > cap) return RTC_ERR_ARG;
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const rtc_area_light &a = lights[i];
+        double ucell[3], vcell[3], inten[3];
+        for (int k = 0; k < 3; ++k) {
+            ucell[k] = a.uvec[k] / (double)a.usteps;
+            vcell[k] = a.vvec[k] / (double)a.vsteps;
+            inten[k] = a.intensity[k] / (double)(a.usteps * a.vsteps);
+        }
+        for (uint32_t v = 0; v < a.vsteps; ++v)
+            for (uint32_t u = 0; u < a.usteps; ++u, ++at)
+                for (int k = 0; k < 3; ++k) {
+                    out[at].position[k] = (a.corner[k] + ucell[k] * ((double)u + 0.5)) + vcell[k] * ((double)v + 0.5);
+                    out[at].intensity[k] = inten[k];
+                }
+    }
+    *n_out = at;
+    return RTC_OK;
+}
+
 rtc_status rtc_shape_init(uint32_t kind, const double transform[16], const rtc_material *mat,
                           rtc_shape *out) { // shape.rs:308-317, 436-444, 525-533
     if (!out || !transform || kind > RTC_CUBE) return RTC_ERR_ARG;

@@ -339,7 +339,9 @@ void build_material(const Defs &defs, const Node *n, rtc_material &mat) {
 
 struct Scene {
     std::vector<rtc_shape> shapes;
-    std::vector<rtc_light> lights; // every `add: light`, in file order
+    std::vector<rtc_area_light> lights; // every `add: light`, in file order; a point light (`at`) is the degenerate 1x1 area light
+    int area_line = 0;                  // line of the first area light (`corner`), 0: the scene has none
+    uint64_t samples = 0;               // samples of the lights so far
     rtc_camera camera;
     bool have_camera = false;
 };
@@ -347,6 +349,11 @@ struct Scene {
 void interpret(const Node &root, Scene &sc) {
     if (root.kind != Node::Seq) fail(root.line, "scene must be a sequence of entries");
     Defs defs;
+    // a scene of point lights holds RTC_MAX_LIGHTS of them, as ever; one with an area light RTC_MAX_LIGHT_SAMPLES samples
+    for (const auto &ep : root.seq)
+        if (ep->kind == Node::Map && !sc.area_line && ep->get("add") && ep->get("add")->kind == Node::Scalar && ep->get("add")->scalar == "light" &&
+            ep->get("corner"))
+            sc.area_line = ep->line;
     for (const auto &ep : root.seq) {
         const Node &e = *ep;
         if (e.kind != Node::Map) fail(e.line, "scene entry must be a map");
@@ -388,11 +395,36 @@ void interpret(const Node &root, Scene &sc) {
             }
             sc.have_camera = true;
         } else if (what == "light") {
-            rtc_light l;
-            as_triple(e.get("at"), "at", l.position);
-            as_triple(e.get("intensity"), "intensity", l.intensity);
-            if (sc.lights.size() == RTC_MAX_LIGHTS) fail(e.line, "too many lights: a scene holds at most " + std::to_string(RTC_MAX_LIGHTS));
-            sc.lights.push_back(l); // (the reference uses lights[1] only, lua.rs:148-150: the single-light entries return that one)
+            rtc_area_light a;
+            std::memset(&a, 0, sizeof a);
+            a.usteps = a.vsteps = 1u;
+            if (e.get("corner")) { // the book's area light: corner / uvec / vvec / usteps / vsteps / intensity
+                if (e.get("at")) fail(e.line, "a light has either 'at' (point light) or 'corner' (area light), not both");
+                as_triple(e.get("corner"), "corner", a.corner);
+                as_triple(e.get("uvec"), "uvec", a.uvec);
+                as_triple(e.get("vvec"), "vvec", a.vvec);
+                auto steps = [&](const char *key) {
+                    const Node *n = e.get(key);
+                    const double v = as_number(n, key);
+                    if (!(v >= 1 && v <= RTC_MAX_LIGHT_SAMPLES) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                        fail(n->line, std::string(key) + " must be an integer in 1.." + std::to_string(RTC_MAX_LIGHT_SAMPLES));
+                    return static_cast<uint32_t>(v);
+                };
+                a.usteps = steps("usteps");
+                a.vsteps = steps("vsteps");
+                if (const Node *j = e.get("jitter")) {
+                    if (j->kind != Node::Scalar || (j->scalar != "false" && j->scalar != "true")) fail(j->line, "jitter must be true or false");
+                    if (j->scalar == "true") fail(j->line, "jitter is not supported: area light samples sit at the cell centres (jitter: false)");
+                }
+            } else {
+                as_triple(e.get("at"), "at", a.corner);
+            }
+            as_triple(e.get("intensity"), "intensity", a.intensity);
+            if (!sc.area_line && sc.lights.size() == RTC_MAX_LIGHTS) fail(e.line, "too many lights: a scene holds at most " + std::to_string(RTC_MAX_LIGHTS));
+            sc.samples += static_cast<uint64_t>(a.usteps) * a.vsteps;
+            if (sc.samples > RTC_MAX_LIGHT_SAMPLES)
+                fail(e.line, "too many light samples: a scene holds at most " + std::to_string(RTC_MAX_LIGHT_SAMPLES) + " (usteps x vsteps, summed over its lights)");
+            sc.lights.push_back(a); // (the reference uses lights[1] only, lua.rs:148-150: the single-light entries return that one)
         } else if (what == "sphere" || what == "plane" || what == "cube") {
             const uint32_t kind = what == "sphere" ? RTC_SPHERE : what == "plane" ? RTC_PLANE : RTC_CUBE;
             double xf[16];
@@ -423,10 +455,13 @@ void set_err(char *errbuf, size_t len, const std::string &msg) {
 
 extern "C" {
 
-// first_only: the single-light entries' form — lights_out receives lights[1] alone, however many the scene has
+// first_only: the single-light entries' form — lights_out receives lights[1] alone, however many the scene has.
+// Exactly one of lights_out (point lights; a scene with an area light is a parse error) and area_out (every light as an
+// rtc_area_light) is given.
 static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out, uint32_t lights_cap,
-                            uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only) {
-    if (!text || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
+                            uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only,
+                            rtc_area_light *area_out = nullptr) {
+    if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -438,6 +473,7 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (p.pos != p.lines.size()) fail(p.lines[p.pos].number, "unexpected content");
         Scene sc;
         interpret(*root, sc);
+        if (sc.area_line && !area_out) fail(sc.area_line, "the scene has an area light: load it with rtc_scene_load_yaml_area_lights");
         if (!first_only && sc.lights.size() > lights_cap) return RTC_ERR_ARG;
         const size_t bytes = sizeof(rtc_shape) * (sc.shapes.empty() ? 1 : sc.shapes.size());
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(bytes));
@@ -446,7 +482,13 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         *shapes_out = arr;
         *n_out = static_cast<uint32_t>(sc.shapes.size());
         const uint32_t nl = first_only ? 1u : static_cast<uint32_t>(sc.lights.size());
-        for (uint32_t i = 0; i < nl; ++i) lights_out[i] = sc.lights[i];
+        for (uint32_t i = 0; i < nl; ++i) {
+            if (area_out) { area_out[i] = sc.lights[i]; continue; }
+            for (int k = 0; k < 3; ++k) { // a point light: corner = position, 1x1
+                lights_out[i].position[k] = sc.lights[i].corner[k];
+                lights_out[i].intensity[k] = sc.lights[i].intensity[k];
+            }
+        }
         *n_lights_out = nl;
         *camera_out = sc.camera;
         return RTC_OK;
@@ -472,6 +514,12 @@ rtc_status rtc_scene_load_yaml_lights(const char *text, rtc_shape **shapes_out, 
                                       uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
                                       size_t errbuf_len) {
     return load_yaml(text, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false);
+}
+
+rtc_status rtc_scene_load_yaml_area_lights(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                           size_t errbuf_len) {
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -501,6 +549,15 @@ rtc_status rtc_scene_load_yaml_lights_file(const char *path, rtc_shape **shapes_
     const rtc_status st = read_file(path, text, errbuf, errbuf_len);
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_lights(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len);
+}
+
+rtc_status rtc_scene_load_yaml_area_lights_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                                uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                                size_t errbuf_len) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_area_lights(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len);
 }
 
 } // extern "C"

@@ -19,7 +19,8 @@
 #include "rtc_internal.h"
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
-                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl);
+                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
+                                       const DevLightTable *lt);
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],
                                       hipStream_t stream);
 extern "C" hipError_t rtc_launch_arith(uint32_t op, const double *a, const double *b, uint32_t n, double *out,
@@ -239,12 +240,27 @@ void fill_world(RenderParams &P, const rtc_world::Gen &G) {
     }
 }
 
-// The further lights of generation G as k_trace's trailing argument; *xl = nullptr for a one-light World (the kernels
-// without that argument). RTC_ERR_UNSUPPORTED when the launch's source has no multi-light kernels.
-rtc_status lights_of(const rtc_world::Gen &G, int src, DevExtraLights &X, const DevExtraLights **xl) {
-    *xl = nullptr;
+// The further lights of generation G as k_trace's trailing argument: *xl (the kernel-argument block) or *lt (the
+// generation's device table, Gen::light_table); both nullptr for a one-light World (the kernels without that argument).
+// RTC_ERR_UNSUPPORTED when the launch's source has no multi-light kernels.
+struct LaunchLights {
+    DevExtraLights extra;
+    DevLightTable table;
+    const DevExtraLights *xl = nullptr;
+    const DevLightTable *lt = nullptr;
+};
+rtc_status lights_of(const rtc_world::Gen &G, int src, LaunchLights &L) {
+    L.xl = nullptr;
+    L.lt = nullptr;
     if (G.n_lights <= 1u) return RTC_OK;
     if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED;
+    if (G.light_table) {
+        L.table.rec = G.ltab;
+        L.table.n = G.n_lights - 1u;
+        L.lt = &L.table;
+        return RTC_OK;
+    }
+    DevExtraLights &X = L.extra;
     std::memset(&X, 0, sizeof X);
     X.n = G.n_lights - 1u;
     for (uint32_t i = 0; i < X.n; ++i)
@@ -252,15 +268,35 @@ rtc_status lights_of(const rtc_world::Gen &G, int src, DevExtraLights &X, const 
             X.pos[i][k] = G.more[i].position[k];
             X.inten[i][k] = G.more[i].intensity[k];
         }
-    *xl = &X;
+    L.xl = &X;
     return RTC_OK;
 }
 
-// L[0] and L[1..n) of a generation, from the caller's array
-void set_lights(rtc_world::Gen &G, const rtc_light *lights, uint32_t n_lights) {
+// L[0] and L[1..n) of a generation, from the caller's array. More than RTC_MAX_LIGHTS of them (or RTC_LIGHT_TABLE=1 and
+// more than one) reach the kernels through the generation's device table, which the caller then writes (light_records).
+void set_lights(const rtc_context *ctx, rtc_world::Gen &G, const rtc_light *lights, uint32_t n_lights) {
     G.light = lights[0];
     G.n_lights = n_lights;
     for (uint32_t i = 1; i < n_lights; ++i) G.more[i - 1u] = lights[i];
+    G.light_table = n_lights > RTC_MAX_LIGHTS || (ctx->light_table && n_lights > 1u);
+}
+// The table's records of L[1..n): position, then intensity (DevLightTable)
+constexpr size_t LIGHT_TABLE_DOUBLES = 6u * (RTC_MAX_LIGHT_SAMPLES - 1u);
+void light_records(const rtc_world::Gen &G, double *rec) {
+    for (uint32_t i = 0; i + 1u < G.n_lights; ++i)
+        for (int k = 0; k < 3; ++k) {
+            rec[6u * i + k] = G.more[i].position[k];
+            rec[6u * i + 3u + k] = G.more[i].intensity[k];
+        }
+}
+// A World's lights as its sample list (12 KB, on the caller's stack: the update path makes no heap allocation either):
+// RTC_OK and 1 <= *n <= RTC_MAX_LIGHT_SAMPLES, or rtc_area_light_expand's RTC_ERR_ARG
+struct LightSamples {
+    rtc_light at[RTC_MAX_LIGHT_SAMPLES];
+};
+rtc_status expand_lights(const rtc_area_light *lights, uint32_t n_lights, LightSamples &out, uint32_t *n) {
+    if (!lights) return RTC_ERR_ARG;
+    return rtc_area_light_expand(lights, n_lights, out.at, RTC_MAX_LIGHT_SAMPLES, n);
 }
 
 // ---- generations (rtc_world::Gen)
@@ -275,6 +311,8 @@ uint32_t light_cap_for(uint32_t n) { return n >= 32u ? (n > 256u ? RTC_LIGHT_LIS
 
 // Points G's tables into its slab for a World of n shapes and returns the bytes they take. isect, shade, idtab and kind —
 // what the host flattens — come first, `*staged` bytes in all: an update stages them in the same layout and copies them at once.
+// The light table is the last of them (always room for RTC_MAX_LIGHT_SAMPLES - 1 records): a generation that does not use
+// it stages and copies only the bytes in front of it.
 size_t carve_gen(rtc_world::Gen &G, uint32_t n, size_t *staged) {
     const size_t na = n ? n : 1u, ng = n ? (n + 63u) / 64u : 1u, npad = rtc_world_build_npad(n);
     unsigned char *base = G.slab;
@@ -287,6 +325,7 @@ size_t carve_gen(rtc_world::Gen &G, uint32_t n, size_t *staged) {
     take(G.shade, na);
     take(G.idtab, na);
     take(G.kind, na);
+    take(G.ltab, LIGHT_TABLE_DOUBLES);
     if (staged) *staged = off;
     take(G.bound, na);
     take(G.isect_s, na);
@@ -514,6 +553,7 @@ rtc_status rtc_context_create(int32_t device, void *stream, rtc_context **out) {
     }
     if (const char *e = std::getenv("RTC_BINNING")) ctx->binning = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_LIGHT_LISTS")) ctx->light_lists = std::atoi(e) != 0;
+    if (const char *e = std::getenv("RTC_LIGHT_TABLE")) ctx->light_table = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_WORLD_UPDATE")) ctx->world_update = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_SKY_ROWS")) ctx->sky_rows = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS")) ctx->bin_small_pixels = std::strtoull(e, nullptr, 10);
@@ -617,16 +657,49 @@ rtc_status rtc_context_device_info(rtc_context *ctx, char *name, size_t cap, int
     return RTC_OK;
 }
 
-static_assert(RTC_DEV_MAX_LIGHTS == RTC_MAX_LIGHTS, "include/rtc.h and rtc_device.h disagree");
+static_assert(RTC_DEV_MAX_LIGHTS == RTC_MAX_LIGHTS && RTC_DEV_MAX_LIGHT_SAMPLES == RTC_MAX_LIGHT_SAMPLES, "include/rtc.h and rtc_device.h disagree");
 
 rtc_status rtc_world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *light, rtc_world **out) {
     return rtc_world_create_lights(ctx, shapes, n, light, 1u, out);
 }
 
-// (the light-space lists are L[0]'s: `light` below)
+static rtc_status world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *lights, uint32_t n_lights,
+                               rtc_world **out);
+static rtc_status world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n, const rtc_light *lights,
+                               uint32_t n_lights);
+
 rtc_status rtc_world_create_lights(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *lights, uint32_t n_lights,
                                    rtc_world **out) {
     if (!ctx || !out || !lights || (n && !shapes) || n_lights == 0u || n_lights > RTC_MAX_LIGHTS) return RTC_ERR_ARG;
+    return world_create(ctx, shapes, n, lights, n_lights, out);
+}
+
+// A World of area lights is the World of their samples (include/rtc.h): up to RTC_MAX_LIGHTS of them take
+// rtc_world_create_lights' path as they are, more go through the generation's device table (set_lights).
+rtc_status rtc_world_create_area_lights(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_area_light *lights,
+                                        uint32_t n_lights, rtc_world **out) {
+    if (!ctx || !out || !lights || (n && !shapes)) return RTC_ERR_ARG;
+    *out = nullptr;
+    LightSamples samples;
+    uint32_t n_samples = 0;
+    const rtc_status es = expand_lights(lights, n_lights, samples, &n_samples);
+    if (es != RTC_OK) return es;
+    return world_create(ctx, shapes, n, samples.at, n_samples, out);
+}
+
+rtc_status rtc_world_update_area_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n,
+                                        const rtc_area_light *lights, uint32_t n_lights) {
+    if (!ctx || !w || !lights || (n && !shapes) || w->ctx != ctx) return RTC_ERR_ARG;
+    LightSamples samples;
+    uint32_t n_samples = 0;
+    const rtc_status es = expand_lights(lights, n_lights, samples, &n_samples);
+    if (es != RTC_OK) return es;
+    return world_update(ctx, w, shapes, n, samples.at, n_samples);
+}
+
+// (the light-space lists are L[0]'s: `light` below; 1 <= n_lights <= RTC_MAX_LIGHT_SAMPLES, checked by the callers)
+static rtc_status world_create(rtc_context *ctx, const rtc_shape *shapes, uint32_t n, const rtc_light *lights, uint32_t n_lights,
+                               rtc_world **out) {
     const rtc_light *light = lights;
     *out = nullptr;
     const rtc_status cs = check_shapes(shapes, n);
@@ -729,7 +802,7 @@ rtc_status rtc_world_create_lights(rtc_context *ctx, const rtc_shape *shapes, ui
     G.pre_limit = std::isfinite(pre_limit) ? pre_limit : 0.;
     G.ngroups = ngroups;
     G.n = n;
-    set_lights(G, lights, n_lights);
+    set_lights(ctx, G, lights, n_lights);
     G.any_refl = any_refl;
     G.any_refr = any_refr;
     for (uint32_t i = 0; i < n; ++i)
@@ -751,6 +824,11 @@ rtc_status rtc_world_create_lights(rtc_context *ctx, const rtc_shape *shapes, ui
     upload(G.idtab, idtab);
     upload(G.pre, pre);
     upload(G.pre_s, pre_s);
+    if (G.light_table) {
+        std::vector<double> rec(LIGHT_TABLE_DOUBLES, 0.);
+        light_records(G, rec.data());
+        upload(G.ltab, rec);
+    }
     // light-space shadow lists: every shadow segment ends at the light, so the objects a segment can meet
     // are listed per direction cell of a cube map around the light, once per World. Reach = twice the far side of the
     // farthest bounded object as seen from the light (longer segments fall back to the group walk).
@@ -835,6 +913,12 @@ uint32_t rtc_world_light_count(const rtc_world *w) { return w ? w->gen[w->cur].n
 rtc_status rtc_world_update_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n, const rtc_light *lights,
                                    uint32_t n_lights) {
     if (!ctx || !w || !lights || (n && !shapes) || w->ctx != ctx || n_lights == 0u || n_lights > RTC_MAX_LIGHTS) return RTC_ERR_ARG;
+    return world_update(ctx, w, shapes, n, lights, n_lights);
+}
+
+// (a generation with a light table stages its records behind the flattened shapes: one copy, in stream order with them)
+static rtc_status world_update(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n, const rtc_light *lights,
+                               uint32_t n_lights) {
     const rtc_light *light = lights;
     const rtc_status cs = check_shapes(shapes, n);
     if (cs != RTC_OK) return cs;
@@ -874,7 +958,9 @@ rtc_status rtc_world_update_lights(rtc_context *ctx, rtc_world *w, const rtc_sha
     flatten_shapes(shapes, n, staged_at(G.isect), staged_at(G.kind), staged_at(G.shade), staged_at(G.idtab), &G.any_refl, &G.any_refr);
     G.n = n;
     G.ngroups = (n + 63u) / 64u;
-    set_lights(G, lights, n_lights);
+    set_lights(ctx, G, lights, n_lights);
+    if (G.light_table) light_records(G, staged_at(G.ltab));
+    else staged = static_cast<size_t>(reinterpret_cast<unsigned char *>(G.ltab) - base); // the table is the last staged block
     G.light_cap = 0;
     G.light_cap_want = light_cap;
     HIP_TRY(hipMemcpyAsync(base, G.stage, staged, hipMemcpyHostToDevice, bs));
@@ -1001,9 +1087,8 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     int src;
     size_t lds_bytes;
     choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u);
-    DevExtraLights extra;
-    const DevExtraLights *xl = nullptr;
-    const rtc_status ls = lights_of(G, src, extra, &xl);
+    LaunchLights LL;
+    const rtc_status ls = lights_of(G, src, LL);
     if (ls != RTC_OK) return ls;
     const int cull = CULL_LEVEL(src);
     const bool refl = G.any_refl || G.any_refr;
@@ -1126,11 +1211,11 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         }
     }
     HIP_TRY(rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, grid_wgs, lds_bytes, stream,
-                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, xl));
+                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, LL.xl, LL.lt));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
     HIP_TRY(record_read(w, G, stream, stream_bit));
     ctx->last = rtc_launch_info{(uint32_t)src, (G.any_refl || G.any_refr) ? 1u : 0u, G.any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
-                                P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], {0u, 0u}};
+                                P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], LL.lt ? 1u : 0u, {0u}};
     ++ctx->launches_total;
     ctx->last_bin = rtc_context::LastBin{};
     if (P.tile_cnt && bin_set >= 0) ctx->last_bin = rtc_context::LastBin{w->serial, (uint32_t)bin_set, nviews, tiles_x, tiles_y};
@@ -1516,9 +1601,8 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         int src;
         size_t lds_bytes;
         choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u);
-        DevExtraLights extra;
-        const DevExtraLights *xl = nullptr;
-        st = lights_of(G, src, extra, &xl);
+        LaunchLights LL;
+        st = lights_of(G, src, LL);
         const uint32_t blk = RTC_BLOCK_FOR(CULL_LEVEL(src), G.any_refl || G.any_refr, G.any_refr, true);
         P.grid_x = (n + blk - 1u) / blk;
         P.grid_y = 1;
@@ -1528,7 +1612,7 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.reps = 1;
         P.chunk_wgs[0] = P.chunk_wgs[1] = P.chunk_wgs[2] = P.chunk_wgs[3] = 0;
         if (st == RTC_OK && rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
-                                             nullptr, xl) != hipSuccess)
+                                             nullptr, LL.xl, LL.lt) != hipSuccess)
             st = RTC_ERR_DEVICE;
     }
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)

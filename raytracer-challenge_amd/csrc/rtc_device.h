@@ -153,6 +153,16 @@ struct DevExtraLights {
     double inten[RTC_DEV_MAX_LIGHTS - 1][3];   // PointLight::intensity
 };
 
+// The same lights for a World of more than RTC_DEV_MAX_LIGHTS samples (area lights, include/rtc.h): a table in HBM, one per
+// World generation, 6 doubles per light — position, then intensity. The table instantiations of k_trace take this block
+// in DevExtraLights' place; the light index is wave-uniform: plain loads of one address per wave (the compiler emits them
+// as global loads today, served by L2; it is free to make them scalar loads).
+enum { RTC_DEV_MAX_LIGHT_SAMPLES = 256 }; // == RTC_MAX_LIGHT_SAMPLES (include/rtc.h)
+struct DevLightTable {
+    const double *rec; // [n][6]
+    uint32_t n;        // how many follow the first: 1 .. RTC_DEV_MAX_LIGHT_SAMPLES - 1
+};
+
 struct RenderParams {
     const DevIsect *isect;
     const uint32_t *kind;

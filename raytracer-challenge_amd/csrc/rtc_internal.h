@@ -58,6 +58,7 @@ struct rtc_context {
         uint32_t set = 0, nviews = 0, tiles_x = 0, tiles_y = 0;
     } last_bin;
     hipEvent_t fence_ev = nullptr; // rtc_context_fence
+    bool light_table = false; // RTC_LIGHT_TABLE=1: Worlds of 2..RTC_MAX_LIGHTS lights read them from the device table too (parity measurements)
     bool light_lists = true; // RTC_LIGHT_LISTS=0: shadow passes of two-level worlds walk the groups (A/B)
     bool world_update = true; // RTC_WORLD_UPDATE=0: render_lua destroys and recreates the World when a job's differs (A/B)
     bool binning = true;  // RTC_BINNING=0: primary rays take the wave-level cull / group walk too (A/B)
@@ -119,8 +120,10 @@ struct rtc_world {
         uint32_t n = 0;
         uint32_t ngroups = 0;
         rtc_light light{};                     // L[0]: the light with the light-space lists
-        uint32_t n_lights = 1;                 // 1 .. RTC_MAX_LIGHTS
-        rtc_light more[RTC_MAX_LIGHTS - 1]{};  // L[1 .. n_lights)
+        uint32_t n_lights = 1;                 // 1 .. RTC_MAX_LIGHT_SAMPLES (an area light counts as its samples)
+        rtc_light more[RTC_MAX_LIGHT_SAMPLES - 1]{}; // L[1 .. n_lights)
+        double *ltab = nullptr;                // device table of L[1 ..): 6 doubles each, room for RTC_MAX_LIGHT_SAMPLES - 1 (carve_gen)
+        bool light_table = false;              // launches read L[1 ..) from ltab (written with this generation) instead of their arguments
         bool any_refl = false, any_refr = false;
         uint32_t light_cap = 0;  // entries per cell of this generation's lists; 0: it has none
         // known to the host build at once; after a device build only once the header has arrived (hdr_pending)

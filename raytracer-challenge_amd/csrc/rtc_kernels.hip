@@ -923,6 +923,14 @@ struct LightInt {
     double light_int[3];
 };
 template <class T> DEVI const T &first_of(const T &t) { return t; }
+// Lights 1..n-1 of the multi-light loop, from the kernel arguments (DevExtraLights) or from the World's table in HBM
+// (DevLightTable, 6 doubles per light). `i` is wave-uniform: plain loads, which the compiler may issue as scalar ones.
+DEVI uint32_t further_light_count(const DevExtraLights &X) { return X.n; }
+DEVI V3 further_light_position(const DevExtraLights &X, uint32_t i) { return mk(X.pos[i][0], X.pos[i][1], X.pos[i][2]); }
+DEVI LightInt further_light_intensity(const DevExtraLights &X, uint32_t i) { return LightInt{{X.inten[i][0], X.inten[i][1], X.inten[i][2]}}; }
+DEVI uint32_t further_light_count(const DevLightTable &X) { return X.n; }
+DEVI V3 further_light_position(const DevLightTable &X, uint32_t i) { return mk(X.rec[6u * i], X.rec[6u * i + 1u], X.rec[6u * i + 2u]); }
+DEVI LightInt further_light_intensity(const DevLightTable &X, uint32_t i) { return LightInt{{X.rec[6u * i + 3u], X.rec[6u * i + 4u], X.rec[6u * i + 5u]}}; }
 
 // World::reflectance (Schlick) shape.rs:768-781
 DEVI double reflectance(V3 eyev, V3 normal, double n1, double n2) {
@@ -1046,7 +1054,8 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // (rtc_device.h) for a World with several (MULTI): lights 1..n-1 ride behind the tables in the kernarg segment, and the
 // shadow and lighting stages loop over them (shade_hit with the FIXME at shape.rs:686 filled in: the sum of every light's
 // lighting(), each with its own is_shadowed_by_light, shape.rs:716). Instantiated only for the sources a multi-light launch
-// takes (SRC_SMEM, SRC_CULL, SRC_CULL2).
+// takes (SRC_SMEM, SRC_CULL, SRC_CULL2). One DevLightTable instead: the same loop reading the lights from the World's table
+// in HBM (more than RTC_MAX_LIGHTS samples: area lights) — same sources, same flavours, nothing new stored.
 template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, class... XL>
 __global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
@@ -1621,11 +1630,11 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             V3 surface_all = mk(0., 0., 0.);
             if constexpr (MULTI) {
                 static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "multi-light launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
-                const DevExtraLights &X = first_of(xl_arg...);
+                const auto &X = first_of(xl_arg...); // DevExtraLights (kernel arguments) or DevLightTable (HBM): further_light_*
                 if (hit) surface_all = lighting(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
-                const uint32_t n_extra = X.n;
+                const uint32_t n_extra = further_light_count(X);
                 for (uint32_t li = 0; li < n_extra; ++li) {
-                    const V3 lp = mk(X.pos[li][0], X.pos[li][1], X.pos[li][2]);
+                    const V3 lp = further_light_position(X, li);
                     V3 ldir = mk(0, 0, 0);
                     double ldist = 0.;
                     if (hit) { // is_shadowed_by_light shape.rs:716-720
@@ -1648,7 +1657,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     }, over, ldir);
                     asm volatile("" ::: "memory"); // as above: the material loads stay below the walk
                     if (hit) {
-                        const LightInt I{{X.inten[li][0], X.inten[li][1], X.inten[li][2]}};
+                        const LightInt I = further_light_intensity(X, li);
                         surface_all = vadd(surface_all, lighting(I, S, m_obj, over, eyev, normal, ldir, l_shadowed));
                     }
                 }
@@ -2428,8 +2437,10 @@ static hipError_t launch_one(const RenderParams &P, dim3 grid, size_t lds_bytes,
 }
 
 // `xl`: NULL for a World with one light; else its lights 1..n-1 (xl->n >= 1), and src one of SRC_SMEM, SRC_CULL, SRC_CULL2.
+// `lt` (instead of `xl`, never both): the same lights as a device table (lt->rec holds lt->n records, rtc_device.h).
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
-                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl) {
+                                       size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
+                                       const DevLightTable *lt) {
     const dim3 grid(nblocks);
 #define RTC_CASE(S, ...)                                                                            \
     if (src == S) {                                                                            \
@@ -2437,11 +2448,19 @@ extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl,
         if (refl) return launch_one<S, true, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);              \
         return launch_one<S, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);                       \
     }
+    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
     if (xl != nullptr) {
         if (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u) return hipErrorInvalidValue;
         RTC_CASE(SRC_SMEM, *xl)
         RTC_CASE(SRC_CULL, *xl)
         RTC_CASE(SRC_CULL2, *xl)
+        return hipErrorInvalidValue;
+    }
+    if (lt != nullptr) {
+        if (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u) return hipErrorInvalidValue;
+        RTC_CASE(SRC_SMEM, *lt)
+        RTC_CASE(SRC_CULL, *lt)
+        RTC_CASE(SRC_CULL2, *lt)
         return hipErrorInvalidValue;
     }
     RTC_CASE(SRC_SMEM)

@@ -171,13 +171,16 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
     if (stats) st = rtc_stats_reset(ctx);
     if (st == RTC_OK && lanes_before == 1u && njobs > 1u) st = rtc_context_set_pipeline(ctx, 3u);
     uint32_t i = 0;
+    std::vector<rtc_area_light> light_buf(RTC_MAX_LIGHT_SAMPLES); // one buffer for every job's lights (26 KB: not on the stack)
+    rtc_area_light *const lights = light_buf.data();
     for (; st == RTC_OK && !stop && i < njobs; ++i) {
         rtc_lua_job job;
         st = rtc_lua_program_job(prog, i, &job);
         if (st != RTC_OK) break;
-        rtc_light lights[RTC_MAX_LIGHTS]; // every light of the job's world (job.light is lights[0])
+        // every light of the job's world, point lights as 1x1 area lights (a World of at most RTC_MAX_LIGHTS samples IS the
+        // rtc_world_create_lights World of those samples)
         uint32_t n_lights = 0;
-        if ((st = rtc_lua_program_job_lights(prog, i, lights, RTC_MAX_LIGHTS, &n_lights)) != RTC_OK) break;
+        if ((st = rtc_lua_program_job_area_lights(prog, i, lights, RTC_MAX_LIGHT_SAMPLES, &n_lights)) != RTC_OK) break;
         const size_t bytes = (size_t)3 * job.camera.hsize * job.camera.vsize;
         Output out;
         if ((st = choose(entry, job, quality, &out)) != RTC_OK) break;
@@ -186,12 +189,12 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
         st = deliver(sl);
         if (st != RTC_OK || stop) break;
         if (!world) { // the program's first job
-            st = rtc_world_create_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
+            st = rtc_world_create_area_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
             if (st != RTC_OK) break;
         } else if (!job.same_world_as_previous && ctx->world_update) {
             // other contents for the resident World, ordered like a launch: the frames in flight keep theirs, and the
             // outputs' ring is safe as it is (a slot is reused only after `depth` later launches)
-            st = rtc_world_update_lights(ctx, world, job.shapes, job.n_shapes, lights, n_lights);
+            st = rtc_world_update_area_lights(ctx, world, job.shapes, job.n_shapes, lights, n_lights);
             if (st != RTC_OK) break;
         } else if (!job.same_world_as_previous) { // RTC_WORLD_UPDATE=0, a new World: nothing may still read the old one
             st = drain(i);
@@ -199,7 +202,7 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
             if (st != RTC_OK || stop) break;
             rtc_world_destroy(world);
             world = nullptr;
-            st = rtc_world_create_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
+            st = rtc_world_create_area_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
             if (st != RTC_OK) break;
         }
         if ((st = sl.d.reserve(bytes)) != RTC_OK) break;

@@ -295,6 +295,23 @@ class World { // shape.rs:633-795
         more_lights.push_back(l);
         return *this;
     }
+    // The book's area light (rtc_area_light, include/rtc.h): the rectangle corner + s*uvec + t*vvec, sampled at the centres
+    // of usteps x vsteps cells, each sample a point light of intensity / (usteps*vsteps). Area lights follow the point
+    // lights in the World's sample list; at most RTC_MAX_LIGHT_SAMPLES samples in all (checked when the World is rendered).
+    // The World keeps its point `light` (the reference's World::new takes one), so it is sample 0 and an area light always
+    // shines beside it — give it Color::BLACK() for a World lit by area lights alone (its shadow rays are still cast).
+    // lights() lists the point lights only; the area lights are `area_lights`.
+    World &add_area_light(Point corner, Vector uvec, Vector vvec, uint32_t usteps, uint32_t vsteps, Color intensity) {
+        if (usteps == 0 || vsteps == 0) check(RTC_ERR_ARG, "World::add_area_light");
+        rtc_area_light a{};
+        a.intensity[0] = intensity.red; a.intensity[1] = intensity.green; a.intensity[2] = intensity.blue;
+        a.corner[0] = corner.x; a.corner[1] = corner.y; a.corner[2] = corner.z;
+        a.uvec[0] = uvec.x; a.uvec[1] = uvec.y; a.uvec[2] = uvec.z;
+        a.vvec[0] = vvec.x; a.vvec[1] = vvec.y; a.vvec[2] = vvec.z;
+        a.usteps = usteps; a.vsteps = vsteps;
+        area_lights.push_back(a);
+        return *this;
+    }
     std::vector<Light> lights() const {
         std::vector<Light> all{light};
         all.insert(all.end(), more_lights.begin(), more_lights.end());
@@ -314,6 +331,7 @@ class World { // shape.rs:633-795
 
     Light light;
     std::vector<Light> more_lights; // lights()[1..]
+    std::vector<rtc_area_light> area_lights; // add_area_light: behind the point lights
     std::vector<Shape> shapes;
     uint32_t last_world_id = 0;
 
@@ -338,7 +356,7 @@ class World { // shape.rs:633-795
                 l.position[0] = wl.position.x; l.position[1] = wl.position.y; l.position[2] = wl.position.z;
                 ls.push_back(l);
             }
-            w = Resident::instance().get(std::move(flat), ls);
+            w = Resident::instance().get(std::move(flat), ls, world.area_lights);
         }
         Uploaded(const Uploaded &) = delete;
         Uploaded &operator=(const Uploaded &) = delete;
@@ -350,21 +368,33 @@ class World { // shape.rs:633-795
             return r;
         }
         rtc_world *get(std::vector<rtc_shape> &&flat, const rtc_light &l) { return get(std::move(flat), std::vector<rtc_light>{l}); }
-        rtc_world *get(std::vector<rtc_shape> &&flat, const std::vector<rtc_light> &ls) {
+        // `area`: the World's area lights, behind its point lights `ls` (none: the rtc_world_*_lights entries, as ever)
+        rtc_world *get(std::vector<rtc_shape> &&flat, const std::vector<rtc_light> &ls, const std::vector<rtc_area_light> &area = {}) {
             const uint32_t nl = static_cast<uint32_t>(ls.size());
+            std::vector<rtc_area_light> all; // every light as an area light, when the World has one
+            if (!area.empty()) {
+                all.resize(ls.size());
+                for (size_t i = 0; i < ls.size(); ++i) check(rtc_area_light_from_point(&ls[i], &all[i]), "World lights");
+                all.insert(all.end(), area.begin(), area.end());
+            }
+            const uint32_t na = static_cast<uint32_t>(all.size());
             const bool same = w_ != nullptr && flat.size() == flat_.size() && ls.size() == lights_.size() &&
-                              std::memcmp(ls.data(), lights_.data(), ls.size() * sizeof(rtc_light)) == 0 &&
+                              std::memcmp(ls.data(), lights_.data(), ls.size() * sizeof(rtc_light)) == 0 && area.size() == area_.size() &&
+                              (area.empty() || std::memcmp(area.data(), area_.data(), area.size() * sizeof(rtc_area_light)) == 0) &&
                               (flat.empty() || std::memcmp(flat.data(), flat_.data(), flat.size() * sizeof(rtc_shape)) == 0);
             if (!same) {
                 // other contents for the World that is resident already (rtc_world_update: no destroy, no allocation while
                 // it does not grow); a rejected update leaves it as it was, and so does this cache
                 if (w_) {
-                    const rtc_status st = rtc_world_update_lights(Device::get(), w_, flat.data(), static_cast<uint32_t>(flat.size()), ls.data(), nl);
-                    if (st == RTC_ERR_NOMEM || st == RTC_ERR_DEVICE) flat_.clear(), lights_.clear(); // a failed growing update: nothing is resident
+                    const rtc_status st = na ? rtc_world_update_area_lights(Device::get(), w_, flat.data(), static_cast<uint32_t>(flat.size()), all.data(), na)
+                                             : rtc_world_update_lights(Device::get(), w_, flat.data(), static_cast<uint32_t>(flat.size()), ls.data(), nl);
+                    if (st == RTC_ERR_NOMEM || st == RTC_ERR_DEVICE) flat_.clear(), lights_.clear(), area_.clear(); // a failed growing update: nothing is resident
                     check(st, "World update");
-                } else check(rtc_world_create_lights(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), ls.data(), nl, &w_), "World upload");
+                } else if (na) check(rtc_world_create_area_lights(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), all.data(), na, &w_), "World upload");
+                else check(rtc_world_create_lights(Device::get(), flat.data(), static_cast<uint32_t>(flat.size()), ls.data(), nl, &w_), "World upload");
                 flat_ = std::move(flat);
                 lights_ = ls;
+                area_ = area;
             }
             return w_;
         }
@@ -375,6 +405,7 @@ class World { // shape.rs:633-795
         rtc_world *w_ = nullptr;
         std::vector<rtc_shape> flat_;
         std::vector<rtc_light> lights_;
+        std::vector<rtc_area_light> area_;
     };
   private:
     bool dirty_ = false;

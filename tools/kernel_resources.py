@@ -22,7 +22,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?", name)
     if m:
         tag = "k_trace<%s,refl=%s,refr=%s,probe=%s" % m.groups()[:4] + (",rgba" if m.group(5) == "1" else "")
-        tag += ",multi>" if "DevExtraLights" in name else ">"  # the instantiations for Worlds with several lights
+        # the instantiations for Worlds with several lights: in the kernel arguments, or in the World's device table
+        tag += ",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">"
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
