@@ -353,6 +353,21 @@ rtc_status  rtc_scene_load_lua_area_lights_file(const char *path, uint32_t rende
                                                 struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
                                                 rtc_camera *camera_out, char *outfile, size_t outfile_len,
                                                 uint32_t *renders_out, char *errbuf, size_t errbuf_len);
+/* Scenes whose camera has a thin lens (struct rtc_lens, below). YAML: `add: camera` with `aperture` (>= 0) and
+ * `focal-distance` (> 0, required when `aperture` is given), optionally `lens-usteps` / `lens-vsteps` (integers, default 1,
+ * at most RTC_MAX_LENS_SAMPLES samples in all). These entries are rtc_scene_load_yaml_area_lights plus the lens:
+ * *has_lens_out = 1 and *lens_out filled when the camera has any of those keys, else 0 and the pinhole lens (aperture 0,
+ * focal distance 1, 1x1). Every other YAML entry returns RTC_ERR_PARSE for a scene with lens keys, with a message naming
+ * these. */
+struct rtc_lens;
+rtc_status  rtc_scene_load_yaml_lens(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                     struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                     rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                     struct rtc_lens *lens_out, uint32_t *has_lens_out);
+rtc_status  rtc_scene_load_yaml_lens_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                          struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                          rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                          struct rtc_lens *lens_out, uint32_t *has_lens_out);
 /* Every light of job `index` as an area light. RTC_ERR_ARG when cap is too small. */
 rtc_status  rtc_lua_program_job_area_lights(const rtc_lua_program *prog, uint32_t index, struct rtc_area_light *lights_out,
                                             uint32_t cap, uint32_t *n_out);
@@ -670,6 +685,53 @@ rtc_status  rtc_world_create_area_lights(rtc_context *ctx, const rtc_shape *shap
 rtc_status  rtc_world_update_area_lights(rtc_context *ctx, rtc_world *w, const rtc_shape *shapes, uint32_t n_shapes,
                                          const rtc_area_light *lights, uint32_t n_lights);
 
+/* Thin-lens camera: depth of field. The camera's rays start on a SQUARE lens of half-width `aperture` in the camera's
+ * z = 0 plane (camera space) and meet on the plane in focus, `focal_distance` along -z; the lens is sampled at the centres
+ * of a usteps x vsteps grid of cells. A thin-lens pixel IS Color::average_over (color.rs:128-139) of usteps*vsteps ordinary
+ * rays, each answered by World::color_at as it stands. For pixel (x, y) and lens sample k = v*usteps + u (v outer, u
+ * inner) the ray is, in f64 without fused multiply-add, in exactly this order (the first four lines are
+ * Camera::ray_for_pixel_offset with offsets 0.5, camera.rs:65-68):
+ *     xoffset = (x + 0.5) * pixel_size            yoffset = (y + 0.5) * pixel_size
+ *     world_x = half_width - xoffset              world_y = half_height - yoffset
+ *     ucell = (2.0*aperture) / (double)usteps     vcell = (2.0*aperture) / (double)vsteps
+ *     lu = -aperture + ucell*(u + 0.5)            lv = -aperture + vcell*(v + 0.5)
+ *     origin = transform_point(view_inv, (lu, lv, 0.0))
+ *     target = transform_point(view_inv, (world_x*focal_distance, world_y*focal_distance, -focal_distance))
+ *     direction = normalize(target - origin)
+ * and the pixel's colour is Color::average_over of color_at(ray_k, MAX_REFLECTIONS) for k = 0..n-1 in that order: three
+ * sums that start at 0.0, add in k order and are divided once by (double)n. aperture = 0, focal_distance = 1, 1x1 is the
+ * pinhole ray of camera.rs:64-76 bit for bit, and its frame is rtc_render's byte for byte.
+ * NO JITTER, NO DISC: the lens is a square sampled at its cell centres. A jittered or disc-shaped lens needs random
+ * numbers or rejection, which the single-ray oracle the frames are checked against cannot follow; both are out of scope. */
+typedef struct rtc_lens {
+    double   aperture;        /* half-width of the square lens in camera space, >= 0, finite */
+    double   focal_distance;  /* distance of the plane in focus along -z of camera space, > 0, finite */
+    uint32_t usteps, vsteps;  /* >= 1 each; usteps*vsteps <= RTC_MAX_LENS_SAMPLES */
+} rtc_lens;
+#define RTC_MAX_LENS_SAMPLES 256u
+/* [host] RTC_ERR_ARG for NULL, a non-finite or negative aperture, a non-positive or non-finite focal distance, a step
+ * count of 0, or more than RTC_MAX_LENS_SAMPLES samples; else RTC_OK. */
+rtc_status  rtc_lens_validate(const rtc_lens *lens);
+/* [host] The normative ray above for pixel (x, y) and lens sample k < usteps*vsteps; ray = {origin xyz, direction xyz}.
+ * RTC_ERR_ARG for a NULL pointer, an invalid lens or k out of range. Extends rtc_camera_ray_for_pixel (camera.rs:64-76). */
+rtc_status  rtc_lens_ray(const rtc_camera *cam, const rtc_lens *lens, uint32_t x, uint32_t y, uint32_t k, double ray[6]);
+/* [device] rtc_render_rows through the lens: same buffers, row range, ordering and pipelining contract (and timing events,
+ * rtc_launch_info with lens_samples = usteps*vsteps). cam->samples must be 1 (RTC_ERR_ARG otherwise: anti-aliasing and
+ * the lens do not compose); both render modes keep their meaning, RTC_MODE_RENDER's black last row and column included.
+ * RTC_FLAG_NO_CULL is bit-identical to the culled frame, RTC_FLAG_LDS_TABLE (or an RTC_SRC override naming an LDS source)
+ * is RTC_ERR_UNSUPPORTED, RTC_FLAG_AA_RESAMPLE is ignored. The launch has no binning kernel and no per-view table: tile
+ * lists, the black tile-row proof and the per-object primary-ray constants all assume the pinhole origin, so every ray
+ * takes the per-wave cull with the lens sample's origin as the shared apex (rtc_launch_info::binned = 0). rtc_stats:
+ * rays_primary = pixels written x n, rays_primary_proven_miss = 0, the other counters count what those rays spawn. Every
+ * World form works: one light, several, area lights through the light table, updated Worlds. */
+rtc_status  rtc_render_lens_rows(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens,
+                                 uint32_t mode, uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags);
+/* [device] rtc_render / rtc_render_rgb8 through the lens: all rows, copied into host memory. Synchronous; `stats` may be NULL. */
+rtc_status  rtc_render_lens(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens,
+                            uint32_t mode, uint32_t flags, double *rgb, rtc_stats *stats);
+rtc_status  rtc_render_lens_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens,
+                                 uint32_t mode, uint32_t flags, uint8_t *rgb8, rtc_stats *stats);
+
 /* Camera::render / render_async for canvas rows [y0, y1) into a DEVICE buffer of
  * (y1-y0)*hsize*3 doubles (row y0 first). Enqueues on the context stream and returns
  * without synchronising. Row-tiling hook for multi-GPU (each rank renders its rows).
@@ -929,7 +991,7 @@ typedef struct rtc_launch_info {
                                      (RTC_TILES_GUIDED, RTC_TILES_KMAX)                                                  */
     uint32_t light_table; /* 1: the launch read lights 1..n-1 from the World's device table (more than RTC_MAX_LIGHTS
                              samples, or RTC_LIGHT_TABLE=1), 0: from its kernel arguments / a one-light World           */
-    uint32_t _reserved[1];
+    uint32_t lens_samples; /* thin-lens launches (rtc_render_lens*): lens samples per pixel, usteps*vsteps; 0 for every other launch */
 } rtc_launch_info;
 rtc_status  rtc_context_last_launch_info(rtc_context *ctx, rtc_launch_info *out);
 

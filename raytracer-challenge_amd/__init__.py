@@ -17,9 +17,9 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
-                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, PATTERNS, STATUS_NAMES, declare)
+                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, PATTERNS, STATUS_NAMES, declare)
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librtc.so"
@@ -292,6 +292,23 @@ def ray_for_pixel(cam: RtcCamera, x: int, y: int, xo: float = 0.5, yo: float = 0
     return np.array(list(out))
 
 
+def lens(aperture: float, focal_distance: float, usteps: int = 1, vsteps: int = 1) -> RtcLens:
+    """A thin lens for DeviceWorld.render_lens: a square of half-width `aperture` in the camera's z = 0 plane, sampled at
+    the centres of usteps x vsteps cells, in focus `focal_distance` in front of the camera (rtc_lens, include/rtc.h; no
+    jitter, no disc). lens(0, 1) is the pinhole."""
+    l = RtcLens()
+    l.aperture, l.focal_distance, l.usteps, l.vsteps = float(aperture), float(focal_distance), int(usteps), int(vsteps)
+    _check(lib().rtc_lens_validate(C.byref(l)), "rtc_lens_validate")
+    return l
+
+
+def lens_ray(cam: RtcCamera, lens: RtcLens, x: int, y: int, k: int) -> np.ndarray:
+    """The ray of pixel (x, y) through lens sample k = v*usteps + u: origin xyz, direction xyz (rtc_lens_ray)."""
+    out = (C.c_double * 6)()
+    _check(lib().rtc_lens_ray(C.byref(cam), C.byref(lens), x, y, k, out), "rtc_lens_ray")
+    return np.array(list(out))
+
+
 def _copy_lights(arr, n: int) -> list:
     out = []
     for i in range(n):
@@ -319,6 +336,30 @@ def load_yaml(text: str | None = None, path: str | None = None):
         w.shapes.append(s)
     lib().rtc_free(shapes)
     return w, cam
+
+
+def load_yaml_lens(text: str | None = None, path: str | None = None):
+    """load_yaml for scenes whose camera may have a thin lens (aperture / focal-distance / lens-usteps / lens-vsteps):
+    -> (World, RtcCamera, RtcLens or None)."""
+    shapes = C.POINTER(RtcShape)()
+    n = C.c_uint32(0)
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
+    err = C.create_string_buffer(512)
+    ln, has = RtcLens(), C.c_uint32(0)
+    if path is not None:
+        st = lib().rtc_scene_load_yaml_lens_file(str(path).encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512,
+                                                 C.byref(ln), C.byref(has))
+    else:
+        st = lib().rtc_scene_load_yaml_lens(text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512,
+                                            C.byref(ln), C.byref(has))
+    _check(st, "rtc_scene_load_yaml_lens", err.value.decode(errors="replace"))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
+    for i in range(n.value):
+        s = RtcShape()
+        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
+        w.shapes.append(s)
+    lib().rtc_free(shapes)
+    return w, cam, (ln if has.value else None)
 
 
 class LuaJob:
@@ -1003,7 +1044,7 @@ class Context:
                 "refractive": bool(i.refractive), "binned_primary_pass": bool(i.binned), "light_lists": bool(i.light_lists),
                 "lane": i.lane, "threads_per_workgroup": i.block, "dynamic_lds_bytes": i.lds_bytes,
                 "tiles_per_workgroup": i.tiles_per_workgroup, "multi_tile_workgroups": i.multi_tile_workgroups,
-                "light_table": bool(i.light_table)}
+                "light_table": bool(i.light_table), "lens_samples": i.lens_samples}
 
     def binning_times_ms(self, last: int = 1024) -> np.ndarray:
         """Durations (ms) of the binning kernels of the most recent `last` timed launches (0 where a launch had none)."""
@@ -1119,6 +1160,32 @@ class DeviceWorld:
         if with_stats:
             return out, _stats_dict(st, cam.samples != 1)
         return out
+
+    def render_lens(self, cam: RtcCamera, lens: RtcLens, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False,
+                    out: np.ndarray | None = None, rgb8: bool = False):
+        """render() through a thin lens (rtc.lens): every pixel is the mean of usteps x vsteps rays from the lens to the
+        pixel's point on the plane in focus — depth of field (rtc_render_lens; rgb8=True: rtc_render_lens_rgb8's uint8 frame)."""
+        dtype = np.uint8 if rgb8 else np.float64
+        if out is None:
+            out = np.empty((cam.vsize, cam.hsize, 3), dtype=dtype)
+        elif out.shape != (cam.vsize, cam.hsize, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous (vsize, hsize, 3) array of float64 (uint8 with rgb8)")
+        st = RtcStats()
+        fn, name = (lib().rtc_render_lens_rgb8, "rtc_render_lens_rgb8") if rgb8 else (lib().rtc_render_lens, "rtc_render_lens")
+        _check(fn(self.ctx._h, self._h, C.byref(cam), C.byref(lens), mode, flags, out.ctypes.data_as(C.POINTER(C.c_uint8 if rgb8 else C.c_double)),
+                  C.byref(st) if with_stats else None), name)
+        if with_stats:
+            d = _stats_dict(st)
+            d["rays_primary_proven_miss"] = st.rays_primary_proven_miss   # 0: no black proof applies when the origin moves
+            return out, d
+        return out
+
+    def render_lens_rows(self, cam: RtcCamera, lens: RtcLens, y0: int, y1: int, d_ptr: int | None, mode: int = MODE_RENDER_ASYNC,
+                         flags: int = 0, d_ptr8: int | None = None) -> None:
+        """render_rows through a thin lens: rows [y0, y1) into the DEVICE buffer at `d_ptr` (rtc_render_lens_rows)."""
+        st = lib().rtc_render_lens_rows(self.ctx._h, self._h, C.byref(cam), C.byref(lens), mode, y0, y1, d_ptr, d_ptr8, flags)
+        if st != 0:
+            raise RtcError(st, "rtc_render_lens_rows")
 
     def render_rgba8(self, cam: RtcCamera, gamma: float = 1.0, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False,
                      out: np.ndarray | None = None):
@@ -1464,8 +1531,8 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel",
-           "load_yaml", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray",
+           "load_yaml", "load_yaml_lens", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",
-           "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcMaterial", "RtcShape", "RtcStats"]
+           "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcLens", "RtcMaterial", "RtcShape", "RtcStats"]

@@ -14,6 +14,7 @@ GATHER_NONE, GATHER_F64, GATHER_U8 = 0, 1, 2
 GROUP_ID_BYTES = 128
 MAX_LIGHTS = 8
 MAX_LIGHT_SAMPLES = 256
+MAX_LENS_SAMPLES = 256
 PATTERNS = {"none": 0, "test": 1, "stripe": 2, "stripes": 2, "gradient": 3, "ring": 4, "checker": 5, "checkers": 5, "grid": 6}
 STATUS_NAMES = {0: "RTC_OK", 1: "RTC_ERR_SINGULAR", 2: "RTC_ERR_NO_COLOR", 3: "RTC_ERR_DEVICE", 4: "RTC_ERR_ARG",
                 5: "RTC_ERR_PARSE", 6: "RTC_ERR_IO", 7: "RTC_ERR_NOMEM", 8: "RTC_ERR_UNSUPPORTED"}
@@ -38,6 +39,10 @@ class RtcAreaLight(C.Structure):
     _fields_ = [("intensity", Vec3), ("corner", Vec3), ("uvec", Vec3), ("vvec", Vec3), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
 
 
+class RtcLens(C.Structure):
+    _fields_ = [("aperture", C.c_double), ("focal_distance", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
+
+
 class RtcCamera(C.Structure):
     _fields_ = [("hsize", C.c_uint32), ("vsize", C.c_uint32), ("fov", C.c_double), ("half_width", C.c_double),
                 ("half_height", C.c_double), ("pixel_size", C.c_double), ("view_inv", Mat16), ("samples", C.c_uint32),
@@ -59,7 +64,7 @@ class RtcHit(C.Structure):
 class RtcLaunchInfo(C.Structure):
     _fields_ = [("source", C.c_uint32), ("reflective", C.c_uint32), ("refractive", C.c_uint32), ("binned", C.c_uint32),
                 ("light_lists", C.c_uint32), ("lane", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint32),
-                ("tiles_per_workgroup", C.c_uint32), ("multi_tile_workgroups", C.c_uint32), ("light_table", C.c_uint32), ("_reserved", C.c_uint32 * 1)]
+                ("tiles_per_workgroup", C.c_uint32), ("multi_tile_workgroups", C.c_uint32), ("light_table", C.c_uint32), ("lens_samples", C.c_uint32)]
 
 
 class RtcLuaJob(C.Structure):
@@ -83,7 +88,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
                 2: "brute force, object table staged in LDS tiles", 3: "one-level per-wave cull", 4: "two-level per-wave cull"}
 
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
-assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48
+assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -108,6 +113,8 @@ PROTOTYPES = {
     "rtc_view_transform": (None, [Vec3, Vec3, Vec3, Mat16]),
     "rtc_camera_init": (C.c_int32, [U32, U32, D, Mat16, C.POINTER(RtcCamera)]),
     "rtc_camera_ray_for_pixel": (None, [C.POINTER(RtcCamera), U32, D, U32, D, C.c_double * 6]),
+    "rtc_lens_validate": (C.c_int32, [C.POINTER(RtcLens)]),
+    "rtc_lens_ray": (C.c_int32, [C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, U32, C.c_double * 6]),
     "rtc_material_default": (None, [C.POINTER(RtcMaterial)]),
     "rtc_shape_init": (C.c_int32, [U32, Mat16, C.POINTER(RtcMaterial), C.POINTER(RtcShape)]),
     "rtc_material_set_pattern": (C.c_int32, [C.POINTER(RtcMaterial), U32, Vec3, Vec3, Mat16]),
@@ -190,6 +197,10 @@ PROTOTYPES = {
                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_scene_load_lua_area_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                         C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_yaml_lens": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                             C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_lens_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                  C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
     "rtc_lua_program_job_area_lights": (C.c_int32, [C.c_void_p, U32, C.POINTER(RtcAreaLight), U32, C.POINTER(U32)]),
     "rtc_free": (None, [VP]),
     "rtc_canvas_write_ppm": (C.c_int32, [C.c_char_p, PD, U32, U32]),
@@ -210,6 +221,9 @@ PROTOTYPES = {
     "rtc_world_update_area_lights": (C.c_int32, [VP, VP, C.POINTER(RtcShape), U32, C.POINTER(RtcAreaLight), U32]),
     "rtc_world_destroy": (None, [VP]),
     "rtc_render_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),
+    "rtc_render_lens_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, U32, VP, VP, U32]),
+    "rtc_render_lens": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, PD, C.POINTER(RtcStats)]),
+    "rtc_render_lens_rgb8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
     "rtc_render_bands": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),
     "rtc_render_views": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, U32, VP, VP, U32, U32]),
     "rtc_render": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, PD, C.POINTER(RtcStats)]),

@@ -111,5 +111,20 @@ def build_facade_area_light_test(force: bool = False) -> Path:
     return exe
 
 
+def build_facade_lens_test(force: bool = False) -> Path:
+    """Compile tests/cpp/test_facade_lens.cpp (the facade's Camera::set_lens) against librtc.so."""
+    src = ROOT / "tests" / "cpp" / "test_facade_lens.cpp"
+    exe = ROOT / "build" / "test_facade_lens"
+    hdr = PKG / "host" / "ch1.hpp"
+    if not src.exists() or not hdr.exists():
+        return None
+    exe.parent.mkdir(parents=True, exist_ok=True)
+    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
+        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
+               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
+        subprocess.run(cmd, check=True)
+    return exe
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))

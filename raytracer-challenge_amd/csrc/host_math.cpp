@@ -231,6 +231,37 @@ void rtc_camera_ray_for_pixel(const rtc_camera *cam, uint32_t x, double x_offset
     ray[3] = dir.x; ray[4] = dir.y; ray[5] = dir.z;
 }
 
+rtc_status rtc_lens_validate(const rtc_lens *lens) {
+    if (!lens) return RTC_ERR_ARG;
+    if (!std::isfinite(lens->aperture) || lens->aperture < 0.) return RTC_ERR_ARG;
+    if (!std::isfinite(lens->focal_distance) || !(lens->focal_distance > 0.)) return RTC_ERR_ARG;
+    if (lens->usteps == 0u || lens->vsteps == 0u) return RTC_ERR_ARG;
+    if ((uint64_t)lens->usteps * lens->vsteps > RTC_MAX_LENS_SAMPLES) return RTC_ERR_ARG;
+    return RTC_OK;
+}
+
+// The normative thin-lens ray (include/rtc.h): camera.rs:64-76 with the origin moved over the lens and the target on the
+// plane in focus; mul, add and div in the stated order (this file is compiled with -ffp-contract=off).
+rtc_status rtc_lens_ray(const rtc_camera *cam, const rtc_lens *lens, uint32_t x, uint32_t y, uint32_t k, double ray[6]) {
+    if (!cam || !ray || rtc_lens_validate(lens) != RTC_OK || k >= lens->usteps * lens->vsteps) return RTC_ERR_ARG;
+    const uint32_t u = k % lens->usteps, v = k / lens->usteps;
+    const double xoffset = (static_cast<double>(x) + 0.5) * cam->pixel_size;
+    const double yoffset = (static_cast<double>(y) + 0.5) * cam->pixel_size;
+    const double world_x = cam->half_width - xoffset;
+    const double world_y = cam->half_height - yoffset;
+    const double ucell = (2.0 * lens->aperture) / static_cast<double>(lens->usteps);
+    const double vcell = (2.0 * lens->aperture) / static_cast<double>(lens->vsteps);
+    const double lu = -lens->aperture + ucell * (static_cast<double>(u) + 0.5);
+    const double lv = -lens->aperture + vcell * (static_cast<double>(v) + 0.5);
+    double origin[3], target[3];
+    xform_point(cam->view_inv, lu, lv, 0., origin);
+    xform_point(cam->view_inv, world_x * lens->focal_distance, world_y * lens->focal_distance, -lens->focal_distance, target);
+    const V3 dir = normalize(V3{target[0] - origin[0], target[1] - origin[1], target[2] - origin[2]});
+    ray[0] = origin[0]; ray[1] = origin[1]; ray[2] = origin[2];
+    ray[3] = dir.x; ray[4] = dir.y; ray[5] = dir.z;
+    return RTC_OK;
+}
+
 void rtc_material_default(rtc_material *out) { // material.rs:273-283 + 364-369 (WHITE)
     std::memset(out, 0, sizeof *out);
     out->pattern_kind = RTC_PATTERN_NONE;

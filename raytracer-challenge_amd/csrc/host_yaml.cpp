@@ -18,6 +18,7 @@
 // plain scalars.
 #include "rtc.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -344,6 +345,8 @@ struct Scene {
     uint64_t samples = 0;               // samples of the lights so far
     rtc_camera camera;
     bool have_camera = false;
+    rtc_lens lens{0., 1., 1u, 1u};      // the camera's thin lens; the pinhole (aperture 0, focal distance 1, 1x1) without lens keys
+    int lens_line = 0;                  // line of the camera entry that has lens keys, 0: none
 };
 
 void interpret(const Node &root, Scene &sc) {
@@ -392,6 +395,29 @@ void interpret(const Node &root, Scene &sc) {
                 const double sv = as_number(s, "samples");
                 if (sv < 0 || sv > 255 || sv != static_cast<double>(static_cast<uint32_t>(sv))) fail(s->line, "samples out of bounds"); // lua.rs:172-183
                 sc.camera.samples = static_cast<uint32_t>(sv);
+            }
+            // thin lens (include/rtc.h): aperture / focal-distance / lens-usteps / lens-vsteps
+            sc.lens = rtc_lens{0., 1., 1u, 1u};
+            sc.lens_line = 0;
+            const Node *ap = e.get("aperture"), *fd = e.get("focal-distance"), *lus = e.get("lens-usteps"), *lvs = e.get("lens-vsteps");
+            if (ap || fd || lus || lvs) {
+                sc.lens_line = e.line;
+                if (ap) sc.lens.aperture = as_number(ap, "aperture");
+                if (ap && !fd) fail(e.line, "a camera with an aperture needs a focal-distance");
+                if (fd) sc.lens.focal_distance = as_number(fd, "focal-distance");
+                auto steps = [&](const Node *n, const char *key) {
+                    if (!n) return 1u;
+                    const double v = as_number(n, key);
+                    if (!(v >= 1 && v <= RTC_MAX_LENS_SAMPLES) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                        fail(n->line, std::string(key) + " must be an integer in 1.." + std::to_string(RTC_MAX_LENS_SAMPLES));
+                    return static_cast<uint32_t>(v);
+                };
+                sc.lens.usteps = steps(lus, "lens-usteps");
+                sc.lens.vsteps = steps(lvs, "lens-vsteps");
+                if (!(sc.lens.aperture >= 0.) || !std::isfinite(sc.lens.aperture)) fail(e.line, "aperture must be a finite number >= 0");
+                if (!(sc.lens.focal_distance > 0.) || !std::isfinite(sc.lens.focal_distance)) fail(e.line, "focal-distance must be a finite number > 0");
+                if (rtc_lens_validate(&sc.lens) != RTC_OK)
+                    fail(e.line, "too many lens samples: lens-usteps x lens-vsteps is at most " + std::to_string(RTC_MAX_LENS_SAMPLES));
             }
             sc.have_camera = true;
         } else if (what == "light") {
@@ -460,8 +486,9 @@ extern "C" {
 // rtc_area_light) is given.
 static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out, uint32_t lights_cap,
                             uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only,
-                            rtc_area_light *area_out = nullptr) {
+                            rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
+    if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -474,6 +501,7 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         Scene sc;
         interpret(*root, sc);
         if (sc.area_line && !area_out) fail(sc.area_line, "the scene has an area light: load it with rtc_scene_load_yaml_area_lights");
+        if (sc.lens_line && !lens_out) fail(sc.lens_line, "the scene's camera has a lens: load it with rtc_scene_load_yaml_lens");
         if (!first_only && sc.lights.size() > lights_cap) return RTC_ERR_ARG;
         const size_t bytes = sizeof(rtc_shape) * (sc.shapes.empty() ? 1 : sc.shapes.size());
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(bytes));
@@ -491,6 +519,10 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         }
         *n_lights_out = nl;
         *camera_out = sc.camera;
+        if (lens_out) {
+            *lens_out = sc.lens;
+            *has_lens_out = sc.lens_line ? 1u : 0u;
+        }
         return RTC_OK;
     } catch (const ParseError &e) {
         set_err(errbuf, errbuf_len, e.what());
@@ -520,6 +552,14 @@ rtc_status rtc_scene_load_yaml_area_lights(const char *text, rtc_shape **shapes_
                                            uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
                                            size_t errbuf_len) {
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out);
+}
+
+rtc_status rtc_scene_load_yaml_lens(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                    uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                    size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out) {
+    if (!lens_out || !has_lens_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -558,6 +598,16 @@ rtc_status rtc_scene_load_yaml_area_lights_file(const char *path, rtc_shape **sh
     const rtc_status st = read_file(path, text, errbuf, errbuf_len);
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_area_lights(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len);
+}
+
+rtc_status rtc_scene_load_yaml_lens_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                         uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                         size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_lens(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                    lens_out, has_lens_out);
 }
 
 } // extern "C"

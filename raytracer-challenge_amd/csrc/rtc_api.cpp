@@ -20,7 +20,7 @@
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt);
+                                       const DevLightTable *lt, const DevLens *lens);
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],
                                       hipStream_t stream);
 extern "C" hipError_t rtc_launch_arith(uint32_t op, const double *a, const double *b, uint32_t n, double *out,
@@ -1060,9 +1060,13 @@ static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_
 
 // rows [y0, y1) in tile rows of 8, tile row k at image rows y0 + 8*k*band_stride; grid_y tile rows. gamma > 0: d_rgb8
 // receives Canvas::to_imgbuf's RGBA at that gamma (4 B/pixel) instead of Color::scale's RGB.
+// lens (validated by the caller, one view, no gamma): a thin-lens launch. Its rays do not start at the camera origin, so it
+// runs no binning kernel and no per-view table — tile lists, black tile rows and DevPrim all assume that origin — never
+// takes an LDS source (there are no lens kernels for them), and launches one workgroup per tile, every tile row included.
 static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t y0,
                                 uint32_t y1, uint32_t band_stride, uint32_t grid_y, void *d_rgb, void *d_rgb8,
-                                uint32_t flags, uint32_t nviews = 1, uint32_t view_rows = 0, float gamma = 0.f) {
+                                uint32_t flags, uint32_t nviews = 1, uint32_t view_rows = 0, float gamma = 0.f,
+                                const rtc_lens *lens = nullptr) {
     HIP_TRY(hipSetDevice(ctx->device));
     rtc_world::Gen *gen = nullptr;
     const rtc_status hs = current_gen(w, &gen);
@@ -1086,10 +1090,21 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     P.remaining = RTC_MAX_REFLECTIONS; // render_pixel passes Camera::MAX_REFLECTIONS camera.rs:98
     int src;
     size_t lds_bytes;
-    choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u);
+    choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u || lens != nullptr);
     LaunchLights LL;
     const rtc_status ls = lights_of(G, src, LL);
     if (ls != RTC_OK) return ls;
+    DevLens dlens;
+    if (lens) {
+        if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED; // RTC_FLAG_LDS_TABLE, RTC_SRC=1|2
+        flags &= ~(uint32_t)RTC_FLAG_AA_RESAMPLE;
+        dlens.aperture = lens->aperture;
+        dlens.focal_distance = lens->focal_distance;
+        dlens.ucell = (2.0 * lens->aperture) / static_cast<double>(lens->usteps); // include/rtc.h's order (no contraction in this file)
+        dlens.vcell = (2.0 * lens->aperture) / static_cast<double>(lens->vsteps);
+        dlens.usteps = lens->usteps;
+        dlens.vsteps = lens->vsteps;
+    }
     const int cull = CULL_LEVEL(src);
     const bool refl = G.any_refl || G.any_refr;
     const uint32_t block = RTC_BLOCK_FOR(cull, refl, G.any_refr, false), tile_w = RTC_TILE_W_FOR(cull, refl, G.any_refr, false);
@@ -1134,7 +1149,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
                                                      : launch_pixels >= ctx->bin_small_pixels));
     rtc_world::BinSet *binset = nullptr;
     int bin_set = -1; // which of w->bin this launch's lists are in (rtc_debug_tile_counts)
-    bool bin_ok = bin_this && ctx->binning && (y0 % 8u) == 0u && G.n != 0u;
+    bool bin_ok = bin_this && ctx->binning && (y0 % 8u) == 0u && G.n != 0u && !lens;
     const uint32_t tiles_x = (cam->hsize + 7u) / 8u, tiles_y = (cam->vsize + 7u) / 8u;
     const size_t tiles = (size_t)tiles_x * tiles_y * nviews;
     if (bin_ok && piped) {
@@ -1178,9 +1193,9 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     }
     if (timed) ctx->bin_timed[slot] = P.tile_cnt != nullptr;
     // per-render prologue table of the brute-force variants (the culled kernels do not use it)
-    if (src != SRC_CULL && src != SRC_CULL2) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
+    if (src != SRC_CULL && src != SRC_CULL2 && !lens) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
     P.total_blocks = P.grid_x * P.grid_y * nviews;
-    P.reps = ctx->tiles_per_wg;
+    P.reps = lens ? 1u : ctx->tiles_per_wg;
     // Guided chunks (RenderParams::chunk_wgs): with `slots` workgroups resident at once, the launch's last f x slots tiles go one
     // per workgroup, the f x slots before them two, then three, four, and everything earlier eight (f = RTC_TILES_GUIDED
     // tenths, default 2.0; 0 = off; the largest chunk = RTC_TILES_KMAX). Launches of fewer than 3 rounds of workgroups are left alone.
@@ -1196,7 +1211,7 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         // as this render kernel, and its few waves wait for slots that long-lived workgroups free late — the solo kernel gains
         // 6 %, the pipelined frame loses 9 % (profiles/r03_exp_tiles_per_workgroup.log).
         const bool heavy_binning = G.n > 4096u && launch_pixels < 8000000ull;
-        if (P.reps == 1u && per_level != 0u && nlevels > 1u && P.total_blocks >= 3u * slots && !heavy_binning) {
+        if (P.reps == 1u && per_level != 0u && nlevels > 1u && P.total_blocks >= 3u * slots && !heavy_binning && !lens) {
             unsigned long long rest = P.total_blocks, tiles[5] = {0, 0, 0, 0, 0};
             for (uint32_t l = 0; l < nlevels && rest; ++l) {
                 unsigned long long tk = (l + 1u == nlevels) ? rest : std::min<unsigned long long>(rest, per_level);
@@ -1211,11 +1226,12 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         }
     }
     HIP_TRY(rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, grid_wgs, lds_bytes, stream,
-                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, LL.xl, LL.lt));
+                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, LL.xl, LL.lt, lens ? &dlens : nullptr));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
     HIP_TRY(record_read(w, G, stream, stream_bit));
     ctx->last = rtc_launch_info{(uint32_t)src, (G.any_refl || G.any_refr) ? 1u : 0u, G.any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
-                                P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], LL.lt ? 1u : 0u, {0u}};
+                                P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], LL.lt ? 1u : 0u,
+                                lens ? lens->usteps * lens->vsteps : 0u};
     ++ctx->launches_total;
     ctx->last_bin = rtc_context::LastBin{};
     if (P.tile_cnt && bin_set >= 0) ctx->last_bin = rtc_context::LastBin{w->serial, (uint32_t)bin_set, nviews, tiles_x, tiles_y};
@@ -1245,6 +1261,23 @@ rtc_status rtc_render_rows(rtc_context *ctx, const rtc_world *w, const rtc_camer
     if (cam->samples > 255u) return RTC_ERR_ARG; // antialiasing_samples is a u8 (camera.rs:24)
     if (y0 == y1) return RTC_OK;
     return render_launch(ctx, w, cam, mode, y0, y1, 1u, (y1 - y0 + 7u) / 8u, d_rgb, d_rgb8, flags);
+}
+
+// The checks every lens entry shares (include/rtc.h): a valid lens, one ray per lens sample
+static rtc_status check_lens(const rtc_camera *cam, const rtc_lens *lens) {
+    if (!cam || rtc_lens_validate(lens) != RTC_OK) return RTC_ERR_ARG;
+    if (cam->samples != 1u) return RTC_ERR_ARG; // anti-aliasing and the lens do not compose
+    return RTC_OK;
+}
+
+rtc_status rtc_render_lens_rows(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens, uint32_t mode,
+                                uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags) {
+    if (!ctx || !w || !cam || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
+    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
+    const rtc_status ls = check_lens(cam, lens);
+    if (ls != RTC_OK) return ls;
+    if (y0 == y1) return RTC_OK;
+    return render_launch(ctx, w, cam, mode, y0, y1, 1u, (y1 - y0 + 7u) / 8u, d_rgb, d_rgb8, flags, 1u, 0u, 0.f, lens);
 }
 
 rtc_status rtc_render_bands(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode,
@@ -1491,7 +1524,7 @@ rtc_status rtc_render_views_rgba8(rtc_context *ctx, const rtc_world *w, const rt
 // hipFree, a device sync, per frame), then to `host`. f64: RGB doubles; else 8-bit rows, RGBA at `gamma` when gamma > 0
 // and Color::scale's RGB otherwise (only those rows leave the kernel: no f64 canvas is written).
 static rtc_status render_frame(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, bool f64,
-                               float gamma, void *host, rtc_stats *stats) {
+                               float gamma, void *host, rtc_stats *stats, const rtc_lens *lens = nullptr) {
     if (!ctx || !w || !cam || !host || w->ctx != ctx) return RTC_ERR_ARG;
     if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || cam->samples > 255u) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1502,7 +1535,7 @@ static rtc_status render_frame(rtc_context *ctx, const rtc_world *w, const rtc_c
     if (stats) st = rtc_stats_reset(ctx);
     if (st == RTC_OK)
         st = render_launch(ctx, w, cam, mode, 0, cam->vsize, 1u, (cam->vsize + 7u) / 8u, f64 ? d : nullptr, f64 ? nullptr : d, flags, 1u, 0u,
-                           gamma);
+                           gamma, lens);
     if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE; // pipelined context: the copy below is on the stream
     // `host` from rtc_host_alloc (page-locked) is filled by one DMA at link speed; pageable memory
     // goes through the runtime's bounce buffers (several times slower)
@@ -1520,6 +1553,20 @@ rtc_status rtc_render(rtc_context *ctx, const rtc_world *w, const rtc_camera *ca
 rtc_status rtc_render_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
                            uint8_t *rgb8, rtc_stats *stats) {
     return render_frame(ctx, w, cam, mode, flags, false, 0.f, rgb8, stats);
+}
+
+rtc_status rtc_render_lens(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens, uint32_t mode,
+                           uint32_t flags, double *rgb, rtc_stats *stats) {
+    const rtc_status ls = check_lens(cam, lens);
+    if (ls != RTC_OK) return ls;
+    return render_frame(ctx, w, cam, mode, flags, true, 0.f, rgb, stats, lens);
+}
+
+rtc_status rtc_render_lens_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens, uint32_t mode,
+                                uint32_t flags, uint8_t *rgb8, rtc_stats *stats) {
+    const rtc_status ls = check_lens(cam, lens);
+    if (ls != RTC_OK) return ls;
+    return render_frame(ctx, w, cam, mode, flags, false, 0.f, rgb8, stats, lens);
 }
 
 rtc_status rtc_render_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, float gamma,
@@ -1612,7 +1659,7 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.reps = 1;
         P.chunk_wgs[0] = P.chunk_wgs[1] = P.chunk_wgs[2] = P.chunk_wgs[3] = 0;
         if (st == RTC_OK && rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
-                                             nullptr, LL.xl, LL.lt) != hipSuccess)
+                                             nullptr, LL.xl, LL.lt, nullptr) != hipSuccess)
             st = RTC_ERR_DEVICE;
     }
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)

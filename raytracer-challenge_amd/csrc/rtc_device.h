@@ -163,6 +163,31 @@ struct DevLightTable {
     uint32_t n;        // how many follow the first: 1 .. RTC_DEV_MAX_LIGHT_SAMPLES - 1
 };
 
+// Thin-lens launches (rtc_render_lens*, include/rtc.h): the lens instantiations of k_trace take this block as their LAST
+// argument, behind the tables and behind a multi-light World's DevExtraLights / DevLightTable; every other kernel has no
+// such argument, so its kernarg segment is what it always was. Sample k of a pixel starts at
+// transform_point(view_inv, (lu, lv, 0)) with lu = -aperture + ucell * (k % usteps + 0.5), lv likewise from k / usteps:
+// the same point for every pixel of the launch, so the kernel moves it to SGPRs (uniform_f64) and hands it to make_bundle
+// as the shared apex, exactly where the pinhole kernels have the camera origin.
+// RTC_LENS_UNIFORM_ORIGIN (-DRTC_LENS_UNIFORM_ORIGIN=n through RTC_CXXFLAGS; measurement only) — same pixels
+// for every value:
+//   2 (default) the bundle's apex comes from SGPRs (make_bundle's shared-apex form, spread 0, ordered walk for two-level
+//               Worlds), the exact intersection tests read the ray origin from the VGPRs it was computed in: a VALU
+//               instruction takes one scalar operand, and those tests multiply the origin by a record that is already
+//               scalar;
+//   1           apex AND ray origin from SGPRs (what the pinhole kernels do with the camera origin);
+//   0           off: the origin stays in VGPRs, as a per-lane value would, and the primary bundle is built in make_bundle's
+//               general form (apex = the axis lane's origin, spread measured, no ordered walk).
+#ifndef RTC_LENS_UNIFORM_ORIGIN
+#define RTC_LENS_UNIFORM_ORIGIN 2
+#endif
+enum { RTC_DEV_MAX_LENS_SAMPLES = 256 }; // == RTC_MAX_LENS_SAMPLES (include/rtc.h)
+struct DevLens {
+    double aperture, focal_distance;
+    double ucell, vcell;     // (2.0 * aperture) / (double)usteps, ... / (double)vsteps — divided once, on the host (IEEE: same bits)
+    uint32_t usteps, vsteps; // usteps * vsteps = samples per pixel, 1 .. RTC_DEV_MAX_LENS_SAMPLES
+};
+
 struct RenderParams {
     const DevIsect *isect;
     const uint32_t *kind;

@@ -922,7 +922,11 @@ DEVI V3 lighting(const PP &P, const DevShade *S, const double *m_obj, V3 point, 
 struct LightInt {
     double light_int[3];
 };
-template <class T> DEVI const T &first_of(const T &t) { return t; }
+template <class T, class... R> DEVI const T &first_of(const T &t, const R &...) { return t; }
+template <class T> DEVI const T &last_of(const T &t) { return t; }
+template <class T, class U, class... R> DEVI const auto &last_of(const T &, const U &u, const R &...r) { return last_of(u, r...); }
+// Does k_trace's trailing argument pack end in a DevLens (a thin-lens launch)?
+template <class... T> constexpr bool has_lens_v = (false || ... || __is_same(T, DevLens));
 // Lights 1..n-1 of the multi-light loop, from the kernel arguments (DevExtraLights) or from the World's table in HBM
 // (DevLightTable, 6 doubles per light). `i` is wave-uniform: plain loads, which the compiler may issue as scalar ones.
 DEVI uint32_t further_light_count(const DevExtraLights &X) { return X.n; }
@@ -1056,6 +1060,11 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // lighting(), each with its own is_shadowed_by_light, shape.rs:716). Instantiated only for the sources a multi-light launch
 // takes (SRC_SMEM, SRC_CULL, SRC_CULL2). One DevLightTable instead: the same loop reading the lights from the World's table
 // in HBM (more than RTC_MAX_LIGHTS samples: area lights) — same sources, same flavours, nothing new stored.
+// A DevLens as the LAST element of XL (alone, or behind the lights' block): the thin-lens flavour (LENS, rtc_render_lens*).
+// Every pixel is Color::average_over of usteps * vsteps rays whose origin moves over the lens; the origin of sample k is the
+// same for every pixel, so it takes the camera origin's place as the wave-uniform shared apex of the primary bundle. What
+// assumes the PINHOLE origin is compiled out: the tile lists, the per-view DevPrim table (closest_prim), the black tile-row
+// proof. Same sources as the multi-light kernels, render flavour only (no PROBE, no RGBA); three running sums per lane.
 template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, class... XL>
 __global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
@@ -1063,8 +1072,10 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         const DevIsect *__restrict__ t_isect_s, const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s,
         const uint32_t *__restrict__ t_orig_s, const DevBound *__restrict__ t_gbound, const DevIdEntry *__restrict__ t_idtab,
         const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
-    constexpr bool MULTI = sizeof...(XL) != 0;
-    static_assert(sizeof...(XL) <= 1, "at most one block of further lights");
+    constexpr bool LENS = has_lens_v<XL...>;
+    constexpr bool MULTI = sizeof...(XL) - (LENS ? 1 : 0) != 0;
+    static_assert(sizeof...(XL) <= (LENS ? 2 : 1), "at most one block of further lights, then at most one lens");
+    static_assert(!LENS || ((SRC == SRC_SMEM || IS_CULL(SRC)) && !PROBE && !RGBA), "lens launches take SRC_SMEM, SRC_CULL or SRC_CULL2, f64 / RGB output");
     constexpr uint32_t BLOCK = RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), TILE_W = RTC_TILE_W_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE);
     extern __shared__ double lds_raw[];
     // Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x 4 doubles x
@@ -1151,7 +1162,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     // tile is stored as Canvas::new left it; the primary rays the reference would have cast are still counted (and reported
     // separately, rtc_stats::rays_primary_proven_miss). One-sample renders only.
     bool sky_tile = false;
-    if constexpr (IS_CULL(SRC) && !PROBE) {
+    if constexpr (IS_CULL(SRC) && !PROBE && !LENS) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
         if (Pt.tile_rows != nullptr && Pt.samples == 1u) {
             const uint32_t ity = (Pt.y0 >> 3) + (tbid / Pt.grid_x) * Pt.band_stride;
@@ -1181,8 +1192,15 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
 
     // render_pixel (camera.rs:94-114): one ray, or the 4 fixed sub-samples followed — for the pixels whose
     // samples differ by more than 0.01 from their mean — by `resample_n` more rays (Camera::resample)
-    const bool aa = !probe && P.samples != 1u;
+    const bool aa = !LENS && !probe && P.samples != 1u;
     uint32_t nsamples = aa ? 4u : 1u;   // grows to 4 + resample_n after sample 3 when some lane resamples
+    // thin lens: sample s = lens_v * usteps + lens_u (v outer, u inner), Color::average_over's running sums in registers
+    uint32_t lens_u = 0u, lens_v = 0u;
+    V3 lens_sum = mk(0., 0., 0.);
+    if constexpr (LENS) {
+        const DevLens &LZ = last_of(xl_arg...);
+        nsamples = LZ.usteps * LZ.vsteps;
+    }
     bool lane_resample = false;         // this lane's pixel tripped the test AND the resample is enabled
     // per thread: the four sub-samples (12 doubles) and Color::average_over's running sums (3 doubles)
     double *aa_store = reinterpret_cast<double *>(reinterpret_cast<char *>(lds_raw) + P.aa_lds_off) + threadIdx.x * 15u;
@@ -1201,6 +1219,20 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         // ray origin of every primary ray: transform_point(view_inv, (0,0,0)) camera.rs:72
         V3 cam_origin = xpoint(Pr.vinv, mk(0., 0., 0.));
         cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
+        V3 lens_origin_v = cam_origin; // (lens flavour: the sample's origin as computed, in VGPRs)
+        if constexpr (LENS) {
+            // the lens sample's origin (include/rtc.h): a point of the lens in camera space, the same for every pixel of the
+            // launch — it takes the camera origin's place as ray origin and, moved to SGPRs, as the primary bundle's shared apex
+            // (RTC_LENS_UNIFORM_ORIGIN, rtc_device.h)
+            const DevLens &LZ = last_of(xl_arg...);
+            const double lu = -LZ.aperture + LZ.ucell * ((double)lens_u + 0.5);
+            const double lv = -LZ.aperture + LZ.vcell * ((double)lens_v + 0.5);
+            cam_origin = xpoint(Pr.vinv, mk(lu, lv, 0.0));
+            lens_origin_v = cam_origin;
+            if constexpr (RTC_LENS_UNIFORM_ORIGIN != 0)
+                cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z));
+            if (++lens_u == LZ.usteps) { lens_u = 0u; ++lens_v; }
+        }
         if (probe) {
             const double *rp = P.rays + (size_t)(in_range ? ray_index : 0u) * 6;
             ro = mk(rp[0], rp[1], rp[2]);
@@ -1220,13 +1252,22 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             const double yoffset = ((double)py + yo) * Pr.pixel_size;
             const double world_x = Pr.half_width - xoffset;
             const double world_y = Pr.half_height - yoffset;
+            if constexpr (LENS) { // the pixel's point on the plane in focus
+                const DevLens &LZ = last_of(xl_arg...);
+                const V3 target = xpoint(Pr.vinv, mk(world_x * LZ.focal_distance, world_y * LZ.focal_distance, -LZ.focal_distance));
+                // (RTC_LENS_UNIFORM_ORIGIN == 2: the exact tests read the origin from VGPRs — same bits — and only the bundle's apex from SGPRs)
+                ro = RTC_LENS_UNIFORM_ORIGIN == 2 ? lens_origin_v : cam_origin;
+                rd = vnormalize_plain(vsub(target, ro));
+                shared_origin = RTC_LENS_UNIFORM_ORIGIN != 0;
+            } else {
             const V3 pixel = xpoint(Pr.vinv, mk(world_x, world_y, -1.));
             ro = cam_origin;
             rd = vnormalize_plain(vsub(pixel, cam_origin));
             shared_origin = true;
+            }
         }
 
-        bool tracing = traced && (s < 4u || lane_resample);
+        bool tracing = traced && (LENS || s < 4u || lane_resample);
         bool first = true; // this ray is the one color_at was called with (depth 0)
         int rem = (int)P.remaining;
         int sp = 0;
@@ -1250,17 +1291,17 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             int hidx = -1, hroot = 0;
             Bundle B{}; // every field defined: an undefined field turns into a value carried around the pass loop
             B.off = true;
-            if constexpr (IS_CULL(SRC) && !PROBE) {
+            if constexpr (IS_CULL(SRC) && !PROBE && !LENS) {
                 if (shared_origin && first) tile_lookup();
             }
-            const bool use_bins = binned && shared_origin && first; // (binned is false in the probe and brute-force variants)
+            const bool use_bins = !LENS && binned && shared_origin && first; // (binned is false in the probe and brute-force variants)
             if constexpr (IS_CULL(SRC)) {
                 if (ballot(tracing) != 0ull && !use_bins) {
                     if (shared_origin && first) B = make_bundle<true, false>(tracing, cam_origin, ro, rd, 0.);
                     else B = make_bundle<false, false>(tracing, cam_origin, ro, rd, 0.);
                 }
             }
-            if (!IS_CULL(SRC) && shared_origin && first) {
+            if (!IS_CULL(SRC) && !LENS && shared_origin && first) { // (DevPrim: the CAMERA origin in object space)
                 for_each_object<SRC>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
                     if (tracing) closest_prim(kind, m, pr, rd, j, best, hidx, hroot);
                     return true;
@@ -1802,6 +1843,13 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             const uint32_t tx = wave * 8u + (lane & 7u), ty = lane >> 3; // position inside the tile
             double *slot = stage_f64 + (ty * TILE_W + tx) * 3u;
             if (!traced) result = mk(0., 0., 0.); // Canvas::new BLACK canvas.rs:37-41
+            if constexpr (LENS) { // Color::average_over color.rs:128-139: sums from 0.0 in sample order, one division each
+                lens_sum = vadd(lens_sum, result);
+                if (s + 1u == nsamples) {
+                    const double l = (double)nsamples;
+                    result = mk(lens_sum.x / l, lens_sum.y / l, lens_sum.z / l);
+                }
+            }
             if (aa) {
                 // aa_store[12..14] hold Color::average_over's running sums (reds = ((0 + c0) + c1) + ..., color.rs:128-139)
                 // while a lane still collects samples, and the pixel's final colour afterwards
@@ -2438,26 +2486,53 @@ static hipError_t launch_one(const RenderParams &P, dim3 grid, size_t lds_bytes,
 
 // `xl`: NULL for a World with one light; else its lights 1..n-1 (xl->n >= 1), and src one of SRC_SMEM, SRC_CULL, SRC_CULL2.
 // `lt` (instead of `xl`, never both): the same lights as a device table (lt->rec holds lt->n records, rtc_device.h).
+// `lens`: non-NULL for a thin-lens launch (render flavour, src one of SRC_SMEM, SRC_CULL, SRC_CULL2, no gamma table).
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt) {
+                                       const DevLightTable *lt, const DevLens *lens) {
     const dim3 grid(nblocks);
+    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
+    if (xl != nullptr && (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u)) return hipErrorInvalidValue;
+    if (lt != nullptr && (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u)) return hipErrorInvalidValue;
+    if (lens != nullptr) {
+        if (P->rays != nullptr || P->gamma != nullptr || P->samples != 1u || lens->usteps == 0u || lens->vsteps == 0u ||
+            (unsigned long long)lens->usteps * lens->vsteps > RTC_MAX_LENS_SAMPLES)
+            return hipErrorInvalidValue;
+#define RTC_LENS_CASE(S, ...)                                                                                                        \
+    if (src == S) {                                                                                                                  \
+        if (refr) return launch_kernel<S, true, true, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__, *lens);      \
+        if (refl) return launch_kernel<S, true, false, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__, *lens);     \
+        return launch_kernel<S, false, false, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__, *lens);              \
+    }
+        if (xl != nullptr) {
+            RTC_LENS_CASE(SRC_SMEM, *xl)
+            RTC_LENS_CASE(SRC_CULL, *xl)
+            RTC_LENS_CASE(SRC_CULL2, *xl)
+        } else if (lt != nullptr) {
+            RTC_LENS_CASE(SRC_SMEM, *lt)
+            RTC_LENS_CASE(SRC_CULL, *lt)
+            RTC_LENS_CASE(SRC_CULL2, *lt)
+        } else {
+            RTC_LENS_CASE(SRC_SMEM)
+            RTC_LENS_CASE(SRC_CULL)
+            RTC_LENS_CASE(SRC_CULL2)
+        }
+#undef RTC_LENS_CASE
+        return hipErrorInvalidValue;
+    }
 #define RTC_CASE(S, ...)                                                                            \
     if (src == S) {                                                                            \
         if (refr) return launch_one<S, true, true>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);               \
         if (refl) return launch_one<S, true, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);              \
         return launch_one<S, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);                       \
     }
-    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
     if (xl != nullptr) {
-        if (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u) return hipErrorInvalidValue;
         RTC_CASE(SRC_SMEM, *xl)
         RTC_CASE(SRC_CULL, *xl)
         RTC_CASE(SRC_CULL2, *xl)
         return hipErrorInvalidValue;
     }
     if (lt != nullptr) {
-        if (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u) return hipErrorInvalidValue;
         RTC_CASE(SRC_SMEM, *lt)
         RTC_CASE(SRC_CULL, *lt)
         RTC_CASE(SRC_CULL2, *lt)

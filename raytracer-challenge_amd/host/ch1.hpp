@@ -427,6 +427,18 @@ class Camera { // camera.rs:17-160
         return c;
     }
     void set_samples(uint8_t n) { antialiasing_samples = n; }
+    // Thin lens, depth of field (rtc_lens, include/rtc.h): a square lens of half-width `aperture`, sampled at the centres of
+    // usteps x vsteps cells, in focus `focal_distance` in front of the camera. With a lens set, render / render_async and
+    // their rgb8 forms go through rtc_render_lens / rtc_render_lens_rgb8 (antialiasing_samples must be 1; the rgba8 forms
+    // have no lens entry and throw). Not part of the reference's Camera.
+    void set_lens(double aperture, double focal_distance, uint32_t usteps = 1, uint32_t vsteps = 1) {
+        const rtc_lens l{aperture, focal_distance, usteps, vsteps};
+        check(rtc_lens_validate(&l), "Camera::set_lens");
+        lens_ = l;
+        has_lens_ = true;
+    }
+    void clear_lens() { has_lens_ = false; }
+    bool has_lens() const { return has_lens_; }
     std::pair<Point, Vector> ray_for_pixel(uint32_t x, uint32_t y) const { // camera.rs:78-82
         double r[6];
         rtc_camera_ray_for_pixel(&flat_, x, 0.5, y, 0.5, r);
@@ -450,7 +462,8 @@ class Camera { // camera.rs:17-160
         c.samples = antialiasing_samples;
         Canvas canvas(hsize, vsize);
         World::Uploaded up(w);
-        check(rtc_render(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
+        if (has_lens_) check(rtc_render_lens(Device::get(), up.w, &c, &lens_, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
+        else check(rtc_render(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
         return canvas;
     }
     Canvas run8(const World &w, uint32_t mode) const {
@@ -458,18 +471,22 @@ class Camera { // camera.rs:17-160
         c.samples = antialiasing_samples;
         Canvas canvas = Canvas::quantised(hsize, vsize);
         World::Uploaded up(w);
-        check(rtc_render_rgb8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
+        if (has_lens_) check(rtc_render_lens_rgb8(Device::get(), up.w, &c, &lens_, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
+        else check(rtc_render_rgb8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
         return canvas;
     }
     Canvas run_rgba8(const World &w, uint32_t mode, float gamma) const {
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
+        if (has_lens_) check(RTC_ERR_UNSUPPORTED, "Camera::render_rgba8 with a lens");
         Canvas canvas = Canvas::imgbuf(hsize, vsize, gamma);
         World::Uploaded up(w);
         check(rtc_render_rgba8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, gamma, canvas.rgba8.data(), nullptr), "Camera::render_rgba8");
         return canvas;
     }
     rtc_camera flat_{};
+    rtc_lens lens_{0., 1., 1u, 1u};
+    bool has_lens_ = false;
 };
 
 namespace detail {

@@ -23,7 +23,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     if m:
         tag = "k_trace<%s,refl=%s,refr=%s,probe=%s" % m.groups()[:4] + (",rgba" if m.group(5) == "1" else "")
         # the instantiations for Worlds with several lights: in the kernel arguments, or in the World's device table
-        tag += ",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">"
+        tag += ",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else ""
+        tag += ",lens>" if "DevLens" in name else ">"  # the thin-lens flavour (rtc_render_lens*)
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
