@@ -368,6 +368,24 @@ rtc_status  rtc_scene_load_yaml_lens_file(const char *path, rtc_shape **shapes_o
                                           struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
                                           rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
                                           struct rtc_lens *lens_out, uint32_t *has_lens_out);
+/* Scenes with motion blur (struct rtc_motion, below). YAML: a shape key `motion:` takes a transform list in the
+ * `transform:` vocabulary — the shape's transform at the shutter's close is that list applied on top of its `transform:`,
+ * by the same left-multiplication (transform_open = the shape's transform) — and `add: camera` takes `shutter-samples`
+ * (an integer in 1..RTC_MAX_SHUTTER_SAMPLES, default 1). These entries are rtc_scene_load_yaml_lens plus the motions:
+ * *motions_out is a malloc'ed array (rtc_free) of *n_motions_out records in file order, *samples_out the shutter samples.
+ * Every other YAML entry returns RTC_ERR_PARSE for a scene with those keys, with a message naming these. The camera does
+ * not move in a scene file (rtc_shutter_scene::cam_close is for callers of the C-ABI). */
+struct rtc_motion;
+rtc_status  rtc_scene_load_yaml_motion(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                       struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                       rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                       struct rtc_lens *lens_out, uint32_t *has_lens_out,
+                                       struct rtc_motion **motions_out, uint32_t *n_motions_out, uint32_t *samples_out);
+rtc_status  rtc_scene_load_yaml_motion_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                            struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                            rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                            struct rtc_lens *lens_out, uint32_t *has_lens_out,
+                                            struct rtc_motion **motions_out, uint32_t *n_motions_out, uint32_t *samples_out);
 /* Every light of job `index` as an area light. RTC_ERR_ARG when cap is too small. */
 rtc_status  rtc_lua_program_job_area_lights(const rtc_lua_program *prog, uint32_t index, struct rtc_area_light *lights_out,
                                             uint32_t cap, uint32_t *n_out);
@@ -731,6 +749,88 @@ rtc_status  rtc_render_lens(rtc_context *ctx, const rtc_world *w, const rtc_came
                             uint32_t mode, uint32_t flags, double *rgb, rtc_stats *stats);
 rtc_status  rtc_render_lens_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens,
                                  uint32_t mode, uint32_t flags, uint8_t *rgb8, rtc_stats *stats);
+
+/* Motion blur: shutter-averaged frames. A motion-blurred frame IS Color::average_over (color.rs:128-139) of n ordinary
+ * frames of the World at n shutter times, the cell centres of the shutter interval [0, 1]:
+ *     t_k = ((double)k + 0.5) / (double)n                    k = 0..n-1, 1 <= n <= RTC_MAX_SHUTTER_SAMPLES
+ *     lerp(a, b, t) = (a == b) ? a : a + (b - a) * t         per matrix element, f64, no fused multiply-add (an element
+ *                                                            that does not move keeps its bits, signed zeros included)
+ * Sub-frame k of a scene (shapes, motions, lights, cam_open, cam_close, lens, n):
+ *   - a shape without a motion record is used verbatim, its `inv` / `inv_t` (and a stale transpose) included;
+ *   - a shape with one keeps kind, world_id and material; inv = rtc_matrix_inverse(M_k) with M_k[i] = lerp(open[i],
+ *     close[i], t_k) and inv_t = transpose(inv): what rtc_shape_init computes from M_k. An index out of range or a shape
+ *     named twice is RTC_ERR_ARG, a singular M_k for any k RTC_ERR_SINGULAR;
+ *   - cam_close == NULL is a static camera; otherwise both cameras agree in every field but view_inv (else RTC_ERR_ARG)
+ *     and cam_k is cam_open with view_inv[i] = lerp(open, close, t_k);
+ *   - the lights (rtc_area_light, the general World form; rtc_area_light_from_point for point lights) do not move;
+ *   - the sub-frame is rtc_render of that World and camera, or rtc_render_lens with a lens (cam->samples must then be 1).
+ * The frame is, per component, a sum that starts at 0.0, adds sub-frames 0..n-1 in that order and is divided once by
+ * (double)n. NO JITTER: the shutter times are the cell centres. INTERPOLATION IS ELEMENT-WISE: translations and scalings
+ * are followed exactly, a rotation is sheared between its end points (the chord, not the arc) — keep the shutter short
+ * against the rotation, or cut the move into several frames. */
+#define RTC_MAX_SHUTTER_SAMPLES 256u
+#define RTC_SHUTTER_RING 8u            /* sub-frame canvases a shutter keeps on the device */
+typedef struct rtc_motion {            /* one moving shape */
+    uint32_t shape;                    /* index into the shape list */
+    uint32_t _pad;
+    double   transform_open[16];       /* the OBJECT transform (not its inverse) at t = 0 */
+    double   transform_close[16];      /* ... at t = 1 */
+} rtc_motion;
+/* [host] t_k above; NaN unless k < n <= RTC_MAX_SHUTTER_SAMPLES. */
+double      rtc_shutter_time(uint32_t n, uint32_t k);
+/* [host] The shapes of sub-frame k into out[0..n_shapes) (out may not overlap shapes). RTC_ERR_ARG: a NULL pointer
+ * (motions may be NULL when n_motions == 0), samples outside 1..RTC_MAX_SHUTTER_SAMPLES, k >= samples, a motion index out
+ * of range or named twice. RTC_ERR_SINGULAR: M_k of a moving shape has no inverse. */
+rtc_status  rtc_shutter_shapes(const rtc_shape *shapes, uint32_t n_shapes, const rtc_motion *motions, uint32_t n_motions,
+                               uint32_t samples, uint32_t k, rtc_shape *out);
+/* [host] The camera of sub-frame k. close == NULL: *out = *open. RTC_ERR_ARG: NULL open / out, samples or k as above,
+ * cameras that differ in anything but view_inv. */
+rtc_status  rtc_shutter_camera(const rtc_camera *open, const rtc_camera *close, uint32_t samples, uint32_t k, rtc_camera *out);
+/* [host] Color::average_over of n frames: `frames` = n consecutive frames of `count` doubles; out[i] = (((0.0 +
+ * frames[0][i]) + frames[1][i]) + ...) / (double)n. A mean that is a NaN is stored as the quiet NaN 0x7FF8000000000000:
+ * IEEE 754 leaves the sign and payload of a NaN to the platform (inf - inf is negative on x86-64 and positive on gfx950),
+ * and host and device must agree in every byte. n = 1..RTC_MAX_SHUTTER_SAMPLES; n = 0, n above that or a NULL pointer is
+ * RTC_ERR_ARG. out may not overlap frames. */
+rtc_status  rtc_canvas_average(const double *frames, uint32_t n, size_t count, double *out);
+/* [device] The same bytes as rtc_canvas_average for frames already in device memory (8-byte aligned), by k_average_over
+ * (csrc/rtc_shutter.hip): RTC_SHUTTER_RING frames per pass, added in sample order to the sum carried in d_out. Enqueued on
+ * the context's stream (after launches of a pipelined context: rtc_context_fence first). d_out must not overlap the frames. */
+rtc_status  rtc_canvas_average_device(rtc_context *ctx, const void *d_frames, uint32_t n, size_t count, void *d_out);
+/* [device] A shutter is bound to a context, like the encoders. It owns a World of its own, created by its first frame and
+ * kept current with rtc_world_update_area_lights (the caller's Worlds are never touched), and grow-only scratch of at most
+ * RTC_SHUTTER_RING f64 sub-frame canvases, one f64 sum canvas and the 8-bit output, however many samples are asked for.
+ * The sub-frames are ordinary launches (rtc_render_rows / rtc_render_lens_rows), back to back on the device — on the
+ * lanes of a pipelined context — into the ring; whenever the ring is full, and behind the last sub-frame, ONE pass of
+ * k_average_over adds the ring to the sum in sample order, and the last pass divides and writes the outputs asked for:
+ * only the finished mean, or its 8-bit form, crosses PCIe. The whole scene is validated for every k before anything is
+ * launched. rtc_stats counters are the sums over the sub-frames, `pixels` included; rtc_launch_info describes the last
+ * sub-frame's launch. Flags follow the sub-frame entry: RTC_FLAG_NO_CULL gives the same bytes, RTC_FLAG_LDS_TABLE with a
+ * lens or several lights is RTC_ERR_UNSUPPORTED.
+ *   render / render_rgb8 / render_rgba8: the mean in host memory — vsize*hsize*3 doubles, Color::scale of the mean
+ *     (vsize*hsize*3 bytes) or to_imgbuf of the mean at `gamma` (vsize*hsize*4 bytes). Synchronous; `stats` may be NULL.
+ *   render_device: any non-empty subset of the three outputs into DEVICE buffers (d_rgb 8-byte aligned); `gamma` is read
+ *     only with d_rgba8. An 8-bit-only caller's f64 mean is never written to HBM. The result is ordered on the context's
+ *     stream: rtc_image_encoder_encode_device may follow directly. */
+typedef struct rtc_shutter_scene {
+    const rtc_shape      *shapes;  uint32_t n_shapes;
+    const rtc_motion     *motions; uint32_t n_motions;  /* motions may be NULL when n_motions == 0 */
+    const rtc_area_light *lights;  uint32_t n_lights;
+    const rtc_camera     *cam_open, *cam_close;         /* cam_close may be NULL */
+    const rtc_lens       *lens;                         /* may be NULL */
+    uint32_t              samples;                      /* 1..RTC_MAX_SHUTTER_SAMPLES */
+    uint32_t              _pad;
+} rtc_shutter_scene;             /* 80 bytes */
+typedef struct rtc_shutter rtc_shutter;
+rtc_status  rtc_shutter_create(rtc_context *ctx, rtc_shutter **out);
+void        rtc_shutter_destroy(rtc_shutter *s);
+rtc_status  rtc_shutter_render(rtc_shutter *s, const rtc_shutter_scene *scene, uint32_t mode, uint32_t flags, double *rgb,
+                               rtc_stats *stats);
+rtc_status  rtc_shutter_render_rgb8(rtc_shutter *s, const rtc_shutter_scene *scene, uint32_t mode, uint32_t flags, uint8_t *rgb8,
+                                    rtc_stats *stats);
+rtc_status  rtc_shutter_render_rgba8(rtc_shutter *s, const rtc_shutter_scene *scene, uint32_t mode, uint32_t flags, float gamma,
+                                     uint8_t *rgba8, rtc_stats *stats);
+rtc_status  rtc_shutter_render_device(rtc_shutter *s, const rtc_shutter_scene *scene, uint32_t mode, uint32_t flags, float gamma,
+                                      void *d_rgb, void *d_rgb8, void *d_rgba8);
 
 /* Camera::render / render_async for canvas rows [y0, y1) into a DEVICE buffer of
  * (y1-y0)*hsize*3 doubles (row y0 first). Enqueues on the context stream and returns

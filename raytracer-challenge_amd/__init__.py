@@ -17,9 +17,9 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
-                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, PATTERNS, STATUS_NAMES, declare)
+                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare)
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librtc.so"
@@ -309,6 +309,64 @@ def lens_ray(cam: RtcCamera, lens: RtcLens, x: int, y: int, k: int) -> np.ndarra
     return np.array(list(out))
 
 
+def motion(shape_index: int, open_transform: Matrix, close_transform: Matrix) -> RtcMotion:
+    """One moving shape of a motion-blurred frame (rtc_motion, include/rtc.h): shape `shape_index` of the World has the
+    OBJECT transform `open_transform` when the shutter opens and `close_transform` when it closes; in between the matrix is
+    interpolated element by element (exact for translations and scalings; a rotation is sheared: keep the shutter short)."""
+    m = RtcMotion()
+    m.shape = int(shape_index)
+    C.memmove(m.transform_open, open_transform.m, C.sizeof(Mat16))
+    C.memmove(m.transform_close, close_transform.m, C.sizeof(Mat16))
+    return m
+
+
+def _motion_array(motions):
+    motions = list(motions or [])
+    arr = (RtcMotion * max(1, len(motions)))()
+    for i, m in enumerate(motions):
+        arr[i] = m
+    return arr, len(motions)
+
+
+def shutter_time(n: int, k: int) -> float:
+    """t_k = (k + 0.5) / n, the centre of cell k of the shutter interval (rtc_shutter_time); NaN unless k < n <= 256."""
+    return float(lib().rtc_shutter_time(n, k))
+
+
+def shutter_shapes(world: "World", motions, samples: int, k: int) -> "World":
+    """The World of sub-frame k of a motion-blurred frame (rtc_shutter_shapes): `world` with every moving shape's inverse
+    recomputed from its interpolated transform; shapes without a motion record and the lights are copied as they are."""
+    arr, n = world.array(), len(world.shapes)
+    marr, nm = _motion_array(motions)
+    out = (RtcShape * max(1, n))()
+    _check(lib().rtc_shutter_shapes(arr, n, marr, nm, samples, k, out), "rtc_shutter_shapes")
+    w = World(list(world.lights))
+    for i in range(n):
+        s = RtcShape()
+        C.memmove(C.byref(s), C.byref(out[i]), C.sizeof(RtcShape))
+        w.shapes.append(s)
+    return w
+
+
+def shutter_camera(cam: RtcCamera, cam_close, samples: int, k: int) -> RtcCamera:
+    """The camera of sub-frame k (rtc_shutter_camera): `cam` with view_inv interpolated towards `cam_close` (None: static)."""
+    out = RtcCamera()
+    _check(lib().rtc_shutter_camera(C.byref(cam), C.byref(cam_close) if cam_close is not None else None, samples, k, C.byref(out)), "rtc_shutter_camera")
+    return out
+
+
+def canvas_average(frames) -> np.ndarray:
+    """Color::average_over of whole frames on the host (rtc_canvas_average): `frames` = (n, ...) float64, n = 1..256; the
+    result has the shape of one frame. Sums start at 0.0, add in frame order and are divided once by n."""
+    a = np.ascontiguousarray(frames, dtype=np.float64)
+    if a.ndim < 1:
+        raise ValueError("frames must be an (n, ...) array")
+    out = np.empty(a.shape[1:], dtype=np.float64)
+    P = C.POINTER(C.c_double)
+    _check(lib().rtc_canvas_average(a.ctypes.data_as(P), a.shape[0], out.size, out.ctypes.data_as(P)), "rtc_canvas_average")
+    return out
+
+
 def _copy_lights(arr, n: int) -> list:
     out = []
     for i in range(n):
@@ -360,6 +418,33 @@ def load_yaml_lens(text: str | None = None, path: str | None = None):
         w.shapes.append(s)
     lib().rtc_free(shapes)
     return w, cam, (ln if has.value else None)
+
+
+def load_yaml_motion(text: str | None = None, path: str | None = None):
+    """load_yaml_lens for scenes with motion blur (a shape's `motion:` transform list, the camera's `shutter-samples`):
+    -> (World, RtcCamera, RtcLens or None, [RtcMotion], samples) — what Shutter.render takes."""
+    shapes, mots = C.POINTER(RtcShape)(), C.POINTER(RtcMotion)()
+    n, nm, samples = C.c_uint32(0), C.c_uint32(0), C.c_uint32(1)
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
+    err = C.create_string_buffer(512)
+    ln, has = RtcLens(), C.c_uint32(0)
+    fn = lib().rtc_scene_load_yaml_motion_file if path is not None else lib().rtc_scene_load_yaml_motion
+    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
+            err, 512, C.byref(ln), C.byref(has), C.byref(mots), C.byref(nm), C.byref(samples))
+    _check(st, "rtc_scene_load_yaml_motion", err.value.decode(errors="replace"))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
+    for i in range(n.value):
+        s = RtcShape()
+        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
+        w.shapes.append(s)
+    motions = []
+    for i in range(nm.value):
+        m = RtcMotion()
+        C.memmove(C.byref(m), C.byref(mots[i]), C.sizeof(RtcMotion))
+        motions.append(m)
+    lib().rtc_free(shapes)
+    lib().rtc_free(mots)
+    return w, cam, (ln if has.value else None), motions, samples.value
 
 
 class LuaJob:
@@ -1058,6 +1143,15 @@ class Context:
         buffer `d_out` (height x width x 4 bytes), enqueued on the context's stream (rtc_canvas_to_rgba8_device)."""
         _check(lib().rtc_canvas_to_rgba8_device(self._h, d_ptr, width, height, gamma, d_out), "rtc_canvas_to_rgba8_device")
 
+    def shutter(self) -> "Shutter":
+        """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
+        return Shutter(self)
+
+    def canvas_average_device(self, d_frames: int, n: int, count: int, d_out: int) -> None:
+        """canvas_average of n frames of `count` doubles at DEVICE address `d_frames` into the device buffer `d_out`, enqueued
+        on the context's stream (rtc_canvas_average_device): the same bytes as the host function."""
+        _check(lib().rtc_canvas_average_device(self._h, C.c_void_p(d_frames), n, count, C.c_void_p(d_out)), "rtc_canvas_average_device")
+
     def device_arith(self, op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.float64)
         bb = np.ascontiguousarray(b if b is not None else a, dtype=np.float64)
@@ -1350,6 +1444,72 @@ class ImageEncoder(_Encoder):
         return self.bytes()
 
 
+class Shutter(_Encoder):
+    """Motion blur on the GPU (rtc_shutter, include/rtc.h): a frame is Color::average_over of `samples` ordinary frames of
+    the World at the shutter's cell centres, rendered back to back on the device and averaged by one kernel; only the mean,
+    or its 8-bit form, crosses PCIe. `motions` is a list of rtc.motion records (or None), `cam_close` the camera at the
+    shutter's close (None: the camera stands still), `lens` a thin lens (rtc.lens; cam.samples must then be 1). The shutter
+    keeps a World of its own: `world` is the host-side World, and no DeviceWorld of the caller is touched."""
+    _kind = "shutter"
+    bytes = write = None   # a shutter delivers frames, not a file
+
+    def _scene(self, world: World, motions, cam: RtcCamera, samples: int, cam_close, lens):
+        sc = RtcShutterScene()
+        shapes, lights = world.array(), world.area_light_array()
+        marr, nm = _motion_array(motions)
+        sc.shapes, sc.n_shapes = shapes, len(world.shapes)
+        sc.motions, sc.n_motions = marr, nm
+        sc.lights, sc.n_lights = lights, len(world.lights)
+        sc.cam_open = C.pointer(cam)
+        if cam_close is not None:
+            sc.cam_close = C.pointer(cam_close)
+        if lens is not None:
+            sc.lens = C.pointer(lens)
+        sc.samples = int(samples)
+        return sc, (shapes, lights, marr)   # the arrays the scene points into
+
+    def _host(self, entry: str, shape, dtype, scene_args, mode, flags, with_stats, out, extra=()):
+        cam = scene_args[2]
+        if out is None:
+            out = np.empty((cam.vsize, cam.hsize) + shape, dtype=dtype)
+        elif out.shape != (cam.vsize, cam.hsize) + shape or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous (vsize, hsize, {shape[0]}) {np.dtype(dtype).name} array")
+        sc, _keep = self._scene(*scene_args)
+        st = RtcStats()
+        ptr = out.ctypes.data_as(C.POINTER(C.c_double if dtype == np.float64 else C.c_uint8))
+        _check(getattr(lib(), entry)(self._h, C.byref(sc), mode, flags, *extra, ptr, C.byref(st) if with_stats else None), entry)
+        if with_stats:
+            d = _stats_dict(st, True)
+            d["rays_primary_proven_miss"] = st.rays_primary_proven_miss
+            return out, d
+        return out
+
+    def render(self, world: World, motions, cam: RtcCamera, samples: int, cam_close=None, lens=None, mode: int = MODE_RENDER_ASYNC,
+               flags: int = 0, with_stats: bool = False, out: np.ndarray | None = None):
+        """The motion-blurred frame as a (vsize, hsize, 3) float64 array (rtc_shutter_render). Stats are the sums over the
+        sub-frames."""
+        return self._host("rtc_shutter_render", (3,), np.float64, (world, motions, cam, samples, cam_close, lens), mode, flags, with_stats, out)
+
+    def render_rgb8(self, world: World, motions, cam: RtcCamera, samples: int, cam_close=None, lens=None, mode: int = MODE_RENDER_ASYNC,
+                    flags: int = 0, with_stats: bool = False, out: np.ndarray | None = None):
+        """Color::scale of the mean, (vsize, hsize, 3) uint8, quantised on the device (rtc_shutter_render_rgb8)."""
+        return self._host("rtc_shutter_render_rgb8", (3,), np.uint8, (world, motions, cam, samples, cam_close, lens), mode, flags, with_stats, out)
+
+    def render_rgba8(self, world: World, motions, cam: RtcCamera, samples: int, gamma: float = 1.0, cam_close=None, lens=None,
+                     mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False, out: np.ndarray | None = None):
+        """to_imgbuf of the mean at `gamma`, (vsize, hsize, 4) uint8 (rtc_shutter_render_rgba8)."""
+        return self._host("rtc_shutter_render_rgba8", (4,), np.uint8, (world, motions, cam, samples, cam_close, lens), mode, flags, with_stats, out,
+                          extra=(C.c_float(gamma),))
+
+    def render_device(self, world: World, motions, cam: RtcCamera, samples: int, d_rgb: int | None = None, d_rgb8: int | None = None,
+                      d_rgba8: int | None = None, gamma: float = 1.0, cam_close=None, lens=None, mode: int = MODE_RENDER_ASYNC,
+                      flags: int = 0) -> None:
+        """The frame into DEVICE buffers, any non-empty subset of the f64 mean (`d_rgb`), Color::scale's bytes (`d_rgb8`) and
+        to_imgbuf's RGBA at `gamma` (`d_rgba8`); ordered on the context's stream, no host wait (rtc_shutter_render_device)."""
+        sc, _keep = self._scene(world, motions, cam, samples, cam_close, lens)
+        _check(lib().rtc_shutter_render_device(self._h, C.byref(sc), mode, flags, gamma, d_rgb, d_rgb8, d_rgba8), "rtc_shutter_render_device")
+
+
 def host_canvas_rgb8(vsize: int, hsize: int) -> np.ndarray:
     """A zeroed (vsize, hsize, 3) uint8 frame in page-locked memory (rtc_host_alloc)."""
     arr = np.frombuffer(_Pinned(vsize * hsize * 3).buf, dtype=np.uint8).reshape(vsize, hsize, 3)
@@ -1531,8 +1691,8 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray",
-           "load_yaml", "load_yaml_lens", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+           "load_yaml", "load_yaml_lens", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",
-           "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcLens", "RtcMaterial", "RtcShape", "RtcStats"]
+           "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcLens", "RtcMotion", "RtcMaterial", "RtcShape", "RtcStats"]

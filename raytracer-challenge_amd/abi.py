@@ -15,6 +15,8 @@ GROUP_ID_BYTES = 128
 MAX_LIGHTS = 8
 MAX_LIGHT_SAMPLES = 256
 MAX_LENS_SAMPLES = 256
+MAX_SHUTTER_SAMPLES = 256
+SHUTTER_RING = 8
 PATTERNS = {"none": 0, "test": 1, "stripe": 2, "stripes": 2, "gradient": 3, "ring": 4, "checker": 5, "checkers": 5, "grid": 6}
 STATUS_NAMES = {0: "RTC_OK", 1: "RTC_ERR_SINGULAR", 2: "RTC_ERR_NO_COLOR", 3: "RTC_ERR_DEVICE", 4: "RTC_ERR_ARG",
                 5: "RTC_ERR_PARSE", 6: "RTC_ERR_IO", 7: "RTC_ERR_NOMEM", 8: "RTC_ERR_UNSUPPORTED"}
@@ -47,6 +49,16 @@ class RtcCamera(C.Structure):
     _fields_ = [("hsize", C.c_uint32), ("vsize", C.c_uint32), ("fov", C.c_double), ("half_width", C.c_double),
                 ("half_height", C.c_double), ("pixel_size", C.c_double), ("view_inv", Mat16), ("samples", C.c_uint32),
                 ("_pad", C.c_uint32)]
+
+
+class RtcMotion(C.Structure):
+    _fields_ = [("shape", C.c_uint32), ("_pad", C.c_uint32), ("transform_open", Mat16), ("transform_close", Mat16)]
+
+
+class RtcShutterScene(C.Structure):
+    _fields_ = [("shapes", C.POINTER(RtcShape)), ("n_shapes", C.c_uint32), ("motions", C.POINTER(RtcMotion)), ("n_motions", C.c_uint32),
+                ("lights", C.POINTER(RtcAreaLight)), ("n_lights", C.c_uint32), ("cam_open", C.POINTER(RtcCamera)),
+                ("cam_close", C.POINTER(RtcCamera)), ("lens", C.POINTER(RtcLens)), ("samples", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class RtcStats(C.Structure):
@@ -89,6 +101,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
 
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24
+assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -201,6 +214,23 @@ PROTOTYPES = {
                                              C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
     "rtc_scene_load_yaml_lens_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_motion": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                               C.POINTER(C.POINTER(RtcMotion)), C.POINTER(U32), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_motion_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                    C.POINTER(C.POINTER(RtcMotion)), C.POINTER(U32), C.POINTER(U32)]),
+    "rtc_shutter_time": (D, [U32, U32]),
+    "rtc_shutter_shapes": (C.c_int32, [C.POINTER(RtcShape), U32, C.POINTER(RtcMotion), U32, U32, U32, C.POINTER(RtcShape)]),
+    "rtc_shutter_camera": (C.c_int32, [C.POINTER(RtcCamera), C.POINTER(RtcCamera), U32, U32, C.POINTER(RtcCamera)]),
+    "rtc_canvas_average": (C.c_int32, [PD, U32, C.c_size_t, PD]),
+    "rtc_canvas_average_device": (C.c_int32, [VP, VP, U32, C.c_size_t, VP]),
+    "rtc_shutter_create": (C.c_int32, [VP, C.POINTER(VP)]),
+    "rtc_shutter_destroy": (None, [VP]),
+    "rtc_shutter_render": (C.c_int32, [VP, C.POINTER(RtcShutterScene), U32, U32, PD, C.POINTER(RtcStats)]),
+    "rtc_shutter_render_rgb8": (C.c_int32, [VP, C.POINTER(RtcShutterScene), U32, U32, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_shutter_render_rgba8": (C.c_int32, [VP, C.POINTER(RtcShutterScene), U32, U32, C.c_float, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_shutter_render_device": (C.c_int32, [VP, C.POINTER(RtcShutterScene), U32, U32, C.c_float, VP, VP, VP]),
     "rtc_lua_program_job_area_lights": (C.c_int32, [C.c_void_p, U32, C.POINTER(RtcAreaLight), U32, C.POINTER(U32)]),
     "rtc_free": (None, [VP]),
     "rtc_canvas_write_ppm": (C.c_int32, [C.c_char_p, PD, U32, U32]),

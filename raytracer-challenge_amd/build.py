@@ -17,7 +17,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "librtc.so"
 
-SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp"]
+SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 COMMON += os.environ.get("RTC_CXXFLAGS", "").split()  # experiments, e.g. -DRTC_WAVES_PER_SIMD=4
 # Kernel file only: MachineLICM hoists the VGPR materialisation of every f64 literal (pow's ~25
@@ -115,6 +115,21 @@ def build_facade_lens_test(force: bool = False) -> Path:
     """Compile tests/cpp/test_facade_lens.cpp (the facade's Camera::set_lens) against librtc.so."""
     src = ROOT / "tests" / "cpp" / "test_facade_lens.cpp"
     exe = ROOT / "build" / "test_facade_lens"
+    hdr = PKG / "host" / "ch1.hpp"
+    if not src.exists() or not hdr.exists():
+        return None
+    exe.parent.mkdir(parents=True, exist_ok=True)
+    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
+        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
+               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
+        subprocess.run(cmd, check=True)
+    return exe
+
+
+def build_facade_shutter_test(force: bool = False) -> Path:
+    """Compile tests/cpp/test_facade_shutter.cpp (the facade's World::set_shape_motion / Camera::set_shutter) against librtc.so."""
+    src = ROOT / "tests" / "cpp" / "test_facade_shutter.cpp"
+    exe = ROOT / "build" / "test_facade_shutter"
     hdr = PKG / "host" / "ch1.hpp"
     if not src.exists() or not hdr.exists():
         return None

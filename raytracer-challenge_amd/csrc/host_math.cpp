@@ -353,6 +353,102 @@ rtc_status rtc_shape_init(uint32_t kind, const double transform[16], const rtc_m
     return RTC_OK;
 }
 
+// ---- motion blur: the normative shutter arithmetic (include/rtc.h); mul, add and div in the stated order (this file is
+// compiled with -ffp-contract=off) ----
+
+static bool shutter_ok(uint32_t n, uint32_t k) { return n >= 1u && n <= RTC_MAX_SHUTTER_SAMPLES && k < n; }
+
+static void shutter_lerp(const double a[16], const double b[16], double t, double out[16]) {
+    for (int i = 0; i < 16; ++i) out[i] = (a[i] == b[i]) ? a[i] : a[i] + (b[i] - a[i]) * t;
+}
+
+// Every motion names a shape of the list, none twice.
+static rtc_status shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes) {
+    if (n_motions && !motions) return RTC_ERR_ARG;
+    for (uint32_t i = 0; i < n_motions; ++i) {
+        if (motions[i].shape >= n_shapes) return RTC_ERR_ARG;
+        for (uint32_t j = 0; j < i; ++j)
+            if (motions[j].shape == motions[i].shape) return RTC_ERR_ARG;
+    }
+    return RTC_OK;
+}
+
+double rtc_shutter_time(uint32_t n, uint32_t k) {
+    if (!shutter_ok(n, k)) return std::nan("");
+    return (static_cast<double>(k) + 0.5) / static_cast<double>(n);
+}
+
+rtc_status rtc_shutter_shapes(const rtc_shape *shapes, uint32_t n_shapes, const rtc_motion *motions, uint32_t n_motions,
+                              uint32_t samples, uint32_t k, rtc_shape *out) {
+    if ((n_shapes && (!shapes || !out)) || !shutter_ok(samples, k)) return RTC_ERR_ARG;
+    const rtc_status ms = shutter_check_motions(motions, n_motions, n_shapes);
+    if (ms != RTC_OK) return ms;
+    const double t = rtc_shutter_time(samples, k);
+    for (uint32_t i = 0; i < n_shapes; ++i) out[i] = shapes[i];
+    for (uint32_t i = 0; i < n_motions; ++i) {
+        double m[16];
+        shutter_lerp(motions[i].transform_open, motions[i].transform_close, t, m);
+        rtc_shape &s = out[motions[i].shape];
+        const rtc_status st = rtc_matrix_inverse(m, s.inv); // what rtc_shape_init computes from M_k
+        if (st != RTC_OK) return st;
+        rtc_matrix_transpose(s.inv, s.inv_t);
+    }
+    return RTC_OK;
+}
+
+// rtc_shutter_shapes' verdict for EVERY k of the shutter, without building the shapes (csrc/rtc_shutter.cpp validates a
+// whole frame before its first launch). Not part of include/rtc.h.
+rtc_status rtc_shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes, uint32_t samples) {
+    if (!shutter_ok(samples, 0u)) return RTC_ERR_ARG;
+    const rtc_status ms = shutter_check_motions(motions, n_motions, n_shapes);
+    if (ms != RTC_OK) return ms;
+    for (uint32_t k = 0; k < samples; ++k) {
+        const double t = rtc_shutter_time(samples, k);
+        for (uint32_t i = 0; i < n_motions; ++i) {
+            double m[16], inv[16];
+            shutter_lerp(motions[i].transform_open, motions[i].transform_close, t, m);
+            const rtc_status st = rtc_matrix_inverse(m, inv);
+            if (st != RTC_OK) return st;
+        }
+    }
+    return RTC_OK;
+}
+
+rtc_status rtc_shutter_camera(const rtc_camera *open, const rtc_camera *close, uint32_t samples, uint32_t k, rtc_camera *out) {
+    if (!open || !out || !shutter_ok(samples, k)) return RTC_ERR_ARG;
+    if (!close) {
+        *out = *open;
+        return RTC_OK;
+    }
+    // every field but view_inv (and the padding); the doubles bit for bit
+    if (open->hsize != close->hsize || open->vsize != close->vsize || open->samples != close->samples ||
+        std::memcmp(&open->fov, &close->fov, sizeof(double)) != 0 || std::memcmp(&open->half_width, &close->half_width, sizeof(double)) != 0 ||
+        std::memcmp(&open->half_height, &close->half_height, sizeof(double)) != 0 ||
+        std::memcmp(&open->pixel_size, &close->pixel_size, sizeof(double)) != 0)
+        return RTC_ERR_ARG;
+    const double t = rtc_shutter_time(samples, k);
+    rtc_camera c = *open;
+    shutter_lerp(open->view_inv, close->view_inv, t, c.view_inv);
+    *out = c;
+    return RTC_OK;
+}
+
+// Color::average_over (color.rs:128-139) of whole frames: sums from 0.0 in frame order, one division each.
+rtc_status rtc_canvas_average(const double *frames, uint32_t n, size_t count, double *out) {
+    if (!frames || !out || n == 0u || n > RTC_MAX_SHUTTER_SAMPLES) return RTC_ERR_ARG;
+    const double d = static_cast<double>(n);
+    const uint64_t nan_bits = 0x7FF8000000000000ull;
+    double kQuietNaN;
+    std::memcpy(&kQuietNaN, &nan_bits, sizeof kQuietNaN);
+    for (size_t i = 0; i < count; ++i) {
+        double s = 0.0;
+        for (uint32_t f = 0; f < n; ++f) s = s + frames[(size_t)f * count + i];
+        const double m = s / d;
+        out[i] = (m != m) ? kQuietNaN : m; // one NaN for every platform (include/rtc.h)
+    }
+    return RTC_OK;
+}
+
 void rtc_free(void *p) { std::free(p); }
 
 } // extern "C"

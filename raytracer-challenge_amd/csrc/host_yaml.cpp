@@ -347,6 +347,9 @@ struct Scene {
     bool have_camera = false;
     rtc_lens lens{0., 1., 1u, 1u};      // the camera's thin lens; the pinhole (aperture 0, focal distance 1, 1x1) without lens keys
     int lens_line = 0;                  // line of the camera entry that has lens keys, 0: none
+    std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
+    uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
+    int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
 };
 
 void interpret(const Node &root, Scene &sc) {
@@ -419,6 +422,15 @@ void interpret(const Node &root, Scene &sc) {
                 if (rtc_lens_validate(&sc.lens) != RTC_OK)
                     fail(e.line, "too many lens samples: lens-usteps x lens-vsteps is at most " + std::to_string(RTC_MAX_LENS_SAMPLES));
             }
+            // motion blur (include/rtc.h): shutter-samples
+            sc.shutter_samples = 1u;
+            if (const Node *ss = e.get("shutter-samples")) {
+                const double v = as_number(ss, "shutter-samples");
+                if (!(v >= 1 && v <= RTC_MAX_SHUTTER_SAMPLES) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                    fail(ss->line, "shutter-samples must be an integer in 1.." + std::to_string(RTC_MAX_SHUTTER_SAMPLES));
+                sc.shutter_samples = static_cast<uint32_t>(v);
+                if (!sc.motion_line) sc.motion_line = e.line;
+            }
             sc.have_camera = true;
         } else if (what == "light") {
             rtc_area_light a;
@@ -462,6 +474,16 @@ void interpret(const Node &root, Scene &sc) {
             const rtc_status st = rtc_shape_init(kind, xf, &mat, &s);
             if (st != RTC_OK) fail(e.line, what + ": " + rtc_strerror(st));
             s.world_id = static_cast<uint32_t>(sc.shapes.size()) + 1; // World::add_shape shape.rs:661-667
+            if (const Node *mv = e.get("motion")) { // motion blur: the transform at the shutter's close = this list on top of the shape's
+                rtc_motion m;
+                std::memset(&m, 0, sizeof m);
+                m.shape = static_cast<uint32_t>(sc.shapes.size());
+                std::memcpy(m.transform_open, xf, sizeof xf);
+                std::memcpy(m.transform_close, xf, sizeof xf);
+                build_transform(defs, mv, m.transform_close);
+                sc.motions.push_back(m);
+                if (!sc.motion_line) sc.motion_line = e.line;
+            }
             sc.shapes.push_back(s);
         } else {
             fail(add->line, "Invalid shape type: " + what); // lua.rs:322-326
@@ -486,12 +508,18 @@ extern "C" {
 // rtc_area_light) is given.
 static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out, uint32_t lights_cap,
                             uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only,
-                            rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr) {
+                            rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr,
+                            rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
+    if (motions_out) {
+        *motions_out = nullptr;
+        *n_motions_out = 0;
+        *samples_out = 1u;
+    }
     try {
         Parser p;
         p.lines = split_lines(text);
@@ -502,10 +530,22 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         interpret(*root, sc);
         if (sc.area_line && !area_out) fail(sc.area_line, "the scene has an area light: load it with rtc_scene_load_yaml_area_lights");
         if (sc.lens_line && !lens_out) fail(sc.lens_line, "the scene's camera has a lens: load it with rtc_scene_load_yaml_lens");
+        if (sc.motion_line && !motions_out) fail(sc.motion_line, "the scene has motion blur (motion / shutter-samples): load it with rtc_scene_load_yaml_motion");
         if (!first_only && sc.lights.size() > lights_cap) return RTC_ERR_ARG;
+        rtc_motion *marr = nullptr;
+        if (motions_out) {
+            marr = static_cast<rtc_motion *>(std::malloc(sizeof(rtc_motion) * (sc.motions.empty() ? 1 : sc.motions.size())));
+            if (!marr) return RTC_ERR_NOMEM;
+            if (!sc.motions.empty()) std::memcpy(marr, sc.motions.data(), sizeof(rtc_motion) * sc.motions.size());
+        }
         const size_t bytes = sizeof(rtc_shape) * (sc.shapes.empty() ? 1 : sc.shapes.size());
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(bytes));
-        if (!arr) return RTC_ERR_NOMEM;
+        if (!arr) { std::free(marr); return RTC_ERR_NOMEM; }
+        if (motions_out) {
+            *motions_out = marr;
+            *n_motions_out = static_cast<uint32_t>(sc.motions.size());
+            *samples_out = sc.shutter_samples;
+        }
         if (!sc.shapes.empty()) std::memcpy(arr, sc.shapes.data(), sizeof(rtc_shape) * sc.shapes.size());
         *shapes_out = arr;
         *n_out = static_cast<uint32_t>(sc.shapes.size());
@@ -562,6 +602,15 @@ rtc_status rtc_scene_load_yaml_lens(const char *text, rtc_shape **shapes_out, ui
                      lens_out, has_lens_out);
 }
 
+rtc_status rtc_scene_load_yaml_motion(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                      uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                      size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_motion **motions_out,
+                                      uint32_t *n_motions_out, uint32_t *samples_out) {
+    if (!lens_out || !has_lens_out || !motions_out || !n_motions_out || !samples_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out, motions_out, n_motions_out, samples_out);
+}
+
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
     if (!path) return RTC_ERR_ARG;
     std::FILE *f = std::fopen(path, "rb");
@@ -608,6 +657,17 @@ rtc_status rtc_scene_load_yaml_lens_file(const char *path, rtc_shape **shapes_ou
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_lens(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                     lens_out, has_lens_out);
+}
+
+rtc_status rtc_scene_load_yaml_motion_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                           size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_motion **motions_out,
+                                           uint32_t *n_motions_out, uint32_t *samples_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_motion(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                      lens_out, has_lens_out, motions_out, n_motions_out, samples_out);
 }
 
 } // extern "C"

@@ -1575,6 +1575,11 @@ rtc_status rtc_render_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_came
     return render_frame(ctx, w, cam, mode, flags, false, gamma, rgba8, stats);
 }
 
+rtc_status rtc_gamma_table_on_stream(rtc_context *ctx, float gamma, const DevGamma **out) {
+    if (!ctx || !out || !gamma_ok(gamma)) return RTC_ERR_ARG;
+    return gamma_table(ctx, gamma, ctx->stream, rtc_context::MAX_LANES, out);
+}
+
 rtc_status rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint32_t width, uint32_t rows, float gamma, void *d_rgba8) {
     if (!ctx || !d_rgb || !d_rgba8 || !gamma_ok(gamma) || ((size_t)d_rgb % sizeof(double)) != 0) return RTC_ERR_ARG;
     const size_t n = (size_t)width * rows;

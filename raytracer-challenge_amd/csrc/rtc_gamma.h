@@ -9,6 +9,7 @@
 //   * host_ppm.cpp     — builds the table, and pins this lookup against rtc_canvas_to_rgba8 in the CPU tests,
 //   * rtc_kernels.hip  — k_trace's RGBA epilogue and k_canvas_to_rgba8 (the f32 estimate below is a guess only: every
 //                        byte is decided by comparisons with the table),
+//   * rtc_shutter.hip  — k_average_over's RGBA output (the mean of a motion-blurred frame),
 //   * rtc_api.cpp      — the context's per-gamma cache of tables in device memory.
 #ifndef RTC_GAMMA_H
 #define RTC_GAMMA_H
@@ -55,5 +56,28 @@ RTC_GHD uint32_t rtc_gamma_byte_with(const DevGamma *g, double c, uint32_t guess
     }
     return rtc_gamma_count(g->t, c, guess);
 }
+
+#if defined(__HIPCC__)
+// The two 8-bit channels of the device: k_trace's epilogues, k_canvas_to_rgba8 (rtc_kernels.hip), k_average_over (rtc_shutter.hip).
+
+// Color::scale(component, 255) color.rs:100-114: `(c * 255.0) as i32` (truncating, saturating,
+// NaN -> 0) then clamp to [0, 255].
+__device__ inline __attribute__((always_inline)) unsigned char scale255(double c) {
+    const double v = c * 255.0;
+    if (!(v >= 0.0)) return 0;   // negative (truncates to <= 0, clamps to 0) or NaN
+    if (v >= 255.0) return 255;  // saturates / clamps
+    return (unsigned char)(int)v; // v_cvt_i32_f64 truncates toward zero
+}
+
+// Canvas::to_imgbuf's channel, scale255(c.powf(1/gamma)) (canvas.rs:61-79, color.rs:55-65), from the launch's threshold
+// table. The f32 estimate only picks which table entries to compare first; the byte is decided by the
+// comparisons (an 8-step binary search when the estimate missed), so it equals the host's bit for bit.
+__device__ inline __attribute__((always_inline)) unsigned char gamma_byte(const DevGamma *g, double c) {
+    const float cf = (float)__builtin_fabs(c);
+    const float v = __builtin_amdgcn_exp2f(g->e * __builtin_amdgcn_logf(cf)) * 255.0f; // v_log_f32 / v_exp_f32
+    const uint32_t guess = v >= 1.0f ? (v < 255.0f ? (uint32_t)v : 255u) : 0u;          // NaN -> 0
+    return (unsigned char)rtc_gamma_byte_with(g, c, guess);
+}
+#endif
 
 #endif

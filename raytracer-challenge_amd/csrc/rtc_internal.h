@@ -184,6 +184,24 @@ extern "C" hipError_t rtc_launch_light_lists_built(uint32_t n, uint32_t cap, con
                                                    hipStream_t stream);
 extern "C" rtc_status rtc_gamma_build_table(float gamma, DevGamma *g); // host_ppm.cpp
 extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
+// k_average_over (rtc_shutter.hip): one pass of Color::average_over over whole canvases. Adds frames[f * stride + i], f = 0..nf-1
+// in that order, to the carried sum (sum_in, NULL: 0.0) for i < count. divisor == 0: stores the sum to f64_out. Otherwise the
+// last pass: divides by `divisor` and writes whichever of f64_out (the mean), rgb8 (Color::scale, 3 B/pixel) and rgba8
+// (to_imgbuf through `g`, 4 B/pixel) are not NULL; the 8-bit outputs need count % 3 == 0. sum_in may equal f64_out.
+struct AverageArgs {
+    const double *frames;
+    const double *sum_in;
+    double *f64_out;
+    unsigned char *rgb8, *rgba8;
+    const DevGamma *g;
+    size_t stride, count;
+    double divisor;
+    uint32_t nf; // 1..RTC_SHUTTER_RING
+};
+extern "C" hipError_t rtc_launch_average_over(const AverageArgs *a, hipStream_t stream);
+extern "C" rtc_status rtc_shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes, uint32_t samples); // host_math.cpp
+// The device table of `gamma` for work enqueued next on the context's own stream (rtc_api.cpp keeps the per-gamma cache).
+extern "C" rtc_status rtc_gamma_table_on_stream(rtc_context *ctx, float gamma, const DevGamma **out);
 extern "C" hipError_t rtc_launch_undeal(const void *staging, void *canvas, uint32_t nranks, uint32_t nframes, uint32_t H,
                                         uint32_t rows_max, size_t row_bytes, hipStream_t stream);
 

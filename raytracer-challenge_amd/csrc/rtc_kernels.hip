@@ -986,24 +986,7 @@ template <> struct FrameT<false> {
     double kr;
 };
 
-// Color::scale(component, 255) color.rs:100-114: `(c * 255.0) as i32` (truncating, saturating,
-// NaN -> 0) then clamp to [0, 255].
-DEVI unsigned char scale255(double c) {
-    const double v = c * 255.0;
-    if (!(v >= 0.0)) return 0;   // negative (truncates to <= 0, clamps to 0) or NaN
-    if (v >= 255.0) return 255;  // saturates / clamps
-    return (unsigned char)(int)v; // v_cvt_i32_f64 truncates toward zero
-}
-
-// Canvas::to_imgbuf's channel, scale255(c.powf(1/gamma)) (canvas.rs:61-79, color.rs:55-65), from the launch's threshold
-// table (rtc_gamma.h). The f32 estimate only picks which table entries to compare first; the byte is decided by the
-// comparisons (an 8-step binary search when the estimate missed), so it equals the host's bit for bit.
-DEVI unsigned char gamma_byte(const DevGamma *g, double c) {
-    const float cf = (float)__builtin_fabs(c);
-    const float v = __builtin_amdgcn_exp2f(g->e * __builtin_amdgcn_logf(cf)) * 255.0f; // v_log_f32 / v_exp_f32
-    const uint32_t guess = v >= 1.0f ? (v < 255.0f ? (uint32_t)v : 255u) : 0u;          // NaN -> 0
-    return (unsigned char)rtc_gamma_byte_with(g, c, guess);
-}
+// scale255 (Color::scale(component, 255)) and gamma_byte (Canvas::to_imgbuf's channel): rtc_gamma.h, shared with rtc_shutter.hip
 
 // The RGBA form of a tile's 8-bit store (Canvas::to_imgbuf: R, G, B, alpha 255 — canvas.rs:74): `rows` x `cols` pixels of
 // the 3-byte staging (rows SRC_STRIDE bytes apart) to rows orow0.. / columns px0.. of `out8` (4 B/pixel, W pixels per row),

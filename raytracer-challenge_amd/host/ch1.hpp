@@ -125,8 +125,9 @@ struct Material { // material.rs:244-369
 struct Shape {
     rtc_shape flat;
     Material material;
+    Matrix transform = Matrix::identity(); // the object transform `flat.inv` was made from (World::set_shape_motion starts there)
     static Shape make(uint32_t kind, const Matrix &m, const Material &mat) {
-        Shape s; s.material = mat;
+        Shape s; s.material = mat; s.transform = m;
         const rtc_material fm = mat.flatten();
         check(rtc_shape_init(kind, m.m.data(), &fm, &s.flat), "Shape::new_with_transform_and_material");
         return s;
@@ -137,6 +138,7 @@ struct Shape {
     // (shape.rs:446-449, 535-538): kept.
     void set_transform(const Matrix &m) {
         check(rtc_matrix_inverse(m.m.data(), flat.inv), "Shape::set_transform");
+        transform = m;
         double t[16];
         rtc_matrix_transpose(flat.kind == RTC_SPHERE ? flat.inv : flat.inv_t, t);
         std::memcpy(flat.inv_t, t, sizeof t);
@@ -317,6 +319,17 @@ class World { // shape.rs:633-795
         all.insert(all.end(), more_lights.begin(), more_lights.end());
         return all;
     }
+    // Motion blur (rtc_motion, include/rtc.h): shape i moves from its own transform, when the shutter opens, to
+    // `transform_at_close`, when it closes; a Camera with set_shutter renders the World averaged over that move, any other
+    // Camera renders it as the shutter opens. Setting it again replaces the move; clear_shape_motions stops every shape.
+    World &set_shape_motion(size_t i, const Matrix &transform_at_close) {
+        if (i >= shapes.size()) check(RTC_ERR_ARG, "World::set_shape_motion");
+        for (auto &mv : motions)
+            if (mv.first == i) { mv.second = transform_at_close; return *this; }
+        motions.emplace_back(i, transform_at_close);
+        return *this;
+    }
+    void clear_shape_motions() { motions.clear(); }
     Shape &get_shape_mut(size_t i) { dirty_ = true; return shapes.at(i); }
     const Shape &get_shape(size_t i) const { return shapes.at(i); }
 
@@ -333,6 +346,7 @@ class World { // shape.rs:633-795
     std::vector<Light> more_lights; // lights()[1..]
     std::vector<rtc_area_light> area_lights; // add_area_light: behind the point lights
     std::vector<Shape> shapes;
+    std::vector<std::pair<size_t, Matrix>> motions; // set_shape_motion: (shape, its transform as the shutter closes)
     uint32_t last_world_id = 0;
 
     // The flattened World resident in HBM. Camera::render(&World) takes the World by reference on every call
@@ -439,6 +453,16 @@ class Camera { // camera.rs:17-160
     }
     void clear_lens() { has_lens_ = false; }
     bool has_lens() const { return has_lens_; }
+    // Motion blur (rtc_shutter, include/rtc.h): with a shutter set, every render form — the lens and render_rgba8 with a
+    // lens included — is the mean of `samples` frames (1..RTC_MAX_SHUTTER_SAMPLES) of the World at the cell centres of the
+    // shutter interval, its shapes moved as World::set_shape_motion says, rendered and averaged on the device by one
+    // process-wide rtc_shutter. Not part of the reference's Camera.
+    void set_shutter(uint32_t samples) {
+        if (samples == 0 || samples > RTC_MAX_SHUTTER_SAMPLES) check(RTC_ERR_ARG, "Camera::set_shutter");
+        shutter_ = samples;
+    }
+    void clear_shutter() { shutter_ = 0; }
+    uint32_t shutter() const { return shutter_; } // 0: none
     std::pair<Point, Vector> ray_for_pixel(uint32_t x, uint32_t y) const { // camera.rs:78-82
         double r[6];
         rtc_camera_ray_for_pixel(&flat_, x, 0.5, y, 0.5, r);
@@ -461,6 +485,11 @@ class Camera { // camera.rs:17-160
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Canvas canvas(hsize, vsize);
+        if (shutter_) {
+            Exposure e(w, c, has_lens_ ? &lens_ : nullptr, shutter_);
+            check(rtc_shutter_render(Exposure::shutter(), &e.scene, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
+            return canvas;
+        }
         World::Uploaded up(w);
         if (has_lens_) check(rtc_render_lens(Device::get(), up.w, &c, &lens_, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
         else check(rtc_render(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
@@ -470,6 +499,11 @@ class Camera { // camera.rs:17-160
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Canvas canvas = Canvas::quantised(hsize, vsize);
+        if (shutter_) {
+            Exposure e(w, c, has_lens_ ? &lens_ : nullptr, shutter_);
+            check(rtc_shutter_render_rgb8(Exposure::shutter(), &e.scene, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
+            return canvas;
+        }
         World::Uploaded up(w);
         if (has_lens_) check(rtc_render_lens_rgb8(Device::get(), up.w, &c, &lens_, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
         else check(rtc_render_rgb8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
@@ -478,15 +512,70 @@ class Camera { // camera.rs:17-160
     Canvas run_rgba8(const World &w, uint32_t mode, float gamma) const {
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
+        if (shutter_) { // (this path has a lens entry: the mean's RGBA is made by the averaging kernel)
+            Canvas canvas = Canvas::imgbuf(hsize, vsize, gamma);
+            Exposure e(w, c, has_lens_ ? &lens_ : nullptr, shutter_);
+            check(rtc_shutter_render_rgba8(Exposure::shutter(), &e.scene, mode, RTC_FLAG_NONE, gamma, canvas.rgba8.data(), nullptr), "Camera::render_rgba8");
+            return canvas;
+        }
         if (has_lens_) check(RTC_ERR_UNSUPPORTED, "Camera::render_rgba8 with a lens");
         Canvas canvas = Canvas::imgbuf(hsize, vsize, gamma);
         World::Uploaded up(w);
         check(rtc_render_rgba8(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, gamma, canvas.rgba8.data(), nullptr), "Camera::render_rgba8");
         return canvas;
     }
+    // One motion-blurred frame's scene (rtc_shutter_scene) with the arrays it points into, and the process-wide shutter.
+    struct Exposure {
+        std::vector<rtc_shape> flat;
+        std::vector<rtc_motion> moves;
+        std::vector<rtc_area_light> lights;
+        rtc_camera cam;
+        rtc_shutter_scene scene{};
+        Exposure(const World &w, const rtc_camera &c, const rtc_lens *lens, uint32_t samples) : cam(c) {
+            for (const Shape &s : w.shapes) {
+                rtc_shape f = s.flat;
+                f.material = s.material.flatten();
+                flat.push_back(f);
+            }
+            for (const auto &mv : w.motions) {
+                rtc_motion m{};
+                m.shape = static_cast<uint32_t>(mv.first);
+                std::memcpy(m.transform_open, w.shapes.at(mv.first).transform.m.data(), sizeof m.transform_open);
+                std::memcpy(m.transform_close, mv.second.m.data(), sizeof m.transform_close);
+                moves.push_back(m);
+            }
+            for (const Light &wl : w.lights()) { // the World's sample list: its point lights, then its area lights
+                rtc_light l;
+                l.intensity[0] = wl.intensity.red; l.intensity[1] = wl.intensity.green; l.intensity[2] = wl.intensity.blue;
+                l.position[0] = wl.position.x; l.position[1] = wl.position.y; l.position[2] = wl.position.z;
+                rtc_area_light a;
+                check(rtc_area_light_from_point(&l, &a), "World lights");
+                lights.push_back(a);
+            }
+            lights.insert(lights.end(), w.area_lights.begin(), w.area_lights.end());
+            scene.shapes = flat.data(); scene.n_shapes = static_cast<uint32_t>(flat.size());
+            scene.motions = moves.data(); scene.n_motions = static_cast<uint32_t>(moves.size());
+            scene.lights = lights.data(); scene.n_lights = static_cast<uint32_t>(lights.size());
+            scene.cam_open = &cam; scene.cam_close = nullptr;
+            scene.lens = lens;
+            scene.samples = samples;
+        }
+        Exposure(const Exposure &) = delete;
+        Exposure &operator=(const Exposure &) = delete;
+        static rtc_shutter *shutter() {
+            struct Holder {
+                rtc_shutter *s = nullptr;
+                Holder() { check(rtc_shutter_create(Device::get(), &s), "rtc_shutter_create"); } // (the context is constructed first, destroyed last)
+                ~Holder() { rtc_shutter_destroy(s); }
+            };
+            static Holder h;
+            return h.s;
+        }
+    };
     rtc_camera flat_{};
     rtc_lens lens_{0., 1., 1u, 1u};
     bool has_lens_ = false;
+    uint32_t shutter_ = 0;
 };
 
 namespace detail {
