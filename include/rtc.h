@@ -1204,6 +1204,73 @@ rtc_status  rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *ray
 rtc_status  rtc_device_arith(rtc_context *ctx, uint32_t op, const double *a, const double *b,
                              uint32_t n, double *out);
 
+/* ==== arbitrary output variables (AOVs): what a pixel SAW ============================== */
+/* Besides its colour a frame can say, per pixel, which object the pixel's ray hit, how far away, where, with which
+ * normal, and how many of the World's light samples are hidden from that point: image planes for picking, masks, depth
+ * compositing and debugging ("why is this pixel black?"), rendered by a small kernel of their own (k_aov,
+ * csrc/rtc_kernels.hip) that runs the primary pass and — only when asked — the shadow passes, and shades nothing.
+ *
+ * For pixel (x, y) the AOV ray is rtc_camera_ray_for_pixel(cam, x, 0.5, y, 0.5): the CENTRE ray, whatever cam->samples
+ * says (centre-sample AOVs beside an anti-aliased colour frame). Let Hit be that ray's rtc_hit as rtc_color_at defines it:
+ * Intersections::get_hit (the smallest t >= 0.0, ties to the lower shape index) with the vectors of
+ * Intersection::compute_vectors. The planes are row-major, idx = y*hsize + x:
+ *
+ *   plane    type        pixel that hits                                   pixel that misses
+ *   index    int32_t     Hit.hit_index                                     -1
+ *   depth    double      Hit.t                                             +infinity
+ *   point    double[3]   Hit.point                                         0.0, 0.0, 0.0
+ *   normal   double[3]   Hit.normal (after the `inside` flip)              0.0, 0.0, 0.0
+ *   flags    uint8_t     1 | (Hit.inside << 1)                             0
+ *   shadow   uint16_t    number of the World's light samples i (all        0
+ *                        rtc_world_light_count(w) of them, in order) with
+ *                        is_shadowed_by_light(Hit.over_point, L[i])
+ *
+ * For a one-light World `shadow` is Hit.shadowed.
+ *   Modes.   RTC_MODE_RENDER gives the pixels of the last row and the last column the miss values: that is where
+ *            Camera::render leaves the canvas black.
+ *   Flags.   RTC_FLAG_NO_CULL gives the same bytes. RTC_FLAG_LDS_TABLE is RTC_ERR_UNSUPPORTED. RTC_FLAG_AA_RESAMPLE is
+ *            ignored.
+ *   Planes.  A NULL plane pointer means "not wanted": that plane is neither computed nor written. With shadow == NULL no
+ *            shadow ray is cast. All six NULL is RTC_ERR_ARG.
+ *   Counters. AOV launches do not touch rtc_stats: they are not renders of the reference.
+ *   Worlds.  Every World form works: one light, several, area lights (up to RTC_MAX_LIGHTS samples in the kernel
+ *            arguments, more from the World's device table), and updated Worlds.
+ *   Ordering. The launch goes on the context's stream and waits for a pending rtc_world_update build exactly as
+ *            rtc_color_at does. After launches of a pipelined context call rtc_context_fence first
+ *            (rtc_canvas_to_rgba8_device's rule). */
+typedef struct rtc_aov_buffers {   /* 48 bytes; NULL = plane not wanted */
+    int32_t *index; double *depth; double *point; double *normal; uint8_t *flags; uint16_t *shadow;
+} rtc_aov_buffers;
+enum { RTC_AOV_VIEW_DEPTH = 0, RTC_AOV_VIEW_NORMAL = 1, RTC_AOV_VIEW_INDEX = 2, RTC_AOV_VIEW_SHADOW = 3 };
+
+/* [host] the normative packing: per-pixel hit records (+ per-pixel shadowed-sample counts, may be NULL = use
+ * hits[i].shadowed) into the planes above, mode rule included. RTC_ERR_ARG: NULL hits / out, all six planes NULL, a mode
+ * that does not exist. */
+rtc_status  rtc_aov_from_hits(const rtc_hit *hits, const uint16_t *shadow_counts, uint32_t width, uint32_t height,
+                              uint32_t mode, const rtc_aov_buffers *out);
+/* [device] enqueue; buffers are DEVICE pointers (depth/point/normal 8-byte aligned, index 4, shadow 2) */
+rtc_status  rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                  const rtc_aov_buffers *d);
+/* [device] the same into HOST buffers; synchronous; scratch is grow-only and owned by the context (rtc_devmem.h) */
+rtc_status  rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                           const rtc_aov_buffers *host);
+/* A plane as an 8-bit RGB picture (height*width*3 bytes) that every existing encoder takes. The rules are f64 with no
+ * fused multiply-add; scale = Color::scale(c, 255) (rtc_color_scale255: truncating, saturating, NaN gives 0).
+ *   DEPTH   needs `depth`. All three channels are scale((far - t) / (far - near)): +inf gives 0, t <= near gives 255.
+ *           near and far must be finite with far > near, otherwise RTC_ERR_ARG.
+ *   NORMAL  needs `normal`. Channel c is scale((n_c + 1.0) * 0.5); a miss is the neutral 127, 127, 127.
+ *   INDEX   needs `index`. A miss (index < 0) is black. Otherwise z = splitmix64((uint64_t)index) — the function written
+ *           out at rtc_camera.samples — and r = (z & 255) | 0x40, g = ((z >> 8) & 255) | 0x40, b = ((z >> 16) & 255) | 0x40.
+ *   SHADOW  needs `shadow`. All channels are scale(1.0 - (double)count / (double)n_lights). n_lights == 0 is RTC_ERR_ARG.
+ * A view whose plane is NULL, or a view that does not exist, is RTC_ERR_ARG. near, far and n_lights are read only by the
+ * views that name them. */
+rtc_status  rtc_aov_view_rgb8(uint32_t view, const rtc_aov_buffers *b, uint32_t width, uint32_t height,
+                              double near, double far, uint32_t n_lights, uint8_t *rgb8);            /* [host], normative */
+/* [device] the same bytes for planes in DEVICE memory, by k_aov_view (one thread per pixel), enqueued on the context's
+ * stream: rtc_image_encoder_encode_device may follow directly. */
+rtc_status  rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_aov_buffers *d, uint32_t width, uint32_t height,
+                                     double near, double far, uint32_t n_lights, void *d_rgb8);      /* [device], same bytes */
+
 #ifdef __cplusplus
 }
 #endif

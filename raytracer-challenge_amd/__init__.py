@@ -19,7 +19,8 @@ import numpy as np
 
 from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
-                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare)
+                  EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
+                  RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW)
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librtc.so"
@@ -1031,6 +1032,72 @@ def write_ppm(path, rgb: np.ndarray) -> None:
 # ---------------------------------------------------------------------------------------
 # device side
 # ---------------------------------------------------------------------------------------
+# ---- AOV planes (include/rtc.h, "arbitrary output variables") ----------------------------------------------------------
+def _aov_view_id(view) -> int:
+    return AOV_VIEWS[view] if isinstance(view, str) else int(view)
+
+
+def _aov_arrays(planes, height: int, width: int) -> dict:
+    """Fresh host arrays for the named planes: (H, W) or (H, W, 3), dtypes of include/rtc.h."""
+    out = {}
+    for name in planes:
+        dtype, comps = AOV_PLANES[name]  # KeyError: not a plane
+        out[name] = np.empty((height, width) if comps == 1 else (height, width, comps), dtype=dtype)
+    if not out:
+        raise ValueError("at least one AOV plane must be asked for")
+    return out
+
+
+def _aov_buffers(addresses: dict) -> RtcAovBuffers:
+    """rtc_aov_buffers from {plane: address}; planes that are missing or None stay NULL (not wanted)."""
+    b = RtcAovBuffers()
+    for name, addr in addresses.items():
+        if name not in AOV_PLANES:
+            raise KeyError(name)
+        setattr(b, name, addr)
+    return b
+
+
+def _aov_host_buffers(arrays: dict) -> RtcAovBuffers:
+    for name, a in arrays.items():
+        dtype, comps = AOV_PLANES[name]
+        if a.dtype != np.dtype(dtype) or not a.flags.c_contiguous:
+            raise ValueError(f"plane {name!r} must be a C-contiguous {dtype} array")
+    return _aov_buffers({name: a.ctypes.data for name, a in arrays.items()})
+
+
+def aov_from_hits(hits, width: int, height: int, mode: int = MODE_RENDER_ASYNC, shadow_counts=None,
+                  planes=("index", "depth", "point", "normal", "flags", "shadow")) -> dict:
+    """rtc_aov_from_hits: width * height hit records (an RtcHit array, row-major) packed into the AOV planes, the mode
+    rule included. `shadow_counts`: per-pixel shadowed-sample counts (default: each record's own `shadowed`)."""
+    out = _aov_arrays(planes, height, width)
+    sc = None
+    if shadow_counts is not None:
+        sc = np.ascontiguousarray(shadow_counts, dtype=np.uint16).reshape(-1)
+        if sc.size != width * height:
+            raise ValueError("shadow_counts must hold one count per pixel")
+    if len(hits) < width * height:
+        raise ValueError("hits must hold one record per pixel")
+    b = _aov_host_buffers(out)
+    _check(lib().rtc_aov_from_hits(hits, sc.ctypes.data_as(C.POINTER(C.c_uint16)) if sc is not None else None, width, height, mode,
+                                   C.byref(b)), "rtc_aov_from_hits")
+    return out
+
+
+def aov_view(view, planes: dict, near: float = 0.0, far: float = 1.0, n_lights: int = 1) -> np.ndarray:
+    """rtc_aov_view_rgb8: one plane ("depth", "normal", "index" or "shadow") of `planes` as an (H, W, 3) uint8 picture."""
+    v = _aov_view_id(view)
+    arrays = {k: np.ascontiguousarray(a, dtype=AOV_PLANES[k][0]) for k, a in planes.items() if a is not None}
+    first = next(iter(arrays.values()), None)
+    if first is None:
+        raise ValueError("no plane given")
+    h, w = first.shape[:2]
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    b = _aov_host_buffers(arrays)
+    _check(lib().rtc_aov_view_rgb8(v, C.byref(b), w, h, near, far, n_lights, out.ctypes.data_as(C.POINTER(C.c_uint8))), "rtc_aov_view_rgb8")
+    return out
+
+
 def _stats_dict(s: RtcStats, with_resample: bool = False) -> dict:
     d = {"rays_primary": s.rays_primary, "rays_shadow": s.rays_shadow, "rays_reflect": s.rays_reflect,
          "rays_refract": s.rays_refract, "pixels": s.pixels}
@@ -1142,6 +1209,14 @@ class Context:
         """Canvas::to_imgbuf of an f64 canvas in DEVICE memory (address `d_ptr`, height x width x 3 doubles) into the device
         buffer `d_out` (height x width x 4 bytes), enqueued on the context's stream (rtc_canvas_to_rgba8_device)."""
         _check(lib().rtc_canvas_to_rgba8_device(self._h, d_ptr, width, height, gamma, d_out), "rtc_canvas_to_rgba8_device")
+
+    def aov_view_device(self, view, pointers: dict, width: int, height: int, d_out: int, near: float = 0.0, far: float = 1.0,
+                        n_lights: int = 1) -> None:
+        """aov_view of planes in DEVICE memory ({plane: address}) into the device buffer `d_out` (height x width x 3 bytes),
+        enqueued on the context's stream (rtc_aov_view_rgb8_device): the same bytes as the host function."""
+        b = _aov_buffers(pointers)
+        _check(lib().rtc_aov_view_rgb8_device(self._h, _aov_view_id(view), C.byref(b), width, height, near, far, n_lights, C.c_void_p(d_out)),
+               "rtc_aov_view_rgb8_device")
 
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
@@ -1330,6 +1405,21 @@ class DeviceWorld:
         st = lib().rtc_render_views(self.ctx._h, self._h, arr, len(arr), mode, first_band, band_stride, d_ptr, d_ptr8, view_rows, flags)
         if st != 0:
             raise RtcError(st, "rtc_render_views")
+
+    def render_aov(self, cam: RtcCamera, planes=("index", "depth", "point", "normal", "flags", "shadow"), mode: int = MODE_RENDER_ASYNC,
+                   flags: int = 0) -> dict:
+        """What each pixel's centre ray saw (rtc_render_aov): {plane: array} for the planes asked for — index int32 (H, W),
+        depth float64 (H, W), point / normal float64 (H, W, 3), flags uint8 (H, W), shadow uint16 (H, W). A plane that is
+        not named is neither computed nor copied; without "shadow" no shadow ray is cast."""
+        out = _aov_arrays(planes, cam.vsize, cam.hsize)
+        b = _aov_host_buffers(out)
+        _check(lib().rtc_render_aov(self.ctx._h, self._h, C.byref(cam), mode, flags, C.byref(b)), "rtc_render_aov")
+        return out
+
+    def render_aov_device(self, cam: RtcCamera, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+        """The same into DEVICE buffers ({plane: address}; rtc_render_aov_device): enqueued on the context's stream."""
+        b = _aov_buffers(pointers)
+        _check(lib().rtc_render_aov_device(self.ctx._h, self._h, C.byref(cam), mode, flags, C.byref(b)), "rtc_render_aov_device")
 
     def color_at(self, rays: np.ndarray, remaining: int = 5, want_hits: bool = False, flags: int = 0):
         """World::color_at for an (n, 6) array of rays; returns rgb (n,3) [and the rtc_hit array]."""

@@ -85,6 +85,16 @@ class RtcLuaJob(C.Structure):
                 ("line", C.c_uint32)]
 
 
+class RtcAovBuffers(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("depth", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("flags", C.c_void_p),
+                ("shadow", C.c_void_p)]
+
+
+AOV_PLANES = {"index": ("int32", 1), "depth": ("float64", 1), "point": ("float64", 3), "normal": ("float64", 3),
+              "flags": ("uint8", 1), "shadow": ("uint16", 1)}  # plane -> (numpy dtype, components per pixel)
+AOV_VIEWS = {"depth": 0, "normal": 1, "index": 2, "shadow": 3}
+AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW = range(4)
+
 LUA_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.POINTER(C.c_uint8))
 LUA_GIF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(RtcLuaJob), C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
 GIF_SEGMENT, GIF_DELAY_CS = 4096, 7
@@ -102,6 +112,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
+assert C.sizeof(RtcAovBuffers) == 48
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -299,6 +310,11 @@ PROTOTYPES = {
     "rtc_group_stats_reset": (C.c_int32, [VP]),
     "rtc_color_at": (C.c_int32, [VP, VP, PD, U32, U32, U32, PD, C.POINTER(RtcHit)]),
     "rtc_device_arith": (C.c_int32, [VP, U32, PD, PD, U32, PD]),
+    "rtc_aov_from_hits": (C.c_int32, [C.POINTER(RtcHit), C.POINTER(C.c_uint16), U32, U32, U32, C.POINTER(RtcAovBuffers)]),
+    "rtc_render_aov_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.POINTER(RtcAovBuffers)]),
+    "rtc_render_aov": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.POINTER(RtcAovBuffers)]),
+    "rtc_aov_view_rgb8": (C.c_int32, [U32, C.POINTER(RtcAovBuffers), U32, U32, D, D, U32, C.POINTER(C.c_uint8)]),
+    "rtc_aov_view_rgb8_device": (C.c_int32, [VP, U32, C.POINTER(RtcAovBuffers), U32, U32, D, D, U32, VP]),
 }
 
 

@@ -17,7 +17,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "librtc.so"
 
-SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip"]
+SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 COMMON += os.environ.get("RTC_CXXFLAGS", "").split()  # experiments, e.g. -DRTC_WAVES_PER_SIMD=4
 # Kernel file only: MachineLICM hoists the VGPR materialisation of every f64 literal (pow's ~25
@@ -46,7 +46,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     cc = hipcc()
     objdir = ROOT / "build" / "rtc"
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h"]
+    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h", CSRC / "rtc_aov.h"]
     objs = []
     for name in SOURCES:
         src = CSRC / name
@@ -130,6 +130,21 @@ def build_facade_shutter_test(force: bool = False) -> Path:
     """Compile tests/cpp/test_facade_shutter.cpp (the facade's World::set_shape_motion / Camera::set_shutter) against librtc.so."""
     src = ROOT / "tests" / "cpp" / "test_facade_shutter.cpp"
     exe = ROOT / "build" / "test_facade_shutter"
+    hdr = PKG / "host" / "ch1.hpp"
+    if not src.exists() or not hdr.exists():
+        return None
+    exe.parent.mkdir(parents=True, exist_ok=True)
+    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
+        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
+               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
+        subprocess.run(cmd, check=True)
+    return exe
+
+
+def build_facade_aov_test(force: bool = False) -> Path:
+    """Compile tests/cpp/test_facade_aov.cpp (the facade's Camera::render_aov and Aov::view) against librtc.so."""
+    src = ROOT / "tests" / "cpp" / "test_facade_aov.cpp"
+    exe = ROOT / "build" / "test_facade_aov"
     hdr = PKG / "host" / "ch1.hpp"
     if not src.exists() or not hdr.exists():
         return None

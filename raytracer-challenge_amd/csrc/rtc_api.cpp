@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rtc.h"
+#include "rtc_aov.h"
 #include "rtc_device.h"
 #include "rtc_internal.h"
 
@@ -1589,6 +1590,108 @@ rtc_status rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint3
     const rtc_status st = gamma_table(ctx, gamma, ctx->stream, rtc_context::MAX_LANES, &g);
     if (st != RTC_OK) return st;
     HIP_TRY(rtc_launch_canvas_to_rgba8(static_cast<const double *>(d_rgb), n, g, static_cast<unsigned char *>(d_rgba8), ctx->stream));
+    return RTC_OK;
+}
+
+// ---- AOV planes (include/rtc.h, "arbitrary output variables") ---------------------------------------------------------
+static bool aov_any(const rtc_aov_buffers *b) { return b->index || b->depth || b->point || b->normal || b->flags || b->shadow; }
+
+rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                 const rtc_aov_buffers *d) {
+    if (!ctx || !w || !cam || !d || w->ctx != ctx || !aov_any(d)) return RTC_ERR_ARG;
+    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
+    if (((size_t)d->depth | (size_t)d->point | (size_t)d->normal) % sizeof(double) != 0 || (size_t)d->index % 4u != 0 || (size_t)d->shadow % 2u != 0)
+        return RTC_ERR_ARG;
+    if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
+    if (flags & RTC_FLAG_LDS_TABLE) return RTC_ERR_UNSUPPORTED; // there are no AOV kernels for the LDS sources
+    HIP_TRY(hipSetDevice(ctx->device));
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status hs = current_gen(w, &gen);
+    if (hs != RTC_OK) return hs;
+    rtc_world::Gen &G = *gen;
+    int src;
+    uint32_t tile_cap;
+    size_t lds_bytes;
+    choose_source(ctx, G.n, flags, &src, &tile_cap, &lds_bytes, true); // as the lens launches: no-cull maps to SRC_SMEM
+    if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED; // RTC_SRC=1|2
+    LaunchLights LL;
+    if (d->shadow) {
+        const rtc_status ls = lights_of(G, src, LL);
+        if (ls != RTC_OK) return ls;
+    }
+    RenderParams P;
+    std::memset(&P, 0, sizeof P);
+    fill_world(P, G);
+    fill_camera(P, cam);
+    AovParams A;
+    std::memset(&A, 0, sizeof A);
+    A.cam = P.views[0];
+    A.W = cam->hsize;
+    A.H = cam->vsize;
+    A.mode = mode;
+    A.tiles_x = (cam->hsize + 7u) / 8u;
+    A.n = G.n;
+    A.ngroups = G.ngroups;
+    A.pre_limit = G.pre_limit;
+    for (int k = 0; k < 3; ++k) A.light_pos[k] = G.light.position[k];
+    A.index = d->index; A.depth = d->depth; A.point = d->point; A.normal = d->normal; A.flags = d->flags; A.shadow = d->shadow;
+    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
+    HIP_TRY(rtc_launch_aov(&A, &P, src, LL.xl, LL.lt, ctx->stream));
+    HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
+    return RTC_OK;
+}
+
+rtc_status rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                          const rtc_aov_buffers *host) {
+    if (!ctx || !w || !cam || !host || w->ctx != ctx || !aov_any(host)) return RTC_ERR_ARG;
+    if (cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)cam->hsize * cam->vsize;
+    // one grow-only block, the planes in order of alignment: depth, point, normal (8), index (4), shadow (2), flags (1)
+    const size_t sizes[6] = {host->depth ? 8u * px : 0u, host->point ? 24u * px : 0u, host->normal ? 24u * px : 0u,
+                             host->index ? 4u * px : 0u, host->shadow ? 2u * px : 0u, host->flags ? px : 0u};
+    void *const dst[6] = {host->depth, host->point, host->normal, host->index, host->shadow, host->flags};
+    size_t off[6], total = 0;
+    for (int k = 0; k < 6; ++k) {
+        off[k] = total;
+        total += (sizes[k] + 7u) & ~(size_t)7u;
+    }
+    const rtc_status st = ctx->d_aov.reserve(total, &ctx->render_allocs);
+    if (st != RTC_OK) return st;
+    unsigned char *base = ctx->d_aov.get();
+    rtc_aov_buffers d;
+    d.depth = host->depth ? reinterpret_cast<double *>(base + off[0]) : nullptr;
+    d.point = host->point ? reinterpret_cast<double *>(base + off[1]) : nullptr;
+    d.normal = host->normal ? reinterpret_cast<double *>(base + off[2]) : nullptr;
+    d.index = host->index ? reinterpret_cast<int32_t *>(base + off[3]) : nullptr;
+    d.shadow = host->shadow ? reinterpret_cast<uint16_t *>(base + off[4]) : nullptr;
+    d.flags = host->flags ? base + off[5] : nullptr;
+    const rtc_status ls = rtc_render_aov_device(ctx, w, cam, mode, flags, &d);
+    if (ls != RTC_OK) return ls;
+    rtc_status out = RTC_OK;
+    for (int k = 0; k < 6 && out == RTC_OK; ++k)
+        if (sizes[k] && hipMemcpyAsync(dst[k], base + off[k], sizes[k], hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    return out;
+}
+
+rtc_status rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_aov_buffers *d, uint32_t width, uint32_t height, double near,
+                                    double far, uint32_t n_lights, void *d_rgb8) {
+    if (!ctx || !d_rgb8) return RTC_ERR_ARG;
+    const rtc_status st = rtc_aov_view_check(view, d, near, far, n_lights);
+    if (st != RTC_OK) return st;
+    if (((size_t)d->depth | (size_t)d->normal) % sizeof(double) != 0 || (size_t)d->index % 4u != 0 || (size_t)d->shadow % 2u != 0) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    AovViewParams V;
+    std::memset(&V, 0, sizeof V);
+    V.view = view;
+    V.n_lights = n_lights;
+    V.n = (size_t)width * height;
+    V.near = near;
+    V.far = far;
+    V.index = d->index; V.depth = d->depth; V.normal = d->normal; V.shadow = d->shadow;
+    V.out = static_cast<unsigned char *>(d_rgb8);
+    HIP_TRY(rtc_launch_aov_view(&V, ctx->stream));
     return RTC_OK;
 }
 

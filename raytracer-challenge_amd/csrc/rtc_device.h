@@ -188,6 +188,32 @@ struct DevLens {
     uint32_t usteps, vsteps; // usteps * vsteps = samples per pixel, 1 .. RTC_DEV_MAX_LENS_SAMPLES
 };
 
+// AOV launches (rtc_render_aov*, include/rtc.h): k_aov's parameter block. The World's tables ride behind it as separate
+// kernel arguments, as for k_trace; a World with several lights adds its DevExtraLights / DevLightTable as the last argument
+// of the SHADOW instantiations. One wave = one 8x8 pixel tile, tile = workgroup id, tiles_x tiles per tile row. A plane
+// pointer that is NULL is a plane that is neither computed nor written (wave-uniform).
+struct AovParams {
+    DevCamera cam;
+    uint32_t W, H, mode, tiles_x;
+    uint32_t n, ngroups;       // the World's objects and groups of 64 (for_each_object reads them by these names)
+    double pre_limit;          // ... and the limit of its prefilter records (DevPre)
+    double light_pos[3];       // L[0]
+    int32_t *index;
+    double *depth, *point, *normal;
+    uint8_t *flags;
+    uint16_t *shadow;          // non-NULL exactly in the SHADOW instantiations
+};
+// k_aov_view (rtc_aov_view_rgb8_device): one of the four views of `n` pixels into `out` (3 B/pixel)
+struct AovViewParams {
+    uint32_t view, n_lights;
+    size_t n;
+    double near, far;
+    const int32_t *index;
+    const double *depth, *normal;
+    const uint16_t *shadow;
+    unsigned char *out;
+};
+
 struct RenderParams {
     const DevIsect *isect;
     const uint32_t *kind;

@@ -33,6 +33,7 @@ struct rtc_context {
     // device canvas of rtc_render (host-canvas entry point): grow-only, reused between frames
     DevBuf<double> d_canvas;
     DevBuf<unsigned char> d_canvas8; // the same for rtc_render_rgb8 (3 B/pixel) and rtc_render_rgba8 (4 B/pixel)
+    DevBuf<unsigned char> d_aov;     // the planes of rtc_render_aov (host-buffer entry point), carved in order of alignment
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -183,6 +184,10 @@ extern "C" hipError_t rtc_launch_light_lists_built(uint32_t n, uint32_t cap, con
                                                    const DevTileBundle *cells, const DevTileBundle *macros, uint32_t *cnt, uint32_t *list,
                                                    hipStream_t stream);
 extern "C" rtc_status rtc_gamma_build_table(float gamma, DevGamma *g); // host_ppm.cpp
+// k_aov / k_aov_view (rtc_kernels.hip). `P`: the World's tables only (fill_world); xl / lt: lights_of, read with A->shadow.
+extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
+                                     hipStream_t stream);
+extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t stream);
 extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
 // k_average_over (rtc_shutter.hip): one pass of Color::average_over over whole canvases. Adds frames[f * stride + i], f = 0..nf-1
 // in that order, to the carried sum (sum_in, NULL: 0.0) for i < count. divisor == 0: stores the sum to f64_out. Otherwise the

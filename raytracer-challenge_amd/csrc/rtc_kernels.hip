@@ -28,6 +28,7 @@
 #include <hip/hip_ext.h>
 
 #include "rtc.h"
+#include "rtc_aov.h"
 #include "rtc_bands.h"
 #include "rtc_device.h"
 #include "rtc_gamma.h"
@@ -2441,6 +2442,193 @@ extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, co
     const size_t want = (n + 255u) / 256u;
     const uint32_t blocks = (uint32_t)(want < 8192u ? want : 8192u); // at most 8192 workgroups (2M lanes); the loop strides over the rest
     hipLaunchKernelGGL(k_canvas_to_rgba8, dim3(blocks), dim3(256), 0, stream, rgb, n, g, out, ((size_t)out % 4u) == 0 ? 1u : 0u);
+    return hipGetLastError();
+}
+
+// ---- AOV planes (rtc_render_aov*, include/rtc.h): what each pixel's centre ray saw ----------------------------------
+// k_trace's primary pass, its compute_vectors and — SHADOW only — one any-hit pass per light sample, and nothing of the
+// shading: no material, no pattern, no recursion, no counters. One wave = one 8x8 pixel tile = one workgroup (tile id =
+// workgroup id, partial tiles on the right and bottom edges mask their lanes), so the primary bundle's cone is tight; the
+// cull walks are wave-level code (ballots, DPP) and stay in converged code, every lane of the wave reaching them.
+// SRC: SRC_SMEM (RTC_FLAG_NO_CULL), SRC_CULL or SRC_CULL2 (the ordered walk with the skip functor, as k_trace's large-world
+// primary pass). There is no binning kernel, no per-launch DevPrim table: closest_world transforms the origin itself, with
+// the arithmetic k_prep_primary has. XL: empty for one light, or the World's further lights (DevExtraLights / DevLightTable),
+// SHADOW instantiations only. Results do not depend on SRC: closer() orders by (t, insertion index), the cull is conservative.
+template <int SRC, bool SHADOW, class... XL>
+__global__ void __launch_bounds__(64, RTC_WAVES_PER_SIMD)
+k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind, const DevShade *__restrict__ t_shade,
+      const DevBound *__restrict__ t_bound, const DevIsect *__restrict__ t_isect_s, const uint32_t *__restrict__ t_kind_s,
+      const DevBound *__restrict__ t_bound_s, const uint32_t *__restrict__ t_orig_s, const DevBound *__restrict__ t_gbound,
+      const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
+    static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "AOV launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
+    static_assert(sizeof...(XL) <= (SHADOW ? 1 : 0), "further lights only where shadow rays are cast, one block at most");
+    Tables T{};
+    T.isect = t_isect; T.kind = t_kind; T.shade = t_shade; T.bound = t_bound;
+    T.isect_s = t_isect_s; T.kind_s = t_kind_s; T.bound_s = t_bound_s; T.orig_s = t_orig_s; T.gbound = t_gbound;
+    T.pre = t_pre; T.pre_s = t_pre_s;
+    const LdsView L{};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
+    const bool in_range = px < A.W && py < A.H;
+    // Camera::render leaves the last row and column untouched (camera.rs:120-121): they get the miss values
+    const bool traced = in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H));
+
+    // ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76
+    V3 cam_origin = xpoint(A.cam.vinv, mk(0., 0., 0.));
+    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
+    const V3 ro = cam_origin;
+    const V3 rd = primary_dir(A.cam, cam_origin, px, py);
+
+    // ---- World::intersect + get_hit, streaming form (k_trace's primary pass without the tile lists) ----
+    double best = __builtin_inf();
+    int hidx = -1, hroot = 0;
+    Bundle B{};
+    B.off = true;
+    if constexpr (IS_CULL(SRC)) {
+        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
+    }
+    auto nearest = [&](int j, auto m, uint32_t kind, auto) {
+        if (traced) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
+        return true;
+    };
+    if constexpr (SRC == SRC_CULL2)
+        for_each_object<SRC, false>(A, T, L, traced, B, nearest, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
+    else
+        for_each_object<SRC>(A, T, L, traced, B, nearest, ro, rd);
+    const bool hit = traced && hidx >= 0;
+
+    // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96), the part the planes hold ----
+    V3 point = mk(0., 0., 0.), normal = mk(0., 0., 0.), over = mk(0., 0., 0.);
+    bool inside = false;
+    if (hit) point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
+    if (SHADOW || A.normal != nullptr || A.flags != nullptr) { // (wave-uniform)
+        if (hit) {
+            const DevShade *S = T.shade + hidx;
+            const double *m_obj = T.isect[hidx].m;
+            const V3 eyev = vneg(rd);
+            V3 ln = mk(0., 1., 0.); // Shape::normal_at shape.rs:34-40
+            const uint32_t kind = S->kind;
+            if (kind == RTC_SPHERE) {
+                const V3 lp = xpoint(m_obj, point);
+                ln = mk(lp.x - 0., lp.y - 0., lp.z - 0.);
+            } else if (kind == RTC_CUBE) { // Cube::normal_at_local shape.rs:601-610
+                const V3 lp = xpoint(m_obj, point);
+                const double ax = fabs(lp.x), ay = fabs(lp.y), az = fabs(lp.z);
+                const double maxc = fmax(ax, fmax(ay, az));
+                if (maxc == ax) ln = mk(lp.x, 0., 0.);
+                else if (maxc == ay) ln = mk(0., lp.y, 0.);
+                else ln = mk(0., 0., lp.z);
+            }
+            if (kind == RTC_PLANE) normal = mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]); // evaluated once per object (DevShade)
+            else normal = vnormalize_plain(xvector3(S->nt, ln));
+            inside = vdot(normal, eyev) < 0.0;
+            if (inside) normal = vneg(normal);
+            over = vadd(point, vmul(normal, RTC_EPSILON));
+        }
+    }
+
+    // ---- is_shadowed_by_light (shape.rs:716-727) per light sample, in order: how many hide the point ----
+    uint32_t count = 0u;
+    if constexpr (SHADOW) {
+        auto one_light = [&](V3 lp) {
+            V3 ldir = mk(0., 0., 0.);
+            double ldist = 0.;
+            if (hit) {
+                const V3 v = vsub(lp, over);
+                ldist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
+                ldir = mk(v.x / ldist, v.y / ldist, v.z / ldist);
+            }
+            bool pending = hit, shadowed = false;
+            Bundle Bl{};
+            Bl.off = true;
+            if constexpr (IS_CULL(SRC)) { // the segment over_point -> light, walked from the light: apex = light (shared), reach-limited
+                if (ballot(hit) != 0ull) Bl = make_bundle<true, true>(hit, lp, lp, vneg(ldir), ldist);
+            }
+            // (the per-lane prefilter in front of the exact tests where k_trace's flat kernels have it: two-level Worlds)
+            for_each_object<SRC, SRC == SRC_CULL2>(A, T, L, pending, Bl, [&](int, auto m, uint32_t kind, auto) {
+                if (pending) {
+                    if (occludes_world(kind, m, over, ldir, ldist)) { shadowed = true; pending = false; }
+                }
+                return ballot(pending) != 0ull; // stop as soon as no lane is pending
+            }, over, ldir);
+            if (shadowed) ++count;
+        };
+        one_light(mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]));
+        if constexpr (sizeof...(XL) == 1) {
+            const auto &X = first_of(xl_arg...); // DevExtraLights (kernel arguments) or DevLightTable (HBM)
+            const uint32_t n_extra = further_light_count(X);
+            for (uint32_t li = 0; li < n_extra; ++li) one_light(further_light_position(X, li));
+        }
+    }
+
+    // ---- the planes asked for (wave-uniform choice), one pixel per lane: plain vector stores ----
+    if (in_range) {
+        const size_t idx = (size_t)py * A.W + px;
+        if (A.index != nullptr) A.index[idx] = hit ? hidx : -1;
+        if (A.depth != nullptr) A.depth[idx] = hit ? best : __builtin_inf();
+        if (A.point != nullptr) { A.point[3u * idx] = point.x; A.point[3u * idx + 1u] = point.y; A.point[3u * idx + 2u] = point.z; }
+        if (A.normal != nullptr) { A.normal[3u * idx] = normal.x; A.normal[3u * idx + 1u] = normal.y; A.normal[3u * idx + 2u] = normal.z; }
+        if (A.flags != nullptr) A.flags[idx] = hit ? (uint8_t)(1u | (inside ? 2u : 0u)) : (uint8_t)0u;
+        if constexpr (SHADOW) A.shadow[idx] = (uint16_t)count;
+    }
+}
+
+// rtc_aov_view_rgb8 on the device: one thread per pixel, the rules of rtc_aov.h, Color::scale by scale255 (rtc_gamma.h)
+__global__ void __launch_bounds__(256) k_aov_view(const AovViewParams V) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= V.n) return;
+    uint8_t o[3];
+    if (V.view == RTC_AOV_VIEW_DEPTH) {
+        o[0] = o[1] = o[2] = scale255(rtc_aov_depth_value(V.depth[i], V.near, V.far));
+    } else if (V.view == RTC_AOV_VIEW_NORMAL) {
+        for (uint32_t k = 0; k < 3u; ++k) o[k] = scale255(rtc_aov_normal_value(V.normal[3u * i + k]));
+    } else if (V.view == RTC_AOV_VIEW_INDEX) {
+        rtc_aov_index_rgb(V.index[i], o);
+    } else {
+        o[0] = o[1] = o[2] = scale255(rtc_aov_shadow_value(V.shadow[i], V.n_lights));
+    }
+    V.out[3u * i] = o[0];
+    V.out[3u * i + 1u] = o[1];
+    V.out[3u * i + 2u] = o[2];
+}
+
+template <int SRC, bool SHADOW, class... XL>
+static hipError_t launch_aov(const AovParams &A, const RenderParams &P, uint32_t tiles, hipStream_t stream, const XL &...xl) {
+    hipLaunchKernelGGL((k_aov<SRC, SHADOW, XL...>), dim3(tiles), dim3(64), 0, stream, A, P.isect, P.kind, P.shade, P.bound, P.isect_s, P.kind_s,
+                       P.bound_s, P.orig_s, P.gbound, P.pre, P.pre_s, xl...);
+    return hipGetLastError();
+}
+
+// `P`: the World's tables only (fill_world). `xl` / `lt` (never both): the further lights of a World with several, read only when
+// A->shadow is set. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
+extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
+                                     hipStream_t stream) {
+    if (A->W == 0u || A->H == 0u || A->tiles_x != (A->W + 7u) / 8u) return hipErrorInvalidValue;
+    const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
+    if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)tiles64;
+    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
+    if (xl != nullptr && (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u)) return hipErrorInvalidValue;
+    if (lt != nullptr && (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u)) return hipErrorInvalidValue;
+#define RTC_AOV_CASE(S)                                                                  \
+    if (src == S) {                                                                      \
+        if (A->shadow == nullptr) return launch_aov<S, false>(*A, *P, tiles, stream);    \
+        if (xl != nullptr) return launch_aov<S, true>(*A, *P, tiles, stream, *xl);       \
+        if (lt != nullptr) return launch_aov<S, true>(*A, *P, tiles, stream, *lt);       \
+        return launch_aov<S, true>(*A, *P, tiles, stream);                               \
+    }
+    RTC_AOV_CASE(SRC_SMEM)
+    RTC_AOV_CASE(SRC_CULL)
+    RTC_AOV_CASE(SRC_CULL2)
+#undef RTC_AOV_CASE
+    return hipErrorInvalidValue;
+}
+
+extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t stream) {
+    if (V->n == 0) return hipSuccess;
+    const size_t blocks = (V->n + 255u) / 256u;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_aov_view, dim3((uint32_t)blocks), dim3(256), 0, stream, *V);
     return hipGetLastError();
 }
 

@@ -425,6 +425,32 @@ class World { // shape.rs:633-795
     bool dirty_ = false;
 };
 
+// What each pixel's centre ray saw (rtc_render_aov, include/rtc.h): the planes of Camera::render_aov, row-major, idx =
+// y*width + x. Not part of the reference: its renderer keeps the hit record to itself.
+struct Aov {
+    uint32_t width = 0, height = 0;
+    uint32_t n_lights = 1;            // light samples of the World it was rendered from: the largest `shadow` count
+    std::vector<int32_t> index;       // World.shapes position of the hit, -1 for a miss
+    std::vector<double> depth;        // t, +infinity for a miss
+    std::vector<double> point;        // [3] per pixel
+    std::vector<double> normal;       // [3] per pixel, after the `inside` flip
+    std::vector<uint8_t> flags;       // 1 = hit, | 2 = inside
+    std::vector<uint16_t> shadow;     // light samples hidden from the hit's over_point
+    enum View : uint32_t { DEPTH = RTC_AOV_VIEW_DEPTH, NORMAL = RTC_AOV_VIEW_NORMAL, INDEX = RTC_AOV_VIEW_INDEX, SHADOW = RTC_AOV_VIEW_SHADOW };
+    bool hit(uint32_t x, uint32_t y) const { return (flags[static_cast<size_t>(y) * width + x] & 1u) != 0; }
+    bool inside(uint32_t x, uint32_t y) const { return (flags[static_cast<size_t>(y) * width + x] & 2u) != 0; }
+    rtc_aov_buffers buffers() {
+        return rtc_aov_buffers{index.data(), depth.data(), point.data(), normal.data(), flags.data(), shadow.data()};
+    }
+    // A plane as a quantised Canvas (rtc_aov_view_rgb8) that every file writer takes; near / far are read by DEPTH only.
+    Canvas view(View v, double near = 0.0, double far = 1.0) const {
+        Canvas c = Canvas::quantised(width, height);
+        const rtc_aov_buffers b = const_cast<Aov *>(this)->buffers();
+        check(rtc_aov_view_rgb8(v, &b, width, height, near, far, n_lights, c.rgb8.data()), "Aov::view");
+        return c;
+    }
+};
+
 class Camera { // camera.rs:17-160
   public:
     static constexpr uint8_t MAX_REFLECTIONS = RTC_MAX_REFLECTIONS;
@@ -479,8 +505,27 @@ class Camera { // camera.rs:17-160
     // to_imgbuf's RGBA at that gamma (Canvas::rgba8), made on the device byte for byte as the host conversion makes it.
     Canvas render_rgba8(const World &w, float gamma) const { return run_rgba8(w, RTC_MODE_RENDER, gamma); }
     Canvas render_async_rgba8(const World &w, float gamma) const { return run_rgba8(w, RTC_MODE_RENDER_ASYNC, gamma); }
+    // The AOV planes of the same frame (struct Aov): the pixel-centre ray's hit record, whatever antialiasing_samples says;
+    // a lens or a shutter has no AOV form (RTC_ERR_UNSUPPORTED).
+    Aov render_aov(const World &w) const { return run_aov(w, RTC_MODE_RENDER); }
+    Aov render_async_aov(const World &w) const { return run_aov(w, RTC_MODE_RENDER_ASYNC); }
 
   private:
+    Aov run_aov(const World &w, uint32_t mode) const {
+        if (has_lens_ || shutter_) check(RTC_ERR_UNSUPPORTED, "Camera::render_aov with a lens or a shutter");
+        rtc_camera c = flat_;
+        c.samples = antialiasing_samples;
+        Aov a;
+        a.width = hsize; a.height = vsize;
+        const size_t px = static_cast<size_t>(hsize) * vsize;
+        a.index.assign(px, -1); a.depth.assign(px, 0.0); a.point.assign(px * 3, 0.0); a.normal.assign(px * 3, 0.0);
+        a.flags.assign(px, 0); a.shadow.assign(px, 0);
+        World::Uploaded up(w);
+        a.n_lights = rtc_world_light_count(up.w);
+        const rtc_aov_buffers b = a.buffers();
+        check(rtc_render_aov(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, &b), "Camera::render_aov");
+        return a;
+    }
     Canvas run(const World &w, uint32_t mode) const {
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;

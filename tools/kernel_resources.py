@@ -1,4 +1,4 @@
-"""Register / scratch / LDS use of every k_trace instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
+"""Register / scratch / LDS use of every k_trace and k_aov instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
 usage: python tools/kernel_resources.py [extra -D flags]"""
 import re
 import subprocess
@@ -14,7 +14,7 @@ t = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
-    if "k_trace" not in name and "undeal" not in name:
+    if "k_trace" not in name and "undeal" not in name and "k_aov" not in name:
         continue
     def g(k):
         m = re.search(k + r": (\d+)", blk)
@@ -25,6 +25,10 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         # the instantiations for Worlds with several lights: in the kernel arguments, or in the World's device table
         tag += ",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else ""
         tag += ",lens>" if "DevLens" in name else ">"  # the thin-lens flavour (rtc_render_lens*)
+    elif (a := re.search(r"k_aovILi(\d)ELb(\d)E", name)):  # the AOV kernel: source, shadow passes, where the further lights come from
+        tag = "k_aov<%s,shadow=%s" % a.groups() + (",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">")
+    elif "k_aov_view" in name:
+        tag = "k_aov_view"
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
