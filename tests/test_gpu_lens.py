@@ -16,6 +16,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from adversarial_worlds import oracle_lens_frame
+
 pytestmark = pytest.mark.gpu
 
 W, H = 70, 45
@@ -52,28 +54,8 @@ def _oracle_lens_frame(rtc, O, name, lens_spec, light_spec=None, u_outer=False, 
     """Color::average_over of the oracle's color_at(rtc_lens_ray(x, y, k)), k in sample order (u_outer: in the WRONG, u-outer
     order). light_spec: (position, intensity) instead of the scene's own light. Computed once, shared, never written to."""
     w, cam = _scene(rtc, name)
-    lens = rtc.lens(*lens_spec)
     light = w.light if light_spec is None else rtc.light(position=light_spec[0], intensity=light_spec[1])
-    lens_ray, color_at = rtc.lib().rtc_lens_ray, O.lib().orc_color_at
-    shapes, n = w.array(), len(w)
-    camr, lensr, lightr = C.byref(cam), C.byref(lens), C.byref(light)
-    ray, rgb = (C.c_double * 6)(), (C.c_double * 3)()
-    us, vs = lens.usteps, lens.vsteps
-    ns = us * vs
-    order = [v * us + u for u in range(us) for v in range(vs)] if u_outer else list(range(ns))
-    out = np.zeros((cam.vsize, cam.hsize, 3), dtype=np.float64)
-    for y in range(cam.vsize):
-        for x in range(cam.hsize):
-            if mode == MODE_RENDER and (x + 1 >= cam.hsize or y + 1 >= cam.vsize):
-                continue   # Camera::render leaves the last row and column black (camera.rs:120-121)
-            r = g = b = 0.0
-            for k in order:
-                assert lens_ray(camr, lensr, x, y, k, ray) == 0
-                color_at(shapes, n, lightr, ray, 5, rgb, None)
-                r += rgb[0]; g += rgb[1]; b += rgb[2]
-            out[y, x] = (r / float(ns), g / float(ns), b / float(ns))
-    out.setflags(write=False)
-    return out
+    return oracle_lens_frame(rtc, O, w.array(), len(w), light, cam, lens_spec, u_outer=u_outer, mode=mode)
 
 
 def _lens_render(gpu, rtc, world, cam, lens_spec, flags=0, mode=MODE_RENDER_ASYNC):
