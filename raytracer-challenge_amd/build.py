@@ -10,6 +10,7 @@ import os
 import shutil
 import subprocess
 import sys
+from functools import partial
 from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
@@ -34,6 +35,11 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (expected /opt/rocm/bin/hipcc)")
 
 
+def kernel_compile_line() -> list[str]:
+    """hipcc and the flags every .hip file is compiled with; the caller adds -c / -S, the source and the output."""
+    return [hipcc(), "--offload-arch=gfx950", *COMMON, *KERNEL_ONLY]
+
+
 def _stale(target: Path, deps: list[Path]) -> bool:
     if not target.exists():
         return True
@@ -53,8 +59,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         obj = objdir / (name + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + headers):
-            extra = KERNEL_ONLY if name.endswith(".hip") else []
-            cmd = [cc, "--offload-arch=gfx950", *COMMON, *extra, "-c", str(src), "-o", str(obj)]
+            flags = kernel_compile_line() if name.endswith(".hip") else [cc, "--offload-arch=gfx950", *COMMON]
+            cmd = [*flags, "-c", str(src), "-o", str(obj)]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.run(cmd, check=True)
@@ -66,10 +72,10 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     return LIB
 
 
-def build_facade_tests(force: bool = False) -> Path:
-    """Compile tests/cpp/test_facade.cpp (C++ mirror of the reference API) against librtc.so."""
-    src = ROOT / "tests" / "cpp" / "test_facade.cpp"
-    exe = ROOT / "build" / "test_facade"
+def _build_facade(name: str, force: bool = False) -> Path:
+    """Compile tests/cpp/<name>.cpp, a program that drives the facade (host/ch1.hpp), against librtc.so."""
+    src = ROOT / "tests" / "cpp" / (name + ".cpp")
+    exe = ROOT / "build" / name
     hdr = PKG / "host" / "ch1.hpp"
     if not src.exists() or not hdr.exists():
         return None
@@ -81,79 +87,13 @@ def build_facade_tests(force: bool = False) -> Path:
     return exe
 
 
-def build_facade_update_test(force: bool = False) -> Path:
-    """Compile tests/cpp/test_facade_update.cpp (the facade's resident World updated in place) against librtc.so."""
-    src = ROOT / "tests" / "cpp" / "test_facade_update.cpp"
-    exe = ROOT / "build" / "test_facade_update"
-    hdr = PKG / "host" / "ch1.hpp"
-    if not src.exists() or not hdr.exists():
-        return None
-    exe.parent.mkdir(parents=True, exist_ok=True)
-    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
-        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
-               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
-        subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_facade_area_light_test(force: bool = False) -> Path:
-    """Compile tests/cpp/test_facade_area_light.cpp (the facade's World::add_area_light) against librtc.so."""
-    src = ROOT / "tests" / "cpp" / "test_facade_area_light.cpp"
-    exe = ROOT / "build" / "test_facade_area_light"
-    hdr = PKG / "host" / "ch1.hpp"
-    if not src.exists() or not hdr.exists():
-        return None
-    exe.parent.mkdir(parents=True, exist_ok=True)
-    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
-        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
-               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
-        subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_facade_lens_test(force: bool = False) -> Path:
-    """Compile tests/cpp/test_facade_lens.cpp (the facade's Camera::set_lens) against librtc.so."""
-    src = ROOT / "tests" / "cpp" / "test_facade_lens.cpp"
-    exe = ROOT / "build" / "test_facade_lens"
-    hdr = PKG / "host" / "ch1.hpp"
-    if not src.exists() or not hdr.exists():
-        return None
-    exe.parent.mkdir(parents=True, exist_ok=True)
-    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
-        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
-               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
-        subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_facade_shutter_test(force: bool = False) -> Path:
-    """Compile tests/cpp/test_facade_shutter.cpp (the facade's World::set_shape_motion / Camera::set_shutter) against librtc.so."""
-    src = ROOT / "tests" / "cpp" / "test_facade_shutter.cpp"
-    exe = ROOT / "build" / "test_facade_shutter"
-    hdr = PKG / "host" / "ch1.hpp"
-    if not src.exists() or not hdr.exists():
-        return None
-    exe.parent.mkdir(parents=True, exist_ok=True)
-    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
-        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
-               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
-        subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_facade_aov_test(force: bool = False) -> Path:
-    """Compile tests/cpp/test_facade_aov.cpp (the facade's Camera::render_aov and Aov::view) against librtc.so."""
-    src = ROOT / "tests" / "cpp" / "test_facade_aov.cpp"
-    exe = ROOT / "build" / "test_facade_aov"
-    hdr = PKG / "host" / "ch1.hpp"
-    if not src.exists() or not hdr.exists():
-        return None
-    exe.parent.mkdir(parents=True, exist_ok=True)
-    if force or _stale(exe, [src, hdr, LIB, ROOT / "include" / "rtc.h"]):
-        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-I{ROOT / 'include'}", f"-I{PKG / 'host'}",
-               str(src), "-o", str(exe), f"-L{PKG}", "-lrtc", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../raytracer-challenge_amd"]
-        subprocess.run(cmd, check=True)
-    return exe
+# the six programs, each callable as f(force=False) -> Path
+build_facade_tests = partial(_build_facade, "test_facade")  # the C++ mirror of the reference API
+build_facade_update_test = partial(_build_facade, "test_facade_update")  # the resident World updated in place
+build_facade_area_light_test = partial(_build_facade, "test_facade_area_light")  # World::add_area_light
+build_facade_lens_test = partial(_build_facade, "test_facade_lens")  # Camera::set_lens
+build_facade_shutter_test = partial(_build_facade, "test_facade_shutter")  # World::set_shape_motion / Camera::set_shutter
+build_facade_aov_test = partial(_build_facade, "test_facade_aov")  # Camera::render_aov and Aov::view
 
 
 if __name__ == "__main__":

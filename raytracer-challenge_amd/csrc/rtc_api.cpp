@@ -1255,10 +1255,18 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     return RTC_OK;
 }
 
+// What rtc_render_rows, rtc_render_lens_rows and rtc_render_bands check first: a context with its own World, a camera with
+// a canvas, somewhere to write, a known mode
+static rtc_status check_render_args(const rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, const void *d_rgb,
+                                    const void *d_rgb8) {
+    if (!ctx || !w || !cam || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
+    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
+    return RTC_OK;
+}
+
 rtc_status rtc_render_rows(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t y0,
                            uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags) {
-    if (!ctx || !w || !cam || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
-    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
+    if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
     if (cam->samples > 255u) return RTC_ERR_ARG; // antialiasing_samples is a u8 (camera.rs:24)
     if (y0 == y1) return RTC_OK;
     return render_launch(ctx, w, cam, mode, y0, y1, 1u, (y1 - y0 + 7u) / 8u, d_rgb, d_rgb8, flags);
@@ -1273,8 +1281,7 @@ static rtc_status check_lens(const rtc_camera *cam, const rtc_lens *lens) {
 
 rtc_status rtc_render_lens_rows(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens, uint32_t mode,
                                 uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags) {
-    if (!ctx || !w || !cam || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
-    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
+    if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
     const rtc_status ls = check_lens(cam, lens);
     if (ls != RTC_OK) return ls;
     if (y0 == y1) return RTC_OK;
@@ -1283,8 +1290,7 @@ rtc_status rtc_render_lens_rows(rtc_context *ctx, const rtc_world *w, const rtc_
 
 rtc_status rtc_render_bands(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode,
                             uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t flags) {
-    if (!ctx || !w || !cam || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
-    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || band_stride == 0) return RTC_ERR_ARG;
+    if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || band_stride == 0) return RTC_ERR_ARG;
     if (cam->samples > 255u) return RTC_ERR_ARG;
     const uint32_t nbands = (cam->vsize + RTC_BAND_ROWS - 1u) / RTC_BAND_ROWS;
     if (first_band >= nbands) return RTC_OK; // this caller owns no band of so small a canvas

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "rtc.h"
 #include "rtc_aov.h"
 #include "rtc_bands.h"
@@ -854,6 +856,66 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
     }
 }
 
+// ---- stages k_trace and k_aov share ------------------------------------------------------------------------------
+// Shape::normal_at shape.rs:34-40: the world normal at `point`, before the inside flip. A plane's normal does not depend on
+// the point: it was evaluated once per object at rtc_world_create (DevShade::plane_n).
+DEVI V3 shape_normal(const DevShade *S, const double *m_obj, V3 point) {
+    V3 ln = mk(0., 1., 0.);
+    const uint32_t kind = S->kind;
+    if (kind == RTC_SPHERE) {
+        const V3 lp = xpoint(m_obj, point);
+        ln = mk(lp.x - 0., lp.y - 0., lp.z - 0.);
+    } else if (kind == RTC_CUBE) { // Cube::normal_at_local shape.rs:601-610
+        const V3 lp = xpoint(m_obj, point);
+        const double ax = fabs(lp.x), ay = fabs(lp.y), az = fabs(lp.z);
+        const double maxc = fmax(ax, fmax(ay, az));
+        if (maxc == ax) ln = mk(lp.x, 0., 0.);
+        else if (maxc == ay) ln = mk(0., lp.y, 0.);
+        else ln = mk(0., 0., lp.z);
+    }
+    if (kind == RTC_PLANE) return mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]);
+    return vnormalize_plain(xvector3(S->nt, ln));
+}
+
+// The shadow ray of is_shadowed_by_light (shape.rs:717-719): v = light - over_point, its length, three divisions. Lanes
+// without a hit keep the `dir` and `dist` they came with.
+DEVI void shadow_ray(V3 light_pos, V3 over, bool hit, V3 &dir, double &dist) {
+    if (hit) {
+        const V3 v = vsub(light_pos, over);
+        dist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
+        dir = mk(v.x / dist, v.y / dist, v.z / dist);
+    }
+}
+
+// The closest-hit walk's body (World::intersect + get_hit, streaming form): the exact test of object j for the lanes still
+// tracing, folded into (best, hidx, hroot). Never stops the walk. Holds references, as a [&] lambda would.
+struct ClosestHit {
+    const bool &tracing;
+    const V3 &ro, &rd;
+    double &best;
+    int &hidx, &hroot;
+    template <class M, class Q> DEVI bool operator()(int j, M m, uint32_t kind, Q) const {
+        if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
+        return true;
+    }
+};
+
+// The any-hit walk's body (is_shadowed shape.rs:721-726): the exact test of one object for the lanes still pending — the
+// first object in the way settles a lane — and the walk goes on while some lane is pending. Holds references, as a [&]
+// lambda would.
+struct AnyHit {
+    bool &pending;
+    const V3 &over, &dir;
+    const double &dist;
+    bool &shadowed;
+    template <class M, class Q> DEVI bool operator()(int, M m, uint32_t kind, Q) const {
+        if (pending) {
+            if (occludes_world(kind, m, over, dir, dist)) { shadowed = true; pending = false; }
+        }
+        return ballot(pending) != 0ull; // stop as soon as no lane is pending
+    }
+};
+
 // ---- patterns (material.rs:41-45 and the six pattern_at bodies) --------------------------
 DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
     const V3 op = xpoint(m_obj, world_point);
@@ -1292,10 +1354,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 });
             } else if (IS_CULL(SRC) && REFL && !(shared_origin && first)) {
                 // reflection / refraction rays: incoherent, per-lane prefilter before the exact test
-                for_each_object<SRC, true>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
-                    return true;
-                }, ro, rd);
+                for_each_object<SRC, true>(P, T, L, tracing, B, ClosestHit{tracing, ro, rd, best, hidx, hroot}, ro, rd);
             } else if (IS_CULL(SRC) && !PROBE && use_bins) {
                 // binned primary pass: the unbounded objects, then the tile's own list (k_bin_tiles) — together
                 // every object this tile's rays can touch
@@ -1345,15 +1404,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 }
             } else if (SRC == SRC_CULL2 && !PROBE && shared_origin && first) {
                 // primary rays of a large world: start at the apex, unit direction -> ordered walk with early stop
-                for_each_object<SRC, false>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
-                    return true;
-                }, ro, rd, [&](float key) { return ballot(tracing && !(best < (double)key)) == 0ull; });
+                for_each_object<SRC, false>(P, T, L, tracing, B, ClosestHit{tracing, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(tracing && !(best < (double)key)) == 0ull; });
             } else {
-                for_each_object<SRC>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
-                    if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
-                    return true;
-                }, ro, rd);
+                for_each_object<SRC>(P, T, L, tracing, B, ClosestHit{tracing, ro, rd, best, hidx, hroot}, ro, rd);
             }
             const bool hit = tracing && hidx >= 0;
             const auto &Ph = KP(P_arg); // shading view: light
@@ -1369,23 +1422,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             if (hit) {
                 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
                 eyev = vneg(rd);
-                // Shape::normal_at shape.rs:34-40. A plane's normal does not depend on the point: it was
-                // evaluated once per object at rtc_world_create (DevShade::plane_n).
-                V3 ln = mk(0., 1., 0.);
-                const uint32_t kind = S->kind;
-                if (kind == RTC_SPHERE) {
-                    const V3 lp = xpoint(m_obj, point);
-                    ln = mk(lp.x - 0., lp.y - 0., lp.z - 0.);
-                } else if (kind == RTC_CUBE) { // Cube::normal_at_local shape.rs:601-610
-                    const V3 lp = xpoint(m_obj, point);
-                    const double ax = fabs(lp.x), ay = fabs(lp.y), az = fabs(lp.z);
-                    const double maxc = fmax(ax, fmax(ay, az));
-                    if (maxc == ax) ln = mk(lp.x, 0., 0.);
-                    else if (maxc == ay) ln = mk(0., lp.y, 0.);
-                    else ln = mk(0., 0., lp.z);
-                }
-                if (kind == RTC_PLANE) normal = mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]);
-                else normal = vnormalize_plain(xvector3(S->nt, ln));
+                normal = shape_normal(S, m_obj, point);
                 inside = vdot(normal, eyev) < 0.0;
                 if (inside) normal = vneg(normal);
                 over = vadd(point, vmul(normal, RTC_EPSILON));
@@ -1393,10 +1430,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 reflectv = vreflect(rd, normal);
                 m_kr = S->reflective;
                 m_tr = S->transparency;
-                // shadow ray: is_shadowed_by_light shape.rs:716-720
-                const V3 v = vsub(lightp, over);
-                sdist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
-                sdir = mk(v.x / sdist, v.y / sdist, v.z / sdist);
+                shadow_ray(lightp, over, hit, sdir, sdist);
             }
 
             // ---- compute_refractive (shape.rs:115-141), open-set form, transparent hits only ----
@@ -1621,12 +1655,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 }
             }
             if (!listed)
-            for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, sh_pending, Bs, [&](int j, auto m, uint32_t kind, auto pr) {
-                if (sh_pending) {
-                    if (occludes_world(kind, m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
-                }
-                return ballot(sh_pending) != 0ull;
-            }, over, sdir);
+            for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, sh_pending, Bs, AnyHit{sh_pending, over, sdir, sdist, shadowed}, over, sdir);
 
             // keep the material / pattern loads of the lighting stage BELOW the shadow loop: hoisted
             // above it they stay live through the loop and cost a wave per SIMD in occupancy
@@ -1662,11 +1691,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     const V3 lp = further_light_position(X, li);
                     V3 ldir = mk(0, 0, 0);
                     double ldist = 0.;
-                    if (hit) { // is_shadowed_by_light shape.rs:716-720
-                        const V3 v = vsub(lp, over);
-                        ldist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
-                        ldir = mk(v.x / ldist, v.y / ldist, v.z / ldist);
-                    }
+                    shadow_ray(lp, over, hit, ldir, ldist);
                     bool l_pending = hit, l_shadowed = false;
                     c_shadow += popc64(ballot(hit));
                     Bundle Bl{};
@@ -1674,12 +1699,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     if constexpr (IS_CULL(SRC)) {
                         if (ballot(hit) != 0ull) Bl = make_bundle<true, true>(hit, lp, lp, vneg(ldir), ldist);
                     }
-                    for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, l_pending, Bl, [&](int j, auto m, uint32_t kind, auto pr) {
-                        if (l_pending) {
-                            if (occludes_world(kind, m, over, ldir, ldist)) { l_shadowed = true; l_pending = false; }
-                        }
-                        return ballot(l_pending) != 0ull;
-                    }, over, ldir);
+                    for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, l_pending, Bl, AnyHit{l_pending, over, ldir, ldist, l_shadowed}, over, ldir);
                     asm volatile("" ::: "memory"); // as above: the material loads stay below the walk
                     if (hit) {
                         const LightInt I = further_light_intensity(X, li);
@@ -2487,14 +2507,10 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
     if constexpr (IS_CULL(SRC)) {
         if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
     }
-    auto nearest = [&](int j, auto m, uint32_t kind, auto) {
-        if (traced) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
-        return true;
-    };
     if constexpr (SRC == SRC_CULL2)
-        for_each_object<SRC, false>(A, T, L, traced, B, nearest, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
+        for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
     else
-        for_each_object<SRC>(A, T, L, traced, B, nearest, ro, rd);
+        for_each_object<SRC>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
     const bool hit = traced && hidx >= 0;
 
     // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96), the part the planes hold ----
@@ -2506,21 +2522,7 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
             const DevShade *S = T.shade + hidx;
             const double *m_obj = T.isect[hidx].m;
             const V3 eyev = vneg(rd);
-            V3 ln = mk(0., 1., 0.); // Shape::normal_at shape.rs:34-40
-            const uint32_t kind = S->kind;
-            if (kind == RTC_SPHERE) {
-                const V3 lp = xpoint(m_obj, point);
-                ln = mk(lp.x - 0., lp.y - 0., lp.z - 0.);
-            } else if (kind == RTC_CUBE) { // Cube::normal_at_local shape.rs:601-610
-                const V3 lp = xpoint(m_obj, point);
-                const double ax = fabs(lp.x), ay = fabs(lp.y), az = fabs(lp.z);
-                const double maxc = fmax(ax, fmax(ay, az));
-                if (maxc == ax) ln = mk(lp.x, 0., 0.);
-                else if (maxc == ay) ln = mk(0., lp.y, 0.);
-                else ln = mk(0., 0., lp.z);
-            }
-            if (kind == RTC_PLANE) normal = mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]); // evaluated once per object (DevShade)
-            else normal = vnormalize_plain(xvector3(S->nt, ln));
+            normal = shape_normal(S, m_obj, point);
             inside = vdot(normal, eyev) < 0.0;
             if (inside) normal = vneg(normal);
             over = vadd(point, vmul(normal, RTC_EPSILON));
@@ -2533,11 +2535,7 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
         auto one_light = [&](V3 lp) {
             V3 ldir = mk(0., 0., 0.);
             double ldist = 0.;
-            if (hit) {
-                const V3 v = vsub(lp, over);
-                ldist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
-                ldir = mk(v.x / ldist, v.y / ldist, v.z / ldist);
-            }
+            shadow_ray(lp, over, hit, ldir, ldist);
             bool pending = hit, shadowed = false;
             Bundle Bl{};
             Bl.off = true;
@@ -2545,12 +2543,7 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
                 if (ballot(hit) != 0ull) Bl = make_bundle<true, true>(hit, lp, lp, vneg(ldir), ldist);
             }
             // (the per-lane prefilter in front of the exact tests where k_trace's flat kernels have it: two-level Worlds)
-            for_each_object<SRC, SRC == SRC_CULL2>(A, T, L, pending, Bl, [&](int, auto m, uint32_t kind, auto) {
-                if (pending) {
-                    if (occludes_world(kind, m, over, ldir, ldist)) { shadowed = true; pending = false; }
-                }
-                return ballot(pending) != 0ull; // stop as soon as no lane is pending
-            }, over, ldir);
+            for_each_object<SRC, SRC == SRC_CULL2>(A, T, L, pending, Bl, AnyHit{pending, over, ldir, ldist, shadowed}, over, ldir);
             if (shadowed) ++count;
         };
         one_light(mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]));
@@ -2592,6 +2585,24 @@ __global__ void __launch_bounds__(256) k_aov_view(const AovViewParams V) {
     V.out[3u * i + 2u] = o[2];
 }
 
+// ---- launch dispatch (rtc_launch_aov, rtc_launch_trace) -----------------------------------------------------------
+// The runtime `src` as a compile-time constant: f(std::integral_constant<int, SRC_x>) for the one of `ALLOWED` it equals.
+template <int... ALLOWED, class F> static hipError_t with_src(int src, F &&f) {
+    hipError_t e = hipErrorInvalidValue; // (a source the launch does not take)
+    (void)(... || (src == ALLOWED && ((e = f(std::integral_constant<int, ALLOWED>{})), true)));
+    return e;
+}
+// A World's further lights as the kernel's trailing argument: f() for one light, f(*xl) for the kernel-argument block,
+// f(*lt) for the device table (never both).
+template <class F> static hipError_t with_further_lights(const DevExtraLights *xl, const DevLightTable *lt, F &&f) {
+    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
+    if (xl != nullptr && (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u)) return hipErrorInvalidValue;
+    if (lt != nullptr && (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u)) return hipErrorInvalidValue;
+    if (xl != nullptr) return f(*xl);
+    if (lt != nullptr) return f(*lt);
+    return f();
+}
+
 template <int SRC, bool SHADOW, class... XL>
 static hipError_t launch_aov(const AovParams &A, const RenderParams &P, uint32_t tiles, hipStream_t stream, const XL &...xl) {
     hipLaunchKernelGGL((k_aov<SRC, SHADOW, XL...>), dim3(tiles), dim3(64), 0, stream, A, P.isect, P.kind, P.shade, P.bound, P.isect_s, P.kind_s,
@@ -2607,21 +2618,12 @@ extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, 
     const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
     if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
     const uint32_t tiles = (uint32_t)tiles64;
-    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
-    if (xl != nullptr && (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u)) return hipErrorInvalidValue;
-    if (lt != nullptr && (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u)) return hipErrorInvalidValue;
-#define RTC_AOV_CASE(S)                                                                  \
-    if (src == S) {                                                                      \
-        if (A->shadow == nullptr) return launch_aov<S, false>(*A, *P, tiles, stream);    \
-        if (xl != nullptr) return launch_aov<S, true>(*A, *P, tiles, stream, *xl);       \
-        if (lt != nullptr) return launch_aov<S, true>(*A, *P, tiles, stream, *lt);       \
-        return launch_aov<S, true>(*A, *P, tiles, stream);                               \
-    }
-    RTC_AOV_CASE(SRC_SMEM)
-    RTC_AOV_CASE(SRC_CULL)
-    RTC_AOV_CASE(SRC_CULL2)
-#undef RTC_AOV_CASE
-    return hipErrorInvalidValue;
+    return with_further_lights(xl, lt, [&](const auto &...x) {
+        return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+            if (A->shadow == nullptr) return launch_aov<S(), false>(*A, *P, tiles, stream); // no shadow rays: the further lights are not read
+            return launch_aov<S(), true>(*A, *P, tiles, stream, x...);
+        });
+    });
 }
 
 extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t stream) {
@@ -2662,60 +2664,28 @@ extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
                                        const DevLightTable *lt, const DevLens *lens) {
     const dim3 grid(nblocks);
-    if (xl != nullptr && lt != nullptr) return hipErrorInvalidValue;
-    if (xl != nullptr && (xl->n == 0u || xl->n > RTC_MAX_LIGHTS - 1u)) return hipErrorInvalidValue;
-    if (lt != nullptr && (lt->rec == nullptr || lt->n == 0u || lt->n > RTC_MAX_LIGHT_SAMPLES - 1u)) return hipErrorInvalidValue;
-    if (lens != nullptr) {
-        if (P->rays != nullptr || P->gamma != nullptr || P->samples != 1u || lens->usteps == 0u || lens->vsteps == 0u ||
-            (unsigned long long)lens->usteps * lens->vsteps > RTC_MAX_LENS_SAMPLES)
-            return hipErrorInvalidValue;
-#define RTC_LENS_CASE(S, ...)                                                                                                        \
-    if (src == S) {                                                                                                                  \
-        if (refr) return launch_kernel<S, true, true, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__, *lens);      \
-        if (refl) return launch_kernel<S, true, false, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__, *lens);     \
-        return launch_kernel<S, false, false, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__, *lens);              \
-    }
-        if (xl != nullptr) {
-            RTC_LENS_CASE(SRC_SMEM, *xl)
-            RTC_LENS_CASE(SRC_CULL, *xl)
-            RTC_LENS_CASE(SRC_CULL2, *xl)
-        } else if (lt != nullptr) {
-            RTC_LENS_CASE(SRC_SMEM, *lt)
-            RTC_LENS_CASE(SRC_CULL, *lt)
-            RTC_LENS_CASE(SRC_CULL2, *lt)
-        } else {
-            RTC_LENS_CASE(SRC_SMEM)
-            RTC_LENS_CASE(SRC_CULL)
-            RTC_LENS_CASE(SRC_CULL2)
+    // the recursion flavour: refractive Worlds carry the full frame stack, reflective ones the LDS stack, the others none
+    auto with_depth = [&](auto &&launch) {
+        if (refr) return launch(std::true_type{}, std::true_type{});
+        if (refl) return launch(std::true_type{}, std::false_type{});
+        return launch(std::false_type{}, std::false_type{});
+    };
+    return with_further_lights(xl, lt, [&](const auto &...x) {
+        if (lens != nullptr) {
+            if (P->rays != nullptr || P->gamma != nullptr || P->samples != 1u || lens->usteps == 0u || lens->vsteps == 0u ||
+                (unsigned long long)lens->usteps * lens->vsteps > RTC_MAX_LENS_SAMPLES)
+                return hipErrorInvalidValue;
+            return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+                return with_depth([&](auto RL, auto RR) { return launch_kernel<S(), RL(), RR(), false, false>(*P, grid, lds_bytes, stream, e0, e1, x..., *lens); });
+            });
         }
-#undef RTC_LENS_CASE
-        return hipErrorInvalidValue;
-    }
-#define RTC_CASE(S, ...)                                                                            \
-    if (src == S) {                                                                            \
-        if (refr) return launch_one<S, true, true>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);               \
-        if (refl) return launch_one<S, true, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);              \
-        return launch_one<S, false, false>(*P, grid, lds_bytes, stream, e0, e1, ##__VA_ARGS__);                       \
-    }
-    if (xl != nullptr) {
-        RTC_CASE(SRC_SMEM, *xl)
-        RTC_CASE(SRC_CULL, *xl)
-        RTC_CASE(SRC_CULL2, *xl)
-        return hipErrorInvalidValue;
-    }
-    if (lt != nullptr) {
-        RTC_CASE(SRC_SMEM, *lt)
-        RTC_CASE(SRC_CULL, *lt)
-        RTC_CASE(SRC_CULL2, *lt)
-        return hipErrorInvalidValue;
-    }
-    RTC_CASE(SRC_SMEM)
-    RTC_CASE(SRC_LDS1)
-    RTC_CASE(SRC_LDSN)
-    RTC_CASE(SRC_CULL)
-    RTC_CASE(SRC_CULL2)
-#undef RTC_CASE
-    return hipErrorInvalidValue;
+        auto flavours = [&](auto S) {
+            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, grid, lds_bytes, stream, e0, e1, x...); });
+        };
+        // the LDS-staged sources exist for one-light pinhole launches only
+        if constexpr (sizeof...(x) == 0) return with_src<SRC_SMEM, SRC_LDS1, SRC_LDSN, SRC_CULL, SRC_CULL2>(src, flavours);
+        else return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, flavours);
+    });
 }
 
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],

@@ -1,14 +1,16 @@
 """Register / scratch / LDS use of every k_trace and k_aov instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
 usage: python tools/kernel_resources.py [extra -D flags]"""
+import importlib.util
 import re
 import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-       f"-I{ROOT / 'include'}", f"-I{ROOT / 'raytracer-challenge_amd' / 'csrc'}", "-mllvm", "-disable-machine-licm",
-       "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:], "-c", str(ROOT / "raytracer-challenge_amd" / "csrc" / "rtc_kernels.hip"),
+spec = importlib.util.spec_from_file_location("_rtc_build", ROOT / "raytracer-challenge_amd" / "build.py")
+build = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(build)
+cmd = [*build.kernel_compile_line(), "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:], "-c", str(build.CSRC / "rtc_kernels.hip"),
        "-o", "/tmp/rtc_k.o"]
 t = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows = []
