@@ -18,6 +18,7 @@
 #include "rtc_aov.h"
 #include "rtc_device.h"
 #include "rtc_internal.h"
+#include "rtc_launch_plan.h"
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
@@ -47,33 +48,6 @@ hipError_t drain_lanes(rtc_context *ctx) {
             if (e != hipSuccess) return e;
         }
     return hipSuccess;
-}
-
-// `multi`: a World with several lights. Its kernels exist for SRC_SMEM, SRC_CULL and SRC_CULL2 only, so the brute-force
-// choice is SRC_SMEM at every size; an LDS source can then only come out of RTC_FLAG_LDS_TABLE or an RTC_SRC override,
-// which the callers refuse (lights_of).
-void choose_source(const rtc_context *ctx, uint32_t n, uint32_t flags, int *src, uint32_t *tile_cap, size_t *lds_bytes, bool multi = false) {
-    // per object in LDS: 96 B inverse rows + 32 B primary prologue + 4 B kind
-    const uint32_t per_obj = 96 + 32 + 4;
-    int s;
-    if (ctx->force_src >= 0) s = ctx->force_src;
-    else if (!(flags & RTC_FLAG_NO_CULL)) s = (n > 256) ? SRC_CULL2 : SRC_CULL; // default: per-wave conservative cull,
-                                                                              // two-level above 4 groups of 64
-    else if (flags & RTC_FLAG_LDS_TABLE) s = SRC_LDS1; // brute force over the LDS-staged object table (LDS tiles when it does not fit)
-    else if (n <= 128 || multi) s = SRC_SMEM;
-    else if (n <= 448) s = SRC_LDS1;
-    else s = SRC_LDSN;
-    uint32_t cap = 0;
-    if (s == SRC_LDS1) {
-        if ((size_t)n * per_obj > 150 * 1024) s = SRC_LDSN;
-        else cap = n ? n : 1;
-    }
-    if (s == SRC_LDSN) cap = ctx->tile_cap;
-    if (s == SRC_SMEM || s == SRC_CULL || s == SRC_CULL2) cap = 0;
-    *src = s;
-    *tile_cap = cap;
-    // kinds sit behind cap*16 doubles; round the block up to 16 bytes
-    *lds_bytes = cap ? (((size_t)cap * per_obj + 15) & ~(size_t)15) : 0;
 }
 
 // 63-bit Morton key of a point inside the box [lo, hi]^3 (21 bits per axis).
@@ -243,23 +217,22 @@ void fill_world(RenderParams &P, const rtc_world::Gen &G) {
 
 // The further lights of generation G as k_trace's trailing argument: *xl (the kernel-argument block) or *lt (the
 // generation's device table, Gen::light_table); both nullptr for a one-light World (the kernels without that argument).
-// RTC_ERR_UNSUPPORTED when the launch's source has no multi-light kernels.
+// (Whether the launch's source has multi-light kernels at all is the plan's business: rtc_launch_plan.h.)
 struct LaunchLights {
     DevExtraLights extra;
     DevLightTable table;
     const DevExtraLights *xl = nullptr;
     const DevLightTable *lt = nullptr;
 };
-rtc_status lights_of(const rtc_world::Gen &G, int src, LaunchLights &L) {
+void lights_of(const rtc_world::Gen &G, LaunchLights &L) {
     L.xl = nullptr;
     L.lt = nullptr;
-    if (G.n_lights <= 1u) return RTC_OK;
-    if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED;
+    if (G.n_lights <= 1u) return;
     if (G.light_table) {
         L.table.rec = G.ltab;
         L.table.n = G.n_lights - 1u;
         L.lt = &L.table;
-        return RTC_OK;
+        return;
     }
     DevExtraLights &X = L.extra;
     std::memset(&X, 0, sizeof X);
@@ -270,7 +243,6 @@ rtc_status lights_of(const rtc_world::Gen &G, int src, LaunchLights &L) {
             X.inten[i][k] = G.more[i].intensity[k];
         }
     L.xl = &X;
-    return RTC_OK;
 }
 
 // L[0] and L[1..n) of a generation, from the caller's array. More than RTC_MAX_LIGHTS of them (or RTC_LIGHT_TABLE=1 and
@@ -1015,33 +987,32 @@ void rtc_world_destroy(rtc_world *w) {
     delete w; // its device buffers too, the device current and idle
 }
 
-// Readies binning set S for a launch: tile lists for `tiles` (view, tile) entries, grown to `tiles_alloc` when they are
-// smaller, and primary-ray records for `prims` (object, view) pairs, grown to `prims_alloc`. A pipelined launch (`sync`)
-// first waits for its lane, which may still read the set. False when there is no memory for the lists: they are an
+// Readies binning set S for a launch: tile lists for the plan's `tiles` (view, tile) entries, grown to `tiles_alloc` when
+// they are smaller, and primary-ray records for `prims` (object, view) pairs, grown to `prims_alloc`. A pipelined launch
+// (`sync`) first waits for its lane, which may still read the set. False when there is no memory for the lists: they are an
 // optimisation, and the launch walks instead (same pixels).
-static bool ready_binset(rtc_context *ctx, rtc_world::BinSet &S, size_t tiles, size_t tiles_alloc, size_t prims, size_t prims_alloc,
-                         bool sync, hipStream_t stream) {
-    if (S.tile_list.capacity() < tiles * RTC_TILE_LIST_CAP) {
+static bool ready_binset(rtc_context *ctx, rtc_world::BinSet &S, const LaunchPlan &plan, bool sync, hipStream_t stream) {
+    if (S.tile_list.capacity() < plan.tiles * RTC_TILE_LIST_CAP) {
         if (sync) (void)hipStreamSynchronize(stream);
         S.tile_cnt.reset(); // both old lists go before either new one is allocated
         S.tile_list.reset();
-        if (S.tile_cnt.reserve(tiles_alloc + RTC_BIN_ROW_WORDS, &ctx->render_allocs) != RTC_OK ||
-            S.tile_list.reserve(tiles_alloc * RTC_TILE_LIST_CAP, &ctx->render_allocs) != RTC_OK) {
+        if (S.tile_cnt.reserve(plan.tiles_alloc + RTC_BIN_ROW_WORDS, &ctx->render_allocs) != RTC_OK ||
+            S.tile_list.reserve(plan.tiles_alloc * RTC_TILE_LIST_CAP, &ctx->render_allocs) != RTC_OK) {
             S.tile_cnt.reset();
             return false;
         }
     }
-    if (S.prim.capacity() < prims) {
+    if (S.prim.capacity() < plan.prims) {
         if (sync) (void)hipStreamSynchronize(stream);
-        if (S.prim.reserve(prims_alloc, &ctx->render_allocs) != RTC_OK) return false;
+        if (S.prim.reserve(plan.prims_alloc, &ctx->render_allocs) != RTC_OK) return false;
     }
     return true;
 }
 
 // k_bin_tiles of the launch's views into set B on `stream` (timed by the event pair `ev`, if any), and the render
 // parameters that read the set.
-static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_world::BinSet &B, bool sky_rows, hipStream_t stream,
-                            const hipEvent_t *ev) {
+static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_world::BinSet &B, const LaunchPlan &plan, bool sky_rows,
+                            hipStream_t stream, const hipEvent_t *ev) {
     uint32_t *cnt = B.tile_cnt.get() + RTC_BIN_ROW_WORDS;
     const hipError_t e = rtc_launch_binning(P.views, P.nviews, P.W, P.H, G.n, G.bound_s, G.gbound, G.orig_s,
                                             G.ngroups, cnt, B.tile_list.get(), P.y0 / 8u, P.band_stride, stream, ev ? ev[0] : nullptr,
@@ -1052,72 +1023,130 @@ static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_
     P.tile_rows = sky_rows ? B.tile_cnt.get() : nullptr;
     P.tile_cnt = cnt;
     P.tile_list = B.tile_list.get();
-    P.tiles_x = (P.W + 7u) / 8u;
-    P.tiles_y = (P.H + 7u) / 8u;
+    P.tiles_x = plan.tiles_x;
+    P.tiles_y = plan.tiles_y;
     P.bin_packed = RTC_BIN_PACKED(G.n) ? 1u : 0u;
     P.n_unb = G.n_unb;
     return hipSuccess;
 }
 
-// rows [y0, y1) in tile rows of 8, tile row k at image rows y0 + 8*k*band_stride; grid_y tile rows. gamma > 0: d_rgb8
-// receives Canvas::to_imgbuf's RGBA at that gamma (4 B/pixel) instead of Color::scale's RGB.
-// lens (validated by the caller, one view, no gamma): a thin-lens launch. Its rays do not start at the camera origin, so it
-// runs no binning kernel and no per-view table — tile lists, black tile rows and DevPrim all assume that origin — never
-// takes an LDS source (there are no lens kernels for them), and launches one workgroup per tile, every tile row included.
-static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t y0,
-                                uint32_t y1, uint32_t band_stride, uint32_t grid_y, void *d_rgb, void *d_rgb8,
-                                uint32_t flags, uint32_t nviews = 1, uint32_t view_rows = 0, float gamma = 0.f,
-                                const rtc_lens *lens = nullptr) {
+// One render launch, as its entry point asks for it. Rows [y0, y1) in tile rows of 8, tile row k at image rows
+// y0 + 8*k*band_stride; grid_y tile rows; `nviews` cameras of one size, view v `view_rows` rows further down the outputs.
+struct LaunchRequest {
+    const rtc_camera *cams = nullptr;
+    uint32_t nviews = 1, view_rows = 0;
+    uint32_t mode = 0, y0 = 0, y1 = 0, band_stride = 1, grid_y = 0;
+    void *d_rgb = nullptr, *d_rgb8 = nullptr;
+    uint32_t flags = 0;
+    float gamma = 0.f;            // > 0: d_rgb8 receives Canvas::to_imgbuf's RGBA at that gamma (4 B/pixel) instead of Color::scale's RGB
+    const rtc_lens *lens = nullptr; // a thin-lens launch (validated by the caller, one view, no gamma)
+};
+// rows [y0, y1) of one camera
+static LaunchRequest rows_request(const rtc_camera *cam, uint32_t mode, uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags) {
+    LaunchRequest rq;
+    rq.cams = cam; rq.mode = mode; rq.y0 = y0; rq.y1 = y1; rq.grid_y = (y1 - y0 + 7u) / 8u;
+    rq.d_rgb = d_rgb; rq.d_rgb8 = d_rgb8; rq.flags = flags;
+    return rq;
+}
+// every band_stride-th band of 8 rows from first_band on: the caller's share of the canvas, packed (rtc_bands.h). False:
+// it owns no band of so small a canvas.
+static bool bands_request(const rtc_camera *cam, uint32_t mode, uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8,
+                          uint32_t flags, LaunchRequest &rq) {
+    const uint32_t nbands = (cam->vsize + RTC_BAND_ROWS - 1u) / RTC_BAND_ROWS;
+    if (first_band >= nbands) return false;
+    rq = rows_request(cam, mode, first_band * RTC_BAND_ROWS, cam->vsize, d_rgb, d_rgb8, flags);
+    rq.band_stride = band_stride;
+    rq.grid_y = (nbands - first_band + band_stride - 1u) / band_stride;
+    return true;
+}
+
+// rtc_plan_launch for a launch of kind `kind` of generation G on this context: the knobs and the World's facts; the
+// caller adds what it asks for.
+static LaunchPlanInputs plan_inputs(const rtc_context *ctx, const rtc_world::Gen &G, uint32_t kind, uint32_t flags) {
+    LaunchPlanInputs in{};
+    in.force_src = ctx->force_src;
+    in.tile_cap = ctx->tile_cap;
+    in.tiles_per_wg = ctx->tiles_per_wg;
+    in.tiles_guided_tenths = ctx->tiles_guided_tenths;
+    in.tiles_slots = ctx->tiles_slots;
+    in.tiles_kmax = ctx->tiles_kmax;
+    in.binning = ctx->binning;
+    in.pipelined = ctx->lanes > 1;
+    in.bin_small_pixels = ctx->bin_small_pixels;
+    in.bin_small_pixels_pipelined = ctx->bin_small_pixels_pipelined;
+    in.n = G.n;
+    in.n_lights = G.n_lights;
+    in.any_refl = G.any_refl;
+    in.any_refr = G.any_refr;
+    in.kind = kind;
+    in.flags = flags;
+    return in;
+}
+
+// Where every render launch starts: the device current, the World's current generation, the plan of `rq` on it.
+static rtc_status plan_request(const rtc_context *ctx, const rtc_world *w, const LaunchRequest &rq, rtc_world::Gen **gen, LaunchPlan &plan) {
     HIP_TRY(hipSetDevice(ctx->device));
-    rtc_world::Gen *gen = nullptr;
-    const rtc_status hs = current_gen(w, &gen);
+    const rtc_status hs = current_gen(w, gen);
     if (hs != RTC_OK) return hs;
-    rtc_world::Gen &G = *gen;
-    RenderParams P;
+    LaunchPlanInputs in = plan_inputs(ctx, **gen, RTC_PLAN_FRAME, rq.flags);
+    in.hsize = rq.cams->hsize; in.vsize = rq.cams->vsize; in.samples = rq.cams->samples; in.nviews = rq.nviews;
+    in.y0 = rq.y0; in.y1 = rq.y1; in.band_stride = rq.band_stride; in.grid_y = rq.grid_y;
+    in.mode = rq.mode;
+    in.lens_samples = rq.lens ? rq.lens->usteps * rq.lens->vsteps : 0u;
+    rtc_plan_launch(in, plan);
+    return RTC_OK;
+}
+
+// The parameter block of a planned launch on generation G: the World's tables and what the plan fixes. The caller adds its
+// cameras or rays and its outputs.
+static void planned_params(const rtc_context *ctx, const rtc_world *w, const rtc_world::Gen &G, const LaunchPlan &plan, RenderParams &P) {
     std::memset(&P, 0, sizeof P);
     fill_world(P, G);
     P.prim = w->d_prim.get();
     if (!ctx->light_lists) P.light_cnt = nullptr;
-    for (uint32_t v = 0; v < nviews; ++v) fill_camera(P, cam + v, v);
-    P.nviews = nviews;
-    P.view_rows = view_rows;
-    P.y0 = y0;
-    P.y1 = y1;
-    P.mode = mode;
-    P.out = static_cast<double *>(d_rgb);
-    P.out8 = static_cast<unsigned char *>(d_rgb8);
+    P.tile_cap = plan.tile_cap;
+    P.flags = plan.flags;
+    P.aa_lds_off = plan.aa_lds_off;
+    P.resample_n = plan.resample_n;
+    P.grid_x = plan.grid_x;
+    P.total_blocks = plan.total_blocks;
+    P.reps = plan.reps;
+    std::memcpy(P.chunk_wgs, plan.chunk_wgs, sizeof P.chunk_wgs);
+}
+static hipError_t trace_planned(const RenderParams &P, const LaunchPlan &plan, const LaunchLights &LL, hipStream_t stream, hipEvent_t e0,
+                                hipEvent_t e1, const DevLens *lens) {
+    return rtc_launch_trace(&P, plan.src, (int)plan.refl, (int)plan.refr, plan.grid_wgs, plan.lds_bytes, stream, e0, e1, LL.xl, LL.lt, lens);
+}
+
+// Carries `plan` (of `rq`, on generation G) out: pick the stream and order it behind the World's build; bin, or prepare the
+// brute-force table; trace; keep the books. What only the device knows at run time is decided here and nowhere else: the
+// walk when there is no memory for the tile lists, the lane, the timing ring, the gamma table.
+static rtc_status launch_planned(rtc_context *ctx, const rtc_world *w, rtc_world::Gen &G, const LaunchRequest &rq, const LaunchPlan &plan) {
+    if (plan.status != RTC_OK) return (rtc_status)plan.status;
+    RenderParams P;
+    planned_params(ctx, w, G, plan, P);
+    for (uint32_t v = 0; v < rq.nviews; ++v) fill_camera(P, rq.cams + v, v);
+    P.nviews = rq.nviews;
+    P.view_rows = rq.view_rows;
+    P.y0 = rq.y0;
+    P.y1 = rq.y1;
+    P.mode = rq.mode;
+    P.grid_y = rq.grid_y;
+    P.band_stride = rq.band_stride;
+    P.out = static_cast<double *>(rq.d_rgb);
+    P.out8 = static_cast<unsigned char *>(rq.d_rgb8);
     P.counters = ctx->d_counters.get();
-    P.rays = nullptr;
     P.remaining = RTC_MAX_REFLECTIONS; // render_pixel passes Camera::MAX_REFLECTIONS camera.rs:98
-    int src;
-    size_t lds_bytes;
-    choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u || lens != nullptr);
     LaunchLights LL;
-    const rtc_status ls = lights_of(G, src, LL);
-    if (ls != RTC_OK) return ls;
+    lights_of(G, LL);
     DevLens dlens;
-    if (lens) {
-        if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED; // RTC_FLAG_LDS_TABLE, RTC_SRC=1|2
-        flags &= ~(uint32_t)RTC_FLAG_AA_RESAMPLE;
+    if (const rtc_lens *lens = rq.lens) {
         dlens.aperture = lens->aperture;
         dlens.focal_distance = lens->focal_distance;
         dlens.ucell = (2.0 * lens->aperture) / static_cast<double>(lens->usteps); // include/rtc.h's order (no contraction in this file)
         dlens.vcell = (2.0 * lens->aperture) / static_cast<double>(lens->vsteps);
         dlens.usteps = lens->usteps;
         dlens.vsteps = lens->vsteps;
-    }
-    const int cull = CULL_LEVEL(src);
-    const bool refl = G.any_refl || G.any_refr;
-    const uint32_t block = RTC_BLOCK_FOR(cull, refl, G.any_refr, false), tile_w = RTC_TILE_W_FOR(cull, refl, G.any_refr, false);
-    P.grid_x = (cam->hsize + tile_w - 1u) / tile_w;
-    P.grid_y = grid_y;
-    P.band_stride = band_stride;
-    P.flags = flags;
-    if (P.samples != 1u) { // the 4 sub-samples of every pixel wait in LDS for the resample test (camera.rs:108)
-        P.aa_lds_off = (uint32_t)lds_bytes;
-        lds_bytes += (size_t)block * 15u * sizeof(double); // + the running sums
-        // Camera::resample traces `antialiasing_samples` more rays (camera.rs:87); u8 in the reference
-        P.resample_n = (flags & RTC_FLAG_AA_RESAMPLE) ? (cam->samples & 0xffu) : 0u;
     }
     // start/stop events cost ~9 us of host time and ~5 us of GPU time per launch (measured): callers
     // that are launch-bound sample every n-th launch instead (rtc_context_set_timing)
@@ -1126,57 +1155,37 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
     if (timed && slot >= ctx->ev_created) // next chunk of the ring
         HIP_TRY(create_events(ctx, std::min<uint32_t>(rtc_context::EV_RING, ctx->ev_created + rtc_context::EV_CHUNK)));
     hipEvent_t *pair = ctx->ev[slot], *pair_bin = ctx->ev_bin[slot];
-    // Which stream. A pipelined context deals the launches round-robin over its lanes; the brute-force variants share one
-    // per-render table (w->d_prim) and stay in order on lane 0.
+    // Which stream. A pipelined context deals the launches round-robin over its lanes; those the plan keeps in order stay on lane 0.
     const bool piped = ctx->lanes > 1;
-    const uint32_t lane = piped ? ((src == SRC_CULL || src == SRC_CULL2) ? (uint32_t)(ctx->lane_next++ % ctx->lanes) : 0u) : 0u;
+    const uint32_t lane = piped && plan.lane_dealt ? (uint32_t)(ctx->lane_next++ % ctx->lanes) : 0u;
     hipStream_t stream = piped ? ctx->lane[lane] : ctx->stream;
     const uint32_t stream_bit = piped ? lane : BIT_STREAM;
     HIP_TRY(order_behind_build(G, stream, stream_bit));
-    if (gamma > 0.f) { // the table goes to the device on this launch's own stream (or is waited for there once)
-        const rtc_status gs = gamma_table(ctx, gamma, stream, piped ? lane : rtc_context::MAX_LANES, &P.gamma);
+    if (rq.gamma > 0.f) { // the table goes to the device on this launch's own stream (or is waited for there once)
+        const rtc_status gs = gamma_table(ctx, rq.gamma, stream, piped ? lane : rtc_context::MAX_LANES, &P.gamma);
         if (gs != RTC_OK) return gs;
     }
-    // the part of the frame this launch renders, in pixels (a rank's bands: its share)
-    const unsigned long long launch_pixels = (unsigned long long)nviews * cam->hsize * std::min<unsigned long long>((unsigned long long)grid_y * 8u, cam->vsize);
-    // binned primary pass (tile rows aligned with the image's): one small kernel puts every object on the list of each 8x8
-    // tile its bounding sphere can touch (same conservative predicate as the wave-level cull), so the render kernel's primary
-    // pass runs exact tests on a short list instead of walking the groups. Two-level worlds always; one-level worlds when the
-    // launch is long enough for the extra kernel (and, in order on one stream, its two cross-stream events) to pay:
-    // bin_small_pixels counts the pixels THIS launch renders — whole frames or one rank's bands (k_bin_tiles lists only the
-    // tile rows the launch renders).
-    const bool bin_this = (src == SRC_CULL2) ||
-                          (src == SRC_CULL && (piped ? launch_pixels >= ctx->bin_small_pixels_pipelined
-                                                     : launch_pixels >= ctx->bin_small_pixels));
     rtc_world::BinSet *binset = nullptr;
     int bin_set = -1; // which of w->bin this launch's lists are in (rtc_debug_tile_counts)
-    bool bin_ok = bin_this && ctx->binning && (y0 % 8u) == 0u && G.n != 0u && !lens;
-    const uint32_t tiles_x = (cam->hsize + 7u) / 8u, tiles_y = (cam->vsize + 7u) / 8u;
-    const size_t tiles = (size_t)tiles_x * tiles_y * nviews;
+    bool bin_ok = plan.bin != 0u;
     if (bin_ok && piped) {
         // lane-local lists: the binning kernel precedes the render kernel on the lane's own stream and runs beside the other
-        // lanes' render kernels — no events. Sized for the largest launch seen (grow-only; growing waits for the lane).
+        // lanes' render kernels — no events. Grow-only; growing waits for the lane.
         rtc_world::BinSet &B = w->bin[lane];
-        bin_ok = ready_binset(ctx, B, tiles, tiles, (size_t)G.n * nviews, (size_t)G.n * nviews, true, stream);
-        if (bin_ok) HIP_TRY(bin_tiles(P, G, B, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
+        bin_ok = ready_binset(ctx, B, plan, true, stream);
+        if (bin_ok) HIP_TRY(bin_tiles(P, G, B, plan, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
         if (bin_ok) bin_set = (int)lane;
     } else if (bin_ok) {
         if (!ctx->side_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-        // Capacity. Both sets are made ready by the FIRST binned launch, and for RTC_MAX_VIEWS views while that stays within
-        // 128 MB per set (1080p: 67 MB; larger frames: exactly the launch's views, growing once if a later launch has more): a
-        // launch sequence must not allocate after its first launch — hipMalloc / hipFree wait for the device, 0.2-3 ms in the
-        // middle of a frame sequence (a 5-frame warm-up launch followed by 8-frame launches did exactly that: 0.09-0.22 ms per
-        // frame instead of 0.07). The lists are an optimisation: when there is no memory for them the launch walks instead.
-        const size_t per_view_bytes = (size_t)tiles_x * tiles_y * sizeof(uint32_t) * (1u + RTC_TILE_LIST_CAP);
-        const uint32_t alloc_views = per_view_bytes * RTC_MAX_VIEWS <= ((size_t)128 << 20) ? (uint32_t)RTC_MAX_VIEWS : nviews;
-        const size_t tiles_alloc = (size_t)tiles_x * tiles_y * alloc_views;
+        // Both sets are made ready by the FIRST binned launch (the plan's tiles_alloc / prims_alloc: a launch sequence must
+        // not allocate after its first launch). When there is no memory for them the launch walks instead.
         for (uint32_t k = 0; k < 2u && bin_ok; ++k) {
             rtc_world::BinSet &S = w->bin[k];
             if (!S.binned) {
                 HIP_TRY(hipEventCreateWithFlags(&S.binned, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&S.traced, hipEventDisableTiming));
             }
-            bin_ok = ready_binset(ctx, S, tiles, tiles_alloc, (size_t)G.n * nviews, (size_t)G.n * std::max(alloc_views, nviews), false, stream);
+            bin_ok = ready_binset(ctx, S, plan, false, stream);
         }
     }
     if (bin_ok && !piped) {
@@ -1187,76 +1196,37 @@ static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const rtc_
         // wait for the render kernel that last read THIS set (two launches ago); the render stream waits for the binning.
         HIP_TRY(hipStreamWaitEvent(ctx->side_stream, B.traced, 0)); // never recorded: no wait
         HIP_TRY(order_behind_build(G, ctx->side_stream, BIT_SIDE));
-        HIP_TRY(bin_tiles(P, G, B, ctx->sky_rows, ctx->side_stream, timed ? pair_bin : nullptr));
+        HIP_TRY(bin_tiles(P, G, B, plan, ctx->sky_rows, ctx->side_stream, timed ? pair_bin : nullptr));
         HIP_TRY(hipEventRecord(B.binned, ctx->side_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, B.binned, 0));
         binset = &B;
     }
     if (timed) ctx->bin_timed[slot] = P.tile_cnt != nullptr;
-    // per-render prologue table of the brute-force variants (the culled kernels do not use it)
-    if (src != SRC_CULL && src != SRC_CULL2 && !lens) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
-    P.total_blocks = P.grid_x * P.grid_y * nviews;
-    P.reps = lens ? 1u : ctx->tiles_per_wg;
-    // Guided chunks (RenderParams::chunk_wgs): with `slots` workgroups resident at once, the launch's last f x slots tiles go one
-    // per workgroup, the f x slots before them two, then three, four, and everything earlier eight (f = RTC_TILES_GUIDED
-    // tenths, default 2.0; 0 = off; the largest chunk = RTC_TILES_KMAX). Launches of fewer than 3 rounds of workgroups are left alone.
-    P.chunk_wgs[0] = P.chunk_wgs[1] = P.chunk_wgs[2] = P.chunk_wgs[3] = 0u;
-    uint32_t grid_wgs = (P.total_blocks + P.reps - 1u) / P.reps;
-    {
-        static const uint32_t sizes[5] = {1u, 2u, 3u, 4u, 8u}; // chunk sizes from the END of the launch backwards
-        const uint32_t slots = ctx->tiles_slots ? ctx->tiles_slots : (1024u * ((G.any_refl || G.any_refr) ? 4u : 5u) / std::max(1u, block / 64u));
-        const unsigned long long per_level = (unsigned long long)slots * ctx->tiles_guided_tenths / 10u;
-        uint32_t nlevels = 1;
-        while (nlevels < 5u && sizes[nlevels] <= ctx->tiles_kmax) ++nlevels;
-        // Not for a large world on a small frame (C3: 10 000 spheres at 1080p): there the NEXT launch's binning kernel is as long
-        // as this render kernel, and its few waves wait for slots that long-lived workgroups free late — the solo kernel gains
-        // 6 %, the pipelined frame loses 9 % (profiles/r03_exp_tiles_per_workgroup.log).
-        const bool heavy_binning = G.n > 4096u && launch_pixels < 8000000ull;
-        if (P.reps == 1u && per_level != 0u && nlevels > 1u && P.total_blocks >= 3u * slots && !heavy_binning && !lens) {
-            unsigned long long rest = P.total_blocks, tiles[5] = {0, 0, 0, 0, 0};
-            for (uint32_t l = 0; l < nlevels && rest; ++l) {
-                unsigned long long tk = (l + 1u == nlevels) ? rest : std::min<unsigned long long>(rest, per_level);
-                if (l) tk -= tk % sizes[l];          // whole workgroups; what does not divide joins the single-tile level
-                tiles[l] = tk;
-                rest -= tk;
-            }
-            tiles[0] += rest;
-            P.chunk_wgs[0] = (uint32_t)(tiles[4] / 8u); P.chunk_wgs[1] = (uint32_t)(tiles[3] / 4u);
-            P.chunk_wgs[2] = (uint32_t)(tiles[2] / 3u); P.chunk_wgs[3] = (uint32_t)(tiles[1] / 2u);
-            grid_wgs = P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3] + (uint32_t)tiles[0];
-        }
-    }
-    HIP_TRY(rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, grid_wgs, lds_bytes, stream,
-                             timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, LL.xl, LL.lt, lens ? &dlens : nullptr));
+    // per-render prologue table of the brute-force variants (the culled and the lens kernels do not use it)
+    if (plan.needs_prep) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
+    HIP_TRY(trace_planned(P, plan, LL, stream, timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, rq.lens ? &dlens : nullptr));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
     HIP_TRY(record_read(w, G, stream, stream_bit));
-    ctx->last = rtc_launch_info{(uint32_t)src, (G.any_refl || G.any_refr) ? 1u : 0u, G.any_refr ? 1u : 0u, P.tile_cnt ? 1u : 0u,
-                                P.light_cnt ? 1u : 0u, lane, block, (uint32_t)lds_bytes, P.reps, P.chunk_wgs[0] + P.chunk_wgs[1] + P.chunk_wgs[2] + P.chunk_wgs[3], LL.lt ? 1u : 0u,
-                                lens ? lens->usteps * lens->vsteps : 0u};
+    ctx->last = rtc_launch_info{(uint32_t)plan.src, plan.refl, plan.refr, P.tile_cnt ? 1u : 0u, P.light_cnt ? 1u : 0u, lane, plan.block,
+                                plan.lds_bytes, plan.reps, plan.chunk_wgs[0] + plan.chunk_wgs[1] + plan.chunk_wgs[2] + plan.chunk_wgs[3],
+                                LL.lt ? 1u : 0u, rq.lens ? rq.lens->usteps * rq.lens->vsteps : 0u};
     ++ctx->launches_total;
     ctx->last_bin = rtc_context::LastBin{};
-    if (P.tile_cnt && bin_set >= 0) ctx->last_bin = rtc_context::LastBin{w->serial, (uint32_t)bin_set, nviews, tiles_x, tiles_y};
-    // rtc_stats::pixels is known here (the kernel traces exactly the pixels of this launch's rows; Camera::render leaves the
-    // last row and column alone, camera.rs:120-121): counted on the host, one atomic per wave less
-    {
-        const bool serial = mode == RTC_MODE_RENDER;
-        unsigned long long rows = 0;
-        for (uint32_t k = 0; k < grid_y; ++k) {
-            const unsigned long long py0 = (unsigned long long)y0 + (unsigned long long)k * band_stride * 8u;
-            if (py0 >= y1) break;
-            unsigned long long r = y1 - py0 < 8u ? y1 - py0 : 8u;
-            if (serial && py0 + r == cam->vsize) --r; // the image's last row
-            rows += r;
-        }
-        ctx->pixels += rows * (cam->hsize - (serial ? 1u : 0u)) * nviews;
-    }
+    if (P.tile_cnt && bin_set >= 0) ctx->last_bin = rtc_context::LastBin{w->serial, (uint32_t)bin_set, rq.nviews, plan.tiles_x, plan.tiles_y};
+    ctx->pixels += plan.counted_pixels;
     ++ctx->launches;
     if (timed) ++ctx->timed;
     return RTC_OK;
 }
 
-// What rtc_render_rows, rtc_render_lens_rows and rtc_render_bands check first: a context with its own World, a camera with
-// a canvas, somewhere to write, a known mode
+static rtc_status render_launch(rtc_context *ctx, const rtc_world *w, const LaunchRequest &rq) {
+    rtc_world::Gen *gen = nullptr;
+    LaunchPlan plan;
+    const rtc_status st = plan_request(ctx, w, rq, &gen, plan);
+    return st != RTC_OK ? st : launch_planned(ctx, w, *gen, rq, plan);
+}
+
+// What every render entry checks first: a context with its own World, a camera with a canvas, somewhere to write, a known mode
 static rtc_status check_render_args(const rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, const void *d_rgb,
                                     const void *d_rgb8) {
     if (!ctx || !w || !cam || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
@@ -1269,7 +1239,7 @@ rtc_status rtc_render_rows(rtc_context *ctx, const rtc_world *w, const rtc_camer
     if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
     if (cam->samples > 255u) return RTC_ERR_ARG; // antialiasing_samples is a u8 (camera.rs:24)
     if (y0 == y1) return RTC_OK;
-    return render_launch(ctx, w, cam, mode, y0, y1, 1u, (y1 - y0 + 7u) / 8u, d_rgb, d_rgb8, flags);
+    return render_launch(ctx, w, rows_request(cam, mode, y0, y1, d_rgb, d_rgb8, flags));
 }
 
 // The checks every lens entry shares (include/rtc.h): a valid lens, one ray per lens sample
@@ -1285,17 +1255,18 @@ rtc_status rtc_render_lens_rows(rtc_context *ctx, const rtc_world *w, const rtc_
     const rtc_status ls = check_lens(cam, lens);
     if (ls != RTC_OK) return ls;
     if (y0 == y1) return RTC_OK;
-    return render_launch(ctx, w, cam, mode, y0, y1, 1u, (y1 - y0 + 7u) / 8u, d_rgb, d_rgb8, flags, 1u, 0u, 0.f, lens);
+    LaunchRequest rq = rows_request(cam, mode, y0, y1, d_rgb, d_rgb8, flags);
+    rq.lens = lens;
+    return render_launch(ctx, w, rq);
 }
 
 rtc_status rtc_render_bands(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode,
                             uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t flags) {
     if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || band_stride == 0) return RTC_ERR_ARG;
     if (cam->samples > 255u) return RTC_ERR_ARG;
-    const uint32_t nbands = (cam->vsize + RTC_BAND_ROWS - 1u) / RTC_BAND_ROWS;
-    if (first_band >= nbands) return RTC_OK; // this caller owns no band of so small a canvas
-    const uint32_t mine = (nbands - first_band + band_stride - 1u) / band_stride;
-    return render_launch(ctx, w, cam, mode, first_band * RTC_BAND_ROWS, cam->vsize, band_stride, mine, d_rgb, d_rgb8, flags);
+    LaunchRequest rq;
+    if (!bands_request(cam, mode, first_band, band_stride, d_rgb, d_rgb8, flags, rq)) return RTC_OK;
+    return render_launch(ctx, w, rq);
 }
 
 rtc_status rtc_stats_read(rtc_context *ctx, rtc_stats *out) {
@@ -1484,34 +1455,33 @@ static_assert(RTC_MAX_VIEWS == RTC_MAX_VIEWS_PER_LAUNCH, "include/rtc.h and rtc_
 static rtc_status render_views(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
                                uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t view_rows,
                                uint32_t flags, float gamma) {
-    if (!ctx || !w || !cams || (!d_rgb && !d_rgb8) || w->ctx != ctx) return RTC_ERR_ARG;
-    if (nviews == 0 || nviews > RTC_MAX_VIEWS_PER_LAUNCH || band_stride == 0 || mode > RTC_MODE_RENDER_ASYNC) return RTC_ERR_ARG;
-    if (cams[0].hsize == 0 || cams[0].vsize == 0) return RTC_ERR_ARG;
+    if (nviews == 0 || nviews > RTC_MAX_VIEWS_PER_LAUNCH || band_stride == 0) return RTC_ERR_ARG;
+    if (check_render_args(ctx, w, cams, mode, d_rgb, d_rgb8) != RTC_OK) return RTC_ERR_ARG;
     for (uint32_t v = 1; v < nviews; ++v)
         if (cams[v].hsize != cams[0].hsize || cams[v].vsize != cams[0].vsize || cams[v].samples != cams[0].samples)
             return RTC_ERR_ARG; // one grid, one sampling pattern per launch
     if (cams[0].samples > 255u) return RTC_ERR_ARG;
-    const uint32_t nbands = (cams[0].vsize + RTC_BAND_ROWS - 1u) / RTC_BAND_ROWS;
-    if (first_band >= nbands) return RTC_OK;
-    const uint32_t mine = (nbands - first_band + band_stride - 1u) / band_stride;
-    if (view_rows < mine * RTC_BAND_ROWS) return RTC_ERR_ARG;
-    int src;
-    uint32_t cap;
-    size_t lds;
-    choose_source(ctx, w->gen[w->cur].n, flags, &src, &cap, &lds);
-    if (src != SRC_CULL && src != SRC_CULL2) {
-        // the brute-force variants keep a per-render table of the camera origin in object space: one view per launch
-        for (uint32_t v = 0; v < nviews; ++v) {
-            const rtc_status st = render_launch(ctx, w, cams + v, mode, first_band * RTC_BAND_ROWS, cams[0].vsize, band_stride, mine,
-                                                d_rgb ? static_cast<double *>(d_rgb) + (size_t)v * view_rows * cams[0].hsize * 3u : nullptr,
-                                                d_rgb8 ? static_cast<unsigned char *>(d_rgb8) + (size_t)v * view_rows * cams[0].hsize * (gamma > 0.f ? 4u : 3u) : nullptr,
-                                                flags, 1u, 0u, gamma);
-            if (st != RTC_OK) return st;
-        }
-        return RTC_OK;
+    LaunchRequest rq;
+    if (!bands_request(cams, mode, first_band, band_stride, d_rgb, d_rgb8, flags, rq)) return RTC_OK;
+    if (view_rows < rq.grid_y * RTC_BAND_ROWS) return RTC_ERR_ARG;
+    rq.nviews = nviews;
+    rq.view_rows = view_rows;
+    rq.gamma = gamma;
+    rtc_world::Gen *gen = nullptr;
+    LaunchPlan plan;
+    rtc_status st = plan_request(ctx, w, rq, &gen, plan);
+    if (st != RTC_OK) return st;
+    if (!plan.needs_prep) return launch_planned(ctx, w, *gen, rq, plan);
+    // the brute-force variants keep a per-render table of the camera origin in object space: one view per launch
+    rq.nviews = 1u;
+    rq.view_rows = 0u;
+    for (uint32_t v = 0; v < nviews && st == RTC_OK; ++v) {
+        rq.cams = cams + v;
+        rq.d_rgb = d_rgb ? static_cast<double *>(d_rgb) + (size_t)v * view_rows * cams[0].hsize * 3u : nullptr;
+        rq.d_rgb8 = d_rgb8 ? static_cast<unsigned char *>(d_rgb8) + (size_t)v * view_rows * cams[0].hsize * (gamma > 0.f ? 4u : 3u) : nullptr;
+        st = render_launch(ctx, w, rq);
     }
-    return render_launch(ctx, w, cams, mode, first_band * RTC_BAND_ROWS, cams[0].vsize, band_stride, mine, d_rgb, d_rgb8, flags,
-                         nviews, view_rows, gamma);
+    return st;
 }
 
 rtc_status rtc_render_views(rtc_context *ctx, const rtc_world *w, const rtc_camera *cams, uint32_t nviews, uint32_t mode,
@@ -1532,17 +1502,19 @@ rtc_status rtc_render_views_rgba8(rtc_context *ctx, const rtc_world *w, const rt
 // and Color::scale's RGB otherwise (only those rows leave the kernel: no f64 canvas is written).
 static rtc_status render_frame(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, bool f64,
                                float gamma, void *host, rtc_stats *stats, const rtc_lens *lens = nullptr) {
-    if (!ctx || !w || !cam || !host || w->ctx != ctx) return RTC_ERR_ARG;
-    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0 || cam->samples > 255u) return RTC_ERR_ARG;
+    if (check_render_args(ctx, w, cam, mode, host, nullptr) != RTC_OK || cam->samples > 255u) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)cam->hsize * cam->vsize, bytes = px * (f64 ? 3 * sizeof(double) : gamma > 0.f ? 4u : 3u);
     rtc_status st = f64 ? ctx->d_canvas.reserve(3 * px, &ctx->render_allocs) : ctx->d_canvas8.reserve(bytes, &ctx->render_allocs);
     if (st != RTC_OK) return st;
     void *d = f64 ? (void *)ctx->d_canvas.get() : (void *)ctx->d_canvas8.get();
     if (stats) st = rtc_stats_reset(ctx);
-    if (st == RTC_OK)
-        st = render_launch(ctx, w, cam, mode, 0, cam->vsize, 1u, (cam->vsize + 7u) / 8u, f64 ? d : nullptr, f64 ? nullptr : d, flags, 1u, 0u,
-                           gamma, lens);
+    if (st == RTC_OK) {
+        LaunchRequest rq = rows_request(cam, mode, 0, cam->vsize, f64 ? d : nullptr, f64 ? nullptr : d, flags);
+        rq.gamma = gamma;
+        rq.lens = lens;
+        st = render_launch(ctx, w, rq);
+    }
     if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE; // pipelined context: the copy below is on the stream
     // `host` from rtc_host_alloc (page-locked) is filled by one DMA at link speed; pageable memory
     // goes through the runtime's bounce buffers (several times slower)
@@ -1604,30 +1576,24 @@ static bool aov_any(const rtc_aov_buffers *b) { return b->index || b->depth || b
 
 rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
                                  const rtc_aov_buffers *d) {
-    if (!ctx || !w || !cam || !d || w->ctx != ctx || !aov_any(d)) return RTC_ERR_ARG;
-    if (mode > RTC_MODE_RENDER_ASYNC || cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
+    if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || !aov_any(d)) return RTC_ERR_ARG;
     if (((size_t)d->depth | (size_t)d->point | (size_t)d->normal) % sizeof(double) != 0 || (size_t)d->index % 4u != 0 || (size_t)d->shadow % 2u != 0)
         return RTC_ERR_ARG;
     if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
-    if (flags & RTC_FLAG_LDS_TABLE) return RTC_ERR_UNSUPPORTED; // there are no AOV kernels for the LDS sources
     HIP_TRY(hipSetDevice(ctx->device));
     rtc_world::Gen *gen = nullptr;
     const rtc_status hs = current_gen(w, &gen);
     if (hs != RTC_OK) return hs;
     rtc_world::Gen &G = *gen;
-    int src;
-    uint32_t tile_cap;
-    size_t lds_bytes;
-    choose_source(ctx, G.n, flags, &src, &tile_cap, &lds_bytes, true); // as the lens launches: no-cull maps to SRC_SMEM
-    if (src != SRC_SMEM && src != SRC_CULL && src != SRC_CULL2) return RTC_ERR_UNSUPPORTED; // RTC_SRC=1|2
+    LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_AOV, flags);
+    in.hsize = cam->hsize; in.vsize = cam->vsize; in.mode = mode;
+    LaunchPlan plan;
+    rtc_plan_launch(in, plan);
+    if (plan.status != RTC_OK) return (rtc_status)plan.status;
     LaunchLights LL;
-    if (d->shadow) {
-        const rtc_status ls = lights_of(G, src, LL);
-        if (ls != RTC_OK) return ls;
-    }
+    if (d->shadow) lights_of(G, LL);
     RenderParams P;
-    std::memset(&P, 0, sizeof P);
-    fill_world(P, G);
+    planned_params(ctx, w, G, plan, P);
     fill_camera(P, cam);
     AovParams A;
     std::memset(&A, 0, sizeof A);
@@ -1635,14 +1601,14 @@ rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc
     A.W = cam->hsize;
     A.H = cam->vsize;
     A.mode = mode;
-    A.tiles_x = (cam->hsize + 7u) / 8u;
+    A.tiles_x = plan.grid_x;
     A.n = G.n;
     A.ngroups = G.ngroups;
     A.pre_limit = G.pre_limit;
     for (int k = 0; k < 3; ++k) A.light_pos[k] = G.light.position[k];
     A.index = d->index; A.depth = d->depth; A.point = d->point; A.normal = d->normal; A.flags = d->flags; A.shadow = d->shadow;
     HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
-    HIP_TRY(rtc_launch_aov(&A, &P, src, LL.xl, LL.lt, ctx->stream));
+    HIP_TRY(rtc_launch_aov(&A, &P, plan.src, LL.xl, LL.lt, ctx->stream));
     HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
     return RTC_OK;
 }
@@ -1747,34 +1713,24 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
     if (st == RTC_OK && hipMemcpyAsync(d_rays.get(), rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;
     if (st == RTC_OK) {
+        LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_PROBE, flags);
+        in.hsize = n;
+        LaunchPlan plan;
+        rtc_plan_launch(in, plan);
+        st = (rtc_status)plan.status;
         RenderParams P;
-        std::memset(&P, 0, sizeof P);
-        fill_world(P, G);
-        P.prim = w->d_prim.get();
-        if (!ctx->light_lists) P.light_cnt = nullptr;
+        planned_params(ctx, w, G, plan, P);
         P.W = n; P.H = 1; P.y0 = 0; P.y1 = 1; P.mode = RTC_MODE_RENDER_ASYNC; P.samples = 1;
+        P.grid_y = 1;
+        P.band_stride = 1;
         P.out = d_rgb.get();
-        P.counters = nullptr;
         P.rays = d_rays.get();
         P.nrays = n;
         P.remaining = remaining;
         P.hits = d_hits.get();
-        int src;
-        size_t lds_bytes;
-        choose_source(ctx, G.n, flags, &src, &P.tile_cap, &lds_bytes, G.n_lights > 1u);
         LaunchLights LL;
-        st = lights_of(G, src, LL);
-        const uint32_t blk = RTC_BLOCK_FOR(CULL_LEVEL(src), G.any_refl || G.any_refr, G.any_refr, true);
-        P.grid_x = (n + blk - 1u) / blk;
-        P.grid_y = 1;
-        P.band_stride = 1;
-        P.flags = flags;
-        P.total_blocks = P.grid_x;
-        P.reps = 1;
-        P.chunk_wgs[0] = P.chunk_wgs[1] = P.chunk_wgs[2] = P.chunk_wgs[3] = 0;
-        if (st == RTC_OK && rtc_launch_trace(&P, src, G.any_refl || G.any_refr, G.any_refr, P.grid_x, lds_bytes, ctx->stream, nullptr,
-                                             nullptr, LL.xl, LL.lt, nullptr) != hipSuccess)
-            st = RTC_ERR_DEVICE;
+        lights_of(G, LL);
+        if (st == RTC_OK && trace_planned(P, plan, LL, ctx->stream, nullptr, nullptr, nullptr) != hipSuccess) st = RTC_ERR_DEVICE;
     }
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;

@@ -16,7 +16,7 @@
 struct rtc_context {
     int device = -1;
     unsigned long long render_allocs = 0; // hipMalloc calls made by render entry points (rtc_debug_render_allocs)
-    unsigned long long pixels = 0; // rtc_stats::pixels of the launches since the last reset (counted by render_launch)
+    unsigned long long pixels = 0; // rtc_stats::pixels of the launches since the last reset (counted by the launch plan, rtc_launch_plan.h)
     hipStream_t stream = nullptr;
     DevBuf<unsigned long long> d_counters;
     // ring of (begin, end) event pairs, one per timed k_trace launch. Created on demand, EV_CHUNK pairs
