@@ -52,7 +52,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     cc = hipcc()
     objdir = ROOT / "build" / "rtc"
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h", CSRC / "rtc_aov.h", CSRC / "rtc_launch_plan.h"]
+    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_parity.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h", CSRC / "rtc_aov.h", CSRC / "rtc_launch_plan.h"]
     objs = []
     for name in SOURCES:
         src = CSRC / name

@@ -19,6 +19,7 @@
 #include "rtc_device.h"
 #include "rtc_internal.h"
 #include "rtc_launch_plan.h"
+#include "rtc_parity.h"
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
@@ -186,6 +187,15 @@ void fill_camera(RenderParams &P, const rtc_camera *cam, uint32_t view = 0) {
     c.half_height = cam->half_height;
     c.pixel_size = cam->pixel_size;
     std::memcpy(c.vinv, cam->view_inv, sizeof(double) * 12);
+    // transform_point(vinv, (0,0,0)) in xpoint's operation order (rtc_kernels.hip; this file is compiled without
+    // contraction, as the kernels are). Not a copy of the translation column: (+0) + (-0) has to come out as it does there.
+    const double *m = c.vinv;
+    const double zero = 0.;
+    bool finite = true;
+    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(m[i]);
+    for (int r = 0; r < 3; ++r) c.origin[r] = m[4 * r] * zero + m[4 * r + 1] * zero + m[4 * r + 2] * zero + m[4 * r + 3];
+    c.origin_ok = finite ? 1u : 0u;
+    c._pad = 0u;
 }
 
 void fill_world(RenderParams &P, const rtc_world::Gen &G) {
@@ -1741,7 +1751,7 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
 }
 
 rtc_status rtc_device_arith(rtc_context *ctx, uint32_t op, const double *a, const double *b, uint32_t n, double *out) {
-    if (!ctx || !a || !out || op > 6 || (op == 1 && !b) || (op == 2 && !b)) return RTC_ERR_ARG;
+    if (!ctx || !a || !out || op > 7 || (op == 1 && !b) || (op == 2 && !b)) return RTC_ERR_ARG;
     if (n == 0) return RTC_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     DevBuf<double> da, db, dout;
@@ -1751,6 +1761,14 @@ rtc_status rtc_device_arith(rtc_context *ctx, uint32_t op, const double *a, cons
     if (st == RTC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = RTC_ERR_DEVICE;
     if (st == RTC_OK && hipMemcpy(out, dout.get(), sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) st = RTC_ERR_DEVICE;
     return st;
+}
+
+// Diagnostic (not part of include/rtc.h): rtc_parity.h's even test — the code the patterns run on the device — evaluated on
+// the host for n values: out[i] = 1 where it holds. The CPU tests pin it against fmod(x, 2.0) == 0.0.
+rtc_status rtc_debug_even_f64(const double *x, size_t n, uint8_t *out) {
+    if (!x || !out) return RTC_ERR_ARG;
+    for (size_t i = 0; i < n; ++i) out[i] = rtc_even_f64(x[i]) ? 1u : 0u;
+    return RTC_OK;
 }
 
 } // extern "C"

@@ -108,6 +108,12 @@ enum { CNT_SLOTS = 256 };
 struct DevCamera {
     double half_width, half_height, pixel_size;
     double vinv[12];
+    // transform_point(vinv, (0,0,0)), the origin of every primary ray (camera.rs:72), evaluated by the host in the device's
+    // operation order (fill_camera, rtc_api.cpp). origin_ok: every element of vinv is finite, so host and device agree on
+    // every bit of it and k_trace takes it from here; otherwise the kernel evaluates it itself (a NaN's sign and payload are
+    // not the same on every machine). k_bin_tiles and k_aov evaluate their own either way.
+    double origin[3];
+    uint32_t origin_ok, _pad;
 };
 enum { RTC_MAX_VIEWS = 8 };
 

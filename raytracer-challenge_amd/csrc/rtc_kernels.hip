@@ -34,6 +34,7 @@
 #include "rtc_bands.h"
 #include "rtc_device.h"
 #include "rtc_gamma.h"
+#include "rtc_parity.h"
 #include "rtc_world_build.h"
 
 // Depth of the reflection / refraction frame stack. A frame is pushed only by a color_at call whose
@@ -924,13 +925,13 @@ DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
     const V3 b = mk(S->pat_b[0], S->pat_b[1], S->pat_b[2]);
     switch (S->pattern_kind) {
     case RTC_PATTERN_TEST: return pp;
-    case RTC_PATTERN_STRIPE: return (fmod(floor(pp.x), 2.0) == 0.) ? a : b;
+    case RTC_PATTERN_STRIPE: return rtc_even_f64(floor(pp.x)) ? a : b; // (`% 2.0 == 0.0`: rtc_parity.h)
     case RTC_PATTERN_GRADIENT: {
         const V3 diff = vsub(b, a); // GradientPattern::new: _diff = b.sub(a)
         return vadd(a, vmul(diff, pp.x - floor(pp.x)));
     }
-    case RTC_PATTERN_RING: return (fmod(floor(sqrt(pp.x * pp.x + pp.y * pp.y)), 2.0) == 0.0) ? a : b;
-    case RTC_PATTERN_CHECKER: return (fmod(floor(pp.x) + floor(pp.y) + floor(pp.z), 2.0) == 0.0) ? a : b;
+    case RTC_PATTERN_RING: return rtc_even_f64(floor(sqrt(pp.x * pp.x + pp.y * pp.y))) ? a : b;
+    case RTC_PATTERN_CHECKER: return rtc_even_f64(floor(pp.x) + floor(pp.y) + floor(pp.z)) ? a : b;
     case RTC_PATTERN_GRID:
         return (fabs(pp.x - floor(pp.x)) < 0.01 || fabs(pp.z - floor(pp.z)) < 0.01) ? b : a;
     default: return mk(0., 0., 0.);
@@ -1188,6 +1189,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     if (!PROBE && bid >= P.total_blocks) break; // (workgroup-uniform)
     uint32_t px = 0, py = 0, ray_index = 0;
     uint32_t view = 0, tbid = bid; // which camera of the launch, and the tile's index inside that view
+    // The tile's column and row in the view's grid: decomposed ONCE per tile (one unsigned division; two with several views),
+    // wave-uniform, and used by the ray set-up, the black-row test, the tile-list lookup and the output stage alike.
+    uint32_t bx = 0, by = 0;
     bool in_range, traced;
     if (probe) {
         ray_index = bid * BLOCK + threadIdx.x;
@@ -1196,7 +1200,8 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     } else {
         const uint32_t tiles = P.grid_x * P.grid_y;
         if (P.nviews > 1u) { view = bid / tiles; tbid = bid % tiles; }
-        const uint32_t bx = tbid % P.grid_x, by = tbid / P.grid_x;
+        by = tbid / P.grid_x;
+        bx = tbid - by * P.grid_x;
         px = bx * TILE_W + wave * 8u + (lane & 7u);
         py = P.y0 + by * P.band_stride * 8u + (lane >> 3);
         in_range = px < P.W && py < P.y1;
@@ -1206,14 +1211,20 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
 
     // Tile rows the binning kernel PROVED black for this view (k_bin_tiles, `rows`): no ray is generated, no pass is run, the
     // tile is stored as Canvas::new left it; the primary rays the reference would have cast are still counted (and reported
-    // separately, rtc_stats::rays_primary_proven_miss). One-sample renders only.
+    // separately, rtc_stats::rays_primary_proven_miss). One-sample renders only. Such a tile goes from here to the output
+    // stage: it skips the sample loop with its camera loads, and stores its zeros through the same code as every other tile.
     bool sky_tile = false;
     if constexpr (IS_CULL(SRC) && !PROBE && !LENS) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
         if (Pt.tile_rows != nullptr && Pt.samples == 1u) {
-            const uint32_t ity = (Pt.y0 >> 3) + (tbid / Pt.grid_x) * Pt.band_stride;
+            const uint32_t ity = (Pt.y0 >> 3) + by * Pt.band_stride;
             const uint32_t first = Pt.tile_rows[2u * view], lastinv = Pt.tile_rows[2u * view + 1u];
             sky_tile = ity < first || ity > ~lastinv; // (no tile of the view is non-empty: first = 0xffffffff)
+        }
+        if (sky_tile) { // counted as cast (the reference casts them), answered by the proof
+            const uint32_t cast = popc64(ballot(traced));
+            c_primary += cast;
+            c_sky += cast;
         }
     }
 
@@ -1226,7 +1237,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         const auto &Pt = KP(P_arg);
         if (Pt.tile_cnt != nullptr) {
             const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave); // wave-uniform by construction
-            const uint32_t itx = (tbid % Pt.grid_x) * (TILE_W / 8u) + wv, ity = (Pt.y0 >> 3) + (tbid / Pt.grid_x) * Pt.band_stride;
+            const uint32_t itx = bx * (TILE_W / 8u) + wv, ity = (Pt.y0 >> 3) + by * Pt.band_stride;
             if (itx < Pt.tiles_x && ity < Pt.tiles_y) {
                 const size_t tile = (size_t)(view * Pt.tiles_y + ity) * Pt.tiles_x + itx;
                 bin_cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)Pt.tile_cnt[tile]);
@@ -1258,13 +1269,20 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     // its lane)
     double *lstk = stack_lds + threadIdx.x;
 
-    for (uint32_t s = 0; s < nsamples; ++s) {
+    for (uint32_t s = sky_tile ? nsamples : 0u; s < nsamples; ++s) { // (a tile proven black: no sample at all)
         V3 ro, rd;
         bool shared_origin;
         const auto &Pr = KP(P_arg).views[view]; // ray-generation view: this workgroup's camera block
-        // ray origin of every primary ray: transform_point(view_inv, (0,0,0)) camera.rs:72
-        V3 cam_origin = xpoint(Pr.vinv, mk(0., 0., 0.));
-        cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
+        // ray origin of every primary ray: transform_point(view_inv, (0,0,0)) camera.rs:72 — as the host evaluated it when
+        // every element of view_inv is finite (DevCamera::origin: the same operations on the same operands, the same bits),
+        // evaluated here otherwise (NaN signs and payloads are the device's own)
+        V3 cam_origin;
+        if (!LENS && Pr.origin_ok != 0u) { // (the lens flavour replaces the origin below)
+            cam_origin = mk(Pr.origin[0], Pr.origin[1], Pr.origin[2]);
+        } else {
+            cam_origin = xpoint(Pr.vinv, mk(0., 0., 0.));
+            cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
+        }
         V3 lens_origin_v = cam_origin; // (lens flavour: the sample's origin as computed, in VGPRs)
         if constexpr (LENS) {
             // the lens sample's origin (include/rtc.h): a point of the lens in camera space, the same for every pixel of the
@@ -1284,9 +1302,6 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             ro = mk(rp[0], rp[1], rp[2]);
             rd = mk(rp[3], rp[4], rp[5]);
             shared_origin = false;
-        } else if (sky_tile) { // proven black: no ray is needed
-            ro = cam_origin; rd = mk(0., 0., 1.);
-            shared_origin = true;
         } else {
             // Camera::ray_for_pixel_offset camera.rs:64-76; sub-sample offsets camera.rs:98,102-105
             double xo = 0.5, yo = 0.5;
@@ -1318,11 +1333,10 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         int rem = (int)P.remaining;
         int sp = 0;
         c_primary += popc64(ballot(tracing));
-        if (sky_tile) { c_sky += popc64(ballot(tracing)); tracing = false; } // counted as cast (the reference casts them), answered by the proof
 
         // Worlds without reflective / transparent materials (REFL == false) need exactly one pass per
         // primary ray; otherwise loop until every lane's frame stack has unwound.
-        for (bool pass_again = !sky_tile; pass_again;) {
+        for (bool pass_again = true; pass_again;) {
             if constexpr (REFL) {
                 bool any_tracing;
                 if constexpr (SRC == SRC_LDSN) any_tracing = __syncthreads_or(tracing ? 1 : 0) != 0;
@@ -1837,15 +1851,8 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 o[2] = result.z;
             }
         } else {
-            // The workgroup's (TILE_W x 8)-pixel tile is staged in LDS (row-major, exactly the canvas layout of
-            // the tile) and written out by the whole workgroup: with TILE_W = 16 each tile row is 384 contiguous
-            // bytes of the f64 canvas (three full 128-byte lines) and 48 contiguous bytes of the 8-bit frame,
-            // stored 16 bytes per lane. Direct per-pixel stores (3 x 8 B at a 24 B stride, 3 single
-            // bytes) cost 1.6x the algorithmic bytes in HBM write traffic (rocprofv3 WRITE_SIZE).
             // Between AA samples Color::average_over's running sums (color.rs:128-139: reds = ((0 + c0) + c1) + ...)
             // wait in the thread's part of the dynamic LDS block (the tile may be staged over the frame stack).
-            const uint32_t tx = wave * 8u + (lane & 7u), ty = lane >> 3; // position inside the tile
-            double *slot = stage_f64 + (ty * TILE_W + tx) * 3u;
             if (!traced) result = mk(0., 0., 0.); // Canvas::new BLACK canvas.rs:37-41
             if constexpr (LENS) { // Color::average_over color.rs:128-139: sums from 0.0 in sample order, one division each
                 lens_sum = vadd(lens_sum, result);
@@ -1887,126 +1894,139 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 result = acc;
                 aa_store[12] = acc.x; aa_store[13] = acc.y; aa_store[14] = acc.z;
             }
-            if (s + 1u == nsamples) {
-                slot[0] = result.x;
-                slot[1] = result.y;
-                slot[2] = result.z;
-                const auto &Po = KP(P_arg); // output view
-                const bool want8 = Po.out8 != nullptr;
-                if (want8) {
-                    unsigned char *q = stage_u8 + (ty * TILE_W + tx) * 3u;
-                    if constexpr (RGBA) { // Canvas::to_imgbuf's channels (rtc_gamma.h)
-                        const DevGamma *gt = Po.gamma;
-                        q[0] = gamma_byte(gt, result.x);
-                        q[1] = gamma_byte(gt, result.y);
-                        q[2] = gamma_byte(gt, result.z);
-                    } else {
-                        q[0] = scale255(result.x);
-                        q[1] = scale255(result.y);
-                        q[2] = scale255(result.z);
-                    }
+        }
+    } // samples
+
+    // ---- the output stage: once per tile, after its last sample; a tile proven black arrives with `result` still BLACK ----
+    if constexpr (!PROBE) {
+        // The workgroup's (TILE_W x 8)-pixel tile is staged in LDS (row-major, exactly the canvas layout of
+        // the tile) and written out by the whole workgroup: with TILE_W = 16 each tile row is 384 contiguous
+        // bytes of the f64 canvas (three full 128-byte lines) and 48 contiguous bytes of the 8-bit frame,
+        // stored 16 bytes per lane. Direct per-pixel stores (3 x 8 B at a 24 B stride, 3 single
+        // bytes) cost 1.6x the algorithmic bytes in HBM write traffic (rocprofv3 WRITE_SIZE).
+        // (the lane number through an opaque copy: the slot arithmetic is done here, per tile, and not hoisted in front of the
+        // tile loop, from where it would be carried — spilled — through the whole trace)
+        uint32_t olane = lane;
+        asm volatile("" : "+v"(olane));
+        const uint32_t tx = wave * 8u + (olane & 7u), ty = olane >> 3; // position inside the tile
+        double *slot = stage_f64 + (ty * TILE_W + tx) * 3u;
+        slot[0] = result.x;
+        slot[1] = result.y;
+        slot[2] = result.z;
+        const auto &Po = KP(P_arg); // output view
+        const bool want8 = Po.out8 != nullptr;
+        if (want8) {
+            unsigned char *q = stage_u8 + (ty * TILE_W + tx) * 3u;
+            if constexpr (RGBA) { // Canvas::to_imgbuf's channels (rtc_gamma.h)
+                const DevGamma *gt = Po.gamma;
+                q[0] = gamma_byte(gt, result.x);
+                q[1] = gamma_byte(gt, result.y);
+                q[2] = gamma_byte(gt, result.z);
+            } else {
+                q[0] = scale255(result.x);
+                q[1] = scale255(result.y);
+                q[2] = scale255(result.z);
+            }
+        }
+        // Canvas stores are non-temporal (written once, never read by the kernel): north star -2.3 %, C3 -4.2 %,
+        // C5 -1.5 % (profiles/r02_exp_nt_stores.log).
+        if constexpr (WAVE_OUTPUT) {
+        // Each wave stores its own 8x8 part of the tile (no workgroup barrier: a wave that is
+        // done retires without waiting for the slowest of its three neighbours). Its LDS
+        // region is written and read by this wave only; LDS operations of one wave execute
+        // in order, the fences only stop the compiler from reordering them.
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t px0 = bx * TILE_W + wave * 8u, py0 = Po.y0 + by * Po.band_stride * 8u,
+                       orow0 = view * Po.view_rows + by * 8u; // first image row / first output row of the tile
+        const uint32_t cols = (px0 >= Po.W) ? 0u : ((Po.W - px0 < 8u) ? (Po.W - px0) : 8u); // valid pixels per row
+        const uint32_t rows = (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;                       // valid tile rows
+        const size_t row_bytes = (size_t)Po.W * 24u;
+        const double *src = stage_f64 + wave * 24u;
+        // a row of the wave's part is 192 contiguous bytes of the canvas: 12 pieces of 16 bytes
+        const bool wide = cols == 8u && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0;
+        if (Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8): nothing of the f64 canvas leaves the chip
+        } else if (wide) {
+            typedef double __attribute__((ext_vector_type(2))) d2;
+            for (uint32_t c = lane; c < rows * 12u; c += 64u) {
+                const uint32_t r = c / 12u, k = c % 12u;
+                const d2 v = *reinterpret_cast<const d2 *>(src + r * (TILE_W * 3u) + k * 2u);
+                char *dst = reinterpret_cast<char *>(Po.out) + (size_t)(orow0 + r) * row_bytes + (size_t)px0 * 24u + k * 16u;
+                __builtin_nontemporal_store(v, reinterpret_cast<d2 *>(dst));
+            }
+        } else {
+            for (uint32_t c = lane; c < rows * cols * 3u; c += 64u) {
+                const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
+                Po.out[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = src[r * (TILE_W * 3u) + k];
+            }
+        }
+        if constexpr (RGBA) {
+            if (want8) store_rgba<8u, TILE_W * 3u, 64u>(stage_u8 + wave * 24u, Po.out8, Po.W, orow0, px0, rows, cols, lane);
+        } else if (want8) {
+            const size_t row8 = (size_t)Po.W * 3u;
+            const unsigned char *src8 = stage_u8 + wave * 24u;
+            // 24 contiguous bytes per row: 3 pieces of 8 bytes
+            const bool wide8 = cols == 8u && (row8 % 8u) == 0 && ((size_t)Po.out8 % 8u) == 0;
+            if (wide8) {
+                typedef unsigned __attribute__((ext_vector_type(2))) u2;
+                for (uint32_t c = lane; c < rows * 3u; c += 64u) {
+                    const uint32_t r = c / 3u, k = c % 3u;
+                    const u2 v = *reinterpret_cast<const u2 *>(src8 + r * (TILE_W * 3u) + k * 8u);
+                    __builtin_nontemporal_store(v, reinterpret_cast<u2 *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * 8u));
                 }
-                // Canvas stores are non-temporal (written once, never read by the kernel): north star -2.3 %, C3 -4.2 %,
-                // C5 -1.5 % (profiles/r02_exp_nt_stores.log).
-                if constexpr (WAVE_OUTPUT) {
-                // Each wave stores its own 8x8 part of the tile (no workgroup barrier: a wave that is
-                // done retires without waiting for the slowest of its three neighbours). Its LDS
-                // region is written and read by this wave only; LDS operations of one wave execute
-                // in order, the fences only stop the compiler from reordering them.
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const uint32_t px0 = (tbid % Po.grid_x) * TILE_W + wave * 8u, py0 = Po.y0 + (tbid / Po.grid_x) * Po.band_stride * 8u,
-                               orow0 = view * Po.view_rows + (tbid / Po.grid_x) * 8u; // first image row / first output row of the tile
-                const uint32_t cols = (px0 >= Po.W) ? 0u : ((Po.W - px0 < 8u) ? (Po.W - px0) : 8u); // valid pixels per row
-                const uint32_t rows = (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;                       // valid tile rows
-                const size_t row_bytes = (size_t)Po.W * 24u;
-                const double *src = stage_f64 + wave * 24u;
-                // a row of the wave's part is 192 contiguous bytes of the canvas: 12 pieces of 16 bytes
-                const bool wide = cols == 8u && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0;
-                if (Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8): nothing of the f64 canvas leaves the chip
-                } else if (wide) {
-                    typedef double __attribute__((ext_vector_type(2))) d2;
-                    for (uint32_t c = lane; c < rows * 12u; c += 64u) {
-                        const uint32_t r = c / 12u, k = c % 12u;
-                        const d2 v = *reinterpret_cast<const d2 *>(src + r * (TILE_W * 3u) + k * 2u);
-                        char *dst = reinterpret_cast<char *>(Po.out) + (size_t)(orow0 + r) * row_bytes + (size_t)px0 * 24u + k * 16u;
-                        __builtin_nontemporal_store(v, reinterpret_cast<d2 *>(dst));
-                    }
-                } else {
-                    for (uint32_t c = lane; c < rows * cols * 3u; c += 64u) {
-                        const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
-                        Po.out[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = src[r * (TILE_W * 3u) + k];
-                    }
-                }
-                if constexpr (RGBA) {
-                    if (want8) store_rgba<8u, TILE_W * 3u, 64u>(stage_u8 + wave * 24u, Po.out8, Po.W, orow0, px0, rows, cols, lane);
-                } else if (want8) {
-                    const size_t row8 = (size_t)Po.W * 3u;
-                    const unsigned char *src8 = stage_u8 + wave * 24u;
-                    // 24 contiguous bytes per row: 3 pieces of 8 bytes
-                    const bool wide8 = cols == 8u && (row8 % 8u) == 0 && ((size_t)Po.out8 % 8u) == 0;
-                    if (wide8) {
-                        typedef unsigned __attribute__((ext_vector_type(2))) u2;
-                        for (uint32_t c = lane; c < rows * 3u; c += 64u) {
-                            const uint32_t r = c / 3u, k = c % 3u;
-                            const u2 v = *reinterpret_cast<const u2 *>(src8 + r * (TILE_W * 3u) + k * 8u);
-                            __builtin_nontemporal_store(v, reinterpret_cast<u2 *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * 8u));
-                        }
-                    } else {
-                        for (uint32_t c = lane; c < rows * cols * 3u; c += 64u) {
-                            const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
-                            Po.out8[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = src8[r * (TILE_W * 3u) + k];
-                        }
-                    }
-                }
-                } else {
-                __syncthreads();
-                const uint32_t px0 = (tbid % Po.grid_x) * TILE_W, py0 = Po.y0 + (tbid / Po.grid_x) * Po.band_stride * 8u,
-                               orow0 = view * Po.view_rows + (tbid / Po.grid_x) * 8u; // first image row / first output row of the tile
-                const uint32_t cols = (Po.W - px0 < TILE_W) ? (Po.W - px0) : TILE_W;      // valid pixels per tile row
-                const uint32_t rows = (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;      // valid tile rows
-                // f64 canvas: 16-byte pieces when every tile row is whole and 16-byte aligned
-                const size_t row_bytes = (size_t)Po.W * 24u;
-                const bool wide = cols == TILE_W && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0;
-                if (Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8)
-                } else if (wide) {
-                    typedef double __attribute__((ext_vector_type(2))) d2;
-                    for (uint32_t c = threadIdx.x; c < rows * (TILE_W * 3u / 2u); c += BLOCK) {
-                        const uint32_t r = c / (TILE_W * 3u / 2u), k = c % (TILE_W * 3u / 2u);
-                        const d2 v = *reinterpret_cast<const d2 *>(stage_f64 + r * (TILE_W * 3u) + k * 2u);
-                        char *dst = reinterpret_cast<char *>(Po.out) + (size_t)(orow0 + r) * row_bytes + (size_t)px0 * 24u + k * 16u;
-                        __builtin_nontemporal_store(v, reinterpret_cast<d2 *>(dst));
-                    }
-                } else {
-                    for (uint32_t c = threadIdx.x; c < rows * cols * 3u; c += BLOCK) {
-                        const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
-                        Po.out[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = stage_f64[r * (TILE_W * 3u) + k];
-                    }
-                }
-                if constexpr (RGBA) {
-                    if (want8) store_rgba<TILE_W, TILE_W * 3u, BLOCK>(stage_u8, Po.out8, Po.W, orow0, px0, rows, cols, threadIdx.x);
-                } else if (want8) {
-                    const size_t row8 = (size_t)Po.W * 3u;
-                    // a tile row is 24 bytes per wave: 16-byte pieces for an even number of waves, 8-byte pieces for one
-                    constexpr uint32_t PIECE = (TILE_W * 3u) % 16u == 0 ? 16u : 8u;
-                    const bool wide8 = cols == TILE_W && (row8 % PIECE) == 0 && ((size_t)Po.out8 % PIECE) == 0;
-                    if (wide8) {
-                        typedef unsigned __attribute__((ext_vector_type(PIECE / 4u))) piece_t;
-                        for (uint32_t c = threadIdx.x; c < rows * (TILE_W * 3u / PIECE); c += BLOCK) {
-                            const uint32_t r = c / (TILE_W * 3u / PIECE), k = c % (TILE_W * 3u / PIECE);
-                            const piece_t v = *reinterpret_cast<const piece_t *>(stage_u8 + r * (TILE_W * 3u) + k * PIECE);
-                            __builtin_nontemporal_store(v, reinterpret_cast<piece_t *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * PIECE));
-                        }
-                    } else {
-                        for (uint32_t c = threadIdx.x; c < rows * cols * 3u; c += BLOCK) {
-                            const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
-                            Po.out8[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = stage_u8[r * (TILE_W * 3u) + k];
-                        }
-                    }
-                }
+            } else {
+                for (uint32_t c = lane; c < rows * cols * 3u; c += 64u) {
+                    const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
+                    Po.out8[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = src8[r * (TILE_W * 3u) + k];
                 }
             }
+        }
+        } else {
+        __syncthreads();
+        const uint32_t px0 = bx * TILE_W, py0 = Po.y0 + by * Po.band_stride * 8u,
+                       orow0 = view * Po.view_rows + by * 8u; // first image row / first output row of the tile
+        const uint32_t cols = (Po.W - px0 < TILE_W) ? (Po.W - px0) : TILE_W;      // valid pixels per tile row
+        const uint32_t rows = (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;      // valid tile rows
+        // f64 canvas: 16-byte pieces when every tile row is whole and 16-byte aligned
+        const size_t row_bytes = (size_t)Po.W * 24u;
+        const bool wide = cols == TILE_W && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0;
+        if (Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8)
+        } else if (wide) {
+            typedef double __attribute__((ext_vector_type(2))) d2;
+            for (uint32_t c = threadIdx.x; c < rows * (TILE_W * 3u / 2u); c += BLOCK) {
+                const uint32_t r = c / (TILE_W * 3u / 2u), k = c % (TILE_W * 3u / 2u);
+                const d2 v = *reinterpret_cast<const d2 *>(stage_f64 + r * (TILE_W * 3u) + k * 2u);
+                char *dst = reinterpret_cast<char *>(Po.out) + (size_t)(orow0 + r) * row_bytes + (size_t)px0 * 24u + k * 16u;
+                __builtin_nontemporal_store(v, reinterpret_cast<d2 *>(dst));
+            }
+        } else {
+            for (uint32_t c = threadIdx.x; c < rows * cols * 3u; c += BLOCK) {
+                const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
+                Po.out[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = stage_f64[r * (TILE_W * 3u) + k];
+            }
+        }
+        if constexpr (RGBA) {
+            if (want8) store_rgba<TILE_W, TILE_W * 3u, BLOCK>(stage_u8, Po.out8, Po.W, orow0, px0, rows, cols, threadIdx.x);
+        } else if (want8) {
+            const size_t row8 = (size_t)Po.W * 3u;
+            // a tile row is 24 bytes per wave: 16-byte pieces for an even number of waves, 8-byte pieces for one
+            constexpr uint32_t PIECE = (TILE_W * 3u) % 16u == 0 ? 16u : 8u;
+            const bool wide8 = cols == TILE_W && (row8 % PIECE) == 0 && ((size_t)Po.out8 % PIECE) == 0;
+            if (wide8) {
+                typedef unsigned __attribute__((ext_vector_type(PIECE / 4u))) piece_t;
+                for (uint32_t c = threadIdx.x; c < rows * (TILE_W * 3u / PIECE); c += BLOCK) {
+                    const uint32_t r = c / (TILE_W * 3u / PIECE), k = c % (TILE_W * 3u / PIECE);
+                    const piece_t v = *reinterpret_cast<const piece_t *>(stage_u8 + r * (TILE_W * 3u) + k * PIECE);
+                    __builtin_nontemporal_store(v, reinterpret_cast<piece_t *>(Po.out8 + (size_t)(orow0 + r) * row8 + (size_t)px0 * 3u + k * PIECE));
+                }
+            } else {
+                for (uint32_t c = threadIdx.x; c < rows * cols * 3u; c += BLOCK) {
+                    const uint32_t r = c / (cols * 3u), k = c % (cols * 3u);
+                    Po.out8[((size_t)(orow0 + r) * Po.W + px0) * 3u + k] = stage_u8[r * (TILE_W * 3u) + k];
+                }
+            }
+        }
         }
     }
 
@@ -2069,6 +2089,7 @@ __global__ void k_arith(uint32_t op, const double *a, const double *b, uint32_t 
     case 1: r = a[i] / b[i]; break;
     case 2: r = pow(a[i], b[i]); break;
     case 3: r = floor(a[i]); break;
+    case 7: r = rtc_even_f64(a[i]) ? 1.0 : 0.0; break; // the patterns' even test (rtc_parity.h)
     default: r = fmod(a[i], 2.0); break;
     }
     out[i] = r;
