@@ -422,7 +422,7 @@ void flatten_shapes(const rtc_shape *shapes, uint32_t n, DevIsect *isect, uint32
         d.kind = s.kind;
         d.pattern_kind = m.pattern_kind;
         d.world_id = all_zero ? i + 1u : s.world_id;
-        if (m.reflective > 0.) any_refl = true;     // reflected_color shape.rs:730
+        if (!(m.reflective <= 0.)) any_refl = true; // reflected_color shape.rs:730: `<= 0.` returns BLACK, so a NaN casts the ray
         if (m.transparency != 0.0) any_refr = true; // refracted_color shape.rs:752
     }
     *refl = any_refl;

@@ -1734,7 +1734,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 else surface = lighting(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
                 bool want_refl = false, want_refr = false;
                 V3 fr_o = mk(0, 0, 0), fr_d = mk(0, 0, 0);
-                if constexpr (REFL) want_refl = (rem != 0) && (m_kr > 0.); // reflected_color shape.rs:730
+                if constexpr (REFL) want_refl = (rem != 0) && !(m_kr <= 0.); // reflected_color shape.rs:730 (NaN: cast)
                 if constexpr (REFR) {
                     if (rem != 0 && m_tr != 0.0) { // refracted_color shape.rs:751-766
                         const double n_ratio = n1 / n2;

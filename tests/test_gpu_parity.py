@@ -92,6 +92,106 @@ def test_device_pow_is_within_a_few_ulp(gpu):
     assert ok.all()
 
 
+def _mp_pow(base, expo):
+    """pow(base, expo) correctly rounded to f64, element by element: mpmath at 120 bits, then ONE rounding to the f64 grid
+    (to fewer than 53 bits where the result is subnormal; beyond the largest double: inf)."""
+    from mpmath import libmp
+    out = np.empty(len(base), dtype=np.float64)
+    ff, pw, pos, tf = libmp.from_float, libmp.mpf_pow, libmp.mpf_pos, libmp.to_float
+    for i, (a, b) in enumerate(zip(base.tolist(), expo.tolist())):
+        r = pw(ff(a), ff(b), 120, "n")
+        _, man, exp, bc = r
+        if not man:                      # 0, inf
+            out[i] = tf(r)
+            continue
+        top = exp + bc - 1               # 2^top <= r < 2^(top + 1)
+        if top < -1075 or (top == -1075 and man == 1):
+            out[i] = 0.0                 # below half of 5e-324, or exactly half (ties to even)
+        elif top == -1075:
+            out[i] = 5e-324
+        else:
+            try:
+                out[i] = tf(pos(r, min(53, top + 1075), "n"))
+            except OverflowError:
+                out[i] = math.inf
+    return out
+
+
+def _ulp_error(got, want):
+    """|got - want| in units of the spacing at `want` (floored at 5e-324; at inf: the spacing below the largest double)."""
+    big = np.finfo(np.float64).max
+    w = np.clip(want, -big, big)
+    g = np.clip(got, -big, big)
+    err = np.abs(g - w) / np.spacing(np.clip(np.abs(w), 5e-324, 2.0 ** 1023))
+    err = np.where(np.isinf(want) != np.isinf(got), err + 1.0, err)
+    return np.where(got == want, 0.0, err)
+
+
+def test_device_pow_over_the_domain_lighting_hands_it(gpu):
+    """factor = reflect_dot_eye.powf(shininess) (material.rs:355) over what lighting() can pass: bases in (0, 1] and the
+    few ulp above 1 that a rounded dot product of unit vectors reaches, against the correctly rounded power (mpmath, 120
+    bits -- not glibc). Exponents in [2^-10, 2^12]: the project's stated 4 ulp, subnormal results included. The C99 Annex F
+    values, which make a frame with shininess 0, +-inf or NaN bit-identical to the oracle's: exact. Every other exponent
+    (beyond 2^12 up to 1e300, below 2^-10 down to 5e-324, negative): twice the largest error measured on the MI355X
+    (1.0 ulp, as on the asserted range), because a random sample does not find the worst case."""
+    from shade_domain_cases import POW_ULP, POW_ULP_WIDE
+    rng = np.random.default_rng(20)
+    below = 1.0 - np.arange(65) * 2.0 ** -53
+    above = 1.0 + np.arange(65) * 2.0 ** -52
+    halves = np.ldexp(1.0, -np.arange(1075))                      # 2^-k down to 5e-324
+    special = np.concatenate([below, above, halves])
+    uni = lambda n: 1.0 - rng.random(n)                           # (0, 1]
+    logu = lambda n, lo=-10., hi=12.: np.exp2(rng.uniform(lo, hi, n))
+    ints = np.arange(1, 401, dtype=np.float64)
+    base = np.concatenate([uni(148000), np.repeat(special, 20), uni(20000), np.repeat(special, 2), uni(5000), special])
+    expo = np.concatenate([logu(148000), logu(special.size * 20), np.repeat(ints, 50), rng.choice(ints, special.size * 2),
+                           np.full(5000, 0.5), np.full(special.size, 0.5)])
+    assert base.size == expo.size and 1.9e5 < base.size < 2.1e5 and base.min() == 5e-324 and (base > 0).all()
+    got = gpu.device_arith(2, base, expo)
+    want = _mp_pow(base, expo)
+    err = _ulp_error(got, want)
+    sub = (want < 2.0 ** -1022) & (want > 0)
+    print(f"pow on [2^-10, 2^12]: {base.size} pairs, {int(sub.sum())} subnormal results, largest error {err.max():.3f} ulp "
+          f"(base {base[err.argmax()]!r}, exponent {expo[err.argmax()]!r})")
+    assert sub.sum() > 100 and not np.isnan(got).any()
+    assert err.max() <= POW_ULP
+
+    # C99 Annex F.10.4.4
+    some = np.concatenate([uni(200), above[1:], halves[::50], [0.5, 1e-300, 5e-324]])
+    lt1, gt1 = some[some < 1.0], some[some > 1.0]
+    anyy = np.concatenate([logu(100, -1074., 1000.), -logu(100, -1074., 1000.), [0.0, -0.0, math.inf, -math.inf, math.nan, 5e-324]])
+    bits = lambda a: np.asarray(a, dtype=np.float64).view(np.uint64)
+    for z in (0.0, -0.0):
+        assert np.array_equal(bits(gpu.device_arith(2, some, np.full(some.size, z))), bits(np.ones(some.size))), "pow(x, +-0) = 1"
+    assert np.array_equal(bits(gpu.device_arith(2, np.ones(anyy.size), anyy)), bits(np.ones(anyy.size))), "pow(1, y) = 1, y NaN included"
+    assert np.array_equal(bits(gpu.device_arith(2, lt1, np.full(lt1.size, math.inf))), bits(np.zeros(lt1.size))), "pow(x < 1, +inf) = +0"
+    assert np.array_equal(gpu.device_arith(2, gt1, np.full(gt1.size, math.inf)), np.full(gt1.size, math.inf)), "pow(x > 1, +inf) = +inf"
+    assert np.array_equal(gpu.device_arith(2, lt1, np.full(lt1.size, -math.inf)), np.full(lt1.size, math.inf)), "pow(x < 1, -inf) = +inf"
+    ne1 = some[some != 1.0]
+    assert np.isnan(gpu.device_arith(2, ne1, np.full(ne1.size, math.nan))).all(), "pow(x != 1, NaN) = NaN"
+
+    # every other finite exponent. The bases are chosen so that the results spread over the whole f64 range instead of
+    # collapsing to 0, 1 or inf: x = exp(-u / |y|), u uniform in [0, 740]; and the special bases as they are.
+    # (|y| within [2^-60, 2^62] for most: beyond, every base but 1 gives 0, 1 or inf)
+    n = 6000
+    y = np.concatenate([logu(n, 12., 62.), -logu(n, -10., 62.), logu(n // 2, -60., -10.), -logu(n // 2, -60., -10.),
+                        logu(500, 62., 996.5), -logu(500, 62., 996.5), logu(500, -1074., -60.), -logu(500, -1074., -60.),
+                        [1e300, -1e300, 1e6, 5e-324, -5e-324, -3.0]])
+    with np.errstate(over="ignore"):
+        x = np.exp(-rng.uniform(0., 740., y.size) / np.abs(y))
+    x = np.where(x > 0., x, 5e-324)
+    x[::7] = rng.choice(special, x[::7].size)
+    x[::11] = uni(x[::11].size)
+    got = gpu.device_arith(2, x, y)
+    want = _mp_pow(x, y)
+    err = _ulp_error(got, want)
+    mid = np.isfinite(want) & (want != 0.) & (want != 1.)
+    print(f"pow beyond [2^-10, 2^12]: {x.size} pairs, {int(mid.sum())} results other than 0, 1 and inf, largest error {err.max():.3f} ulp "
+          f"(base {x[err.argmax()]!r}, exponent {y[err.argmax()]!r})")
+    assert mid.sum() > x.size // 2 and not np.isnan(got).any()
+    assert err.max() <= POW_ULP_WIDE
+
+
 # ------------------------------------------------------------------ reference KATs on the GPU
 def test_reference_kats_through_color_at(rtc, gpu, O):
     """shape.rs:1073-1112 (test_color_at1-3), :1041 (world4), :1132 (shadow1), :1231-1266
