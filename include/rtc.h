@@ -1023,7 +1023,9 @@ void        rtc_image_encoder_destroy(rtc_image_encoder *e);
 /* rtc_lua_program_render with every file of the script saved by its name: the same launches, lanes and job order as
  * rtc_lua_program_render_gif; `fn` receives, per job —
  *   RTC_LUA_OUT_FILE        a Render job: the whole file the save table gives its name (rtc_image_format's bytes of its
- *                           rows), encoded on the GPU behind the render on the same lane (PPM: printed on the host);
+ *                           rows), encoded on the GPU behind the render on the same lane (PPM: printed on the host); a
+ *                           name of the float table (hdr, pfm, exr — consulted first, see "float files" below): the job
+ *                           renders its f64 canvas instead and the file is rtc_float_format's bytes of it (EXR: HALF);
  *   RTC_LUA_OUT_GIF_RECORD  an AddFrame job: its GIF record, as rtc_lua_program_render_gif delivers it.
  * Before the first launch every Render name is looked up (RTC_ERR_UNSUPPORTED) and every Render size checked against its
  * format (RTC_ERR_ARG); then nothing is rendered. [device] */
@@ -1271,6 +1273,92 @@ rtc_status  rtc_aov_view_rgb8(uint32_t view, const rtc_aov_buffers *b, uint32_t 
  * stream: rtc_image_encoder_encode_device may follow directly. */
 rtc_status  rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_aov_buffers *d, uint32_t width, uint32_t height,
                                      double near, double far, uint32_t n_lights, void *d_rgb8);      /* [device], same bytes */
+
+/* ==== float files: the f64 canvas and the AOV planes saved as data ==================== */
+/* Every writer above takes Color::scale'd 8-bit rows: components above 1.0 are clipped and a depth plane becomes a picture.
+ * These three keep the numbers. Input: the f64 canvas, `rgb` = height*width*3 doubles, top row first (what rtc_render,
+ * rtc_render_lens, rtc_shutter_render_device and rtc_canvas_average_device produce), and — for EXR — the AOV planes of
+ * rtc_aov_buffers. The float table, a table of its own beside rtc_image_format_for_name's (which does not know these
+ * names) with the same extension rule:
+ *   hdr   RTC_FLOAT_HDR   Radiance RGBE           pfm   RTC_FLOAT_PFM   Portable Float Map           exr   RTC_FLOAT_EXR   OpenEXR
+ * Width and height 1..65535. All integers little-endian; no field not listed is written.
+ *
+ * Conversions (csrc/rtc_float.h, the same integer arithmetic on the host and on the device — no hardware conversion):
+ *   f64 -> f32   IEEE round-to-nearest-even; subnormals kept; overflow gives +-inf; any NaN becomes 0x7FC00000.
+ *   f64 -> f16   round-to-nearest-even directly from the f64, never through f32 (1 + 2^-11 + 2^-30 is 0x3C01; through f32
+ *                it would be 0x3C00); subnormals kept; overflow gives +-inf; any NaN becomes 0x7E00.
+ *   f64 -> RGBE  Ward's float2rgbe, made exact. Each component is first mapped: NaN or < 0 -> 0, above 0x1.FEp+126 ->
+ *                0x1.FEp+126. v = the largest mapped component. v < 1e-32: the pixel is 0,0,0,0. Otherwise frexp(v) = (m, e),
+ *                byte c = floor(ldexp(comp_c, 8 - e)) (always <= 255), E = e + 128. Decoding byte * 2^(E - 136) differs from
+ *                the mapped component by less than v / 128.
+ *
+ *   PFM:  "PF\n<w> <h>\n-1.0\n" (decimal), then the rows BOTTOM to top, R,G,B of each pixel as f32.
+ *   HDR:  "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y <h> +X <w>\n", then the scanlines, top row first.
+ *         8 <= w <= 32767: a scanline is 02 02 hi(w) lo(w), then the row's R, G, B and E byte planes, each coded on its own:
+ *           split the plane into MAXIMAL runs of equal bytes;
+ *           every maximal run of length >= 4 is run tokens (128 + n, byte): n = 127 while 127 or more bytes remain, then one
+ *           token for the rest (n >= 1);
+ *           every stretch between such runs is literal tokens (n, n bytes): n = 128 while 128 or more bytes remain, then
+ *           one token for the rest.
+ *         Nothing crosses a plane or a row. A coded plane never exceeds w + ceil(w / 128) bytes (alternating bytes reach it).
+ *         Any other width: flat R,G,B,E pixels. (The rule is on maximal runs, not on a left-to-right parse, so the tokens of
+ *         a row can be found by a segmented scan.)
+ *   EXR:  single-part scanline file, NO_COMPRESSION. Magic 76 2F 31 01, version word 2 (i32). Attributes, each
+ *         name NUL type NUL size (i32) value, in this order: channels (chlist), compression (compression) = 0 (1 byte),
+ *         dataWindow (box2i) = 0,0,w-1,h-1, displayWindow (box2i) = the same, lineOrder (lineOrder) = 0 (1 byte),
+ *         pixelAspectRatio (float) = 1.0f, screenWindowCenter (v2f) = 0,0, screenWindowWidth (float) = 1.0f; then a 0 byte.
+ *         A chlist entry: name NUL, pixel type (i32: 0 UINT, 1 HALF, 2 FLOAT), pLinear 0 and three reserved 0 bytes,
+ *         xSampling 1, ySampling 1 (i32 each); the list ends with a 0 byte. Then h u64 scanline offsets (from the start of
+ *         the file), then per scanline, top first: i32 y, i32 bytes of pixel data, and each channel's w values in chlist
+ *         order. The channels are those the caller supplies, in byte-wise alphabetical order:
+ *           B G N.X N.Y N.Z P.X P.Y P.Z R Z id shadow
+ *         R, G, B = `rgb` (HALF or FLOAT: rgb_type); Z = aov.depth (FLOAT; a miss is +inf); N.* = aov.normal, P.* = aov.point
+ *         (FLOAT); id = aov.index + 1 (UINT, 0 = miss); shadow = aov.shadow (UINT). Any subset: a NULL plane is not stored;
+ *         no canvas and no plane is RTC_ERR_ARG, and so is a canvas with an rgb_type that is neither. aov.flags is not
+ *         stored. No ZIP / PIZ compression, no tiles, no multi-part files.
+ *   HDR and PFM read `rgb` alone (NULL is RTC_ERR_ARG) and ignore rgb_type.
+ *
+ * rtc_float_format_for_name: the float table's format for `name` (RTC_ERR_UNSUPPORTED if none; RTC_ERR_ARG for NULL).
+ * rtc_float_format: the whole file — bytes needed (0 on bad arguments); writes at most cap. Host, normative.
+ * rtc_canvas_save_f64: the file of the canvas to `path`, the format from the name (EXR: HALF); RTC_ERR_UNSUPPORTED before
+ *   anything is opened. Host.
+ * rtc_hdr_rle_row: one plane of one row by the rule above — *n = bytes needed, at most cap of them written (out may be NULL
+ *   when cap is 0). RTC_ERR_ARG for a NULL plane or n, or width 0. Host.
+ * The entries that take a NAME and hold f64 data consult the float table first, then the 8-bit table: ch1::Canvas::save of
+ * an unquantised Canvas, the Python rtc.save given a float64 array, rtc_lua_program_render_saved (a Render job named *.hdr,
+ * *.pfm or *.exr renders its f64 canvas on its lane and delivers the file as RTC_LUA_OUT_FILE; EXR: HALF). */
+enum { RTC_FLOAT_HDR = 0, RTC_FLOAT_PFM = 1, RTC_FLOAT_EXR = 2 };
+enum { RTC_EXR_HALF = 1, RTC_EXR_FLOAT = 2 };
+typedef struct rtc_float_planes {   /* 64 bytes */
+    const double *rgb; rtc_aov_buffers aov; uint32_t rgb_type; uint32_t _pad;
+} rtc_float_planes;
+rtc_status  rtc_float_format_for_name(const char *name, uint32_t *format);
+size_t      rtc_float_format(uint32_t format, const rtc_float_planes *p, uint32_t width, uint32_t height, uint8_t *buf, size_t cap);
+rtc_status  rtc_canvas_save_f64(const char *path, const double *rgb, uint32_t width, uint32_t height);
+rtc_status  rtc_hdr_rle_row(const uint8_t *plane, uint32_t width, uint8_t *out, size_t cap, size_t *n);
+/* The float writers on the device: rtc_float_format's bytes for planes already in device memory (csrc/rtc_float.hip); only
+ * the finished file crosses PCIe, behind its 8-byte length. PFM, EXR and the flat form of HDR are packed by one kernel (one
+ * thread per 16 bytes of the file; the header and EXR's offset table computed on the host); RLE HDR is a chain — planar
+ * R,G,B,E bytes, each row-plane's coded size by a wave, a scan over the 4h sizes, the tokens — whose length exists only on
+ * the device; its buffer is sized from the worst case above. An encoder is bound to a context and owns its scratch, grow-only.
+ *   encode_device: `d` holds DEVICE pointers (rgb and every f64 plane 8-byte aligned, index 4, shadow 2), encoded on the
+ *     context's stream in order with what the caller put there before (after launches of a pipelined context:
+ *     rtc_context_fence first); blocks until the file is on the host. Bad arguments are RTC_ERR_ARG and launch nothing.
+ *   render: Camera::render's f64 canvas through the rows path into the encoder's scratch, then the file; the canvas never
+ *     leaves the device. The bytes equal rtc_float_format of rtc_render's canvas. render_lens: the same through
+ *     rtc_render_lens_rows (lens == NULL: render). rgb_type is read for EXR only.
+ *   bytes: the last file (bytes needed; writes at most cap; 0 before the first); write: the same to `path`. [device] */
+typedef struct rtc_float_encoder rtc_float_encoder;
+rtc_status  rtc_float_encoder_create(rtc_context *ctx, rtc_float_encoder **out);
+rtc_status  rtc_float_encoder_encode_device(rtc_float_encoder *e, uint32_t format, const rtc_float_planes *d, uint32_t width,
+                                            uint32_t height);
+rtc_status  rtc_float_encoder_render(rtc_float_encoder *e, uint32_t format, const rtc_world *w, const rtc_camera *cam,
+                                     uint32_t mode, uint32_t flags, uint32_t rgb_type);
+rtc_status  rtc_float_encoder_render_lens(rtc_float_encoder *e, uint32_t format, const rtc_world *w, const rtc_camera *cam,
+                                          const rtc_lens *lens, uint32_t mode, uint32_t flags, uint32_t rgb_type);
+size_t      rtc_float_encoder_bytes(const rtc_float_encoder *e, uint8_t *buf, size_t cap);
+rtc_status  rtc_float_encoder_write(const rtc_float_encoder *e, const char *path);
+void        rtc_float_encoder_destroy(rtc_float_encoder *e);
 
 #ifdef __cplusplus
 }

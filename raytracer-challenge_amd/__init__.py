@@ -20,7 +20,8 @@ import numpy as np
 from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
-                  RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW)
+                  RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
+                  RtcFloatPlanes, FLOAT_FORMATS, FLOAT_HDR, FLOAT_PFM, FLOAT_EXR, EXR_TYPES, EXR_HALF, EXR_FLOAT)
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librtc.so"
@@ -1018,10 +1019,81 @@ def image_encode(fmt, pixels: np.ndarray) -> bytes:
 
 
 def save(path, pixels: np.ndarray) -> None:
-    """rtc_canvas_save: image_encode's bytes for the format `path`'s extension names, written to `path`."""
+    """rtc_canvas_save: image_encode's bytes for the format `path`'s extension names, written to `path`. A float64 (H, W, 3)
+    canvas under a name of the float table (.hdr, .pfm, .exr) is saved as data (rtc_canvas_save_f64: float_encode's bytes,
+    EXR as HALF); every other array and name goes through the 8-bit table as before."""
+    if isinstance(pixels, np.ndarray) and pixels.dtype == np.float64 and lib().rtc_float_format_for_name(str(path).encode(), C.byref(C.c_uint32())) == 0:
+        a = _canvas_f64(pixels)
+        _check(lib().rtc_canvas_save_f64(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[1], a.shape[0]),
+               "rtc_canvas_save_f64", str(path))
+        return
     a = _pixels_u8(pixels)
     _check(lib().rtc_canvas_save(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], a.shape[2]),
            "rtc_canvas_save", str(path))
+
+
+# ---- float files (include/rtc.h, "float files"): Radiance HDR, PFM, OpenEXR ----------------------------------------------
+def float_format_for_name(name) -> int:
+    """The float table's format for a file name (rtc_float_format_for_name): one of FLOAT_FORMATS' values; any other
+    extension raises RtcError (RTC_ERR_UNSUPPORTED)."""
+    f = C.c_uint32()
+    _check(lib().rtc_float_format_for_name(str(name).encode(), C.byref(f)), "rtc_float_format_for_name", str(name))
+    return f.value
+
+
+def _float_format(fmt) -> int:
+    return FLOAT_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+def _canvas_f64(rgb) -> np.ndarray:
+    a = np.ascontiguousarray(rgb, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("the canvas must be an (H, W, 3) float64 array")
+    return a
+
+
+def _float_planes(rgb_address, plane_addresses: dict, rgb_type) -> RtcFloatPlanes:
+    """rtc_float_planes from the canvas' address (or None) and {plane: address}."""
+    p = RtcFloatPlanes()
+    p.rgb = rgb_address
+    p.aov = _aov_buffers(plane_addresses or {})
+    p.rgb_type = EXR_TYPES[rgb_type] if isinstance(rgb_type, str) else int(rgb_type)
+    return p
+
+
+def float_encode(fmt, rgb=None, planes=None, rgb_type="half") -> bytes:
+    """The float file of an (H, W, 3) float64 canvas in format `fmt` ("hdr", "pfm", "exr" or its value), encoded on the host
+    (rtc_float_format): what FloatEncoder makes on the GPU. EXR also stores the AOV planes of `planes` ({plane: array}, as
+    DeviceWorld.render_aov returns them; "flags" is not stored) — with or without a canvas — and its R, G, B as `rgb_type`
+    ("half" or "float")."""
+    a = None if rgb is None else _canvas_f64(rgb)
+    arrays = dict(planes or {})
+    b = _aov_host_buffers(arrays) if arrays else RtcAovBuffers()
+    shapes = {x.shape[:2] for x in ([a] if a is not None else []) + list(arrays.values())}
+    if len(shapes) != 1:
+        raise ValueError("float_encode needs a canvas or planes, all of one height and width")
+    h, w = shapes.pop()
+    p = _float_planes(None if a is None else a.ctypes.data, {}, rgb_type)
+    p.aov = b
+    f = _float_format(fmt)
+    P8 = C.POINTER(C.c_uint8)
+    need = lib().rtc_float_format(f, C.byref(p), w, h, None, 0)
+    if need == 0:
+        raise RtcError(4, "rtc_float_format", f"format {fmt}, {w}x{h}")
+    buf = np.empty(need, dtype=np.uint8)
+    lib().rtc_float_format(f, C.byref(p), w, h, buf.ctypes.data_as(P8), need)
+    return buf.tobytes()
+
+
+def hdr_rle_row(plane) -> bytes:
+    """One byte plane of one Radiance scanline, run-length coded by the maximal-run rule (rtc_hdr_rle_row)."""
+    a = np.ascontiguousarray(plane, dtype=np.uint8).reshape(-1)
+    n = C.c_size_t()
+    P8 = C.POINTER(C.c_uint8)
+    _check(lib().rtc_hdr_rle_row(a.ctypes.data_as(P8), a.size, None, 0, C.byref(n)), "rtc_hdr_rle_row")
+    buf = np.empty(n.value, dtype=np.uint8)
+    _check(lib().rtc_hdr_rle_row(a.ctypes.data_as(P8), a.size, buf.ctypes.data_as(P8), n.value, C.byref(n)), "rtc_hdr_rle_row")
+    return buf.tobytes()
 
 
 def write_ppm(path, rgb: np.ndarray) -> None:
@@ -1531,6 +1603,30 @@ class ImageEncoder(_Encoder):
         """Camera::render + set_gamma(gamma) + write_to_file(name of format `fmt`), the frame never leaving the device."""
         _check(lib().rtc_image_encoder_render(self._h, _image_format(fmt), world._h, C.byref(cam), mode, flags, gamma),
                "rtc_image_encoder_render", f"format {fmt}")
+        return self.bytes()
+
+
+class FloatEncoder(_Encoder):
+    """The float file writers on the GPU (rtc_float_encoder): Radiance HDR, PFM and OpenEXR of an f64 canvas (and, for EXR,
+    AOV planes) already in device memory, or of a frame rendered straight into the encoder; only the finished file crosses
+    PCIe. The bytes equal float_encode's."""
+    _kind = "float_encoder"
+
+    def encode_device(self, fmt, d_rgb: int | None, width: int, height: int, pointers: dict | None = None, rgb_type="half") -> bytes:
+        """Encode the height x width x 3 float64 canvas at device address d_rgb (None: an EXR of planes only) and the AOV
+        planes at `pointers` ({plane: device address}, EXR) as `fmt`, on the context's stream."""
+        p = _float_planes(d_rgb, pointers, rgb_type)
+        _check(lib().rtc_float_encoder_encode_device(self._h, _float_format(fmt), C.byref(p), width, height),
+               "rtc_float_encoder_encode_device", f"format {fmt}, {width}x{height}")
+        return self.bytes()
+
+    def render(self, fmt, world: "DeviceWorld", cam: RtcCamera, lens: RtcLens | None = None, rgb_type="half", mode: int = MODE_RENDER_ASYNC,
+               flags: int = 0) -> bytes:
+        """Camera::render (through `lens` when given) + save under a name of format `fmt`, the f64 canvas never leaving the
+        device."""
+        t = EXR_TYPES[rgb_type] if isinstance(rgb_type, str) else int(rgb_type)
+        _check(lib().rtc_float_encoder_render_lens(self._h, _float_format(fmt), world._h, C.byref(cam), C.byref(lens) if lens is not None else None,
+                                                   mode, flags, t), "rtc_float_encoder_render", f"format {fmt}")
         return self.bytes()
 
 

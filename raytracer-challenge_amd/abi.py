@@ -90,6 +90,14 @@ class RtcAovBuffers(C.Structure):
                 ("shadow", C.c_void_p)]
 
 
+class RtcFloatPlanes(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("aov", RtcAovBuffers), ("rgb_type", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+FLOAT_FORMATS = {"hdr": 0, "pfm": 1, "exr": 2}
+FLOAT_HDR, FLOAT_PFM, FLOAT_EXR = range(3)
+EXR_TYPES = {"half": 1, "float": 2}
+EXR_HALF, EXR_FLOAT = 1, 2
 AOV_PLANES = {"index": ("int32", 1), "depth": ("float64", 1), "point": ("float64", 3), "normal": ("float64", 3),
               "flags": ("uint8", 1), "shadow": ("uint16", 1)}  # plane -> (numpy dtype, components per pixel)
 AOV_VIEWS = {"depth": 0, "normal": 1, "index": 2, "shadow": 3}
@@ -112,7 +120,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
-assert C.sizeof(RtcAovBuffers) == 48
+assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -315,6 +323,17 @@ PROTOTYPES = {
     "rtc_render_aov": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.POINTER(RtcAovBuffers)]),
     "rtc_aov_view_rgb8": (C.c_int32, [U32, C.POINTER(RtcAovBuffers), U32, U32, D, D, U32, C.POINTER(C.c_uint8)]),
     "rtc_aov_view_rgb8_device": (C.c_int32, [VP, U32, C.POINTER(RtcAovBuffers), U32, U32, D, D, U32, VP]),
+    "rtc_float_format_for_name": (C.c_int32, [C.c_char_p, C.POINTER(U32)]),
+    "rtc_float_format": (C.c_size_t, [U32, C.POINTER(RtcFloatPlanes), U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_canvas_save_f64": (C.c_int32, [C.c_char_p, PD, U32, U32]),
+    "rtc_hdr_rle_row": (C.c_int32, [C.POINTER(C.c_uint8), U32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtc_float_encoder_create": (C.c_int32, [VP, C.POINTER(VP)]),
+    "rtc_float_encoder_encode_device": (C.c_int32, [VP, U32, C.POINTER(RtcFloatPlanes), U32, U32]),
+    "rtc_float_encoder_render": (C.c_int32, [VP, U32, VP, C.POINTER(RtcCamera), U32, U32, U32]),
+    "rtc_float_encoder_render_lens": (C.c_int32, [VP, U32, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, U32]),
+    "rtc_float_encoder_bytes": (C.c_size_t, [VP, C.POINTER(C.c_uint8), C.c_size_t]),
+    "rtc_float_encoder_write": (C.c_int32, [VP, C.c_char_p]),
+    "rtc_float_encoder_destroy": (None, [VP]),
 }
 
 

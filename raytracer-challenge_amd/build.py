@@ -18,7 +18,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "librtc.so"
 
-SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_launch_plan.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp"]
+SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_launch_plan.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp", "host_float.cpp", "rtc_float.hip"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 COMMON += os.environ.get("RTC_CXXFLAGS", "").split()  # experiments, e.g. -DRTC_WAVES_PER_SIMD=4
 # Kernel file only: MachineLICM hoists the VGPR materialisation of every f64 literal (pow's ~25
@@ -52,7 +52,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     cc = hipcc()
     objdir = ROOT / "build" / "rtc"
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_parity.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h", CSRC / "rtc_aov.h", CSRC / "rtc_launch_plan.h"]
+    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_parity.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h", CSRC / "rtc_aov.h", CSRC / "rtc_launch_plan.h", CSRC / "rtc_float.h"]
     objs = []
     for name in SOURCES:
         src = CSRC / name
@@ -87,13 +87,14 @@ def _build_facade(name: str, force: bool = False) -> Path:
     return exe
 
 
-# the six programs, each callable as f(force=False) -> Path
+# the seven programs, each callable as f(force=False) -> Path
 build_facade_tests = partial(_build_facade, "test_facade")  # the C++ mirror of the reference API
 build_facade_update_test = partial(_build_facade, "test_facade_update")  # the resident World updated in place
 build_facade_area_light_test = partial(_build_facade, "test_facade_area_light")  # World::add_area_light
 build_facade_lens_test = partial(_build_facade, "test_facade_lens")  # Camera::set_lens
 build_facade_shutter_test = partial(_build_facade, "test_facade_shutter")  # World::set_shape_motion / Camera::set_shutter
 build_facade_aov_test = partial(_build_facade, "test_facade_aov")  # Camera::render_aov and Aov::view
+build_facade_float_test = partial(_build_facade, "test_facade_float")  # Canvas::save of float files, Aov::save_exr
 
 
 if __name__ == "__main__":

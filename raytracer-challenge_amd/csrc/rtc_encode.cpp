@@ -1,6 +1,6 @@
 // rtc_encode.cpp — [device] the device file writers' shared host side (rtc_encode.h): which chains make each file, the
 // host's part of the file, and the encoder objects of include/rtc.h (rtc_gif_writer, rtc_jpeg_encoder, rtc_png_encoder,
-// rtc_image_encoder) on one core.
+// rtc_image_encoder, rtc_float_encoder) on one core.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +11,7 @@
 
 #include "rtc.h"
 #include "rtc_encode.h"
+#include "rtc_float.h"
 #include "rtc_gif.h"
 #include "rtc_image.h"
 #include "rtc_internal.h"
@@ -57,6 +58,10 @@ rtc_status RtcEncoder::enqueue(const RtcEncodeJob &job, const void *d_pixels, ui
     *e = RtcEncoded{};
     e->width = w;
     e->height = h;
+    if (job.kind == RtcEncodeJob::FLOAT) {
+        const rtc_float_planes d{static_cast<const double *>(d_pixels), job.aov, job.rgb_type, 0u};
+        return rtc_float_enqueue(flt, job.format, &d, w, h, s, e);
+    }
     if (job.kind == RtcEncodeJob::GIF_RECORD) return rtc_gif_enqueue(gif, px, w, h, s, e);
     if (job.kind == RtcEncodeJob::PNG) return rtc_png_enqueue(png, px, w, h, channels, s, e);
     if (job.kind == RtcEncodeJob::JPEG || job.format == RTC_IMAGE_JPEG) {
@@ -104,6 +109,7 @@ struct rtc_gif_writer : RtcEncoderObject {
 struct rtc_jpeg_encoder : RtcEncoderObject {};
 struct rtc_png_encoder : RtcEncoderObject {};
 struct rtc_image_encoder : RtcEncoderObject {};
+struct rtc_float_encoder : RtcEncoderObject {};
 
 namespace {
 
@@ -182,6 +188,19 @@ rtc_status write_file(const RtcEncoderObject *o, const char *path, uint8_t trail
     if (!f) return RTC_ERR_IO;
     const bool ok = std::fwrite(o->file.data(), 1, o->file.size(), f) == o->file.size() && (!trailer || std::fwrite(&trailer, 1, 1, f) == 1);
     return (std::fclose(f) == 0 && ok) ? RTC_OK : RTC_ERR_IO;
+}
+
+// Camera::render's f64 canvas into the object's frame through the rows path (the lens entry with a lens); the context's
+// stream waits for it.
+rtc_status render_f64(RtcEncoderObject *o, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens, uint32_t mode, uint32_t flags) {
+    rtc_context *ctx = o->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rtc_status st = o->d_frame.reserve((size_t)3 * sizeof(double) * cam->hsize * cam->vsize);
+    if (st != RTC_OK) return st;
+    st = lens ? rtc_render_lens_rows(ctx, w, cam, lens, mode, 0, cam->vsize, o->d_frame.get(), nullptr, flags)
+              : rtc_render_rows(ctx, w, cam, mode, 0, cam->vsize, o->d_frame.get(), nullptr, flags);
+    if (st == RTC_OK) st = rtc_context_fence(ctx);
+    return st;
 }
 
 bool gamma_ok(float gamma) { return gamma > 0.0f && gamma <= 3.4028235e38f; }
@@ -295,3 +314,36 @@ rtc_status rtc_image_encoder_render(rtc_image_encoder *e, uint32_t format, const
 
 size_t rtc_image_encoder_bytes(const rtc_image_encoder *e, uint8_t *buf, size_t cap) { return bytes_of(e, buf, cap, 0); }
 rtc_status rtc_image_encoder_write(const rtc_image_encoder *e, const char *path) { return write_file(e, path, 0); }
+
+rtc_status rtc_float_encoder_create(rtc_context *ctx, rtc_float_encoder **out) { return create(ctx, out); }
+void rtc_float_encoder_destroy(rtc_float_encoder *e) { destroy(e); }
+
+rtc_status rtc_float_encoder_encode_device(rtc_float_encoder *e, uint32_t format, const rtc_float_planes *d, uint32_t width, uint32_t height) {
+    RtcFloatLayout L;
+    if (!e || !rtc_float_layout(format, d, width, height, &L, nullptr)) return RTC_ERR_ARG;
+    RtcEncodeJob job{RtcEncodeJob::FLOAT, 0, format};
+    job.rgb_type = d->rgb_type;
+    job.aov = d->aov;
+    return encode(e, job, d->rgb, width, height, 3, 0);
+}
+
+rtc_status rtc_float_encoder_render_lens(rtc_float_encoder *e, uint32_t format, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens,
+                                         uint32_t mode, uint32_t flags, uint32_t rgb_type) {
+    if (!e || !w || !cam || w->ctx != e->ctx) return RTC_ERR_ARG;
+    if (!rtc_float_size_ok(format, cam->hsize, cam->vsize) || (format == RTC_FLOAT_EXR && rgb_type != RTC_EXR_HALF && rgb_type != RTC_EXR_FLOAT))
+        return RTC_ERR_ARG;
+    const rtc_status st = render_f64(e, w, cam, lens, mode, flags);
+    if (st != RTC_OK) return st;
+    rtc_float_planes d{};
+    d.rgb = reinterpret_cast<const double *>(e->d_frame.get());
+    d.rgb_type = rgb_type;
+    return rtc_float_encoder_encode_device(e, format, &d, cam->hsize, cam->vsize);
+}
+
+rtc_status rtc_float_encoder_render(rtc_float_encoder *e, uint32_t format, const rtc_world *w, const rtc_camera *cam, uint32_t mode,
+                                    uint32_t flags, uint32_t rgb_type) {
+    return rtc_float_encoder_render_lens(e, format, w, cam, nullptr, mode, flags, rgb_type);
+}
+
+size_t rtc_float_encoder_bytes(const rtc_float_encoder *e, uint8_t *buf, size_t cap) { return bytes_of(e, buf, cap, 0); }
+rtc_status rtc_float_encoder_write(const rtc_float_encoder *e, const char *path) { return write_file(e, path, 0); }

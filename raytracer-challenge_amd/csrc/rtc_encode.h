@@ -1,5 +1,5 @@
 // rtc_encode.h — the one internal interface of the device file writers (rtc_gif.hip, rtc_jpeg.hip, rtc_png.hip,
-// rtc_image.hip), used by the encoder objects (rtc_encode.cpp) and the Lua lane loop (rtc_lua_render.cpp). Not part of the
+// rtc_image.hip, rtc_float.hip), used by the encoder objects (rtc_encode.cpp) and the Lua lane loop (rtc_lua_render.cpp). Not part of the
 // ABI.
 //
 // A chain is enqueued behind the frame on a stream and leaves a body in device memory whose length is known only on the
@@ -19,9 +19,13 @@
 
 // What to produce from a frame in device memory.
 struct RtcEncodeJob {
-    enum Kind : uint32_t { GIF_RECORD, JPEG, PNG, SAVED } kind = GIF_RECORD;
+    enum Kind : uint32_t { GIF_RECORD, JPEG, PNG, SAVED, FLOAT } kind = GIF_RECORD;
     int32_t quality = 0; // JPEG
-    uint32_t format = 0; // SAVED: the save table's RTC_IMAGE_* format
+    uint32_t format = 0; // SAVED: the save table's RTC_IMAGE_* format; FLOAT: the float table's RTC_FLOAT_*
+    // FLOAT: the frame is the f64 canvas (height*width*3 doubles, or null for an EXR of planes only); EXR's type for its
+    // R, G, B and the AOV planes to store beside them (device pointers, null = none)
+    uint32_t rgb_type = RTC_EXR_HALF;
+    rtc_aov_buffers aov = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // What an enqueued chain leaves behind.
@@ -98,6 +102,13 @@ struct PackScratch {
     ~PackScratch();
 };
 
+struct FloatScratch {
+    PackScratch pack;                // the file, the header (with EXR's channel table behind it) and the length
+    DevBuf<uint8_t> planes;          // RLE HDR: the R, G, B, E byte planes of every row
+    DevBuf<uint32_t> sizes;          // ... the coded size of each of the 4h row-planes
+    DevBuf<unsigned long long> offs; // ... and where each starts in the file
+};
+
 // The chains, their arguments checked by the callers. The input is height*width*channels bytes (GIF: channels 3).
 rtc_status rtc_gif_enqueue(GifScratch &sc, const uint8_t *d_rgb8, uint32_t width, uint32_t height, hipStream_t s, RtcEncoded *e);
 rtc_status rtc_jpeg_enqueue(JpegScratch &sc, const uint8_t *d_pixels, uint32_t width, uint32_t height, uint32_t channels,
@@ -108,12 +119,17 @@ rtc_status rtc_png_enqueue(PngScratch &sc, const uint8_t *d_pixels, uint32_t wid
 rtc_status rtc_image_pack_enqueue(PackScratch &sc, uint32_t format, const uint8_t *d_pixels, uint32_t width, uint32_t height,
                                   uint32_t channels, hipStream_t s, RtcEncoded *e);
 
+// rtc_float.hip: a float file (RTC_FLOAT_*) of the planes at d (device pointers)
+rtc_status rtc_float_enqueue(FloatScratch &sc, uint32_t format, const rtc_float_planes *d, uint32_t width, uint32_t height, hipStream_t s,
+                             RtcEncoded *e);
+
 // The scratch of every chain. Its owner makes its device current and waits for its streams before letting it go.
 struct RtcEncoder {
     GifScratch gif;
     JpegScratch jpeg;
     PngScratch png;
     PackScratch pack;
+    FloatScratch flt;
 
     // enqueue `job` for the frame at d_pixels on `s`
     rtc_status enqueue(const RtcEncodeJob &job, const void *d_pixels, uint32_t width, uint32_t height, uint32_t channels, hipStream_t s,

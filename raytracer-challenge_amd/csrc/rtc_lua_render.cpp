@@ -14,6 +14,7 @@
 
 #include "rtc.h"
 #include "rtc_encode.h"
+#include "rtc_float.h"
 #include "rtc_image.h"
 #include "rtc_internal.h"
 
@@ -36,11 +37,12 @@ bool ends_with(const char *name, const char *ext) { // any case, as the `image` 
 }
 
 // What a job delivers: `format` (RTC_LUA_OUT_*) and either an encoded file (`job`) or the rows, copied behind the render
-// (a saved PPM's rows are printed at delivery).
+// (a saved PPM's rows are printed at delivery). `f64`: the job renders its f64 canvas, not 8-bit rows (a float file).
 struct Output {
     uint32_t format = RTC_LUA_OUT_RGB8;
     bool encoded = false;
     RtcEncodeJob job;
+    bool f64 = false;
 };
 
 rtc_status choose(Entry entry, const rtc_lua_job &job, int32_t quality, Output *out) {
@@ -63,6 +65,10 @@ rtc_status choose(Entry entry, const rtc_lua_job &job, int32_t quality, Output *
             break;
         }
         uint32_t f = 0;
+        if (rtc_float_format_for_name(job.outfile, &f) == RTC_OK) { // the float table first
+            *out = {RTC_LUA_OUT_FILE, true, {RtcEncodeJob::FLOAT, 0, f}, true};
+            break;
+        }
         const rtc_status st = rtc_image_format_for_name(job.outfile, &f);
         if (st != RTC_OK) return st;
         *out = {RTC_LUA_OUT_FILE, f != RTC_IMAGE_PPM, {RtcEncodeJob::SAVED, 0, f}};
@@ -83,6 +89,10 @@ rtc_status check_saved(const rtc_lua_program *prog) {
             if (job.camera.hsize == 0 || job.camera.vsize == 0 || job.camera.hsize > 65535u || job.camera.vsize > 65535u) return RTC_ERR_ARG;
             continue;
         }
+        if (rtc_float_format_for_name(job.outfile, &f) == RTC_OK) {
+            if (!rtc_float_size_ok(f, job.camera.hsize, job.camera.vsize)) return RTC_ERR_ARG;
+            continue;
+        }
         const rtc_status fs = rtc_image_format_for_name(job.outfile, &f);
         if (fs != RTC_OK) return fs == RTC_ERR_ARG ? RTC_ERR_UNSUPPORTED : fs;
         if (!rtc_image_size_ok(f, job.camera.hsize, job.camera.vsize) || job.camera.hsize > 65535u || job.camera.vsize > 65535u)
@@ -101,7 +111,7 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
     HIP_TRY(hipSetDevice(ctx->device));
     constexpr uint32_t RING = rtc_context::MAX_LANES + 1u; // a frame's buffers are reused only after `depth` later launches
     struct Slot {
-        DevBuf<uint8_t> d;     // the frame's rows
+        DevBuf<uint8_t> d;     // the frame's rows (a float file's job: its f64 canvas)
         uint8_t *h = nullptr;  // the delivered bytes (page-locked)
         size_t hcap = 0;
         RtcEncoder enc;
@@ -205,14 +215,14 @@ rtc_status render_lua(rtc_context *ctx, const rtc_lua_program *prog, uint32_t mo
             st = rtc_world_create_area_lights(ctx, job.shapes, job.n_shapes, lights, n_lights, &world);
             if (st != RTC_OK) break;
         }
-        if ((st = sl.d.reserve(bytes)) != RTC_OK) break;
+        if ((st = sl.d.reserve(out.f64 ? bytes * sizeof(double) : bytes)) != RTC_OK) break;
         if (!out.encoded && (st = host_buf(sl, bytes)) != RTC_OK) break;
         if (out.encoded) {
             if (!sl.h_len && hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { st = RTC_ERR_NOMEM; break; }
             if (!copy && hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) != hipSuccess) { copy = nullptr; st = RTC_ERR_DEVICE; break; }
         }
         if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { st = RTC_ERR_DEVICE; break; }
-        st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, nullptr, sl.d.get(), flags);
+        st = rtc_render_rows(ctx, world, &job.camera, mode, 0, job.camera.vsize, out.f64 ? sl.d.get() : nullptr, out.f64 ? nullptr : sl.d.get(), flags);
         if (st != RTC_OK) break;
         hipStream_t s = ctx->lanes > 1u ? ctx->lane[ctx->last.lane] : ctx->stream; // the stream that launch went to
         if (out.encoded) {

@@ -19,6 +19,7 @@
 
 #include <array>
 #include <cstdint>
+#include <cstdio>
 #include <memory>
 #include <cctype>
 #include <exception>
@@ -237,9 +238,16 @@ class Canvas { // canvas.rs:16-109
     }
     // Canvas::write_to_file with every codec of the save table (include/rtc.h, rtc_canvas_save): png, jpg / jpeg (quality
     // 75), gif, ppm, bmp, tga, tif / tiff, ico, ff, pam by the name's last extension, any case; anything else panics with
-    // RTC_ERR_UNSUPPORTED and writes nothing. The same frame and gamma rules as write_to_file.
+    // RTC_ERR_UNSUPPORTED and writes nothing. The same frame and gamma rules as write_to_file. An f64 Canvas under a name
+    // of the float table (hdr, pfm, exr; rtc_canvas_save_f64) is saved as data: the pixels themselves, unclipped and
+    // without gamma (EXR as HALF). A quantised Canvas has no such numbers left and goes through the 8-bit table.
     void save(const std::string &file_name) const {
         const char *where = "Canvas::save";
+        uint32_t float_format = 0;
+        if (!is_imgbuf() && !is_quantised() && rtc_float_format_for_name(file_name.c_str(), &float_format) == RTC_OK) {
+            check(rtc_canvas_save_f64(file_name.c_str(), pixels.data(), width, height), where);
+            return;
+        }
         if (is_imgbuf()) {
             if (gamma != rgba8_gamma)
                 throw Panic(RTC_ERR_ARG, "Canvas::save(" + file_name + "): gamma was changed after Camera::render_rgba8 made this frame");
@@ -448,6 +456,21 @@ struct Aov {
         const rtc_aov_buffers b = const_cast<Aov *>(this)->buffers();
         check(rtc_aov_view_rgb8(v, &b, width, height, near, far, n_lights, c.rgb8.data()), "Aov::view");
         return c;
+    }
+    // The planes as data: one multi-channel OpenEXR file (rtc_float_format, include/rtc.h) — Z, N.*, P.*, id, shadow and,
+    // with an f64 `colour` Canvas of the same size, its R, G, B as HALF (FLOAT with `colour_as_float`).
+    void save_exr(const std::string &file_name, const Canvas *colour = nullptr, bool colour_as_float = false) const {
+        const char *where = "Aov::save_exr";
+        if (colour && (colour->width != width || colour->height != height || colour->pixels.size() != static_cast<size_t>(width) * height * 3))
+            throw Panic(RTC_ERR_ARG, std::string(where) + "(" + file_name + "): the colour Canvas must be an f64 Canvas of the planes' size");
+        rtc_float_planes p{colour ? colour->pixels.data() : nullptr, const_cast<Aov *>(this)->buffers(), colour_as_float ? RTC_EXR_FLOAT : RTC_EXR_HALF, 0u};
+        std::vector<uint8_t> file(rtc_float_format(RTC_FLOAT_EXR, &p, width, height, nullptr, 0));
+        if (file.empty()) check(RTC_ERR_ARG, where);
+        rtc_float_format(RTC_FLOAT_EXR, &p, width, height, file.data(), file.size());
+        std::FILE *f = std::fopen(file_name.c_str(), "wb");
+        if (!f) check(RTC_ERR_IO, where);
+        const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+        if (std::fclose(f) != 0 || !ok) check(RTC_ERR_IO, where);
     }
 };
 
