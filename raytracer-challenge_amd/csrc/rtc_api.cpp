@@ -23,7 +23,7 @@
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt, const DevLens *lens);
+                                       const DevLightTable *lt, const DevLens *lens, int one_sample);
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],
                                       hipStream_t stream);
 extern "C" hipError_t rtc_launch_arith(uint32_t op, const double *a, const double *b, uint32_t n, double *out,
@@ -539,6 +539,7 @@ rtc_status rtc_context_create(int32_t device, void *stream, rtc_context **out) {
     if (const char *e = std::getenv("RTC_LIGHT_TABLE")) ctx->light_table = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_WORLD_UPDATE")) ctx->world_update = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_SKY_ROWS")) ctx->sky_rows = std::atoi(e) != 0;
+    if (const char *e = std::getenv("RTC_ONE_SAMPLE")) ctx->one_sample = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS")) ctx->bin_small_pixels = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS_PIPELINED")) ctx->bin_small_pixels_pipelined = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("RTC_TILES_PER_WG")) {
@@ -1123,9 +1124,10 @@ static void planned_params(const rtc_context *ctx, const rtc_world *w, const rtc
     P.reps = plan.reps;
     std::memcpy(P.chunk_wgs, plan.chunk_wgs, sizeof P.chunk_wgs);
 }
-static hipError_t trace_planned(const RenderParams &P, const LaunchPlan &plan, const LaunchLights &LL, hipStream_t stream, hipEvent_t e0,
-                                hipEvent_t e1, const DevLens *lens) {
-    return rtc_launch_trace(&P, plan.src, (int)plan.refl, (int)plan.refr, plan.grid_wgs, plan.lds_bytes, stream, e0, e1, LL.xl, LL.lt, lens);
+static hipError_t trace_planned(const rtc_context *ctx, const RenderParams &P, const LaunchPlan &plan, const LaunchLights &LL, hipStream_t stream,
+                                hipEvent_t e0, hipEvent_t e1, const DevLens *lens) {
+    return rtc_launch_trace(&P, plan.src, (int)plan.refl, (int)plan.refr, plan.grid_wgs, plan.lds_bytes, stream, e0, e1, LL.xl, LL.lt, lens,
+                            ctx->one_sample ? 1 : 0);
 }
 
 // Carries `plan` (of `rq`, on generation G) out: pick the stream and order it behind the World's build; bin, or prepare the
@@ -1214,7 +1216,7 @@ static rtc_status launch_planned(rtc_context *ctx, const rtc_world *w, rtc_world
     if (timed) ctx->bin_timed[slot] = P.tile_cnt != nullptr;
     // per-render prologue table of the brute-force variants (the culled and the lens kernels do not use it)
     if (plan.needs_prep) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
-    HIP_TRY(trace_planned(P, plan, LL, stream, timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, rq.lens ? &dlens : nullptr));
+    HIP_TRY(trace_planned(ctx, P, plan, LL, stream, timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, rq.lens ? &dlens : nullptr));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
     HIP_TRY(record_read(w, G, stream, stream_bit));
     ctx->last = rtc_launch_info{(uint32_t)plan.src, plan.refl, plan.refr, P.tile_cnt ? 1u : 0u, P.light_cnt ? 1u : 0u, lane, plan.block,
@@ -1740,7 +1742,7 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.hits = d_hits.get();
         LaunchLights LL;
         lights_of(G, LL);
-        if (st == RTC_OK && trace_planned(P, plan, LL, ctx->stream, nullptr, nullptr, nullptr) != hipSuccess) st = RTC_ERR_DEVICE;
+        if (st == RTC_OK && trace_planned(ctx, P, plan, LL, ctx->stream, nullptr, nullptr, nullptr) != hipSuccess) st = RTC_ERR_DEVICE;
     }
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;

@@ -1112,7 +1112,12 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // same for every pixel, so it takes the camera origin's place as the wave-uniform shared apex of the primary bundle. What
 // assumes the PINHOLE origin is compiled out: the tile lists, the per-view DevPrim table (closest_prim), the black tile-row
 // proof. Same sources as the multi-light kernels, render flavour only (no PROBE, no RGBA); three running sums per lane.
-template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, class... XL>
+// ONE = true (render flavour of SRC_CULL and SRC_CULL2, never LENS): the launch of a camera with samples == 1, the reference's
+// default (Camera::render_async) and the only launch the benchmark makes. `aa` is the constant false, so the sample loop is one
+// straight pass and the sub-sample store, the resample test and the averaging are not part of the code: nothing of them is
+// carried — spilled — across the tile loop and the pass loop. The generic kernel takes exactly this path when P.samples == 1,
+// so the results cannot differ; rtc_launch_trace sends a launch here only when P.samples == 1 (RTC_ONE_SAMPLE=0: never).
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, bool ONE = false, class... XL>
 __global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
         const DevShade *__restrict__ t_shade, const DevPrim *__restrict__ t_prim, const DevBound *__restrict__ t_bound,
@@ -1123,6 +1128,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     constexpr bool MULTI = sizeof...(XL) - (LENS ? 1 : 0) != 0;
     static_assert(sizeof...(XL) <= (LENS ? 2 : 1), "at most one block of further lights, then at most one lens");
     static_assert(!LENS || ((SRC == SRC_SMEM || IS_CULL(SRC)) && !PROBE && !RGBA), "lens launches take SRC_SMEM, SRC_CULL or SRC_CULL2, f64 / RGB output");
+    static_assert(!ONE || (IS_CULL(SRC) && !PROBE && !LENS), "the one-sample flavour: pinhole render launches of SRC_CULL and SRC_CULL2");
     constexpr uint32_t BLOCK = RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), TILE_W = RTC_TILE_W_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE);
     extern __shared__ double lds_raw[];
     // Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x 4 doubles x
@@ -1216,7 +1222,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     bool sky_tile = false;
     if constexpr (IS_CULL(SRC) && !PROBE && !LENS) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
-        if (Pt.tile_rows != nullptr && Pt.samples == 1u) {
+        if (Pt.tile_rows != nullptr && (ONE || Pt.samples == 1u)) {
             const uint32_t ity = (Pt.y0 >> 3) + by * Pt.band_stride;
             const uint32_t first = Pt.tile_rows[2u * view], lastinv = Pt.tile_rows[2u * view + 1u];
             sky_tile = ity < first || ity > ~lastinv; // (no tile of the view is non-empty: first = 0xffffffff)
@@ -1249,7 +1255,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
 
     // render_pixel (camera.rs:94-114): one ray, or the 4 fixed sub-samples followed — for the pixels whose
     // samples differ by more than 0.01 from their mean — by `resample_n` more rays (Camera::resample)
-    const bool aa = !LENS && !probe && P.samples != 1u;
+    const bool aa = !ONE && !LENS && !probe && P.samples != 1u; // (ONE: P.samples == 1, the launcher's condition)
     uint32_t nsamples = aa ? 4u : 1u;   // grows to 4 + resample_n after sample 3 when some lane resamples
     // thin lens: sample s = lens_v * usteps + lens_u (v outer, u inner), Color::average_over's running sums in registers
     uint32_t lens_u = 0u, lens_v = 0u;
@@ -2657,33 +2663,43 @@ extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t st
 
 // ---- launchers (called from rtc_api.cpp) --------------------------------------------------
 // XL: nothing (one light), or the World's further lights (k_trace's trailing argument)
-template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA, class... XL>
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA, bool ONE, class... XL>
 static hipError_t launch_kernel(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
                                 hipEvent_t e1, const XL &...xl) {
     if (lds_bytes > 48 * 1024) { // more dynamic LDS than the default limit: opt in (up to 160 KiB per CU on gfx950)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA, XL...>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA, ONE, XL...>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
     // e0/e1 (may be NULL) receive the dispatch's own begin/end timestamps: no marker packets on the stream
-    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA, XL...>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
+    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA, ONE, XL...>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
                           P.kind, P.shade, P.prim, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.idtab, P.pre, P.pre_s, xl...);
     return hipGetLastError();
 }
+// `one_sample`: a render launch of a camera with samples == 1 takes the one-sample instantiation (ONE), which exists for the
+// product sources SRC_CULL and SRC_CULL2 only; the measurement-only sources keep the generic kernel.
 template <int SRC, bool REFL, bool REFR, class... XL>
-static hipError_t launch_one(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
+static hipError_t launch_one(const RenderParams &P, bool one_sample, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
                              hipEvent_t e1, const XL &...xl) {
-    if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
-    if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true>(P, grid, lds_bytes, stream, e0, e1, xl...);
-    return launch_kernel<SRC, REFL, REFR, false, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
+    if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
+    if constexpr (IS_CULL(SRC)) {
+        if (one_sample && P.samples == 1u) {
+            if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true, true>(P, grid, lds_bytes, stream, e0, e1, xl...);
+            return launch_kernel<SRC, REFL, REFR, false, false, true>(P, grid, lds_bytes, stream, e0, e1, xl...);
+        }
+    }
+    if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
+    return launch_kernel<SRC, REFL, REFR, false, false, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
 }
 
 // `xl`: NULL for a World with one light; else its lights 1..n-1 (xl->n >= 1), and src one of SRC_SMEM, SRC_CULL, SRC_CULL2.
 // `lt` (instead of `xl`, never both): the same lights as a device table (lt->rec holds lt->n records, rtc_device.h).
 // `lens`: non-NULL for a thin-lens launch (render flavour, src one of SRC_SMEM, SRC_CULL, SRC_CULL2, no gamma table).
+// `one_sample`: non-zero lets a pinhole render launch with P->samples == 1 take the one-sample instantiation (the context's
+// RTC_ONE_SAMPLE switch); zero keeps every launch on the generic kernel.
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt, const DevLens *lens) {
+                                       const DevLightTable *lt, const DevLens *lens, int one_sample) {
     const dim3 grid(nblocks);
     // the recursion flavour: refractive Worlds carry the full frame stack, reflective ones the LDS stack, the others none
     auto with_depth = [&](auto &&launch) {
@@ -2697,11 +2713,11 @@ extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl,
                 (unsigned long long)lens->usteps * lens->vsteps > RTC_MAX_LENS_SAMPLES)
                 return hipErrorInvalidValue;
             return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-                return with_depth([&](auto RL, auto RR) { return launch_kernel<S(), RL(), RR(), false, false>(*P, grid, lds_bytes, stream, e0, e1, x..., *lens); });
+                return with_depth([&](auto RL, auto RR) { return launch_kernel<S(), RL(), RR(), false, false, false>(*P, grid, lds_bytes, stream, e0, e1, x..., *lens); });
             });
         }
         auto flavours = [&](auto S) {
-            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, grid, lds_bytes, stream, e0, e1, x...); });
+            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, one_sample != 0, grid, lds_bytes, stream, e0, e1, x...); });
         };
         // the LDS-staged sources exist for one-light pinhole launches only
         if constexpr (sizeof...(x) == 0) return with_src<SRC_SMEM, SRC_LDS1, SRC_LDSN, SRC_CULL, SRC_CULL2>(src, flavours);
