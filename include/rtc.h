@@ -386,6 +386,23 @@ rtc_status  rtc_scene_load_yaml_motion_file(const char *path, rtc_shape **shapes
                                             rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
                                             struct rtc_lens *lens_out, uint32_t *has_lens_out,
                                             struct rtc_motion **motions_out, uint32_t *n_motions_out, uint32_t *samples_out);
+/* Scenes whose camera has a projection (struct rtc_projection, below). YAML: `add: camera` with `projection: orthographic`
+ * and `ortho-width` (> 0, required), or `projection: panorama` with, optionally, `pano-h-span` / `pano-v-span` (radians,
+ * defaults 2*pi and pi); `field-of-view` may then be left out (it is not read; pi/2 is stored). These entries are
+ * rtc_scene_load_yaml_lens plus the projection: *has_projection_out = 1 and *proj_out filled when the camera has any of
+ * those keys, else 0 and *proj_out zeroed. Every other YAML entry returns RTC_ERR_PARSE for a scene with those keys, with a
+ * message naming these. A camera with both lens keys and a projection is RTC_ERR_PARSE. Lua cameras stay pinholes. */
+struct rtc_projection;
+rtc_status  rtc_scene_load_yaml_projection(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                           struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                           rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                           struct rtc_lens *lens_out, uint32_t *has_lens_out,
+                                           struct rtc_projection *proj_out, uint32_t *has_projection_out);
+rtc_status  rtc_scene_load_yaml_projection_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                                struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                                rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                                struct rtc_lens *lens_out, uint32_t *has_lens_out,
+                                                struct rtc_projection *proj_out, uint32_t *has_projection_out);
 /* Every light of job `index` as an area light. RTC_ERR_ARG when cap is too small. */
 rtc_status  rtc_lua_program_job_area_lights(const rtc_lua_program *prog, uint32_t index, struct rtc_area_light *lights_out,
                                             uint32_t cap, uint32_t *n_out);
@@ -750,6 +767,67 @@ rtc_status  rtc_render_lens(rtc_context *ctx, const rtc_world *w, const rtc_came
 rtc_status  rtc_render_lens_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_lens *lens,
                                  uint32_t mode, uint32_t flags, uint8_t *rgb8, rtc_stats *stats);
 
+/* Orthographic and equirectangular panorama cameras: other primary rays, everything behind the primary hit unchanged. `cam`
+ * supplies hsize, vsize and view_inv; fov, half_width, half_height and pixel_size are not read. The ray of pixel (x, y) is,
+ * in f64 without fused multiply-add, in exactly this order:
+ *   ORTHOGRAPHIC (parallel rays; the first three lines are Camera::new's aspect rule, camera.rs:33-58, with width/2 in
+ *   place of tan(fov/2), evaluated once, on the host):
+ *     aspect = (double)hsize / (double)vsize
+ *     half_w = width / 2.0          (aspect >= 1)    or   (width / 2.0) * aspect   (aspect < 1)
+ *     half_h = half_w / aspect      (aspect >= 1)    or   width / 2.0
+ *     pixel  = (half_w * 2.0) / (double)hsize
+ *     world_x = half_w - (x + 0.5) * pixel           world_y = half_h - (y + 0.5) * pixel
+ *     origin    = transform_point(view_inv, (world_x, world_y, 0.0))
+ *     direction = normalize(transform_point(view_inv, (world_x, world_y, -1.0)) - origin)
+ *   PANORAMA (every ray leaves the camera origin; longitude across the frame, latitude down it). rtc_projection_tables is
+ *   the normative statement of the trigonometry, evaluated on the host with the C library's sin and cos:
+ *     phi_x   = h_span * (0.5 - ((double)x + 0.5) / (double)hsize)        col[x] = { sin(phi_x), cos(phi_x) }
+ *     theta_y = v_span * (0.5 - ((double)y + 0.5) / (double)vsize)        row[y] = { sin(theta_y), cos(theta_y) }
+ *     origin    = transform_point(view_inv, (0, 0, 0))
+ *     d_cam     = ( row[y].cos * col[x].sin,  row[y].sin,  -(row[y].cos * col[x].cos) )
+ *     direction = normalize(transform_point(view_inv, d_cam) - origin)
+ *   The frame's centre looks down the camera's -z axis and column 0 is on the side of the pinhole camera's column 0. The
+ *   device never evaluates sin or cos: it reads the two tables and multiplies, so its rays are rtc_projection_ray's bit for
+ *   bit whatever the machine's libm does.
+ * The pixel's colour is World::color_at(ray, MAX_REFLECTIONS) as it stands. */
+enum { RTC_PROJ_ORTHOGRAPHIC = 1, RTC_PROJ_PANORAMA = 2 };
+typedef struct rtc_projection {
+    uint32_t kind;     /* RTC_PROJ_ORTHOGRAPHIC or RTC_PROJ_PANORAMA */
+    double   width;    /* orthographic: world-space width of the view, > 0, finite (ignored for panorama) */
+    double   h_span;   /* panorama: longitude covered by the frame, radians, 0 < h_span <= 2*pi (ignored for orthographic) */
+    double   v_span;   /* panorama: latitude covered, radians, 0 < v_span <= pi */
+} rtc_projection;
+/* [host] RTC_ERR_ARG for NULL, a kind that is neither; orthographic: a width that is not finite or not > 0; panorama: a span
+ * that is NaN, not > 0, or above 2*pi (h_span) / pi (v_span), the doubles nearest to them as M_PI gives them; else RTC_OK. */
+rtc_status  rtc_projection_validate(const rtc_projection *p);
+/* [host] The normative ray above; ray = {origin xyz, direction xyz}. RTC_ERR_ARG for a NULL pointer, an invalid projection,
+ * a canvas without pixels, or (x, y) outside it. */
+rtc_status  rtc_projection_ray(const rtc_camera *cam, const rtc_projection *p, uint32_t x, uint32_t y, double ray[6]);
+/* [host] The panorama's tables: col[hsize][2] and row[vsize][2], {sin, cos} each. RTC_ERR_ARG for a NULL pointer, an invalid
+ * projection, a canvas without pixels, or the orthographic kind (it has no tables). */
+rtc_status  rtc_projection_tables(const rtc_camera *cam, const rtc_projection *p, double *col, double *row);
+/* [device] rtc_render_rows with the projection's rays: same buffers, row range, ordering and pipelining contract (and timing
+ * events; rtc_context_last_launch_projection reports the kind, rtc_launch_info lens_samples = 0 and binned = 0). cam->samples must be 1 (RTC_ERR_ARG
+ * otherwise); both render modes keep their meaning, RTC_MODE_RENDER's black last row and column included. RTC_FLAG_NO_CULL
+ * is byte-identical to the culled frame, RTC_FLAG_LDS_TABLE (or an RTC_SRC override naming an LDS source) is
+ * RTC_ERR_UNSUPPORTED, RTC_FLAG_AA_RESAMPLE is ignored. The launch is planned as a thin-lens launch of one sample: no
+ * binning kernel, no per-view table, one workgroup per tile. A panorama's primary rays take the per-wave cull with the
+ * camera origin as the shared apex (a tile too wide to bound, near the poles or in a small frame, tests every object); an
+ * orthographic tile's bundle has its apex at one lane's origin and its spread measured. rtc_stats: rays_primary = pixels
+ * written, rays_primary_proven_miss = 0. Every World form works: one light, several, area lights through the light table,
+ * updated Worlds.
+ * The panorama's tables live in two grow-only device buffers of the context, keyed by (hsize, vsize, h_span, v_span) and
+ * uploaded only when the key changes. Before such an upload the context WAITS for all its streams (every pipeline lane and
+ * the in-order stream), so no launch in flight still reads the tables that are overwritten; a loop that renders one
+ * panorama size never uploads, or waits, after its first frame. */
+rtc_status  rtc_render_projection_rows(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                       uint32_t mode, uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags);
+/* [device] rtc_render / rtc_render_rgb8 with the projection's rays: all rows, copied into host memory. Synchronous; `stats` may be NULL. */
+rtc_status  rtc_render_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                  uint32_t mode, uint32_t flags, double *rgb, rtc_stats *stats);
+rtc_status  rtc_render_projection_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                       uint32_t mode, uint32_t flags, uint8_t *rgb8, rtc_stats *stats);
+
 /* Motion blur: shutter-averaged frames. A motion-blurred frame IS Color::average_over (color.rs:128-139) of n ordinary
  * frames of the World at n shutter times, the cell centres of the shutter interval [0, 1]:
  *     t_k = ((double)k + 0.5) / (double)n                    k = 0..n-1, 1 <= n <= RTC_MAX_SHUTTER_SAMPLES
@@ -1096,6 +1174,10 @@ typedef struct rtc_launch_info {
     uint32_t lens_samples; /* thin-lens launches (rtc_render_lens*): lens samples per pixel, usteps*vsteps; 0 for every other launch */
 } rtc_launch_info;
 rtc_status  rtc_context_last_launch_info(rtc_context *ctx, rtc_launch_info *out);
+/* The projection of the most recent render launch: RTC_PROJ_ORTHOGRAPHIC or RTC_PROJ_PANORAMA for a projection launch
+ * (rtc_render_projection*), 0 for every other launch. An entry of its own: rtc_launch_info has no reserved word left and
+ * keeps its 48 bytes. RTC_ERR_ARG for a NULL pointer or before the first launch, as rtc_context_last_launch_info. */
+rtc_status  rtc_context_last_launch_projection(rtc_context *ctx, uint32_t *out);
 
 /* Page-lock a canvas the CALLER allocated (a Rust `Vec<Color>`, canvas.rs:16-22: 24 bytes per pixel,
  * the layout rtc_render writes) so that rtc_render / rtc_group_render_host fill it by DMA at link speed

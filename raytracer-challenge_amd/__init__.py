@@ -12,12 +12,13 @@ calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -311,6 +312,33 @@ def lens_ray(cam: RtcCamera, lens: RtcLens, x: int, y: int, k: int) -> np.ndarra
     return np.array(list(out))
 
 
+def projection(kind, width: float = 0.0, h_span: float = 2.0 * math.pi, v_span: float = math.pi) -> RtcProjection:
+    """A projection for DeviceWorld.render_projection (rtc_projection, include/rtc.h). kind "orthographic" (or
+    PROJ_ORTHOGRAPHIC): parallel rays, `width` the world-space width of the view. kind "panorama" (PROJ_PANORAMA): the
+    equirectangular frame of every direction around the camera, `h_span` radians of longitude across it (at most 2 pi) and
+    `v_span` of latitude down it (at most pi); its centre looks where the pinhole camera looks."""
+    k = {"orthographic": PROJ_ORTHOGRAPHIC, "panorama": PROJ_PANORAMA}.get(kind, kind)
+    p = RtcProjection()
+    p.kind, p.width, p.h_span, p.v_span = int(k), float(width), float(h_span), float(v_span)
+    _check(lib().rtc_projection_validate(C.byref(p)), "rtc_projection_validate")
+    return p
+
+
+def projection_ray(cam: RtcCamera, proj: RtcProjection, x: int, y: int) -> np.ndarray:
+    """The ray of pixel (x, y) under `proj`: origin xyz, direction xyz (rtc_projection_ray)."""
+    out = (C.c_double * 6)()
+    _check(lib().rtc_projection_ray(C.byref(cam), C.byref(proj), x, y, out), "rtc_projection_ray")
+    return np.array(list(out))
+
+
+def projection_tables(cam: RtcCamera, proj: RtcProjection):
+    """A panorama's (col, row) tables, (hsize, 2) and (vsize, 2) arrays of {sin, cos} (rtc_projection_tables)."""
+    col, row = np.empty((cam.hsize, 2)), np.empty((cam.vsize, 2))
+    _check(lib().rtc_projection_tables(C.byref(cam), C.byref(proj), col.ctypes.data_as(C.POINTER(C.c_double)), row.ctypes.data_as(C.POINTER(C.c_double))),
+           "rtc_projection_tables")
+    return col, row
+
+
 def motion(shape_index: int, open_transform: Matrix, close_transform: Matrix) -> RtcMotion:
     """One moving shape of a motion-blurred frame (rtc_motion, include/rtc.h): shape `shape_index` of the World has the
     OBJECT transform `open_transform` when the shutter opens and `close_transform` when it closes; in between the matrix is
@@ -420,6 +448,27 @@ def load_yaml_lens(text: str | None = None, path: str | None = None):
         w.shapes.append(s)
     lib().rtc_free(shapes)
     return w, cam, (ln if has.value else None)
+
+
+def load_yaml_projection(text: str | None = None, path: str | None = None):
+    """load_yaml_lens for scenes whose camera may have a projection (projection: orthographic | panorama, ortho-width,
+    pano-h-span, pano-v-span): -> (World, RtcCamera, RtcLens or None, RtcProjection or None)."""
+    shapes = C.POINTER(RtcShape)()
+    n = C.c_uint32(0)
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
+    err = C.create_string_buffer(512)
+    ln, has, pj, has_pj = RtcLens(), C.c_uint32(0), RtcProjection(), C.c_uint32(0)
+    fn = lib().rtc_scene_load_yaml_projection_file if path is not None else lib().rtc_scene_load_yaml_projection
+    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
+            err, 512, C.byref(ln), C.byref(has), C.byref(pj), C.byref(has_pj))
+    _check(st, "rtc_scene_load_yaml_projection", err.value.decode(errors="replace"))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
+    for i in range(n.value):
+        s = RtcShape()
+        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
+        w.shapes.append(s)
+    lib().rtc_free(shapes)
+    return w, cam, (ln if has.value else None), (pj if has_pj.value else None)
 
 
 def load_yaml_motion(text: str | None = None, path: str | None = None):
@@ -1264,11 +1313,13 @@ class Context:
         """Object source, lists and lane the most recent render launch ran with (rtc_context_last_launch_info)."""
         i = RtcLaunchInfo()
         _check(lib().rtc_context_last_launch_info(self._h, C.byref(i)), "rtc_context_last_launch_info")
+        pk = C.c_uint32(0)
+        _check(lib().rtc_context_last_launch_projection(self._h, C.byref(pk)), "rtc_context_last_launch_projection")
         return {"source": i.source, "source_name": SOURCE_NAMES.get(i.source, "?"), "reflective": bool(i.reflective),
                 "refractive": bool(i.refractive), "binned_primary_pass": bool(i.binned), "light_lists": bool(i.light_lists),
                 "lane": i.lane, "threads_per_workgroup": i.block, "dynamic_lds_bytes": i.lds_bytes,
                 "tiles_per_workgroup": i.tiles_per_workgroup, "multi_tile_workgroups": i.multi_tile_workgroups,
-                "light_table": bool(i.light_table), "lens_samples": i.lens_samples}
+                "light_table": bool(i.light_table), "lens_samples": i.lens_samples, "projection": pk.value}
 
     def binning_times_ms(self, last: int = 1024) -> np.ndarray:
         """Durations (ms) of the binning kernels of the most recent `last` timed launches (0 where a launch had none)."""
@@ -1427,6 +1478,32 @@ class DeviceWorld:
         st = lib().rtc_render_lens_rows(self.ctx._h, self._h, C.byref(cam), C.byref(lens), mode, y0, y1, d_ptr, d_ptr8, flags)
         if st != 0:
             raise RtcError(st, "rtc_render_lens_rows")
+
+    def render_projection(self, cam: RtcCamera, proj: RtcProjection, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False,
+                          out: np.ndarray | None = None, rgb8: bool = False):
+        """render() with the rays of an orthographic or panorama camera (rtc.projection) instead of the pinhole's; cam gives
+        the size and the view (rtc_render_projection; rgb8=True: rtc_render_projection_rgb8's uint8 frame)."""
+        dtype = np.uint8 if rgb8 else np.float64
+        if out is None:
+            out = np.empty((cam.vsize, cam.hsize, 3), dtype=dtype)
+        elif out.shape != (cam.vsize, cam.hsize, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous (vsize, hsize, 3) array of float64 (uint8 with rgb8)")
+        st = RtcStats()
+        fn, name = (lib().rtc_render_projection_rgb8, "rtc_render_projection_rgb8") if rgb8 else (lib().rtc_render_projection, "rtc_render_projection")
+        _check(fn(self.ctx._h, self._h, C.byref(cam), C.byref(proj), mode, flags, out.ctypes.data_as(C.POINTER(C.c_uint8 if rgb8 else C.c_double)),
+                  C.byref(st) if with_stats else None), name)
+        if with_stats:
+            d = _stats_dict(st)
+            d["rays_primary_proven_miss"] = st.rays_primary_proven_miss   # 0: the black proof is for pinhole rays
+            return out, d
+        return out
+
+    def render_projection_rows(self, cam: RtcCamera, proj: RtcProjection, y0: int, y1: int, d_ptr: int | None, mode: int = MODE_RENDER_ASYNC,
+                               flags: int = 0, d_ptr8: int | None = None) -> None:
+        """render_rows with a projection's rays: rows [y0, y1) into the DEVICE buffer at `d_ptr` (rtc_render_projection_rows)."""
+        st = lib().rtc_render_projection_rows(self.ctx._h, self._h, C.byref(cam), C.byref(proj), mode, y0, y1, d_ptr, d_ptr8, flags)
+        if st != 0:
+            raise RtcError(st, "rtc_render_projection_rows")
 
     def render_rgba8(self, cam: RtcCamera, gamma: float = 1.0, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_stats: bool = False,
                      out: np.ndarray | None = None):
@@ -1877,8 +1954,8 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
-           "load_yaml", "load_yaml_lens", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+           "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",
            "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcLens", "RtcMotion", "RtcMaterial", "RtcShape", "RtcStats"]

@@ -15,6 +15,7 @@ GROUP_ID_BYTES = 128
 MAX_LIGHTS = 8
 MAX_LIGHT_SAMPLES = 256
 MAX_LENS_SAMPLES = 256
+PROJ_ORTHOGRAPHIC, PROJ_PANORAMA = 1, 2  # rtc_projection::kind
 MAX_SHUTTER_SAMPLES = 256
 SHUTTER_RING = 8
 PATTERNS = {"none": 0, "test": 1, "stripe": 2, "stripes": 2, "gradient": 3, "ring": 4, "checker": 5, "checkers": 5, "grid": 6}
@@ -43,6 +44,10 @@ class RtcAreaLight(C.Structure):
 
 class RtcLens(C.Structure):
     _fields_ = [("aperture", C.c_double), ("focal_distance", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
+
+
+class RtcProjection(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("_pad", C.c_uint32), ("width", C.c_double), ("h_span", C.c_double), ("v_span", C.c_double)]
 
 
 class RtcCamera(C.Structure):
@@ -118,7 +123,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
                 2: "brute force, object table staged in LDS tiles", 3: "one-level per-wave cull", 4: "two-level per-wave cull"}
 
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
-assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24
+assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24 and C.sizeof(RtcProjection) == 32
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
 assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64
 
@@ -147,6 +152,9 @@ PROTOTYPES = {
     "rtc_camera_ray_for_pixel": (None, [C.POINTER(RtcCamera), U32, D, U32, D, C.c_double * 6]),
     "rtc_lens_validate": (C.c_int32, [C.POINTER(RtcLens)]),
     "rtc_lens_ray": (C.c_int32, [C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, U32, C.c_double * 6]),
+    "rtc_projection_validate": (C.c_int32, [C.POINTER(RtcProjection)]),
+    "rtc_projection_ray": (C.c_int32, [C.POINTER(RtcCamera), C.POINTER(RtcProjection), U32, U32, C.c_double * 6]),
+    "rtc_projection_tables": (C.c_int32, [C.POINTER(RtcCamera), C.POINTER(RtcProjection), PD, PD]),
     "rtc_material_default": (None, [C.POINTER(RtcMaterial)]),
     "rtc_shape_init": (C.c_int32, [U32, Mat16, C.POINTER(RtcMaterial), C.POINTER(RtcShape)]),
     "rtc_material_set_pattern": (C.c_int32, [C.POINTER(RtcMaterial), U32, Vec3, Vec3, Mat16]),
@@ -229,6 +237,12 @@ PROTOTYPES = {
                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_scene_load_lua_area_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                         C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
+    "rtc_scene_load_yaml_projection": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                   C.POINTER(RtcProjection), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_projection_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                        C.POINTER(RtcProjection), C.POINTER(U32)]),
     "rtc_scene_load_yaml_lens": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                              C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
     "rtc_scene_load_yaml_lens_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
@@ -273,6 +287,10 @@ PROTOTYPES = {
     "rtc_render_lens_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, U32, VP, VP, U32]),
     "rtc_render_lens": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, PD, C.POINTER(RtcStats)]),
     "rtc_render_lens_rgb8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcLens), U32, U32, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_render_projection_rows": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), U32, U32, U32, VP, VP, U32]),
+    "rtc_render_projection": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), U32, U32, PD, C.POINTER(RtcStats)]),
+    "rtc_render_projection_rgb8": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), U32, U32, C.POINTER(C.c_uint8), C.POINTER(RtcStats)]),
+    "rtc_context_last_launch_projection": (C.c_int32, [VP, C.POINTER(U32)]),
     "rtc_render_bands": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, VP, VP, U32]),
     "rtc_render_views": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, U32, U32, VP, VP, U32, U32]),
     "rtc_render": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, PD, C.POINTER(RtcStats)]),

@@ -87,11 +87,12 @@ def _build_facade(name: str, force: bool = False) -> Path:
     return exe
 
 
-# the seven programs, each callable as f(force=False) -> Path
+# the eight programs, each callable as f(force=False) -> Path
 build_facade_tests = partial(_build_facade, "test_facade")  # the C++ mirror of the reference API
 build_facade_update_test = partial(_build_facade, "test_facade_update")  # the resident World updated in place
 build_facade_area_light_test = partial(_build_facade, "test_facade_area_light")  # World::add_area_light
 build_facade_lens_test = partial(_build_facade, "test_facade_lens")  # Camera::set_lens
+build_facade_projection_test = partial(_build_facade, "test_facade_projection")  # Camera::set_projection
 build_facade_shutter_test = partial(_build_facade, "test_facade_shutter")  # World::set_shape_motion / Camera::set_shutter
 build_facade_aov_test = partial(_build_facade, "test_facade_aov")  # Camera::render_aov and Aov::view
 build_facade_float_test = partial(_build_facade, "test_facade_float")  # Canvas::save of float files, Aov::save_exr

@@ -262,6 +262,68 @@ rtc_status rtc_lens_ray(const rtc_camera *cam, const rtc_lens *lens, uint32_t x,
     return RTC_OK;
 }
 
+rtc_status rtc_projection_validate(const rtc_projection *p) {
+    if (!p) return RTC_ERR_ARG;
+    if (p->kind == RTC_PROJ_ORTHOGRAPHIC) return std::isfinite(p->width) && p->width > 0. ? RTC_OK : RTC_ERR_ARG;
+    if (p->kind != RTC_PROJ_PANORAMA) return RTC_ERR_ARG;
+    if (!(p->h_span > 0.) || !(p->h_span <= 2.0 * M_PI)) return RTC_ERR_ARG; // (NaN fails the first test)
+    if (!(p->v_span > 0.) || !(p->v_span <= M_PI)) return RTC_ERR_ARG;
+    return RTC_OK;
+}
+
+// half_w, half_h and pixel of the orthographic rays (include/rtc.h): Camera::new's aspect rule with width / 2 for the half view
+extern "C" void rtc_projection_ortho_terms(uint32_t hsize, uint32_t vsize, double width, double out[3]) {
+    const double half_view = width / 2.0;
+    const double aspect = static_cast<double>(hsize) / static_cast<double>(vsize);
+    if (aspect < 1.0) {
+        out[1] = half_view;
+        out[0] = half_view * aspect;
+    } else {
+        out[0] = half_view;
+        out[1] = half_view / aspect;
+    }
+    out[2] = (out[0] * 2.0) / static_cast<double>(hsize);
+}
+
+// {sin, cos} of cell i of n over `span` (include/rtc.h): the one place the panorama's angles are evaluated
+static void pano_entry(double span, uint32_t i, uint32_t n, double out[2]) {
+    const double a = span * (0.5 - (static_cast<double>(i) + 0.5) / static_cast<double>(n));
+    out[0] = std::sin(a);
+    out[1] = std::cos(a);
+}
+
+rtc_status rtc_projection_tables(const rtc_camera *cam, const rtc_projection *p, double *col, double *row) {
+    if (!cam || !col || !row || rtc_projection_validate(p) != RTC_OK || p->kind != RTC_PROJ_PANORAMA) return RTC_ERR_ARG;
+    if (cam->hsize == 0u || cam->vsize == 0u) return RTC_ERR_ARG;
+    for (uint32_t x = 0; x < cam->hsize; ++x) pano_entry(p->h_span, x, cam->hsize, col + 2u * static_cast<size_t>(x));
+    for (uint32_t y = 0; y < cam->vsize; ++y) pano_entry(p->v_span, y, cam->vsize, row + 2u * static_cast<size_t>(y));
+    return RTC_OK;
+}
+
+// The normative projection ray (include/rtc.h); mul, add and div in the stated order (this file is compiled with -ffp-contract=off).
+rtc_status rtc_projection_ray(const rtc_camera *cam, const rtc_projection *p, uint32_t x, uint32_t y, double ray[6]) {
+    if (!cam || !ray || rtc_projection_validate(p) != RTC_OK || x >= cam->hsize || y >= cam->vsize) return RTC_ERR_ARG;
+    double origin[3], target[3];
+    if (p->kind == RTC_PROJ_ORTHOGRAPHIC) {
+        double t[3];
+        rtc_projection_ortho_terms(cam->hsize, cam->vsize, p->width, t);
+        const double world_x = t[0] - (static_cast<double>(x) + 0.5) * t[2];
+        const double world_y = t[1] - (static_cast<double>(y) + 0.5) * t[2];
+        xform_point(cam->view_inv, world_x, world_y, 0., origin);
+        xform_point(cam->view_inv, world_x, world_y, -1., target);
+    } else {
+        double c[2], r[2];
+        pano_entry(p->h_span, x, cam->hsize, c);
+        pano_entry(p->v_span, y, cam->vsize, r);
+        xform_point(cam->view_inv, 0., 0., 0., origin);
+        xform_point(cam->view_inv, r[1] * c[0], r[0], -(r[1] * c[1]), target);
+    }
+    const V3 dir = normalize(V3{target[0] - origin[0], target[1] - origin[1], target[2] - origin[2]});
+    ray[0] = origin[0]; ray[1] = origin[1]; ray[2] = origin[2];
+    ray[3] = dir.x; ray[4] = dir.y; ray[5] = dir.z;
+    return RTC_OK;
+}
+
 void rtc_material_default(rtc_material *out) { // material.rs:273-283 + 364-369 (WHITE)
     std::memset(out, 0, sizeof *out);
     out->pattern_kind = RTC_PATTERN_NONE;

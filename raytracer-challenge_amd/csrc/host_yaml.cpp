@@ -347,6 +347,8 @@ struct Scene {
     bool have_camera = false;
     rtc_lens lens{0., 1., 1u, 1u};      // the camera's thin lens; the pinhole (aperture 0, focal distance 1, 1x1) without lens keys
     int lens_line = 0;                  // line of the camera entry that has lens keys, 0: none
+    rtc_projection proj{};              // the camera's projection (include/rtc.h); zeroed without projection keys
+    int proj_line = 0;                  // line of the camera entry that has projection keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -391,8 +393,31 @@ void interpret(const Node &root, Scene &sc) {
                 h != static_cast<double>(static_cast<uint32_t>(h)))
                 fail(e.line, "camera width/height must be positive integers"); // lua.rs:159-170
             rtc_view_transform(from, to, up, view);
-            const rtc_status st = rtc_camera_init(static_cast<uint32_t>(w), static_cast<uint32_t>(h),
-                                                  as_number(e.get("field-of-view"), "field-of-view"), view, &sc.camera);
+            // projection (include/rtc.h): projection / ortho-width / pano-h-span / pano-v-span; its rays do not read the field of view
+            sc.proj = rtc_projection{};
+            sc.proj_line = 0;
+            const Node *pk = e.get("projection"), *ow = e.get("ortho-width"), *phs = e.get("pano-h-span"), *pvs = e.get("pano-v-span");
+            if (pk || ow || phs || pvs) {
+                sc.proj_line = e.line;
+                if (!pk || pk->kind != Node::Scalar || (pk->scalar != "orthographic" && pk->scalar != "panorama"))
+                    fail(e.line, "projection must be orthographic or panorama");
+                if (pk->scalar == "orthographic") {
+                    if (phs || pvs) fail(e.line, "pano-h-span / pano-v-span belong to projection: panorama");
+                    if (!ow) fail(e.line, "an orthographic camera needs an ortho-width");
+                    sc.proj.kind = RTC_PROJ_ORTHOGRAPHIC;
+                    sc.proj.width = as_number(ow, "ortho-width");
+                    if (rtc_projection_validate(&sc.proj) != RTC_OK) fail(ow->line, "ortho-width must be a finite number > 0");
+                } else {
+                    if (ow) fail(e.line, "ortho-width belongs to projection: orthographic");
+                    sc.proj.kind = RTC_PROJ_PANORAMA;
+                    sc.proj.h_span = phs ? as_number(phs, "pano-h-span") : 2.0 * M_PI;
+                    sc.proj.v_span = pvs ? as_number(pvs, "pano-v-span") : M_PI;
+                    if (rtc_projection_validate(&sc.proj) != RTC_OK)
+                        fail(e.line, "pano-h-span must be in (0, 2*pi] and pano-v-span in (0, pi], in radians");
+                }
+            }
+            const double fov = (sc.proj_line && !e.get("field-of-view")) ? M_PI / 2.0 : as_number(e.get("field-of-view"), "field-of-view");
+            const rtc_status st = rtc_camera_init(static_cast<uint32_t>(w), static_cast<uint32_t>(h), fov, view, &sc.camera);
             if (st != RTC_OK) fail(e.line, std::string("camera: ") + rtc_strerror(st));
             if (const Node *s = e.get("samples")) {
                 const double sv = as_number(s, "samples");
@@ -421,6 +446,7 @@ void interpret(const Node &root, Scene &sc) {
                 if (!(sc.lens.focal_distance > 0.) || !std::isfinite(sc.lens.focal_distance)) fail(e.line, "focal-distance must be a finite number > 0");
                 if (rtc_lens_validate(&sc.lens) != RTC_OK)
                     fail(e.line, "too many lens samples: lens-usteps x lens-vsteps is at most " + std::to_string(RTC_MAX_LENS_SAMPLES));
+                if (sc.proj_line) fail(e.line, "a camera has a lens or a projection, not both");
             }
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
@@ -509,9 +535,11 @@ extern "C" {
 static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out, uint32_t lights_cap,
                             uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only,
                             rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr,
-                            rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr) {
+                            rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr,
+                            rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
+    if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -530,6 +558,8 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         interpret(*root, sc);
         if (sc.area_line && !area_out) fail(sc.area_line, "the scene has an area light: load it with rtc_scene_load_yaml_area_lights");
         if (sc.lens_line && !lens_out) fail(sc.lens_line, "the scene's camera has a lens: load it with rtc_scene_load_yaml_lens");
+        if (sc.proj_line && !proj_out)
+            fail(sc.proj_line, "the scene's camera has a projection (projection / ortho-width / pano-h-span / pano-v-span): load it with rtc_scene_load_yaml_projection");
         if (sc.motion_line && !motions_out) fail(sc.motion_line, "the scene has motion blur (motion / shutter-samples): load it with rtc_scene_load_yaml_motion");
         if (!first_only && sc.lights.size() > lights_cap) return RTC_ERR_ARG;
         rtc_motion *marr = nullptr;
@@ -562,6 +592,10 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (lens_out) {
             *lens_out = sc.lens;
             *has_lens_out = sc.lens_line ? 1u : 0u;
+        }
+        if (proj_out) {
+            *proj_out = sc.proj;
+            *has_projection_out = sc.proj_line ? 1u : 0u;
         }
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -609,6 +643,15 @@ rtc_status rtc_scene_load_yaml_motion(const char *text, rtc_shape **shapes_out, 
     if (!lens_out || !has_lens_out || !motions_out || !n_motions_out || !samples_out) return RTC_ERR_ARG;
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
                      lens_out, has_lens_out, motions_out, n_motions_out, samples_out);
+}
+
+rtc_status rtc_scene_load_yaml_projection(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                          uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                          size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out,
+                                          uint32_t *has_projection_out) {
+    if (!lens_out || !has_lens_out || !proj_out || !has_projection_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out, nullptr, nullptr, nullptr, proj_out, has_projection_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -668,6 +711,17 @@ rtc_status rtc_scene_load_yaml_motion_file(const char *path, rtc_shape **shapes_
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_motion(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                       lens_out, has_lens_out, motions_out, n_motions_out, samples_out);
+}
+
+rtc_status rtc_scene_load_yaml_projection_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                               uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                               size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out,
+                                               uint32_t *has_projection_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_projection(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                          lens_out, has_lens_out, proj_out, has_projection_out);
 }
 
 } // extern "C"

@@ -23,7 +23,7 @@
 
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt, const DevLens *lens, int one_sample);
+                                       const DevLightTable *lt, const DevLens *lens, const DevProjection *proj, int one_sample);
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],
                                       hipStream_t stream);
 extern "C" hipError_t rtc_launch_arith(uint32_t op, const double *a, const double *b, uint32_t n, double *out,
@@ -628,6 +628,13 @@ rtc_status rtc_context_last_launch_info(rtc_context *ctx, rtc_launch_info *out) 
     return RTC_OK;
 }
 
+rtc_status rtc_context_last_launch_projection(rtc_context *ctx, uint32_t *out) {
+    if (!ctx || !out) return RTC_ERR_ARG;
+    if (ctx->launches_total == 0) return RTC_ERR_ARG; // nothing launched yet
+    *out = ctx->last_projection;
+    return RTC_OK;
+}
+
 rtc_status rtc_context_device_info(rtc_context *ctx, char *name, size_t cap, int32_t *compute_units, int32_t *clock_mhz) {
     if (!ctx) return RTC_ERR_ARG;
     hipDeviceProp_t prop;
@@ -1051,6 +1058,7 @@ struct LaunchRequest {
     uint32_t flags = 0;
     float gamma = 0.f;            // > 0: d_rgb8 receives Canvas::to_imgbuf's RGBA at that gamma (4 B/pixel) instead of Color::scale's RGB
     const rtc_lens *lens = nullptr; // a thin-lens launch (validated by the caller, one view, no gamma)
+    const rtc_projection *proj = nullptr; // an orthographic or panorama launch (likewise; never with a lens)
 };
 // rows [y0, y1) of one camera
 static LaunchRequest rows_request(const rtc_camera *cam, uint32_t mode, uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags) {
@@ -1103,7 +1111,7 @@ static rtc_status plan_request(const rtc_context *ctx, const rtc_world *w, const
     in.hsize = rq.cams->hsize; in.vsize = rq.cams->vsize; in.samples = rq.cams->samples; in.nviews = rq.nviews;
     in.y0 = rq.y0; in.y1 = rq.y1; in.band_stride = rq.band_stride; in.grid_y = rq.grid_y;
     in.mode = rq.mode;
-    in.lens_samples = rq.lens ? rq.lens->usteps * rq.lens->vsteps : 0u;
+    in.lens_samples = rq.lens ? rq.lens->usteps * rq.lens->vsteps : rq.proj ? 1u : 0u; // a projection launch is planned as a lens launch of one sample
     rtc_plan_launch(in, plan);
     return RTC_OK;
 }
@@ -1125,9 +1133,31 @@ static void planned_params(const rtc_context *ctx, const rtc_world *w, const rtc
     std::memcpy(P.chunk_wgs, plan.chunk_wgs, sizeof P.chunk_wgs);
 }
 static hipError_t trace_planned(const rtc_context *ctx, const RenderParams &P, const LaunchPlan &plan, const LaunchLights &LL, hipStream_t stream,
-                                hipEvent_t e0, hipEvent_t e1, const DevLens *lens) {
+                                hipEvent_t e0, hipEvent_t e1, const DevLens *lens, const DevProjection *proj) {
     return rtc_launch_trace(&P, plan.src, (int)plan.refl, (int)plan.refr, plan.grid_wgs, plan.lds_bytes, stream, e0, e1, LL.xl, LL.lt, lens,
-                            ctx->one_sample ? 1 : 0);
+                            proj, ctx->one_sample ? 1 : 0);
+}
+
+// The panorama tables of (cam, proj) in the context's two buffers (include/rtc.h: rtc_projection_tables, keyed by size and
+// spans). A launch in flight may still read the tables of another key, so a change of key first waits for every stream of
+// the context — the lanes and the in-order stream — and then uploads synchronously; the same key again does nothing.
+static rtc_status pano_tables(rtc_context *ctx, const rtc_camera *cam, const rtc_projection *proj) {
+    rtc_context::PanoKey key{cam->hsize, cam->vsize, proj->h_span, proj->v_span};
+    if (ctx->pano_valid && std::memcmp(&key, &ctx->pano_key, sizeof key) == 0) return RTC_OK;
+    std::vector<double> col(2u * (size_t)cam->hsize), row(2u * (size_t)cam->vsize);
+    if (rtc_projection_tables(cam, proj, col.data(), row.data()) != RTC_OK) return RTC_ERR_ARG;
+    HIP_TRY(drain_lanes(ctx));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->pano_valid = false;
+    rtc_status st = ctx->d_pano_col.reserve(col.size(), &ctx->render_allocs);
+    if (st == RTC_OK) st = ctx->d_pano_row.reserve(row.size(), &ctx->render_allocs);
+    if (st == RTC_OK) st = ctx->d_pano_col.upload(col.data(), col.size());
+    if (st == RTC_OK) st = ctx->d_pano_row.upload(row.data(), row.size());
+    if (st != RTC_OK) return st;
+    ctx->pano_key = key;
+    ctx->pano_valid = true;
+    ++ctx->pano_uploads;
+    return RTC_OK;
 }
 
 // Carries `plan` (of `rq`, on generation G) out: pick the stream and order it behind the World's build; bin, or prepare the
@@ -1159,6 +1189,20 @@ static rtc_status launch_planned(rtc_context *ctx, const rtc_world *w, rtc_world
         dlens.vcell = (2.0 * lens->aperture) / static_cast<double>(lens->vsteps);
         dlens.usteps = lens->usteps;
         dlens.vsteps = lens->vsteps;
+    }
+    DevProjection dproj{};
+    if (const rtc_projection *proj = rq.proj) {
+        dproj.kind = proj->kind;
+        if (proj->kind == RTC_PROJ_ORTHOGRAPHIC) {
+            double t[3];
+            rtc_projection_ortho_terms(rq.cams->hsize, rq.cams->vsize, proj->width, t);
+            dproj.half_w = t[0]; dproj.half_h = t[1]; dproj.pixel = t[2];
+        } else {
+            const rtc_status ts = pano_tables(ctx, rq.cams, proj);
+            if (ts != RTC_OK) return ts;
+            dproj.col = ctx->d_pano_col.get();
+            dproj.row = ctx->d_pano_row.get();
+        }
     }
     // start/stop events cost ~9 us of host time and ~5 us of GPU time per launch (measured): callers
     // that are launch-bound sample every n-th launch instead (rtc_context_set_timing)
@@ -1216,12 +1260,14 @@ static rtc_status launch_planned(rtc_context *ctx, const rtc_world *w, rtc_world
     if (timed) ctx->bin_timed[slot] = P.tile_cnt != nullptr;
     // per-render prologue table of the brute-force variants (the culled and the lens kernels do not use it)
     if (plan.needs_prep) HIP_TRY(rtc_launch_prep(G.isect, w->d_prim.get(), G.n, P.views[0].vinv, stream));
-    HIP_TRY(trace_planned(ctx, P, plan, LL, stream, timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, rq.lens ? &dlens : nullptr));
+    HIP_TRY(trace_planned(ctx, P, plan, LL, stream, timed ? pair[0] : nullptr, timed ? pair[1] : nullptr, rq.lens ? &dlens : nullptr,
+                          rq.proj ? &dproj : nullptr));
     if (binset) HIP_TRY(hipEventRecord(binset->traced, ctx->stream));
     HIP_TRY(record_read(w, G, stream, stream_bit));
     ctx->last = rtc_launch_info{(uint32_t)plan.src, plan.refl, plan.refr, P.tile_cnt ? 1u : 0u, P.light_cnt ? 1u : 0u, lane, plan.block,
                                 plan.lds_bytes, plan.reps, plan.chunk_wgs[0] + plan.chunk_wgs[1] + plan.chunk_wgs[2] + plan.chunk_wgs[3],
                                 LL.lt ? 1u : 0u, rq.lens ? rq.lens->usteps * rq.lens->vsteps : 0u};
+    ctx->last_projection = rq.proj ? rq.proj->kind : 0u;
     ++ctx->launches_total;
     ctx->last_bin = rtc_context::LastBin{};
     if (P.tile_cnt && bin_set >= 0) ctx->last_bin = rtc_context::LastBin{w->serial, (uint32_t)bin_set, rq.nviews, plan.tiles_x, plan.tiles_y};
@@ -1272,6 +1318,24 @@ rtc_status rtc_render_lens_rows(rtc_context *ctx, const rtc_world *w, const rtc_
     return render_launch(ctx, w, rq);
 }
 
+// The checks every projection entry shares (include/rtc.h): a valid projection, one ray per pixel
+static rtc_status check_projection(const rtc_camera *cam, const rtc_projection *proj) {
+    if (!cam || rtc_projection_validate(proj) != RTC_OK) return RTC_ERR_ARG;
+    if (cam->samples != 1u) return RTC_ERR_ARG; // anti-aliasing and the projections do not compose
+    return RTC_OK;
+}
+
+rtc_status rtc_render_projection_rows(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode,
+                                      uint32_t y0, uint32_t y1, void *d_rgb, void *d_rgb8, uint32_t flags) {
+    if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || y0 > y1 || y1 > cam->vsize) return RTC_ERR_ARG;
+    const rtc_status ps = check_projection(cam, proj);
+    if (ps != RTC_OK) return ps;
+    if (y0 == y1) return RTC_OK;
+    LaunchRequest rq = rows_request(cam, mode, y0, y1, d_rgb, d_rgb8, flags);
+    rq.proj = proj;
+    return render_launch(ctx, w, rq);
+}
+
 rtc_status rtc_render_bands(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode,
                             uint32_t first_band, uint32_t band_stride, void *d_rgb, void *d_rgb8, uint32_t flags) {
     if (check_render_args(ctx, w, cam, mode, d_rgb, d_rgb8) != RTC_OK || band_stride == 0) return RTC_ERR_ARG;
@@ -1305,6 +1369,13 @@ rtc_status rtc_stats_read(rtc_context *ctx, rtc_stats *out) {
 // Diagnostic (not part of include/rtc.h): device allocations made by the render entry points of this context so far — the
 // binning sets and rtc_render's scratch canvas. A frame sequence must stop allocating after its first launch
 // (tests/test_gpu_group.py::test_render_paths_stop_allocating_after_the_first_launch).
+// Test hook (not in include/rtc.h): how often this context has uploaded panorama tables (pano_tables)
+extern "C" rtc_status rtc_debug_projection_uploads(rtc_context *ctx, unsigned long long *out) {
+    if (!ctx || !out) return RTC_ERR_ARG;
+    *out = ctx->pano_uploads;
+    return RTC_OK;
+}
+
 extern "C" rtc_status rtc_debug_render_allocs(rtc_context *ctx, unsigned long long *out) {
     if (!ctx || !out) return RTC_ERR_ARG;
     *out = ctx->render_allocs;
@@ -1513,7 +1584,7 @@ rtc_status rtc_render_views_rgba8(rtc_context *ctx, const rtc_world *w, const rt
 // hipFree, a device sync, per frame), then to `host`. f64: RGB doubles; else 8-bit rows, RGBA at `gamma` when gamma > 0
 // and Color::scale's RGB otherwise (only those rows leave the kernel: no f64 canvas is written).
 static rtc_status render_frame(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, bool f64,
-                               float gamma, void *host, rtc_stats *stats, const rtc_lens *lens = nullptr) {
+                               float gamma, void *host, rtc_stats *stats, const rtc_lens *lens = nullptr, const rtc_projection *proj = nullptr) {
     if (check_render_args(ctx, w, cam, mode, host, nullptr) != RTC_OK || cam->samples > 255u) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)cam->hsize * cam->vsize, bytes = px * (f64 ? 3 * sizeof(double) : gamma > 0.f ? 4u : 3u);
@@ -1525,6 +1596,7 @@ static rtc_status render_frame(rtc_context *ctx, const rtc_world *w, const rtc_c
         LaunchRequest rq = rows_request(cam, mode, 0, cam->vsize, f64 ? d : nullptr, f64 ? nullptr : d, flags);
         rq.gamma = gamma;
         rq.lens = lens;
+        rq.proj = proj;
         st = render_launch(ctx, w, rq);
     }
     if (st == RTC_OK && drain_lanes(ctx) != hipSuccess) st = RTC_ERR_DEVICE; // pipelined context: the copy below is on the stream
@@ -1558,6 +1630,20 @@ rtc_status rtc_render_lens_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_
     const rtc_status ls = check_lens(cam, lens);
     if (ls != RTC_OK) return ls;
     return render_frame(ctx, w, cam, mode, flags, false, 0.f, rgb8, stats, lens);
+}
+
+rtc_status rtc_render_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode,
+                                 uint32_t flags, double *rgb, rtc_stats *stats) {
+    const rtc_status ps = check_projection(cam, proj);
+    if (ps != RTC_OK) return ps;
+    return render_frame(ctx, w, cam, mode, flags, true, 0.f, rgb, stats, nullptr, proj);
+}
+
+rtc_status rtc_render_projection_rgb8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode,
+                                      uint32_t flags, uint8_t *rgb8, rtc_stats *stats) {
+    const rtc_status ps = check_projection(cam, proj);
+    if (ps != RTC_OK) return ps;
+    return render_frame(ctx, w, cam, mode, flags, false, 0.f, rgb8, stats, nullptr, proj);
 }
 
 rtc_status rtc_render_rgba8(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, float gamma,
@@ -1742,7 +1828,7 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
         P.hits = d_hits.get();
         LaunchLights LL;
         lights_of(G, LL);
-        if (st == RTC_OK && trace_planned(ctx, P, plan, LL, ctx->stream, nullptr, nullptr, nullptr) != hipSuccess) st = RTC_ERR_DEVICE;
+        if (st == RTC_OK && trace_planned(ctx, P, plan, LL, ctx->stream, nullptr, nullptr, nullptr, nullptr) != hipSuccess) st = RTC_ERR_DEVICE;
     }
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;

@@ -194,6 +194,20 @@ struct DevLens {
     uint32_t usteps, vsteps; // usteps * vsteps = samples per pixel, 1 .. RTC_DEV_MAX_LENS_SAMPLES
 };
 
+// Projection launches (rtc_render_projection*, include/rtc.h): the projection instantiations of k_trace take this block as
+// their LAST argument, exactly where the lens instantiations have their DevLens (never both); every other kernel has no such
+// argument. One flavour for both kinds: `kind` is wave-uniform and read in the ray generation only.
+//   orthographic: half_w, half_h, pixel as the host derived them (rtc_projection_ortho_terms) — per-lane origins on the
+//                 camera's z = 0 plane, one direction; the primary bundle is make_bundle's general form;
+//   panorama:     col[W][2] and row[H][2], {sin, cos} of the pixel's longitude and latitude, evaluated by the HOST
+//                 (rtc_projection_tables; the context's buffers, rtc_internal.h) — the kernel multiplies and never calls
+//                 sin or cos; every ray leaves the camera origin, the primary bundle's shared apex as in the pinhole kernels.
+struct DevProjection {
+    uint32_t kind, _pad;         // RTC_PROJ_ORTHOGRAPHIC / RTC_PROJ_PANORAMA
+    double half_w, half_h, pixel;
+    const double *col, *row;     // panorama only
+};
+
 // AOV launches (rtc_render_aov*, include/rtc.h): k_aov's parameter block. The World's tables ride behind it as separate
 // kernel arguments, as for k_trace; a World with several lights adds its DevExtraLights / DevLightTable as the last argument
 // of the SHADOW instantiations. One wave = one 8x8 pixel tile, tile = workgroup id, tiles_x tiles per tile row. A plane

@@ -51,6 +51,7 @@ struct rtc_context {
     uint64_t lane_next = 0;   // launches dealt so far
     // the source / lists the most recent render launch ran with (rtc_context_last_launch_info)
     rtc_launch_info last{};
+    uint32_t last_projection = 0; // ... and its projection kind, 0: none (rtc_context_last_launch_projection)
     uint64_t launches_total = 0; // render launches since the context was created (never reset)
     // the tile lists the most recent render launch read, if it was binned (rtc_debug_tile_counts): the World's upload serial
     // (a World created later at the same address has another), which of its sets, and the launch's grid
@@ -91,6 +92,17 @@ struct rtc_context {
     };
     DevBuf<DevGamma> d_gamma; // GAMMA_SLOTS tables, allocated by the first RGBA call
     GammaSlot gamma_slot[GAMMA_SLOTS];
+    // Panorama tables (rtc_render_projection*, include/rtc.h): {sin, cos} per column and per row of the frame, the host's
+    // rtc_projection_tables, uploaded when the key changes — behind a wait for every stream of the context, since a launch
+    // in flight may read the tables that are replaced (pano_tables, rtc_api.cpp). One panorama size in a loop: one upload.
+    struct PanoKey {
+        uint32_t hsize, vsize;
+        double h_span, v_span;
+    };
+    DevBuf<double> d_pano_col, d_pano_row;
+    PanoKey pano_key{};
+    bool pano_valid = false;
+    unsigned long long pano_uploads = 0; // uploads so far (rtc_debug_projection_uploads)
 };
 
 struct rtc_world {
@@ -185,6 +197,7 @@ extern "C" hipError_t rtc_launch_light_lists_built(uint32_t n, uint32_t cap, con
                                                    const DevTileBundle *cells, const DevTileBundle *macros, uint32_t *cnt, uint32_t *list,
                                                    hipStream_t stream);
 extern "C" rtc_status rtc_gamma_build_table(float gamma, DevGamma *g); // host_ppm.cpp
+extern "C" void rtc_projection_ortho_terms(uint32_t hsize, uint32_t vsize, double width, double out[3]); // host_math.cpp: half_w, half_h, pixel
 // k_aov / k_aov_view (rtc_kernels.hip). `P`: the World's tables only (fill_world); xl / lt: lights_of, read with A->shadow.
 extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
                                      hipStream_t stream);

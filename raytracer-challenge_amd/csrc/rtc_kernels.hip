@@ -991,6 +991,8 @@ template <class T> DEVI const T &last_of(const T &t) { return t; }
 template <class T, class U, class... R> DEVI const auto &last_of(const T &, const U &u, const R &...r) { return last_of(u, r...); }
 // Does k_trace's trailing argument pack end in a DevLens (a thin-lens launch)?
 template <class... T> constexpr bool has_lens_v = (false || ... || __is_same(T, DevLens));
+// ... or in a DevProjection (an orthographic or panorama launch)?
+template <class... T> constexpr bool has_projection_v = (false || ... || __is_same(T, DevProjection));
 // Lights 1..n-1 of the multi-light loop, from the kernel arguments (DevExtraLights) or from the World's table in HBM
 // (DevLightTable, 6 doubles per light). `i` is wave-uniform: plain loads, which the compiler may issue as scalar ones.
 DEVI uint32_t further_light_count(const DevExtraLights &X) { return X.n; }
@@ -1112,7 +1114,13 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // same for every pixel, so it takes the camera origin's place as the wave-uniform shared apex of the primary bundle. What
 // assumes the PINHOLE origin is compiled out: the tile lists, the per-view DevPrim table (closest_prim), the black tile-row
 // proof. Same sources as the multi-light kernels, render flavour only (no PROBE, no RGBA); three running sums per lane.
-// ONE = true (render flavour of SRC_CULL and SRC_CULL2, never LENS): the launch of a camera with samples == 1, the reference's
+// A DevProjection in the DevLens' place (never both): the projection flavour (PROJ, rtc_render_projection*), one for both kinds.
+// Only the ray generation differs — a wave-uniform branch on the kind: an orthographic pixel's ray starts at its own point of
+// the camera's z = 0 plane (per-lane origins: the primary bundle is make_bundle's general form, no ordered walk), a panorama
+// pixel's direction is the product of two host-computed {sin, cos} table entries and starts at the camera origin (shared apex,
+// ordered walk, as the pinhole kernels; a tile too wide to bound runs with B.off). It compiles out what LENS compiles out,
+// and the lens' running sums as well: one ray per pixel. Same sources, render flavour only.
+// ONE = true (render flavour of SRC_CULL and SRC_CULL2, never LENS or PROJ): the launch of a camera with samples == 1, the reference's
 // default (Camera::render_async) and the only launch the benchmark makes. `aa` is the constant false, so the sample loop is one
 // straight pass and the sub-sample store, the resample test and the averaging are not part of the code: nothing of them is
 // carried — spilled — across the tile loop and the pass loop. The generic kernel takes exactly this path when P.samples == 1,
@@ -1125,10 +1133,13 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         const uint32_t *__restrict__ t_orig_s, const DevBound *__restrict__ t_gbound, const DevIdEntry *__restrict__ t_idtab,
         const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
     constexpr bool LENS = has_lens_v<XL...>;
-    constexpr bool MULTI = sizeof...(XL) - (LENS ? 1 : 0) != 0;
-    static_assert(sizeof...(XL) <= (LENS ? 2 : 1), "at most one block of further lights, then at most one lens");
-    static_assert(!LENS || ((SRC == SRC_SMEM || IS_CULL(SRC)) && !PROBE && !RGBA), "lens launches take SRC_SMEM, SRC_CULL or SRC_CULL2, f64 / RGB output");
-    static_assert(!ONE || (IS_CULL(SRC) && !PROBE && !LENS), "the one-sample flavour: pinhole render launches of SRC_CULL and SRC_CULL2");
+    constexpr bool PROJ = has_projection_v<XL...>;
+    constexpr bool ALT = LENS || PROJ; // primary rays that are not the pinhole's: whatever assumes the camera origin is compiled out
+    constexpr bool MULTI = sizeof...(XL) - (ALT ? 1 : 0) != 0;
+    static_assert(!(LENS && PROJ), "a lens or a projection, never both");
+    static_assert(sizeof...(XL) <= (ALT ? 2 : 1), "at most one block of further lights, then at most one lens or projection");
+    static_assert(!ALT || ((SRC == SRC_SMEM || IS_CULL(SRC)) && !PROBE && !RGBA), "lens and projection launches take SRC_SMEM, SRC_CULL or SRC_CULL2, f64 / RGB output");
+    static_assert(!ONE || (IS_CULL(SRC) && !PROBE && !ALT), "the one-sample flavour: pinhole render launches of SRC_CULL and SRC_CULL2");
     constexpr uint32_t BLOCK = RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), TILE_W = RTC_TILE_W_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE);
     extern __shared__ double lds_raw[];
     // Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x 4 doubles x
@@ -1220,7 +1231,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     // separately, rtc_stats::rays_primary_proven_miss). One-sample renders only. Such a tile goes from here to the output
     // stage: it skips the sample loop with its camera loads, and stores its zeros through the same code as every other tile.
     bool sky_tile = false;
-    if constexpr (IS_CULL(SRC) && !PROBE && !LENS) { // (the proof is for rays from the camera origin)
+    if constexpr (IS_CULL(SRC) && !PROBE && !ALT) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
         if (Pt.tile_rows != nullptr && (ONE || Pt.samples == 1u)) {
             const uint32_t ity = (Pt.y0 >> 3) + by * Pt.band_stride;
@@ -1255,7 +1266,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
 
     // render_pixel (camera.rs:94-114): one ray, or the 4 fixed sub-samples followed — for the pixels whose
     // samples differ by more than 0.01 from their mean — by `resample_n` more rays (Camera::resample)
-    const bool aa = !ONE && !LENS && !probe && P.samples != 1u; // (ONE: P.samples == 1, the launcher's condition)
+    const bool aa = !ONE && !ALT && !probe && P.samples != 1u; // (ONE: P.samples == 1, the launcher's condition)
     uint32_t nsamples = aa ? 4u : 1u;   // grows to 4 + resample_n after sample 3 when some lane resamples
     // thin lens: sample s = lens_v * usteps + lens_u (v outer, u inner), Color::average_over's running sums in registers
     uint32_t lens_u = 0u, lens_v = 0u;
@@ -1319,7 +1330,24 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             const double yoffset = ((double)py + yo) * Pr.pixel_size;
             const double world_x = Pr.half_width - xoffset;
             const double world_y = Pr.half_height - yoffset;
-            if constexpr (LENS) { // the pixel's point on the plane in focus
+            if constexpr (PROJ) { // include/rtc.h's projection rays, in its order (the pinhole's world_x / world_y above are dead code here)
+                const DevProjection &PJ = last_of(xl_arg...);
+                if (PJ.kind == RTC_PROJ_ORTHOGRAPHIC) { // (wave-uniform) parallel rays from the camera's z = 0 plane
+                    const double ox = PJ.half_w - ((double)px + 0.5) * PJ.pixel;
+                    const double oy = PJ.half_h - ((double)py + 0.5) * PJ.pixel;
+                    ro = xpoint(Pr.vinv, mk(ox, oy, 0.));
+                    rd = vnormalize_plain(vsub(xpoint(Pr.vinv, mk(ox, oy, -1.)), ro));
+                    shared_origin = false;
+                } else { // panorama: {sin, cos} of the pixel's longitude and latitude from the host's tables, one 16-byte load each
+                    typedef double SinCos __attribute__((ext_vector_type(2)));
+                    const SinCos c = *reinterpret_cast<const SinCos *>(PJ.col + 2u * (size_t)(in_range ? px : 0u)); // (lanes outside the canvas: entry 0)
+                    const SinCos r = *reinterpret_cast<const SinCos *>(PJ.row + 2u * (size_t)(in_range ? py : 0u));
+                    const V3 target = xpoint(Pr.vinv, mk(r.y * c.x, r.x, -(r.y * c.y)));
+                    ro = cam_origin;
+                    rd = vnormalize_plain(vsub(target, cam_origin));
+                    shared_origin = true;
+                }
+            } else if constexpr (LENS) { // the pixel's point on the plane in focus
                 const DevLens &LZ = last_of(xl_arg...);
                 const V3 target = xpoint(Pr.vinv, mk(world_x * LZ.focal_distance, world_y * LZ.focal_distance, -LZ.focal_distance));
                 // (RTC_LENS_UNIFORM_ORIGIN == 2: the exact tests read the origin from VGPRs — same bits — and only the bundle's apex from SGPRs)
@@ -1334,7 +1362,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             }
         }
 
-        bool tracing = traced && (LENS || s < 4u || lane_resample);
+        bool tracing = traced && (ALT || s < 4u || lane_resample);
         bool first = true; // this ray is the one color_at was called with (depth 0)
         int rem = (int)P.remaining;
         int sp = 0;
@@ -1357,17 +1385,17 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             int hidx = -1, hroot = 0;
             Bundle B{}; // every field defined: an undefined field turns into a value carried around the pass loop
             B.off = true;
-            if constexpr (IS_CULL(SRC) && !PROBE && !LENS) {
+            if constexpr (IS_CULL(SRC) && !PROBE && !ALT) {
                 if (shared_origin && first) tile_lookup();
             }
-            const bool use_bins = !LENS && binned && shared_origin && first; // (binned is false in the probe and brute-force variants)
+            const bool use_bins = !ALT && binned && shared_origin && first; // (binned is false in the probe and brute-force variants)
             if constexpr (IS_CULL(SRC)) {
                 if (ballot(tracing) != 0ull && !use_bins) {
                     if (shared_origin && first) B = make_bundle<true, false>(tracing, cam_origin, ro, rd, 0.);
                     else B = make_bundle<false, false>(tracing, cam_origin, ro, rd, 0.);
                 }
             }
-            if (!IS_CULL(SRC) && !LENS && shared_origin && first) { // (DevPrim: the CAMERA origin in object space)
+            if (!IS_CULL(SRC) && !ALT && shared_origin && first) { // (DevPrim: the CAMERA origin in object space)
                 for_each_object<SRC>(P, T, L, tracing, B, [&](int j, auto m, uint32_t kind, auto pr) {
                     if (tracing) closest_prim(kind, m, pr, rd, j, best, hidx, hroot);
                     return true;
@@ -2695,11 +2723,12 @@ static hipError_t launch_one(const RenderParams &P, bool one_sample, dim3 grid, 
 // `xl`: NULL for a World with one light; else its lights 1..n-1 (xl->n >= 1), and src one of SRC_SMEM, SRC_CULL, SRC_CULL2.
 // `lt` (instead of `xl`, never both): the same lights as a device table (lt->rec holds lt->n records, rtc_device.h).
 // `lens`: non-NULL for a thin-lens launch (render flavour, src one of SRC_SMEM, SRC_CULL, SRC_CULL2, no gamma table).
+// `proj`: non-NULL for a projection launch, under the same conditions; a panorama's tables hold P->W and P->H entries. Never both.
 // `one_sample`: non-zero lets a pinhole render launch with P->samples == 1 take the one-sample instantiation (the context's
 // RTC_ONE_SAMPLE switch); zero keeps every launch on the generic kernel.
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt, const DevLens *lens, int one_sample) {
+                                       const DevLightTable *lt, const DevLens *lens, const DevProjection *proj, int one_sample) {
     const dim3 grid(nblocks);
     // the recursion flavour: refractive Worlds carry the full frame stack, reflective ones the LDS stack, the others none
     auto with_depth = [&](auto &&launch) {
@@ -2707,7 +2736,16 @@ extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl,
         if (refl) return launch(std::true_type{}, std::false_type{});
         return launch(std::false_type{}, std::false_type{});
     };
+    if (lens != nullptr && proj != nullptr) return hipErrorInvalidValue;
     return with_further_lights(xl, lt, [&](const auto &...x) {
+        if (proj != nullptr) {
+            if (P->rays != nullptr || P->gamma != nullptr || P->samples != 1u) return hipErrorInvalidValue;
+            if (proj->kind != RTC_PROJ_ORTHOGRAPHIC && (proj->kind != RTC_PROJ_PANORAMA || proj->col == nullptr || proj->row == nullptr))
+                return hipErrorInvalidValue;
+            return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+                return with_depth([&](auto RL, auto RR) { return launch_kernel<S(), RL(), RR(), false, false, false>(*P, grid, lds_bytes, stream, e0, e1, x..., *proj); });
+            });
+        }
         if (lens != nullptr) {
             if (P->rays != nullptr || P->gamma != nullptr || P->samples != 1u || lens->usteps == 0u || lens->vsteps == 0u ||
                 (unsigned long long)lens->usteps * lens->vsteps > RTC_MAX_LENS_SAMPLES)

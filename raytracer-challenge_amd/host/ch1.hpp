@@ -497,11 +497,26 @@ class Camera { // camera.rs:17-160
     void set_lens(double aperture, double focal_distance, uint32_t usteps = 1, uint32_t vsteps = 1) {
         const rtc_lens l{aperture, focal_distance, usteps, vsteps};
         check(rtc_lens_validate(&l), "Camera::set_lens");
+        if (has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::set_lens on a camera with a projection");
         lens_ = l;
         has_lens_ = true;
     }
     void clear_lens() { has_lens_ = false; }
     bool has_lens() const { return has_lens_; }
+    // Orthographic and panorama cameras (rtc_projection, include/rtc.h). With a projection set, render / render_async and
+    // their rgb8 forms go through rtc_render_projection / rtc_render_projection_rgb8: this camera's size and view, the
+    // projection's rays (antialiasing_samples must be 1). A lens and a projection exclude each other (whichever is set second
+    // throws); the rgba8 forms, render_aov and a shutter have no projection entry and throw. Not part of the reference's Camera.
+    void set_projection(const rtc_projection &p) {
+        check(rtc_projection_validate(&p), "Camera::set_projection");
+        if (has_lens_) check(RTC_ERR_UNSUPPORTED, "Camera::set_projection on a camera with a lens");
+        proj_ = p;
+        has_projection_ = true;
+    }
+    void set_orthographic(double width) { set_projection(rtc_projection{RTC_PROJ_ORTHOGRAPHIC, width, 0., 0.}); }
+    void set_panorama(double h_span = 6.283185307179586 /* 2 pi */, double v_span = 3.141592653589793 /* pi */) { set_projection(rtc_projection{RTC_PROJ_PANORAMA, 0., h_span, v_span}); }
+    void clear_projection() { has_projection_ = false; }
+    bool has_projection() const { return has_projection_; }
     // Motion blur (rtc_shutter, include/rtc.h): with a shutter set, every render form — the lens and render_rgba8 with a
     // lens included — is the mean of `samples` frames (1..RTC_MAX_SHUTTER_SAMPLES) of the World at the cell centres of the
     // shutter interval, its shapes moved as World::set_shape_motion says, rendered and averaged on the device by one
@@ -536,6 +551,7 @@ class Camera { // camera.rs:17-160
   private:
     Aov run_aov(const World &w, uint32_t mode) const {
         if (has_lens_ || shutter_) check(RTC_ERR_UNSUPPORTED, "Camera::render_aov with a lens or a shutter");
+        if (has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_aov with a projection");
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Aov a;
@@ -553,6 +569,12 @@ class Camera { // camera.rs:17-160
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Canvas canvas(hsize, vsize);
+        if (has_projection_) {
+            if (shutter_) check(RTC_ERR_UNSUPPORTED, "Camera::render with a projection and a shutter");
+            World::Uploaded up(w);
+            check(rtc_render_projection(Device::get(), up.w, &c, &proj_, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
+            return canvas;
+        }
         if (shutter_) {
             Exposure e(w, c, has_lens_ ? &lens_ : nullptr, shutter_);
             check(rtc_shutter_render(Exposure::shutter(), &e.scene, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr), "Camera::render");
@@ -567,6 +589,12 @@ class Camera { // camera.rs:17-160
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Canvas canvas = Canvas::quantised(hsize, vsize);
+        if (has_projection_) {
+            if (shutter_) check(RTC_ERR_UNSUPPORTED, "Camera::render with a projection and a shutter");
+            World::Uploaded up(w);
+            check(rtc_render_projection_rgb8(Device::get(), up.w, &c, &proj_, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
+            return canvas;
+        }
         if (shutter_) {
             Exposure e(w, c, has_lens_ ? &lens_ : nullptr, shutter_);
             check(rtc_shutter_render_rgb8(Exposure::shutter(), &e.scene, mode, RTC_FLAG_NONE, canvas.rgb8.data(), nullptr), "Camera::render");
@@ -580,6 +608,7 @@ class Camera { // camera.rs:17-160
     Canvas run_rgba8(const World &w, uint32_t mode, float gamma) const {
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
+        if (has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_rgba8 with a projection");
         if (shutter_) { // (this path has a lens entry: the mean's RGBA is made by the averaging kernel)
             Canvas canvas = Canvas::imgbuf(hsize, vsize, gamma);
             Exposure e(w, c, has_lens_ ? &lens_ : nullptr, shutter_);
@@ -643,6 +672,8 @@ class Camera { // camera.rs:17-160
     rtc_camera flat_{};
     rtc_lens lens_{0., 1., 1u, 1u};
     bool has_lens_ = false;
+    rtc_projection proj_{};
+    bool has_projection_ = false;
     uint32_t shutter_ = 0;
 };
 

@@ -27,7 +27,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         tag += ",one" if m.group(6) == "1" else ""  # the one-sample flavour (cameras with samples == 1)
         # the instantiations for Worlds with several lights: in the kernel arguments, or in the World's device table
         tag += ",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else ""
-        tag += ",lens>" if "DevLens" in name else ">"  # the thin-lens flavour (rtc_render_lens*)
+        # the thin-lens flavour (rtc_render_lens*) and the projection flavour (rtc_render_projection*)
+        tag += ",lens>" if "DevLens" in name else ",proj>" if "DevProjection" in name else ">"
     elif (a := re.search(r"k_aovILi(\d)ELb(\d)E", name)):  # the AOV kernel: source, shadow passes, where the further lights come from
         tag = "k_aov<%s,shadow=%s" % a.groups() + (",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">")
     elif "k_aov_view" in name:
