@@ -10,6 +10,7 @@ import os
 import shutil
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor, as_completed
 from functools import partial
 from pathlib import Path
 
@@ -18,7 +19,10 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "librtc.so"
 
-SOURCES = ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_launch_plan.cpp", "rtc_group.cpp", "rtc_kernels.hip", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp", "host_float.cpp", "rtc_float.hip"]
+# The render path's kernel sources, by far the longest compiles: first in SOURCES, so that they start first. The tools
+# (tools/kernel_resources.py, the ISA listings for tools/isa_compare.py) run over exactly these.
+KERNEL_SOURCES = ["rtc_kernels.hip"]
+SOURCES = KERNEL_SOURCES + ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_launch_plan.cpp", "rtc_group.cpp", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp", "host_float.cpp", "rtc_float.hip"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 COMMON += os.environ.get("RTC_CXXFLAGS", "").split()  # experiments, e.g. -DRTC_WAVES_PER_SIMD=4
 # Kernel file only: MachineLICM hoists the VGPR materialisation of every f64 literal (pow's ~25
@@ -47,23 +51,38 @@ def _stale(target: Path, deps: list[Path]) -> bool:
     return any(d.stat().st_mtime > t for d in deps)
 
 
+def jobs() -> int:
+    """How many compilers run at once: MAX_JOBS when set, else the CPU count; never more than 16."""
+    return max(1, min(16, int(os.environ.get("MAX_JOBS") or os.cpu_count() or 1)))
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Compile every source to an object in build/ and link librtc.so next to this file."""
+    """Compile every stale source to an object in build/, jobs() at a time, and link librtc.so next to this file."""
     cc = hipcc()
     objdir = ROOT / "build" / "rtc"
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [ROOT / "include" / "rtc.h", CSRC / "rtc_device.h", CSRC / "rtc_internal.h", CSRC / "rtc_bands.h", CSRC / "rtc_gamma.h", CSRC / "rtc_parity.h", CSRC / "rtc_gif.h", CSRC / "rtc_jpeg.h", CSRC / "rtc_png.h", CSRC / "rtc_image.h", CSRC / "rtc_encode.h", CSRC / "rtc_devmem.h", CSRC / "rtc_world_build.h", CSRC / "rtc_aov.h", CSRC / "rtc_launch_plan.h", CSRC / "rtc_float.h"]
-    objs = []
-    for name in SOURCES:
+    headers = [ROOT / "include" / "rtc.h", *sorted(CSRC.glob("*.h"))]
+    objs = [objdir / (name + ".o") for name in SOURCES]
+    cmds = []
+    for name, obj in zip(SOURCES, objs):
         src = CSRC / name
-        obj = objdir / (name + ".o")
-        objs.append(obj)
         if force or _stale(obj, [src] + headers):
             flags = kernel_compile_line() if name.endswith(".hip") else [cc, "--offload-arch=gfx950", *COMMON]
-            cmd = [*flags, "-c", str(src), "-o", str(obj)]
-            if verbose:
-                print(" ".join(cmd), file=sys.stderr)
-            subprocess.run(cmd, check=True)
+            cmds.append([*flags, "-c", str(src), "-o", str(obj)])
+
+    def compile_one(cmd: list[str]) -> subprocess.CompletedProcess:
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+    with ThreadPoolExecutor(max_workers=jobs()) as pool:
+        for done in as_completed([pool.submit(compile_one, cmd) for cmd in cmds]):
+            r = done.result()
+            sys.stderr.write(r.stdout)  # each compiler's output in one piece, as soon as it has finished
+            if r.returncode != 0:  # the first failure to finish is the one raised; queued compiles never start (the
+                # `with` still waits for the compilers already running: their objects stay whole)
+                pool.shutdown(wait=False, cancel_futures=True)
+                r.check_returncode()
     if force or _stale(LIB, objs):
         cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB), *map(str, objs), "-ldl"]
         if verbose:

@@ -253,7 +253,7 @@ def exact_cases():
             assert h[i].hit_index == 0 and h[i].t == 0.0, f"ray {i}: t = +-0 on the plane is a hit"
     rays = [(0.5, 0., 0.5, 0., -1., 1.), (0.5, 0., 0.5, 0., 1., 1.), (0.5, -0., 0.5, 0., -1., 1.), (0.5, -0., 0.5, 0.25, 0.5, -1.)]
     cs.append(Case("plane_origin_on_plane", "plane_zero_t", number([shp(PLANE)]), L((1., 5., -2.)), rays, plane_origin))
-    # plane_t_certainly_negative's guards (rtc_kernels.hip:304): scaling(2^260, 2^-520, 2^260) has determinant 1 and multiplies
+    # plane_t_certainly_negative's guards (rtc_kernels.hip): scaling(2^260, 2^-520, 2^260) has determinant 1 and multiplies
     # the local o.y and d.y by 2^520. o.y = 2^-1020 -> 2^-500 (at the lo guard), d.y = 2^60 -> 2^580 (beyond hi): the quotient
     # -2^-1080 underflows to -0.0, which t >= 0.0 accepts. d.y = 2^-20 -> 2^500 exactly: t = -2^-1000, a miss.
     def plane_underflow(h, _):
@@ -318,7 +318,7 @@ def exact_cases():
     shapes = number([shp(PLANE), shp(PLANE, ("translation", 0., 3., 0.), m=mat(color=(0.5, 0.5, 0.5)))])
     cs.append(Case("shadow_occluder_t_equals_distance", "shadow", shapes, O.light((0., 3., -4.)), [(0., 1., -5., 0., -1., 1.)], shadow_equal))
 
-    # Shading material.rs:339-352 and the kernel's pow skip (rtc_kernels.hip:1020): specular +-0, rde exactly 1, shininess
+    # Shading material.rs:339-352 and the kernel's pow skip (lighting, rtc_kernels.hip): specular +-0, rde exactly 1, shininess
     # 0 / 200 / 1e300; from straight above with the light straight above, reflectv == eyev == normal: rde == 1.
     for sp in (0.0, -0.0, 0.9):
         for sh in (0.0, 200.0, 1e300):
@@ -486,7 +486,7 @@ def pixel_ray(cam, x, y, xo=0.5, yo=0.5):
 
 def tile_row_bound(cam, ty, W):
     """A plain restatement (f64) of cone_misses_plane's lower bound for the floor y = 0 over tile row ty: the smallest
-    d.y of any pixel-area corner of the row, less the cone's margin (rtc_kernels.hip:2292, 2332-2334)."""
+    d.y of any pixel-area corner of the row, less the cone's margin (cone_misses_plane and its use in k_bin_tiles, rtc_kernels.hip)."""
     worst = math.inf
     for tx in range((W + 7) // 8):
         ax = pixel_ray(cam, tx * 8 + 3, ty * 8 + 3)[3:]

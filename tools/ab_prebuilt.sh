@@ -10,7 +10,7 @@ for w in $WL; do
       cp _ab/rtc_$v.so $LIB
       timeout -k 10 120 python bench.py --workload $w --steps 96 --warmup 16 --lean 2>/dev/null | python3 -c "
 import sys,json
-d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w', '$v', 'kernel/frame', d['roofline']['kernel_ms_per_frame'], 'ms/frame', d['ms_per_step'])" || echo "$w $v failed"
+d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w', '$v', 'kernel/frame', d['roofline']['kernel_ms_per_frame'], 'ms/frame', d['ms_per_step'])" || { echo "$w $v failed: stopping"; cp /tmp/rtc_orig.so $LIB; exit 1; }  # nothing more is started on a GPU after a failed run
     done
   done
 done

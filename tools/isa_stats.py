@@ -1,9 +1,8 @@
 """Static instruction mix of the k_trace and k_aov variants from hipcc -S output (tools: see DESIGN.md).
-usage: python tools/isa_stats.py /tmp/k.s"""
-import re
+usage: python tools/isa_stats.py K.s [MORE.s ...]   (listings of the kernel units, build.KERNEL_SOURCES; read as one)"""
 import sys
 
-s = open(sys.argv[1]).read()
+s = "\n".join(open(p).read() for p in sys.argv[1:])
 for name, label in (("_Z7k_traceILi3ELb0ELb0ELb0E", "flat cull"), ("_Z7k_traceILi3ELb1ELb0ELb0E", "reflect cull"),
                     ("_Z7k_traceILi3ELb1ELb1ELb0E", "refract cull"), ("_Z7k_traceILi4ELb0ELb0ELb0E", "flat cull2"),
                     ("_Z5k_aovILi3ELb0EJEE", "aov cull"), ("_Z5k_aovILi4ELb0EJEE", "aov cull2"), ("_Z5k_aovILi3ELb1EJEE", "aov cull +sh"),

@@ -4,15 +4,24 @@ import importlib.util
 import re
 import subprocess
 import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 spec = importlib.util.spec_from_file_location("_rtc_build", ROOT / "raytracer-challenge_amd" / "build.py")
 build = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(build)
-cmd = [*build.kernel_compile_line(), "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:], "-c", str(build.CSRC / "rtc_kernels.hip"),
-       "-o", "/tmp/rtc_k.o"]
-t = subprocess.run(cmd, capture_output=True, text=True).stderr
+
+
+def remarks(name):  # one kernel unit's remarks
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [*build.kernel_compile_line(), "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:], "-c", str(build.CSRC / name), "-o", tmp + "/k.o"]
+        return subprocess.run(cmd, capture_output=True, text=True).stderr
+
+
+with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
+    t = "".join(pool.map(remarks, build.KERNEL_SOURCES))
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
