@@ -1356,6 +1356,90 @@ rtc_status  rtc_aov_view_rgb8(uint32_t view, const rtc_aov_buffers *b, uint32_t 
 rtc_status  rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_aov_buffers *d, uint32_t width, uint32_t height,
                                      double near, double far, uint32_t n_lights, void *d_rgb8);      /* [device], same bytes */
 
+/* ==== ambient occlusion: how much of the hemisphere over a pixel's hit is blocked nearby ===== */
+/* One more plane of the AOV family: per pixel, how many of a fixed fan of rays leaving the centre ray's hit into the
+ * hemisphere about its normal meet something within `radius`. It is what puts the contact shadow under a sphere resting on
+ * a floor, which the point-light shading (one `ambient` term for every surface) cannot. Rendered by a kernel of its own
+ * (k_ao, csrc/rtc_kernels.hip): k_aov's primary pass and compute_vectors, then one bounded any-hit pass per sample.
+ *
+ *   Samples. Cosine-weighted directions at the centres of a usteps x vsteps grid of the unit square, NO JITTER (the area
+ *   light's and the lens's rule). For sample k = v*usteps + u (v outer, u inner) the HOST evaluates, in f64:
+ *       r   = sqrt(((double)u + 0.5) / (double)usteps)
+ *       phi = ((2.0 * M_PI) * ((double)v + 0.5)) / (double)vsteps
+ *       local_k = ( r * cos(phi),  r * sin(phi),  sqrt(1.0 - r * r) )
+ *   rtc_ao_expand is the normative list. The device reads that table and never evaluates sin or cos
+ *   (rtc_projection_tables' rule), so its rays are the host's bit for bit whatever the machine's libm does.
+ *
+ *   The ray of a sample, rtc_ao_ray: f64, no fused multiply-add, every product and sum in exactly this order. With
+ *   n = normal and l = local:
+ *       sign = copysign(1.0, n.z)
+ *       a    = -1.0 / (sign + n.z)
+ *       b    = (n.x * n.y) * a
+ *       t    = ( 1.0 + ((sign * n.x) * n.x) * a,   sign * b,                   -(sign * n.x) )
+ *       s    = ( b,                                sign + ((n.y * n.y) * a),   -n.y )
+ *       origin      = over_point
+ *       direction.c = ((t.c * l.x) + (s.c * l.y)) + (n.c * l.z)          c = x, y, z
+ *   (t, s, n) is the branch-free orthonormal basis of Duff et al., "Building an Orthonormal Basis, Revisited" (JCGT 2017).
+ *   The direction is NOT renormalised: it is unit to a few ulp, and leaving it so saves a square root and three IEEE
+ *   divisions per ray. Distances along the ray (`t` below) are measured in the direction's own length.
+ *
+ *   The plane. For pixel (x, y) let Hit be the centre ray's rtc_hit exactly as the AOV section defines it. `ao` is
+ *   uint16_t, row-major, and for a pixel that hits holds the number of samples k for which
+ *   World::intersect(rtc_ao_ray(Hit.normal, Hit.over_point, local_k)) has a hit (Intersections::get_hit: the smallest
+ *   t >= 0.0) with t < radius — is_shadowed_by_light's comparison (shape.rs:716-727) with `radius` in place of the distance
+ *   to the light. A pixel that misses holds 0; so do the last row and column under RTC_MODE_RENDER.
+ *
+ *   Viewing and saving need no view of their own: the plane has the `shadow` plane's type. Put it in
+ *   rtc_aov_buffers::shadow and pass n_lights = usteps*vsteps: RTC_AOV_VIEW_SHADOW is then scale(1 - count/n), on the host
+ *   and on the device, and the EXR writer stores it as its `shadow` channel.
+ *   Flags, ordering, counters, Worlds: as rtc_render_aov_device. RTC_FLAG_NO_CULL gives the same bytes, RTC_FLAG_LDS_TABLE
+ *   is RTC_ERR_UNSUPPORTED; rtc_stats is not touched; nothing about the lights is read, so every World form works.
+ *   Limits. The centre ray only (whatever cam->samples says), no jitter, and no AO of lens, shutter, group or Lua launches:
+ *   composite the plane over those frames with rtc_canvas_apply_ao. */
+#define RTC_MAX_AO_SAMPLES 256u
+typedef struct rtc_ao {            /* 16 bytes */
+    double   radius;               /* > 0; +infinity = unbounded. Anything else, NaN included, is RTC_ERR_ARG */
+    uint32_t usteps, vsteps;       /* >= 1 each; usteps*vsteps <= RTC_MAX_AO_SAMPLES */
+} rtc_ao;
+/* [host] RTC_ERR_ARG for NULL or a field outside the ranges above; else RTC_OK. */
+rtc_status  rtc_ao_validate(const rtc_ao *ao);
+/* [host] the normative sample list: dirs[3*k + c] = local_k.c for k < usteps*vsteps, and *n = usteps*vsteps. `dirs` needs
+ * room for 3*usteps*vsteps doubles (at most 3*RTC_MAX_AO_SAMPLES). RTC_ERR_ARG: NULL, an invalid rtc_ao. */
+rtc_status  rtc_ao_expand(const rtc_ao *ao, double *dirs, uint32_t *n);
+/* [host] the normative ray; ray = {origin xyz, direction xyz}. RTC_ERR_ARG: a NULL pointer. */
+rtc_status  rtc_ao_ray(const double normal[3], const double over_point[3], const double local[3], double ray[6]);
+/* [host] the normative packing: per-pixel hit records and per-pixel occluded-sample counts into the plane, mode rule
+ * included, a miss gives 0. RTC_ERR_ARG: a NULL pointer, a mode that does not exist. */
+rtc_status  rtc_ao_from_hits(const rtc_hit *hits, const uint16_t *counts, uint32_t width, uint32_t height, uint32_t mode,
+                             uint16_t *out);
+/* [device] enqueue on the context's stream; d_ao is a DEVICE pointer, 2-byte aligned, hsize*vsize entries. The sample table
+ * lives in a grow-only buffer of the context and is written in stream order in front of the launch. */
+rtc_status  rtc_render_ao_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                                 uint32_t flags, uint16_t *d_ao);
+/* [device] the same into HOST memory; synchronous; scratch is grow-only and owned by the context */
+rtc_status  rtc_render_ao(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                          uint32_t flags, uint16_t *ao_out);
+/* Compositing, in place: every component c of pixel i becomes c * (1.0 - strength * ((double)ao[i] / (double)n_samples)),
+ * f64 in that order. 0 <= strength <= 1 and n_samples >= 1, else RTC_ERR_ARG (NaN included); so are NULL pointers and a
+ * d_rgb that is not 8-byte aligned or a d_ao that is not 2-byte aligned. [host] normative; [device] one thread per pixel on
+ * the context's stream, the same bytes — every encoder can follow directly. */
+rtc_status  rtc_canvas_apply_ao(double *rgb, const uint16_t *ao, uint32_t n_samples, double strength, uint32_t width, uint32_t height);
+rtc_status  rtc_canvas_apply_ao_device(rtc_context *ctx, void *d_rgb, const void *d_ao, uint32_t n_samples, double strength,
+                                       uint32_t width, uint32_t height);
+/* Scenes whose camera asks for ambient occlusion. YAML: `add: camera` with `ao-radius` (> 0, or .inf) and, optionally,
+ * `ao-usteps` / `ao-vsteps` (integers, default 4, at most RTC_MAX_AO_SAMPLES samples in all; they need an `ao-radius`).
+ * These entries are rtc_scene_load_yaml_lens plus the AO record: *has_ao_out = 1 and *ao_out filled when the camera has any
+ * of those keys, else 0 and *ao_out zeroed. The keys ask for a pass; they change no other entry's result, so every other
+ * YAML entry loads such a scene and ignores them. */
+rtc_status  rtc_scene_load_yaml_ao(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                   struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                   rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                   struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out);
+rtc_status  rtc_scene_load_yaml_ao_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                        struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                        rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                        struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out);
+
 /* ==== float files: the f64 canvas and the AOV planes saved as data ==================== */
 /* Every writer above takes Color::scale'd 8-bit rows: components above 1.0 are clipped and a depth plane becomes a picture.
  * These three keep the numbers. Input: the f64 canvas, `rgb` = height*width*3 doubles, top row first (what rtc_render,

@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -312,6 +312,54 @@ def lens_ray(cam: RtcCamera, lens: RtcLens, x: int, y: int, k: int) -> np.ndarra
     return np.array(list(out))
 
 
+def ao(radius: float, usteps: int = 4, vsteps: int = 4) -> RtcAo:
+    """An ambient-occlusion pass for DeviceWorld.render_ao (rtc_ao, include/rtc.h): usteps x vsteps cosine-weighted rays per
+    pixel into the hemisphere over the centre ray's hit, each asking for something nearer than `radius` (math.inf:
+    unbounded). No jitter: the samples sit at the cell centres."""
+    a = RtcAo()
+    a.radius, a.usteps, a.vsteps = float(radius), int(usteps), int(vsteps)
+    _check(lib().rtc_ao_validate(C.byref(a)), "rtc_ao_validate")
+    return a
+
+
+def ao_expand(ao: RtcAo) -> np.ndarray:
+    """The pass's sample directions about the normal (0, 0, 1), an (n, 3) array in the order k = v*usteps + u (rtc_ao_expand)."""
+    dirs, n = np.empty((MAX_AO_SAMPLES, 3)), C.c_uint32(0)
+    _check(lib().rtc_ao_expand(C.byref(ao), dirs.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)), "rtc_ao_expand")
+    return dirs[:n.value].copy()
+
+
+def ao_ray(normal, over_point, local) -> np.ndarray:
+    """The ray of the sample direction `local` from `over_point` about `normal`: origin xyz, direction xyz (rtc_ao_ray)."""
+    out = (C.c_double * 6)()
+    _check(lib().rtc_ao_ray(Vec3(*[float(v) for v in normal]), Vec3(*[float(v) for v in over_point]), Vec3(*[float(v) for v in local]), out), "rtc_ao_ray")
+    return np.array(list(out))
+
+
+def ao_from_hits(hits, counts, width: int, height: int, mode: int = MODE_RENDER_ASYNC) -> np.ndarray:
+    """rtc_ao_from_hits: width * height hit records (an RtcHit array, row-major) and their occluded-sample counts packed into
+    the (height, width) uint16 plane, the mode rule included."""
+    c = np.ascontiguousarray(counts, dtype=np.uint16).reshape(-1)
+    if len(hits) != width * height or c.size != width * height:
+        raise ValueError("ao_from_hits needs width * height hit records and counts")
+    out = np.empty((height, width), dtype=np.uint16)
+    _check(lib().rtc_ao_from_hits(hits, c.ctypes.data_as(C.POINTER(C.c_uint16)), width, height, mode, out.ctypes.data_as(C.POINTER(C.c_uint16))),
+           "rtc_ao_from_hits")
+    return out
+
+
+def apply_ao(rgb: np.ndarray, ao_plane: np.ndarray, n_samples: int, strength: float = 1.0) -> np.ndarray:
+    """rtc_canvas_apply_ao: a copy of the (H, W, 3) f64 canvas with every component multiplied by
+    1 - strength * count / n_samples of its pixel."""
+    out = np.array(rgb, dtype=np.float64, order="C", copy=True)
+    a = np.ascontiguousarray(ao_plane, dtype=np.uint16)
+    if out.ndim != 3 or out.shape[2] != 3 or a.shape != out.shape[:2]:
+        raise ValueError("apply_ao needs an (H, W, 3) canvas and an (H, W) plane")
+    _check(lib().rtc_canvas_apply_ao(out.ctypes.data_as(C.POINTER(C.c_double)), a.ctypes.data_as(C.POINTER(C.c_uint16)), int(n_samples), float(strength),
+                                     out.shape[1], out.shape[0]), "rtc_canvas_apply_ao")
+    return out
+
+
 def projection(kind, width: float = 0.0, h_span: float = 2.0 * math.pi, v_span: float = math.pi) -> RtcProjection:
     """A projection for DeviceWorld.render_projection (rtc_projection, include/rtc.h). kind "orthographic" (or
     PROJ_ORTHOGRAPHIC): parallel rays, `width` the world-space width of the view. kind "panorama" (PROJ_PANORAMA): the
@@ -448,6 +496,27 @@ def load_yaml_lens(text: str | None = None, path: str | None = None):
         w.shapes.append(s)
     lib().rtc_free(shapes)
     return w, cam, (ln if has.value else None)
+
+
+def load_yaml_ao(text: str | None = None, path: str | None = None):
+    """load_yaml_lens for scenes whose camera may ask for ambient occlusion (ao-radius / ao-usteps / ao-vsteps):
+    -> (World, RtcCamera, RtcLens or None, RtcAo or None)."""
+    shapes = C.POINTER(RtcShape)()
+    n = C.c_uint32(0)
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
+    err = C.create_string_buffer(512)
+    ln, has, a, has_a = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
+    fn = lib().rtc_scene_load_yaml_ao_file if path is not None else lib().rtc_scene_load_yaml_ao
+    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
+            err, 512, C.byref(ln), C.byref(has), C.byref(a), C.byref(has_a))
+    _check(st, "rtc_scene_load_yaml_ao", err.value.decode(errors="replace"))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
+    for i in range(n.value):
+        s = RtcShape()
+        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
+        w.shapes.append(s)
+    lib().rtc_free(shapes)
+    return w, cam, (ln if has.value else None), (a if has_a.value else None)
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
@@ -1341,6 +1410,12 @@ class Context:
         _check(lib().rtc_aov_view_rgb8_device(self._h, _aov_view_id(view), C.byref(b), width, height, near, far, n_lights, C.c_void_p(d_out)),
                "rtc_aov_view_rgb8_device")
 
+    def apply_ao_device(self, d_rgb: int, d_ao: int, n_samples: int, strength: float, width: int, height: int) -> None:
+        """apply_ao in place on an f64 canvas and a uint16 plane in DEVICE memory, enqueued on the context's stream
+        (rtc_canvas_apply_ao_device): the same bytes as the host function."""
+        _check(lib().rtc_canvas_apply_ao_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_ao), int(n_samples), float(strength), width, height),
+               "rtc_canvas_apply_ao_device")
+
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
         return Shutter(self)
@@ -1569,6 +1644,17 @@ class DeviceWorld:
         """The same into DEVICE buffers ({plane: address}; rtc_render_aov_device): enqueued on the context's stream."""
         b = _aov_buffers(pointers)
         _check(lib().rtc_render_aov_device(self.ctx._h, self._h, C.byref(cam), mode, flags, C.byref(b)), "rtc_render_aov_device")
+
+    def render_ao(self, cam: RtcCamera, ao: RtcAo, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> np.ndarray:
+        """The ambient-occlusion plane (rtc_render_ao): a (vsize, hsize) uint16 array, per pixel the number of the pass's
+        samples that meet something within its radius; 0 where the centre ray misses."""
+        out = np.empty((cam.vsize, cam.hsize), dtype=np.uint16)
+        _check(lib().rtc_render_ao(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, out.ctypes.data_as(C.POINTER(C.c_uint16))), "rtc_render_ao")
+        return out
+
+    def render_ao_device(self, cam: RtcCamera, ao: RtcAo, d_ao: int, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+        """The same into a DEVICE buffer of vsize * hsize uint16 (rtc_render_ao_device): enqueued on the context's stream."""
+        _check(lib().rtc_render_ao_device(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.c_void_p(d_ao)), "rtc_render_ao_device")
 
     def color_at(self, rays: np.ndarray, remaining: int = 5, want_hits: bool = False, flags: int = 0):
         """World::color_at for an (n, 6) array of rays; returns rgb (n,3) [and the rtc_hit array]."""
@@ -1954,7 +2040,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
            "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",

@@ -15,6 +15,7 @@ GROUP_ID_BYTES = 128
 MAX_LIGHTS = 8
 MAX_LIGHT_SAMPLES = 256
 MAX_LENS_SAMPLES = 256
+MAX_AO_SAMPLES = 256
 PROJ_ORTHOGRAPHIC, PROJ_PANORAMA = 1, 2  # rtc_projection::kind
 MAX_SHUTTER_SAMPLES = 256
 SHUTTER_RING = 8
@@ -44,6 +45,10 @@ class RtcAreaLight(C.Structure):
 
 class RtcLens(C.Structure):
     _fields_ = [("aperture", C.c_double), ("focal_distance", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
+
+
+class RtcAo(C.Structure):
+    _fields_ = [("radius", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
 
 
 class RtcProjection(C.Structure):
@@ -125,7 +130,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24 and C.sizeof(RtcProjection) == 32
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
-assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64
+assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64 and C.sizeof(RtcAo) == 16
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -341,6 +346,20 @@ PROTOTYPES = {
     "rtc_render_aov": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), U32, U32, C.POINTER(RtcAovBuffers)]),
     "rtc_aov_view_rgb8": (C.c_int32, [U32, C.POINTER(RtcAovBuffers), U32, U32, D, D, U32, C.POINTER(C.c_uint8)]),
     "rtc_aov_view_rgb8_device": (C.c_int32, [VP, U32, C.POINTER(RtcAovBuffers), U32, U32, D, D, U32, VP]),
+    "rtc_ao_validate": (C.c_int32, [C.POINTER(RtcAo)]),
+    "rtc_ao_expand": (C.c_int32, [C.POINTER(RtcAo), PD, C.POINTER(U32)]),
+    "rtc_ao_ray": (C.c_int32, [PD, PD, PD, PD]),
+    "rtc_ao_from_hits": (C.c_int32, [C.POINTER(RtcHit), C.POINTER(C.c_uint16), U32, U32, U32, C.POINTER(C.c_uint16)]),
+    "rtc_render_ao_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, VP]),
+    "rtc_render_ao": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(C.c_uint16)]),
+    "rtc_canvas_apply_ao": (C.c_int32, [PD, C.POINTER(C.c_uint16), U32, D, U32, U32]),
+    "rtc_canvas_apply_ao_device": (C.c_int32, [VP, VP, VP, U32, D, U32, U32]),
+    "rtc_scene_load_yaml_ao": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                           C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                           C.POINTER(RtcAo), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_ao_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                C.POINTER(RtcAo), C.POINTER(U32)]),
     "rtc_float_format_for_name": (C.c_int32, [C.c_char_p, C.POINTER(U32)]),
     "rtc_float_format": (C.c_size_t, [U32, C.POINTER(RtcFloatPlanes), U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
     "rtc_canvas_save_f64": (C.c_int32, [C.c_char_p, PD, U32, U32]),

@@ -240,6 +240,15 @@ rtc_status rtc_lens_validate(const rtc_lens *lens) {
     return RTC_OK;
 }
 
+// (here, beside the other records the scene loader validates; the rest of the ambient-occlusion pass: host_ao.cpp)
+rtc_status rtc_ao_validate(const rtc_ao *ao) {
+    if (!ao) return RTC_ERR_ARG;
+    if (!(ao->radius > 0.)) return RTC_ERR_ARG; // (NaN fails the test; +inf passes: unbounded)
+    if (ao->usteps == 0u || ao->vsteps == 0u) return RTC_ERR_ARG;
+    if ((uint64_t)ao->usteps * ao->vsteps > RTC_MAX_AO_SAMPLES) return RTC_ERR_ARG;
+    return RTC_OK;
+}
+
 // The normative thin-lens ray (include/rtc.h): camera.rs:64-76 with the origin moved over the lens and the target on the
 // plane in focus; mul, add and div in the stated order (this file is compiled with -ffp-contract=off).
 rtc_status rtc_lens_ray(const rtc_camera *cam, const rtc_lens *lens, uint32_t x, uint32_t y, uint32_t k, double ray[6]) {

@@ -19,6 +19,7 @@
 #include "rtc.h"
 
 #include <cmath>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -349,6 +350,8 @@ struct Scene {
     int lens_line = 0;                  // line of the camera entry that has lens keys, 0: none
     rtc_projection proj{};              // the camera's projection (include/rtc.h); zeroed without projection keys
     int proj_line = 0;                  // line of the camera entry that has projection keys, 0: none
+    rtc_ao ao{};                        // the camera's ambient-occlusion pass (include/rtc.h); zeroed without ao keys
+    int ao_line = 0;                    // line of the camera entry that has ao keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -448,6 +451,28 @@ void interpret(const Node &root, Scene &sc) {
                     fail(e.line, "too many lens samples: lens-usteps x lens-vsteps is at most " + std::to_string(RTC_MAX_LENS_SAMPLES));
                 if (sc.proj_line) fail(e.line, "a camera has a lens or a projection, not both");
             }
+            // ambient occlusion (include/rtc.h): ao-radius / ao-usteps / ao-vsteps; asks for a pass, changes no ray of the frame
+            sc.ao = rtc_ao{};
+            sc.ao_line = 0;
+            const Node *aor = e.get("ao-radius"), *aou = e.get("ao-usteps"), *aov = e.get("ao-vsteps");
+            if (aor || aou || aov) {
+                sc.ao_line = e.line;
+                if (!aor) fail(e.line, "ao-usteps / ao-vsteps need an ao-radius");
+                const bool unbounded = aor->kind == Node::Scalar && (aor->scalar == ".inf" || aor->scalar == "+.inf"); // YAML's spelling
+                sc.ao.radius = unbounded ? std::numeric_limits<double>::infinity() : as_number(aor, "ao-radius");
+                auto steps = [&](const Node *n, const char *key) {
+                    if (!n) return 4u;
+                    const double v = as_number(n, key);
+                    if (!(v >= 1 && v <= RTC_MAX_AO_SAMPLES) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                        fail(n->line, std::string(key) + " must be an integer in 1.." + std::to_string(RTC_MAX_AO_SAMPLES));
+                    return static_cast<uint32_t>(v);
+                };
+                sc.ao.usteps = steps(aou, "ao-usteps");
+                sc.ao.vsteps = steps(aov, "ao-vsteps");
+                if (!(sc.ao.radius > 0.)) fail(aor->line, "ao-radius must be a number > 0 (.inf: unbounded)");
+                if (rtc_ao_validate(&sc.ao) != RTC_OK)
+                    fail(e.line, "too many ambient-occlusion samples: ao-usteps x ao-vsteps is at most " + std::to_string(RTC_MAX_AO_SAMPLES));
+            }
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
             if (const Node *ss = e.get("shutter-samples")) {
@@ -536,10 +561,12 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
                             uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, bool first_only,
                             rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr,
                             rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr,
-                            rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr) {
+                            rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr, rtc_ao *ao_out = nullptr,
+                            uint32_t *has_ao_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
+    if ((ao_out == nullptr) != (has_ao_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -597,6 +624,10 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
             *proj_out = sc.proj;
             *has_projection_out = sc.proj_line ? 1u : 0u;
         }
+        if (ao_out) {
+            *ao_out = sc.ao;
+            *has_ao_out = sc.ao_line ? 1u : 0u;
+        }
         return RTC_OK;
     } catch (const ParseError &e) {
         set_err(errbuf, errbuf_len, e.what());
@@ -652,6 +683,14 @@ rtc_status rtc_scene_load_yaml_projection(const char *text, rtc_shape **shapes_o
     if (!lens_out || !has_lens_out || !proj_out || !has_projection_out) return RTC_ERR_ARG;
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
                      lens_out, has_lens_out, nullptr, nullptr, nullptr, proj_out, has_projection_out);
+}
+
+rtc_status rtc_scene_load_yaml_ao(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out, uint32_t lights_cap,
+                                  uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, rtc_lens *lens_out,
+                                  uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out) {
+    if (!lens_out || !has_lens_out || !ao_out || !has_ao_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out, nullptr, nullptr, nullptr, nullptr, nullptr, ao_out, has_ao_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -722,6 +761,16 @@ rtc_status rtc_scene_load_yaml_projection_file(const char *path, rtc_shape **sha
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_projection(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                           lens_out, has_lens_out, proj_out, has_projection_out);
+}
+
+rtc_status rtc_scene_load_yaml_ao_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                       uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                       size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_ao(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                  lens_out, has_lens_out, ao_out, has_ao_out);
 }
 
 } // extern "C"

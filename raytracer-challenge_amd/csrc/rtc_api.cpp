@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rtc.h"
+#include "rtc_ao.h"
 #include "rtc_aov.h"
 #include "rtc_device.h"
 #include "rtc_internal.h"
@@ -1762,6 +1763,91 @@ rtc_status rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_a
     V.index = d->index; V.depth = d->depth; V.normal = d->normal; V.shadow = d->shadow;
     V.out = static_cast<unsigned char *>(d_rgb8);
     HIP_TRY(rtc_launch_aov_view(&V, ctx->stream));
+    return RTC_OK;
+}
+
+// ---- ambient occlusion (include/rtc.h) ------------------------------------------------------------------------------------
+// The sample table of `ao`'s grid in the context's buffer, for work enqueued next on the context's stream.
+static rtc_status ao_table(rtc_context *ctx, const rtc_ao *ao) {
+    const rtc_status rs = ctx->d_ao_dirs.reserve(3u * RTC_MAX_AO_SAMPLES, &ctx->render_allocs);
+    if (rs != RTC_OK) return rs;
+    if (ctx->ao_usteps == ao->usteps && ctx->ao_vsteps == ao->vsteps) return RTC_OK;
+    // another grid: launches in flight read the old table (stream order covers the device side) and an earlier copy may
+    // still read ao_host
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->ao_usteps = ctx->ao_vsteps = 0u;
+    uint32_t n = 0;
+    const rtc_status es = rtc_ao_expand(ao, ctx->ao_host, &n);
+    if (es != RTC_OK) return es;
+    HIP_TRY(hipMemcpyAsync(ctx->d_ao_dirs.get(), ctx->ao_host, sizeof(double) * 3u * n, hipMemcpyHostToDevice, ctx->stream));
+    ctx->ao_usteps = ao->usteps;
+    ctx->ao_vsteps = ao->vsteps;
+    return RTC_OK;
+}
+
+rtc_status rtc_render_ao_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                                uint32_t flags, uint16_t *d_ao) {
+    if (check_render_args(ctx, w, cam, mode, d_ao, nullptr) != RTC_OK || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
+    if ((size_t)d_ao % 2u != 0) return RTC_ERR_ARG;
+    if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
+    HIP_TRY(hipSetDevice(ctx->device));
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status hs = current_gen(w, &gen);
+    if (hs != RTC_OK) return hs;
+    rtc_world::Gen &G = *gen;
+    LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_AOV, flags); // k_aov's plan: the same grid, no dynamic LDS
+    in.hsize = cam->hsize; in.vsize = cam->vsize; in.mode = mode;
+    LaunchPlan plan;
+    rtc_plan_launch(in, plan);
+    if (plan.status != RTC_OK) return (rtc_status)plan.status;
+    const rtc_status ts = ao_table(ctx, ao);
+    if (ts != RTC_OK) return ts;
+    RenderParams P;
+    planned_params(ctx, w, G, plan, P);
+    fill_camera(P, cam);
+    AoParams A;
+    std::memset(&A, 0, sizeof A);
+    A.cam = P.views[0];
+    A.W = cam->hsize;
+    A.H = cam->vsize;
+    A.mode = mode;
+    A.tiles_x = plan.grid_x;
+    A.n = G.n;
+    A.ngroups = G.ngroups;
+    A.pre_limit = G.pre_limit;
+    A.radius = ao->radius;
+    A.nsamples = ao->usteps * ao->vsteps;
+    A.out = d_ao;
+    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
+    HIP_TRY(rtc_launch_ao(&A, ctx->d_ao_dirs.get(), &P, plan.src, ctx->stream));
+    HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
+    return RTC_OK;
+}
+
+rtc_status rtc_render_ao(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
+                         uint16_t *ao_out) {
+    if (!ctx || !w || !cam || !ao_out || w->ctx != ctx || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
+    if (cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)cam->hsize * cam->vsize;
+    const rtc_status st = ctx->d_ao.reserve(px, &ctx->render_allocs);
+    if (st != RTC_OK) return st;
+    const rtc_status ls = rtc_render_ao_device(ctx, w, cam, ao, mode, flags, ctx->d_ao.get());
+    if (ls != RTC_OK) return ls;
+    rtc_status out = RTC_OK;
+    if (hipMemcpyAsync(ao_out, ctx->d_ao.get(), sizeof(uint16_t) * px, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    return out;
+}
+
+rtc_status rtc_canvas_apply_ao_device(rtc_context *ctx, void *d_rgb, const void *d_ao, uint32_t n_samples, double strength, uint32_t width,
+                                      uint32_t height) {
+    if (!ctx || !d_rgb || !d_ao || rtc_ao_apply_check(n_samples, strength) != RTC_OK) return RTC_ERR_ARG;
+    if (((size_t)d_rgb % sizeof(double)) != 0 || ((size_t)d_ao % 2u) != 0) return RTC_ERR_ARG;
+    const size_t n = (size_t)width * height;
+    if (n == 0) return RTC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(rtc_launch_apply_ao(static_cast<double *>(d_rgb), static_cast<const uint16_t *>(d_ao), n, n_samples, strength, ctx->stream));
     return RTC_OK;
 }
 

@@ -233,6 +233,17 @@ struct AovViewParams {
     const uint16_t *shadow;
     unsigned char *out;
 };
+// k_ao (rtc_render_ao_device): the ambient-occlusion plane of a W x H frame. The sample table (3 doubles per sample, the
+// host's rtc_ao_expand) is a kernel argument of its own, so that its reads are scalar loads.
+struct AoParams {
+    DevCamera cam;
+    uint32_t W, H, mode, tiles_x;
+    uint32_t n, ngroups;       // the World's objects and groups of 64 (for_each_object reads them by these names)
+    double pre_limit;          // ... and the limit of its prefilter records (DevPre)
+    double radius;             // rtc_ao::radius (+inf: unbounded)
+    uint32_t nsamples, _pad;   // 1..RTC_MAX_AO_SAMPLES
+    uint16_t *out;
+};
 
 struct RenderParams {
     const DevIsect *isect;

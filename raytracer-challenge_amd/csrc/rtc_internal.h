@@ -34,6 +34,13 @@ struct rtc_context {
     DevBuf<double> d_canvas;
     DevBuf<unsigned char> d_canvas8; // the same for rtc_render_rgb8 (3 B/pixel) and rtc_render_rgba8 (4 B/pixel)
     DevBuf<unsigned char> d_aov;     // the planes of rtc_render_aov (host-buffer entry point), carved in order of alignment
+    // Ambient occlusion (rtc_render_ao*, include/rtc.h): the sample table of the most recent launch's grid, the host's
+    // rtc_ao_expand, copied in stream order in front of the launch when the grid changes (one grid in a loop: one copy);
+    // `ao_host` is the copy's source and is rewritten only behind a wait for the stream. The radius is a kernel argument.
+    DevBuf<double> d_ao_dirs;        // room for RTC_MAX_AO_SAMPLES directions, allocated by the first AO launch
+    double ao_host[3u * RTC_MAX_AO_SAMPLES] = {};
+    uint32_t ao_usteps = 0, ao_vsteps = 0; // the grid d_ao_dirs holds; 0: none yet
+    DevBuf<uint16_t> d_ao;           // the plane of rtc_render_ao (host-buffer entry point)
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -202,6 +209,9 @@ extern "C" void rtc_projection_ortho_terms(uint32_t hsize, uint32_t vsize, doubl
 extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
                                      hipStream_t stream);
 extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t stream);
+// k_ao / k_apply_ao (rtc_kernels.hip). `P`: the World's tables only (fill_world); `dirs`: the sample table in device memory.
+extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, hipStream_t stream);
+extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_t n, uint32_t n_samples, double strength, hipStream_t stream);
 extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
 // k_average_over (rtc_shutter.hip): one pass of Color::average_over over whole canvases. Adds frames[f * stride + i], f = 0..nf-1
 // in that order, to the carried sum (sum_in, NULL: 0.0) for i < count. divisor == 0: stores the sum to f64_out. Otherwise the

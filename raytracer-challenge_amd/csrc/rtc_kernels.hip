@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "rtc.h"
+#include "rtc_ao.h"
 #include "rtc_aov.h"
 #include "rtc_bands.h"
 #include "rtc_device.h"
@@ -2640,6 +2641,115 @@ __global__ void __launch_bounds__(256) k_aov_view(const AovViewParams V) {
     V.out[3u * i + 2u] = o[2];
 }
 
+// ---- ambient occlusion (rtc_render_ao*, include/rtc.h) ---------------------------------------------------------------
+// k_aov's shape — one wave = one 8x8 pixel tile = one workgroup, the same primary pass and compute_vectors, one pixel per
+// lane stored — with, in place of the light loop, a wave-uniform loop over the samples of the host's table: sample k's local
+// direction is read by a uniform address (scalar loads, SGPRs), each lane turns it about its own normal (rtc_ao.h: the
+// header's arithmetic, no sin or cos here) and the bounded any-hit walk counts the lanes that meet something with t < radius.
+// The tangent frame is built once per pixel, in front of the loop (its one division). Lanes without a hit carry
+// pending = false through every walk: the walks are wave-level code and stay converged.
+// Cull sources: per sample a bundle over the lanes' rays, origins per lane (apex = the axis lane's over_point, rho the spread
+// of the others around it). It is make_bundle's unbounded per-lane-origin form with the reach put in afterwards, not its
+// REACH form: that one is for segments the exact test walks from the far end (spread = reach) and gives up on an unbounded
+// reach, where this pass starts every exact ray at its lane's origin (spread = rho) and radius = +inf still has a cone to
+// cull with. Where a tile's normals diverge the cone passes 0.98 / the axis dot falls under 0.2 and the bundle goes off:
+// every object is a candidate, which is correct and slower. Results do not depend on SRC.
+// The per-lane prefilter (ray_touches_pre: it takes d.d, so the direction need not be unit) stands in front of the exact tests
+// in the one-level walks too, where k_aov's shadow passes have it for two-level Worlds only: a shadow bundle always holds, an AO
+// bundle is off wherever a tile's normals diverge, and then the filter is the only cull there is. RTC_AO_LANE_FILTER_ONE_LEVEL=0
+// takes it out (A/B: north star, 1080p, 0.35 -> 0.22 ms at 4 samples, 4.5 -> 2.6 ms at 64; profiles/ao_lane_filter_ab.log).
+#ifndef RTC_AO_LANE_FILTER_ONE_LEVEL
+#define RTC_AO_LANE_FILTER_ONE_LEVEL 1
+#endif
+template <int SRC>
+__global__ void __launch_bounds__(64, RTC_WAVES_PER_SIMD)
+k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
+     const DevShade *__restrict__ t_shade, const DevBound *__restrict__ t_bound, const DevIsect *__restrict__ t_isect_s,
+     const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s, const uint32_t *__restrict__ t_orig_s,
+     const DevBound *__restrict__ t_gbound, const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s) {
+    static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "AO launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
+    Tables T{};
+    T.isect = t_isect; T.kind = t_kind; T.shade = t_shade; T.bound = t_bound;
+    T.isect_s = t_isect_s; T.kind_s = t_kind_s; T.bound_s = t_bound_s; T.orig_s = t_orig_s; T.gbound = t_gbound;
+    T.pre = t_pre; T.pre_s = t_pre_s;
+    const LdsView L{};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
+    const bool in_range = px < A.W && py < A.H;
+    // Camera::render leaves the last row and column untouched (camera.rs:120-121): they get the miss value
+    const bool traced = in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H));
+
+    // ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76
+    V3 cam_origin = xpoint(A.cam.vinv, mk(0., 0., 0.));
+    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
+    const V3 ro = cam_origin;
+    const V3 rd = primary_dir(A.cam, cam_origin, px, py);
+
+    // ---- World::intersect + get_hit, streaming form (k_aov's primary pass) ----
+    double best = __builtin_inf();
+    int hidx = -1, hroot = 0;
+    Bundle B{};
+    B.off = true;
+    if constexpr (IS_CULL(SRC)) {
+        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
+    }
+    if constexpr (SRC == SRC_CULL2)
+        for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
+    else
+        for_each_object<SRC>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
+    const bool hit = traced && hidx >= 0;
+
+    // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96): normal and over_point; then the tangent frame ----
+    V3 normal = mk(0., 0., 0.), over = mk(0., 0., 0.), tv = mk(0., 0., 0.), sv = mk(0., 0., 0.);
+    if (hit) {
+        const V3 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
+        const DevShade *S = T.shade + hidx;
+        const double *m_obj = T.isect[hidx].m;
+        normal = shape_normal(S, m_obj, point);
+        if (vdot(normal, vneg(rd)) < 0.0) normal = vneg(normal);
+        over = vadd(point, vmul(normal, RTC_EPSILON));
+        const double nn[3] = {normal.x, normal.y, normal.z};
+        double t3[3], s3[3];
+        rtc_ao_frame(nn, t3, s3);
+        tv = mk(t3[0], t3[1], t3[2]);
+        sv = mk(s3[0], s3[1], s3[2]);
+    }
+
+    // ---- one bounded any-hit pass per sample, in the table's order: how many meet something within the radius ----
+    uint32_t count = 0u;
+    const double radius = A.radius;
+    const uint32_t ns = A.nsamples;
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double lx = t_dirs[3u * k], ly = t_dirs[3u * k + 1u], lz = t_dirs[3u * k + 2u]; // (k is wave-uniform: scalar loads)
+        const V3 dir = mk(rtc_ao_dir(tv.x, sv.x, normal.x, lx, ly, lz), rtc_ao_dir(tv.y, sv.y, normal.y, lx, ly, lz),
+                          rtc_ao_dir(tv.z, sv.z, normal.z, lx, ly, lz));
+        bool pending = hit, occluded = false;
+        Bundle Bk{};
+        Bk.off = true;
+        if constexpr (IS_CULL(SRC)) {
+            if (ballot(hit) != 0ull) {
+                Bk = make_bundle<false, false>(hit, over, over, dir, 0.);
+                // the reach, rounded up as make_bundle's REACH form rounds it (f32, 1e-4 relative: the direction is unit to a few ulp)
+                if (radius < 1e30) Bk.tmax = uniform_f64((double)(fmaxf(0.f, (float)radius) * 1.0001f + 1e-30f));
+            }
+        }
+        for_each_object<SRC, SRC == SRC_CULL2 || (SRC == SRC_CULL && RTC_AO_LANE_FILTER_ONE_LEVEL)>(A, T, L, pending, Bk, AnyHit{pending, over, dir, radius, occluded}, over, dir);
+        if (occluded) ++count;
+    }
+
+    if (in_range) A.out[(size_t)py * A.W + px] = (uint16_t)count; // one pixel per lane: plain vector stores
+}
+
+// rtc_canvas_apply_ao on the device: one thread per pixel, rtc_ao.h's factor
+__global__ void __launch_bounds__(256) k_apply_ao(double *__restrict__ rgb, const uint16_t *__restrict__ ao, size_t n, uint32_t n_samples, double strength) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double f = rtc_ao_factor(ao[i], n_samples, strength);
+    rgb[3u * i] = rgb[3u * i] * f;
+    rgb[3u * i + 1u] = rgb[3u * i + 1u] * f;
+    rgb[3u * i + 2u] = rgb[3u * i + 2u] * f;
+}
+
 // ---- launch dispatch (rtc_launch_aov, rtc_launch_trace) -----------------------------------------------------------
 // The runtime `src` as a compile-time constant: f(std::integral_constant<int, SRC_x>) for the one of `ALLOWED` it equals.
 template <int... ALLOWED, class F> static hipError_t with_src(int src, F &&f) {
@@ -2686,6 +2796,28 @@ extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t st
     const size_t blocks = (V->n + 255u) / 256u;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_aov_view, dim3((uint32_t)blocks), dim3(256), 0, stream, *V);
+    return hipGetLastError();
+}
+
+// `P`: the World's tables only (fill_world). `dirs`: A->nsamples directions in device memory. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
+extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, hipStream_t stream) {
+    if (A->W == 0u || A->H == 0u || A->tiles_x != (A->W + 7u) / 8u || A->out == nullptr || dirs == nullptr) return hipErrorInvalidValue;
+    if (A->nsamples == 0u || A->nsamples > RTC_MAX_AO_SAMPLES) return hipErrorInvalidValue;
+    const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
+    if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)tiles64;
+    return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+        hipLaunchKernelGGL((k_ao<S()>), dim3(tiles), dim3(64), 0, stream, *A, dirs, P->isect, P->kind, P->shade, P->bound, P->isect_s, P->kind_s,
+                           P->bound_s, P->orig_s, P->gbound, P->pre, P->pre_s);
+        return hipGetLastError();
+    });
+}
+
+extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_t n, uint32_t n_samples, double strength, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255u) / 256u;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_apply_ao, dim3((uint32_t)blocks), dim3(256), 0, stream, rgb, ao, n, n_samples, strength);
     return hipGetLastError();
 }
 

@@ -190,6 +190,13 @@ class Canvas { // canvas.rs:16-109
     bool is_imgbuf() const { return pixels.empty() && !rgba8.empty(); }
     void write_pixel(uint32_t x, uint32_t y, Color c) { double *p = at(x, y); p[0] = c.red; p[1] = c.green; p[2] = c.blue; }
     Color get_pixel(uint32_t x, uint32_t y) const { const double *p = const_cast<Canvas *>(this)->at(x, y); return {p[0], p[1], p[2]}; }
+    // Ambient occlusion composited in place (rtc_canvas_apply_ao, include/rtc.h): every component of pixel i times
+    // 1 - strength * ao[i] / n_samples. `ao` is Camera::render_ao's `shadow` plane and n_samples its n_lights. f64 canvases only.
+    void apply_ao(const std::vector<uint16_t> &ao, uint32_t n_samples, double strength = 1.0) {
+        if (pixels.size() != static_cast<size_t>(width) * height * 3 || ao.size() != static_cast<size_t>(width) * height)
+            throw Panic(RTC_ERR_ARG, "Canvas::apply_ao: an f64 Canvas and a plane of its size are needed");
+        check(rtc_canvas_apply_ao(pixels.data(), ao.data(), n_samples, strength, width, height), "Canvas::apply_ao");
+    }
     void write_to_file_simple(const std::string &file_name) const { // canvas.rs:86-109
         if (is_imgbuf()) { // the PPM is Color::scale's (gamma 1): only an RGBA frame of gamma 1 holds those bytes
             if (rgba8_gamma != 1.0f) throw Panic(RTC_ERR_ARG, "Canvas::write_to_file_simple: the Canvas holds RGBA at gamma != 1 (Camera::render_rgba8)");
@@ -547,6 +554,12 @@ class Camera { // camera.rs:17-160
     // a lens or a shutter has no AOV form (RTC_ERR_UNSUPPORTED).
     Aov render_aov(const World &w) const { return run_aov(w, RTC_MODE_RENDER); }
     Aov render_async_aov(const World &w) const { return run_aov(w, RTC_MODE_RENDER_ASYNC); }
+    // The ambient-occlusion plane of the same frame (rtc_render_ao, include/rtc.h): an Aov whose `shadow` plane holds, per
+    // pixel, how many of ao.usteps x ao.vsteps hemisphere rays from the centre ray's hit meet something within ao.radius,
+    // and whose n_lights is that sample count — so Aov::view(Aov::SHADOW) is the AO picture and save_exr stores the counts.
+    // The other planes are empty. A lens, a shutter or a projection has no AO form (RTC_ERR_UNSUPPORTED).
+    Aov render_ao(const World &w, const rtc_ao &ao) const { return run_ao(w, ao, RTC_MODE_RENDER); }
+    Aov render_async_ao(const World &w, const rtc_ao &ao) const { return run_ao(w, ao, RTC_MODE_RENDER_ASYNC); }
 
   private:
     Aov run_aov(const World &w, uint32_t mode) const {
@@ -563,6 +576,19 @@ class Camera { // camera.rs:17-160
         a.n_lights = rtc_world_light_count(up.w);
         const rtc_aov_buffers b = a.buffers();
         check(rtc_render_aov(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, &b), "Camera::render_aov");
+        return a;
+    }
+    Aov run_ao(const World &w, const rtc_ao &ao, uint32_t mode) const {
+        if (has_lens_ || shutter_ || has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_ao with a lens, a shutter or a projection");
+        check(rtc_ao_validate(&ao), "Camera::render_ao");
+        rtc_camera c = flat_;
+        c.samples = antialiasing_samples;
+        Aov a;
+        a.width = hsize; a.height = vsize;
+        a.n_lights = ao.usteps * ao.vsteps;
+        a.shadow.assign(static_cast<size_t>(hsize) * vsize, 0);
+        World::Uploaded up(w);
+        check(rtc_render_ao(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, a.shadow.data()), "Camera::render_ao");
         return a;
     }
     Canvas run(const World &w, uint32_t mode) const {

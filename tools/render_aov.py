@@ -1,12 +1,15 @@
 """Render a YAML scene and what its pixels saw (the AOV planes, include/rtc.h "arbitrary output variables"):
-    python tools/render_aov.py SCENE.yml OUTDIR [--near N --far F] [--exr [PLANES]]
+    python tools/render_aov.py SCENE.yml OUTDIR [--near N --far F] [--exr [PLANES]] [--ao [RADIUS,USTEPS,VSTEPS]] [--ao-strength S]
 writes OUTDIR/beauty.png (the colour frame) and depth.png, normal.png, index.png, shadow.png (rtc_aov_view_rgb8's pictures of
 the planes). Colour frame, planes and pictures stay in device memory; every file is encoded there (ImageEncoder.encode_device)
 and only the finished files cross PCIe — plus, when --near / --far are not both given, the depth plane, whose smallest and
 largest finite value they default to. --exr also writes OUTDIR/frame.exr: ONE multi-channel OpenEXR file of data, not pictures —
 the f64 colour frame as HALF R, G, B plus the planes asked for (a comma-separated list of depth, normal, point, index,
 shadow; all five when none is named) as Z, N.*, P.*, id and shadow channels (FloatEncoder.encode_device, include/rtc.h
-"float files"). Needs an MI355X (there is no CPU path)."""
+"float files"). --ao also renders the ambient-occlusion plane (include/rtc.h "ambient occlusion") — with the pass the scene's
+camera asks for (ao-radius / ao-usteps / ao-vsteps) or the one given here — and writes OUTDIR/ao.png, the plane seen as a shadow
+plane (white: open, black: every sample occluded), and OUTDIR/beauty_ao.png, the colour frame with every pixel multiplied by
+1 - S * count / samples (rtc_canvas_apply_ao_device; S = --ao-strength, default 1), both made on the device. Needs an MI355X (there is no CPU path)."""
 import argparse
 import sys
 from pathlib import Path
@@ -23,12 +26,23 @@ def main(argv):
     ap.add_argument("--near", type=float, default=None)
     ap.add_argument("--far", type=float, default=None)
     ap.add_argument("--exr", nargs="?", const="depth,normal,point,index,shadow", default=None, metavar="PLANES")
+    ap.add_argument("--ao", nargs="?", const="", default=None, metavar="RADIUS,USTEPS,VSTEPS")
+    ap.add_argument("--ao-strength", type=float, default=1.0)
     args = ap.parse_args(argv[1:])
     rtc = package()
     abi = __import__("importlib").import_module(rtc.__name__ + ".abi")
     import numpy as np
     import torch
     world, cam = rtc.load_yaml(path=args.scene)
+    ao = None
+    if args.ao is not None:
+        if args.ao:
+            radius, usteps, vsteps = args.ao.split(",")
+            ao = rtc.ao(float(radius), int(usteps), int(vsteps))
+        else:
+            ao = rtc.load_yaml_ao(path=args.scene)[3]
+            if ao is None:
+                ap.error("--ao: the scene's camera has no ao-radius; give RADIUS,USTEPS,VSTEPS")
     width, height = cam.hsize, cam.vsize
     out = Path(args.outdir)
     out.mkdir(parents=True, exist_ok=True)
@@ -67,6 +81,18 @@ def main(argv):
         sizes["frame.exr"] = (out / "frame.exr").write_bytes(
             fenc.encode_device("exr", rgb.data_ptr(), width, height, {p: dev[p].data_ptr() for p in wanted}, "half"))
         fenc.close()
+    if ao is not None:
+        n = ao.usteps * ao.vsteps
+        rgb = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
+        rgba = torch.zeros(width * height * 4, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        dw.render_ao_device(cam, ao, dev["shadow"].data_ptr())   # (the shadow plane's pictures are written: its buffer is free)
+        ctx.aov_view_device("shadow", {"shadow": dev["shadow"].data_ptr()}, width, height, pic.data_ptr(), n_lights=n)
+        sizes["ao"] = (out / "ao.png").write_bytes(enc.encode_device("png", pic.data_ptr(), width, height, 3))
+        dw.render_rows(cam, 0, height, rgb.data_ptr())
+        ctx.apply_ao_device(rgb.data_ptr(), dev["shadow"].data_ptr(), n, args.ao_strength, width, height)
+        ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
+        sizes["beauty_ao"] = (out / "beauty_ao.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
     hits = int((dev["index"] >= 0).sum().item())
     print(f"{out}: {width}x{height}, {len(world)} shapes, {n_lights} light sample(s), {hits} of {width * height} pixels hit, "
           f"depth {near:.6g} .. {far:.6g}; bytes: " + ", ".join(f"{k if '.' in k else k + '.png'} {v}" for k, v in sizes.items()))
