@@ -1440,6 +1440,80 @@ rtc_status  rtc_scene_load_yaml_ao_file(const char *path, rtc_shape **shapes_out
                                         rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
                                         struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out);
 
+/* ==== colour bleeding: one bounce of light gathered over the ambient-occlusion fan ============ */
+/* The light that reaches a pixel's hit by way of ONE other surface: a red sphere on a white floor tints the floor. The pass
+ * is an rtc_ao — the same struct and rtc_ao_validate, the same fan (rtc_ao_expand, rtc_ao_ray), at most RTC_MAX_AO_SAMPLES
+ * samples — and every sample's ray is shaded where the AO pass only asks whether it meets something. Rendered by a kernel of
+ * its own (k_gather, csrc/rtc_kernels.hip): k_ao's primary pass and tangent frame, then per sample a closest-hit walk, the
+ * light loop with its any-hit walks, and lighting() — the function k_trace shades with.
+ *
+ *   The sample. For pixel (x, y) let Hit be the centre ray's rtc_hit exactly as the AOV section defines it, and for sample k
+ *   let ray_k = rtc_ao_ray(Hit.normal, Hit.over_point, local_k). Then
+ *       L_k = shade_hit's `surface` for ray_k's first hit (Intersections::get_hit: the smallest t >= 0.0), if that hit
+ *             exists and has t < radius: the sum over the World's light samples, in light order, of Material::lighting at the
+ *             hit's over_point with eyev = -ray_k.direction, each with its own is_shadowed_by_light ("Worlds with several
+ *             lights");
+ *       L_k = (0, 0, 0) otherwise.
+ *   This is World::color_at of the reference with remaining == 0 whenever `reflectance` is finite: reflected_color and
+ *   refracted_color are BLACK there (shape.rs:730, 752), and adding them only turns -0.0 into +0.0, which the mean's leading
+ *   `0.0 +` does anyway. No compute_refractive, no reflectv and no Schlick term is evaluated.
+ *
+ *   The planes. Row-major f64, three doubles per pixel, for a pass of n = usteps*vsteps samples:
+ *       radiance[c] = ((((0.0 + L_0[c]) + L_1[c]) + ...) / (double)n)     Color::average_over, in sample order; a mean that is
+ *                                                                          a NaN is stored as 0x7FF8000000000000 (the rule of
+ *                                                                          rtc_canvas_average)
+ *       bounce[c]   = (base[c] * diffuse) * radiance[c]                    a NaN product is stored as that NaN too
+ *   `base` is the colour Material::lighting starts from for the PRIMARY hit — the pattern colour at Hit.over_point (the point
+ *   k_trace passes to lighting) or material.color — and `diffuse` that material's coefficient: the Lambertian term of a
+ *   cosine-weighted fan, ready to be added to a frame (rtc_canvas_add_scaled). A pixel that misses holds zeros in both
+ *   planes; under RTC_MODE_RENDER so do the last row and the last column.
+ *   Flags, ordering, counters, Worlds: as rtc_render_aov_device. RTC_FLAG_NO_CULL gives the same bytes, RTC_FLAG_LDS_TABLE is
+ *   RTC_ERR_UNSUPPORTED; rtc_stats is not touched; every World form works (one light, 2..RTC_MAX_LIGHTS in the kernel
+ *   arguments, more from the World's light table, updated Worlds).
+ *   Limits. One bounce; the centre ray only (whatever cam->samples says); no jitter; no gather of lens, shutter, projection,
+ *   group or Lua launches; no specular or transmitted indirect light (a mirror reflects no bleeding, glass passes none). */
+typedef struct rtc_gather_buffers { /* 16 bytes; NULL = not wanted: that plane is neither computed nor written */
+    double *radiance;               /* hsize*vsize*3 */
+    double *bounce;                 /* hsize*vsize*3 */
+} rtc_gather_buffers;
+/* [host] the normative packing. hits: width*height centre-ray records; sample_hits[i*n_samples + k] and
+ * sample_rgb[3*(i*n_samples + k) + c]: the record and the colour (World::color_at, remaining 0) of pixel i's sample k, read
+ * only where hits[i] hits; albedo[3*i + c] = base[c] * diffuse of pixel i's hit (may be NULL when out->bounce is). Applies
+ * the radius rule (t < radius counts), the mean, the NaN rule, the bounce product and the mode rule. RTC_ERR_ARG: a NULL
+ * input, both planes NULL, n_samples outside 1..RTC_MAX_AO_SAMPLES, a radius that rtc_ao_validate refuses, a mode that does
+ * not exist. */
+rtc_status  rtc_gather_from_hits(const rtc_hit *hits, const rtc_hit *sample_hits, const double *sample_rgb, const double *albedo,
+                                 uint32_t n_samples, double radius, uint32_t width, uint32_t height, uint32_t mode,
+                                 const rtc_gather_buffers *out);
+/* [device] enqueue on the context's stream; the planes are DEVICE pointers, 8-byte aligned. Both NULL: RTC_ERR_ARG. The
+ * sample table is the context buffer rtc_render_ao_device fills. */
+rtc_status  rtc_render_gather_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                                     uint32_t flags, const rtc_gather_buffers *d);
+/* [device] the same into HOST memory; synchronous; scratch is grow-only and owned by the context */
+rtc_status  rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                              uint32_t flags, const rtc_gather_buffers *host);
+/* Compositing, in place: every component c of pixel i becomes c + strength * plane[3*i + its channel], f64 in that order
+ * (one product, one sum). strength is finite and >= 0, else RTC_ERR_ARG (NaN included); so are NULL pointers and a device
+ * pointer that is not 8-byte aligned. [host] normative; [device] one thread per pixel on the context's stream, the same
+ * bytes — every encoder can follow directly. */
+rtc_status  rtc_canvas_add_scaled(double *rgb, const double *plane, double strength, uint32_t width, uint32_t height);
+rtc_status  rtc_canvas_add_scaled_device(rtc_context *ctx, void *d_rgb, const void *d_plane, double strength, uint32_t width,
+                                         uint32_t height);
+/* Scenes whose camera asks for a gather pass. YAML: `add: camera` with `gather-radius` (> 0, or .inf) and, optionally,
+ * `gather-usteps` / `gather-vsteps`: the rules and defaults of the ao-* keys. These entries are rtc_scene_load_yaml_ao plus a
+ * second rtc_ao record: *has_gather_out = 1 and *gather_out filled when the camera has any of those keys, else 0 and
+ * *gather_out zeroed. Like the ao-* keys they ask for a pass, and every other YAML entry ignores them. */
+rtc_status  rtc_scene_load_yaml_gather(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                       struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                       rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                       struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
+                                       rtc_ao *gather_out, uint32_t *has_gather_out);
+rtc_status  rtc_scene_load_yaml_gather_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                            struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                            rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                            struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
+                                            rtc_ao *gather_out, uint32_t *has_gather_out);
+
 /* ==== float files: the f64 canvas and the AOV planes saved as data ==================== */
 /* Every writer above takes Color::scale'd 8-bit rows: components above 1.0 are clipped and a depth plane becomes a picture.
  * These three keep the numbers. Input: the f64 canvas, `rgb` = height*width*3 doubles, top row first (what rtc_render,

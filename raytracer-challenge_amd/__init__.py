@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -360,6 +360,38 @@ def apply_ao(rgb: np.ndarray, ao_plane: np.ndarray, n_samples: int, strength: fl
     return out
 
 
+def gather_from_hits(hits, sample_hits, sample_rgb, albedo, n_samples: int, radius: float, width: int, height: int,
+                     mode: int = MODE_RENDER_ASYNC, planes=("radiance", "bounce")) -> dict:
+    """rtc_gather_from_hits: width * height centre-ray records (an RtcHit array, row-major), per pixel n_samples sample records
+    (an RtcHit array of width * height * n_samples) and their colours (..., 3), and the per-pixel base * diffuse (..., 3; may
+    be None when "bounce" is not asked for) packed into the planes asked for: {"radiance": (H, W, 3), "bounce": (H, W, 3)},
+    the radius rule, the mean, the NaN rule and the mode rule included."""
+    npx = width * height
+    rgb = np.ascontiguousarray(sample_rgb, dtype=np.float64).reshape(-1)
+    if len(hits) != npx or len(sample_hits) != npx * n_samples or rgb.size != npx * n_samples * 3:
+        raise ValueError("gather_from_hits needs width * height records and n_samples records and colours for each")
+    alb = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float64).reshape(-1)
+    if alb is not None and alb.size != npx * 3:
+        raise ValueError("gather_from_hits needs width * height * 3 albedo values")
+    out = {name: np.empty((height, width, 3)) for name in planes}
+    b = RtcGatherBuffers(**{name: a.ctypes.data for name, a in out.items()})
+    _check(lib().rtc_gather_from_hits(hits, sample_hits, rgb.ctypes.data_as(C.POINTER(C.c_double)),
+                                      None if alb is None else alb.ctypes.data_as(C.POINTER(C.c_double)), int(n_samples), float(radius),
+                                      width, height, mode, C.byref(b)), "rtc_gather_from_hits")
+    return out
+
+
+def add_scaled(rgb: np.ndarray, plane: np.ndarray, strength: float = 1.0) -> np.ndarray:
+    """rtc_canvas_add_scaled: a copy of the (H, W, 3) f64 canvas with strength * plane added, component by component."""
+    out = np.array(rgb, dtype=np.float64, order="C", copy=True)
+    pl = np.ascontiguousarray(plane, dtype=np.float64)
+    if out.ndim != 3 or out.shape[2] != 3 or pl.shape != out.shape:
+        raise ValueError("add_scaled needs an (H, W, 3) canvas and a plane of its shape")
+    _check(lib().rtc_canvas_add_scaled(out.ctypes.data_as(C.POINTER(C.c_double)), pl.ctypes.data_as(C.POINTER(C.c_double)), float(strength),
+                                       out.shape[1], out.shape[0]), "rtc_canvas_add_scaled")
+    return out
+
+
 def projection(kind, width: float = 0.0, h_span: float = 2.0 * math.pi, v_span: float = math.pi) -> RtcProjection:
     """A projection for DeviceWorld.render_projection (rtc_projection, include/rtc.h). kind "orthographic" (or
     PROJ_ORTHOGRAPHIC): parallel rays, `width` the world-space width of the view. kind "panorama" (PROJ_PANORAMA): the
@@ -517,6 +549,27 @@ def load_yaml_ao(text: str | None = None, path: str | None = None):
         w.shapes.append(s)
     lib().rtc_free(shapes)
     return w, cam, (ln if has.value else None), (a if has_a.value else None)
+
+
+def load_yaml_gather(text: str | None = None, path: str | None = None):
+    """load_yaml_ao for scenes whose camera may also ask for a gather pass (gather-radius / gather-usteps / gather-vsteps):
+    -> (World, RtcCamera, RtcLens or None, RtcAo or None, RtcAo or None), the last the gather pass."""
+    shapes = C.POINTER(RtcShape)()
+    n = C.c_uint32(0)
+    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
+    err = C.create_string_buffer(512)
+    ln, has, a, has_a, g, has_g = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
+    fn = lib().rtc_scene_load_yaml_gather_file if path is not None else lib().rtc_scene_load_yaml_gather
+    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
+            err, 512, C.byref(ln), C.byref(has), C.byref(a), C.byref(has_a), C.byref(g), C.byref(has_g))
+    _check(st, "rtc_scene_load_yaml_gather", err.value.decode(errors="replace"))
+    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
+    for i in range(n.value):
+        s = RtcShape()
+        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
+        w.shapes.append(s)
+    lib().rtc_free(shapes)
+    return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None)
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
@@ -1416,6 +1469,12 @@ class Context:
         _check(lib().rtc_canvas_apply_ao_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_ao), int(n_samples), float(strength), width, height),
                "rtc_canvas_apply_ao_device")
 
+    def add_scaled_device(self, d_rgb: int, d_plane: int, strength: float, width: int, height: int) -> None:
+        """add_scaled in place on an f64 canvas and an f64 plane in DEVICE memory, enqueued on the context's stream
+        (rtc_canvas_add_scaled_device): the same bytes as the host function."""
+        _check(lib().rtc_canvas_add_scaled_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_plane), float(strength), width, height),
+               "rtc_canvas_add_scaled_device")
+
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
         return Shutter(self)
@@ -1655,6 +1714,21 @@ class DeviceWorld:
     def render_ao_device(self, cam: RtcCamera, ao: RtcAo, d_ao: int, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
         """The same into a DEVICE buffer of vsize * hsize uint16 (rtc_render_ao_device): enqueued on the context's stream."""
         _check(lib().rtc_render_ao_device(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.c_void_p(d_ao)), "rtc_render_ao_device")
+
+    def render_gather(self, cam: RtcCamera, ao: RtcAo, mode: int = MODE_RENDER_ASYNC, flags: int = 0, planes=("radiance", "bounce")) -> dict:
+        """The one-bounce gather pass (rtc_render_gather): {"radiance": (vsize, hsize, 3), "bounce": (vsize, hsize, 3)} f64 for
+        the planes asked for — the mean colour the fan `ao` sees from the centre ray's hit within its radius, and that mean
+        times the hit's own base colour and diffuse coefficient, ready for add_scaled. Zeros where the centre ray misses."""
+        out = {name: np.empty((cam.vsize, cam.hsize, 3)) for name in planes}
+        b = RtcGatherBuffers(**{name: a.ctypes.data for name, a in out.items()})
+        _check(lib().rtc_render_gather(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.byref(b)), "rtc_render_gather")
+        return out
+
+    def render_gather_device(self, cam: RtcCamera, ao: RtcAo, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+        """The same into DEVICE buffers of vsize * hsize * 3 doubles, {"radiance": pointer, "bounce": pointer} with either left
+        out (rtc_render_gather_device): enqueued on the context's stream."""
+        b = RtcGatherBuffers(**{name: int(p) for name, p in pointers.items()})
+        _check(lib().rtc_render_gather_device(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.byref(b)), "rtc_render_gather_device")
 
     def color_at(self, rays: np.ndarray, remaining: int = 5, want_hits: bool = False, flags: int = 0):
         """World::color_at for an (n, 6) array of rays; returns rgb (n,3) [and the rtc_hit array]."""
@@ -2040,7 +2114,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
            "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",

@@ -51,6 +51,10 @@ class RtcAo(C.Structure):
     _fields_ = [("radius", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
 
 
+class RtcGatherBuffers(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("bounce", C.c_void_p)]
+
+
 class RtcProjection(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("_pad", C.c_uint32), ("width", C.c_double), ("h_span", C.c_double), ("v_span", C.c_double)]
 
@@ -130,7 +134,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24 and C.sizeof(RtcProjection) == 32
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
-assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64 and C.sizeof(RtcAo) == 16
+assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64 and C.sizeof(RtcAo) == 16 and C.sizeof(RtcGatherBuffers) == 16
 
 D = C.c_double
 PD = C.POINTER(C.c_double)
@@ -360,6 +364,17 @@ PROTOTYPES = {
     "rtc_scene_load_yaml_ao_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                 C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
                                                 C.POINTER(RtcAo), C.POINTER(U32)]),
+    "rtc_gather_from_hits": (C.c_int32, [C.POINTER(RtcHit), C.POINTER(RtcHit), PD, PD, U32, D, U32, U32, U32, C.POINTER(RtcGatherBuffers)]),
+    "rtc_render_gather_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
+    "rtc_render_gather": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
+    "rtc_canvas_add_scaled": (C.c_int32, [PD, PD, D, U32, U32]),
+    "rtc_canvas_add_scaled_device": (C.c_int32, [VP, VP, VP, D, U32, U32]),
+    "rtc_scene_load_yaml_gather": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                               C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_gather_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                    C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32)]),
     "rtc_float_format_for_name": (C.c_int32, [C.c_char_p, C.POINTER(U32)]),
     "rtc_float_format": (C.c_size_t, [U32, C.POINTER(RtcFloatPlanes), U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
     "rtc_canvas_save_f64": (C.c_int32, [C.c_char_p, PD, U32, U32]),

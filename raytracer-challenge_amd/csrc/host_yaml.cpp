@@ -352,6 +352,8 @@ struct Scene {
     int proj_line = 0;                  // line of the camera entry that has projection keys, 0: none
     rtc_ao ao{};                        // the camera's ambient-occlusion pass (include/rtc.h); zeroed without ao keys
     int ao_line = 0;                    // line of the camera entry that has ao keys, 0: none
+    rtc_ao gather{};                    // the camera's gather pass (include/rtc.h "colour bleeding"); zeroed without gather keys
+    int gather_line = 0;                // line of the camera entry that has gather keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -451,28 +453,33 @@ void interpret(const Node &root, Scene &sc) {
                     fail(e.line, "too many lens samples: lens-usteps x lens-vsteps is at most " + std::to_string(RTC_MAX_LENS_SAMPLES));
                 if (sc.proj_line) fail(e.line, "a camera has a lens or a projection, not both");
             }
-            // ambient occlusion (include/rtc.h): ao-radius / ao-usteps / ao-vsteps; asks for a pass, changes no ray of the frame
-            sc.ao = rtc_ao{};
-            sc.ao_line = 0;
-            const Node *aor = e.get("ao-radius"), *aou = e.get("ao-usteps"), *aov = e.get("ao-vsteps");
-            if (aor || aou || aov) {
-                sc.ao_line = e.line;
-                if (!aor) fail(e.line, "ao-usteps / ao-vsteps need an ao-radius");
+            // ambient occlusion and the gather pass (include/rtc.h): PREFIX-radius / PREFIX-usteps / PREFIX-vsteps with PREFIX = ao or
+            // gather, one rule for both; each asks for a pass and changes no ray of the frame
+            auto fan = [&](const std::string &pre, const char *noun, rtc_ao &out, int &line) {
+                out = rtc_ao{};
+                line = 0;
+                const std::string kr = pre + "-radius", ku = pre + "-usteps", kv = pre + "-vsteps";
+                const Node *aor = e.get(kr.c_str()), *aou = e.get(ku.c_str()), *aov = e.get(kv.c_str());
+                if (!(aor || aou || aov)) return;
+                line = e.line;
+                if (!aor) fail(e.line, ku + " / " + kv + (pre == "ao" ? " need an " : " need a ") + kr);
                 const bool unbounded = aor->kind == Node::Scalar && (aor->scalar == ".inf" || aor->scalar == "+.inf"); // YAML's spelling
-                sc.ao.radius = unbounded ? std::numeric_limits<double>::infinity() : as_number(aor, "ao-radius");
-                auto steps = [&](const Node *n, const char *key) {
+                out.radius = unbounded ? std::numeric_limits<double>::infinity() : as_number(aor, kr.c_str());
+                auto steps = [&](const Node *n, const std::string &key) {
                     if (!n) return 4u;
-                    const double v = as_number(n, key);
+                    const double v = as_number(n, key.c_str());
                     if (!(v >= 1 && v <= RTC_MAX_AO_SAMPLES) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
-                        fail(n->line, std::string(key) + " must be an integer in 1.." + std::to_string(RTC_MAX_AO_SAMPLES));
+                        fail(n->line, key + " must be an integer in 1.." + std::to_string(RTC_MAX_AO_SAMPLES));
                     return static_cast<uint32_t>(v);
                 };
-                sc.ao.usteps = steps(aou, "ao-usteps");
-                sc.ao.vsteps = steps(aov, "ao-vsteps");
-                if (!(sc.ao.radius > 0.)) fail(aor->line, "ao-radius must be a number > 0 (.inf: unbounded)");
-                if (rtc_ao_validate(&sc.ao) != RTC_OK)
-                    fail(e.line, "too many ambient-occlusion samples: ao-usteps x ao-vsteps is at most " + std::to_string(RTC_MAX_AO_SAMPLES));
-            }
+                out.usteps = steps(aou, ku);
+                out.vsteps = steps(aov, kv);
+                if (!(out.radius > 0.)) fail(aor->line, kr + " must be a number > 0 (.inf: unbounded)");
+                if (rtc_ao_validate(&out) != RTC_OK)
+                    fail(e.line, std::string("too many ") + noun + " samples: " + ku + " x " + kv + " is at most " + std::to_string(RTC_MAX_AO_SAMPLES));
+            };
+            fan("ao", "ambient-occlusion", sc.ao, sc.ao_line);
+            fan("gather", "gather", sc.gather, sc.gather_line);
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
             if (const Node *ss = e.get("shutter-samples")) {
@@ -562,11 +569,12 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
                             rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr,
                             rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr,
                             rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr, rtc_ao *ao_out = nullptr,
-                            uint32_t *has_ao_out = nullptr) {
+                            uint32_t *has_ao_out = nullptr, rtc_ao *gather_out = nullptr, uint32_t *has_gather_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
     if ((ao_out == nullptr) != (has_ao_out == nullptr)) return RTC_ERR_ARG;
+    if ((gather_out == nullptr) != (has_gather_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -627,6 +635,10 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (ao_out) {
             *ao_out = sc.ao;
             *has_ao_out = sc.ao_line ? 1u : 0u;
+        }
+        if (gather_out) {
+            *gather_out = sc.gather;
+            *has_gather_out = sc.gather_line ? 1u : 0u;
         }
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -691,6 +703,15 @@ rtc_status rtc_scene_load_yaml_ao(const char *text, rtc_shape **shapes_out, uint
     if (!lens_out || !has_lens_out || !ao_out || !has_ao_out) return RTC_ERR_ARG;
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
                      lens_out, has_lens_out, nullptr, nullptr, nullptr, nullptr, nullptr, ao_out, has_ao_out);
+}
+
+rtc_status rtc_scene_load_yaml_gather(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                      uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                      rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out, rtc_ao *gather_out,
+                                      uint32_t *has_gather_out) {
+    if (!lens_out || !has_lens_out || !ao_out || !has_ao_out || !gather_out || !has_gather_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out, nullptr, nullptr, nullptr, nullptr, nullptr, ao_out, has_ao_out, gather_out, has_gather_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -771,6 +792,17 @@ rtc_status rtc_scene_load_yaml_ao_file(const char *path, rtc_shape **shapes_out,
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_ao(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                   lens_out, has_lens_out, ao_out, has_ao_out);
+}
+
+rtc_status rtc_scene_load_yaml_gather_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                           size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
+                                           rtc_ao *gather_out, uint32_t *has_gather_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_gather(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                      lens_out, has_lens_out, ao_out, has_ao_out, gather_out, has_gather_out);
 }
 
 } // extern "C"

@@ -18,6 +18,7 @@
 #include "rtc_ao.h"
 #include "rtc_aov.h"
 #include "rtc_device.h"
+#include "rtc_gather.h"
 #include "rtc_internal.h"
 #include "rtc_launch_plan.h"
 #include "rtc_parity.h"
@@ -1848,6 +1849,84 @@ rtc_status rtc_canvas_apply_ao_device(rtc_context *ctx, void *d_rgb, const void 
     if (n == 0) return RTC_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(rtc_launch_apply_ao(static_cast<double *>(d_rgb), static_cast<const uint16_t *>(d_ao), n, n_samples, strength, ctx->stream));
+    return RTC_OK;
+}
+
+// ---- colour bleeding: the one-bounce gather pass (include/rtc.h) ----------------------------------------------------------
+rtc_status rtc_render_gather_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                                    uint32_t flags, const rtc_gather_buffers *d) {
+    if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
+    if (!d->radiance && !d->bounce) return RTC_ERR_ARG;
+    if (((size_t)d->radiance | (size_t)d->bounce) % sizeof(double) != 0) return RTC_ERR_ARG;
+    if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
+    HIP_TRY(hipSetDevice(ctx->device));
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status hs = current_gen(w, &gen);
+    if (hs != RTC_OK) return hs;
+    rtc_world::Gen &G = *gen;
+    LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_AOV, flags); // k_aov's plan: the same grid, no dynamic LDS
+    in.hsize = cam->hsize; in.vsize = cam->vsize; in.mode = mode;
+    LaunchPlan plan;
+    rtc_plan_launch(in, plan);
+    if (plan.status != RTC_OK) return (rtc_status)plan.status;
+    const rtc_status ts = ao_table(ctx, ao); // the fan is the AO pass's: one table per context, whichever pass filled it
+    if (ts != RTC_OK) return ts;
+    LaunchLights LL;
+    lights_of(G, LL);
+    RenderParams P;
+    planned_params(ctx, w, G, plan, P);
+    fill_camera(P, cam);
+    GatherParams A;
+    std::memset(&A, 0, sizeof A);
+    A.cam = P.views[0];
+    A.W = cam->hsize;
+    A.H = cam->vsize;
+    A.mode = mode;
+    A.tiles_x = plan.grid_x;
+    A.n = G.n;
+    A.ngroups = G.ngroups;
+    A.pre_limit = G.pre_limit;
+    A.radius = ao->radius;
+    A.nsamples = ao->usteps * ao->vsteps;
+    for (int k = 0; k < 3; ++k) {
+        A.light_pos[k] = G.light.position[k];
+        A.light_int[k] = G.light.intensity[k];
+    }
+    A.radiance = d->radiance;
+    A.bounce = d->bounce;
+    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
+    HIP_TRY(rtc_launch_gather(&A, ctx->d_ao_dirs.get(), &P, plan.src, LL.xl, LL.lt, ctx->stream));
+    HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
+    return RTC_OK;
+}
+
+rtc_status rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
+                             const rtc_gather_buffers *host) {
+    if (!ctx || !w || !cam || !host || (!host->radiance && !host->bounce) || w->ctx != ctx || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
+    if (cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t plane = (size_t)cam->hsize * cam->vsize * 3u;
+    const rtc_status st = ctx->d_gather.reserve(2u * plane, &ctx->render_allocs);
+    if (st != RTC_OK) return st;
+    rtc_gather_buffers d;
+    d.radiance = host->radiance ? ctx->d_gather.get() : nullptr;
+    d.bounce = host->bounce ? ctx->d_gather.get() + plane : nullptr;
+    const rtc_status ls = rtc_render_gather_device(ctx, w, cam, ao, mode, flags, &d);
+    if (ls != RTC_OK) return ls;
+    rtc_status out = RTC_OK;
+    if (d.radiance && hipMemcpyAsync(host->radiance, d.radiance, sizeof(double) * plane, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    if (d.bounce && hipMemcpyAsync(host->bounce, d.bounce, sizeof(double) * plane, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    return out;
+}
+
+rtc_status rtc_canvas_add_scaled_device(rtc_context *ctx, void *d_rgb, const void *d_plane, double strength, uint32_t width, uint32_t height) {
+    if (!ctx || !d_rgb || !d_plane || rtc_gather_strength_check(strength) != RTC_OK) return RTC_ERR_ARG;
+    if (((size_t)d_rgb | (size_t)d_plane) % sizeof(double) != 0) return RTC_ERR_ARG;
+    const size_t n = (size_t)width * height;
+    if (n == 0) return RTC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(rtc_launch_add_scaled(static_cast<double *>(d_rgb), static_cast<const double *>(d_plane), n, strength, ctx->stream));
     return RTC_OK;
 }
 

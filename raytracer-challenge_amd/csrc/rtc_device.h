@@ -244,6 +244,18 @@ struct AoParams {
     uint32_t nsamples, _pad;   // 1..RTC_MAX_AO_SAMPLES
     uint16_t *out;
 };
+// k_gather (rtc_render_gather_device): the radiance and bounce planes of a W x H frame. AoParams' fields under the same
+// names, the World's first light as lighting() reads it (light_int), and the planes (nullptr: not wanted).
+struct GatherParams {
+    DevCamera cam;
+    uint32_t W, H, mode, tiles_x;
+    uint32_t n, ngroups;
+    double pre_limit;
+    double radius;
+    uint32_t nsamples, _pad;
+    double light_pos[3], light_int[3]; // L[0]; the further lights are the kernel's trailing argument, as k_aov's
+    double *radiance, *bounce;
+};
 
 struct RenderParams {
     const DevIsect *isect;

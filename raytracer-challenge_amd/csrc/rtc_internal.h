@@ -41,6 +41,7 @@ struct rtc_context {
     double ao_host[3u * RTC_MAX_AO_SAMPLES] = {};
     uint32_t ao_usteps = 0, ao_vsteps = 0; // the grid d_ao_dirs holds; 0: none yet
     DevBuf<uint16_t> d_ao;           // the plane of rtc_render_ao (host-buffer entry point)
+    DevBuf<double> d_gather;         // the planes of rtc_render_gather (host-buffer entry point): radiance, then bounce
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -212,6 +213,10 @@ extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t st
 // k_ao / k_apply_ao (rtc_kernels.hip). `P`: the World's tables only (fill_world); `dirs`: the sample table in device memory.
 extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, hipStream_t stream);
 extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_t n, uint32_t n_samples, double strength, hipStream_t stream);
+// k_gather / k_add_scaled (rtc_kernels.hip). `P`, `dirs`: as rtc_launch_ao; `xl` / `lt`: as rtc_launch_aov.
+extern "C" hipError_t rtc_launch_gather(const GatherParams *A, const double *dirs, const RenderParams *P, int src, const DevExtraLights *xl,
+                                        const DevLightTable *lt, hipStream_t stream);
+extern "C" hipError_t rtc_launch_add_scaled(double *rgb, const double *plane, size_t n, double strength, hipStream_t stream);
 extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
 // k_average_over (rtc_shutter.hip): one pass of Color::average_over over whole canvases. Adds frames[f * stride + i], f = 0..nf-1
 // in that order, to the carried sum (sum_in, NULL: 0.0) for i < count. divisor == 0: stores the sum to f64_out. Otherwise the

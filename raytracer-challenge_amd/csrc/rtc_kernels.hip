@@ -34,6 +34,7 @@
 #include "rtc_aov.h"
 #include "rtc_bands.h"
 #include "rtc_device.h"
+#include "rtc_gather.h"
 #include "rtc_gamma.h"
 #include "rtc_parity.h"
 #include "rtc_world_build.h"
@@ -2750,6 +2751,174 @@ __global__ void __launch_bounds__(256) k_apply_ao(double *__restrict__ rgb, cons
     rgb[3u * i + 2u] = rgb[3u * i + 2u] * f;
 }
 
+// ---- colour bleeding: one bounce gathered over the AO fan (rtc_render_gather*, include/rtc.h) ------------------------
+// k_ao's shape, primary pass, compute_vectors and tangent frame, and its wave-uniform sample loop with the directions by
+// scalar loads. Per sample, where k_ao asks "anything within the radius?":
+//   1. a closest-hit walk (ClosestHit) for the lanes whose pixel hit, with k_ao's per-sample bundle (per-lane origins, the
+//      reach in tmax when the radius is finite) and the per-lane prefilter. Both are culls: an object they drop cannot be
+//      hit with 0 <= t < radius, and a hit at t >= radius is not counted whatever it is, so the bytes never depend on them.
+//      The ordered walk's early exit (Skip) needs rays that start at the bundle's apex and is not available here: this walk
+//      visits every candidate, where k_ao's any-hit walk stops at the first object in the way.
+//   2. for the lanes with a counted hit (one with t < radius): the secondary normal, the inside flip against -dir, the
+//      over-point, eyev = -dir — compute_vectors without compute_refractive and reflectv, which remaining == 0 never reads.
+//   3. the light loop as k_aov<SRC, true, XL...> runs it (shadow_ray, the light's bundle, AnyHit), each light followed by
+//      lighting() — the function k_trace shades with, so the terms are k_trace's arithmetic — summed in light order.
+//   4. the sample's colour added to three doubles per lane (a lane without a counted hit adds 0.0).
+// Lanes without work carry pending = false; every walk is reached by the whole wave. Whether `bounce` is wanted is a
+// wave-uniform argument (A.bounce): one `base` evaluation per pixel behind the loop, from the primary hit's index and
+// over-point, which are live through the loop anyway. XL: as k_aov's (nothing, DevExtraLights or DevLightTable).
+// Registers: the loop carries the primary hit's frame (normal, over, t, s: 24 VGPRs), the accumulator (6) and, across the
+// light loop, the secondary hit (normal, over, direction: 18) on top of what a walk needs, which is more than k_ao's 90; the
+// bound is four waves per SIMD (128 VGPRs), the step at which no instantiation spills (profiles/gather_kernel_resources.txt).
+#ifndef RTC_GATHER_WAVES_PER_SIMD
+#define RTC_GATHER_WAVES_PER_SIMD 4
+#endif
+template <int SRC, class... XL>
+__global__ void __launch_bounds__(64, RTC_GATHER_WAVES_PER_SIMD)
+k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
+         const DevShade *__restrict__ t_shade, const DevBound *__restrict__ t_bound, const DevIsect *__restrict__ t_isect_s,
+         const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s, const uint32_t *__restrict__ t_orig_s,
+         const DevBound *__restrict__ t_gbound, const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
+    static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "gather launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
+    static_assert(sizeof...(XL) <= 1, "the further lights: one block at most");
+    Tables T{};
+    T.isect = t_isect; T.kind = t_kind; T.shade = t_shade; T.bound = t_bound;
+    T.isect_s = t_isect_s; T.kind_s = t_kind_s; T.bound_s = t_bound_s; T.orig_s = t_orig_s; T.gbound = t_gbound;
+    T.pre = t_pre; T.pre_s = t_pre_s;
+    const LdsView L{};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
+    const bool in_range = px < A.W && py < A.H;
+    // Camera::render leaves the last row and column untouched (camera.rs:120-121): they get the miss value
+    const bool traced = in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H));
+
+    // ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76
+    V3 cam_origin = xpoint(A.cam.vinv, mk(0., 0., 0.));
+    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
+    const V3 ro = cam_origin;
+    const V3 rd = primary_dir(A.cam, cam_origin, px, py);
+
+    // ---- World::intersect + get_hit, streaming form (k_aov's primary pass) ----
+    double best = __builtin_inf();
+    int hidx = -1, hroot = 0;
+    Bundle B{};
+    B.off = true;
+    if constexpr (IS_CULL(SRC)) {
+        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
+    }
+    if constexpr (SRC == SRC_CULL2)
+        for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
+    else
+        for_each_object<SRC>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
+    const bool hit = traced && hidx >= 0;
+
+    // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96): normal and over_point; then the tangent frame ----
+    V3 normal = mk(0., 0., 0.), over = mk(0., 0., 0.), tv = mk(0., 0., 0.), sv = mk(0., 0., 0.);
+    if (hit) {
+        const V3 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
+        const DevShade *S = T.shade + hidx;
+        const double *m_obj = T.isect[hidx].m;
+        normal = shape_normal(S, m_obj, point);
+        if (vdot(normal, vneg(rd)) < 0.0) normal = vneg(normal);
+        over = vadd(point, vmul(normal, RTC_EPSILON));
+        const double nn[3] = {normal.x, normal.y, normal.z};
+        double t3[3], s3[3];
+        rtc_ao_frame(nn, t3, s3);
+        tv = mk(t3[0], t3[1], t3[2]);
+        sv = mk(s3[0], s3[1], s3[2]);
+    }
+
+    // ---- per sample, in the table's order: the first hit within the radius, shaded under every light ----
+    V3 acc = mk(0.0, 0.0, 0.0); // Color::average_over's sum: from 0.0, in sample order
+    const double radius = A.radius;
+    const uint32_t ns = A.nsamples;
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double lx = t_dirs[3u * k], ly = t_dirs[3u * k + 1u], lz = t_dirs[3u * k + 2u]; // (k is wave-uniform: scalar loads)
+        const V3 dir = mk(rtc_ao_dir(tv.x, sv.x, normal.x, lx, ly, lz), rtc_ao_dir(tv.y, sv.y, normal.y, lx, ly, lz),
+                          rtc_ao_dir(tv.z, sv.z, normal.z, lx, ly, lz));
+        // 1. World::intersect + get_hit of the sample's ray
+        double sbest = __builtin_inf();
+        int sidx = -1, sroot = 0;
+        Bundle Bk{};
+        Bk.off = true;
+        if constexpr (IS_CULL(SRC)) {
+            if (ballot(hit) != 0ull) {
+                Bk = make_bundle<false, false>(hit, over, over, dir, 0.);
+                // the reach, rounded up as make_bundle's REACH form rounds it (k_ao's rule)
+                if (radius < 1e30) Bk.tmax = uniform_f64((double)(fmaxf(0.f, (float)radius) * 1.0001f + 1e-30f));
+            }
+        }
+        for_each_object<SRC, SRC == SRC_CULL2 || (SRC == SRC_CULL && RTC_AO_LANE_FILTER_ONE_LEVEL)>(A, T, L, hit, Bk, ClosestHit{hit, over, dir, sbest, sidx, sroot}, over, dir);
+        const bool counted = hit && sidx >= 0 && sbest < radius;
+
+        // 2. compute_vectors of the counted hit: eyev = -dir, the normal with its inside flip, over_point
+        const DevShade *S2 = T.shade + (counted ? sidx : 0);
+        const double *m2 = T.isect[counted ? sidx : 0].m;
+        const V3 seye = vneg(dir);
+        V3 snormal = mk(0., 0., 0.), sover = mk(0., 0., 0.);
+        if (counted) {
+            const V3 spoint = vadd(over, vmul(dir, sbest)); // Ray::position vec.rs:207-209
+            snormal = shape_normal(S2, m2, spoint);
+            if (vdot(snormal, seye) < 0.0) snormal = vneg(snormal);
+            sover = vadd(spoint, vmul(snormal, RTC_EPSILON));
+        }
+
+        // 3. surface = lighting(L[0]) + lighting(L[1]) + ..., in light order, each with its own is_shadowed_by_light
+        auto one_light = [&](V3 lp, const auto &I) {
+            V3 ldir = mk(0., 0., 0.);
+            double ldist = 0.;
+            shadow_ray(lp, sover, counted, ldir, ldist);
+            bool pending = counted, shadowed = false;
+            Bundle Bl{};
+            Bl.off = true;
+            if constexpr (IS_CULL(SRC)) { // the segment over_point -> light, walked from the light: apex = light (shared), reach-limited
+                if (ballot(counted) != 0ull) Bl = make_bundle<true, true>(counted, lp, lp, vneg(ldir), ldist);
+            }
+            for_each_object<SRC, SRC == SRC_CULL2>(A, T, L, pending, Bl, AnyHit{pending, sover, ldir, ldist, shadowed}, sover, ldir);
+            asm volatile("" ::: "memory"); // as k_trace's light loop: the material loads stay below the walk
+            V3 term = mk(0., 0., 0.);
+            if (counted) term = lighting(I, S2, m2, sover, seye, snormal, ldir, shadowed);
+            return term;
+        };
+        V3 surface = one_light(mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]), A);
+        if constexpr (sizeof...(XL) == 1) {
+            const auto &X = first_of(xl_arg...); // DevExtraLights (kernel arguments) or DevLightTable (HBM)
+            const uint32_t n_extra = further_light_count(X);
+            for (uint32_t li = 0; li < n_extra; ++li) surface = vadd(surface, one_light(further_light_position(X, li), further_light_intensity(X, li)));
+        }
+
+        // 4. the sum, in sample order
+        acc = vadd(acc, surface);
+    }
+
+    // ---- the planes asked for (wave-uniform choice), one pixel per lane: plain vector stores ----
+    V3 rad = mk(0.0, 0.0, 0.0);
+    if (hit) rad = mk(rtc_gather_mean(acc.x, ns), rtc_gather_mean(acc.y, ns), rtc_gather_mean(acc.z, ns));
+    const size_t idx = (size_t)py * A.W + px;
+    if (A.radiance != nullptr && in_range) {
+        A.radiance[3u * idx] = rad.x; A.radiance[3u * idx + 1u] = rad.y; A.radiance[3u * idx + 2u] = rad.z;
+    }
+    if (A.bounce != nullptr) {
+        V3 out = mk(0.0, 0.0, 0.0);
+        if (hit) { // `base` as lighting() takes it for the primary hit: the pattern colour at over_point, or the material's colour
+            const DevShade *S = T.shade + hidx;
+            const V3 base = (S->pattern_kind != RTC_PATTERN_NONE) ? pattern_color(S, T.isect[hidx].m, over) : mk(S->color[0], S->color[1], S->color[2]);
+            const double kd = S->diffuse;
+            out = mk(rtc_gather_bounce(base.x * kd, rad.x), rtc_gather_bounce(base.y * kd, rad.y), rtc_gather_bounce(base.z * kd, rad.z));
+        }
+        if (in_range) { A.bounce[3u * idx] = out.x; A.bounce[3u * idx + 1u] = out.y; A.bounce[3u * idx + 2u] = out.z; }
+    }
+}
+
+// rtc_canvas_add_scaled on the device: one thread per pixel, rtc_gather.h's sum
+__global__ void __launch_bounds__(256) k_add_scaled(double *__restrict__ rgb, const double *__restrict__ plane, size_t n, double strength) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    rgb[3u * i] = rtc_gather_add_scaled(rgb[3u * i], plane[3u * i], strength);
+    rgb[3u * i + 1u] = rtc_gather_add_scaled(rgb[3u * i + 1u], plane[3u * i + 1u], strength);
+    rgb[3u * i + 2u] = rtc_gather_add_scaled(rgb[3u * i + 2u], plane[3u * i + 2u], strength);
+}
+
 // ---- launch dispatch (rtc_launch_aov, rtc_launch_trace) -----------------------------------------------------------
 // The runtime `src` as a compile-time constant: f(std::integral_constant<int, SRC_x>) for the one of `ALLOWED` it equals.
 template <int... ALLOWED, class F> static hipError_t with_src(int src, F &&f) {
@@ -2818,6 +2987,33 @@ extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_
     const size_t blocks = (n + 255u) / 256u;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_apply_ao, dim3((uint32_t)blocks), dim3(256), 0, stream, rgb, ao, n, n_samples, strength);
+    return hipGetLastError();
+}
+
+// `P`: the World's tables only (fill_world). `dirs`: A->nsamples directions in device memory. `xl` / `lt` (never both): the
+// further lights of a World with several. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
+extern "C" hipError_t rtc_launch_gather(const GatherParams *A, const double *dirs, const RenderParams *P, int src, const DevExtraLights *xl,
+                                        const DevLightTable *lt, hipStream_t stream) {
+    if (A->W == 0u || A->H == 0u || A->tiles_x != (A->W + 7u) / 8u || (A->radiance == nullptr && A->bounce == nullptr) || dirs == nullptr)
+        return hipErrorInvalidValue;
+    if (A->nsamples == 0u || A->nsamples > RTC_MAX_AO_SAMPLES) return hipErrorInvalidValue;
+    const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
+    if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)tiles64;
+    return with_further_lights(xl, lt, [&](const auto &...x) {
+        return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+            hipLaunchKernelGGL((k_gather<S(), std::decay_t<decltype(x)>...>), dim3(tiles), dim3(64), 0, stream, *A, dirs, P->isect, P->kind, P->shade,
+                               P->bound, P->isect_s, P->kind_s, P->bound_s, P->orig_s, P->gbound, P->pre, P->pre_s, x...);
+            return hipGetLastError();
+        });
+    });
+}
+
+extern "C" hipError_t rtc_launch_add_scaled(double *rgb, const double *plane, size_t n, double strength, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255u) / 256u;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_add_scaled, dim3((uint32_t)blocks), dim3(256), 0, stream, rgb, plane, n, strength);
     return hipGetLastError();
 }
 

@@ -197,6 +197,13 @@ class Canvas { // canvas.rs:16-109
             throw Panic(RTC_ERR_ARG, "Canvas::apply_ao: an f64 Canvas and a plane of its size are needed");
         check(rtc_canvas_apply_ao(pixels.data(), ao.data(), n_samples, strength, width, height), "Canvas::apply_ao");
     }
+    // A plane added in place (rtc_canvas_add_scaled, include/rtc.h): every component c becomes c + strength * plane's. `plane`
+    // is three doubles per pixel, Camera::render_gather's `bounce` for one. f64 canvases only.
+    void add_scaled(const std::vector<double> &plane, double strength = 1.0) {
+        if (pixels.size() != static_cast<size_t>(width) * height * 3 || plane.size() != pixels.size())
+            throw Panic(RTC_ERR_ARG, "Canvas::add_scaled: an f64 Canvas and a plane of its size are needed");
+        check(rtc_canvas_add_scaled(pixels.data(), plane.data(), strength, width, height), "Canvas::add_scaled");
+    }
     void write_to_file_simple(const std::string &file_name) const { // canvas.rs:86-109
         if (is_imgbuf()) { // the PPM is Color::scale's (gamma 1): only an RGBA frame of gamma 1 holds those bytes
             if (rgba8_gamma != 1.0f) throw Panic(RTC_ERR_ARG, "Canvas::write_to_file_simple: the Canvas holds RGBA at gamma != 1 (Camera::render_rgba8)");
@@ -481,6 +488,14 @@ struct Aov {
     }
 };
 
+// One bounce of indirect light per pixel (rtc_render_gather, include/rtc.h "colour bleeding"): the planes of
+// Camera::render_gather, row-major, three doubles per pixel. Not part of the reference.
+struct Gather {
+    uint32_t width = 0, height = 0;
+    std::vector<double> radiance;     // the mean colour the fan sees from the centre ray's hit, within its radius
+    std::vector<double> bounce;       // radiance times the hit's base colour and diffuse coefficient: Canvas::add_scaled takes it
+};
+
 class Camera { // camera.rs:17-160
   public:
     static constexpr uint8_t MAX_REFLECTIONS = RTC_MAX_REFLECTIONS;
@@ -560,6 +575,10 @@ class Camera { // camera.rs:17-160
     // The other planes are empty. A lens, a shutter or a projection has no AO form (RTC_ERR_UNSUPPORTED).
     Aov render_ao(const World &w, const rtc_ao &ao) const { return run_ao(w, ao, RTC_MODE_RENDER); }
     Aov render_async_ao(const World &w, const rtc_ao &ao) const { return run_ao(w, ao, RTC_MODE_RENDER_ASYNC); }
+    // The one-bounce gather pass of the same frame (rtc_render_gather): what the fan `ao` sees from every centre ray's hit,
+    // shaded under the World's lights. A lens, a shutter or a projection has no gather form (RTC_ERR_UNSUPPORTED).
+    Gather render_gather(const World &w, const rtc_ao &ao) const { return run_gather(w, ao, RTC_MODE_RENDER); }
+    Gather render_async_gather(const World &w, const rtc_ao &ao) const { return run_gather(w, ao, RTC_MODE_RENDER_ASYNC); }
 
   private:
     Aov run_aov(const World &w, uint32_t mode) const {
@@ -590,6 +609,20 @@ class Camera { // camera.rs:17-160
         World::Uploaded up(w);
         check(rtc_render_ao(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, a.shadow.data()), "Camera::render_ao");
         return a;
+    }
+    Gather run_gather(const World &w, const rtc_ao &ao, uint32_t mode) const {
+        if (has_lens_ || shutter_ || has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_gather with a lens, a shutter or a projection");
+        check(rtc_ao_validate(&ao), "Camera::render_gather");
+        rtc_camera c = flat_;
+        c.samples = antialiasing_samples;
+        Gather g;
+        g.width = hsize; g.height = vsize;
+        g.radiance.assign(static_cast<size_t>(hsize) * vsize * 3, 0.0);
+        g.bounce.assign(static_cast<size_t>(hsize) * vsize * 3, 0.0);
+        const rtc_gather_buffers b{g.radiance.data(), g.bounce.data()};
+        World::Uploaded up(w);
+        check(rtc_render_gather(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, &b), "Camera::render_gather");
+        return g;
     }
     Canvas run(const World &w, uint32_t mode) const {
         rtc_camera c = flat_;

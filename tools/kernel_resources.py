@@ -1,4 +1,4 @@
-"""Register / scratch / LDS use of every k_trace, k_aov and k_ao instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
+"""Register / scratch / LDS use of every k_trace, k_aov, k_ao and k_gather instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
 usage: python tools/kernel_resources.py [extra -D flags]"""
 import importlib.util
 import re
@@ -25,7 +25,7 @@ with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
-    if "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name:
+    if "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name and "k_gather" not in name and "k_add_scaled" not in name:
         continue
     def g(k):
         m = re.search(k + r": (\d+)", blk)
@@ -46,6 +46,10 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         tag = "k_ao<%s>" % a.group(1)
     elif "k_apply_ao" in name:
         tag = "k_apply_ao"
+    elif (a := re.search(r"k_gatherILi(\d)E", name)):  # the gather kernel: source, where the further lights come from
+        tag = "k_gather<%s" % a.group(1) + (",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">")
+    elif "k_add_scaled" in name:
+        tag = "k_add_scaled"
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")

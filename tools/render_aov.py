@@ -1,5 +1,6 @@
 """Render a YAML scene and what its pixels saw (the AOV planes, include/rtc.h "arbitrary output variables"):
     python tools/render_aov.py SCENE.yml OUTDIR [--near N --far F] [--exr [PLANES]] [--ao [RADIUS,USTEPS,VSTEPS]] [--ao-strength S]
+                                                [--gather [RADIUS,USTEPS,VSTEPS]] [--gather-strength S]
 writes OUTDIR/beauty.png (the colour frame) and depth.png, normal.png, index.png, shadow.png (rtc_aov_view_rgb8's pictures of
 the planes). Colour frame, planes and pictures stay in device memory; every file is encoded there (ImageEncoder.encode_device)
 and only the finished files cross PCIe — plus, when --near / --far are not both given, the depth plane, whose smallest and
@@ -9,7 +10,12 @@ shadow; all five when none is named) as Z, N.*, P.*, id and shadow channels (Flo
 "float files"). --ao also renders the ambient-occlusion plane (include/rtc.h "ambient occlusion") — with the pass the scene's
 camera asks for (ao-radius / ao-usteps / ao-vsteps) or the one given here — and writes OUTDIR/ao.png, the plane seen as a shadow
 plane (white: open, black: every sample occluded), and OUTDIR/beauty_ao.png, the colour frame with every pixel multiplied by
-1 - S * count / samples (rtc_canvas_apply_ao_device; S = --ao-strength, default 1), both made on the device. Needs an MI355X (there is no CPU path)."""
+1 - S * count / samples (rtc_canvas_apply_ao_device; S = --ao-strength, default 1), both made on the device. --gather also
+renders the one-bounce gather pass (include/rtc.h "colour bleeding") — with the pass the scene's camera asks for
+(gather-radius / gather-usteps / gather-vsteps) or the one given here — and writes OUTDIR/frame.png (the colour frame again,
+through the f64 canvas), OUTDIR/bounce.png (the bounce plane as a picture) and OUTDIR/frame_bounce.png, the colour frame plus
+S * bounce (rtc_canvas_add_scaled_device; S = --gather-strength, default 1), all made on the device. Needs an MI355X (there is
+no CPU path)."""
 import argparse
 import sys
 from pathlib import Path
@@ -28,6 +34,8 @@ def main(argv):
     ap.add_argument("--exr", nargs="?", const="depth,normal,point,index,shadow", default=None, metavar="PLANES")
     ap.add_argument("--ao", nargs="?", const="", default=None, metavar="RADIUS,USTEPS,VSTEPS")
     ap.add_argument("--ao-strength", type=float, default=1.0)
+    ap.add_argument("--gather", nargs="?", const="", default=None, metavar="RADIUS,USTEPS,VSTEPS")
+    ap.add_argument("--gather-strength", type=float, default=1.0)
     args = ap.parse_args(argv[1:])
     rtc = package()
     abi = __import__("importlib").import_module(rtc.__name__ + ".abi")
@@ -43,6 +51,15 @@ def main(argv):
             ao = rtc.load_yaml_ao(path=args.scene)[3]
             if ao is None:
                 ap.error("--ao: the scene's camera has no ao-radius; give RADIUS,USTEPS,VSTEPS")
+    gather = None
+    if args.gather is not None:
+        if args.gather:
+            radius, usteps, vsteps = args.gather.split(",")
+            gather = rtc.ao(float(radius), int(usteps), int(vsteps))
+        else:
+            gather = rtc.load_yaml_gather(path=args.scene)[4]
+            if gather is None:
+                ap.error("--gather: the scene's camera has no gather-radius; give RADIUS,USTEPS,VSTEPS")
     width, height = cam.hsize, cam.vsize
     out = Path(args.outdir)
     out.mkdir(parents=True, exist_ok=True)
@@ -93,6 +110,22 @@ def main(argv):
         ctx.apply_ao_device(rgb.data_ptr(), dev["shadow"].data_ptr(), n, args.ao_strength, width, height)
         ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
         sizes["beauty_ao"] = (out / "beauty_ao.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
+    if gather is not None:
+        rgb = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
+        bounce = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
+        rgba = torch.zeros(width * height * 4, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+
+        def save(name, d_canvas):   # Color::scale at gamma 1, then the PNG, on the device
+            ctx.canvas_to_rgba8_device(d_canvas, width, height, 1.0, rgba.data_ptr())
+            sizes[name] = (out / f"{name}.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
+
+        dw.render_rows(cam, 0, height, rgb.data_ptr())
+        dw.render_gather_device(cam, gather, {"bounce": bounce.data_ptr()})
+        save("frame", rgb.data_ptr())
+        save("bounce", bounce.data_ptr())
+        ctx.add_scaled_device(rgb.data_ptr(), bounce.data_ptr(), args.gather_strength, width, height)
+        save("frame_bounce", rgb.data_ptr())
     hits = int((dev["index"] >= 0).sum().item())
     print(f"{out}: {width}x{height}, {len(world)} shapes, {n_lights} light sample(s), {hits} of {width * height} pixels hit, "
           f"depth {near:.6g} .. {far:.6g}; bytes: " + ", ".join(f"{k if '.' in k else k + '.png'} {v}" for k, v in sizes.items()))
