@@ -486,17 +486,17 @@ def _copy_lights(arr, n: int) -> list:
     return out
 
 
-def load_yaml(text: str | None = None, path: str | None = None):
-    """jamis.yml-vocabulary loader -> (World, RtcCamera); the World holds every `add: light` of the file."""
-    shapes = C.POINTER(RtcShape)()
-    n = C.c_uint32(0)
+def _load_scene(entry: str, text: str | None, path: str | None, *extra, where: str | None = None):
+    """What the load_yaml* functions share: `entry` (its `_file` twin when `path` is given) called with the common buffers and
+    then `extra`, the entry point's further out-arguments, each by reference; failures raise under `where` (default: `entry`).
+    -> (World with every `add: light` of the file and the shapes copied out of the library's array, RtcCamera)."""
+    shapes, n = C.POINTER(RtcShape)(), C.c_uint32(0)
     lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
     err = C.create_string_buffer(512)
-    if path is not None:
-        st = lib().rtc_scene_load_yaml_area_lights_file(str(path).encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512)
-    else:
-        st = lib().rtc_scene_load_yaml_area_lights(text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512)
-    _check(st, "rtc_scene_load_yaml", err.value.decode(errors="replace"))
+    fn = getattr(lib(), entry + "_file" if path is not None else entry)
+    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
+            err, 512, *map(C.byref, extra))
+    _check(st, where or entry, err.value.decode(errors="replace"))
     w = World([_copy_light(lgts[i]) for i in range(nl.value)])
     for i in range(n.value):
         s = RtcShape()
@@ -506,116 +506,54 @@ def load_yaml(text: str | None = None, path: str | None = None):
     return w, cam
 
 
+def load_yaml(text: str | None = None, path: str | None = None):
+    """jamis.yml-vocabulary loader -> (World, RtcCamera); the World holds every `add: light` of the file."""
+    return _load_scene("rtc_scene_load_yaml_area_lights", text, path, where="rtc_scene_load_yaml")
+
+
 def load_yaml_lens(text: str | None = None, path: str | None = None):
     """load_yaml for scenes whose camera may have a thin lens (aperture / focal-distance / lens-usteps / lens-vsteps):
     -> (World, RtcCamera, RtcLens or None)."""
-    shapes = C.POINTER(RtcShape)()
-    n = C.c_uint32(0)
-    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
-    err = C.create_string_buffer(512)
     ln, has = RtcLens(), C.c_uint32(0)
-    if path is not None:
-        st = lib().rtc_scene_load_yaml_lens_file(str(path).encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512,
-                                                 C.byref(ln), C.byref(has))
-    else:
-        st = lib().rtc_scene_load_yaml_lens(text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam), err, 512,
-                                            C.byref(ln), C.byref(has))
-    _check(st, "rtc_scene_load_yaml_lens", err.value.decode(errors="replace"))
-    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
-    for i in range(n.value):
-        s = RtcShape()
-        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
-        w.shapes.append(s)
-    lib().rtc_free(shapes)
+    w, cam = _load_scene("rtc_scene_load_yaml_lens", text, path, ln, has)
     return w, cam, (ln if has.value else None)
 
 
 def load_yaml_ao(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes whose camera may ask for ambient occlusion (ao-radius / ao-usteps / ao-vsteps):
     -> (World, RtcCamera, RtcLens or None, RtcAo or None)."""
-    shapes = C.POINTER(RtcShape)()
-    n = C.c_uint32(0)
-    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
-    err = C.create_string_buffer(512)
     ln, has, a, has_a = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
-    fn = lib().rtc_scene_load_yaml_ao_file if path is not None else lib().rtc_scene_load_yaml_ao
-    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
-            err, 512, C.byref(ln), C.byref(has), C.byref(a), C.byref(has_a))
-    _check(st, "rtc_scene_load_yaml_ao", err.value.decode(errors="replace"))
-    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
-    for i in range(n.value):
-        s = RtcShape()
-        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
-        w.shapes.append(s)
-    lib().rtc_free(shapes)
+    w, cam = _load_scene("rtc_scene_load_yaml_ao", text, path, ln, has, a, has_a)
     return w, cam, (ln if has.value else None), (a if has_a.value else None)
 
 
 def load_yaml_gather(text: str | None = None, path: str | None = None):
     """load_yaml_ao for scenes whose camera may also ask for a gather pass (gather-radius / gather-usteps / gather-vsteps):
     -> (World, RtcCamera, RtcLens or None, RtcAo or None, RtcAo or None), the last the gather pass."""
-    shapes = C.POINTER(RtcShape)()
-    n = C.c_uint32(0)
-    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
-    err = C.create_string_buffer(512)
     ln, has, a, has_a, g, has_g = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
-    fn = lib().rtc_scene_load_yaml_gather_file if path is not None else lib().rtc_scene_load_yaml_gather
-    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
-            err, 512, C.byref(ln), C.byref(has), C.byref(a), C.byref(has_a), C.byref(g), C.byref(has_g))
-    _check(st, "rtc_scene_load_yaml_gather", err.value.decode(errors="replace"))
-    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
-    for i in range(n.value):
-        s = RtcShape()
-        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
-        w.shapes.append(s)
-    lib().rtc_free(shapes)
+    w, cam = _load_scene("rtc_scene_load_yaml_gather", text, path, ln, has, a, has_a, g, has_g)
     return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None)
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes whose camera may have a projection (projection: orthographic | panorama, ortho-width,
     pano-h-span, pano-v-span): -> (World, RtcCamera, RtcLens or None, RtcProjection or None)."""
-    shapes = C.POINTER(RtcShape)()
-    n = C.c_uint32(0)
-    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
-    err = C.create_string_buffer(512)
     ln, has, pj, has_pj = RtcLens(), C.c_uint32(0), RtcProjection(), C.c_uint32(0)
-    fn = lib().rtc_scene_load_yaml_projection_file if path is not None else lib().rtc_scene_load_yaml_projection
-    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
-            err, 512, C.byref(ln), C.byref(has), C.byref(pj), C.byref(has_pj))
-    _check(st, "rtc_scene_load_yaml_projection", err.value.decode(errors="replace"))
-    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
-    for i in range(n.value):
-        s = RtcShape()
-        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
-        w.shapes.append(s)
-    lib().rtc_free(shapes)
+    w, cam = _load_scene("rtc_scene_load_yaml_projection", text, path, ln, has, pj, has_pj)
     return w, cam, (ln if has.value else None), (pj if has_pj.value else None)
 
 
 def load_yaml_motion(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes with motion blur (a shape's `motion:` transform list, the camera's `shutter-samples`):
     -> (World, RtcCamera, RtcLens or None, [RtcMotion], samples) — what Shutter.render takes."""
-    shapes, mots = C.POINTER(RtcShape)(), C.POINTER(RtcMotion)()
-    n, nm, samples = C.c_uint32(0), C.c_uint32(0), C.c_uint32(1)
-    lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
-    err = C.create_string_buffer(512)
     ln, has = RtcLens(), C.c_uint32(0)
-    fn = lib().rtc_scene_load_yaml_motion_file if path is not None else lib().rtc_scene_load_yaml_motion
-    st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
-            err, 512, C.byref(ln), C.byref(has), C.byref(mots), C.byref(nm), C.byref(samples))
-    _check(st, "rtc_scene_load_yaml_motion", err.value.decode(errors="replace"))
-    w = World([_copy_light(lgts[i]) for i in range(nl.value)])
-    for i in range(n.value):
-        s = RtcShape()
-        C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
-        w.shapes.append(s)
+    mots, nm, samples = C.POINTER(RtcMotion)(), C.c_uint32(0), C.c_uint32(1)
+    w, cam = _load_scene("rtc_scene_load_yaml_motion", text, path, ln, has, mots, nm, samples)
     motions = []
     for i in range(nm.value):
         m = RtcMotion()
         C.memmove(C.byref(m), C.byref(mots[i]), C.sizeof(RtcMotion))
         motions.append(m)
-    lib().rtc_free(shapes)
     lib().rtc_free(mots)
     return w, cam, (ln if has.value else None), motions, samples.value
 

@@ -1674,11 +1674,15 @@ rtc_status rtc_canvas_to_rgba8_device(rtc_context *ctx, const void *d_rgb, uint3
 // ---- AOV planes (include/rtc.h, "arbitrary output variables") ---------------------------------------------------------
 static bool aov_any(const rtc_aov_buffers *b) { return b->index || b->depth || b->point || b->normal || b->flags || b->shadow; }
 
-rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
-                                 const rtc_aov_buffers *d) {
-    if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || !aov_any(d)) return RTC_ERR_ARG;
-    if (((size_t)d->depth | (size_t)d->point | (size_t)d->normal) % sizeof(double) != 0 || (size_t)d->index % 4u != 0 || (size_t)d->shadow % 2u != 0)
-        return RTC_ERR_ARG;
+extern "C++" { // (two templates: the entry points around them have C linkage)
+// What the device entry points of the three tile passes (k_aov, k_ao, k_gather: one workgroup per 8x8 tile) share behind
+// their own argument checks: the tile-count limit, the World's current generation, k_aov's plan (the same grid for all three,
+// no dynamic LDS), the World's tables in `P` and the common fields of the pass's zeroed parameter block `A`; then
+// fill(G) -> rtc_status, the pass's own set-up and fields, and launch(P, src) -> hipError_t, its rtc_launch_* call, between
+// order_behind_build and record_read.
+template <class FILL, class LAUNCH>
+static rtc_status tile_pass(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, TileParams &A,
+                            FILL &&fill, LAUNCH &&launch) {
     if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
     HIP_TRY(hipSetDevice(ctx->device));
     rtc_world::Gen *gen = nullptr;
@@ -1690,13 +1694,9 @@ rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc
     LaunchPlan plan;
     rtc_plan_launch(in, plan);
     if (plan.status != RTC_OK) return (rtc_status)plan.status;
-    LaunchLights LL;
-    if (d->shadow) lights_of(G, LL);
     RenderParams P;
     planned_params(ctx, w, G, plan, P);
     fill_camera(P, cam);
-    AovParams A;
-    std::memset(&A, 0, sizeof A);
     A.cam = P.views[0];
     A.W = cam->hsize;
     A.H = cam->vsize;
@@ -1705,12 +1705,46 @@ rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc
     A.n = G.n;
     A.ngroups = G.ngroups;
     A.pre_limit = G.pre_limit;
-    for (int k = 0; k < 3; ++k) A.light_pos[k] = G.light.position[k];
-    A.index = d->index; A.depth = d->depth; A.point = d->point; A.normal = d->normal; A.flags = d->flags; A.shadow = d->shadow;
+    const rtc_status fs = fill(G);
+    if (fs != RTC_OK) return fs;
     HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
-    HIP_TRY(rtc_launch_aov(&A, &P, plan.src, LL.xl, LL.lt, ctx->stream));
+    HIP_TRY(launch(P, plan.src));
     HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
     return RTC_OK;
+}
+
+// The host-buffer twins' way back: each wanted plane (bytes != 0) copied on the context's stream, then the stream's end
+// awaited — after a failed copy too, which ends the copying.
+struct PlaneCopy {
+    void *dst;
+    const void *src;
+    size_t bytes;
+};
+template <size_t N> static rtc_status copy_planes_back(rtc_context *ctx, const PlaneCopy (&planes)[N]) {
+    rtc_status out = RTC_OK;
+    for (const PlaneCopy &c : planes)
+        if (out == RTC_OK && c.bytes && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
+    return out;
+}
+} // extern "C++"
+
+rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                 const rtc_aov_buffers *d) {
+    if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || !aov_any(d)) return RTC_ERR_ARG;
+    if (((size_t)d->depth | (size_t)d->point | (size_t)d->normal) % sizeof(double) != 0 || (size_t)d->index % 4u != 0 || (size_t)d->shadow % 2u != 0)
+        return RTC_ERR_ARG;
+    AovParams A;
+    std::memset(&A, 0, sizeof A);
+    LaunchLights LL;
+    return tile_pass(ctx, w, cam, mode, flags, A,
+        [&](rtc_world::Gen &G) {
+            if (d->shadow) lights_of(G, LL);
+            for (int k = 0; k < 3; ++k) A.light_pos[k] = G.light.position[k];
+            A.index = d->index; A.depth = d->depth; A.point = d->point; A.normal = d->normal; A.flags = d->flags; A.shadow = d->shadow;
+            return RTC_OK;
+        },
+        [&](const RenderParams &P, int src) { return rtc_launch_aov(&A, &P, src, LL.xl, LL.lt, ctx->stream); });
 }
 
 rtc_status rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
@@ -1740,11 +1774,9 @@ rtc_status rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera
     d.flags = host->flags ? base + off[5] : nullptr;
     const rtc_status ls = rtc_render_aov_device(ctx, w, cam, mode, flags, &d);
     if (ls != RTC_OK) return ls;
-    rtc_status out = RTC_OK;
-    for (int k = 0; k < 6 && out == RTC_OK; ++k)
-        if (sizes[k] && hipMemcpyAsync(dst[k], base + off[k], sizes[k], hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    return out;
+    PlaneCopy back[6];
+    for (int k = 0; k < 6; ++k) back[k] = PlaneCopy{dst[k], base + off[k], sizes[k]};
+    return copy_planes_back(ctx, back);
 }
 
 rtc_status rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_aov_buffers *d, uint32_t width, uint32_t height, double near,
@@ -1790,39 +1822,16 @@ rtc_status rtc_render_ao_device(rtc_context *ctx, const rtc_world *w, const rtc_
                                 uint32_t flags, uint16_t *d_ao) {
     if (check_render_args(ctx, w, cam, mode, d_ao, nullptr) != RTC_OK || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
     if ((size_t)d_ao % 2u != 0) return RTC_ERR_ARG;
-    if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
-    HIP_TRY(hipSetDevice(ctx->device));
-    rtc_world::Gen *gen = nullptr;
-    const rtc_status hs = current_gen(w, &gen);
-    if (hs != RTC_OK) return hs;
-    rtc_world::Gen &G = *gen;
-    LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_AOV, flags); // k_aov's plan: the same grid, no dynamic LDS
-    in.hsize = cam->hsize; in.vsize = cam->vsize; in.mode = mode;
-    LaunchPlan plan;
-    rtc_plan_launch(in, plan);
-    if (plan.status != RTC_OK) return (rtc_status)plan.status;
-    const rtc_status ts = ao_table(ctx, ao);
-    if (ts != RTC_OK) return ts;
-    RenderParams P;
-    planned_params(ctx, w, G, plan, P);
-    fill_camera(P, cam);
     AoParams A;
     std::memset(&A, 0, sizeof A);
-    A.cam = P.views[0];
-    A.W = cam->hsize;
-    A.H = cam->vsize;
-    A.mode = mode;
-    A.tiles_x = plan.grid_x;
-    A.n = G.n;
-    A.ngroups = G.ngroups;
-    A.pre_limit = G.pre_limit;
-    A.radius = ao->radius;
-    A.nsamples = ao->usteps * ao->vsteps;
-    A.out = d_ao;
-    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
-    HIP_TRY(rtc_launch_ao(&A, ctx->d_ao_dirs.get(), &P, plan.src, ctx->stream));
-    HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
-    return RTC_OK;
+    return tile_pass(ctx, w, cam, mode, flags, A,
+        [&](rtc_world::Gen &) {
+            A.radius = ao->radius;
+            A.nsamples = ao->usteps * ao->vsteps;
+            A.out = d_ao;
+            return ao_table(ctx, ao);
+        },
+        [&](const RenderParams &P, int src) { return rtc_launch_ao(&A, ctx->d_ao_dirs.get(), &P, src, ctx->stream); });
 }
 
 rtc_status rtc_render_ao(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
@@ -1835,10 +1844,7 @@ rtc_status rtc_render_ao(rtc_context *ctx, const rtc_world *w, const rtc_camera 
     if (st != RTC_OK) return st;
     const rtc_status ls = rtc_render_ao_device(ctx, w, cam, ao, mode, flags, ctx->d_ao.get());
     if (ls != RTC_OK) return ls;
-    rtc_status out = RTC_OK;
-    if (hipMemcpyAsync(ao_out, ctx->d_ao.get(), sizeof(uint16_t) * px, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    return out;
+    return copy_planes_back(ctx, {{ao_out, ctx->d_ao.get(), sizeof(uint16_t) * px}});
 }
 
 rtc_status rtc_canvas_apply_ao_device(rtc_context *ctx, void *d_rgb, const void *d_ao, uint32_t n_samples, double strength, uint32_t width,
@@ -1858,46 +1864,23 @@ rtc_status rtc_render_gather_device(rtc_context *ctx, const rtc_world *w, const 
     if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
     if (!d->radiance && !d->bounce) return RTC_ERR_ARG;
     if (((size_t)d->radiance | (size_t)d->bounce) % sizeof(double) != 0) return RTC_ERR_ARG;
-    if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
-    HIP_TRY(hipSetDevice(ctx->device));
-    rtc_world::Gen *gen = nullptr;
-    const rtc_status hs = current_gen(w, &gen);
-    if (hs != RTC_OK) return hs;
-    rtc_world::Gen &G = *gen;
-    LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_AOV, flags); // k_aov's plan: the same grid, no dynamic LDS
-    in.hsize = cam->hsize; in.vsize = cam->vsize; in.mode = mode;
-    LaunchPlan plan;
-    rtc_plan_launch(in, plan);
-    if (plan.status != RTC_OK) return (rtc_status)plan.status;
-    const rtc_status ts = ao_table(ctx, ao); // the fan is the AO pass's: one table per context, whichever pass filled it
-    if (ts != RTC_OK) return ts;
-    LaunchLights LL;
-    lights_of(G, LL);
-    RenderParams P;
-    planned_params(ctx, w, G, plan, P);
-    fill_camera(P, cam);
     GatherParams A;
     std::memset(&A, 0, sizeof A);
-    A.cam = P.views[0];
-    A.W = cam->hsize;
-    A.H = cam->vsize;
-    A.mode = mode;
-    A.tiles_x = plan.grid_x;
-    A.n = G.n;
-    A.ngroups = G.ngroups;
-    A.pre_limit = G.pre_limit;
-    A.radius = ao->radius;
-    A.nsamples = ao->usteps * ao->vsteps;
-    for (int k = 0; k < 3; ++k) {
-        A.light_pos[k] = G.light.position[k];
-        A.light_int[k] = G.light.intensity[k];
-    }
-    A.radiance = d->radiance;
-    A.bounce = d->bounce;
-    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
-    HIP_TRY(rtc_launch_gather(&A, ctx->d_ao_dirs.get(), &P, plan.src, LL.xl, LL.lt, ctx->stream));
-    HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
-    return RTC_OK;
+    LaunchLights LL;
+    return tile_pass(ctx, w, cam, mode, flags, A,
+        [&](rtc_world::Gen &G) {
+            lights_of(G, LL);
+            A.radius = ao->radius;
+            A.nsamples = ao->usteps * ao->vsteps;
+            for (int k = 0; k < 3; ++k) {
+                A.light_pos[k] = G.light.position[k];
+                A.light_int[k] = G.light.intensity[k];
+            }
+            A.radiance = d->radiance;
+            A.bounce = d->bounce;
+            return ao_table(ctx, ao); // the fan is the AO pass's: one table per context, whichever pass filled it
+        },
+        [&](const RenderParams &P, int src) { return rtc_launch_gather(&A, ctx->d_ao_dirs.get(), &P, src, LL.xl, LL.lt, ctx->stream); });
 }
 
 rtc_status rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
@@ -1913,11 +1896,8 @@ rtc_status rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_cam
     d.bounce = host->bounce ? ctx->d_gather.get() + plane : nullptr;
     const rtc_status ls = rtc_render_gather_device(ctx, w, cam, ao, mode, flags, &d);
     if (ls != RTC_OK) return ls;
-    rtc_status out = RTC_OK;
-    if (d.radiance && hipMemcpyAsync(host->radiance, d.radiance, sizeof(double) * plane, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    if (d.bounce && hipMemcpyAsync(host->bounce, d.bounce, sizeof(double) * plane, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) out = RTC_ERR_DEVICE;
-    return out;
+    return copy_planes_back(ctx, {{host->radiance, d.radiance, d.radiance ? sizeof(double) * plane : 0u},
+                                  {host->bounce, d.bounce, d.bounce ? sizeof(double) * plane : 0u}});
 }
 
 rtc_status rtc_canvas_add_scaled_device(rtc_context *ctx, void *d_rgb, const void *d_plane, double strength, uint32_t width, uint32_t height) {

@@ -208,15 +208,21 @@ struct DevProjection {
     const double *col, *row;     // panorama only
 };
 
-// AOV launches (rtc_render_aov*, include/rtc.h): k_aov's parameter block. The World's tables ride behind it as separate
-// kernel arguments, as for k_trace; a World with several lights adds its DevExtraLights / DevLightTable as the last argument
-// of the SHADOW instantiations. One wave = one 8x8 pixel tile, tile = workgroup id, tiles_x tiles per tile row. A plane
-// pointer that is NULL is a plane that is neither computed nor written (wave-uniform).
-struct AovParams {
+// The tile passes (k_aov, k_ao, k_gather): one wave = one 8x8 pixel tile, tile = workgroup id, tiles_x tiles per tile row.
+// What their parameter blocks open with, under the names for_each_object and the passes' shared stages read; the host fills
+// it in one place (tile_pass, rtc_api.cpp). The World's tables ride behind the block as separate kernel arguments, as for
+// k_trace. The blocks' sizes and field offsets are kernel-argument offsets, part of every tile pass's instruction stream:
+// pinned below.
+struct TileParams {
     DevCamera cam;
     uint32_t W, H, mode, tiles_x;
-    uint32_t n, ngroups;       // the World's objects and groups of 64 (for_each_object reads them by these names)
+    uint32_t n, ngroups;       // the World's objects and groups of 64
     double pre_limit;          // ... and the limit of its prefilter records (DevPre)
+};
+// AOV launches (rtc_render_aov*, include/rtc.h): k_aov's parameter block. A World with several lights adds its
+// DevExtraLights / DevLightTable as the last argument of the SHADOW instantiations. A plane pointer that is NULL is a plane
+// that is neither computed nor written (wave-uniform).
+struct AovParams : TileParams {
     double light_pos[3];       // L[0]
     int32_t *index;
     double *depth, *point, *normal;
@@ -235,27 +241,35 @@ struct AovViewParams {
 };
 // k_ao (rtc_render_ao_device): the ambient-occlusion plane of a W x H frame. The sample table (3 doubles per sample, the
 // host's rtc_ao_expand) is a kernel argument of its own, so that its reads are scalar loads.
-struct AoParams {
-    DevCamera cam;
-    uint32_t W, H, mode, tiles_x;
-    uint32_t n, ngroups;       // the World's objects and groups of 64 (for_each_object reads them by these names)
-    double pre_limit;          // ... and the limit of its prefilter records (DevPre)
+struct AoParams : TileParams {
     double radius;             // rtc_ao::radius (+inf: unbounded)
     uint32_t nsamples, _pad;   // 1..RTC_MAX_AO_SAMPLES
     uint16_t *out;
 };
-// k_gather (rtc_render_gather_device): the radiance and bounce planes of a W x H frame. AoParams' fields under the same
-// names, the World's first light as lighting() reads it (light_int), and the planes (nullptr: not wanted).
-struct GatherParams {
-    DevCamera cam;
-    uint32_t W, H, mode, tiles_x;
-    uint32_t n, ngroups;
-    double pre_limit;
+// k_gather (rtc_render_gather_device): the radiance and bounce planes of a W x H frame. AoParams' radius and nsamples under
+// the same names, the World's first light as lighting() reads it (light_int), and the planes (nullptr: not wanted).
+struct GatherParams : TileParams {
     double radius;
     uint32_t nsamples, _pad;
     double light_pos[3], light_int[3]; // L[0]; the further lights are the kernel's trailing argument, as k_aov's
     double *radiance, *bounce;
 };
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof" // (a block with a base is not standard-layout; both compilers lay it out as C would)
+#define RTC_PIN(T, field, at) static_assert(__builtin_offsetof(T, field) == (at), #T "::" #field " moved")
+static_assert(sizeof(DevCamera) == 152 && sizeof(TileParams) == 184, "the tile passes' common fields changed size");
+RTC_PIN(TileParams, cam, 0); RTC_PIN(TileParams, W, 152); RTC_PIN(TileParams, H, 156); RTC_PIN(TileParams, mode, 160);
+RTC_PIN(TileParams, tiles_x, 164); RTC_PIN(TileParams, n, 168); RTC_PIN(TileParams, ngroups, 172); RTC_PIN(TileParams, pre_limit, 176);
+static_assert(sizeof(AovParams) == 256, "AovParams changed size");
+RTC_PIN(AovParams, light_pos, 184); RTC_PIN(AovParams, index, 208); RTC_PIN(AovParams, depth, 216); RTC_PIN(AovParams, point, 224);
+RTC_PIN(AovParams, normal, 232); RTC_PIN(AovParams, flags, 240); RTC_PIN(AovParams, shadow, 248);
+static_assert(sizeof(AoParams) == 208, "AoParams changed size");
+RTC_PIN(AoParams, radius, 184); RTC_PIN(AoParams, nsamples, 192); RTC_PIN(AoParams, out, 200);
+static_assert(sizeof(GatherParams) == 264, "GatherParams changed size");
+RTC_PIN(GatherParams, radius, 184); RTC_PIN(GatherParams, nsamples, 192); RTC_PIN(GatherParams, light_pos, 200);
+RTC_PIN(GatherParams, light_int, 224); RTC_PIN(GatherParams, radiance, 248); RTC_PIN(GatherParams, bounce, 256);
+#undef RTC_PIN
+#pragma GCC diagnostic pop
 
 struct RenderParams {
     const DevIsect *isect;

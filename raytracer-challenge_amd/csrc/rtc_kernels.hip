@@ -2522,11 +2522,69 @@ extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, co
     return hipGetLastError();
 }
 
+// ---- stages the tile passes share (k_aov, k_ao, k_gather) -----------------------------------------------------------
+// Each in the form that leaves the kernels' instruction streams as they were ("Shared stages of the tile
+// passes"): results by value, the tables filled in place. The primary pass's closest-hit walk, the shadow test of one light, the
+// sample direction and the whole hit frame as one function are not among them: as functions they compile to other code.
+
+// The World's tables from a tile pass's eleven pointer arguments (k_trace's, less prim and idtab).
+DEVI void tile_tables(Tables &T, const DevIsect *isect, const uint32_t *kind, const DevShade *shade, const DevBound *bound, const DevIsect *isect_s,
+                      const uint32_t *kind_s, const DevBound *bound_s, const uint32_t *orig_s, const DevBound *gbound, const DevPre *pre,
+                      const DevPre *pre_s) {
+    T.isect = isect; T.kind = kind; T.shade = shade; T.bound = bound;
+    T.isect_s = isect_s; T.kind_s = kind_s; T.bound_s = bound_s; T.orig_s = orig_s; T.gbound = gbound;
+    T.pre = pre; T.pre_s = pre_s;
+}
+
+// The lane's pixel: one wave = one 8x8 tile = one workgroup, tile id = workgroup id, one pixel per lane. in_range: the pixel
+// exists (partial tiles on the right and bottom edges mask their lanes) and is stored; traced: it also gets a ray —
+// Camera::render leaves the last row and column untouched (camera.rs:120-121), they get the miss values.
+struct TileLane { uint32_t px, py; bool in_range, traced; };
+DEVI TileLane tile_lane(const TileParams &A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
+    const bool in_range = px < A.W && py < A.H;
+    return TileLane{px, py, in_range, in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H))};
+}
+
+// ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76. The origin is the same in every lane (SGPRs): the primary bundle's shared apex.
+struct PrimaryRay { V3 ro, rd; };
+DEVI PrimaryRay primary_ray(const DevCamera &C, uint32_t px, uint32_t py) {
+    V3 cam_origin = xpoint(C.vinv, mk(0., 0., 0.));
+    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z));
+    return PrimaryRay{cam_origin, primary_dir(C, cam_origin, px, py)};
+}
+
+// The hit frame of k_ao and k_gather, in two parts. Intersection::compute_vectors' normal (shape.rs:144-152, 75-96) of object
+// `hidx` at `point`, flipped to face a ray of direction rd; and rtc_ao.h's tangent frame about it, built once per pixel, in
+// front of the sample loop (its one division).
+DEVI V3 facing_normal(const Tables &T, int hidx, V3 point, V3 rd) {
+    V3 normal = shape_normal(T.shade + hidx, T.isect[hidx].m, point);
+    if (vdot(normal, vneg(rd)) < 0.0) normal = vneg(normal);
+    return normal;
+}
+struct Tangents { V3 tv, sv; };
+DEVI Tangents tangent_frame(V3 normal) {
+    const double nn[3] = {normal.x, normal.y, normal.z};
+    double t3[3], s3[3];
+    rtc_ao_frame(nn, t3, s3);
+    return Tangents{mk(t3[0], t3[1], t3[2]), mk(s3[0], s3[1], s3[2])};
+}
+
+// The reach of a sample's bundle (k_ao, k_gather): per sample a bundle over the lanes' rays, origins per lane (apex = the axis
+// lane's over_point, rho the spread of the others around it). It is make_bundle's unbounded per-lane-origin form with the reach
+// put in afterwards, not its REACH form: that one is for segments the exact test walks from the far end (spread = reach) and
+// gives up on an unbounded reach, where these passes start every exact ray at its lane's origin (spread = rho) and
+// radius = +inf still has a cone to cull with. Rounded up as the REACH form rounds it (f32, 1e-4 relative: the direction is
+// unit to a few ulp).
+DEVI void limit_reach(Bundle &Bk, double radius) {
+    if (radius < 1e30) Bk.tmax = uniform_f64((double)(fmaxf(0.f, (float)radius) * 1.0001f + 1e-30f));
+}
+
 // ---- AOV planes (rtc_render_aov*, include/rtc.h): what each pixel's centre ray saw ----------------------------------
 // k_trace's primary pass, its compute_vectors and — SHADOW only — one any-hit pass per light sample, and nothing of the
-// shading: no material, no pattern, no recursion, no counters. One wave = one 8x8 pixel tile = one workgroup (tile id =
-// workgroup id, partial tiles on the right and bottom edges mask their lanes), so the primary bundle's cone is tight; the
-// cull walks are wave-level code (ballots, DPP) and stay in converged code, every lane of the wave reaching them.
+// shading: no material, no pattern, no recursion, no counters. One wave = one 8x8 pixel tile (tile_lane), so the primary
+// bundle's cone is tight; the cull walks are wave-level code (ballots, DPP) and stay in converged code, every lane reaching them.
 // SRC: SRC_SMEM (RTC_FLAG_NO_CULL), SRC_CULL or SRC_CULL2 (the ordered walk with the skip functor, as k_trace's large-world
 // primary pass). There is no binning kernel, no per-launch DevPrim table: closest_world transforms the origin itself, with
 // the arithmetic k_prep_primary has. XL: empty for one light, or the World's further lights (DevExtraLights / DevLightTable),
@@ -2540,21 +2598,13 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
     static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "AOV launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
     static_assert(sizeof...(XL) <= (SHADOW ? 1 : 0), "further lights only where shadow rays are cast, one block at most");
     Tables T{};
-    T.isect = t_isect; T.kind = t_kind; T.shade = t_shade; T.bound = t_bound;
-    T.isect_s = t_isect_s; T.kind_s = t_kind_s; T.bound_s = t_bound_s; T.orig_s = t_orig_s; T.gbound = t_gbound;
-    T.pre = t_pre; T.pre_s = t_pre_s;
+    tile_tables(T, t_isect, t_kind, t_shade, t_bound, t_isect_s, t_kind_s, t_bound_s, t_orig_s, t_gbound, t_pre, t_pre_s);
     const LdsView L{};
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
-    const bool in_range = px < A.W && py < A.H;
-    // Camera::render leaves the last row and column untouched (camera.rs:120-121): they get the miss values
-    const bool traced = in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H));
-
-    // ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76
-    V3 cam_origin = xpoint(A.cam.vinv, mk(0., 0., 0.));
-    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
-    const V3 ro = cam_origin;
-    const V3 rd = primary_dir(A.cam, cam_origin, px, py);
+    const TileLane lane = tile_lane(A);
+    const uint32_t px = lane.px, py = lane.py;
+    const bool in_range = lane.in_range, traced = lane.traced;
+    const PrimaryRay pr = primary_ray(A.cam, px, py);
+    const V3 ro = pr.ro, rd = pr.rd;
 
     // ---- World::intersect + get_hit, streaming form (k_trace's primary pass without the tile lists) ----
     double best = __builtin_inf();
@@ -2562,7 +2612,7 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
     Bundle B{};
     B.off = true;
     if constexpr (IS_CULL(SRC)) {
-        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
+        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, ro, ro, rd, 0.);
     }
     if constexpr (SRC == SRC_CULL2)
         for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
@@ -2647,14 +2697,10 @@ __global__ void __launch_bounds__(256) k_aov_view(const AovViewParams V) {
 // lane stored — with, in place of the light loop, a wave-uniform loop over the samples of the host's table: sample k's local
 // direction is read by a uniform address (scalar loads, SGPRs), each lane turns it about its own normal (rtc_ao.h: the
 // header's arithmetic, no sin or cos here) and the bounded any-hit walk counts the lanes that meet something with t < radius.
-// The tangent frame is built once per pixel, in front of the loop (its one division). Lanes without a hit carry
-// pending = false through every walk: the walks are wave-level code and stay converged.
-// Cull sources: per sample a bundle over the lanes' rays, origins per lane (apex = the axis lane's over_point, rho the spread
-// of the others around it). It is make_bundle's unbounded per-lane-origin form with the reach put in afterwards, not its
-// REACH form: that one is for segments the exact test walks from the far end (spread = reach) and gives up on an unbounded
-// reach, where this pass starts every exact ray at its lane's origin (spread = rho) and radius = +inf still has a cone to
-// cull with. Where a tile's normals diverge the cone passes 0.98 / the axis dot falls under 0.2 and the bundle goes off:
-// every object is a candidate, which is correct and slower. Results do not depend on SRC.
+// Lanes without a hit carry pending = false through every walk: the walks are wave-level code and stay converged.
+// Cull sources: per sample a bundle over the lanes' rays (limit_reach). Where a tile's normals diverge the cone passes 0.98 /
+// the axis dot falls under 0.2 and the bundle goes off: every object is a candidate, which is correct and slower. Results do
+// not depend on SRC.
 // The per-lane prefilter (ray_touches_pre: it takes d.d, so the direction need not be unit) stands in front of the exact tests
 // in the one-level walks too, where k_aov's shadow passes have it for two-level Worlds only: a shadow bundle always holds, an AO
 // bundle is off wherever a tile's normals diverge, and then the filter is the only cull there is. RTC_AO_LANE_FILTER_ONE_LEVEL=0
@@ -2662,6 +2708,7 @@ __global__ void __launch_bounds__(256) k_aov_view(const AovViewParams V) {
 #ifndef RTC_AO_LANE_FILTER_ONE_LEVEL
 #define RTC_AO_LANE_FILTER_ONE_LEVEL 1
 #endif
+template <int SRC> constexpr bool SAMPLE_LANE_FILTER = SRC == SRC_CULL2 || (SRC == SRC_CULL && RTC_AO_LANE_FILTER_ONE_LEVEL); // the sample walks of k_ao and k_gather
 template <int SRC>
 __global__ void __launch_bounds__(64, RTC_WAVES_PER_SIMD)
 k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
@@ -2670,21 +2717,13 @@ k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__rest
      const DevBound *__restrict__ t_gbound, const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s) {
     static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "AO launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
     Tables T{};
-    T.isect = t_isect; T.kind = t_kind; T.shade = t_shade; T.bound = t_bound;
-    T.isect_s = t_isect_s; T.kind_s = t_kind_s; T.bound_s = t_bound_s; T.orig_s = t_orig_s; T.gbound = t_gbound;
-    T.pre = t_pre; T.pre_s = t_pre_s;
+    tile_tables(T, t_isect, t_kind, t_shade, t_bound, t_isect_s, t_kind_s, t_bound_s, t_orig_s, t_gbound, t_pre, t_pre_s);
     const LdsView L{};
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
-    const bool in_range = px < A.W && py < A.H;
-    // Camera::render leaves the last row and column untouched (camera.rs:120-121): they get the miss value
-    const bool traced = in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H));
-
-    // ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76
-    V3 cam_origin = xpoint(A.cam.vinv, mk(0., 0., 0.));
-    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
-    const V3 ro = cam_origin;
-    const V3 rd = primary_dir(A.cam, cam_origin, px, py);
+    const TileLane lane = tile_lane(A);
+    const uint32_t px = lane.px, py = lane.py;
+    const bool in_range = lane.in_range, traced = lane.traced;
+    const PrimaryRay pr = primary_ray(A.cam, px, py);
+    const V3 ro = pr.ro, rd = pr.rd;
 
     // ---- World::intersect + get_hit, streaming form (k_aov's primary pass) ----
     double best = __builtin_inf();
@@ -2692,7 +2731,7 @@ k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__rest
     Bundle B{};
     B.off = true;
     if constexpr (IS_CULL(SRC)) {
-        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
+        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, ro, ro, rd, 0.);
     }
     if constexpr (SRC == SRC_CULL2)
         for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
@@ -2704,16 +2743,11 @@ k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__rest
     V3 normal = mk(0., 0., 0.), over = mk(0., 0., 0.), tv = mk(0., 0., 0.), sv = mk(0., 0., 0.);
     if (hit) {
         const V3 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
-        const DevShade *S = T.shade + hidx;
-        const double *m_obj = T.isect[hidx].m;
-        normal = shape_normal(S, m_obj, point);
-        if (vdot(normal, vneg(rd)) < 0.0) normal = vneg(normal);
+        normal = facing_normal(T, hidx, point, rd);
         over = vadd(point, vmul(normal, RTC_EPSILON));
-        const double nn[3] = {normal.x, normal.y, normal.z};
-        double t3[3], s3[3];
-        rtc_ao_frame(nn, t3, s3);
-        tv = mk(t3[0], t3[1], t3[2]);
-        sv = mk(s3[0], s3[1], s3[2]);
+        const Tangents tf = tangent_frame(normal);
+        tv = tf.tv;
+        sv = tf.sv;
     }
 
     // ---- one bounded any-hit pass per sample, in the table's order: how many meet something within the radius ----
@@ -2730,11 +2764,10 @@ k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__rest
         if constexpr (IS_CULL(SRC)) {
             if (ballot(hit) != 0ull) {
                 Bk = make_bundle<false, false>(hit, over, over, dir, 0.);
-                // the reach, rounded up as make_bundle's REACH form rounds it (f32, 1e-4 relative: the direction is unit to a few ulp)
-                if (radius < 1e30) Bk.tmax = uniform_f64((double)(fmaxf(0.f, (float)radius) * 1.0001f + 1e-30f));
+                limit_reach(Bk, radius);
             }
         }
-        for_each_object<SRC, SRC == SRC_CULL2 || (SRC == SRC_CULL && RTC_AO_LANE_FILTER_ONE_LEVEL)>(A, T, L, pending, Bk, AnyHit{pending, over, dir, radius, occluded}, over, dir);
+        for_each_object<SRC, SAMPLE_LANE_FILTER<SRC>>(A, T, L, pending, Bk, AnyHit{pending, over, dir, radius, occluded}, over, dir);
         if (occluded) ++count;
     }
 
@@ -2782,21 +2815,13 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
     static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "gather launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
     static_assert(sizeof...(XL) <= 1, "the further lights: one block at most");
     Tables T{};
-    T.isect = t_isect; T.kind = t_kind; T.shade = t_shade; T.bound = t_bound;
-    T.isect_s = t_isect_s; T.kind_s = t_kind_s; T.bound_s = t_bound_s; T.orig_s = t_orig_s; T.gbound = t_gbound;
-    T.pre = t_pre; T.pre_s = t_pre_s;
+    tile_tables(T, t_isect, t_kind, t_shade, t_bound, t_isect_s, t_kind_s, t_bound_s, t_orig_s, t_gbound, t_pre, t_pre_s);
     const LdsView L{};
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = (blockIdx.x % A.tiles_x) * 8u + (lane & 7u), py = (blockIdx.x / A.tiles_x) * 8u + (lane >> 3);
-    const bool in_range = px < A.W && py < A.H;
-    // Camera::render leaves the last row and column untouched (camera.rs:120-121): they get the miss value
-    const bool traced = in_range && !(A.mode == RTC_MODE_RENDER && (px + 1u >= A.W || py + 1u >= A.H));
-
-    // ray_for_pixel(x, 0.5, y, 0.5): camera.rs:64-76
-    V3 cam_origin = xpoint(A.cam.vinv, mk(0., 0., 0.));
-    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z)); // same in every lane
-    const V3 ro = cam_origin;
-    const V3 rd = primary_dir(A.cam, cam_origin, px, py);
+    const TileLane lane = tile_lane(A);
+    const uint32_t px = lane.px, py = lane.py;
+    const bool in_range = lane.in_range, traced = lane.traced;
+    const PrimaryRay pr = primary_ray(A.cam, px, py);
+    const V3 ro = pr.ro, rd = pr.rd;
 
     // ---- World::intersect + get_hit, streaming form (k_aov's primary pass) ----
     double best = __builtin_inf();
@@ -2804,7 +2829,7 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
     Bundle B{};
     B.off = true;
     if constexpr (IS_CULL(SRC)) {
-        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, cam_origin, ro, rd, 0.);
+        if (ballot(traced) != 0ull) B = make_bundle<true, false>(traced, ro, ro, rd, 0.);
     }
     if constexpr (SRC == SRC_CULL2)
         for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
@@ -2816,16 +2841,11 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
     V3 normal = mk(0., 0., 0.), over = mk(0., 0., 0.), tv = mk(0., 0., 0.), sv = mk(0., 0., 0.);
     if (hit) {
         const V3 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
-        const DevShade *S = T.shade + hidx;
-        const double *m_obj = T.isect[hidx].m;
-        normal = shape_normal(S, m_obj, point);
-        if (vdot(normal, vneg(rd)) < 0.0) normal = vneg(normal);
+        normal = facing_normal(T, hidx, point, rd);
         over = vadd(point, vmul(normal, RTC_EPSILON));
-        const double nn[3] = {normal.x, normal.y, normal.z};
-        double t3[3], s3[3];
-        rtc_ao_frame(nn, t3, s3);
-        tv = mk(t3[0], t3[1], t3[2]);
-        sv = mk(s3[0], s3[1], s3[2]);
+        const Tangents tf = tangent_frame(normal);
+        tv = tf.tv;
+        sv = tf.sv;
     }
 
     // ---- per sample, in the table's order: the first hit within the radius, shaded under every light ----
@@ -2844,11 +2864,10 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
         if constexpr (IS_CULL(SRC)) {
             if (ballot(hit) != 0ull) {
                 Bk = make_bundle<false, false>(hit, over, over, dir, 0.);
-                // the reach, rounded up as make_bundle's REACH form rounds it (k_ao's rule)
-                if (radius < 1e30) Bk.tmax = uniform_f64((double)(fmaxf(0.f, (float)radius) * 1.0001f + 1e-30f));
+                limit_reach(Bk, radius);
             }
         }
-        for_each_object<SRC, SRC == SRC_CULL2 || (SRC == SRC_CULL && RTC_AO_LANE_FILTER_ONE_LEVEL)>(A, T, L, hit, Bk, ClosestHit{hit, over, dir, sbest, sidx, sroot}, over, dir);
+        for_each_object<SRC, SAMPLE_LANE_FILTER<SRC>>(A, T, L, hit, Bk, ClosestHit{hit, over, dir, sbest, sidx, sroot}, over, dir);
         const bool counted = hit && sidx >= 0 && sbest < radius;
 
         // 2. compute_vectors of the counted hit: eyev = -dir, the normal with its inside flip, over_point
@@ -2937,25 +2956,30 @@ template <class F> static hipError_t with_further_lights(const DevExtraLights *x
     return f();
 }
 
-template <int SRC, bool SHADOW, class... XL>
-static hipError_t launch_aov(const AovParams &A, const RenderParams &P, uint32_t tiles, hipStream_t stream, const XL &...xl) {
-    hipLaunchKernelGGL((k_aov<SRC, SHADOW, XL...>), dim3(tiles), dim3(64), 0, stream, A, P.isect, P.kind, P.shade, P.bound, P.isect_s, P.kind_s,
-                       P.bound_s, P.orig_s, P.gbound, P.pre, P.pre_s, xl...);
-    return hipGetLastError();
+// A tile pass's workgroups, one per 8x8 tile; 0 for a block whose size and tiles_x do not hold together.
+static uint32_t tile_count(const TileParams &A) {
+    if (A.W == 0u || A.H == 0u || A.tiles_x != (A.W + 7u) / 8u) return 0u;
+    const unsigned long long tiles64 = (unsigned long long)A.tiles_x * ((A.H + 7u) / 8u);
+    return tiles64 > 0x7fffffffull ? 0u : (uint32_t)tiles64;
+}
+// The World's eleven tables as a tile pass's kernel arguments, in tile_tables' order: f(isect, kind, ..., pre_s).
+template <class F> static hipError_t with_tables(const RenderParams &P, F &&f) {
+    return f(P.isect, P.kind, P.shade, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.pre, P.pre_s);
 }
 
 // `P`: the World's tables only (fill_world). `xl` / `lt` (never both): the further lights of a World with several, read only when
 // A->shadow is set. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
 extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
                                      hipStream_t stream) {
-    if (A->W == 0u || A->H == 0u || A->tiles_x != (A->W + 7u) / 8u) return hipErrorInvalidValue;
-    const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
-    if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
-    const uint32_t tiles = (uint32_t)tiles64;
+    const uint32_t tiles = tile_count(*A);
+    if (tiles == 0u) return hipErrorInvalidValue;
     return with_further_lights(xl, lt, [&](const auto &...x) {
         return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-            if (A->shadow == nullptr) return launch_aov<S(), false>(*A, *P, tiles, stream); // no shadow rays: the further lights are not read
-            return launch_aov<S(), true>(*A, *P, tiles, stream, x...);
+            return with_tables(*P, [&](auto... t) {
+                if (A->shadow == nullptr) hipLaunchKernelGGL((k_aov<S(), false>), dim3(tiles), dim3(64), 0, stream, *A, t...); // no shadow rays: the further lights are not read
+                else hipLaunchKernelGGL((k_aov<S(), true, std::decay_t<decltype(x)>...>), dim3(tiles), dim3(64), 0, stream, *A, t..., x...);
+                return hipGetLastError();
+            });
         });
     });
 }
@@ -2970,15 +2994,14 @@ extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t st
 
 // `P`: the World's tables only (fill_world). `dirs`: A->nsamples directions in device memory. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
 extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, hipStream_t stream) {
-    if (A->W == 0u || A->H == 0u || A->tiles_x != (A->W + 7u) / 8u || A->out == nullptr || dirs == nullptr) return hipErrorInvalidValue;
+    const uint32_t tiles = tile_count(*A);
+    if (tiles == 0u || A->out == nullptr || dirs == nullptr) return hipErrorInvalidValue;
     if (A->nsamples == 0u || A->nsamples > RTC_MAX_AO_SAMPLES) return hipErrorInvalidValue;
-    const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
-    if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
-    const uint32_t tiles = (uint32_t)tiles64;
     return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-        hipLaunchKernelGGL((k_ao<S()>), dim3(tiles), dim3(64), 0, stream, *A, dirs, P->isect, P->kind, P->shade, P->bound, P->isect_s, P->kind_s,
-                           P->bound_s, P->orig_s, P->gbound, P->pre, P->pre_s);
-        return hipGetLastError();
+        return with_tables(*P, [&](auto... t) {
+            hipLaunchKernelGGL((k_ao<S()>), dim3(tiles), dim3(64), 0, stream, *A, dirs, t...);
+            return hipGetLastError();
+        });
     });
 }
 
@@ -2994,17 +3017,15 @@ extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_
 // further lights of a World with several. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
 extern "C" hipError_t rtc_launch_gather(const GatherParams *A, const double *dirs, const RenderParams *P, int src, const DevExtraLights *xl,
                                         const DevLightTable *lt, hipStream_t stream) {
-    if (A->W == 0u || A->H == 0u || A->tiles_x != (A->W + 7u) / 8u || (A->radiance == nullptr && A->bounce == nullptr) || dirs == nullptr)
-        return hipErrorInvalidValue;
+    const uint32_t tiles = tile_count(*A);
+    if (tiles == 0u || (A->radiance == nullptr && A->bounce == nullptr) || dirs == nullptr) return hipErrorInvalidValue;
     if (A->nsamples == 0u || A->nsamples > RTC_MAX_AO_SAMPLES) return hipErrorInvalidValue;
-    const unsigned long long tiles64 = (unsigned long long)A->tiles_x * ((A->H + 7u) / 8u);
-    if (tiles64 > 0x7fffffffull) return hipErrorInvalidValue;
-    const uint32_t tiles = (uint32_t)tiles64;
     return with_further_lights(xl, lt, [&](const auto &...x) {
         return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-            hipLaunchKernelGGL((k_gather<S(), std::decay_t<decltype(x)>...>), dim3(tiles), dim3(64), 0, stream, *A, dirs, P->isect, P->kind, P->shade,
-                               P->bound, P->isect_s, P->kind_s, P->bound_s, P->orig_s, P->gbound, P->pre, P->pre_s, x...);
-            return hipGetLastError();
+            return with_tables(*P, [&](auto... t) {
+                hipLaunchKernelGGL((k_gather<S(), std::decay_t<decltype(x)>...>), dim3(tiles), dim3(64), 0, stream, *A, dirs, t..., x...);
+                return hipGetLastError();
+            });
         });
     });
 }
