@@ -1127,7 +1127,12 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // straight pass and the sub-sample store, the resample test and the averaging are not part of the code: nothing of them is
 // carried — spilled — across the tile loop and the pass loop. The generic kernel takes exactly this path when P.samples == 1,
 // so the results cannot differ; rtc_launch_trace sends a launch here only when P.samples == 1 (RTC_ONE_SAMPLE=0: never).
-template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, bool ONE = false, class... XL>
+// WHOLE = true (on top of ONE; one light, f64 output only): a launch of ONE camera whose every tile is a whole 8-row tile of
+// contiguous rows inside the canvas — whole_tile_launch below, the launcher's condition (RTC_WHOLE_TILES=0: never). Every lane
+// is in range and traced, the view is views[0], band_stride is 1, and the output stage is the 16-byte form alone: the
+// per-lane range state, the view and band terms and the narrow and 8-bit output forms are not part of the code. The ONE
+// kernel evaluates each of them to exactly these constants for such a launch, so the results cannot differ.
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, bool ONE = false, bool WHOLE = false, class... XL>
 __global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
         const DevShade *__restrict__ t_shade, const DevPrim *__restrict__ t_prim, const DevBound *__restrict__ t_bound,
@@ -1142,6 +1147,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     static_assert(sizeof...(XL) <= (ALT ? 2 : 1), "at most one block of further lights, then at most one lens or projection");
     static_assert(!ALT || ((SRC == SRC_SMEM || IS_CULL(SRC)) && !PROBE && !RGBA), "lens and projection launches take SRC_SMEM, SRC_CULL or SRC_CULL2, f64 / RGB output");
     static_assert(!ONE || (IS_CULL(SRC) && !PROBE && !ALT), "the one-sample flavour: pinhole render launches of SRC_CULL and SRC_CULL2");
+    static_assert(!WHOLE || (ONE && !RGBA && !MULTI), "the whole-tile flavour: one-sample launches of one light, f64 output");
     constexpr uint32_t BLOCK = RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), TILE_W = RTC_TILE_W_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE);
     extern __shared__ double lds_raw[];
     // Reflection-only Worlds keep their 32-byte frames (surface, kr) in LDS instead of scratch memory: 5 levels x 4 doubles x
@@ -1218,14 +1224,14 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         traced = in_range;
     } else {
         const uint32_t tiles = P.grid_x * P.grid_y;
-        if (P.nviews > 1u) { view = bid / tiles; tbid = bid % tiles; }
+        if (!WHOLE && P.nviews > 1u) { view = bid / tiles; tbid = bid % tiles; }
         by = tbid / P.grid_x;
         bx = tbid - by * P.grid_x;
         px = bx * TILE_W + wave * 8u + (lane & 7u);
-        py = P.y0 + by * P.band_stride * 8u + (lane >> 3);
-        in_range = px < P.W && py < P.y1;
+        py = P.y0 + by * (WHOLE ? 1u : P.band_stride) * 8u + (lane >> 3);
+        in_range = WHOLE || (px < P.W && py < P.y1);
         // Camera::render leaves the last row and column untouched (camera.rs:120-121)
-        traced = in_range && !(P.mode == RTC_MODE_RENDER && (px + 1u >= P.W || py + 1u >= P.H));
+        traced = WHOLE || (in_range && !(P.mode == RTC_MODE_RENDER && (px + 1u >= P.W || py + 1u >= P.H)));
     }
 
     // Tile rows the binning kernel PROVED black for this view (k_bin_tiles, `rows`): no ray is generated, no pass is run, the
@@ -1236,12 +1242,12 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     if constexpr (IS_CULL(SRC) && !PROBE && !ALT) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
         if (Pt.tile_rows != nullptr && (ONE || Pt.samples == 1u)) {
-            const uint32_t ity = (Pt.y0 >> 3) + by * Pt.band_stride;
+            const uint32_t ity = (Pt.y0 >> 3) + by * (WHOLE ? 1u : Pt.band_stride);
             const uint32_t first = Pt.tile_rows[2u * view], lastinv = Pt.tile_rows[2u * view + 1u];
             sky_tile = ity < first || ity > ~lastinv; // (no tile of the view is non-empty: first = 0xffffffff)
         }
         if (sky_tile) { // counted as cast (the reference casts them), answered by the proof
-            const uint32_t cast = popc64(ballot(traced));
+            const uint32_t cast = WHOLE ? 64u : popc64(ballot(traced)); // (WHOLE: every lane of the wave is traced)
             c_primary += cast;
             c_sky += cast;
         }
@@ -1256,9 +1262,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         const auto &Pt = KP(P_arg);
         if (Pt.tile_cnt != nullptr) {
             const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave); // wave-uniform by construction
-            const uint32_t itx = bx * (TILE_W / 8u) + wv, ity = (Pt.y0 >> 3) + by * Pt.band_stride;
-            if (itx < Pt.tiles_x && ity < Pt.tiles_y) {
-                const size_t tile = (size_t)(view * Pt.tiles_y + ity) * Pt.tiles_x + itx;
+            const uint32_t itx = bx * (TILE_W / 8u) + wv, ity = (Pt.y0 >> 3) + by * (WHOLE ? 1u : Pt.band_stride);
+            if (WHOLE || (itx < Pt.tiles_x && ity < Pt.tiles_y)) { // (WHOLE: every tile of the launch is a tile of the image)
+                const size_t tile = (size_t)((WHOLE ? 0u : view * Pt.tiles_y) + ity) * Pt.tiles_x + itx;
                 bin_cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)Pt.tile_cnt[tile]);
                 if (lane < bin_cnt) bin_ent = Pt.tile_list[tile * RTC_TILE_LIST_CAP + lane];
                 binned = bin_cnt <= RTC_TILE_LIST_CAP; // an overflowing list is incomplete: walk instead
@@ -1291,7 +1297,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     for (uint32_t s = sky_tile ? nsamples : 0u; s < nsamples; ++s) { // (a tile proven black: no sample at all)
         V3 ro, rd;
         bool shared_origin;
-        const auto &Pr = KP(P_arg).views[view]; // ray-generation view: this workgroup's camera block
+        const auto &Pr = KP(P_arg).views[WHOLE ? 0u : view]; // ray-generation view: this workgroup's camera block
         // ray origin of every primary ray: transform_point(view_inv, (0,0,0)) camera.rs:72 — as the host evaluated it when
         // every element of view_inv is finite (DevCamera::origin: the same operations on the same operands, the same bits),
         // evaluated here otherwise (NaN signs and payloads are the device's own)
@@ -1368,7 +1374,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         bool first = true; // this ray is the one color_at was called with (depth 0)
         int rem = (int)P.remaining;
         int sp = 0;
-        c_primary += popc64(ballot(tracing));
+        c_primary += WHOLE ? 64u : popc64(ballot(tracing)); // (WHOLE: every lane of the wave starts out tracing)
 
         // Worlds without reflective / transparent materials (REFL == false) need exactly one pass per
         // primary ray; otherwise loop until every lane's frame stack has unwound.
@@ -1410,7 +1416,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 // every object this tile's rays can touch
                 // (the view's primary-ray constants come from the binning kernel's table: only the direction is transformed)
                 const auto &Pb = KP(P_arg);
-                const DevPrim *__restrict__ vprim = T.prim + (size_t)view * Pb.n;
+                const DevPrim *__restrict__ vprim = WHOLE ? T.prim : T.prim + (size_t)view * Pb.n;
                 // closest_prim: the camera origin in object space and the sphere's c from that table, 24 VALU instructions
                 // fewer per sphere test than transforming the origin again (closest_world)
                 auto binned_test = [&](uint32_t kind, const double *m, uint32_t j) {
@@ -1950,7 +1956,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         slot[1] = result.y;
         slot[2] = result.z;
         const auto &Po = KP(P_arg); // output view
-        const bool want8 = Po.out8 != nullptr;
+        const bool want8 = !WHOLE && Po.out8 != nullptr;
         if (want8) {
             unsigned char *q = stage_u8 + (ty * TILE_W + tx) * 3u;
             if constexpr (RGBA) { // Canvas::to_imgbuf's channels (rtc_gamma.h)
@@ -1974,15 +1980,16 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t px0 = bx * TILE_W + wave * 8u, py0 = Po.y0 + by * Po.band_stride * 8u,
-                       orow0 = view * Po.view_rows + by * 8u; // first image row / first output row of the tile
-        const uint32_t cols = (px0 >= Po.W) ? 0u : ((Po.W - px0 < 8u) ? (Po.W - px0) : 8u); // valid pixels per row
-        const uint32_t rows = (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;                       // valid tile rows
+        const uint32_t px0 = bx * TILE_W + wave * 8u, py0 = Po.y0 + by * (WHOLE ? 1u : Po.band_stride) * 8u,
+                       orow0 = (WHOLE ? 0u : view * Po.view_rows) + by * 8u; // first image row / first output row of the tile
+        // (WHOLE: eight whole rows of eight pixels, 16-byte aligned, and an f64 canvas to store them in)
+        const uint32_t cols = WHOLE ? 8u : (px0 >= Po.W) ? 0u : ((Po.W - px0 < 8u) ? (Po.W - px0) : 8u); // valid pixels per row
+        const uint32_t rows = WHOLE ? 8u : (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;                       // valid tile rows
         const size_t row_bytes = (size_t)Po.W * 24u;
         const double *src = stage_f64 + wave * 24u;
         // a row of the wave's part is 192 contiguous bytes of the canvas: 12 pieces of 16 bytes
-        const bool wide = cols == 8u && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0;
-        if (Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8): nothing of the f64 canvas leaves the chip
+        const bool wide = WHOLE || (cols == 8u && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0);
+        if (!WHOLE && Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8): nothing of the f64 canvas leaves the chip
         } else if (wide) {
             typedef double __attribute__((ext_vector_type(2))) d2;
             for (uint32_t c = lane; c < rows * 12u; c += 64u) {
@@ -2020,14 +2027,15 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
         }
         } else {
         __syncthreads();
-        const uint32_t px0 = bx * TILE_W, py0 = Po.y0 + by * Po.band_stride * 8u,
-                       orow0 = view * Po.view_rows + by * 8u; // first image row / first output row of the tile
-        const uint32_t cols = (Po.W - px0 < TILE_W) ? (Po.W - px0) : TILE_W;      // valid pixels per tile row
-        const uint32_t rows = (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;      // valid tile rows
+        const uint32_t px0 = bx * TILE_W, py0 = Po.y0 + by * (WHOLE ? 1u : Po.band_stride) * 8u,
+                       orow0 = (WHOLE ? 0u : view * Po.view_rows) + by * 8u; // first image row / first output row of the tile
+        // (WHOLE: eight whole tile rows, 16-byte aligned, and an f64 canvas to store them in)
+        const uint32_t cols = WHOLE ? TILE_W : (Po.W - px0 < TILE_W) ? (Po.W - px0) : TILE_W;      // valid pixels per tile row
+        const uint32_t rows = WHOLE ? 8u : (Po.y1 - py0 < 8u) ? (Po.y1 - py0) : 8u;      // valid tile rows
         // f64 canvas: 16-byte pieces when every tile row is whole and 16-byte aligned
         const size_t row_bytes = (size_t)Po.W * 24u;
-        const bool wide = cols == TILE_W && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0;
-        if (Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8)
+        const bool wide = WHOLE || (cols == TILE_W && (row_bytes % 16u) == 0 && ((size_t)Po.out % 16u) == 0);
+        if (!WHOLE && Po.out == nullptr) { // 8-bit frame only (rtc_render_rgb8)
         } else if (wide) {
             typedef double __attribute__((ext_vector_type(2))) d2;
             for (uint32_t c = threadIdx.x; c < rows * (TILE_W * 3u / 2u); c += BLOCK) {
@@ -3040,27 +3048,77 @@ extern "C" hipError_t rtc_launch_add_scaled(double *rgb, const double *plane, si
 
 // ---- launchers (called from rtc_api.cpp) --------------------------------------------------
 // XL: nothing (one light), or the World's further lights (k_trace's trailing argument)
-template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA, bool ONE, class... XL>
+template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA, bool ONE, bool WHOLE = false, class... XL>
 static hipError_t launch_kernel(const RenderParams &P, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
                                 hipEvent_t e1, const XL &...xl) {
     if (lds_bytes > 48 * 1024) { // more dynamic LDS than the default limit: opt in (up to 160 KiB per CU on gfx950)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA, ONE, XL...>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<SRC, REFL, REFR, PROBE, RGBA, ONE, WHOLE, XL...>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
     // e0/e1 (may be NULL) receive the dispatch's own begin/end timestamps: no marker packets on the stream
-    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA, ONE, XL...>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
+    hipExtLaunchKernelGGL((k_trace<SRC, REFL, REFR, PROBE, RGBA, ONE, WHOLE, XL...>), grid, dim3(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE)), lds_bytes, stream, e0, e1, 0, P, P.isect,
                           P.kind, P.shade, P.prim, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.idtab, P.pre, P.pre_s, xl...);
     return hipGetLastError();
 }
+// The kernels the whole-tile flavour (WHOLE) is instantiated for: the culled sources' flat, reflective and refractive kernels,
+// one light, f64 output — without the flat two-level one, which comes out with 95 VGPRs against its one-sample twin's 94
+//  and stays on that twin.
+static constexpr bool whole_tile_kernel(int src, bool refl) { return IS_CULL(src) && !(src == SRC_CULL2 && !refl); }
+// What the flavour assumes of a launch, in one place: launch_one asks here and nowhere else, with the very parameter block
+// the kernel reads. `src`, `refl`, `refr`: the kernel that would run; `further_lights`: the World has more than one light (a
+// DevExtraLights or DevLightTable rides behind the tables).
+//   - the one-sample flavour's own conditions: a culled source, a render (not a probe) launch, one ray per pixel;
+//   - one light, no gamma table, an f64 canvas (16-byte aligned) and no 8-bit output: the output stage is the 16-byte form;
+//   - one view, contiguous rows (band_stride 1), RTC_MODE_RENDER_ASYNC (Camera::render leaves a row and a column untraced);
+//   - whole tiles only: W a multiple of the tile's width, rows [y0, y1) on tile-row boundaries and inside the canvas, and a
+//     grid that is exactly those tiles — every lane of every workgroup is in range and traced, every tile row is whole;
+//   - tile lists, where the launch has them, laid out for exactly this image: every tile of the launch has a list.
+static bool whole_tile_launch(const RenderParams &P, int src, bool refl, bool refr, bool further_lights) {
+    if (!whole_tile_kernel(src, refl) || P.rays != nullptr || P.samples != 1u) return false;
+    const uint32_t tile_w = RTC_TILE_W_FOR(CULL_LEVEL(src), refl, refr, false); // the pixels a workgroup's tile is wide
+    if (further_lights || P.gamma != nullptr || P.out8 != nullptr) return false;
+    if (P.out == nullptr || ((size_t)P.out % 16u) != 0) return false;
+    if (P.nviews != 1u || P.band_stride != 1u || P.mode != RTC_MODE_RENDER_ASYNC) return false;
+    if (P.W == 0u || P.W % tile_w != 0u || P.y1 <= P.y0 || P.y1 > P.H || P.y0 % 8u != 0u || (P.y1 - P.y0) % 8u != 0u) return false;
+    if (P.tile_cnt != nullptr && (P.tiles_x != P.W / 8u || (unsigned long long)P.tiles_y * 8u < P.y1)) return false;
+    return P.grid_x == P.W / tile_w && P.grid_y == (P.y1 - P.y0) / 8u;
+}
+// Test hook (not in include/rtc.h): whole_tile_launch of a parameter block with these fields, for the kernel a World with
+// these flavours would run (tests/test_host_whole_tile.py). Pointers are given as addresses; none is dereferenced.
+struct WholeTileQuery {
+    uint64_t out, out8, gamma, rays, tile_cnt;
+    uint32_t samples, nviews, band_stride, mode, W, H, y0, y1, grid_x, grid_y, tiles_x, tiles_y;
+    int32_t src;
+    uint32_t refl, refr, further_lights;
+};
+extern "C" int rtc_debug_whole_tile_launch(const WholeTileQuery *q) {
+    if (q == nullptr) return -1;
+    RenderParams P{};
+    P.out = reinterpret_cast<double *>((uintptr_t)q->out);
+    P.out8 = reinterpret_cast<unsigned char *>((uintptr_t)q->out8);
+    P.gamma = reinterpret_cast<const DevGamma *>((uintptr_t)q->gamma);
+    P.rays = reinterpret_cast<const double *>((uintptr_t)q->rays);
+    P.tile_cnt = reinterpret_cast<const uint32_t *>((uintptr_t)q->tile_cnt);
+    P.tiles_x = q->tiles_x; P.tiles_y = q->tiles_y;
+    P.samples = q->samples; P.nviews = q->nviews; P.band_stride = q->band_stride; P.mode = q->mode;
+    P.W = q->W; P.H = q->H; P.y0 = q->y0; P.y1 = q->y1; P.grid_x = q->grid_x; P.grid_y = q->grid_y;
+    return whole_tile_launch(P, q->src, q->refl != 0u, q->refr != 0u, q->further_lights != 0u) ? 1 : 0;
+}
+
 // `one_sample`: a render launch of a camera with samples == 1 takes the one-sample instantiation (ONE), which exists for the
 // product sources SRC_CULL and SRC_CULL2 only; the measurement-only sources keep the generic kernel.
+// `whole_tiles`: such a launch of one light for which whole_tile_launch holds takes the whole-tile instantiation (WHOLE) on top.
 template <int SRC, bool REFL, bool REFR, class... XL>
-static hipError_t launch_one(const RenderParams &P, bool one_sample, dim3 grid, size_t lds_bytes, hipStream_t stream, hipEvent_t e0,
-                             hipEvent_t e1, const XL &...xl) {
+static hipError_t launch_one(const RenderParams &P, bool one_sample, bool whole_tiles, dim3 grid, size_t lds_bytes, hipStream_t stream,
+                             hipEvent_t e0, hipEvent_t e1, const XL &...xl) {
     if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
     if constexpr (IS_CULL(SRC)) {
         if (one_sample && P.samples == 1u) {
+            if constexpr (sizeof...(XL) == 0 && whole_tile_kernel(SRC, REFL)) {
+                if (whole_tiles && whole_tile_launch(P, SRC, REFL, REFR, false))
+                    return launch_kernel<SRC, REFL, REFR, false, false, true, true>(P, grid, lds_bytes, stream, e0, e1);
+            }
             if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true, true>(P, grid, lds_bytes, stream, e0, e1, xl...);
             return launch_kernel<SRC, REFL, REFR, false, false, true>(P, grid, lds_bytes, stream, e0, e1, xl...);
         }
@@ -3075,9 +3133,12 @@ static hipError_t launch_one(const RenderParams &P, bool one_sample, dim3 grid, 
 // `proj`: non-NULL for a projection launch, under the same conditions; a panorama's tables hold P->W and P->H entries. Never both.
 // `one_sample`: non-zero lets a pinhole render launch with P->samples == 1 take the one-sample instantiation (the context's
 // RTC_ONE_SAMPLE switch); zero keeps every launch on the generic kernel.
+// `whole_tiles`: non-zero lets such a launch take the whole-tile instantiation where it qualifies (whole_tile_launch; the
+// context's RTC_WHOLE_TILES switch); zero, or one_sample zero, keeps every launch on the kernels it had without the flavour.
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
-                                       const DevLightTable *lt, const DevLens *lens, const DevProjection *proj, int one_sample) {
+                                       const DevLightTable *lt, const DevLens *lens, const DevProjection *proj, int one_sample,
+                                       int whole_tiles) {
     const dim3 grid(nblocks);
     // the recursion flavour: refractive Worlds carry the full frame stack, reflective ones the LDS stack, the others none
     auto with_depth = [&](auto &&launch) {
@@ -3104,7 +3165,7 @@ extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl,
             });
         }
         auto flavours = [&](auto S) {
-            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, one_sample != 0, grid, lds_bytes, stream, e0, e1, x...); });
+            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, one_sample != 0, whole_tiles != 0, grid, lds_bytes, stream, e0, e1, x...); });
         };
         // the LDS-staged sources exist for one-light pinhole launches only
         if constexpr (sizeof...(x) == 0) return with_src<SRC_SMEM, SRC_LDS1, SRC_LDSN, SRC_CULL, SRC_CULL2>(src, flavours);

@@ -30,10 +30,11 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     def g(k):
         m = re.search(k + r": (\d+)", blk)
         return m.group(1) if m else "?"
-    m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?(?:Lb(\d)E)?", name)
+    m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?(?:Lb(\d)E)?(?:Lb(\d)E)?", name)
     if m:
         tag = "k_trace<%s,refl=%s,refr=%s,probe=%s" % m.groups()[:4] + (",rgba" if m.group(5) == "1" else "")
         tag += ",one" if m.group(6) == "1" else ""  # the one-sample flavour (cameras with samples == 1)
+        tag += ",whole" if m.group(7) == "1" else ""  # the whole-tile flavour on top of it (one camera, whole tiles, f64 output)
         # the instantiations for Worlds with several lights: in the kernel arguments, or in the World's device table
         tag += ",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else ""
         # the thin-lens flavour (rtc_render_lens*) and the projection flavour (rtc_render_projection*)
