@@ -542,6 +542,7 @@ rtc_status rtc_context_create(int32_t device, void *stream, rtc_context **out) {
     if (const char *e = std::getenv("RTC_LIGHT_TABLE")) ctx->light_table = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_WORLD_UPDATE")) ctx->world_update = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_SKY_ROWS")) ctx->sky_rows = std::atoi(e) != 0;
+    if (const char *e = std::getenv("RTC_BIN_SORT")) ctx->bin_sort = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_ONE_SAMPLE")) ctx->one_sample = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_WHOLE_TILES")) ctx->whole_tiles = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS")) ctx->bin_small_pixels = std::strtoull(e, nullptr, 10);
@@ -1032,14 +1033,18 @@ static bool ready_binset(rtc_context *ctx, rtc_world::BinSet &S, const LaunchPla
 }
 
 // k_bin_tiles of the launch's views into set B on `stream` (timed by the event pair `ev`, if any), and the render
-// parameters that read the set.
-static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_world::BinSet &B, const LaunchPlan &plan, bool sky_rows,
+// parameters that read the set. `sort` (decided here): the packed lists' short ones sorted (RTC_TILE_SORT_CAP, rtc_device.h), for the
+// render kernels' scalar walk: flat one-level worlds (the kernels that have it, trace_scalar_walk), unless RTC_BIN_SORT=0.
+static hipError_t bin_tiles(const rtc_context *ctx, RenderParams &P, const rtc_world::Gen &G, const rtc_world::BinSet &B, const LaunchPlan &plan,
                             hipStream_t stream, const hipEvent_t *ev) {
+    // the one place that decides it: the worlds whose render kernels have the scalar walk (trace_scalar_walk, rtc_kernels.hip)
+    const bool sort = ctx->bin_sort && plan.src == SRC_CULL && !plan.refl;
+    const bool sky_rows = ctx->sky_rows;
     uint32_t *cnt = B.tile_cnt.get() + RTC_BIN_ROW_WORDS;
     const hipError_t e = rtc_launch_binning(P.views, P.nviews, P.W, P.H, G.n, G.bound_s, G.gbound, G.orig_s,
                                             G.ngroups, cnt, B.tile_list.get(), P.y0 / 8u, P.band_stride, stream, ev ? ev[0] : nullptr,
                                             ev ? ev[1] : nullptr, G.isect_s, G.kind_s, G.n_unb, B.tile_cnt.get(),
-                                            G.isect, B.prim.get());
+                                            G.isect, B.prim.get(), sort ? 1u : 0u);
     if (e != hipSuccess) return e;
     P.prim = B.prim.get();
     P.tile_rows = sky_rows ? B.tile_cnt.get() : nullptr;
@@ -1047,7 +1052,7 @@ static hipError_t bin_tiles(RenderParams &P, const rtc_world::Gen &G, const rtc_
     P.tile_list = B.tile_list.get();
     P.tiles_x = plan.tiles_x;
     P.tiles_y = plan.tiles_y;
-    P.bin_packed = RTC_BIN_PACKED(G.n) ? 1u : 0u;
+    P.bin_packed = RTC_BIN_PACKED(G.n) ? (sort ? 2u : 1u) : 0u;
     P.n_unb = G.n_unb;
     return hipSuccess;
 }
@@ -1233,7 +1238,7 @@ static rtc_status launch_planned(rtc_context *ctx, const rtc_world *w, rtc_world
         // lanes' render kernels — no events. Grow-only; growing waits for the lane.
         rtc_world::BinSet &B = w->bin[lane];
         bin_ok = ready_binset(ctx, B, plan, true, stream);
-        if (bin_ok) HIP_TRY(bin_tiles(P, G, B, plan, ctx->sky_rows, stream, timed ? pair_bin : nullptr));
+        if (bin_ok) HIP_TRY(bin_tiles(ctx, P, G, B, plan, stream, timed ? pair_bin : nullptr));
         if (bin_ok) bin_set = (int)lane;
     } else if (bin_ok) {
         if (!ctx->side_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
@@ -1256,7 +1261,7 @@ static rtc_status launch_planned(rtc_context *ctx, const rtc_world *w, rtc_world
         // wait for the render kernel that last read THIS set (two launches ago); the render stream waits for the binning.
         HIP_TRY(hipStreamWaitEvent(ctx->side_stream, B.traced, 0)); // never recorded: no wait
         HIP_TRY(order_behind_build(G, ctx->side_stream, BIT_SIDE));
-        HIP_TRY(bin_tiles(P, G, B, plan, ctx->sky_rows, ctx->side_stream, timed ? pair_bin : nullptr));
+        HIP_TRY(bin_tiles(ctx, P, G, B, plan, ctx->side_stream, timed ? pair_bin : nullptr));
         HIP_TRY(hipEventRecord(B.binned, ctx->side_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, B.binned, 0));
         binset = &B;
@@ -1460,6 +1465,28 @@ extern "C" rtc_status rtc_debug_tile_counts(rtc_context *ctx, const rtc_world *w
     dims[0] = 1u; dims[1] = L.nviews; dims[2] = L.tiles_x; dims[3] = L.tiles_y;
     if (counts) HIP_TRY(hipMemcpy(counts, B.tile_cnt.get() + RTC_BIN_ROW_WORDS, sizeof(uint32_t) * tiles, hipMemcpyDeviceToHost));
     if (rows) HIP_TRY(hipMemcpy(rows, B.tile_cnt.get(), sizeof(uint32_t) * 2u * L.nviews, hipMemcpyDeviceToHost));
+    return RTC_OK;
+}
+
+// Diagnostic (not part of include/rtc.h), rtc_debug_tile_counts' companion: the lists themselves, of the same launch and under
+// the same guards. dims as there. lists (`lists_cap` words, at least nviews * tiles_y * tiles_x * 64): 64 entry slots per
+// (view, tile) in the counts' order, of which the first min(count, 64) hold the list — packed entries (key's upper half above
+// the object index; ascending in lists of at most RTC_TILE_SORT_CAP entries of a flat one-level world unless RTC_BIN_SORT=0) in
+// Worlds of at most 65 536 objects, plain indices above that; the other slots hold stale words. Waits for the context's work first. Copies only.
+extern "C" rtc_status rtc_debug_tile_lists(rtc_context *ctx, const rtc_world *w, uint32_t dims[4], uint32_t *lists, size_t lists_cap) {
+    if (!ctx || !w || !dims || !lists || w->ctx != ctx) return RTC_ERR_ARG;
+    dims[0] = dims[1] = dims[2] = dims[3] = 0u;
+    const rtc_context::LastBin &L = ctx->last_bin;
+    if (L.world_serial == 0 || L.world_serial != w->serial) return RTC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(drain_lanes(ctx));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->side_stream) HIP_TRY(hipStreamSynchronize(ctx->side_stream));
+    const rtc_world::BinSet &B = w->bin[L.set];
+    const size_t words = (size_t)L.nviews * L.tiles_x * L.tiles_y * RTC_TILE_LIST_CAP;
+    if (!B.tile_list.get() || B.tile_list.capacity() < words || lists_cap < words) return RTC_ERR_ARG;
+    dims[0] = 1u; dims[1] = L.nviews; dims[2] = L.tiles_x; dims[3] = L.tiles_y;
+    HIP_TRY(hipMemcpy(lists, B.tile_list.get(), sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 

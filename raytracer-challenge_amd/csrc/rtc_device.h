@@ -73,6 +73,11 @@ struct DevTileBundle {
     uint32_t off;                 // 1: could not be bounded — every object is a candidate
 };
 #define RTC_TILE_LIST_CAP 64u // one lane per entry in the render kernel's nearest-first walk
+// Packed lists of at most this many entries leave k_bin_tiles sorted ascending when the launch asks for it (flat one-level worlds:
+// RenderParams::bin_packed == 2), and k_trace walks those in SGPRs; longer ones stay in table order and take the
+// wave-minimum walk. 16: the binning wave's LDS copy of its 64 lists is 4.3 KB (64 entries each would be 16.6 KB, which
+// halved the binning kernel's resident waves: C4 +3 %), and ranking is at most 16 x 16 compares per lane.
+#define RTC_TILE_SORT_CAP 16u
 
 // Light-space shadow lists (two-level worlds). Every shadow segment ends at the light (is_shadowed_by_light shape.rs:716-720),
 // so seen from the light it is a ray in some direction: a cube map of RTC_LIGHT_R x RTC_LIGHT_R direction cells per face
@@ -298,7 +303,7 @@ struct RenderParams {
     const uint32_t *light_list;
     uint32_t light_cap;          // entries per cell of THIS World's lists
     double light_reach;
-    uint32_t bin_packed;        // tile-list entries carry the upper half of the object's key above its index (RTC_BIN_PACKED)
+    uint32_t bin_packed;        // tile-list entries carry the upper half of the object's key above its index (RTC_BIN_PACKED); 2: and lists of <= RTC_TILE_SORT_CAP entries are sorted
     uint32_t n_unb;             // unbounded objects = the first n_unb entries of isect_s / kind_s / orig_s
     uint32_t ngroups;
     uint32_t n;

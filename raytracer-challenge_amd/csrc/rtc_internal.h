@@ -73,6 +73,9 @@ struct rtc_context {
     bool world_update = true; // RTC_WORLD_UPDATE=0: render_lua destroys and recreates the World when a job's differs (A/B)
     bool binning = true;  // RTC_BINNING=0: primary rays take the wave-level cull / group walk too (A/B)
     bool sky_rows = true; // RTC_SKY_ROWS=0: tile rows the binning kernel proved black are traced like any other (A/B)
+    // RTC_BIN_SORT=0: k_bin_tiles leaves every packed list in table order and the render kernels take the wave-minimum walk
+    // (tests, A/B); otherwise the short lists of flat one-level worlds are sorted for the scalar walk (RTC_TILE_SORT_CAP).
+    bool bin_sort = true;
     bool one_sample = true; // RTC_ONE_SAMPLE=0: launches of cameras with samples == 1 take the generic render kernel (A/B, parity tests)
     bool whole_tiles = true; // RTC_WHOLE_TILES=0: no launch takes the whole-tile render kernels (A/B, parity tests); RTC_ONE_SAMPLE=0 implies it
     // one-level worlds (<= 256 objects) are binned only in launches of at least this many views (RTC_BIN_SMALL_VIEWS): the
@@ -198,7 +201,7 @@ extern "C" hipError_t rtc_launch_binning(const DevCamera *views, uint32_t nviews
                                          const DevBound *gbound, const uint32_t *orig_s, uint32_t ngroups, uint32_t *cnt, uint32_t *list,
                                          uint32_t row0, uint32_t row_stride, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
                                          const DevIsect *isect_s, const uint32_t *kind_s, uint32_t n_unb, uint32_t *rows,
-                                         const DevIsect *isect, DevPrim *prim);
+                                         const DevIsect *isect, DevPrim *prim, uint32_t sort);
 enum { RTC_BIN_ROW_WORDS = 2 * RTC_MAX_VIEWS }; // a BinSet's tile_cnt buffer starts with the views' row words (RenderParams::tile_rows)
 extern "C" hipError_t rtc_launch_light_lists(uint32_t n, uint32_t cap, const DevBound *bound, const double light[3], double reach, DevTileBundle *cells,
                                              DevTileBundle *macros, uint32_t *cnt, uint32_t *list, hipStream_t stream);

@@ -44,12 +44,28 @@
 // remaining = 5 (Camera::MAX_REFLECTIONS, camera.rs:31) suspends at most 5 shade_hit calls.
 #define RTC_MAX_STACK 5
 // 2nd argument of __launch_bounds__ = minimum waves per SIMD (caps VGPRs: 5 -> 96, 4 -> 128,
-// 3 -> 168, 2 -> 256). Measured on the north-star scene (culled flat kernel, 90 VGPRs):
+// 3 -> 168, 2 -> 256, 6 -> 80). Measured on the north-star scene (culled flat kernel, 90 VGPRs):
 // 4 -> 0.0784 ms, 5 -> 0.0736 ms, 6 -> 0.0882 ms with 256-thread workgroups and one frame per launch; with
-// 128-thread workgroups and 8 frames per launch 4, 5 and 6 measure the same (0.5365 ms per launch).
+// 128-thread workgroups and 8 frames per launch 4, 5 and 6 measure the same (0.5365 ms per launch). Every one of these
+// six-wave figures was taken on a kernel that SPILLED at 80 VGPRs (56 - 84 B of scratch per lane): they
+// say what the spills cost, not what a sixth wave is worth.
 // Kernels that carry the reflection/refraction frame stack: see RTC_WAVES_PER_SIMD_STACK.
-#ifndef RTC_WAVES_PER_SIMD
+// The bound is a constant of the instantiation (trace_waves_per_simd): the flat one-level one-sample whole-tile kernel
+// takes RTC_WAVES_PER_SIMD_WHOLE, every other k_trace RTC_WAVES_PER_SIMD or RTC_WAVES_PER_SIMD_STACK.
+#ifdef RTC_WAVES_PER_SIMD
+#ifndef RTC_WAVES_PER_SIMD_WHOLE
+#define RTC_WAVES_PER_SIMD_WHOLE RTC_WAVES_PER_SIMD // a sweep of RTC_WAVES_PER_SIMD moves the flagship kernel too
+#endif
+#else
 #define RTC_WAVES_PER_SIMD 5
+#endif
+// k_trace<SRC_CULL, flat, ONE, WHOLE>, the north star's kernel: the only one that fits six waves (80 VGPRs) without a
+// private segment (78 VGPRs, 0 B; tools/kernel_resources.py -DRTC_WAVES_PER_SIMD_WHOLE=6; its one-sample twin gets 12 B of
+// scratch at 6). Measured that way, without spills, for the first time (profiles/sorted_lists_ab.log): the
+// kernel alone is 5.5 % faster at 6, the pipelined frame — three launches and their binning kernels sharing the chip — is
+// not (-0.05 % +- 0.8 %), and on top of the scalar tile-list walk 6 is slower than 5. So it stays 5.
+#ifndef RTC_WAVES_PER_SIMD_WHOLE
+#define RTC_WAVES_PER_SIMD_WHOLE 5
 #endif
 // Frame-stack kernels (124 VGPRs) on a reflective 2048x2048 / 100-sphere scene: 4 -> 0.871 ms,
 // 5 -> 0.870, 6 -> 0.862 (forcing more waves trades spills for occupancy: a wash).
@@ -1032,6 +1048,30 @@ DEVI ParamPtr param_view() {
     return (ParamPtr)a;
 }
 #define KP(arg) (*param_view())
+// The tile lists and their counts through the same address space: k_trace never writes them (k_bin_tiles did, in an earlier
+// dispatch), and a wave asks for its own tile's — a wave-uniform address — so the loads are scalar ones and the words arrive
+// in SGPRs.
+typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
+DEVI ConstWords const_words(const uint32_t *p) { return (ConstWords)(unsigned long long)p; }
+// The packed tile lists' walk in k_trace: 1 = the scalar walk over k_bin_tiles' sorted lists, 0 = the wave-minimum extraction
+// (which does not care about the lists' order), kept for the A/B. trace_scalar_walk: the instantiations that take it.
+#ifndef RTC_SCALAR_TILE_WALK
+#define RTC_SCALAR_TILE_WALK 1
+#endif
+// The flat one-level k_trace kernels (SRC_CULL, no frame stack) with the binned pass take the scalar walk for the sorted
+// lists — the launches whose lists k_bin_tiles sorts (rtc_launch_binning's `sort`: the host asks for it for exactly these
+// worlds). Not the two-level kernels: at 10 000 objects the binning kernel is as long as the render kernel and has no time
+// to spare. Not the frame-stack kernels: the primary pass is a small part of their frames, and with both walks in it the
+// reflective whole-tile kernel measured 0.6 % slower (C4). Not the anti-aliased kernels of Worlds with several lights, which
+// came out of the compiler with 4 to 8 B per lane more scratch than they had. All of those keep the wave-minimum extraction
+// alone, which walks lists in any order, and their code is the parent's (tools/kernel_resources.py, tools/isa_compare.py;
+// profiles/sorted_lists_*). `lights`: 0 one light, 1 the further lights in the kernel arguments (DevExtraLights), 2 in the
+// World's table (DevLightTable).
+constexpr bool trace_scalar_walk(int src, bool refl, bool one, int lights) {
+    if (RTC_SCALAR_TILE_WALK == 0 || src != SRC_CULL || refl) return false;
+    if (!one && lights != 0) return false;
+    return true;
+}
 
 // One suspended shade_hit call (shape.rs:685-700) on a lane's stack. The stack lives in scratch
 // (dynamic index), so its size is HBM/L2 traffic: Worlds without transparent materials (REFR ==
@@ -1132,8 +1172,13 @@ DEVI V3 combine(V3 surface, V3 reflected, V3 refracted, bool schlick, double R) 
 // is in range and traced, the view is views[0], band_stride is 1, and the output stage is the 16-byte form alone: the
 // per-lane range state, the view and band terms and the narrow and 8-bit output forms are not part of the code. The ONE
 // kernel evaluates each of them to exactly these constants for such a launch, so the results cannot differ.
+// __launch_bounds__' waves per SIMD of a k_trace instantiation (the macros above).
+constexpr int trace_waves_per_simd(int src, bool refl, bool one, bool whole) {
+    if (refl) return RTC_WAVES_PER_SIMD_STACK;
+    return (src == SRC_CULL && one && whole) ? RTC_WAVES_PER_SIMD_WHOLE : RTC_WAVES_PER_SIMD;
+}
 template <int SRC, bool REFL, bool REFR, bool PROBE, bool RGBA = false, bool ONE = false, bool WHOLE = false, class... XL>
-__global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), (REFL ? RTC_WAVES_PER_SIMD_STACK : RTC_WAVES_PER_SIMD))
+__global__ void __launch_bounds__(RTC_BLOCK_FOR(CULL_LEVEL(SRC), REFL, REFR, PROBE), trace_waves_per_simd(SRC, REFL, ONE, WHOLE))
 k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
         const DevShade *__restrict__ t_shade, const DevPrim *__restrict__ t_prim, const DevBound *__restrict__ t_bound,
         const DevIsect *__restrict__ t_isect_s, const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s,
@@ -1256,8 +1301,15 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     // Binned primary pass: this wave's 8x8 tile has a list of the objects its primary rays can touch (k_bin_tiles): lane e
     // holds entry e. Requested where the pass needs it: a request at kernel entry, ahead of the ray generation, measured
     // slower (north star +3 %, C5 +4 %; profiles/r02_exp_packed_tile_lists.log).
+    // SCALAR_WALK: the count and the list's first entry come through scalar loads, issued together, into SGPRs (a sorted
+    // list's entry k IS the k-th smallest, k_bin_tiles) — no per-lane list state; the lists that are not sorted (longer than
+    // RTC_TILE_SORT_CAP, or a launch that did not sort) are read per lane where their walk starts.
+    constexpr int LIGHTS = (false || ... || __is_same(XL, DevExtraLights)) ? 1 : (false || ... || __is_same(XL, DevLightTable)) ? 2 : 0;
+    constexpr bool SCALAR_WALK = IS_CULL(SRC) && !PROBE && !ALT && trace_scalar_walk(SRC, REFL, ONE, LIGHTS);
     bool binned = false;
     uint32_t bin_cnt = 0, bin_ent = 0xffffffffu;
+    ConstWords bin_list = nullptr; // SCALAR_WALK: the tile's list (wave-uniform)
+    uint32_t bin_head = 0;         // SCALAR_WALK: its entry 0 (an empty list's: whatever the slot holds, never used)
     auto tile_lookup = [&]() {
         const auto &Pt = KP(P_arg);
         if (Pt.tile_cnt != nullptr) {
@@ -1265,8 +1317,14 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             const uint32_t itx = bx * (TILE_W / 8u) + wv, ity = (Pt.y0 >> 3) + by * (WHOLE ? 1u : Pt.band_stride);
             if (WHOLE || (itx < Pt.tiles_x && ity < Pt.tiles_y)) { // (WHOLE: every tile of the launch is a tile of the image)
                 const size_t tile = (size_t)((WHOLE ? 0u : view * Pt.tiles_y) + ity) * Pt.tiles_x + itx;
-                bin_cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)Pt.tile_cnt[tile]);
-                if (lane < bin_cnt) bin_ent = Pt.tile_list[tile * RTC_TILE_LIST_CAP + lane];
+                if constexpr (SCALAR_WALK) {
+                    bin_list = const_words(Pt.tile_list) + tile * RTC_TILE_LIST_CAP;
+                    bin_cnt = const_words(Pt.tile_cnt)[tile];
+                    bin_head = bin_list[0];
+                } else {
+                    bin_cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)Pt.tile_cnt[tile]);
+                    if (lane < bin_cnt) bin_ent = Pt.tile_list[tile * RTC_TILE_LIST_CAP + lane];
+                }
                 binned = bin_cnt <= RTC_TILE_LIST_CAP; // an overflowing list is incomplete: walk instead
             }
         }
@@ -1429,9 +1487,30 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 // the tile's list, nearest first: lane e holds entry e and the lower bound of the distance from the camera to
                 // its (inflated) bounding sphere — every intersection of that object has t >= key for these unit-direction
                 // rays — and the walk stops at the first key no lane can use any more (as the ordered group walk does)
-                if (Pb.bin_packed) {
-                    // entry = key's upper 16 bits (truncated: still a lower bound) above the object index: the wave's
-                    // minimum IS the next object and its key
+                if (SCALAR_WALK && Pb.bin_packed == 2u && bin_cnt <= RTC_TILE_SORT_CAP) {
+                    // entry = key's upper 16 bits (truncated: still a lower bound) above the object index, and the list is
+                    // sorted ascending by it (k_bin_tiles): entry k is the k-th nearest object and its key. A scalar loop
+                    // over the count, entries in SGPRs — the sequence of exact tests and early-out decisions of the
+                    // wave-minimum extraction below, without the reduction. Entry k + 1 is requested before entry k's test:
+                    // one scalar load beside the test's own kind[j] load, answered under the same wait (slot k + 1 <= 16 is
+                    // one of the tile's own 64 slots; used only when it is below the count). Eight entries per load, held in
+                    // SGPRs, was compiled first: picking entry k mod 8 out of them is a chain of seven compare-and-select
+                    // pairs per entry, 14 scalar instructions where this form has one load.
+                    uint32_t e_next = bin_head;
+                    for (uint32_t k = 0; k < bin_cnt; ++k) {
+                        const uint32_t e = e_next;
+                        e_next = bin_list[k + 1u];
+                        const float kmin = __builtin_bit_cast(float, e & 0xffff0000u);
+                        if (ballot(tracing && !(best < (double)kmin)) == 0ull) break;
+                        const uint32_t j = e & 0xffffu;
+                        if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
+                    }
+                } else if (Pb.bin_packed) {
+                    // the same walk over lists in any order: lane e holds entry e, the wave's minimum IS the next object and
+                    // its key
+                    if constexpr (SCALAR_WALK) { // (the per-lane form of the list, which the scalar walk does not need)
+                        if (lane < bin_cnt) bin_ent = ((const uint32_t *)(unsigned long long)bin_list)[lane];
+                    }
                     uint32_t ent = lane < bin_cnt ? bin_ent : 0xffffffffu;
                     for (;;) {
                         const uint32_t e = ~wave_max_u32(~ent);
@@ -1445,6 +1524,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 } else { // more than 65 536 objects: plain indices, keys from the bounds
                     uint32_t my_j = 0u;
                     float my_key = 0.f;
+                    if constexpr (SCALAR_WALK) { // (the per-lane form of the list, which only this walk needs)
+                        if (lane < bin_cnt) bin_ent = ((const uint32_t *)(unsigned long long)bin_list)[lane];
+                    }
                     if (lane < bin_cnt) {
                         my_j = bin_ent;
                         my_key = bound_key(cam_origin, T.bound[my_j]);
@@ -2253,11 +2335,17 @@ DEVI bool cone_misses_plane(const double *m, V3 o, const DevTileBundle &t) {
     return lower > 1e-4 * __builtin_sqrt(rr);
 }
 
+// SORT (its own instantiation; packed lists only: the launcher's condition): lists of at most RTC_TILE_SORT_CAP entries leave
+// sorted ascending by entry, the order k_trace's scalar walk takes them in. A lane keeps a copy of its list's first entries
+// in LDS (entry s of lane l at word l * (CAP + 1) + s: the odd stride keeps the lanes' accesses to one slot on different
+// banks) and ranks them once the group walk is over. SORT = false is the kernel as it always was, LDS-free.
+template <bool SORT>
 __global__ void __launch_bounds__(64) k_bin_tiles(const BinParams Q, const DevBound *__restrict__ bound_s, const DevBound *__restrict__ gbound,
                                                    const uint32_t *__restrict__ orig_s, uint32_t ngroups, uint32_t *__restrict__ cnt,
                                                    uint32_t *__restrict__ list, const DevIsect *__restrict__ isect_s,
                                                    const uint32_t *__restrict__ kind_s, uint32_t n_unb, uint32_t *__restrict__ rows,
                                                    const DevIsect *__restrict__ isect, DevPrim *__restrict__ prim) {
+    __shared__ uint32_t ents[SORT ? 64u * (RTC_TILE_SORT_CAP + 1u) : 1u];
     const uint32_t macros = Q.macros_x * Q.macros_y;
     const uint32_t view = blockIdx.x / macros, m = blockIdx.x % macros, lane = threadIdx.x;
     // The view's per-object primary-ray constants (camera origin in object space, the sphere's c: k_prep_primary's table,
@@ -2319,8 +2407,34 @@ __global__ void __launch_bounds__(64) k_bin_tiles(const BinParams Q, const DevBo
                 const uint32_t ej = (uint32_t)__builtin_amdgcn_readlane((int)entry, (int)l);
                 if (mine && bundle_touches(TB, bj)) {
                     if (my_cnt < RTC_TILE_LIST_CAP) my_list[my_cnt] = ej;
+                    if constexpr (SORT) {
+                        if (my_cnt < RTC_TILE_SORT_CAP) ents[lane * (RTC_TILE_SORT_CAP + 1u) + my_cnt] = ej;
+                    }
                     ++my_cnt;
                 }
+            }
+        }
+    }
+    if constexpr (SORT) {
+        // Every lane ranks its own list, all 64 at once: an entry's rank is the number of the list's entries below it (entries
+        // are unique: the object index is part of them), and the entry goes to that slot of the list — over the table-order
+        // copy the appends left there. The lists' copies come out of LDS once, into registers (slots past a lane's count: the
+        // largest word, below nothing); then at most c x 16 compares for the wave's longest short list c, and nothing at all
+        // for a wave whose lists have at most one entry each.
+        const uint32_t c = my_cnt <= RTC_TILE_SORT_CAP ? my_cnt : 0u; // (my_cnt != 0: the tile is `mine`)
+        const uint32_t cmax = wave_max_u32(c);
+        if (cmax >= 2u) {
+            const uint32_t *const row = ents + lane * (RTC_TILE_SORT_CAP + 1u);
+            uint32_t v[RTC_TILE_SORT_CAP];
+#pragma unroll
+            for (uint32_t k = 0; k < RTC_TILE_SORT_CAP; ++k) v[k] = k < c ? row[k] : 0xffffffffu;
+#pragma unroll
+            for (uint32_t e = 0; e < RTC_TILE_SORT_CAP; ++e) {
+                if (e >= cmax) break; // (wave-uniform)
+                uint32_t rank = 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < RTC_TILE_SORT_CAP; ++k) rank += v[k] < v[e] ? 1u : 0u;
+                if (e < c) my_list[rank] = v[e];
             }
         }
     }
@@ -2346,7 +2460,7 @@ extern "C" hipError_t rtc_launch_binning(const DevCamera *views, uint32_t nviews
                                          const DevBound *gbound, const uint32_t *orig_s, uint32_t ngroups, uint32_t *cnt, uint32_t *list,
                                          uint32_t row0, uint32_t row_stride, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
                                          const DevIsect *isect_s, const uint32_t *kind_s, uint32_t n_unb, uint32_t *rows,
-                                         const DevIsect *isect, DevPrim *prim) {
+                                         const DevIsect *isect, DevPrim *prim, uint32_t sort) {
     if (n == 0) return hipSuccess;
     if (hipMemsetAsync(rows, 0xff, sizeof(uint32_t) * 2u * RTC_MAX_VIEWS, stream) != hipSuccess) return hipGetLastError();
     BinParams Q;
@@ -2358,8 +2472,13 @@ extern "C" hipError_t rtc_launch_binning(const DevCamera *views, uint32_t nviews
     Q.tiles_x = (W + 7u) / 8u; Q.tiles_y = (H + 7u) / 8u;
     Q.macros_x = (Q.tiles_x + 7u) / 8u; Q.macros_y = (Q.tiles_y + 7u) / 8u;
     // e0/e1 (may be NULL): the dispatch's own begin/end timestamps, as for k_trace
-    hipExtLaunchKernelGGL(k_bin_tiles, dim3(nviews * Q.macros_x * Q.macros_y), dim3(64), 0, stream, e0, e1, 0, Q, bound_s, gbound, orig_s, ngroups, cnt, list,
-                          isect_s, kind_s, n_unb, rows, isect, prim);
+    const dim3 grid(nviews * Q.macros_x * Q.macros_y);
+    if (sort != 0u && Q.packed != 0u)
+        hipExtLaunchKernelGGL(k_bin_tiles<true>, grid, dim3(64), 0, stream, e0, e1, 0, Q, bound_s, gbound, orig_s, ngroups, cnt, list, isect_s, kind_s, n_unb,
+                              rows, isect, prim);
+    else
+        hipExtLaunchKernelGGL(k_bin_tiles<false>, grid, dim3(64), 0, stream, e0, e1, 0, Q, bound_s, gbound, orig_s, ngroups, cnt, list, isect_s, kind_s, n_unb,
+                              rows, isect, prim);
     return hipGetLastError();
 }
 

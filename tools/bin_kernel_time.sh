@@ -8,7 +8,7 @@ for w in $1; do
   python3 - "$f" "$w" <<'PY'
 import csv, sys
 for r in csv.DictReader(open(sys.argv[1])):
-    if r["Name"].startswith(("k_bin", "void k_trace")):
+    if r["Name"].startswith(("k_bin", "void k_bin", "void k_trace")):
         print(sys.argv[2], r["Name"][:24], "calls", r["Calls"], "avg_us", round(float(r["AverageNs"]) / 1e3, 1))
 PY
 done
