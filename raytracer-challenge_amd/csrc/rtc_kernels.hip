@@ -100,12 +100,49 @@ DEVI V3 vnormalize_plain(V3 a) {
 // (ISA: V_DIV_SCALE_F64). vnormalize_shared evaluates that part once when |mag| is in [2^-400, 2^400] and every
 // component is +-0 or at least 2^-500 in magnitude (then no scaling happens, VCC is clear and v_div_fmas is a plain fma):
 // 5 + 3 x 4 instructions + the guards instead of 33, bit-identical (tests/test_gpu_round3.py: rtc_device_arith op 5 vs op 6
-// vs the host, 2 M triples). The binning kernel uses it (primary_dir); k_trace keeps vnormalize_plain, where the shared form
-// measured no gain (north star equal, C4 +1 %, profiles/r03_exp_shared_normalize.log).
+// vs the host, 2 M triples). The binning kernel uses it (primary_dir). In k_trace this per-lane form measured no gain (north
+// star equal, C4 +1 %, profiles/r03_exp_shared_normalize.log: both paths compiled in line and blended per lane); the flat
+// k_trace kernels take vnormalize_wave below, every other kernel keeps vnormalize_plain.
 DEVI V3 vnormalize_shared(V3 a) {
     const double mag = sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
     auto in_range = [](double v) { return __builtin_amdgcn_class(v, 0x060 /* +-0 */) || fabs(v) >= 0x1p-500; };
     if (fabs(mag) >= 0x1p-400 && fabs(mag) <= 0x1p400 && in_range(a.x) && in_range(a.y) && in_range(a.z)) {
+        const double r0 = __builtin_amdgcn_rcp(mag);
+        const double e0 = __builtin_fma(-mag, r0, 1.0);
+        const double r1 = __builtin_fma(r0, e0, r0);
+        const double e1 = __builtin_fma(-mag, r1, 1.0);
+        const double r = __builtin_fma(r1, e1, r1);
+        auto quot = [&](double x) {
+            const double q = x * r;
+            const double rem = __builtin_fma(-mag, q, x);
+            return __builtin_amdgcn_div_fixup(__builtin_fma(rem, r, q), mag, x);
+        };
+        return mk(quot(a.x), quot(a.y), quot(a.z));
+    }
+    return mk(a.x / mag, a.y / mag, a.z / mag);
+}
+// The same two forms, chosen per WAVE: the guard is evaluated per lane and balloted over the active lanes, and the wave takes
+// the shared form when no active lane fails it, the three plain divisions (one cold block) otherwise. Both forms give the
+// same bits in every lane that passes the guard, so which one a wave takes cannot change a result and nothing is blended.
+// Also returns `mag`, the correctly rounded square root (the shadow ray's distance).
+// The guard, exact and stricter than vnormalize_shared's condition:
+//   * v_frexp_exp_i32_f64 of each component (0 for +-0; the true exponent of a denormal), an integer minimum and one
+//     compare: every component is +-0 or at least 2^-500 in magnitude (2^-500 = 0.5 * 2^-499: exponent >= -499);
+//   * mag's biased exponent field in [1023 - 400, 1023 + 399], read off its upper word with one subtraction and one unsigned
+//     compare: mag in [2^-400, 2^400). mag is a square root: +0, positive, +inf or NaN, so zero, infinite and NaN magnitudes
+//     (fields 0 and 2047, and a NaN's sign bit only makes the difference larger) all fail and take the plain divisions.
+// Inf and NaN COMPONENTS need no term of their own (frexp_exp gives 0 for them, which passes): they make mag inf or NaN,
+// which fails. And even without that, v_div_fixup — the last instruction of both forms, with the same numerator and
+// denominator — decides every quotient with a NaN, an infinity or a zero among the two from those two operands alone,
+// whatever the refined quotient it is handed. tests/test_gpu_shared_normalize_flat.py (rtc_device_arith op 8 vs op 6 vs
+// the host) pins all of it, waves with lanes on both sides of the guard included.
+DEVI V3 vnormalize_wave(V3 a, double &mag_out) {
+    const double mag = sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
+    mag_out = mag;
+    const int emin = min(min(__builtin_amdgcn_frexp_exp(a.x), __builtin_amdgcn_frexp_exp(a.y)), __builtin_amdgcn_frexp_exp(a.z));
+    const uint32_t mag_hi = (uint32_t)(__builtin_bit_cast(unsigned long long, mag) >> 32);
+    const bool fits = emin >= -499 && mag_hi - ((1023u - 400u) << 20) < (800u << 20);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fits) == 0ull, 1)) { // (wave-uniform)
         const double r0 = __builtin_amdgcn_rcp(mag);
         const double e0 = __builtin_fma(-mag, r0, 1.0);
         const double r1 = __builtin_fma(r0, e0, r0);
@@ -878,7 +915,8 @@ DEVI void for_each_object(const PP &P, const Tables &T, const LdsView &L, bool l
 // ---- stages k_trace and k_aov share ------------------------------------------------------------------------------
 // Shape::normal_at shape.rs:34-40: the world normal at `point`, before the inside flip. A plane's normal does not depend on
 // the point: it was evaluated once per object at rtc_world_create (DevShade::plane_n).
-DEVI V3 shape_normal(const DevShade *S, const double *m_obj, V3 point) {
+// WAVE_NORM: the sphere's and the cube's normalisation through vnormalize_wave (the flat k_trace kernels), same bits.
+template <bool WAVE_NORM = false> DEVI V3 shape_normal(const DevShade *S, const double *m_obj, V3 point) {
     V3 ln = mk(0., 1., 0.);
     const uint32_t kind = S->kind;
     if (kind == RTC_SPHERE) {
@@ -893,14 +931,22 @@ DEVI V3 shape_normal(const DevShade *S, const double *m_obj, V3 point) {
         else ln = mk(0., 0., lp.z);
     }
     if (kind == RTC_PLANE) return mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]);
+    if constexpr (WAVE_NORM) {
+        double mag;
+        return vnormalize_wave(xvector3(S->nt, ln), mag);
+    }
     return vnormalize_plain(xvector3(S->nt, ln));
 }
 
 // The shadow ray of is_shadowed_by_light (shape.rs:717-719): v = light - over_point, its length, three divisions. Lanes
-// without a hit keep the `dir` and `dist` they came with.
-DEVI void shadow_ray(V3 light_pos, V3 over, bool hit, V3 &dir, double &dist) {
+// without a hit keep the `dir` and `dist` they came with. WAVE_NORM: through vnormalize_wave (the flat k_trace kernels), same bits.
+template <bool WAVE_NORM = false> DEVI void shadow_ray(V3 light_pos, V3 over, bool hit, V3 &dir, double &dist) {
     if (hit) {
         const V3 v = vsub(light_pos, over);
+        if constexpr (WAVE_NORM) {
+            dir = vnormalize_wave(v, dist);
+            return;
+        }
         dist = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
         dir = mk(v.x / dist, v.y / dist, v.z / dist);
     }
@@ -1071,6 +1117,19 @@ constexpr bool trace_scalar_walk(int src, bool refl, bool one, int lights) {
     if (RTC_SCALAR_TILE_WALK == 0 || src != SRC_CULL || refl) return false;
     if (!one && lights != 0) return false;
     return true;
+}
+// Vector::normalize through vnormalize_wave (one reciprocal per normalisation, chosen per wave) in the flat k_trace kernels:
+// a mask of sites, 1 = the pinhole ray generation, 2 = shadow_ray, 4 = shape_normal; 0 = vnormalize_plain and the three
+// divisions everywhere, the code as it was (kept for the A/B). trace_wave_normalize: the instantiations that take it — the
+// render flavour of SRC_CULL and SRC_CULL2 without a frame stack, one light, pinhole camera (with ONE and WHOLE and without).
+// The frame-stack kernels sit at their register limit (the per-lane form cost them 1.2 %,
+// profiles/r03_exp_shared_normalize.log); they, the multi-light, lens, projection, brute-force and probe instantiations and
+// k_aov, k_ao and k_gather are the parent's code (tools/isa_compare.py; profiles/shared_normalize_flat_*).
+#ifndef RTC_SHARED_NORMALIZE_FLAT
+#define RTC_SHARED_NORMALIZE_FLAT 7
+#endif
+constexpr bool trace_wave_normalize(int site, int src, bool refl, bool probe, bool alt, bool multi) {
+    return (RTC_SHARED_NORMALIZE_FLAT & site) != 0 && IS_CULL(src) && !refl && !probe && !alt && !multi;
 }
 
 // One suspended shade_hit call (shape.rs:685-700) on a lane's stack. The stack lives in scratch
@@ -1423,7 +1482,12 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             } else {
             const V3 pixel = xpoint(Pr.vinv, mk(world_x, world_y, -1.));
             ro = cam_origin;
-            rd = vnormalize_plain(vsub(pixel, cam_origin));
+            if constexpr (trace_wave_normalize(1, SRC, REFL, PROBE, ALT, MULTI)) {
+                double mag;
+                rd = vnormalize_wave(vsub(pixel, cam_origin), mag);
+            } else {
+                rd = vnormalize_plain(vsub(pixel, cam_origin));
+            }
             shared_origin = true;
             }
         }
@@ -1560,7 +1624,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             if (hit) {
                 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
                 eyev = vneg(rd);
-                normal = shape_normal(S, m_obj, point);
+                normal = shape_normal<trace_wave_normalize(4, SRC, REFL, PROBE, ALT, MULTI)>(S, m_obj, point);
                 inside = vdot(normal, eyev) < 0.0;
                 if (inside) normal = vneg(normal);
                 over = vadd(point, vmul(normal, RTC_EPSILON));
@@ -1568,7 +1632,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 reflectv = vreflect(rd, normal);
                 m_kr = S->reflective;
                 m_tr = S->transparency;
-                shadow_ray(lightp, over, hit, sdir, sdist);
+                shadow_ray<trace_wave_normalize(2, SRC, REFL, PROBE, ALT, MULTI)>(lightp, over, hit, sdir, sdist);
             }
 
             // ---- compute_refractive (shape.rs:115-141), open-set form, transparent hits only ----
@@ -2206,6 +2270,15 @@ __global__ void k_arith(uint32_t op, const double *a, const double *b, uint32_t 
             const V3 v = mk(a[i], a[i + 1], a[i + 2]);
             const V3 r3 = op == 5u ? vnormalize_shared(v) : vnormalize_plain(v);
             out[i] = r3.x; out[i + 1] = r3.y; out[i + 2] = r3.z;
+        }
+        return;
+    }
+    if (op == 8u) { // the same through vnormalize_wave, the flat k_trace kernels' form: thread t takes triple t, so a wave holds 64
+        // consecutive triples and takes one form for all of them
+        if (3ull * i + 2u < n) {
+            double mag;
+            const V3 r3 = vnormalize_wave(mk(a[3u * i], a[3u * i + 1u], a[3u * i + 2u]), mag);
+            out[3u * i] = r3.x; out[3u * i + 1u] = r3.y; out[3u * i + 2u] = r3.z;
         }
         return;
     }
