@@ -1602,6 +1602,93 @@ size_t      rtc_float_encoder_bytes(const rtc_float_encoder *e, uint8_t *buf, si
 rtc_status  rtc_float_encoder_write(const rtc_float_encoder *e, const char *path);
 void        rtc_float_encoder_destroy(rtc_float_encoder *e);
 
+/* ==== edge-aware filter: smoothing an AO, shadow or bounce plane under the AOV guides ================= */
+/* The sample fans (rtc_render_ao, rtc_render_gather, the `shadow` plane of an area-light World) place their samples at cell
+ * centres with no jitter, so a plane of few samples shows bands. This pass is the other half of the technique: an à-trous
+ * ("with holes") wavelet filter — a 5x5 B3-spline kernel applied `passes` times, its taps 1, 2, 4, ... pixels apart — whose
+ * every tap is weighted by how well the neighbour's AOV guides (rtc_render_aov's `index`, `point` and `normal` planes) agree
+ * with the pixel's own: the scheme of Dammertz et al., "Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
+ * Filtering" (HPG 2010), with a point-to-plane distance in place of the position distance. It smooths along a surface and
+ * not across an edge, a crease or a silhouette.
+ *
+ * All of it is f64 with no fused multiply-add, every product and sum evaluated in exactly the order written.
+ *   inv = 1.0 / plane_sigma, once (0.0 for +infinity);  h = {0.0625, 0.25, 0.375, 0.25, 0.0625}.
+ *   Pass i (from 0) reads plane A_i and writes A_{i+1} with step s = 1 << i; A_0 = `in`, the last pass writes `out`.
+ *   For pixel p = (x, y):
+ *     index[p] < 0: the pixel's values are copied bit for bit. Otherwise acc[c] = 0.0, wsum = 0.0, and for j = 0..4 (outer,
+ *     dy = (j - 2)*s) and i = 0..4 (inner, dx = (i - 2)*s), with q = (x + dx, y + dy), the tap is SKIPPED — nothing is added,
+ *     and its value is never read into the arithmetic — when
+ *       q is outside the image, or index[q] < 0,
+ *       or RTC_FILTER_SAME_OBJECT is set and index[q] != index[p],
+ *       or !(wz > 0.0), where e.c = point[q].c - point[p].c, d = fabs(((n_p.x*e.x) + (n_p.y*e.y)) + (n_p.z*e.z)),
+ *          wz = 1.0 - d*inv,
+ *       or !(m > 0.0), where m = ((n_p.x*n_q.x) + (n_p.y*n_q.y)) + (n_p.z*n_q.z); after this test m = m*m is applied
+ *          normal_squarings times,
+ *       or !(w > 0.0), where w = ((h[j]*h[i])*wz)*m.
+ *     Otherwise acc[c] = acc[c] + w*A_i[q][c] and wsum = wsum + w.
+ *     After the taps: wsum > 0.0 gives A_{i+1}[p][c] = acc[c] / wsum, a NaN quotient stored as 0x7FF8000000000000
+ *     (rtc_canvas_average's rule); otherwise the pixel is copied.
+ *   The comparisons are written so that a NaN guide drops a tap and poisons no sum; an inf under a skipped tap is harmless.
+ *
+ * Defaults, chosen so that a filtered 4x4-sample AO plane of data/ambient_occlusion.yml is closer (RMS) to the 16x16-sample
+ * plane than the raw one (profiles/filter_quality.log): RTC_FILTER_DEFAULT_*. plane_sigma is a distance in world units and
+ * relative to nothing.
+ * Limits. No variance guidance and no temporal accumulation; colour frames are not filtered (their texture is not in the
+ * guides); one sigma per call, none per pixel; the guides are those of the centre ray, so no filtering of lens, shutter,
+ * projection, group or Lua launches. */
+enum { RTC_FILTER_SAME_OBJECT = 1u << 0 };
+#define RTC_MAX_FILTER_PASSES 5u
+#define RTC_FILTER_DEFAULT_PLANE_SIGMA 0.05
+#define RTC_FILTER_DEFAULT_PASSES 2u
+#define RTC_FILTER_DEFAULT_NORMAL_SQUARINGS 3u
+typedef struct rtc_filter {          /* 24 bytes */
+    double   plane_sigma;            /* > 0, +infinity allowed (no plane test); NaN, 0, negative: RTC_ERR_ARG */
+    uint32_t passes;                 /* 1..RTC_MAX_FILTER_PASSES; pass i (from 0) has step s = 1 << i */
+    uint32_t normal_squarings;       /* 0..8: the normal weight is (n_p . n_q) squared this many times */
+    uint32_t flags;                  /* RTC_FILTER_SAME_OBJECT or 0; other bits RTC_ERR_ARG */
+    uint32_t _pad;                   /* 0 */
+} rtc_filter;
+/* [host] RTC_ERR_ARG for NULL or a field outside the ranges above (a nonzero _pad included); else RTC_OK. */
+rtc_status  rtc_filter_validate(const rtc_filter *flt);
+/* [host] the normative filter. `in` and `out`: row-major f64 planes of `channels` (1 or 3) values per pixel, not the same
+ * buffer. Of `guides` only index, point and normal are read; a NULL among the three is RTC_ERR_ARG, like a NULL pointer,
+ * another channel count or an invalid rtc_filter. The intermediate planes live in scratch (RTC_ERR_NOMEM without it). */
+rtc_status  rtc_plane_filter(const double *in, uint32_t channels, const rtc_aov_buffers *guides, uint32_t width, uint32_t height,
+                             const rtc_filter *flt, double *out);
+/* [device] the same bytes for planes in DEVICE memory, enqueued on the context's stream under the ordering rule of
+ * rtc_canvas_apply_ao_device: k_atrous (csrc/rtc_filter.hip), one launch per pass. d_in, d_out, point and normal 8-byte
+ * aligned, index 4; otherwise RTC_ERR_ARG, and nothing is launched. The ping-pong plane is a grow-only buffer of the context:
+ * no allocation per call once it has its size. */
+rtc_status  rtc_plane_filter_device(rtc_context *ctx, const void *d_in, uint32_t channels, const rtc_aov_buffers *d_guides,
+                                    uint32_t width, uint32_t height, const rtc_filter *flt, void *d_out);
+/* A count plane (rtc_render_ao's, or rtc_aov_buffers::shadow) as the fraction the filter takes: out[i] = (double)counts[i] /
+ * (double)n. n == 0 and NULL pointers are RTC_ERR_ARG; on the device also a d_counts that is not 2-byte or a d_out that is not
+ * 8-byte aligned. [host] normative; [device] one thread per pixel on the context's stream, the same bytes. */
+rtc_status  rtc_counts_to_fraction(const uint16_t *counts, uint32_t n, uint32_t width, uint32_t height, double *out);
+rtc_status  rtc_counts_to_fraction_device(rtc_context *ctx, const void *d_counts, uint32_t n, uint32_t width, uint32_t height,
+                                          void *d_out);
+/* Compositing an occlusion FRACTION, in place: every component c of pixel i becomes c * (1.0 - strength * occ[i]), f64 in that
+ * order: rtc_canvas_apply_ao's f64 sibling, and its bytes whenever occ = count/n. 0 <= strength <= 1, else RTC_ERR_ARG (NaN
+ * included); so are NULL pointers and a device pointer that is not 8-byte aligned. [host] normative; [device] the same bytes. */
+rtc_status  rtc_canvas_apply_occlusion(double *rgb, const double *occ, double strength, uint32_t width, uint32_t height);
+rtc_status  rtc_canvas_apply_occlusion_device(rtc_context *ctx, void *d_rgb, const void *d_occ, double strength, uint32_t width,
+                                              uint32_t height);
+/* Scenes whose camera asks for the filter. YAML: `add: camera` with `filter-plane-sigma` (> 0, or .inf) and, optionally,
+ * `filter-passes` (1..RTC_MAX_FILTER_PASSES) and `filter-normal-squarings` (0..8), which need a `filter-plane-sigma` and
+ * default to RTC_FILTER_DEFAULT_*; flags = RTC_FILTER_SAME_OBJECT. These entries are rtc_scene_load_yaml_gather plus the filter
+ * record: *has_filter_out = 1 and *filter_out filled when the camera has any of those keys, else 0 and *filter_out zeroed.
+ * Like the ao-* keys they ask for a pass, and every other YAML entry ignores them. */
+rtc_status  rtc_scene_load_yaml_filter(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                       struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                       rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                       struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
+                                       rtc_ao *gather_out, uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out);
+rtc_status  rtc_scene_load_yaml_filter_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                            struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                            rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                            struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
+                                            rtc_ao *gather_out, uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -392,6 +392,68 @@ def add_scaled(rgb: np.ndarray, plane: np.ndarray, strength: float = 1.0) -> np.
     return out
 
 
+def filter_spec(plane_sigma: float = FILTER_DEFAULT_PLANE_SIGMA, passes: int = FILTER_DEFAULT_PASSES,
+                normal_squarings: int = FILTER_DEFAULT_NORMAL_SQUARINGS, same_object: bool = True) -> RtcFilter:
+    """An edge-aware filter for plane_filter (rtc_filter, include/rtc.h): `passes` à-trous passes with taps 1, 2, 4, ... pixels
+    apart; a tap counts less the farther it lies off the pixel's tangent plane (`plane_sigma`, world units; math.inf: no plane
+    test) and the more its normal turns away ((n_p . n_q) squared `normal_squarings` times), and with `same_object` not at all
+    when it belongs to another object."""
+    f = RtcFilter()
+    f.plane_sigma, f.passes, f.normal_squarings, f.flags = float(plane_sigma), int(passes), int(normal_squarings), FILTER_SAME_OBJECT if same_object else 0
+    _check(lib().rtc_filter_validate(C.byref(f)), "rtc_filter_validate")
+    return f
+
+
+def _filter_guides(planes: dict, height: int, width: int) -> dict:
+    """The index, point and normal planes of `planes` (a dict as DeviceWorld.render_aov returns it) as the filter reads them."""
+    out = {}
+    for name in ("index", "point", "normal"):
+        dtype, comps = AOV_PLANES[name]
+        a = np.ascontiguousarray(planes[name], dtype=dtype)  # KeyError: the filter needs all three
+        if a.shape != ((height, width) if comps == 1 else (height, width, comps)):
+            raise ValueError(f"guide plane {name!r} does not have the values' size")
+        out[name] = a
+    return out
+
+
+def plane_filter(values: np.ndarray, planes: dict, flt: RtcFilter) -> np.ndarray:
+    """rtc_plane_filter: the (H, W) or (H, W, 3) f64 plane `values` (an occlusion fraction, a radiance or bounce plane) filtered
+    under the guides `planes` = {"index", "point", "normal"}; a new array of the same shape."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.ndim not in (2, 3) or (v.ndim == 3 and v.shape[2] != 3):
+        raise ValueError("plane_filter needs an (H, W) or (H, W, 3) plane")
+    g = _filter_guides(planes, v.shape[0], v.shape[1])
+    out = np.empty_like(v)
+    b = _aov_host_buffers(g)
+    _check(lib().rtc_plane_filter(v.ctypes.data_as(C.POINTER(C.c_double)), 1 if v.ndim == 2 else 3, C.byref(b), v.shape[1], v.shape[0], C.byref(flt),
+                                  out.ctypes.data_as(C.POINTER(C.c_double))), "rtc_plane_filter")
+    return out
+
+
+def counts_to_fraction(counts: np.ndarray, n: int) -> np.ndarray:
+    """rtc_counts_to_fraction: an (H, W) uint16 count plane (DeviceWorld.render_ao's, or an AOV `shadow` plane) as the f64
+    fraction count / n that plane_filter and apply_occlusion take."""
+    c = np.ascontiguousarray(counts, dtype=np.uint16)
+    if c.ndim != 2:
+        raise ValueError("counts_to_fraction needs an (H, W) plane")
+    out = np.empty(c.shape, dtype=np.float64)
+    _check(lib().rtc_counts_to_fraction(c.ctypes.data_as(C.POINTER(C.c_uint16)), int(n), c.shape[1], c.shape[0], out.ctypes.data_as(C.POINTER(C.c_double))),
+           "rtc_counts_to_fraction")
+    return out
+
+
+def apply_occlusion(rgb: np.ndarray, occ: np.ndarray, strength: float = 1.0) -> np.ndarray:
+    """rtc_canvas_apply_occlusion: a copy of the (H, W, 3) f64 canvas with every component multiplied by
+    1 - strength * occ of its pixel; apply_ao's bytes when occ is counts_to_fraction of its plane."""
+    out = np.array(rgb, dtype=np.float64, order="C", copy=True)
+    o = np.ascontiguousarray(occ, dtype=np.float64)
+    if out.ndim != 3 or out.shape[2] != 3 or o.shape != out.shape[:2]:
+        raise ValueError("apply_occlusion needs an (H, W, 3) canvas and an (H, W) plane")
+    _check(lib().rtc_canvas_apply_occlusion(out.ctypes.data_as(C.POINTER(C.c_double)), o.ctypes.data_as(C.POINTER(C.c_double)), float(strength),
+                                            out.shape[1], out.shape[0]), "rtc_canvas_apply_occlusion")
+    return out
+
+
 def projection(kind, width: float = 0.0, h_span: float = 2.0 * math.pi, v_span: float = math.pi) -> RtcProjection:
     """A projection for DeviceWorld.render_projection (rtc_projection, include/rtc.h). kind "orthographic" (or
     PROJ_ORTHOGRAPHIC): parallel rays, `width` the world-space width of the view. kind "panorama" (PROJ_PANORAMA): the
@@ -533,6 +595,14 @@ def load_yaml_gather(text: str | None = None, path: str | None = None):
     ln, has, a, has_a, g, has_g = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
     w, cam = _load_scene("rtc_scene_load_yaml_gather", text, path, ln, has, a, has_a, g, has_g)
     return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None)
+
+
+def load_yaml_filter(text: str | None = None, path: str | None = None):
+    """load_yaml_gather for scenes whose camera may also ask for the edge-aware filter (filter-plane-sigma / filter-passes /
+    filter-normal-squarings): -> (World, RtcCamera, RtcLens or None, RtcAo or None, RtcAo or None, RtcFilter or None)."""
+    ln, has, a, has_a, g, has_g, f, has_f = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcFilter(), C.c_uint32(0)
+    w, cam = _load_scene("rtc_scene_load_yaml_filter", text, path, ln, has, a, has_a, g, has_g, f, has_f)
+    return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None), (f if has_f.value else None)
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
@@ -1413,6 +1483,26 @@ class Context:
         _check(lib().rtc_canvas_add_scaled_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_plane), float(strength), width, height),
                "rtc_canvas_add_scaled_device")
 
+    def plane_filter_device(self, d_in: int, channels: int, pointers: dict, width: int, height: int, flt: RtcFilter, d_out: int) -> None:
+        """plane_filter of an f64 plane of `channels` values per pixel in DEVICE memory into the device buffer `d_out`, under the
+        guides `pointers` = {"index", "point", "normal"} (device addresses), enqueued on the context's stream
+        (rtc_plane_filter_device): the same bytes as the host function."""
+        b = _aov_buffers(pointers)
+        _check(lib().rtc_plane_filter_device(self._h, C.c_void_p(d_in), int(channels), C.byref(b), width, height, C.byref(flt), C.c_void_p(d_out)),
+               "rtc_plane_filter_device")
+
+    def counts_to_fraction_device(self, d_counts: int, n: int, width: int, height: int, d_out: int) -> None:
+        """counts_to_fraction of a uint16 plane in DEVICE memory into the f64 device buffer `d_out`, enqueued on the context's
+        stream (rtc_counts_to_fraction_device): the same bytes as the host function."""
+        _check(lib().rtc_counts_to_fraction_device(self._h, C.c_void_p(d_counts), int(n), width, height, C.c_void_p(d_out)),
+               "rtc_counts_to_fraction_device")
+
+    def apply_occlusion_device(self, d_rgb: int, d_occ: int, strength: float, width: int, height: int) -> None:
+        """apply_occlusion in place on an f64 canvas and an f64 fraction plane in DEVICE memory, enqueued on the context's stream
+        (rtc_canvas_apply_occlusion_device): the same bytes as the host function."""
+        _check(lib().rtc_canvas_apply_occlusion_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_occ), float(strength), width, height),
+               "rtc_canvas_apply_occlusion_device")
+
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
         return Shutter(self)
@@ -2052,7 +2142,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
            "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",

@@ -51,6 +51,15 @@ class RtcAo(C.Structure):
     _fields_ = [("radius", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32)]
 
 
+class RtcFilter(C.Structure):
+    _fields_ = [("plane_sigma", C.c_double), ("passes", C.c_uint32), ("normal_squarings", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+FILTER_SAME_OBJECT = 1
+MAX_FILTER_PASSES = 5
+FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS = 0.05, 2, 3  # RTC_FILTER_DEFAULT_*
+
+
 class RtcGatherBuffers(C.Structure):
     _fields_ = [("radiance", C.c_void_p), ("bounce", C.c_void_p)]
 
@@ -386,6 +395,19 @@ PROTOTYPES = {
     "rtc_float_encoder_bytes": (C.c_size_t, [VP, C.POINTER(C.c_uint8), C.c_size_t]),
     "rtc_float_encoder_write": (C.c_int32, [VP, C.c_char_p]),
     "rtc_float_encoder_destroy": (None, [VP]),
+    "rtc_filter_validate": (C.c_int32, [C.POINTER(RtcFilter)]),
+    "rtc_plane_filter": (C.c_int32, [PD, U32, C.POINTER(RtcAovBuffers), U32, U32, C.POINTER(RtcFilter), PD]),
+    "rtc_plane_filter_device": (C.c_int32, [VP, VP, U32, C.POINTER(RtcAovBuffers), U32, U32, C.POINTER(RtcFilter), VP]),
+    "rtc_counts_to_fraction": (C.c_int32, [C.POINTER(C.c_uint16), U32, U32, U32, PD]),
+    "rtc_counts_to_fraction_device": (C.c_int32, [VP, VP, U32, U32, U32, VP]),
+    "rtc_canvas_apply_occlusion": (C.c_int32, [PD, PD, D, U32, U32]),
+    "rtc_canvas_apply_occlusion_device": (C.c_int32, [VP, VP, VP, D, U32, U32]),
+    "rtc_scene_load_yaml_filter": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                               C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcFilter), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_filter_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                    C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcFilter), C.POINTER(U32)]),
 }
 
 

@@ -354,6 +354,8 @@ struct Scene {
     int ao_line = 0;                    // line of the camera entry that has ao keys, 0: none
     rtc_ao gather{};                    // the camera's gather pass (include/rtc.h "colour bleeding"); zeroed without gather keys
     int gather_line = 0;                // line of the camera entry that has gather keys, 0: none
+    rtc_filter filter{};                // the camera's edge-aware filter (include/rtc.h); zeroed without filter keys
+    int filter_line = 0;                // line of the camera entry that has filter keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -480,6 +482,27 @@ void interpret(const Node &root, Scene &sc) {
             };
             fan("ao", "ambient-occlusion", sc.ao, sc.ao_line);
             fan("gather", "gather", sc.gather, sc.gather_line);
+            // the edge-aware filter (include/rtc.h): filter-plane-sigma / filter-passes / filter-normal-squarings; asks for a pass too
+            sc.filter = rtc_filter{};
+            sc.filter_line = 0;
+            const Node *fps = e.get("filter-plane-sigma"), *fpa = e.get("filter-passes"), *fns = e.get("filter-normal-squarings");
+            if (fps || fpa || fns) {
+                sc.filter_line = e.line;
+                if (!fps) fail(e.line, "filter-passes / filter-normal-squarings need a filter-plane-sigma");
+                const bool unbounded = fps->kind == Node::Scalar && (fps->scalar == ".inf" || fps->scalar == "+.inf");
+                sc.filter.plane_sigma = unbounded ? std::numeric_limits<double>::infinity() : as_number(fps, "filter-plane-sigma");
+                if (!(sc.filter.plane_sigma > 0.)) fail(fps->line, "filter-plane-sigma must be a number > 0 (.inf: no plane test)");
+                auto whole = [&](const Node *n, const char *key, uint32_t lo, uint32_t hi, uint32_t dflt) {
+                    if (!n) return dflt;
+                    const double v = as_number(n, key);
+                    if (!(v >= lo && v <= hi) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                        fail(n->line, std::string(key) + " must be an integer in " + std::to_string(lo) + ".." + std::to_string(hi));
+                    return static_cast<uint32_t>(v);
+                };
+                sc.filter.passes = whole(fpa, "filter-passes", 1u, RTC_MAX_FILTER_PASSES, RTC_FILTER_DEFAULT_PASSES);
+                sc.filter.normal_squarings = whole(fns, "filter-normal-squarings", 0u, 8u, RTC_FILTER_DEFAULT_NORMAL_SQUARINGS);
+                sc.filter.flags = RTC_FILTER_SAME_OBJECT; // every range of rtc_filter_validate is checked above, key by key
+            }
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
             if (const Node *ss = e.get("shutter-samples")) {
@@ -569,12 +592,14 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
                             rtc_area_light *area_out = nullptr, rtc_lens *lens_out = nullptr, uint32_t *has_lens_out = nullptr,
                             rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr,
                             rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr, rtc_ao *ao_out = nullptr,
-                            uint32_t *has_ao_out = nullptr, rtc_ao *gather_out = nullptr, uint32_t *has_gather_out = nullptr) {
+                            uint32_t *has_ao_out = nullptr, rtc_ao *gather_out = nullptr, uint32_t *has_gather_out = nullptr,
+                            rtc_filter *filter_out = nullptr, uint32_t *has_filter_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
     if ((ao_out == nullptr) != (has_ao_out == nullptr)) return RTC_ERR_ARG;
     if ((gather_out == nullptr) != (has_gather_out == nullptr)) return RTC_ERR_ARG;
+    if ((filter_out == nullptr) != (has_filter_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -639,6 +664,10 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (gather_out) {
             *gather_out = sc.gather;
             *has_gather_out = sc.gather_line ? 1u : 0u;
+        }
+        if (filter_out) {
+            *filter_out = sc.filter;
+            *has_filter_out = sc.filter_line ? 1u : 0u;
         }
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -712,6 +741,16 @@ rtc_status rtc_scene_load_yaml_gather(const char *text, rtc_shape **shapes_out, 
     if (!lens_out || !has_lens_out || !ao_out || !has_ao_out || !gather_out || !has_gather_out) return RTC_ERR_ARG;
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
                      lens_out, has_lens_out, nullptr, nullptr, nullptr, nullptr, nullptr, ao_out, has_ao_out, gather_out, has_gather_out);
+}
+
+rtc_status rtc_scene_load_yaml_filter(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                      uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                      rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out, rtc_ao *gather_out,
+                                      uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out) {
+    if (!lens_out || !has_lens_out || !ao_out || !has_ao_out || !gather_out || !has_gather_out || !filter_out || !has_filter_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out, nullptr, nullptr, nullptr, nullptr, nullptr, ao_out, has_ao_out, gather_out, has_gather_out,
+                     filter_out, has_filter_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -803,6 +842,17 @@ rtc_status rtc_scene_load_yaml_gather_file(const char *path, rtc_shape **shapes_
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_gather(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                       lens_out, has_lens_out, ao_out, has_ao_out, gather_out, has_gather_out);
+}
+
+rtc_status rtc_scene_load_yaml_filter_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                           size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
+                                           rtc_ao *gather_out, uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_filter(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                      lens_out, has_lens_out, ao_out, has_ao_out, gather_out, has_gather_out, filter_out, has_filter_out);
 }
 
 } // extern "C"

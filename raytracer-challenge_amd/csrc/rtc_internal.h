@@ -42,6 +42,7 @@ struct rtc_context {
     uint32_t ao_usteps = 0, ao_vsteps = 0; // the grid d_ao_dirs holds; 0: none yet
     DevBuf<uint16_t> d_ao;           // the plane of rtc_render_ao (host-buffer entry point)
     DevBuf<double> d_gather;         // the planes of rtc_render_gather (host-buffer entry point): radiance, then bounce
+    DevBuf<double> d_filter;         // the ping-pong plane of rtc_plane_filter_device: width*height*channels, when passes > 1
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -237,6 +238,19 @@ struct AverageArgs {
     uint32_t nf; // 1..RTC_SHUTTER_RING
 };
 extern "C" hipError_t rtc_launch_average_over(const AverageArgs *a, hipStream_t stream);
+// k_atrous (rtc_filter.hip): one pass of the edge-aware filter (include/rtc.h), src to dst (never the same plane), taps `step`
+// pixels apart; `inv` = 1.0 / plane_sigma. grid_x is the launcher's own. k_counts_to_fraction / k_apply_occlusion beside it.
+struct AtrousArgs {
+    const double *src;
+    double *dst;
+    const int32_t *index;
+    const double *point, *normal;
+    double inv;
+    uint32_t width, height, step, squarings, grid_x;
+};
+extern "C" hipError_t rtc_launch_atrous(const AtrousArgs *a, uint32_t channels, bool same, hipStream_t stream);
+extern "C" hipError_t rtc_launch_counts_to_fraction(const uint16_t *counts, size_t px, uint32_t n, double *out, hipStream_t stream);
+extern "C" hipError_t rtc_launch_apply_occlusion(double *rgb, const double *occ, size_t px, double strength, hipStream_t stream);
 extern "C" rtc_status rtc_shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes, uint32_t samples); // host_math.cpp
 // The device table of `gamma` for work enqueued next on the context's own stream (rtc_api.cpp keeps the per-gamma cache).
 extern "C" rtc_status rtc_gamma_table_on_stream(rtc_context *ctx, float gamma, const DevGamma **out);

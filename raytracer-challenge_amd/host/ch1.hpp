@@ -197,6 +197,13 @@ class Canvas { // canvas.rs:16-109
             throw Panic(RTC_ERR_ARG, "Canvas::apply_ao: an f64 Canvas and a plane of its size are needed");
         check(rtc_canvas_apply_ao(pixels.data(), ao.data(), n_samples, strength, width, height), "Canvas::apply_ao");
     }
+    // An occlusion FRACTION composited in place (rtc_canvas_apply_occlusion, include/rtc.h): every component of pixel i times
+    // 1 - strength * occ[i]; apply_ao's bytes when occ is Aov::occlusion, and what takes a filtered plane. f64 canvases only.
+    void apply_occlusion(const std::vector<double> &occ, double strength = 1.0) {
+        if (pixels.size() != static_cast<size_t>(width) * height * 3 || occ.size() != static_cast<size_t>(width) * height)
+            throw Panic(RTC_ERR_ARG, "Canvas::apply_occlusion: an f64 Canvas and a plane of its size are needed");
+        check(rtc_canvas_apply_occlusion(pixels.data(), occ.data(), strength, width, height), "Canvas::apply_occlusion");
+    }
     // A plane added in place (rtc_canvas_add_scaled, include/rtc.h): every component c becomes c + strength * plane's. `plane`
     // is three doubles per pixel, Camera::render_gather's `bounce` for one. f64 canvases only.
     void add_scaled(const std::vector<double> &plane, double strength = 1.0) {
@@ -470,6 +477,28 @@ struct Aov {
         const rtc_aov_buffers b = const_cast<Aov *>(this)->buffers();
         check(rtc_aov_view_rgb8(v, &b, width, height, near, far, n_lights, c.rgb8.data()), "Aov::view");
         return c;
+    }
+    // The `shadow` plane as the fraction count / n_lights (rtc_counts_to_fraction): what filter and Canvas::apply_occlusion take.
+    std::vector<double> occlusion() const {
+        if (shadow.size() != static_cast<size_t>(width) * height) throw Panic(RTC_ERR_ARG, "Aov::occlusion: the Aov has no shadow plane");
+        std::vector<double> out(shadow.size());
+        check(rtc_counts_to_fraction(shadow.data(), n_lights, width, height, out.data()), "Aov::occlusion");
+        return out;
+    }
+    // A plane of `channels` (1 or 3) doubles per pixel — an occlusion fraction, a Gather's radiance or bounce — smoothed under
+    // this Aov's index, point and normal planes by the edge-aware filter (rtc_plane_filter, include/rtc.h).
+    std::vector<double> filter(const std::vector<double> &plane, uint32_t channels, const rtc_filter &spec) const {
+        const size_t px = static_cast<size_t>(width) * height;
+        if (index.size() != px || point.size() != 3 * px || normal.size() != 3 * px || plane.size() != px * channels)
+            throw Panic(RTC_ERR_ARG, "Aov::filter: the index, point and normal planes and a plane of their size are needed");
+        std::vector<double> out(plane.size());
+        const rtc_aov_buffers b = const_cast<Aov *>(this)->buffers();
+        check(rtc_plane_filter(plane.data(), channels, &b, width, height, &spec, out.data()), "Aov::filter");
+        return out;
+    }
+    // rtc.h's default filter: RTC_FILTER_DEFAULT_*, taps of the same object only
+    static rtc_filter default_filter() {
+        return rtc_filter{RTC_FILTER_DEFAULT_PLANE_SIGMA, RTC_FILTER_DEFAULT_PASSES, RTC_FILTER_DEFAULT_NORMAL_SQUARINGS, RTC_FILTER_SAME_OBJECT, 0u};
     }
     // The planes as data: one multi-channel OpenEXR file (rtc_float_format, include/rtc.h) — Z, N.*, P.*, id, shadow and,
     // with an f64 `colour` Canvas of the same size, its R, G, B as HALF (FLOAT with `colour_as_float`).

@@ -1,5 +1,6 @@
 """Register / scratch / LDS use of every k_trace, k_aov, k_ao and k_gather instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
-usage: python tools/kernel_resources.py [extra -D flags]"""
+With --filter: of the edge-aware filter's kernels (csrc/rtc_filter.hip) instead.
+usage: python tools/kernel_resources.py [--filter] [extra -D flags]"""
 import importlib.util
 import re
 import subprocess
@@ -14,18 +15,24 @@ build = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(build)
 
 
+FILTER = "--filter" in sys.argv[1:]
+EXTRA = [a for a in sys.argv[1:] if a != "--filter"]
+
+
 def remarks(name):  # one kernel unit's remarks
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [*build.kernel_compile_line(), "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:], "-c", str(build.CSRC / name), "-o", tmp + "/k.o"]
+        cmd = [*build.kernel_compile_line(), "-Rpass-analysis=kernel-resource-usage", *EXTRA, "-c", str(build.CSRC / name), "-o", tmp + "/k.o"]
         return subprocess.run(cmd, capture_output=True, text=True).stderr
 
 
 with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
-    t = "".join(pool.map(remarks, build.KERNEL_SOURCES))
+    t = "".join(pool.map(remarks, build.FILTER_KERNEL_SOURCES if FILTER else build.KERNEL_SOURCES))
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
-    if "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name and "k_gather" not in name and "k_add_scaled" not in name:
+    if FILTER:
+        pass
+    elif "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name and "k_gather" not in name and "k_add_scaled" not in name:
         continue
     def g(k):
         m = re.search(k + r": (\d+)", blk)
@@ -51,6 +58,12 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         tag = "k_gather<%s" % a.group(1) + (",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">")
     elif "k_add_scaled" in name:
         tag = "k_add_scaled"
+    elif (a := re.search(r"k_atrousILj(\d)ELb(\d)E", name)):  # the filter kernel: channels, RTC_FILTER_SAME_OBJECT
+        tag = "k_atrous<%s,same=%s>" % a.groups()
+    elif "k_counts_to_fraction" in name:
+        tag = "k_counts_to_fraction"
+    elif "k_apply_occlusion" in name:
+        tag = "k_apply_occlusion"
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")

@@ -1,6 +1,7 @@
 """Render a YAML scene and what its pixels saw (the AOV planes, include/rtc.h "arbitrary output variables"):
     python tools/render_aov.py SCENE.yml OUTDIR [--near N --far F] [--exr [PLANES]] [--ao [RADIUS,USTEPS,VSTEPS]] [--ao-strength S]
                                                 [--gather [RADIUS,USTEPS,VSTEPS]] [--gather-strength S]
+                                                [--filter [PLANE_SIGMA,PASSES,NORMAL_SQUARINGS]]
 writes OUTDIR/beauty.png (the colour frame) and depth.png, normal.png, index.png, shadow.png (rtc_aov_view_rgb8's pictures of
 the planes). Colour frame, planes and pictures stay in device memory; every file is encoded there (ImageEncoder.encode_device)
 and only the finished files cross PCIe — plus, when --near / --far are not both given, the depth plane, whose smallest and
@@ -14,8 +15,13 @@ plane (white: open, black: every sample occluded), and OUTDIR/beauty_ao.png, the
 renders the one-bounce gather pass (include/rtc.h "colour bleeding") — with the pass the scene's camera asks for
 (gather-radius / gather-usteps / gather-vsteps) or the one given here — and writes OUTDIR/frame.png (the colour frame again,
 through the f64 canvas), OUTDIR/bounce.png (the bounce plane as a picture) and OUTDIR/frame_bounce.png, the colour frame plus
-S * bounce (rtc_canvas_add_scaled_device; S = --gather-strength, default 1), all made on the device. Needs an MI355X (there is
-no CPU path)."""
+S * bounce (rtc_canvas_add_scaled_device; S = --gather-strength, default 1), all made on the device. --filter, together with
+--ao and / or --gather, also smooths their planes with the edge-aware filter (include/rtc.h "edge-aware filter") under the index,
+point and normal planes of the same frame — with the filter the scene's camera asks for (filter-plane-sigma / filter-passes /
+filter-normal-squarings), the one given here, or rtc.h's defaults — and writes OUTDIR/ao_filtered.png and
+beauty_ao_filtered.png (rtc_counts_to_fraction_device, rtc_plane_filter_device, rtc_canvas_apply_occlusion_device),
+OUTDIR/bounce_filtered.png and frame_bounce_filtered.png, and, with both passes, OUTDIR/frame_filtered.png: the colour frame times
+the filtered occlusion plus the filtered bounce. Needs an MI355X (there is no CPU path)."""
 import argparse
 import sys
 from pathlib import Path
@@ -36,6 +42,7 @@ def main(argv):
     ap.add_argument("--ao-strength", type=float, default=1.0)
     ap.add_argument("--gather", nargs="?", const="", default=None, metavar="RADIUS,USTEPS,VSTEPS")
     ap.add_argument("--gather-strength", type=float, default=1.0)
+    ap.add_argument("--filter", nargs="?", const="", default=None, metavar="PLANE_SIGMA,PASSES,NORMAL_SQUARINGS")
     args = ap.parse_args(argv[1:])
     rtc = package()
     abi = __import__("importlib").import_module(rtc.__name__ + ".abi")
@@ -60,6 +67,15 @@ def main(argv):
             gather = rtc.load_yaml_gather(path=args.scene)[4]
             if gather is None:
                 ap.error("--gather: the scene's camera has no gather-radius; give RADIUS,USTEPS,VSTEPS")
+    flt = None
+    if args.filter is not None:
+        if ao is None and gather is None:
+            ap.error("--filter smooths the planes of --ao and --gather: give at least one of them")
+        if args.filter:
+            sigma, passes, squarings = args.filter.split(",")
+            flt = rtc.filter_spec(float(sigma), passes=int(passes), normal_squarings=int(squarings))
+        else:
+            flt = rtc.load_yaml_filter(path=args.scene)[5] or rtc.filter_spec()
     width, height = cam.hsize, cam.vsize
     out = Path(args.outdir)
     out.mkdir(parents=True, exist_ok=True)
@@ -98,6 +114,8 @@ def main(argv):
         sizes["frame.exr"] = (out / "frame.exr").write_bytes(
             fenc.encode_device("exr", rgb.data_ptr(), width, height, {p: dev[p].data_ptr() for p in wanted}, "half"))
         fenc.close()
+    guides = {p: dev[p].data_ptr() for p in ("index", "point", "normal")}   # what --filter smooths under
+    filtered_frame = None
     if ao is not None:
         n = ao.usteps * ao.vsteps
         rgb = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
@@ -110,6 +128,21 @@ def main(argv):
         ctx.apply_ao_device(rgb.data_ptr(), dev["shadow"].data_ptr(), n, args.ao_strength, width, height)
         ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
         sizes["beauty_ao"] = (out / "beauty_ao.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
+        if flt is not None:
+            occ, occ_f = (torch.zeros(width * height, dtype=torch.float64, device="cuda:0") for _ in range(2))
+            torch.cuda.synchronize()
+            ctx.counts_to_fraction_device(dev["shadow"].data_ptr(), n, width, height, occ.data_ptr())
+            ctx.plane_filter_device(occ.data_ptr(), 1, guides, width, height, flt, occ_f.data_ptr())
+            rgb.fill_(1.0)   # the plane as a picture: white times 1 - occlusion
+            torch.cuda.synchronize()
+            ctx.apply_occlusion_device(rgb.data_ptr(), occ_f.data_ptr(), 1.0, width, height)
+            ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
+            sizes["ao_filtered"] = (out / "ao_filtered.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
+            dw.render_rows(cam, 0, height, rgb.data_ptr())
+            ctx.apply_occlusion_device(rgb.data_ptr(), occ_f.data_ptr(), args.ao_strength, width, height)
+            ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
+            sizes["beauty_ao_filtered"] = (out / "beauty_ao_filtered.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
+            filtered_frame = rgb   # the colour frame times the filtered occlusion; --gather adds its filtered bounce
     if gather is not None:
         rgb = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
         bounce = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
@@ -126,6 +159,17 @@ def main(argv):
         save("bounce", bounce.data_ptr())
         ctx.add_scaled_device(rgb.data_ptr(), bounce.data_ptr(), args.gather_strength, width, height)
         save("frame_bounce", rgb.data_ptr())
+        if flt is not None:
+            bounce_f = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
+            torch.cuda.synchronize()
+            ctx.plane_filter_device(bounce.data_ptr(), 3, guides, width, height, flt, bounce_f.data_ptr())
+            save("bounce_filtered", bounce_f.data_ptr())
+            dw.render_rows(cam, 0, height, rgb.data_ptr())
+            ctx.add_scaled_device(rgb.data_ptr(), bounce_f.data_ptr(), args.gather_strength, width, height)
+            save("frame_bounce_filtered", rgb.data_ptr())
+            if filtered_frame is not None:
+                ctx.add_scaled_device(filtered_frame.data_ptr(), bounce_f.data_ptr(), args.gather_strength, width, height)
+                save("frame_filtered", filtered_frame.data_ptr())
     hits = int((dev["index"] >= 0).sum().item())
     print(f"{out}: {width}x{height}, {len(world)} shapes, {n_lights} light sample(s), {hits} of {width * height} pixels hit, "
           f"depth {near:.6g} .. {far:.6g}; bytes: " + ", ".join(f"{k if '.' in k else k + '.png'} {v}" for k, v in sizes.items()))
