@@ -1689,6 +1689,94 @@ rtc_status  rtc_scene_load_yaml_filter_file(const char *path, rtc_shape **shapes
                                             struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
                                             rtc_ao *gather_out, uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out);
 
+/* ==== edge-adaptive anti-aliasing: extra rays only where the frame has contrast ====================== */
+/* A one-sample frame is fast and stair-stepped; cam->samples != 1 pays four or more rays for every pixel, sky and flat floor
+ * included. This pass renders the one-sample frame, finds the pixels whose neighbourhood has contrast — Color::distance_from
+ * against 0.01, the reference's own "needs more samples" test (camera.rs:109) — and replaces only those by the mean of a
+ * usteps x vsteps grid of sub-samples (Color::average_over, the lens's rule), all of it on the device.
+ *
+ * The statement: f64, no fused multiply-add, in exactly this order.
+ *   Rendered area R. RTC_MODE_RENDER_ASYNC: every pixel. RTC_MODE_RENDER: the pixels with x < hsize-1 and y < vsize-1; the
+ *     last row and column stay black, are never refined and are never compared against.
+ *   Mask, on the centre-sample frame C (rtc_render's bytes with cam->samples == 1): pixel p in R gets mask byte 1 iff some
+ *     4-neighbour q (left, right, up, down) that is also in R has d(p, q) > threshold, where dr = C[p].r - C[q].r (dg, db
+ *     alike) and d = sqrt(((dr*dr) + (dg*dg)) + (db*db)), an IEEE sqrt: Color::distance_from (color.rs:122-126). A NaN
+ *     distance compares false. Every other byte is 0. d is bitwise symmetric in p and q. The mask is taken once: refined
+ *     values never feed back into it.
+ *   Sample k of n = usteps*vsteps: u = k % usteps, v = k / usteps, x_offset = ((double)u + 0.5) / (double)usteps,
+ *     y_offset = ((double)v + 0.5) / (double)vsteps. 2 x 2 gives the reference's four fixed sub-samples in its order
+ *     (camera.rs:102-105).
+ *   A refined pixel (mask 1) is Color::average_over of color_at(rtc_camera_ray_for_pixel(cam, x, x_offset_k, y, y_offset_k),
+ *     RTC_MAX_REFLECTIONS) for k = 0..n-1: three sums that start at 0.0, add in k order and are divided once by (double)n.
+ *   An unrefined pixel keeps C's bytes.
+ * Limits. Pinhole cameras only: no adaptive form of the lens, the projections, the shutter, rtc_group or Lua launches. One
+ * detection pass, 4 neighbours, the colour frame as its only guide; no jitter (the oracle could not follow it). */
+#define RTC_MAX_AA_SAMPLES 256u
+#define RTC_AA_DEFAULT_THRESHOLD 0.01          /* camera.rs:109 */
+#define RTC_AA_DEFAULT_STEPS 4u                /* what an absent aa-usteps / aa-vsteps key means */
+#define RTC_AA_DEFAULT_MAX_RAYS (1u << 21)     /* 96 MB of rays and 48 MB of colours at the most */
+typedef struct rtc_adaptive {
+    double   threshold;        /* any value but NaN; +inf refines nothing, a negative value every pixel that has a neighbour */
+    uint32_t usteps, vsteps;   /* >= 1 each, usteps*vsteps <= RTC_MAX_AA_SAMPLES */
+    uint32_t max_rays;         /* refinement rays per probe launch; 0 = RTC_AA_DEFAULT_MAX_RAYS; otherwise >= usteps*vsteps */
+    uint32_t _pad;             /* 0 */
+} rtc_adaptive;                /* 24 bytes */
+typedef struct rtc_adaptive_info { /* 24 bytes */
+    uint64_t pixels_refined;   /* mask bytes that are 1 */
+    uint64_t rays_refined;     /* pixels_refined * usteps*vsteps */
+    uint32_t launches;         /* probe launches: ceil(pixels_refined / floor(max_rays / (usteps*vsteps))) */
+    uint32_t _pad;
+} rtc_adaptive_info;
+/* [host] RTC_ERR_ARG for NULL or a field outside the ranges above (a nonzero _pad included); else RTC_OK. */
+rtc_status  rtc_adaptive_validate(const rtc_adaptive *spec);
+/* [host] the offsets of sample k. RTC_ERR_ARG: a NULL pointer, an invalid spec, k >= usteps*vsteps. */
+rtc_status  rtc_adaptive_offset(const rtc_adaptive *spec, uint32_t k, double *x_offset, double *y_offset);
+/* [host] the normative mask of the row-major f64 canvas `rgb` into `mask` (width*height bytes); *n_flagged (may be NULL)
+ * receives the number of 1 bytes. RTC_ERR_ARG: a NULL rgb or mask, a mode that does not exist, a NaN threshold. */
+rtc_status  rtc_adaptive_mask(const double *rgb, uint32_t width, uint32_t height, uint32_t mode, double threshold,
+                              uint8_t *mask, uint64_t *n_flagged);
+/* [device] the same bytes for any canvas in DEVICE memory, enqueued on the context's stream (k_aa_mask, csrc/rtc_adaptive.hip):
+ * d_rgb 8-byte aligned (else RTC_ERR_ARG), d_mask any address. Exactly width*height bytes are written. More than 2^31-1
+ * pixels is RTC_ERR_ARG. The per-tile counts go to a grow-only buffer of the context. */
+rtc_status  rtc_adaptive_mask_device(rtc_context *ctx, const void *d_rgb, uint32_t width, uint32_t height, uint32_t mode,
+                                     double threshold, void *d_mask);
+/* [device] the adaptive frame into the caller's DEVICE canvas d_rgb (hsize*vsize*3 doubles, 8-byte aligned), where
+ * rtc_canvas_to_rgba8_device and every _encode_device entry take it; d_mask (hsize*vsize bytes, may be NULL) receives the
+ * mask; *info (may be NULL) what was refined.
+ *   cam->samples must be 1 (RTC_ERR_ARG otherwise). RTC_FLAG_NO_CULL gives the same bytes, RTC_FLAG_LDS_TABLE is
+ *   RTC_ERR_UNSUPPORTED, RTC_FLAG_AA_RESAMPLE is ignored. Every World form works: one light, several, area lights through
+ *   the light table, updated Worlds.
+ *   Pipeline (csrc/rtc_adaptive.hip): the one-sample launch of rtc_render_rows; k_aa_mask; k_aa_scan (prefix sum of the
+ *   tile counts); k_aa_list (the flagged pixels, row-major tile by tile, the same order in every run); then per chunk of
+ *   floor(max_rays / n) pixels k_aa_rays, rtc_color_at's kernel on device rays, k_aa_resolve.
+ *   Ordering. rtc_render_aov_device's rule: everything goes on the context's stream; after launches of a pipelined context
+ *   call rtc_context_fence first. The call reads back ONE count, the number of flagged pixels, which sizes the list and the
+ *   chunks: it waits for the stream once, after the scan, and returns with the refinement enqueued, not finished.
+ *   Counters. The base frame counts in rtc_stats exactly as rtc_render_rows counts it. The refinement rays count as
+ *   rtc_color_at counts its rays: not at all (probe launches carry no counters); info->rays_refined says how many there were.
+ *   Memory. The tile counts, the list, the chunk's rays and colours (and the mask when d_mask is NULL) are grow-only buffers
+ *   of the context: a second call of the same size allocates nothing. */
+rtc_status  rtc_render_adaptive_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_adaptive *spec,
+                                       uint32_t mode, uint32_t flags, void *d_rgb, void *d_mask, rtc_adaptive_info *info);
+/* [device] the same call with the frame (hsize*vsize*3 doubles) and, when `mask` is not NULL, the mask copied into HOST
+ * memory. Synchronous. `stats` (may be NULL) as in rtc_render: reset before, read after. */
+rtc_status  rtc_render_adaptive(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_adaptive *spec,
+                                uint32_t mode, uint32_t flags, double *rgb, uint8_t *mask, rtc_adaptive_info *info, rtc_stats *stats);
+/* Scenes whose camera asks for adaptive anti-aliasing. YAML: `add: camera` with any of `aa-threshold` (a number, .inf
+ * allowed; default RTC_AA_DEFAULT_THRESHOLD), `aa-usteps` and `aa-vsteps` (integers >= 1 whose product is at most
+ * RTC_MAX_AA_SAMPLES; default RTC_AA_DEFAULT_STEPS each); max_rays = 0. These entries are rtc_scene_load_yaml_area_lights
+ * plus the record: *has_adaptive_out = 1 and *adaptive_out filled when the camera has any of those keys, else 0 and
+ * *adaptive_out zeroed. A camera with aa-* keys and lens or projection keys is RTC_ERR_PARSE with a message that says so,
+ * whichever entry loads it; otherwise every other YAML entry ignores the aa-* keys. */
+rtc_status  rtc_scene_load_yaml_adaptive(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                         struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                         rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                         rtc_adaptive *adaptive_out, uint32_t *has_adaptive_out);
+rtc_status  rtc_scene_load_yaml_adaptive_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                              struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                              rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                              rtc_adaptive *adaptive_out, uint32_t *has_adaptive_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcAdaptive, RtcAdaptiveInfo, MAX_AA_SAMPLES, AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -454,6 +454,39 @@ def apply_occlusion(rgb: np.ndarray, occ: np.ndarray, strength: float = 1.0) -> 
     return out
 
 
+def adaptive(threshold: float = AA_DEFAULT_THRESHOLD, usteps: int = AA_DEFAULT_STEPS, vsteps: int = AA_DEFAULT_STEPS, max_rays: int = 0) -> RtcAdaptive:
+    """A spec for DeviceWorld.render_adaptive (rtc_adaptive, include/rtc.h): pixels whose colour is farther than `threshold`
+    (Color::distance_from) from a 4-neighbour's are re-rendered as the mean of usteps x vsteps sub-samples; `max_rays` bounds the
+    rays of one refinement launch (0: the library's default)."""
+    a = RtcAdaptive()
+    a.threshold, a.usteps, a.vsteps, a.max_rays = float(threshold), int(usteps), int(vsteps), int(max_rays)
+    _check(lib().rtc_adaptive_validate(C.byref(a)), "rtc_adaptive_validate")
+    return a
+
+
+def adaptive_offset(spec: RtcAdaptive, k: int) -> tuple:
+    """rtc_adaptive_offset: (x_offset, y_offset) of sample k of the spec's grid."""
+    xo, yo = C.c_double(0.0), C.c_double(0.0)
+    _check(lib().rtc_adaptive_offset(C.byref(spec), int(k), C.byref(xo), C.byref(yo)), "rtc_adaptive_offset")
+    return xo.value, yo.value
+
+
+def adaptive_mask(rgb: np.ndarray, mode: int, threshold: float) -> np.ndarray:
+    """rtc_adaptive_mask: the (H, W) uint8 mask of the (H, W, 3) f64 canvas — 1 where a pixel of the rendered area differs from
+    a 4-neighbour in it by more than `threshold`."""
+    c = np.ascontiguousarray(rgb, dtype=np.float64)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("adaptive_mask needs an (H, W, 3) canvas")
+    mask = np.empty(c.shape[:2], dtype=np.uint8)
+    _check(lib().rtc_adaptive_mask(c.ctypes.data_as(C.POINTER(C.c_double)), c.shape[1], c.shape[0], int(mode), float(threshold),
+                                   mask.ctypes.data_as(C.POINTER(C.c_uint8)), None), "rtc_adaptive_mask")
+    return mask
+
+
+def _adaptive_info_dict(info: RtcAdaptiveInfo) -> dict:
+    return {"pixels_refined": int(info.pixels_refined), "rays_refined": int(info.rays_refined), "launches": int(info.launches)}
+
+
 def projection(kind, width: float = 0.0, h_span: float = 2.0 * math.pi, v_span: float = math.pi) -> RtcProjection:
     """A projection for DeviceWorld.render_projection (rtc_projection, include/rtc.h). kind "orthographic" (or
     PROJ_ORTHOGRAPHIC): parallel rays, `width` the world-space width of the view. kind "panorama" (PROJ_PANORAMA): the
@@ -603,6 +636,14 @@ def load_yaml_filter(text: str | None = None, path: str | None = None):
     ln, has, a, has_a, g, has_g, f, has_f = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcFilter(), C.c_uint32(0)
     w, cam = _load_scene("rtc_scene_load_yaml_filter", text, path, ln, has, a, has_a, g, has_g, f, has_f)
     return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None), (f if has_f.value else None)
+
+
+def load_yaml_adaptive(text: str | None = None, path: str | None = None):
+    """load_yaml for scenes whose camera may ask for adaptive anti-aliasing (aa-threshold / aa-usteps / aa-vsteps):
+    -> (World, RtcCamera, RtcAdaptive or None)."""
+    a, has = RtcAdaptive(), C.c_uint32(0)
+    w, cam = _load_scene("rtc_scene_load_yaml_adaptive", text, path, a, has)
+    return w, cam, (a if has.value else None)
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
@@ -1503,6 +1544,12 @@ class Context:
         _check(lib().rtc_canvas_apply_occlusion_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_occ), float(strength), width, height),
                "rtc_canvas_apply_occlusion_device")
 
+    def adaptive_mask_device(self, d_rgb: int, width: int, height: int, mode: int, threshold: float, d_mask: int) -> None:
+        """adaptive_mask of an f64 canvas in DEVICE memory into the device bytes `d_mask`, enqueued on the context's stream
+        (rtc_adaptive_mask_device): the same bytes as the host function."""
+        _check(lib().rtc_adaptive_mask_device(self._h, C.c_void_p(d_rgb), width, height, mode, float(threshold), C.c_void_p(d_mask)),
+               "rtc_adaptive_mask_device")
+
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
         return Shutter(self)
@@ -1751,6 +1798,35 @@ class DeviceWorld:
         b = RtcGatherBuffers(**{name: a.ctypes.data for name, a in out.items()})
         _check(lib().rtc_render_gather(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.byref(b)), "rtc_render_gather")
         return out
+
+    def render_adaptive(self, cam: RtcCamera, spec: RtcAdaptive, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_mask: bool = False,
+                        with_stats: bool = False):
+        """The edge-adaptively anti-aliased frame (rtc_render_adaptive; rtc.adaptive makes `spec`): the one-sample frame with
+        every pixel whose 4-neighbourhood has contrast replaced by the mean of usteps x vsteps sub-samples.
+        -> (frame (vsize, hsize, 3) float64, info dict {pixels_refined, rays_refined, launches}), then the (vsize, hsize) uint8
+        mask with `with_mask` and the rtc_stats dict with `with_stats`."""
+        out = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
+        mask = np.empty((cam.vsize, cam.hsize), dtype=np.uint8) if with_mask else None
+        info, st = RtcAdaptiveInfo(), RtcStats()
+        _check(lib().rtc_render_adaptive(self.ctx._h, self._h, C.byref(cam), C.byref(spec), mode, flags, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                         mask.ctypes.data_as(C.POINTER(C.c_uint8)) if with_mask else None, C.byref(info),
+                                         C.byref(st) if with_stats else None), "rtc_render_adaptive")
+        res = [out, _adaptive_info_dict(info)]
+        if with_mask:
+            res.append(mask)
+        if with_stats:
+            res.append(_stats_dict(st))
+        return tuple(res)
+
+    def render_adaptive_device(self, cam: RtcCamera, spec: RtcAdaptive, d_rgb: int, d_mask: int | None = None, mode: int = MODE_RENDER_ASYNC,
+                               flags: int = 0) -> dict:
+        """render_adaptive into the DEVICE canvas `d_rgb` (vsize*hsize*3 doubles) and, when given, the device mask `d_mask`
+        (vsize*hsize bytes), on the context's stream (rtc_render_adaptive_device): waits once, for the number of flagged pixels,
+        and returns the info dict with the refinement enqueued."""
+        info = RtcAdaptiveInfo()
+        _check(lib().rtc_render_adaptive_device(self.ctx._h, self._h, C.byref(cam), C.byref(spec), mode, flags, C.c_void_p(d_rgb),
+                                                C.c_void_p(d_mask) if d_mask else None, C.byref(info)), "rtc_render_adaptive_device")
+        return _adaptive_info_dict(info)
 
     def render_gather_device(self, cam: RtcCamera, ao: RtcAo, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
         """The same into DEVICE buffers of vsize * hsize * 3 doubles, {"radiance": pointer, "bounce": pointer} with either left
@@ -2142,7 +2218,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "adaptive", "adaptive_offset", "adaptive_mask", "load_yaml_adaptive", "RtcAdaptive", "RtcAdaptiveInfo", "MAX_AA_SAMPLES", "AA_DEFAULT_THRESHOLD", "AA_DEFAULT_STEPS", "AA_DEFAULT_MAX_RAYS", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
            "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",

@@ -60,6 +60,18 @@ MAX_FILTER_PASSES = 5
 FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS = 0.05, 2, 3  # RTC_FILTER_DEFAULT_*
 
 
+class RtcAdaptive(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("usteps", C.c_uint32), ("vsteps", C.c_uint32), ("max_rays", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class RtcAdaptiveInfo(C.Structure):
+    _fields_ = [("pixels_refined", C.c_uint64), ("rays_refined", C.c_uint64), ("launches", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+MAX_AA_SAMPLES = 256
+AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS = 0.01, 4, 1 << 21  # RTC_AA_DEFAULT_*
+
+
 class RtcGatherBuffers(C.Structure):
     _fields_ = [("radiance", C.c_void_p), ("bounce", C.c_void_p)]
 
@@ -408,6 +420,17 @@ PROTOTYPES = {
     "rtc_scene_load_yaml_filter_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                     C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
                                                     C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcFilter), C.POINTER(U32)]),
+    "rtc_adaptive_validate": (C.c_int32, [C.POINTER(RtcAdaptive)]),
+    "rtc_adaptive_offset": (C.c_int32, [C.POINTER(RtcAdaptive), U32, PD, PD]),
+    "rtc_adaptive_mask": (C.c_int32, [PD, U32, U32, U32, D, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]),
+    "rtc_adaptive_mask_device": (C.c_int32, [VP, VP, U32, U32, U32, D, VP]),
+    "rtc_render_adaptive_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAdaptive), U32, U32, VP, VP, C.POINTER(RtcAdaptiveInfo)]),
+    "rtc_render_adaptive": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAdaptive), U32, U32, PD, C.POINTER(C.c_uint8),
+                                        C.POINTER(RtcAdaptiveInfo), C.POINTER(RtcStats)]),
+    "rtc_scene_load_yaml_adaptive": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                 C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcAdaptive), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_adaptive_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                      C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcAdaptive), C.POINTER(U32)]),
 }
 
 

@@ -356,6 +356,8 @@ struct Scene {
     int gather_line = 0;                // line of the camera entry that has gather keys, 0: none
     rtc_filter filter{};                // the camera's edge-aware filter (include/rtc.h); zeroed without filter keys
     int filter_line = 0;                // line of the camera entry that has filter keys, 0: none
+    rtc_adaptive adaptive{};            // the camera's adaptive anti-aliasing (include/rtc.h); zeroed without aa keys
+    int adaptive_line = 0;              // line of the camera entry that has aa keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -503,6 +505,28 @@ void interpret(const Node &root, Scene &sc) {
                 sc.filter.normal_squarings = whole(fns, "filter-normal-squarings", 0u, 8u, RTC_FILTER_DEFAULT_NORMAL_SQUARINGS);
                 sc.filter.flags = RTC_FILTER_SAME_OBJECT; // every range of rtc_filter_validate is checked above, key by key
             }
+            // edge-adaptive anti-aliasing (include/rtc.h): aa-threshold / aa-usteps / aa-vsteps, each with a default; asks for a pass
+            sc.adaptive = rtc_adaptive{};
+            sc.adaptive_line = 0;
+            const Node *aat = e.get("aa-threshold"), *aau = e.get("aa-usteps"), *aav = e.get("aa-vsteps");
+            if (aat || aau || aav) {
+                sc.adaptive_line = e.line;
+                if (sc.lens_line || sc.proj_line) fail(e.line, "aa-threshold / aa-usteps / aa-vsteps belong to a pinhole camera: not with lens or projection keys");
+                const bool unbounded = aat && aat->kind == Node::Scalar && (aat->scalar == ".inf" || aat->scalar == "+.inf");
+                sc.adaptive.threshold = !aat ? RTC_AA_DEFAULT_THRESHOLD : unbounded ? std::numeric_limits<double>::infinity() : as_number(aat, "aa-threshold");
+                if (sc.adaptive.threshold != sc.adaptive.threshold) fail(aat->line, "aa-threshold must be a number (.inf: refine nothing)");
+                auto steps = [&](const Node *n, const char *key) {
+                    if (!n) return (uint32_t)RTC_AA_DEFAULT_STEPS;
+                    const double v = as_number(n, key);
+                    if (!(v >= 1 && v <= RTC_MAX_AA_SAMPLES) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                        fail(n->line, std::string(key) + " must be an integer in 1.." + std::to_string(RTC_MAX_AA_SAMPLES));
+                    return static_cast<uint32_t>(v);
+                };
+                sc.adaptive.usteps = steps(aau, "aa-usteps");
+                sc.adaptive.vsteps = steps(aav, "aa-vsteps");
+                if ((uint64_t)sc.adaptive.usteps * sc.adaptive.vsteps > RTC_MAX_AA_SAMPLES) // with the checks above: every range of rtc_adaptive_validate
+                    fail(e.line, "too many anti-aliasing samples: aa-usteps x aa-vsteps is at most " + std::to_string(RTC_MAX_AA_SAMPLES));
+            }
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
             if (const Node *ss = e.get("shutter-samples")) {
@@ -593,13 +617,15 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
                             rtc_motion **motions_out = nullptr, uint32_t *n_motions_out = nullptr, uint32_t *samples_out = nullptr,
                             rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr, rtc_ao *ao_out = nullptr,
                             uint32_t *has_ao_out = nullptr, rtc_ao *gather_out = nullptr, uint32_t *has_gather_out = nullptr,
-                            rtc_filter *filter_out = nullptr, uint32_t *has_filter_out = nullptr) {
+                            rtc_filter *filter_out = nullptr, uint32_t *has_filter_out = nullptr,
+                            rtc_adaptive *adaptive_out = nullptr, uint32_t *has_adaptive_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
     if ((ao_out == nullptr) != (has_ao_out == nullptr)) return RTC_ERR_ARG;
     if ((gather_out == nullptr) != (has_gather_out == nullptr)) return RTC_ERR_ARG;
     if ((filter_out == nullptr) != (has_filter_out == nullptr)) return RTC_ERR_ARG;
+    if ((adaptive_out == nullptr) != (has_adaptive_out == nullptr)) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -668,6 +694,10 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (filter_out) {
             *filter_out = sc.filter;
             *has_filter_out = sc.filter_line ? 1u : 0u;
+        }
+        if (adaptive_out) {
+            *adaptive_out = sc.adaptive;
+            *has_adaptive_out = sc.adaptive_line ? 1u : 0u;
         }
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -751,6 +781,15 @@ rtc_status rtc_scene_load_yaml_filter(const char *text, rtc_shape **shapes_out, 
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
                      lens_out, has_lens_out, nullptr, nullptr, nullptr, nullptr, nullptr, ao_out, has_ao_out, gather_out, has_gather_out,
                      filter_out, has_filter_out);
+}
+
+rtc_status rtc_scene_load_yaml_adaptive(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                        uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                        rtc_adaptive *adaptive_out, uint32_t *has_adaptive_out) {
+    if (!adaptive_out || !has_adaptive_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     adaptive_out, has_adaptive_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -853,6 +892,16 @@ rtc_status rtc_scene_load_yaml_filter_file(const char *path, rtc_shape **shapes_
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_filter(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                       lens_out, has_lens_out, ao_out, has_ao_out, gather_out, has_gather_out, filter_out, has_filter_out);
+}
+
+rtc_status rtc_scene_load_yaml_adaptive_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                             uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                             size_t errbuf_len, rtc_adaptive *adaptive_out, uint32_t *has_adaptive_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_adaptive(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                        adaptive_out, has_adaptive_out);
 }
 
 } // extern "C"

@@ -1967,6 +1967,36 @@ rtc_status rtc_host_unregister(void *p) {
     return hipHostUnregister(p) == hipSuccess ? RTC_OK : RTC_ERR_DEVICE;
 }
 
+// (rtc_internal.h) the probe launch of rtc_color_at and of the adaptive pass's refinement: plan, parameters, trace
+rtc_status rtc_color_at_device(rtc_context *ctx, const rtc_world *w, const double *d_rays, uint32_t n, uint32_t remaining, uint32_t flags,
+                               double *d_rgb, rtc_hit *d_hits, bool record) {
+    rtc_world::Gen *gen = nullptr;
+    const rtc_status gs = current_gen(w, &gen);
+    if (gs != RTC_OK) return gs;
+    rtc_world::Gen &G = *gen;
+    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
+    LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_PROBE, flags);
+    in.hsize = n;
+    LaunchPlan plan;
+    rtc_plan_launch(in, plan);
+    if (plan.status != RTC_OK) return (rtc_status)plan.status;
+    RenderParams P;
+    planned_params(ctx, w, G, plan, P);
+    P.W = n; P.H = 1; P.y0 = 0; P.y1 = 1; P.mode = RTC_MODE_RENDER_ASYNC; P.samples = 1;
+    P.grid_y = 1;
+    P.band_stride = 1;
+    P.out = d_rgb;
+    P.rays = d_rays;
+    P.nrays = n;
+    P.remaining = remaining;
+    P.hits = d_hits;
+    LaunchLights LL;
+    lights_of(G, LL);
+    if (trace_planned(ctx, P, plan, LL, ctx->stream, nullptr, nullptr, nullptr, nullptr) != hipSuccess) return RTC_ERR_DEVICE;
+    if (record) HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
+    return RTC_OK;
+}
+
 rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays, uint32_t n, uint32_t remaining,
                         uint32_t flags, double *rgb, rtc_hit *hits) {
     if (!ctx || !w || !rays || !rgb || w->ctx != ctx) return RTC_ERR_ARG;
@@ -1978,32 +2008,12 @@ rtc_status rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *rays
     rtc_world::Gen *gen = nullptr;
     rtc_status st = current_gen(w, &gen);
     if (st != RTC_OK) return st;
-    rtc_world::Gen &G = *gen;
-    HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
+    HIP_TRY(order_behind_build(*gen, ctx->stream, BIT_STREAM));
     if (d_rays.reserve((size_t)6 * n) != RTC_OK || d_rgb.reserve((size_t)3 * n) != RTC_OK || (hits && d_hits.reserve(n) != RTC_OK))
         st = RTC_ERR_DEVICE;
     if (st == RTC_OK && hipMemcpyAsync(d_rays.get(), rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;
-    if (st == RTC_OK) {
-        LaunchPlanInputs in = plan_inputs(ctx, G, RTC_PLAN_PROBE, flags);
-        in.hsize = n;
-        LaunchPlan plan;
-        rtc_plan_launch(in, plan);
-        st = (rtc_status)plan.status;
-        RenderParams P;
-        planned_params(ctx, w, G, plan, P);
-        P.W = n; P.H = 1; P.y0 = 0; P.y1 = 1; P.mode = RTC_MODE_RENDER_ASYNC; P.samples = 1;
-        P.grid_y = 1;
-        P.band_stride = 1;
-        P.out = d_rgb.get();
-        P.rays = d_rays.get();
-        P.nrays = n;
-        P.remaining = remaining;
-        P.hits = d_hits.get();
-        LaunchLights LL;
-        lights_of(G, LL);
-        if (st == RTC_OK && trace_planned(ctx, P, plan, LL, ctx->stream, nullptr, nullptr, nullptr, nullptr) != hipSuccess) st = RTC_ERR_DEVICE;
-    }
+    if (st == RTC_OK) st = rtc_color_at_device(ctx, w, d_rays.get(), n, remaining, flags, d_rgb.get(), d_hits.get(), false);
     if (st == RTC_OK && hipMemcpyAsync(rgb, d_rgb.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         st = RTC_ERR_DEVICE;
     if (st == RTC_OK && hits && hipMemcpyAsync(hits, d_hits.get(), sizeof(rtc_hit) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 
 #include "rtc.h"
 
@@ -66,6 +67,31 @@ public:
 private:
     T *p_ = nullptr;
     size_t cap_ = 0;
+};
+
+// One page-locked 32-bit word of host memory, the landing place of a count that the host reads after a stream wait.
+// Allocated on first use, freed with its owner.
+class PinnedWord {
+public:
+    PinnedWord() = default;
+    PinnedWord(const PinnedWord &) = delete;
+    PinnedWord &operator=(const PinnedWord &) = delete;
+    ~PinnedWord() {
+        if (p_) (void)hipHostFree(p_);
+    }
+    rtc_status ready() {
+        if (p_) return RTC_OK;
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p_), sizeof(uint32_t), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            p_ = nullptr;
+        }
+        return rtc_status_of(e);
+    }
+    uint32_t *get() const { return p_; }
+
+private:
+    uint32_t *p_ = nullptr;
 };
 
 #endif

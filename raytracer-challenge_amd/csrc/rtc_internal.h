@@ -43,6 +43,14 @@ struct rtc_context {
     DevBuf<uint16_t> d_ao;           // the plane of rtc_render_ao (host-buffer entry point)
     DevBuf<double> d_gather;         // the planes of rtc_render_gather (host-buffer entry point): radiance, then bounce
     DevBuf<double> d_filter;         // the ping-pong plane of rtc_plane_filter_device: width*height*channels, when passes > 1
+    // Edge-adaptive anti-aliasing (rtc_adaptive.cpp; include/rtc.h), all grow-only:
+    DevBuf<uint32_t> d_aa_tiles;     // per 32x8 tile its count of flagged pixels, then its offset in the list, then the total
+    DevBuf<uint32_t> d_aa_list;      // the flagged pixels' indices y*hsize + x, tile by tile
+    DevBuf<unsigned char> d_aa_mask; // the mask of a call that was given none
+    DevBuf<double> d_aa_rays;        // one chunk's rays, 6 doubles each, pixel-major with the samples innermost
+    DevBuf<double> d_aa_colors;      // ... and their colours, 3 doubles each
+    DevBuf<double> d_aa_canvas;      // the frame of rtc_render_adaptive (host-buffer entry point)
+    PinnedWord aa_total;             // where the number of flagged pixels lands
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -251,6 +259,32 @@ struct AtrousArgs {
 extern "C" hipError_t rtc_launch_atrous(const AtrousArgs *a, uint32_t channels, bool same, hipStream_t stream);
 extern "C" hipError_t rtc_launch_counts_to_fraction(const uint16_t *counts, size_t px, uint32_t n, double *out, hipStream_t stream);
 extern "C" hipError_t rtc_launch_apply_occlusion(double *rgb, const double *occ, size_t px, double strength, hipStream_t stream);
+// Edge-adaptive anti-aliasing (rtc_adaptive.hip; include/rtc.h). Tiles are 32 x 8 pixels, numbered row-major.
+enum { RTC_AA_TILE_W = 32, RTC_AA_TILE_H = 8 };
+// k_aa_mask: the mask of the canvas `rgb` and, per tile, its number of 1 bytes in counts[tile]
+extern "C" hipError_t rtc_launch_aa_mask(const double *rgb, uint32_t width, uint32_t height, uint32_t mode, double threshold, unsigned char *mask,
+                                         uint32_t *counts, hipStream_t stream);
+// k_aa_scan: offsets[t] = counts[0] + ... + counts[t-1] for the `tiles` tiles, *total = their sum; one workgroup
+extern "C" hipError_t rtc_launch_aa_scan(const uint32_t *counts, uint32_t tiles, uint32_t *offsets, uint32_t *total, hipStream_t stream);
+// k_aa_list: tile t's flagged pixels, row-major within the tile, as y*width + x in list[offsets[t] ...]
+extern "C" hipError_t rtc_launch_aa_list(const unsigned char *mask, uint32_t width, uint32_t height, const uint32_t *counts, const uint32_t *offsets,
+                                         uint32_t *list, hipStream_t stream);
+// k_aa_rays / k_aa_resolve: the `pixels` list entries from `list` on, `usteps*vsteps` samples each
+struct AaRayArgs {
+    double half_width, half_height, pixel_size;
+    double vinv[12];
+    double origin[3]; // rtc_camera_ray_for_pixel's origin, evaluated by the host
+    const uint32_t *list;
+    double *rays;     // k_aa_rays: out, pixels * n * 6
+    uint32_t width, usteps, vsteps, pixels;
+};
+extern "C" hipError_t rtc_launch_aa_rays(const AaRayArgs *a, hipStream_t stream);
+extern "C" hipError_t rtc_launch_aa_resolve(const uint32_t *list, const double *colors, uint32_t pixels, uint32_t n, double *rgb, hipStream_t stream);
+// The middle of rtc_color_at (rtc_api.cpp): World::color_at for n rays in DEVICE memory into d_rgb (n x 3 doubles) and, when
+// not NULL, d_hits, enqueued on the context's stream behind a pending build of the World. `record`: the launch is not
+// awaited by its caller, so a later rtc_world_update has to wait for it.
+extern "C" rtc_status rtc_color_at_device(rtc_context *ctx, const rtc_world *w, const double *d_rays, uint32_t n, uint32_t remaining, uint32_t flags,
+                                          double *d_rgb, rtc_hit *d_hits, bool record);
 extern "C" rtc_status rtc_shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes, uint32_t samples); // host_math.cpp
 // The device table of `gamma` for work enqueued next on the context's own stream (rtc_api.cpp keeps the per-gamma cache).
 extern "C" rtc_status rtc_gamma_table_on_stream(rtc_context *ctx, float gamma, const DevGamma **out);

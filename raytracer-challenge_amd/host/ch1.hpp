@@ -578,6 +578,21 @@ class Camera { // camera.rs:17-160
     }
     void clear_shutter() { shutter_ = 0; }
     uint32_t shutter() const { return shutter_; } // 0: none
+    // Edge-adaptive anti-aliasing (rtc_adaptive, include/rtc.h): with it set, render / render_async / render_async1 give the
+    // one-sample frame with every pixel whose 4-neighbourhood has contrast replaced by the mean of usteps x vsteps sub-samples
+    // (rtc_render_adaptive); adaptive_info() says what the last such render refined. antialiasing_samples must be 1. A lens, a
+    // shutter or a projection has no adaptive form, and neither have the 8-bit renders: they throw RTC_ERR_UNSUPPORTED, as
+    // render_ao does. Not part of the reference's Camera.
+    void set_adaptive(double threshold = RTC_AA_DEFAULT_THRESHOLD, uint32_t usteps = RTC_AA_DEFAULT_STEPS, uint32_t vsteps = RTC_AA_DEFAULT_STEPS,
+                      uint32_t max_rays = 0) {
+        const rtc_adaptive a{threshold, usteps, vsteps, max_rays, 0u};
+        check(rtc_adaptive_validate(&a), "Camera::set_adaptive");
+        adaptive_ = a;
+        has_adaptive_ = true;
+    }
+    void clear_adaptive() { has_adaptive_ = false; }
+    bool has_adaptive() const { return has_adaptive_; }
+    const rtc_adaptive_info &adaptive_info() const { return adaptive_info_; }
     std::pair<Point, Vector> ray_for_pixel(uint32_t x, uint32_t y) const { // camera.rs:78-82
         double r[6];
         rtc_camera_ray_for_pixel(&flat_, x, 0.5, y, 0.5, r);
@@ -657,6 +672,13 @@ class Camera { // camera.rs:17-160
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Canvas canvas(hsize, vsize);
+        if (has_adaptive_) {
+            if (has_lens_ || shutter_ || has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render with adaptive anti-aliasing and a lens, a shutter or a projection");
+            World::Uploaded up(w);
+            check(rtc_render_adaptive(Device::get(), up.w, &c, &adaptive_, mode, RTC_FLAG_NONE, canvas.pixels.data(), nullptr, &adaptive_info_, nullptr),
+                  "Camera::render");
+            return canvas;
+        }
         if (has_projection_) {
             if (shutter_) check(RTC_ERR_UNSUPPORTED, "Camera::render with a projection and a shutter");
             World::Uploaded up(w);
@@ -674,6 +696,7 @@ class Camera { // camera.rs:17-160
         return canvas;
     }
     Canvas run8(const World &w, uint32_t mode) const {
+        if (has_adaptive_) check(RTC_ERR_UNSUPPORTED, "Camera::render_rgb8 with adaptive anti-aliasing");
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Canvas canvas = Canvas::quantised(hsize, vsize);
@@ -694,6 +717,7 @@ class Camera { // camera.rs:17-160
         return canvas;
     }
     Canvas run_rgba8(const World &w, uint32_t mode, float gamma) const {
+        if (has_adaptive_) check(RTC_ERR_UNSUPPORTED, "Camera::render_rgba8 with adaptive anti-aliasing");
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         if (has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_rgba8 with a projection");
@@ -763,6 +787,9 @@ class Camera { // camera.rs:17-160
     rtc_projection proj_{};
     bool has_projection_ = false;
     uint32_t shutter_ = 0;
+    rtc_adaptive adaptive_{};
+    bool has_adaptive_ = false;
+    mutable rtc_adaptive_info adaptive_info_{};
 };
 
 namespace detail {

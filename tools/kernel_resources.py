@@ -1,6 +1,7 @@
 """Register / scratch / LDS use of every k_trace, k_aov, k_ao and k_gather instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
-With --filter: of the edge-aware filter's kernels (csrc/rtc_filter.hip) instead.
-usage: python tools/kernel_resources.py [--filter] [extra -D flags]"""
+With --filter: of the edge-aware filter's kernels (csrc/rtc_filter.hip) instead; with --adaptive: of the adaptive anti-aliasing
+kernels (csrc/rtc_adaptive.hip).
+usage: python tools/kernel_resources.py [--filter | --adaptive] [extra -D flags]"""
 import importlib.util
 import re
 import subprocess
@@ -16,7 +17,8 @@ spec.loader.exec_module(build)
 
 
 FILTER = "--filter" in sys.argv[1:]
-EXTRA = [a for a in sys.argv[1:] if a != "--filter"]
+ADAPTIVE = "--adaptive" in sys.argv[1:]
+EXTRA = [a for a in sys.argv[1:] if a not in ("--filter", "--adaptive")]
 
 
 def remarks(name):  # one kernel unit's remarks
@@ -26,11 +28,12 @@ def remarks(name):  # one kernel unit's remarks
 
 
 with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
-    t = "".join(pool.map(remarks, build.FILTER_KERNEL_SOURCES if FILTER else build.KERNEL_SOURCES))
+    t = "".join(pool.map(remarks, build.FILTER_KERNEL_SOURCES if FILTER else [n for n in build.ADAPTIVE_SOURCES if n.endswith(".hip")] if ADAPTIVE
+                         else build.KERNEL_SOURCES))
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
-    if FILTER:
+    if FILTER or ADAPTIVE:
         pass
     elif "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name and "k_gather" not in name and "k_add_scaled" not in name:
         continue
@@ -64,6 +67,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         tag = "k_counts_to_fraction"
     elif "k_apply_occlusion" in name:
         tag = "k_apply_occlusion"
+    elif (a := re.search(r"(k_aa_[a-z]+)", name)):  # the adaptive anti-aliasing kernels
+        tag = a.group(1)
     else:
         tag = name[:44]
     scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
