@@ -1777,6 +1777,128 @@ rtc_status  rtc_scene_load_yaml_adaptive_file(const char *path, rtc_shape **shap
                                               rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
                                               rtc_adaptive *adaptive_out, uint32_t *has_adaptive_out);
 
+/* ==== exposure, tone mapping and bloom: from a linear f64 frame to one that fits 8 bits ============== */
+/* A World of several lights, an area light's samples or a bounce plane on top give canvases brighter than 1.0. Every 8-bit
+ * path ends in Color::scale, which clamps: a lit floor becomes a flat white patch. These passes are the step between the
+ * linear frame and rtc_canvas_to_rgba8[_device] / the encoders: frame statistics, an exposure and a tone curve, and the glare
+ * (bloom) around highlights. Each has a normative host statement and a device form that gives the same bytes.
+ *
+ * Arithmetic: f64 throughout, no fused multiply-add, the operations in exactly the order written here. A NaN result is
+ * stored as 0x7FF8000000000000 (rtc_canvas_average's rule). Nothing here calls exp, log or pow on the device — the device's
+ * versions are not the host's bit for bit — which is why the curves are the rational ones, why the auto exposure uses the
+ * ARITHMETIC mean luminance and not the log-average, and why the bloom's weights are a host table that travels in the kernel
+ * arguments.
+ *
+ * Luminance: Y(c) = ((0.2126*r) + (0.7152*g)) + (0.0722*b). */
+typedef struct rtc_luminance { /* 24 bytes */
+    double   max;              /* the largest contributing luminance; 0.0 when none contributes */
+    double   sum;              /* the contributions' sum in the tree order below */
+    uint64_t count;            /* how many pixels contribute */
+} rtc_luminance;
+/* [host] the normative statistics of the row-major f64 canvas `rgb` (width*height*3 doubles).
+ *   A pixel contributes y = Y(c) when y > 0.0 && y < +inf; otherwise it contributes +0.0 and is not counted (NaN, negative,
+ *   zero and infinite luminances alike).
+ *   max starts at 0.0 and is the largest contributing y: independent of the order.
+ *   sum: take the contributions in row-major order; reduce blocks of 256 consecutive values, the last block padded with +0.0:
+ *   within a block, for s = 128, 64, ..., 1 do v[i] = v[i] + v[i+s] for every i < s, and v[0] is the block's result; reduce the
+ *   block results the same way, level by level, until one value is left (a frame of at most 256 pixels: one level; an empty
+ *   frame: one block of padding, sum +0.0).
+ *   count is an integer sum.
+ * RTC_ERR_ARG: a NULL pointer. RTC_ERR_NOMEM: no room for the block results (width*height/256 doubles). */
+rtc_status  rtc_canvas_luminance(const double *rgb, uint32_t width, uint32_t height, rtc_luminance *out);
+/* [device] the same record for a canvas in DEVICE memory, written into DEVICE memory at d_out (24 bytes), enqueued on the
+ * context's stream (k_lum_pixels, then k_lum_records per further level, csrc/rtc_post.hip: one launch per level, at most three
+ * below 2^24 pixels); no host wait, so rtc_canvas_tonemap_device can read it in stream order. Ordering and alignment are
+ * rtc_canvas_apply_ao_device's: d_rgb and d_out 8-byte aligned, else RTC_ERR_ARG and nothing is launched. More than 2^32-256
+ * pixels (2^24-1 workgroups of 256) is RTC_ERR_ARG. The levels' block results go to a grow-only buffer of the context. */
+rtc_status  rtc_canvas_luminance_device(rtc_context *ctx, const void *d_rgb, uint32_t width, uint32_t height, void *d_out);
+
+#define RTC_TONEMAP_LINEAR   0u
+#define RTC_TONEMAP_REINHARD 1u
+#define RTC_TONEMAP_ACES     2u
+#define RTC_TONEMAP_AUTO_EXPOSURE 1u  /* flags: `exposure` is the key (0.18, say) that the frame's mean luminance is mapped to */
+#define RTC_TONEMAP_AUTO_WHITE    2u  /* flags: the white point is the frame's largest luminance after exposure */
+typedef struct rtc_tonemap {
+    double   exposure;         /* finite, > 0: the multiplier, or the key with RTC_TONEMAP_AUTO_EXPOSURE */
+    double   white;            /* > 0, +inf allowed (plain Reinhard): the luminance REINHARD maps to 1; ignored with AUTO_WHITE */
+    uint32_t curve;            /* RTC_TONEMAP_* */
+    uint32_t flags;            /* RTC_TONEMAP_AUTO_* */
+} rtc_tonemap;                 /* 24 bytes */
+/* [host] RTC_ERR_ARG for NULL, an exposure that is not finite and > 0, a white that is not > 0 (NaN included), an unknown
+ * curve or an unknown flag bit; else RTC_OK. */
+rtc_status  rtc_tonemap_validate(const rtc_tonemap *spec);
+/* [host] the normative multiplier and white term of a frame. `stats` may be NULL without AUTO flags and is RTC_ERR_ARG
+ * with them; an invalid spec or a NULL output is RTC_ERR_ARG.
+ *   m = exposure. With AUTO_EXPOSURE: mean = sum / (double)count, and m = exposure / mean when count > 0 && mean > 0.0,
+ *   else m = 1.0.
+ *   Lw = white. With AUTO_WHITE: Lw = max * m.
+ *   inv_w2 = 1.0 / (Lw*Lw) when Lw > 0.0 && Lw < +inf, else 0.0. */
+rtc_status  rtc_tonemap_resolve(const rtc_tonemap *spec, const rtc_luminance *stats, double *m, double *inv_w2);
+/* [host] the normative tone map of `in` (width*height*3 doubles) into `out`, which may be `in`. Per pixel first c' = c * m
+ * per channel, then
+ *   LINEAR:   c'.
+ *   REINHARD  (extended, on luminance): L = Y(c'). If !(L > 0.0) the pixel is c'. Otherwise s = (1.0 + (L*inv_w2)) / (1.0 + L)
+ *             and out = c' * s per channel.
+ *   ACES      (Narkowicz's fit, per channel x = c'): if !(x > 0.0) the result is 0.0. Otherwise a = (2.51*x) + 0.03,
+ *             b = (2.43*x) + 0.59, o = (x*a) / ((x*b) + 0.14); the result is 1.0 if o > 1.0, else o.
+ * `stats` as in rtc_tonemap_resolve. RTC_ERR_ARG: a NULL canvas, an invalid spec, AUTO flags without stats. */
+rtc_status  rtc_canvas_tonemap(const double *in, uint32_t width, uint32_t height, const rtc_tonemap *spec,
+                               const rtc_luminance *stats, double *out);
+/* [device] the same bytes for canvases in DEVICE memory (k_tonemap, one thread per pixel). d_stats is the record
+ * rtc_canvas_luminance_device left in DEVICE memory: every thread derives m and inv_w2 from it, so an auto-exposed frame
+ * never waits for the stream. d_stats may be NULL without AUTO flags. d_out may be d_in. Ordering, alignment and the largest
+ * frame as above. */
+rtc_status  rtc_canvas_tonemap_device(rtc_context *ctx, const void *d_in, uint32_t width, uint32_t height, const rtc_tonemap *spec,
+                                      const void *d_stats, void *d_out);
+
+#define RTC_MAX_BLOOM_RADIUS 32u
+typedef struct rtc_bloom {
+    double   threshold;        /* finite, >= 0: only luminance above it glares */
+    double   strength;         /* finite, >= 0: how much of the blurred bright pass is added */
+    double   sigma;            /* finite, > 0, in pixels; (2.0*sigma)*sigma must be > 0.0 too (no underflow) */
+    uint32_t radius;           /* 1..RTC_MAX_BLOOM_RADIUS: 2*radius + 1 taps per axis */
+    uint32_t _pad;             /* 0 */
+} rtc_bloom;                   /* 32 bytes */
+/* [host] RTC_ERR_ARG for NULL or a field outside the ranges above; else RTC_OK. */
+rtc_status  rtc_bloom_validate(const rtc_bloom *spec);
+/* [host only] the normative weights w[0 .. 2*radius]: g[k] = exp(-((double)(k*k)) / ((2.0*sigma)*sigma)) for k = -R..R;
+ * sum adds the g[k] in k order, starting at 0.0; w[k+R] = g[k] / sum. The device never evaluates exp: the table travels in
+ * the kernel arguments. RTC_ERR_ARG: an invalid spec, a NULL table. */
+rtc_status  rtc_bloom_weights(const rtc_bloom *spec, double *w);
+/* [host] the normative bloom of `in` (width*height*3 doubles, C) into `out`, which may be `in`.
+ *   Bright pass B[p]: L = Y(C[p]). If !(L > threshold) || !(L < +inf), B is (+0.0, +0.0, +0.0). Otherwise
+ *     k = (L - threshold) / L and B_c = C_c * k.
+ *   Horizontal pass: H[x,y]_c starts acc = 0.0; for k = -R..R in order, acc = acc + (w[k+R] * B[x+k, y]_c). A tap outside
+ *     the image has the value +0.0; adding it or skipping it gives the same bytes, since acc can never be -0.0.
+ *   Vertical pass: V[x,y]_c the same over H[x, y+k]_c.
+ *   Composite: out_c = C_c + (strength * V_c).
+ * RTC_ERR_ARG: a NULL canvas, an invalid spec. RTC_ERR_NOMEM: no room for the two planes B and H. */
+rtc_status  rtc_canvas_bloom(const double *in, uint32_t width, uint32_t height, const rtc_bloom *spec, double *out);
+/* [device] the same bytes for canvases in DEVICE memory: k_bloom_h (bright pass at staging, a row segment and its halo in
+ * LDS, H into a grow-only plane of the context), then k_bloom_v (a tile of H with its halo rows in LDS, one channel per
+ * sweep, writes the composite). d_out may be d_in: the vertical pass reads C only at its own pixel. Ordering and alignment
+ * as above. A frame of more than 2^24-1 row segments (ceil(width/256) * height) or 32 x 64 tiles is RTC_ERR_ARG: a launch
+ * holds fewer than 2^32 threads. A second call of the same size allocates nothing. */
+rtc_status  rtc_canvas_bloom_device(rtc_context *ctx, const void *d_in, uint32_t width, uint32_t height, const rtc_bloom *spec,
+                                    void *d_out);
+/* Scenes whose camera asks for post-processing. YAML: `add: camera` with any of
+ *   tonemap-curve (linear | reinhard | aces; default reinhard), tonemap-exposure (finite, > 0; default 1.0), tonemap-key (finite,
+ *   > 0: sets RTC_TONEMAP_AUTO_EXPOSURE with that key and excludes tonemap-exposure), tonemap-white (a number > 0, .inf, or
+ *   `auto`: RTC_TONEMAP_AUTO_WHITE; default .inf);
+ *   bloom-threshold (default 1.0), bloom-strength (default 0.5), bloom-sigma (default 2.0), bloom-radius (integer; default 6).
+ * These entries are rtc_scene_load_yaml_area_lights plus the two records: *has_tonemap_out = 1 and *tonemap_out filled when
+ * the camera has any tonemap-* key, else 0 and the record zeroed; the bloom-* keys and *bloom_out alike. A value outside a
+ * record's ranges, or tonemap-key together with tonemap-exposure, is RTC_ERR_PARSE with a message. Every other YAML entry
+ * ignores the keys. */
+rtc_status  rtc_scene_load_yaml_post(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                     struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                     rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                     rtc_tonemap *tonemap_out, uint32_t *has_tonemap_out, rtc_bloom *bloom_out, uint32_t *has_bloom_out);
+rtc_status  rtc_scene_load_yaml_post_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                          struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                          rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                          rtc_tonemap *tonemap_out, uint32_t *has_tonemap_out, rtc_bloom *bloom_out, uint32_t *has_bloom_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcAdaptive, RtcAdaptiveInfo, MAX_AA_SAMPLES, AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcAdaptive, RtcAdaptiveInfo, MAX_AA_SAMPLES, AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS, RtcLuminance, RtcTonemap, RtcBloom, TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES, TONEMAP_CURVES, TONEMAP_AUTO_EXPOSURE, TONEMAP_AUTO_WHITE, MAX_BLOOM_RADIUS, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -483,6 +483,79 @@ def adaptive_mask(rgb: np.ndarray, mode: int, threshold: float) -> np.ndarray:
     return mask
 
 
+def _canvas_arg(rgb: np.ndarray, what: str) -> np.ndarray:
+    c = np.ascontiguousarray(rgb, dtype=np.float64)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError(what + " needs an (H, W, 3) canvas")
+    return c
+
+
+def tonemap_spec(curve="reinhard", exposure: float = 1.0, white: float = math.inf, key: float | None = None, auto_white: bool = False) -> RtcTonemap:
+    """A record for rtc.tonemap / Context.tonemap_device (rtc_tonemap, include/rtc.h). `curve`: "linear", "reinhard", "aces" or
+    a TONEMAP_* value. `exposure` multiplies every channel; `key`, when given, replaces it: the frame's mean luminance is mapped
+    to that value (TONEMAP_AUTO_EXPOSURE, needs the statistics). `white` is the luminance REINHARD maps to 1 (inf: the plain
+    curve); `auto_white` takes the frame's largest luminance (TONEMAP_AUTO_WHITE, needs the statistics)."""
+    t = RtcTonemap()
+    t.curve = TONEMAP_CURVES[curve] if isinstance(curve, str) else int(curve)
+    t.exposure = float(exposure if key is None else key)
+    t.white = float(white)
+    t.flags = (TONEMAP_AUTO_EXPOSURE if key is not None else 0) | (TONEMAP_AUTO_WHITE if auto_white else 0)
+    _check(lib().rtc_tonemap_validate(C.byref(t)), "rtc_tonemap_validate")
+    return t
+
+
+def bloom_spec(threshold: float = 1.0, strength: float = 0.5, sigma: float = 2.0, radius: int = 6) -> RtcBloom:
+    """A record for rtc.bloom / Context.bloom_device (rtc_bloom, include/rtc.h): luminance above `threshold` is blurred by a
+    separable Gaussian of `sigma` pixels cut at `radius` (1..MAX_BLOOM_RADIUS) and added `strength` times."""
+    b = RtcBloom()
+    b.threshold, b.strength, b.sigma, b.radius = float(threshold), float(strength), float(sigma), int(radius)
+    _check(lib().rtc_bloom_validate(C.byref(b)), "rtc_bloom_validate")
+    return b
+
+
+def luminance(rgb: np.ndarray) -> RtcLuminance:
+    """rtc_canvas_luminance: the frame statistics {max, sum, count} of an (H, W, 3) f64 canvas, the sum in the header's tree order."""
+    c = _canvas_arg(rgb, "luminance")
+    out = RtcLuminance()
+    _check(lib().rtc_canvas_luminance(c.ctypes.data_as(C.POINTER(C.c_double)), c.shape[1], c.shape[0], C.byref(out)), "rtc_canvas_luminance")
+    return out
+
+
+def tonemap_resolve(spec: RtcTonemap, stats: RtcLuminance | None = None) -> tuple:
+    """rtc_tonemap_resolve: (m, inv_w2), the multiplier and white term `spec` gives a frame with the statistics `stats`."""
+    m, iw = C.c_double(0.0), C.c_double(0.0)
+    _check(lib().rtc_tonemap_resolve(C.byref(spec), C.byref(stats) if stats is not None else None, C.byref(m), C.byref(iw)), "rtc_tonemap_resolve")
+    return m.value, iw.value
+
+
+def tonemap(rgb: np.ndarray, spec: RtcTonemap, stats: RtcLuminance | None = None) -> np.ndarray:
+    """rtc_canvas_tonemap: the tone-mapped copy of an (H, W, 3) f64 canvas. With an AUTO flag in `spec` the statistics are
+    `stats`, or the canvas's own when none are given."""
+    c = _canvas_arg(rgb, "tonemap")
+    if stats is None and spec.flags:
+        stats = luminance(c)
+    out = np.empty_like(c)
+    _check(lib().rtc_canvas_tonemap(c.ctypes.data_as(C.POINTER(C.c_double)), c.shape[1], c.shape[0], C.byref(spec),
+                                    C.byref(stats) if stats is not None else None, out.ctypes.data_as(C.POINTER(C.c_double))), "rtc_canvas_tonemap")
+    return out
+
+
+def bloom_weights(spec: RtcBloom) -> np.ndarray:
+    """rtc_bloom_weights: the 2*radius + 1 normalised Gaussian weights of `spec`."""
+    w = np.empty(2 * spec.radius + 1, dtype=np.float64)
+    _check(lib().rtc_bloom_weights(C.byref(spec), w.ctypes.data_as(C.POINTER(C.c_double))), "rtc_bloom_weights")
+    return w
+
+
+def bloom(rgb: np.ndarray, spec: RtcBloom) -> np.ndarray:
+    """rtc_canvas_bloom: a copy of an (H, W, 3) f64 canvas with the blurred bright pass added."""
+    c = _canvas_arg(rgb, "bloom")
+    out = np.empty_like(c)
+    _check(lib().rtc_canvas_bloom(c.ctypes.data_as(C.POINTER(C.c_double)), c.shape[1], c.shape[0], C.byref(spec),
+                                  out.ctypes.data_as(C.POINTER(C.c_double))), "rtc_canvas_bloom")
+    return out
+
+
 def _adaptive_info_dict(info: RtcAdaptiveInfo) -> dict:
     return {"pixels_refined": int(info.pixels_refined), "rays_refined": int(info.rays_refined), "launches": int(info.launches)}
 
@@ -644,6 +717,15 @@ def load_yaml_adaptive(text: str | None = None, path: str | None = None):
     a, has = RtcAdaptive(), C.c_uint32(0)
     w, cam = _load_scene("rtc_scene_load_yaml_adaptive", text, path, a, has)
     return w, cam, (a if has.value else None)
+
+
+def load_yaml_post(text: str | None = None, path: str | None = None):
+    """load_yaml for scenes whose camera may ask for post-processing (tonemap-curve / tonemap-exposure / tonemap-key /
+    tonemap-white, bloom-threshold / bloom-strength / bloom-sigma / bloom-radius): -> (World, RtcCamera, RtcTonemap or None,
+    RtcBloom or None)."""
+    t, has_t, b, has_b = RtcTonemap(), C.c_uint32(0), RtcBloom(), C.c_uint32(0)
+    w, cam = _load_scene("rtc_scene_load_yaml_post", text, path, t, has_t, b, has_b)
+    return w, cam, (t if has_t.value else None), (b if has_b.value else None)
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
@@ -1550,6 +1632,22 @@ class Context:
         _check(lib().rtc_adaptive_mask_device(self._h, C.c_void_p(d_rgb), width, height, mode, float(threshold), C.c_void_p(d_mask)),
                "rtc_adaptive_mask_device")
 
+    def luminance_device(self, d_rgb: int, width: int, height: int, d_out: int) -> None:
+        """rtc.luminance of an f64 canvas in DEVICE memory into the 24 device bytes at `d_out`, enqueued on the context's stream
+        (rtc_canvas_luminance_device): the host function's bytes, no host wait."""
+        _check(lib().rtc_canvas_luminance_device(self._h, C.c_void_p(d_rgb), width, height, C.c_void_p(d_out)), "rtc_canvas_luminance_device")
+
+    def tonemap_device(self, d_in: int, width: int, height: int, spec: RtcTonemap, d_out: int, d_stats: int | None = None) -> None:
+        """rtc.tonemap of a canvas in DEVICE memory into `d_out` (may be `d_in`), enqueued on the context's stream
+        (rtc_canvas_tonemap_device); `d_stats`: the record luminance_device left in device memory, needed with an AUTO flag."""
+        _check(lib().rtc_canvas_tonemap_device(self._h, C.c_void_p(d_in), width, height, C.byref(spec), C.c_void_p(d_stats) if d_stats else None,
+                                               C.c_void_p(d_out)), "rtc_canvas_tonemap_device")
+
+    def bloom_device(self, d_in: int, width: int, height: int, spec: RtcBloom, d_out: int) -> None:
+        """rtc.bloom of a canvas in DEVICE memory into `d_out` (may be `d_in`), enqueued on the context's stream
+        (rtc_canvas_bloom_device)."""
+        _check(lib().rtc_canvas_bloom_device(self._h, C.c_void_p(d_in), width, height, C.byref(spec), C.c_void_p(d_out)), "rtc_canvas_bloom_device")
+
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
         return Shutter(self)
@@ -2218,7 +2316,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "adaptive", "adaptive_offset", "adaptive_mask", "load_yaml_adaptive", "RtcAdaptive", "RtcAdaptiveInfo", "MAX_AA_SAMPLES", "AA_DEFAULT_THRESHOLD", "AA_DEFAULT_STEPS", "AA_DEFAULT_MAX_RAYS", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "tonemap_spec", "bloom_spec", "luminance", "tonemap_resolve", "tonemap", "bloom", "bloom_weights", "load_yaml_post", "RtcLuminance", "RtcTonemap", "RtcBloom", "TONEMAP_LINEAR", "TONEMAP_REINHARD", "TONEMAP_ACES", "TONEMAP_AUTO_EXPOSURE", "TONEMAP_AUTO_WHITE", "MAX_BLOOM_RADIUS", "adaptive", "adaptive_offset", "adaptive_mask", "load_yaml_adaptive", "RtcAdaptive", "RtcAdaptiveInfo", "MAX_AA_SAMPLES", "AA_DEFAULT_THRESHOLD", "AA_DEFAULT_STEPS", "AA_DEFAULT_MAX_RAYS", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
            "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",

@@ -72,6 +72,24 @@ MAX_AA_SAMPLES = 256
 AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS = 0.01, 4, 1 << 21  # RTC_AA_DEFAULT_*
 
 
+class RtcLuminance(C.Structure):
+    _fields_ = [("max", C.c_double), ("sum", C.c_double), ("count", C.c_uint64)]
+
+
+class RtcTonemap(C.Structure):
+    _fields_ = [("exposure", C.c_double), ("white", C.c_double), ("curve", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RtcBloom(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("strength", C.c_double), ("sigma", C.c_double), ("radius", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2  # rtc_tonemap::curve
+TONEMAP_CURVES = {"linear": 0, "reinhard": 1, "aces": 2}
+TONEMAP_AUTO_EXPOSURE, TONEMAP_AUTO_WHITE = 1, 2  # rtc_tonemap::flags
+MAX_BLOOM_RADIUS = 32
+
+
 class RtcGatherBuffers(C.Structure):
     _fields_ = [("radiance", C.c_void_p), ("bounce", C.c_void_p)]
 
@@ -155,6 +173,7 @@ SOURCE_NAMES = {0: "brute force, records through the scalar cache", 1: "brute fo
 assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(RtcHit) == 184
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24 and C.sizeof(RtcProjection) == 32
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
+assert C.sizeof(RtcLuminance) == 24 and C.sizeof(RtcTonemap) == 24 and C.sizeof(RtcBloom) == 32
 assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64 and C.sizeof(RtcAo) == 16 and C.sizeof(RtcGatherBuffers) == 16
 
 D = C.c_double
@@ -431,6 +450,22 @@ PROTOTYPES = {
                                                  C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcAdaptive), C.POINTER(U32)]),
     "rtc_scene_load_yaml_adaptive_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                       C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcAdaptive), C.POINTER(U32)]),
+    "rtc_canvas_luminance": (C.c_int32, [PD, U32, U32, C.POINTER(RtcLuminance)]),
+    "rtc_canvas_luminance_device": (C.c_int32, [VP, VP, U32, U32, VP]),
+    "rtc_tonemap_validate": (C.c_int32, [C.POINTER(RtcTonemap)]),
+    "rtc_tonemap_resolve": (C.c_int32, [C.POINTER(RtcTonemap), C.POINTER(RtcLuminance), PD, PD]),
+    "rtc_canvas_tonemap": (C.c_int32, [PD, U32, U32, C.POINTER(RtcTonemap), C.POINTER(RtcLuminance), PD]),
+    "rtc_canvas_tonemap_device": (C.c_int32, [VP, VP, U32, U32, C.POINTER(RtcTonemap), VP, VP]),
+    "rtc_bloom_validate": (C.c_int32, [C.POINTER(RtcBloom)]),
+    "rtc_bloom_weights": (C.c_int32, [C.POINTER(RtcBloom), PD]),
+    "rtc_canvas_bloom": (C.c_int32, [PD, U32, U32, C.POINTER(RtcBloom), PD]),
+    "rtc_canvas_bloom_device": (C.c_int32, [VP, VP, U32, U32, C.POINTER(RtcBloom), VP]),
+    "rtc_scene_load_yaml_post": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                             C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcTonemap), C.POINTER(U32),
+                                             C.POINTER(RtcBloom), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_post_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                  C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcTonemap), C.POINTER(U32),
+                                                  C.POINTER(RtcBloom), C.POINTER(U32)]),
 }
 
 

@@ -358,6 +358,11 @@ struct Scene {
     int filter_line = 0;                // line of the camera entry that has filter keys, 0: none
     rtc_adaptive adaptive{};            // the camera's adaptive anti-aliasing (include/rtc.h); zeroed without aa keys
     int adaptive_line = 0;              // line of the camera entry that has aa keys, 0: none
+    bool want_post = false;             // the entry asked for the post-processing records: only then are their keys read
+    rtc_tonemap tonemap{};              // the camera's tone map (include/rtc.h); zeroed without tonemap-* keys
+    int tonemap_line = 0;               // line of the camera entry that has tonemap-* keys, 0: none
+    rtc_bloom bloom{};                  // the camera's bloom; zeroed without bloom-* keys
+    int bloom_line = 0;                 // line of the camera entry that has bloom-* keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -527,6 +532,57 @@ void interpret(const Node &root, Scene &sc) {
                 if ((uint64_t)sc.adaptive.usteps * sc.adaptive.vsteps > RTC_MAX_AA_SAMPLES) // with the checks above: every range of rtc_adaptive_validate
                     fail(e.line, "too many anti-aliasing samples: aa-usteps x aa-vsteps is at most " + std::to_string(RTC_MAX_AA_SAMPLES));
             }
+            // exposure, tone mapping and bloom (include/rtc.h): tonemap-* and bloom-*, each with a default; every other entry ignores them
+            sc.tonemap = rtc_tonemap{};
+            sc.bloom = rtc_bloom{};
+            sc.tonemap_line = sc.bloom_line = 0;
+            if (sc.want_post) {
+                const Node *tc = e.get("tonemap-curve"), *te = e.get("tonemap-exposure"), *tk = e.get("tonemap-key"), *tw = e.get("tonemap-white");
+                if (tc || te || tk || tw) {
+                    sc.tonemap_line = e.line;
+                    if (te && tk) fail(tk->line, "tonemap-key sets the exposure from the frame's mean luminance: not together with tonemap-exposure");
+                    sc.tonemap.curve = RTC_TONEMAP_REINHARD;
+                    if (tc) {
+                        if (tc->kind != Node::Scalar) fail(tc->line, "tonemap-curve must be linear, reinhard or aces");
+                        if (tc->scalar == "linear") sc.tonemap.curve = RTC_TONEMAP_LINEAR;
+                        else if (tc->scalar == "reinhard") sc.tonemap.curve = RTC_TONEMAP_REINHARD;
+                        else if (tc->scalar == "aces") sc.tonemap.curve = RTC_TONEMAP_ACES;
+                        else fail(tc->line, "tonemap-curve must be linear, reinhard or aces: " + tc->scalar);
+                    }
+                    sc.tonemap.exposure = tk ? as_number(tk, "tonemap-key") : te ? as_number(te, "tonemap-exposure") : 1.0;
+                    if (tk) sc.tonemap.flags |= RTC_TONEMAP_AUTO_EXPOSURE;
+                    if (!(sc.tonemap.exposure > 0.0 && sc.tonemap.exposure < std::numeric_limits<double>::infinity()))
+                        fail((tk ? tk : te)->line, std::string(tk ? "tonemap-key" : "tonemap-exposure") + " must be a finite number above 0");
+                    sc.tonemap.white = std::numeric_limits<double>::infinity();
+                    if (tw && tw->kind == Node::Scalar && tw->scalar == "auto") {
+                        sc.tonemap.flags |= RTC_TONEMAP_AUTO_WHITE;
+                        sc.tonemap.white = 1.0; // ignored with the flag; any valid value
+                    } else if (tw && !(tw->kind == Node::Scalar && (tw->scalar == ".inf" || tw->scalar == "+.inf"))) {
+                        sc.tonemap.white = as_number(tw, "tonemap-white");
+                        if (!(sc.tonemap.white > 0.0)) fail(tw->line, "tonemap-white must be a number above 0, .inf or auto");
+                    }
+                }
+                const Node *bt = e.get("bloom-threshold"), *bs = e.get("bloom-strength"), *bg = e.get("bloom-sigma"), *br = e.get("bloom-radius");
+                if (bt || bs || bg || br) {
+                    sc.bloom_line = e.line;
+                    sc.bloom.threshold = bt ? as_number(bt, "bloom-threshold") : 1.0;
+                    sc.bloom.strength = bs ? as_number(bs, "bloom-strength") : 0.5;
+                    sc.bloom.sigma = bg ? as_number(bg, "bloom-sigma") : 2.0;
+                    sc.bloom.radius = 6u;
+                    if (br) {
+                        const double v = as_number(br, "bloom-radius");
+                        if (!(v >= 1 && v <= RTC_MAX_BLOOM_RADIUS) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                            fail(br->line, "bloom-radius must be an integer in 1.." + std::to_string(RTC_MAX_BLOOM_RADIUS));
+                        sc.bloom.radius = static_cast<uint32_t>(v);
+                    }
+                    // with the radius above: every range of rtc_bloom_validate (this file links without host_post.cpp)
+                    const double inf = std::numeric_limits<double>::infinity();
+                    if (!(sc.bloom.threshold >= 0.0 && sc.bloom.threshold < inf)) fail((bt ? bt : &e)->line, "bloom-threshold must be a finite number of at least 0");
+                    if (!(sc.bloom.strength >= 0.0 && sc.bloom.strength < inf)) fail((bs ? bs : &e)->line, "bloom-strength must be a finite number of at least 0");
+                    if (!(sc.bloom.sigma > 0.0 && sc.bloom.sigma < inf) || !((2.0 * sc.bloom.sigma) * sc.bloom.sigma > 0.0))
+                        fail((bg ? bg : &e)->line, "bloom-sigma must be a finite number above 0");
+                }
+            }
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
             if (const Node *ss = e.get("shutter-samples")) {
@@ -618,7 +674,9 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
                             rtc_projection *proj_out = nullptr, uint32_t *has_projection_out = nullptr, rtc_ao *ao_out = nullptr,
                             uint32_t *has_ao_out = nullptr, rtc_ao *gather_out = nullptr, uint32_t *has_gather_out = nullptr,
                             rtc_filter *filter_out = nullptr, uint32_t *has_filter_out = nullptr,
-                            rtc_adaptive *adaptive_out = nullptr, uint32_t *has_adaptive_out = nullptr) {
+                            rtc_adaptive *adaptive_out = nullptr, uint32_t *has_adaptive_out = nullptr,
+                            rtc_tonemap *tonemap_out = nullptr, uint32_t *has_tonemap_out = nullptr, rtc_bloom *bloom_out = nullptr,
+                            uint32_t *has_bloom_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
@@ -626,6 +684,7 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
     if ((gather_out == nullptr) != (has_gather_out == nullptr)) return RTC_ERR_ARG;
     if ((filter_out == nullptr) != (has_filter_out == nullptr)) return RTC_ERR_ARG;
     if ((adaptive_out == nullptr) != (has_adaptive_out == nullptr)) return RTC_ERR_ARG;
+    if (!tonemap_out != !has_tonemap_out || !bloom_out != !has_bloom_out || !tonemap_out != !bloom_out) return RTC_ERR_ARG;
     *shapes_out = nullptr;
     *n_out = 0;
     *n_lights_out = 0;
@@ -641,6 +700,7 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         NodeP root = p.parse_block(p.lines[0].indent);
         if (p.pos != p.lines.size()) fail(p.lines[p.pos].number, "unexpected content");
         Scene sc;
+        sc.want_post = tonemap_out != nullptr;
         interpret(*root, sc);
         if (sc.area_line && !area_out) fail(sc.area_line, "the scene has an area light: load it with rtc_scene_load_yaml_area_lights");
         if (sc.lens_line && !lens_out) fail(sc.lens_line, "the scene's camera has a lens: load it with rtc_scene_load_yaml_lens");
@@ -698,6 +758,12 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (adaptive_out) {
             *adaptive_out = sc.adaptive;
             *has_adaptive_out = sc.adaptive_line ? 1u : 0u;
+        }
+        if (tonemap_out) {
+            *tonemap_out = sc.tonemap;
+            *has_tonemap_out = sc.tonemap_line ? 1u : 0u;
+            *bloom_out = sc.bloom;
+            *has_bloom_out = sc.bloom_line ? 1u : 0u;
         }
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -790,6 +856,15 @@ rtc_status rtc_scene_load_yaml_adaptive(const char *text, rtc_shape **shapes_out
     return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                      adaptive_out, has_adaptive_out);
+}
+
+rtc_status rtc_scene_load_yaml_post(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out, uint32_t lights_cap,
+                                    uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, rtc_tonemap *tonemap_out,
+                                    uint32_t *has_tonemap_out, rtc_bloom *bloom_out, uint32_t *has_bloom_out) {
+    if (!tonemap_out || !has_tonemap_out || !bloom_out || !has_bloom_out) return RTC_ERR_ARG;
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, tonemap_out, has_tonemap_out, bloom_out, has_bloom_out);
 }
 
 static rtc_status read_file(const char *path, std::string &text, char *errbuf, size_t errbuf_len) {
@@ -902,6 +977,16 @@ rtc_status rtc_scene_load_yaml_adaptive_file(const char *path, rtc_shape **shape
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_adaptive(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                         adaptive_out, has_adaptive_out);
+}
+
+rtc_status rtc_scene_load_yaml_post_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                         uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                         rtc_tonemap *tonemap_out, uint32_t *has_tonemap_out, rtc_bloom *bloom_out, uint32_t *has_bloom_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_post(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                    tonemap_out, has_tonemap_out, bloom_out, has_bloom_out);
 }
 
 } // extern "C"

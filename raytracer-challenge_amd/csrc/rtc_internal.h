@@ -51,6 +51,9 @@ struct rtc_context {
     DevBuf<double> d_aa_colors;      // ... and their colours, 3 doubles each
     DevBuf<double> d_aa_canvas;      // the frame of rtc_render_adaptive (host-buffer entry point)
     PinnedWord aa_total;             // where the number of flagged pixels lands
+    // Post-processing (rtc_post.cpp; include/rtc.h), grow-only:
+    DevBuf<rtc_luminance> d_post_lum; // the block results of the statistics' levels 0 and 1 (frames of more than 256 pixels)
+    DevBuf<double> d_post_hor;        // the bloom's horizontal pass H: three planes of width*height
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -285,6 +288,23 @@ extern "C" hipError_t rtc_launch_aa_resolve(const uint32_t *list, const double *
 // awaited by its caller, so a later rtc_world_update has to wait for it.
 extern "C" rtc_status rtc_color_at_device(rtc_context *ctx, const rtc_world *w, const double *d_rays, uint32_t n, uint32_t remaining, uint32_t flags,
                                           double *d_rgb, rtc_hit *d_hits, bool record);
+// Post-processing (rtc_post.hip; include/rtc.h). k_lum_pixels / k_lum_records: the statistics of the n pixels of `rgb` into *out
+// (device memory), one launch per level of the tree; `scratch`: room for ceil(n/256) + ceil(ceil(n/256)/256) records when n > 256.
+extern "C" hipError_t rtc_launch_luminance(const double *rgb, size_t n, rtc_luminance *scratch, rtc_luminance *out, hipStream_t stream);
+// k_tonemap: `stats` (device memory) is read only with an AUTO flag; out may be in
+extern "C" hipError_t rtc_launch_tonemap(const double *in, double *out, size_t n, const rtc_tonemap *spec, const rtc_luminance *stats,
+                                         hipStream_t stream);
+// k_bloom_h, then k_bloom_v: `hor` has room for three planes of width*height; w: rtc_bloom_weights; out may be in. grid_x is
+// the launcher's own.
+struct BloomArgs {
+    const double *in;
+    double *out;
+    double *hor;
+    double threshold, strength;
+    double w[2u * RTC_MAX_BLOOM_RADIUS + 1u];
+    uint32_t width, height, radius, grid_x;
+};
+extern "C" hipError_t rtc_launch_bloom(const BloomArgs *a, hipStream_t stream);
 extern "C" rtc_status rtc_shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes, uint32_t samples); // host_math.cpp
 // The device table of `gamma` for work enqueued next on the context's own stream (rtc_api.cpp keeps the per-gamma cache).
 extern "C" rtc_status rtc_gamma_table_on_stream(rtc_context *ctx, float gamma, const DevGamma **out);

@@ -211,6 +211,26 @@ class Canvas { // canvas.rs:16-109
             throw Panic(RTC_ERR_ARG, "Canvas::add_scaled: an f64 Canvas and a plane of its size are needed");
         check(rtc_canvas_add_scaled(pixels.data(), plane.data(), strength, width, height), "Canvas::add_scaled");
     }
+    // The glare of highlights added in place (rtc_canvas_bloom, include/rtc.h): luminance above spec.threshold, blurred by a
+    // separable Gaussian, times spec.strength. f64 canvases only. Not part of the reference's Canvas.
+    void bloom(const rtc_bloom &spec) {
+        if (pixels.size() != static_cast<size_t>(width) * height * 3) throw Panic(RTC_ERR_ARG, "Canvas::bloom: an f64 Canvas is needed");
+        check(rtc_canvas_bloom(pixels.data(), width, height, &spec, pixels.data()), "Canvas::bloom");
+    }
+    // Exposure and a tone curve in place (rtc_canvas_tonemap): what comes before to_rgba8 or a file writer when the frame is
+    // brighter than 1.0. With an AUTO flag in `spec` the Canvas takes its own statistics first (rtc_canvas_luminance).
+    void tonemap(const rtc_tonemap &spec) {
+        if (pixels.size() != static_cast<size_t>(width) * height * 3) throw Panic(RTC_ERR_ARG, "Canvas::tonemap: an f64 Canvas is needed");
+        rtc_luminance stats{};
+        if (spec.flags != 0u) check(rtc_canvas_luminance(pixels.data(), width, height, &stats), "Canvas::tonemap");
+        check(rtc_canvas_tonemap(pixels.data(), width, height, &spec, spec.flags != 0u ? &stats : nullptr, pixels.data()), "Canvas::tonemap");
+    }
+    rtc_luminance luminance() const { // the frame statistics (rtc_canvas_luminance)
+        if (pixels.size() != static_cast<size_t>(width) * height * 3) throw Panic(RTC_ERR_ARG, "Canvas::luminance: an f64 Canvas is needed");
+        rtc_luminance stats{};
+        check(rtc_canvas_luminance(pixels.data(), width, height, &stats), "Canvas::luminance");
+        return stats;
+    }
     void write_to_file_simple(const std::string &file_name) const { // canvas.rs:86-109
         if (is_imgbuf()) { // the PPM is Color::scale's (gamma 1): only an RGBA frame of gamma 1 holds those bytes
             if (rgba8_gamma != 1.0f) throw Panic(RTC_ERR_ARG, "Canvas::write_to_file_simple: the Canvas holds RGBA at gamma != 1 (Camera::render_rgba8)");

@@ -1,7 +1,7 @@
 """Register / scratch / LDS use of every k_trace, k_aov, k_ao and k_gather instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
 With --filter: of the edge-aware filter's kernels (csrc/rtc_filter.hip) instead; with --adaptive: of the adaptive anti-aliasing
-kernels (csrc/rtc_adaptive.hip).
-usage: python tools/kernel_resources.py [--filter | --adaptive] [extra -D flags]"""
+kernels (csrc/rtc_adaptive.hip); with --post: of the post-processing kernels (csrc/rtc_post.hip).
+usage: python tools/kernel_resources.py [--filter | --adaptive | --post] [extra -D flags]"""
 import importlib.util
 import re
 import subprocess
@@ -18,7 +18,8 @@ spec.loader.exec_module(build)
 
 FILTER = "--filter" in sys.argv[1:]
 ADAPTIVE = "--adaptive" in sys.argv[1:]
-EXTRA = [a for a in sys.argv[1:] if a not in ("--filter", "--adaptive")]
+POST = "--post" in sys.argv[1:]
+EXTRA = [a for a in sys.argv[1:] if a not in ("--filter", "--adaptive", "--post")]
 
 
 def remarks(name):  # one kernel unit's remarks
@@ -29,11 +30,11 @@ def remarks(name):  # one kernel unit's remarks
 
 with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
     t = "".join(pool.map(remarks, build.FILTER_KERNEL_SOURCES if FILTER else [n for n in build.ADAPTIVE_SOURCES if n.endswith(".hip")] if ADAPTIVE
-                         else build.KERNEL_SOURCES))
+                         else [n for n in build.POST_SOURCES if n.endswith(".hip")] if POST else build.KERNEL_SOURCES))
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
-    if FILTER or ADAPTIVE:
+    if FILTER or ADAPTIVE or POST:
         pass
     elif "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name and "k_gather" not in name and "k_add_scaled" not in name:
         continue
@@ -68,6 +69,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     elif "k_apply_occlusion" in name:
         tag = "k_apply_occlusion"
     elif (a := re.search(r"(k_aa_[a-z]+)", name)):  # the adaptive anti-aliasing kernels
+        tag = a.group(1)
+    elif (a := re.search(r"(k_lum_[a-z]+|k_tonemap|k_bloom_[hv])", name)):  # the post-processing kernels
         tag = a.group(1)
     else:
         tag = name[:44]
