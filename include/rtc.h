@@ -1899,6 +1899,86 @@ rtc_status  rtc_scene_load_yaml_post_file(const char *path, rtc_shape **shapes_o
                                           rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
                                           rtc_tonemap *tonemap_out, uint32_t *has_tonemap_out, rtc_bloom *bloom_out, uint32_t *has_bloom_out);
 
+/* ==== resizing f64 canvases: five filters, a host statement, the same bytes on the device ============= */
+/* A frame traced at 2x or 3x and filtered down is anti-aliasing for every launch family that has none of its own
+ * (orthographic and panorama frames, the lens, AOV views, AO and gather planes); a small plane filtered up can be composited
+ * over a full-size frame. The resize sits between rtc_canvas_bloom / rtc_canvas_tonemap and rtc_canvas_to_rgba8 or an encoder.
+ * Frames are linear: there is no gamma-aware resize, no 8-bit resize and no resize of uint16 count planes (convert those with
+ * rtc_counts_to_fraction first).
+ *
+ * Arithmetic: f64 throughout, no fused multiply-add, the operations in exactly the order written here.
+ *
+ * The filters k(x), each 0.0 outside its radius R; a = fabs(x):
+ *   BOX          R = 0.5  1.0 when x > -0.5 && x <= 0.5
+ *   TRIANGLE     R = 1    a < 1: 1.0 - a
+ *   CATMULL_ROM  R = 2    a < 1: ((((1.5*a) - 2.5)*a)*a) + 1.0;  a < 2: (((((-0.5*a) + 2.5)*a) - 4.0)*a) + 2.0
+ *   MITCHELL     R = 2    (B = C = 1/3) a < 1: (((((7.0*a) - 12.0)*a)*a) + (16.0/3.0)) / 6.0;
+ *                         a < 2: (((((((-7.0/3.0)*a) + 12.0)*a) - 20.0)*a) + (32.0/3.0)) / 6.0
+ *   LANCZOS3     R = 3    x == 0: 1.0;  a < 3: p = 3.141592653589793*x, q = p/3.0, (sin(p)/p) * (sin(q)/q)
+ *
+ * The table of one axis, n_in -> n_out (what Pillow does: taps outside the image are dropped, the rest renormalised):
+ *   scale = (double)n_in / (double)n_out;  fs = scale > 1.0 ? scale : 1.0;  support = R*fs.
+ *   For output o: c = ((double)o + 0.5)*scale;
+ *     first = max(0, floor((c - support) + 0.5));  end = min(n_in, floor((c + support) + 0.5));  count = end - first.
+ *     raw[j] = k(((((double)(first + j)) + 0.5) - c) / fs) for j = 0 .. count-1;
+ *     sum adds the raw[j] in j order, starting at 0.0;  w[j] = raw[j] / sum.
+ * An axis with n_in == n_out is NOT filtered, whatever the filter (Mitchell, which does not interpolate, included): its
+ * table is first = o, count = 1, w = 1.0 and its pass copies the values' bytes. A resize to the same size returns the input.
+ *
+ * The frame: the horizontal pass first, w_in x h_in -> w_out x h_in, then the vertical pass -> w_out x h_out; the order is
+ * fixed. One output channel of a filtered pass is acc = 0.0; for j = 0 .. count-1 in order: acc = acc + (w[j] * v[first + j]);
+ * a NaN result is stored as 0x7FF8000000000000. A NaN or an infinity of the input reaches exactly the outputs whose taps
+ * cover it on both axes (0.0 * inf is NaN, and is kept). */
+enum { RTC_RESIZE_BOX = 0, RTC_RESIZE_TRIANGLE = 1, RTC_RESIZE_CATMULL_ROM = 2, RTC_RESIZE_MITCHELL = 3, RTC_RESIZE_LANCZOS3 = 4 };
+/* An axis may have at most this many taps per output (a condition, not a tuning value): one output's source span is then at
+ * most 24 KiB of pixels, which fits a workgroup's LDS even when the workgroup handles a single output column. */
+#define RTC_MAX_RESIZE_TAPS 1024u
+typedef struct rtc_resize {
+    uint32_t filter;           /* RTC_RESIZE_* */
+    uint32_t _pad;             /* 0 */
+} rtc_resize;                  /* 8 bytes */
+/* [host] RTC_ERR_ARG for NULL, an unknown filter or _pad != 0; else RTC_OK. */
+rtc_status  rtc_resize_validate(const rtc_resize *spec);
+/* [host] the largest count of the axis n_in -> n_out under `filter` (1 when n_in == n_out); 0 for a zero size or an unknown
+ * filter. The value may exceed RTC_MAX_RESIZE_TAPS: such an axis is refused by the entries below. */
+uint32_t    rtc_resize_taps(uint32_t n_in, uint32_t n_out, uint32_t filter);
+/* [host] the normative table of one axis: first[o], count[o] and w[o*taps + j] for o < n_out, taps = rtc_resize_taps(n_in,
+ * n_out, filter), each row of w zero-padded past count[o]. RTC_ERR_ARG: a NULL pointer, a zero size, an invalid spec, more
+ * than RTC_MAX_RESIZE_TAPS taps. RTC_ERR_NOMEM: no room for the raw weights of one output. */
+rtc_status  rtc_resize_weights(uint32_t n_in, uint32_t n_out, const rtc_resize *spec, uint32_t *first, uint32_t *count, double *w);
+/* [host] the normative resize of `in` (w_in*h_in*3 doubles, row-major) into `out` (w_out*h_out*3 doubles). RTC_ERR_ARG, with
+ * `out` untouched: a NULL pointer, a zero size, an invalid spec, an axis of more than RTC_MAX_RESIZE_TAPS taps, `out`
+ * overlapping `in`. RTC_ERR_NOMEM: no room for the tables or the intermediate w_out x h_in frame. */
+rtc_status  rtc_canvas_resize(const double *in, uint32_t w_in, uint32_t h_in, const rtc_resize *spec, double *out, uint32_t w_out,
+                              uint32_t h_out);
+/* [device] the same bytes for canvases in DEVICE memory, enqueued on the context's stream (csrc/rtc_resize.hip: k_resize_h,
+ * then k_resize_v; an unchanged axis has no pass, and a resize to the same size is k_resize_copy). Nothing on the device
+ * evaluates a filter: the tables of an axis are built on the host by rtc_resize_weights' own function, uploaded to a
+ * grow-only device buffer and cached by the context for the last four (n_in, n_out, filter) triples. A call whose tables are
+ * cached does not wait for the stream and uploads nothing; a MISS WAITS FOR THE CONTEXT'S STREAM before it replaces the
+ * least recently used tables, as a new panorama size does. The intermediate frame is a grow-only plane of the context.
+ * d_in and d_out 8-byte aligned and not overlapping, else RTC_ERR_ARG; the host entry's refusals hold too, and a pass whose
+ * grid would reach 2^32 threads (2^24 - 1 workgroups of 256) is RTC_ERR_ARG. Nothing is launched by a refused call. */
+rtc_status  rtc_canvas_resize_device(rtc_context *ctx, const void *d_in, uint32_t w_in, uint32_t h_in, const rtc_resize *spec,
+                                     void *d_out, uint32_t w_out, uint32_t h_out);
+/* Scenes whose camera asks for a delivered size other than the traced one. YAML: `add: camera` with any of
+ *   output-width, output-height (integers, 1 .. 2^31-1; an absent one keeps the frame's aspect: out_h = max(1,
+ *   floor(((double)out_w * (double)height) / (double)width + 0.5)), and alike for out_w),
+ *   output-filter (box | triangle | catmull-rom | mitchell | lanczos3; default lanczos3).
+ * These entries are rtc_scene_load_yaml_projection plus the record: *has_resize_out = 1, *resize_out, *out_w and *out_h
+ * filled when the camera has any output-* key; else 0, the record zeroed and *out_w, *out_h the camera's own size. A value
+ * outside the ranges, or output-filter alone, is RTC_ERR_PARSE with a message. Every other YAML entry ignores the keys. */
+rtc_status  rtc_scene_load_yaml_resize(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                       struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                       rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                       rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out, uint32_t *has_proj_out,
+                                       rtc_resize *resize_out, uint32_t *out_w, uint32_t *out_h, uint32_t *has_resize_out);
+rtc_status  rtc_scene_load_yaml_resize_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                            struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                            rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                            rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out, uint32_t *has_proj_out,
+                                            rtc_resize *resize_out, uint32_t *out_w, uint32_t *out_h, uint32_t *has_resize_out);
+
 #ifdef __cplusplus
 }
 #endif

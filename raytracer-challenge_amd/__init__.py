@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcAdaptive, RtcAdaptiveInfo, MAX_AA_SAMPLES, AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS, RtcLuminance, RtcTonemap, RtcBloom, TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES, TONEMAP_CURVES, TONEMAP_AUTO_EXPOSURE, TONEMAP_AUTO_WHITE, MAX_BLOOM_RADIUS, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
+from .abi import (LUA_FRAME_FN, LUA_GIF_FN, LUA_FILE_FN, LUA_OUT_RGB8, LUA_OUT_GIF_RECORD, LUA_OUT_JPEG, LUA_OUT_PNG, LUA_OUT_FILE, IMAGE_FORMATS, IMAGE_JPEG_QUALITY, TIFF_STRIP_BYTES, PNG_SEGMENT, PNG_CHAIN, GIF_SEGMENT, GIF_DELAY_CS, RtcLuaJob, RtcCamera, RtcHit, RtcLaunchInfo, RtcLight, RtcAreaLight, RtcLens, RtcAo, MAX_AO_SAMPLES, RtcGatherBuffers, RtcAdaptive, RtcAdaptiveInfo, MAX_AA_SAMPLES, AA_DEFAULT_THRESHOLD, AA_DEFAULT_STEPS, AA_DEFAULT_MAX_RAYS, RtcLuminance, RtcTonemap, RtcBloom, TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES, TONEMAP_CURVES, TONEMAP_AUTO_EXPOSURE, TONEMAP_AUTO_WHITE, MAX_BLOOM_RADIUS, RtcResize, RESIZE_BOX, RESIZE_TRIANGLE, RESIZE_CATMULL_ROM, RESIZE_MITCHELL, RESIZE_LANCZOS3, RESIZE_FILTERS, MAX_RESIZE_TAPS, RtcFilter, FILTER_SAME_OBJECT, MAX_FILTER_PASSES, FILTER_DEFAULT_PLANE_SIGMA, FILTER_DEFAULT_PASSES, FILTER_DEFAULT_NORMAL_SQUARINGS, RtcProjection, PROJ_ORTHOGRAPHIC, PROJ_PANORAMA, RtcMotion, RtcShutterScene, RtcMaterial, RtcShape, RtcStats, Mat16, Vec3, SOURCE_NAMES,
                   SPHERE, PLANE, CUBE, MODE_RENDER, MODE_RENDER_ASYNC, FLAG_NONE, FLAG_NO_CULL, FLAG_AA_RESAMPLE, FLAG_LDS_TABLE,
                   EXCHANGE_RCCL, EXCHANGE_P2P, GATHER_NONE, GATHER_F64, GATHER_U8, GROUP_ID_BYTES, MAX_LIGHTS, MAX_LIGHT_SAMPLES, MAX_LENS_SAMPLES, MAX_SHUTTER_SAMPLES, SHUTTER_RING, PATTERNS, STATUS_NAMES, declare,
                   RtcAovBuffers, AOV_PLANES, AOV_VIEWS, AOV_VIEW_DEPTH, AOV_VIEW_NORMAL, AOV_VIEW_INDEX, AOV_VIEW_SHADOW,
@@ -556,6 +556,39 @@ def bloom(rgb: np.ndarray, spec: RtcBloom) -> np.ndarray:
     return out
 
 
+def resize_spec(filter="lanczos3") -> RtcResize:
+    """A record for rtc.resize / Context.resize_device (rtc_resize, include/rtc.h). `filter`: "box", "triangle", "catmull-rom",
+    "mitchell", "lanczos3" or a RESIZE_* value."""
+    r = RtcResize()
+    r.filter = RESIZE_FILTERS[filter] if isinstance(filter, str) else int(filter)
+    _check(lib().rtc_resize_validate(C.byref(r)), "rtc_resize_validate")
+    return r
+
+
+def resize_weights(n_in: int, n_out: int, spec: RtcResize) -> tuple:
+    """rtc_resize_weights: (first, count, w), the normative table of the axis n_in -> n_out: two uint32 arrays of n_out and an
+    (n_out, rtc_resize_taps) f64 array, each row zero-padded past its count."""
+    taps = lib().rtc_resize_taps(n_in, n_out, spec.filter)
+    if taps == 0:
+        raise RtcError(4, "rtc_resize_taps")
+    first, count = np.zeros(n_out, dtype=np.uint32), np.zeros(n_out, dtype=np.uint32)
+    w = np.zeros((n_out, taps), dtype=np.float64)
+    _check(lib().rtc_resize_weights(n_in, n_out, C.byref(spec), first.ctypes.data_as(C.POINTER(C.c_uint32)), count.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    w.ctypes.data_as(C.POINTER(C.c_double))), "rtc_resize_weights")
+    return first, count, w
+
+
+def resize(rgb: np.ndarray, width: int, height: int, spec: RtcResize | None = None) -> np.ndarray:
+    """rtc_canvas_resize: an (H, W, 3) f64 canvas filtered to (height, width, 3): the horizontal pass first, an unchanged axis
+    copied. `spec`: resize_spec(); LANCZOS3 when none is given."""
+    c = _canvas_arg(rgb, "resize")
+    out = np.empty((int(height), int(width), 3), dtype=np.float64)
+    spec = resize_spec() if spec is None else spec
+    _check(lib().rtc_canvas_resize(c.ctypes.data_as(C.POINTER(C.c_double)), c.shape[1], c.shape[0], C.byref(spec),
+                                   out.ctypes.data_as(C.POINTER(C.c_double)), int(width), int(height)), "rtc_canvas_resize")
+    return out
+
+
 def _adaptive_info_dict(info: RtcAdaptiveInfo) -> dict:
     return {"pixels_refined": int(info.pixels_refined), "rays_refined": int(info.rays_refined), "launches": int(info.launches)}
 
@@ -726,6 +759,16 @@ def load_yaml_post(text: str | None = None, path: str | None = None):
     t, has_t, b, has_b = RtcTonemap(), C.c_uint32(0), RtcBloom(), C.c_uint32(0)
     w, cam = _load_scene("rtc_scene_load_yaml_post", text, path, t, has_t, b, has_b)
     return w, cam, (t if has_t.value else None), (b if has_b.value else None)
+
+
+def load_yaml_resize(text: str | None = None, path: str | None = None):
+    """load_yaml_projection for scenes whose camera may ask for a delivered size (output-width / output-height / output-filter):
+    -> (World, RtcCamera, RtcLens or None, RtcProjection or None, RtcResize or None, out_width, out_height); without the keys
+    the size is the camera's own."""
+    ln, has, pj, has_pj = RtcLens(), C.c_uint32(0), RtcProjection(), C.c_uint32(0)
+    rs, ow, oh, has_rs = RtcResize(), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    w, cam = _load_scene("rtc_scene_load_yaml_resize", text, path, ln, has, pj, has_pj, rs, ow, oh, has_rs)
+    return w, cam, (ln if has.value else None), (pj if has_pj.value else None), (rs if has_rs.value else None), ow.value, oh.value
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
@@ -1648,6 +1691,12 @@ class Context:
         (rtc_canvas_bloom_device)."""
         _check(lib().rtc_canvas_bloom_device(self._h, C.c_void_p(d_in), width, height, C.byref(spec), C.c_void_p(d_out)), "rtc_canvas_bloom_device")
 
+    def resize_device(self, d_in: int, w_in: int, h_in: int, spec: RtcResize, d_out: int, w_out: int, h_out: int) -> None:
+        """rtc.resize of a canvas in DEVICE memory into `d_out` (w_out * h_out * 3 doubles, not overlapping `d_in`), enqueued on
+        the context's stream (rtc_canvas_resize_device). A new (n_in, n_out, filter) axis waits for the stream once, to upload its table."""
+        _check(lib().rtc_canvas_resize_device(self._h, C.c_void_p(d_in), w_in, h_in, C.byref(spec), C.c_void_p(d_out), w_out, h_out),
+               "rtc_canvas_resize_device")
+
     def shutter(self) -> "Shutter":
         """A motion-blur renderer bound to this context (rtc_shutter): Shutter.render and its 8-bit / device forms."""
         return Shutter(self)
@@ -2316,7 +2365,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
     return out
 
 
-__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "tonemap_spec", "bloom_spec", "luminance", "tonemap_resolve", "tonemap", "bloom", "bloom_weights", "load_yaml_post", "RtcLuminance", "RtcTonemap", "RtcBloom", "TONEMAP_LINEAR", "TONEMAP_REINHARD", "TONEMAP_ACES", "TONEMAP_AUTO_EXPOSURE", "TONEMAP_AUTO_WHITE", "MAX_BLOOM_RADIUS", "adaptive", "adaptive_offset", "adaptive_mask", "load_yaml_adaptive", "RtcAdaptive", "RtcAdaptiveInfo", "MAX_AA_SAMPLES", "AA_DEFAULT_THRESHOLD", "AA_DEFAULT_STEPS", "AA_DEFAULT_MAX_RAYS", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
+__all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "tonemap_spec", "bloom_spec", "luminance", "tonemap_resolve", "tonemap", "bloom", "bloom_weights", "load_yaml_post", "resize_spec", "resize_weights", "resize", "load_yaml_resize", "RtcResize", "RESIZE_BOX", "RESIZE_TRIANGLE", "RESIZE_CATMULL_ROM", "RESIZE_MITCHELL", "RESIZE_LANCZOS3", "MAX_RESIZE_TAPS", "RtcLuminance", "RtcTonemap", "RtcBloom", "TONEMAP_LINEAR", "TONEMAP_REINHARD", "TONEMAP_ACES", "TONEMAP_AUTO_EXPOSURE", "TONEMAP_AUTO_WHITE", "MAX_BLOOM_RADIUS", "adaptive", "adaptive_offset", "adaptive_mask", "load_yaml_adaptive", "RtcAdaptive", "RtcAdaptiveInfo", "MAX_AA_SAMPLES", "AA_DEFAULT_THRESHOLD", "AA_DEFAULT_STEPS", "AA_DEFAULT_MAX_RAYS", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
            "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",

@@ -90,6 +90,15 @@ TONEMAP_AUTO_EXPOSURE, TONEMAP_AUTO_WHITE = 1, 2  # rtc_tonemap::flags
 MAX_BLOOM_RADIUS = 32
 
 
+class RtcResize(C.Structure):
+    _fields_ = [("filter", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+RESIZE_BOX, RESIZE_TRIANGLE, RESIZE_CATMULL_ROM, RESIZE_MITCHELL, RESIZE_LANCZOS3 = range(5)  # rtc_resize::filter
+RESIZE_FILTERS = {"box": 0, "triangle": 1, "catmull-rom": 2, "mitchell": 3, "lanczos3": 4}
+MAX_RESIZE_TAPS = 1024
+
+
 class RtcGatherBuffers(C.Structure):
     _fields_ = [("radiance", C.c_void_p), ("bounce", C.c_void_p)]
 
@@ -174,6 +183,7 @@ assert C.sizeof(RtcMaterial) == 264 and C.sizeof(RtcShape) == 528 and C.sizeof(R
 assert C.sizeof(RtcAreaLight) == 104 and C.sizeof(RtcLaunchInfo) == 48 and C.sizeof(RtcLens) == 24 and C.sizeof(RtcProjection) == 32
 assert C.sizeof(RtcMotion) == 264 and C.sizeof(RtcShutterScene) == 80
 assert C.sizeof(RtcLuminance) == 24 and C.sizeof(RtcTonemap) == 24 and C.sizeof(RtcBloom) == 32
+assert C.sizeof(RtcResize) == 8
 assert C.sizeof(RtcAovBuffers) == 48 and C.sizeof(RtcFloatPlanes) == 64 and C.sizeof(RtcAo) == 16 and C.sizeof(RtcGatherBuffers) == 16
 
 D = C.c_double
@@ -466,6 +476,17 @@ PROTOTYPES = {
     "rtc_scene_load_yaml_post_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcTonemap), C.POINTER(U32),
                                                   C.POINTER(RtcBloom), C.POINTER(U32)]),
+    "rtc_resize_validate": (C.c_int32, [C.POINTER(RtcResize)]),
+    "rtc_resize_taps": (U32, [U32, U32, U32]),
+    "rtc_resize_weights": (C.c_int32, [U32, U32, C.POINTER(RtcResize), C.POINTER(U32), C.POINTER(U32), PD]),
+    "rtc_canvas_resize": (C.c_int32, [PD, U32, U32, C.POINTER(RtcResize), PD, U32, U32]),
+    "rtc_canvas_resize_device": (C.c_int32, [VP, VP, U32, U32, C.POINTER(RtcResize), VP, U32, U32]),
+    "rtc_scene_load_yaml_resize": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                               C.POINTER(RtcProjection), C.POINTER(U32), C.POINTER(RtcResize), C.POINTER(U32), C.POINTER(U32), C.POINTER(U32)]),
+    "rtc_scene_load_yaml_resize_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
+                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
+                                                    C.POINTER(RtcProjection), C.POINTER(U32), C.POINTER(RtcResize), C.POINTER(U32), C.POINTER(U32), C.POINTER(U32)]),
 }
 
 

@@ -25,7 +25,8 @@ KERNEL_SOURCES = ["rtc_kernels.hip"]
 FILTER_KERNEL_SOURCES = ["rtc_filter.hip"]  # the edge-aware filter's kernels: tools/kernel_resources.py --filter
 ADAPTIVE_SOURCES = ["host_adaptive.cpp", "rtc_adaptive.cpp", "rtc_adaptive.hip"]  # edge-adaptive anti-aliasing: tools/kernel_resources.py --adaptive
 POST_SOURCES = ["host_post.cpp", "rtc_post.cpp", "rtc_post.hip"]  # exposure, tone mapping and bloom: tools/kernel_resources.py --post
-SOURCES = KERNEL_SOURCES + ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_launch_plan.cpp", "rtc_group.cpp", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp", "host_ao.cpp", "host_gather.cpp", "host_float.cpp", "rtc_float.hip", "host_filter.cpp", "rtc_filter.cpp", "rtc_filter.hip"] + ADAPTIVE_SOURCES + POST_SOURCES
+RESIZE_SOURCES = ["host_resize.cpp", "rtc_resize.cpp", "rtc_resize.hip"]  # resizing f64 canvases: tools/kernel_resources.py --resize
+SOURCES = KERNEL_SOURCES + ["host_math.cpp", "host_ppm.cpp", "host_yaml.cpp", "host_lua.cpp", "rtc_api.cpp", "rtc_launch_plan.cpp", "rtc_group.cpp", "rtc_world_build.hip", "host_gif.cpp", "rtc_gif.hip", "host_jpeg.cpp", "rtc_jpeg.hip", "host_png.cpp", "rtc_png.hip", "host_image.cpp", "rtc_image.hip", "rtc_encode.cpp", "rtc_lua_render.cpp", "rtc_shutter.cpp", "rtc_shutter.hip", "host_aov.cpp", "host_ao.cpp", "host_gather.cpp", "host_float.cpp", "rtc_float.hip", "host_filter.cpp", "rtc_filter.cpp", "rtc_filter.hip"] + ADAPTIVE_SOURCES + POST_SOURCES + RESIZE_SOURCES
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 COMMON += os.environ.get("RTC_CXXFLAGS", "").split()  # experiments, e.g. -DRTC_WAVES_PER_SIMD=4
 # Kernel file only: MachineLICM hoists the VGPR materialisation of every f64 literal (pow's ~25
@@ -109,7 +110,7 @@ def _build_facade(name: str, force: bool = False) -> Path:
     return exe
 
 
-# the thirteen programs, each callable as f(force=False) -> Path
+# the fourteen programs, each callable as f(force=False) -> Path
 build_facade_tests = partial(_build_facade, "test_facade")  # the C++ mirror of the reference API
 build_facade_update_test = partial(_build_facade, "test_facade_update")  # the resident World updated in place
 build_facade_area_light_test = partial(_build_facade, "test_facade_area_light")  # World::add_area_light
@@ -123,6 +124,7 @@ build_facade_gather_test = partial(_build_facade, "test_facade_gather")  # Camer
 build_facade_filter_test = partial(_build_facade, "test_facade_filter")  # Aov::filter and Canvas::apply_occlusion
 build_facade_adaptive_test = partial(_build_facade, "test_facade_adaptive")  # Camera::set_adaptive
 build_facade_post_test = partial(_build_facade, "test_facade_post")  # Canvas::bloom and Canvas::tonemap
+build_facade_resize_test = partial(_build_facade, "test_facade_resize")  # Canvas::resized
 
 
 if __name__ == "__main__":

@@ -363,6 +363,10 @@ struct Scene {
     int tonemap_line = 0;               // line of the camera entry that has tonemap-* keys, 0: none
     rtc_bloom bloom{};                  // the camera's bloom; zeroed without bloom-* keys
     int bloom_line = 0;                 // line of the camera entry that has bloom-* keys, 0: none
+    bool want_resize = false;           // the entry asked for the delivered size: only then are the output-* keys read
+    rtc_resize resize{};                // the camera's output filter (include/rtc.h); zeroed without output-* keys
+    uint32_t out_w = 0, out_h = 0;      // the delivered size; the camera's own without output-* keys
+    int resize_line = 0;                // line of the camera entry that has output-* keys, 0: none
     std::vector<rtc_motion> motions;    // every shape with a `motion:` key, in file order
     uint32_t shutter_samples = 1;       // the camera's `shutter-samples`
     int motion_line = 0;                // line of the first entry with a motion-blur key (motion / shutter-samples), 0: none
@@ -583,6 +587,41 @@ void interpret(const Node &root, Scene &sc) {
                         fail((bg ? bg : &e)->line, "bloom-sigma must be a finite number above 0");
                 }
             }
+            // the delivered size (include/rtc.h): output-width / output-height / output-filter; every other entry ignores them
+            sc.resize = rtc_resize{};
+            sc.out_w = sc.camera.hsize;
+            sc.out_h = sc.camera.vsize;
+            sc.resize_line = 0;
+            if (sc.want_resize) {
+                const Node *ow = e.get("output-width"), *oh = e.get("output-height"), *of = e.get("output-filter");
+                if (ow || oh || of) {
+                    sc.resize_line = e.line;
+                    if (!ow && !oh) fail(of->line, "output-filter needs output-width or output-height");
+                    auto size = [&](const Node *n, const char *key) {
+                        const double v = as_number(n, key);
+                        if (!(v >= 1 && v <= 2147483647.0) || v != static_cast<double>(static_cast<uint32_t>(v))) // (NaN fails the first test)
+                            fail(n->line, std::string(key) + " must be an integer in 1..2147483647");
+                        return static_cast<uint32_t>(v);
+                    };
+                    // an absent side keeps the frame's aspect, rounded to nearest, at least 1
+                    auto aspect = [](uint32_t given, uint32_t other_in, uint32_t given_in) {
+                        const double v = std::floor((static_cast<double>(given) * static_cast<double>(other_in)) / static_cast<double>(given_in) + 0.5);
+                        return v < 1.0 ? 1u : v > 2147483647.0 ? 2147483647u : static_cast<uint32_t>(v);
+                    };
+                    if (ow) sc.out_w = size(ow, "output-width");
+                    if (oh) sc.out_h = size(oh, "output-height");
+                    if (!oh) sc.out_h = aspect(sc.out_w, sc.camera.vsize, sc.camera.hsize);
+                    if (!ow) sc.out_w = aspect(sc.out_h, sc.camera.hsize, sc.camera.vsize);
+                    sc.resize.filter = RTC_RESIZE_LANCZOS3;
+                    if (of) {
+                        static const char *const names[] = {"box", "triangle", "catmull-rom", "mitchell", "lanczos3"};
+                        uint32_t f = 0;
+                        while (f < 5u && (of->kind != Node::Scalar || of->scalar != names[f])) ++f;
+                        if (f == 5u) fail(of->line, "output-filter must be box, triangle, catmull-rom, mitchell or lanczos3");
+                        sc.resize.filter = f;
+                    }
+                }
+            }
             // motion blur (include/rtc.h): shutter-samples
             sc.shutter_samples = 1u;
             if (const Node *ss = e.get("shutter-samples")) {
@@ -665,6 +704,12 @@ void set_err(char *errbuf, size_t len, const std::string &msg) {
 extern "C" {
 
 // first_only: the single-light entries' form — lights_out receives lights[1] alone, however many the scene has.
+// What rtc_scene_load_yaml_resize adds to its neighbours' outputs.
+struct ResizeOut {
+    rtc_resize *resize;
+    uint32_t *out_w, *out_h, *has;
+};
+
 // Exactly one of lights_out (point lights; a scene with an area light is a parse error) and area_out (every light as an
 // rtc_area_light) is given.
 static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out, uint32_t lights_cap,
@@ -676,7 +721,7 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
                             rtc_filter *filter_out = nullptr, uint32_t *has_filter_out = nullptr,
                             rtc_adaptive *adaptive_out = nullptr, uint32_t *has_adaptive_out = nullptr,
                             rtc_tonemap *tonemap_out = nullptr, uint32_t *has_tonemap_out = nullptr, rtc_bloom *bloom_out = nullptr,
-                            uint32_t *has_bloom_out = nullptr) {
+                            uint32_t *has_bloom_out = nullptr, const ResizeOut *resize_out = nullptr) {
     if (!text || !shapes_out || !n_out || (!lights_out && !area_out) || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
     if ((lens_out == nullptr) != (has_lens_out == nullptr)) return RTC_ERR_ARG;
     if ((proj_out == nullptr) != (has_projection_out == nullptr)) return RTC_ERR_ARG;
@@ -701,6 +746,7 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
         if (p.pos != p.lines.size()) fail(p.lines[p.pos].number, "unexpected content");
         Scene sc;
         sc.want_post = tonemap_out != nullptr;
+        sc.want_resize = resize_out != nullptr;
         interpret(*root, sc);
         if (sc.area_line && !area_out) fail(sc.area_line, "the scene has an area light: load it with rtc_scene_load_yaml_area_lights");
         if (sc.lens_line && !lens_out) fail(sc.lens_line, "the scene's camera has a lens: load it with rtc_scene_load_yaml_lens");
@@ -764,6 +810,12 @@ static rtc_status load_yaml(const char *text, rtc_shape **shapes_out, uint32_t *
             *has_tonemap_out = sc.tonemap_line ? 1u : 0u;
             *bloom_out = sc.bloom;
             *has_bloom_out = sc.bloom_line ? 1u : 0u;
+        }
+        if (resize_out) {
+            *resize_out->resize = sc.resize;
+            *resize_out->out_w = sc.have_camera ? sc.out_w : sc.camera.hsize;
+            *resize_out->out_h = sc.have_camera ? sc.out_h : sc.camera.vsize;
+            *resize_out->has = sc.resize_line ? 1u : 0u;
         }
         return RTC_OK;
     } catch (const ParseError &e) {
@@ -977,6 +1029,29 @@ rtc_status rtc_scene_load_yaml_adaptive_file(const char *path, rtc_shape **shape
     if (st != RTC_OK) return st;
     return rtc_scene_load_yaml_adaptive(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
                                         adaptive_out, has_adaptive_out);
+}
+
+rtc_status rtc_scene_load_yaml_resize(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out, uint32_t lights_cap,
+                                      uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, rtc_lens *lens_out,
+                                      uint32_t *has_lens_out, rtc_projection *proj_out, uint32_t *has_proj_out, rtc_resize *resize_out,
+                                      uint32_t *out_w, uint32_t *out_h, uint32_t *has_resize_out) {
+    if (!lens_out || !has_lens_out || !proj_out || !has_proj_out || !resize_out || !out_w || !out_h || !has_resize_out) return RTC_ERR_ARG;
+    const ResizeOut ro{resize_out, out_w, out_h, has_resize_out};
+    return load_yaml(text, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len, false, lights_out,
+                     lens_out, has_lens_out, nullptr, nullptr, nullptr, proj_out, has_proj_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ro);
+}
+
+rtc_status rtc_scene_load_yaml_resize_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                           size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out,
+                                           uint32_t *has_proj_out, rtc_resize *resize_out, uint32_t *out_w, uint32_t *out_h,
+                                           uint32_t *has_resize_out) {
+    std::string text;
+    const rtc_status st = read_file(path, text, errbuf, errbuf_len);
+    if (st != RTC_OK) return st;
+    return rtc_scene_load_yaml_resize(text.c_str(), shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, errbuf, errbuf_len,
+                                      lens_out, has_lens_out, proj_out, has_proj_out, resize_out, out_w, out_h, has_resize_out);
 }
 
 rtc_status rtc_scene_load_yaml_post_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,

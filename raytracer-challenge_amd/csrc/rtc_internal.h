@@ -54,6 +54,20 @@ struct rtc_context {
     // Post-processing (rtc_post.cpp; include/rtc.h), grow-only:
     DevBuf<rtc_luminance> d_post_lum; // the block results of the statistics' levels 0 and 1 (frames of more than 256 pixels)
     DevBuf<double> d_post_hor;        // the bloom's horizontal pass H: three planes of width*height
+    // Resizing (rtc_resize.cpp; include/rtc.h), grow-only. A slot holds the device table of one axis: n_out records {first,
+    // count} (two uint32 in the room of a double), then n_out rows of `taps` weights. A slot is rewritten only on a miss,
+    // behind a wait for the stream; `used` orders the slots for replacement (the smallest is the least recently used).
+    static constexpr uint32_t RESIZE_SLOTS = 4;
+    struct ResizeSlot {
+        bool valid = false;
+        uint32_t n_in = 0, n_out = 0, filter = 0, taps = 0;
+        unsigned long long used = 0;
+        DevBuf<double> table;
+    };
+    ResizeSlot resize_slot[RESIZE_SLOTS];
+    unsigned long long resize_clock = 0;   // the `used` stamp of the most recent call
+    unsigned long long resize_uploads = 0; // tables uploaded so far (rtc_debug_resize_uploads)
+    DevBuf<double> d_resize_mid;           // the intermediate w_out x h_in frame of a resize that changes both axes
     int force_src = -1;   // RTC_SRC env override (experiments)
     uint32_t tiles_per_wg = 1; // tiles one workgroup renders in sequence (RTC_TILES_PER_WG)
     uint32_t tiles_guided_tenths = 20; // guided chunks: tiles per chunk level in tenths of the resident workgroups (RTC_TILES_GUIDED; 0 = off)
@@ -305,6 +319,21 @@ struct BloomArgs {
     uint32_t width, height, radius, grid_x;
 };
 extern "C" hipError_t rtc_launch_bloom(const BloomArgs *a, hipStream_t stream);
+// Resizing (rtc_resize.hip; include/rtc.h). fc: n_out records {first, count}; w: n_out rows of `taps` weights; the geometry
+// (taps .. grid_x) is filled by the launchers from the pass's plan (rtc_resize.h). k_resize_h: w_in x h_in -> w_out x h_in;
+// k_resize_v: w_out x (the axis's n_in rows) -> w_out x h_out.
+struct ResizeArgs {
+    const double *in;
+    double *out;
+    const uint2 *fc;
+    const double *w;
+    uint32_t w_in, h_in, w_out, h_out;
+    uint32_t taps, seg, rows, pitch, grid_x;
+};
+struct ResizePassPlan;
+extern "C" hipError_t rtc_launch_resize_h(const ResizeArgs *a, const ResizePassPlan *p, hipStream_t stream);
+extern "C" hipError_t rtc_launch_resize_v(const ResizeArgs *a, const ResizePassPlan *p, hipStream_t stream);
+extern "C" hipError_t rtc_launch_resize_copy(const double *in, double *out, size_t n, hipStream_t stream); // n: values
 extern "C" rtc_status rtc_shutter_check_motions(const rtc_motion *motions, uint32_t n_motions, uint32_t n_shapes, uint32_t samples); // host_math.cpp
 // The device table of `gamma` for work enqueued next on the context's own stream (rtc_api.cpp keeps the per-gamma cache).
 extern "C" rtc_status rtc_gamma_table_on_stream(rtc_context *ctx, float gamma, const DevGamma **out);

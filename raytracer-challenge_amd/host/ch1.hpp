@@ -231,6 +231,16 @@ class Canvas { // canvas.rs:16-109
         check(rtc_canvas_luminance(pixels.data(), width, height, &stats), "Canvas::luminance");
         return stats;
     }
+    // A copy of this Canvas filtered to w x h (rtc_canvas_resize, include/rtc.h): the horizontal pass first, an axis whose size
+    // does not change copied. What turns a frame traced at 2x or 3x into an anti-aliased one, and a small plane into one that
+    // can be composited over a full-size frame. f64 canvases only. Not part of the reference's Canvas.
+    Canvas resized(uint32_t w, uint32_t h, const rtc_resize &spec) const {
+        if (pixels.empty() || pixels.size() != static_cast<size_t>(width) * height * 3) throw Panic(RTC_ERR_ARG, "Canvas::resized: an f64 Canvas is needed");
+        Canvas out(w, h);
+        out.gamma = gamma;
+        check(rtc_canvas_resize(pixels.data(), width, height, &spec, out.pixels.data(), w, h), "Canvas::resized");
+        return out;
+    }
     void write_to_file_simple(const std::string &file_name) const { // canvas.rs:86-109
         if (is_imgbuf()) { // the PPM is Color::scale's (gamma 1): only an RGBA frame of gamma 1 holds those bytes
             if (rgba8_gamma != 1.0f) throw Panic(RTC_ERR_ARG, "Canvas::write_to_file_simple: the Canvas holds RGBA at gamma != 1 (Camera::render_rgba8)");

@@ -1,7 +1,8 @@
 """Register / scratch / LDS use of every k_trace, k_aov, k_ao and k_gather instantiation (hipcc -Rpass-analysis=kernel-resource-usage); CPU only.
 With --filter: of the edge-aware filter's kernels (csrc/rtc_filter.hip) instead; with --adaptive: of the adaptive anti-aliasing
-kernels (csrc/rtc_adaptive.hip); with --post: of the post-processing kernels (csrc/rtc_post.hip).
-usage: python tools/kernel_resources.py [--filter | --adaptive | --post] [extra -D flags]"""
+kernels (csrc/rtc_adaptive.hip); with --post: of the post-processing kernels (csrc/rtc_post.hip); with --resize: of the resize
+kernels (csrc/rtc_resize.hip; k_resize_h's LDS is dynamic, at most RTC_RESIZE_LDS_BUDGET, and is not in the remark).
+usage: python tools/kernel_resources.py [--filter | --adaptive | --post | --resize] [extra -D flags]"""
 import importlib.util
 import re
 import subprocess
@@ -19,7 +20,8 @@ spec.loader.exec_module(build)
 FILTER = "--filter" in sys.argv[1:]
 ADAPTIVE = "--adaptive" in sys.argv[1:]
 POST = "--post" in sys.argv[1:]
-EXTRA = [a for a in sys.argv[1:] if a not in ("--filter", "--adaptive", "--post")]
+RESIZE = "--resize" in sys.argv[1:]
+EXTRA = [a for a in sys.argv[1:] if a not in ("--filter", "--adaptive", "--post", "--resize")]
 
 
 def remarks(name):  # one kernel unit's remarks
@@ -30,11 +32,12 @@ def remarks(name):  # one kernel unit's remarks
 
 with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
     t = "".join(pool.map(remarks, build.FILTER_KERNEL_SOURCES if FILTER else [n for n in build.ADAPTIVE_SOURCES if n.endswith(".hip")] if ADAPTIVE
-                         else [n for n in build.POST_SOURCES if n.endswith(".hip")] if POST else build.KERNEL_SOURCES))
+                         else [n for n in build.POST_SOURCES if n.endswith(".hip")] if POST
+                         else [n for n in build.RESIZE_SOURCES if n.endswith(".hip")] if RESIZE else build.KERNEL_SOURCES))
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
-    if FILTER or ADAPTIVE or POST:
+    if FILTER or ADAPTIVE or POST or RESIZE:
         pass
     elif "k_trace" not in name and "undeal" not in name and "k_aov" not in name and "k_ao" not in name and "k_apply_ao" not in name and "k_gather" not in name and "k_add_scaled" not in name:
         continue
@@ -71,6 +74,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     elif (a := re.search(r"(k_aa_[a-z]+)", name)):  # the adaptive anti-aliasing kernels
         tag = a.group(1)
     elif (a := re.search(r"(k_lum_[a-z]+|k_tonemap|k_bloom_[hv])", name)):  # the post-processing kernels
+        tag = a.group(1)
+    elif (a := re.search(r"(k_resize_[a-z]+)", name)):  # the resize kernels
         tag = a.group(1)
     else:
         tag = name[:44]
