@@ -937,6 +937,38 @@ template <bool WAVE_NORM = false> DEVI V3 shape_normal(const DevShade *S, const 
     }
     return vnormalize_plain(xvector3(S->nt, ln));
 }
+// The same function for a caller that already holds the object's kind (trace_short_chains' SC_KIND: nothing waits for
+// DevShade::kind's load) and, GROUPED, with the two records a sphere's or a cube's normal reads — rows 0..2 of the inverse and
+// DevShade::nt, both at addresses the hit index alone decides — requested together, ahead of the arithmetic (SC_NORMAL). The
+// operations and their operands are shape_normal's.
+template <bool WAVE_NORM, bool GROUPED> DEVI V3 shape_normal_of(uint32_t kind, const DevShade *S, const double *m_obj, V3 point) {
+    if (kind == RTC_PLANE) return mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]);
+    double mi[12], nt[9];
+    if constexpr (GROUPED) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) mi[i] = m_obj[i];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) nt[i] = S->nt[i];
+    }
+    V3 ln = mk(0., 1., 0.);
+    if (kind == RTC_SPHERE) {
+        const V3 lp = GROUPED ? xpoint(mi, point) : xpoint(m_obj, point);
+        ln = mk(lp.x - 0., lp.y - 0., lp.z - 0.);
+    } else if (kind == RTC_CUBE) {
+        const V3 lp = GROUPED ? xpoint(mi, point) : xpoint(m_obj, point);
+        const double ax = fabs(lp.x), ay = fabs(lp.y), az = fabs(lp.z);
+        const double maxc = fmax(ax, fmax(ay, az));
+        if (maxc == ax) ln = mk(lp.x, 0., 0.);
+        else if (maxc == ay) ln = mk(0., lp.y, 0.);
+        else ln = mk(0., 0., lp.z);
+    }
+    const V3 wn = GROUPED ? xvector3(nt, ln) : xvector3(S->nt, ln);
+    if constexpr (WAVE_NORM) {
+        double mag;
+        return vnormalize_wave(wn, mag);
+    }
+    return vnormalize_plain(wn);
+}
 
 // The shadow ray of is_shadowed_by_light (shape.rs:717-719): v = light - over_point, its length, three divisions. Lanes
 // without a hit keep the `dir` and `dist` they came with. WAVE_NORM: through vnormalize_wave (the flat k_trace kernels), same bits.
@@ -1130,6 +1162,26 @@ constexpr bool trace_scalar_walk(int src, bool refl, bool one, int lights) {
 #endif
 constexpr bool trace_wave_normalize(int site, int src, bool refl, bool probe, bool alt, bool multi) {
     return (RTC_SHARED_NORMALIZE_FLAT & site) != 0 && IS_CULL(src) && !refl && !probe && !alt && !multi;
+}
+// Shorter chains of dependent loads per tile in the flat one-sample k_trace kernels: loads are moved, merged or requested
+// together, no arithmetic changes. A mask of items, 0 = the code as it was in every kernel (kept for the A/B):
+//   1  the tile header's two tile_rows words through scalar loads (const_words), not a per-lane load + readfirstlane
+//   2  the tile lookup in the tile header: the kernel arguments it needs in one group, then tile_rows' words, the tile's
+//      count and its list's first entry in one more
+//   4  unbounded objects of the binned primary pass: orig_s[k], kind_s[k] and isect_s[k] requested together
+//   8  the packed tile-list walks: kind[j], isect[j] and prim[j] requested together, ahead of the kind switch
+//  16  the hit object's kind carried per lane beside hidx (binned pass) instead of DevShade::kind's load before the normal
+//  32  sphere and cube normal: isect[hidx].m and DevShade::nt requested together
+//  64  the shadow-list stage's kernel arguments in one group
+// 128  a lane's own light cell: its counter and the first batch of its list requested together
+// trace_short_chains: the instantiations that take an item — the one-sample render flavour of SRC_CULL without a frame stack,
+// one light (with WHOLE and without). Every other kernel is the parent's code (tools/isa_compare.py; profiles/short_chains_*).
+#ifndef RTC_SHORT_CHAINS
+#define RTC_SHORT_CHAINS 255
+#endif
+enum { SC_ROWS = 1, SC_LOOKUP = 2, SC_UNBOUNDED = 4, SC_WALK = 8, SC_KIND = 16, SC_NORMAL = 32, SC_SHADOW_ARGS = 64, SC_CELL = 128 };
+constexpr bool trace_short_chains(int item, int src, bool refl, bool one, bool multi) {
+    return (RTC_SHORT_CHAINS & item) != 0 && src == SRC_CULL && !refl && one && !multi;
 }
 
 // One suspended shade_hit call (shape.rs:685-700) on a lane's stack. The stack lives in scratch
@@ -1343,11 +1395,23 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     // separately, rtc_stats::rays_primary_proven_miss). One-sample renders only. Such a tile goes from here to the output
     // stage: it skips the sample loop with its camera loads, and stores its zeros through the same code as every other tile.
     bool sky_tile = false;
-    if constexpr (IS_CULL(SRC) && !PROBE && !ALT) { // (the proof is for rays from the camera origin)
+    // trace_short_chains' SC_LOOKUP: the proof's words come with the tile's list, further down (tile_header)
+    constexpr bool HEADER_LOOKUP = trace_short_chains(SC_LOOKUP, SRC, REFL, ONE, MULTI);
+    // SC_KIND: the binned pass keeps the kind of each lane's closest object beside hidx — it holds every tested object's kind
+    // in an SGPR — and the normal starts from that instead of waiting for DevShade::kind, which the host fills from the same
+    // rtc_shape::kind as kind[] and kind_s[] (flatten_shapes, for rtc_world_create and rtc_world_update alike). The walks
+    // that are not the binned pass (no lists, an overflowing list) read DevShade::kind as before.
+    constexpr bool CARRY_KIND = trace_short_chains(SC_KIND, SRC, REFL, ONE, MULTI);
+    if constexpr (IS_CULL(SRC) && !PROBE && !ALT && !HEADER_LOOKUP) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
         if (Pt.tile_rows != nullptr && (ONE || Pt.samples == 1u)) {
             const uint32_t ity = (Pt.y0 >> 3) + by * (WHOLE ? 1u : Pt.band_stride);
-            const uint32_t first = Pt.tile_rows[2u * view], lastinv = Pt.tile_rows[2u * view + 1u];
+            uint32_t first, lastinv;
+            if constexpr (trace_short_chains(SC_ROWS, SRC, REFL, ONE, MULTI)) { // k_bin_tiles wrote them, the view is wave-uniform: scalar loads
+                first = const_words(Pt.tile_rows)[2u * view], lastinv = const_words(Pt.tile_rows)[2u * view + 1u];
+            } else {
+                first = Pt.tile_rows[2u * view], lastinv = Pt.tile_rows[2u * view + 1u];
+            }
             sky_tile = ity < first || ity > ~lastinv; // (no tile of the view is non-empty: first = 0xffffffff)
         }
         if (sky_tile) { // counted as cast (the reference casts them), answered by the proof
@@ -1388,6 +1452,45 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             }
         }
     };
+    // HEADER_LOOKUP: the black-row test and tile_lookup in one place, two scalar round trips per tile. First the kernel
+    // arguments both read, one group; then — both addresses are known from those — the view's two tile_rows words and
+    // the tile's count and first list entry, one more. Every pointer is tested before anything is read through it, as above;
+    // a one-sample pinhole launch looks its tile up in its only pass, so nothing is asked for that the pass would not ask
+    // for, except by the tiles proven black (their tile is a tile of the same tables: in bounds).
+    if constexpr (HEADER_LOOKUP) {
+        static_assert(SCALAR_WALK, "the header lookup is the scalar walk's");
+        const auto &Pt = KP(P_arg);
+        unsigned long long q_cnt = (unsigned long long)Pt.tile_cnt, q_list = (unsigned long long)Pt.tile_list, q_rows = (unsigned long long)Pt.tile_rows;
+        uint32_t a_tiles_x = Pt.tiles_x, a_tiles_y = WHOLE ? 0u : Pt.tiles_y;
+        const uint32_t a_y0 = P.y0; // (the set-up view's, with its grid_x: the tile's decomposition above reads both)
+        // (the empty statement takes and returns its operands in SGPRs: every load above has been asked for, and is waited
+        // for once, before one of the values is looked at; left to itself the compiler asks for each where it is first used)
+        asm volatile("" : "+s"(q_cnt), "+s"(q_list), "+s"(q_rows), "+s"(a_tiles_x), "+s"(a_tiles_y) : "s"(a_y0), "s"(P.grid_x));
+        const ConstWords a_cnt = (ConstWords)q_cnt, a_list = (ConstWords)q_list, a_rows = (ConstWords)q_rows;
+        const uint32_t ity = (a_y0 >> 3) + by * (WHOLE ? 1u : Pt.band_stride);
+        uint32_t first = 0u, lastinv = 0u; // (no proof: no row is below 0 or above 0xffffffff)
+        bool looked_up = false;
+        if (a_rows != nullptr) first = a_rows[2u * view], lastinv = a_rows[2u * view + 1u];
+        if (a_cnt != nullptr) {
+            const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave); // wave-uniform by construction
+            const uint32_t itx = bx * (TILE_W / 8u) + wv;
+            if (WHOLE || (itx < a_tiles_x && ity < a_tiles_y)) { // (WHOLE: every tile of the launch is a tile of the image)
+                const size_t tile = (size_t)((WHOLE ? 0u : view * a_tiles_y) + ity) * a_tiles_x + itx;
+                bin_list = a_list + tile * RTC_TILE_LIST_CAP;
+                bin_cnt = a_cnt[tile];
+                bin_head = bin_list[0];
+                looked_up = true;
+            }
+        }
+        asm volatile("" : "+s"(first), "+s"(lastinv), "+s"(bin_cnt), "+s"(bin_head)); // the four words: one wait
+        binned = looked_up && bin_cnt <= RTC_TILE_LIST_CAP; // an overflowing list is incomplete: walk instead
+        sky_tile = ity < first || ity > ~lastinv; // (no tile of the view is non-empty: first = 0xffffffff)
+        if (sky_tile) { // counted as cast (the reference casts them), answered by the proof
+            const uint32_t cast = WHOLE ? 64u : popc64(ballot(traced));
+            c_primary += cast;
+            c_sky += cast;
+        }
+    }
 
     // render_pixel (camera.rs:94-114): one ray, or the 4 fixed sub-samples followed — for the pixels whose
     // samples differ by more than 0.01 from their mean — by `resample_n` more rays (Camera::resample)
@@ -1515,7 +1618,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             int hidx = -1, hroot = 0;
             Bundle B{}; // every field defined: an undefined field turns into a value carried around the pass loop
             B.off = true;
-            if constexpr (IS_CULL(SRC) && !PROBE && !ALT) {
+            if constexpr (IS_CULL(SRC) && !PROBE && !ALT && !HEADER_LOOKUP) { // (HEADER_LOOKUP: looked up with the tile's header)
                 if (shared_origin && first) tile_lookup();
             }
             const bool use_bins = !ALT && binned && shared_origin && first; // (binned is false in the probe and brute-force variants)
@@ -1543,10 +1646,54 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 // fewer per sphere test than transforming the origin again (closest_world)
                 auto binned_test = [&](uint32_t kind, const double *m, uint32_t j) {
                     closest_prim(kind, m, reinterpret_cast<const double *>(vprim + j), rd, (int)j, best, hidx, hroot);
+                    // CARRY_KIND: object j is a lane's closest hit exactly when hidx names it after its test; its kind goes above
+                    // the root bit of hroot (0 or 1, and read by the refractive kernels only): no further value beside hidx
+                    if constexpr (CARRY_KIND) {
+                        if (hidx == (int)j) hroot = (hroot & 1) | (int)(kind << 1);
+                    }
                 };
+                // trace_short_chains' SC_WALK / SC_UNBOUNDED: the kind, the record and the DevPrim row of object j (record
+                // and kind at `recs` / `kinds`) as values, requested together ahead of the kind switch — which otherwise
+                // stands between the kind's load and the others'. A plane's test reads one row of them.
+                // `j_loaded`: j itself comes from a load (orig_s[k]) that is still under way — then it, the kind and the record
+                // are one group and the DevPrim row, whose address needs j, a second one.
+                auto binned_test_grouped = [&](auto kinds, const DevIsect *recs, uint32_t at, uint32_t j, bool j_loaded) {
+                    uint32_t kd = kinds[at];
+                    DevIsect rec = recs[at];
+                    // (all of it in SGPRs here: asked for together, one wait — see the tile header)
+                    if (j_loaded)
+                        asm volatile("" : "+s"(j), "+s"(kd), "+s"(rec.m[0]), "+s"(rec.m[1]), "+s"(rec.m[2]), "+s"(rec.m[4]), "+s"(rec.m[5]),
+                                     "+s"(rec.m[6]), "+s"(rec.m[8]), "+s"(rec.m[9]), "+s"(rec.m[10]));
+                    DevPrim pr = vprim[j];
+                    if (j_loaded)
+                        asm volatile("" : "+s"(pr.ox), "+s"(pr.oy), "+s"(pr.oz), "+s"(pr.c));
+                    else
+                        asm volatile("" : "+s"(kd), "+s"(rec.m[0]), "+s"(rec.m[1]), "+s"(rec.m[2]), "+s"(rec.m[4]), "+s"(rec.m[5]), "+s"(rec.m[6]),
+                                     "+s"(rec.m[8]), "+s"(rec.m[9]), "+s"(rec.m[10]), "+s"(pr.ox), "+s"(pr.oy), "+s"(pr.oz), "+s"(pr.c));
+                    const double prv[4] = {pr.ox, pr.oy, pr.oz, pr.c};
+                    closest_prim(kd, rec.m, prv, rd, (int)j, best, hidx, hroot);
+                    if constexpr (CARRY_KIND) {
+                        if (hidx == (int)j) hroot = (hroot & 1) | (int)(kd << 1);
+                    }
+                };
+                // ... and what the two loops below read of the kernel arguments — their bounds and the one table pointer that is
+                // not in registers yet — asked for here, together (operands of an empty statement: in SGPRs at this point).
+                // kind_s is then read through const_words' address space, as the tile lists are: written when the World was
+                // built, never by k_trace (a pointer that has been such an operand reads through scalar loads only from there).
+                if constexpr (trace_short_chains(SC_UNBOUNDED, SRC, REFL, ONE, MULTI)) {
+                    unsigned long long q_kind_s = (unsigned long long)T.kind_s;
+                    asm volatile("" : "+s"(q_kind_s) : "s"(Pb.n_unb), "s"(Pb.bin_packed));
+                    for (uint32_t k = 0; k < Pb.n_unb; ++k) {
+                        const uint32_t jo = T.orig_s[k];
+                        if (tracing) binned_test_grouped((ConstWords)q_kind_s, T.isect_s, k, jo, true);
+                    }
+                } else {
+                if constexpr (trace_short_chains(SC_WALK, SRC, REFL, ONE, MULTI))
+                    asm volatile("" ::"s"(Pb.n_unb), "s"(Pb.bin_packed));
                 for (uint32_t k = 0; k < Pb.n_unb; ++k) {
                     const uint32_t jo = T.orig_s[k];
                     if (tracing) binned_test(T.kind_s[k], T.isect_s[k].m, jo);
+                }
                 }
                 // the tile's list, nearest first: lane e holds entry e and the lower bound of the distance from the camera to
                 // its (inflated) bounding sphere — every intersection of that object has t >= key for these unit-direction
@@ -1567,7 +1714,11 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         const float kmin = __builtin_bit_cast(float, e & 0xffff0000u);
                         if (ballot(tracing && !(best < (double)kmin)) == 0ull) break;
                         const uint32_t j = e & 0xffffu;
-                        if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
+                        if constexpr (trace_short_chains(SC_WALK, SRC, REFL, ONE, MULTI)) {
+                            if (tracing) binned_test_grouped(T.kind, T.isect, j, j, false);
+                        } else {
+                            if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
+                        }
                     }
                 } else if (Pb.bin_packed) {
                     // the same walk over lists in any order: lane e holds entry e, the wave's minimum IS the next object and
@@ -1583,7 +1734,11 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         if (ballot(tracing && !(best < (double)kmin)) == 0ull) break;
                         if (ent == e) ent = 0xffffffffu;
                         const uint32_t j = e & 0xffffu;
-                        if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
+                        if constexpr (trace_short_chains(SC_WALK, SRC, REFL, ONE, MULTI)) {
+                            if (tracing) binned_test_grouped(T.kind, T.isect, j, j, false);
+                        } else {
+                            if (tracing) binned_test(T.kind[j], T.isect[j].m, j);
+                        }
                     }
                 } else { // more than 65 536 objects: plain indices, keys from the bounds
                     uint32_t my_j = 0u;
@@ -1624,7 +1779,12 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             if (hit) {
                 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
                 eyev = vneg(rd);
-                normal = shape_normal<trace_wave_normalize(4, SRC, REFL, PROBE, ALT, MULTI)>(S, m_obj, point);
+                if constexpr (CARRY_KIND || trace_short_chains(SC_NORMAL, SRC, REFL, ONE, MULTI)) {
+                    const uint32_t nkind = (CARRY_KIND && use_bins) ? (uint32_t)hroot >> 1 : S->kind; // (use_bins is wave-uniform)
+                    normal = shape_normal_of<trace_wave_normalize(4, SRC, REFL, PROBE, ALT, MULTI), trace_short_chains(SC_NORMAL, SRC, REFL, ONE, MULTI)>(nkind, S, m_obj, point);
+                } else {
+                    normal = shape_normal<trace_wave_normalize(4, SRC, REFL, PROBE, ALT, MULTI)>(S, m_obj, point);
+                }
                 inside = vdot(normal, eyev) < 0.0;
                 if (inside) normal = vneg(normal);
                 over = vadd(point, vmul(normal, RTC_EPSILON));
@@ -1716,7 +1876,29 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             // test of a survivor is wave-level, its record fetched by uniform index.
             bool listed = false;
             if constexpr (SRC == SRC_CULL) {
-                const auto &Pl = KP(P_arg);
+                // trace_short_chains' SC_SHADOW_ARGS: what this stage reads of the kernel arguments as one group of loads under
+                // one wait, held in SGPRs, instead of one load and one wait per term of the condition below and per loop
+                // bound (the pointers are still tested before anything is read through them)
+                struct ShadowArgs {
+                    const uint32_t *light_cnt, *light_list;
+                    uint32_t light_cap, n_unb;
+                    double light_reach, pre_limit;
+                };
+                auto shadow_args = [&]() -> decltype(auto) {
+                    if constexpr (trace_short_chains(SC_SHADOW_ARGS, SRC, REFL, ONE, MULTI)) {
+                        const auto &Pa = KP(P_arg);
+                        unsigned long long p0 = (unsigned long long)Pa.light_cnt, p1 = (unsigned long long)Pa.light_list;
+                        unsigned long long d0 = __builtin_bit_cast(unsigned long long, Pa.light_reach), d1 = __builtin_bit_cast(unsigned long long, Pa.pre_limit);
+                        uint32_t u0 = Pa.light_cap, u1 = Pa.n_unb;
+                        asm volatile("" : "+s"(p0), "+s"(p1), "+s"(u0), "+s"(u1), "+s"(d0), "+s"(d1)); // all of them, here
+                        typedef const __attribute__((address_space(1))) uint32_t *GlobalWords; // (global memory, as every kernel argument's)
+                        return ShadowArgs{(const uint32_t *)(GlobalWords)p0, (const uint32_t *)(GlobalWords)p1, u0, u1, __builtin_bit_cast(double, d0), __builtin_bit_cast(double, d1)};
+                    } else {
+                        return (KP(P_arg)); // the parameter block itself: each field loaded where it is read
+                    }
+                };
+                const auto &Pl = shadow_args();
+                constexpr bool CELL_TOGETHER = trace_short_chains(SC_CELL, SRC, REFL, ONE, MULTI);
                 // (light_cap == RTC_LIGHT_LIST_CAP_SMALL: a one-level World's own lists; a larger World only gets here with the
                 // one-level cull FORCED, RTC_SRC=3 — its 128-entry lists feed a filter step — and takes the bundle walk)
                 if (Pl.light_cnt != nullptr && Pl.light_cap == RTC_LIGHT_LIST_CAP_SMALL && ballot(hit) != 0ull && ballot(hit && !(sdist <= Pl.light_reach)) == 0ull) {
@@ -1724,6 +1906,17 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     static_assert((LB == 1u || LB == 2u || LB == 4u) && RTC_LIGHT_LIST_CAP_SMALL % LB == 0u, "a batch of entries is one aligned vector load");
                     const uint32_t cid = hit ? light_cell(vneg(sdir)) : 0u;
                     const uint32_t ccnt = hit ? Pl.light_cnt[cid] : 0u; // every lane its own cell's counter: one round trip
+                    // SC_CELL: the first batch of the lane's own list with the counter — both addresses come from cid alone, and
+                    // a cell's CAP slots exist whatever its count; the batch is masked by the count where it is used, as every batch
+                    uint32_t ent0[LB] = {};
+                    if constexpr (CELL_TOGETHER) {
+                        const uint32_t *l0 = Pl.light_list + (size_t)cid * RTC_LIGHT_LIST_CAP_SMALL;
+                        if (hit) {
+                            if constexpr (LB == 4u) { const uint4 v = *reinterpret_cast<const uint4 *>(l0); ent0[0] = v.x; ent0[1] = v.y; ent0[2] = v.z; ent0[3] = v.w; }
+                            else if constexpr (LB == 2u) { const uint2 v = *reinterpret_cast<const uint2 *>(l0); ent0[0] = v.x; ent0[1] = v.y; }
+                            else ent0[0] = l0[0];
+                        }
+                    }
                     listed = ballot(ccnt > Pl.light_cap) == 0ull;      // a cell whose list overflowed is incomplete: fall back
                     if (listed) {
                         for (uint32_t k = 0; k < Pl.n_unb && ballot(sh_pending) != 0ull; ++k) { // unbounded objects: never listed
@@ -1746,6 +1939,10 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         const uint32_t *mylist = Pl.light_list + (size_t)cid * RTC_LIGHT_LIST_CAP_SMALL;
                         for (uint32_t k0 = 0; ballot(sh_pending && k0 < ccnt) != 0ull; k0 += LB) {
                             uint32_t ent[LB]; // (all lanes load: k0 + LB <= the cap, no branch around the loads; entries past the counter are masked)
+                            if (CELL_TOGETHER && k0 == 0u) { // (wave-uniform) the batch that came with the counter
+#pragma unroll
+                                for (uint32_t b = 0; b < LB; ++b) ent[b] = ent0[b];
+                            } else
                             if constexpr (LB == 4u) { const uint4 v = *reinterpret_cast<const uint4 *>(mylist + k0); ent[0] = v.x; ent[1] = v.y; ent[2] = v.z; ent[3] = v.w; }
                             else if constexpr (LB == 2u) { const uint2 v = *reinterpret_cast<const uint2 *>(mylist + k0); ent[0] = v.x; ent[1] = v.y; }
                             else ent[0] = mylist[k0];
