@@ -1287,7 +1287,9 @@ rtc_status  rtc_color_at(rtc_context *ctx, const rtc_world *w, const double *ray
  * of the division expansion (rtc_kernels.hip vnormalize_shared; an experiment, must equal 6 bit for bit). op 7: the
  * patterns' even test (csrc/rtc_parity.h), 1.0 where fmod(a, 2) == 0 and 0.0 elsewhere, decided without fmod.
  * op 8: Vector::normalize as 5 / 6, in the form the flat render kernels run (rtc_kernels.hip vnormalize_wave: the
- * shared-divisor form or the three divisions, chosen per wave of 64 consecutive triples); must equal 6 bit for bit. */
+ * shared-divisor form or the three divisions, chosen per wave of 64 consecutive triples); must equal 6 bit for bit.
+ * op 9: sqrt as the flat render kernels call it (rtc_kernels.hip sqrt_wave: the expansion's bare core or plain sqrt,
+ * chosen per wave of 64 consecutive values); must equal 0 bit for bit. */
 rtc_status  rtc_device_arith(rtc_context *ctx, uint32_t op, const double *a, const double *b,
                              uint32_t n, double *out);
 

@@ -94,6 +94,77 @@ DEVI V3 vnormalize_plain(V3 a) {
     const double mag = sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
     return mk(a.x / mag, a.y / mag, a.z / mag);
 }
+// sqrt(x) (f64) without the part of hipcc's expansion that an ordinary operand does not need. The expansion is 21 VALU
+// instructions: a compare of x against 2^-767 and v_ldexp_f64 of x by 256 where it is below (so that v_rsq_f64 never sees a
+// denormal); the root itself — v_rsq_f64, two multiplies, seven fmas, the sequence of sqrt_bare below —; v_ldexp_f64 of the
+// root by -128 where x was scaled; and a v_cmp_class_f64 select that hands x itself back where it is +-0 or +inf. With the
+// selects and the constants' moves that is eleven instructions around a ten-instruction core.
+// The guard, on x's upper word: sign clear and biased exponent in [256, 2047), one subtraction and one unsigned compare. x is
+// then finite, positive, normal and at least 2^-767 (field 256 = 1023 - 767); +-0 and denormals (field 0), negative numbers
+// and -0 (sign bit: the difference wraps far above the bound), +inf and NaN (field 2047) fail. For such an x
+//   * the compare against 2^-767 is false, so both v_ldexp_f64 shift by 0: the identity on any finite number;
+//   * x is neither +-0 nor +inf, so the class select keeps the root;
+// and the core alone gives the expansion's bits. sqrt_wave chooses per WAVE, as vnormalize_wave below does: the guard is
+// evaluated per lane and balloted over the active lanes; the wave runs the bare core when no active lane fails it and plain
+// sqrt(x), in one cold block, otherwise. Both give the same bits in every lane that passes, so which one a wave takes cannot
+// change a result and nothing is blended (tests/test_gpu_bare_sqrt.py: rtc_device_arith op 9 vs op 0 vs the host).
+constexpr bool sqrt_bare_ok(uint32_t hi) { return hi - (256u << 20) < ((2047u - 256u) << 20); }
+constexpr uint32_t f64_hi(double x) { return (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32); }
+static_assert(sqrt_bare_ok(f64_hi(0x1p-767)), "2^-767 passes");
+static_assert(!sqrt_bare_ok(f64_hi(0x1.fffffffffffffp-768)), "the double below 2^-767 fails");
+static_assert(sqrt_bare_ok(f64_hi(0x1.fffffffffffffp1023)), "DBL_MAX passes");
+static_assert(!sqrt_bare_ok(f64_hi(__builtin_inf())) && !sqrt_bare_ok(f64_hi(__builtin_nan(""))), "+inf and NaN fail");
+static_assert(!sqrt_bare_ok(f64_hi(0.0)) && !sqrt_bare_ok(f64_hi(-0.0)) && !sqrt_bare_ok(f64_hi(-1.0)), "+0, -0 and -1.0 fail");
+static_assert(!sqrt_bare_ok(f64_hi(0x1p-1022 / 2)), "DBL_MIN / 2 (a denormal) fails");
+DEVI double sqrt_bare(double x) { // the expansion's core, for an x that passes sqrt_bare_ok
+    const double y = __builtin_amdgcn_rsq(x);
+    const double g0 = x * y;
+    const double h0 = 0.5 * y;
+    const double r0 = __builtin_fma(-h0, g0, 0.5);
+    const double g1 = __builtin_fma(g0, r0, g0);
+    const double h1 = __builtin_fma(h0, r0, h0);
+    const double d0 = __builtin_fma(-g1, g1, x);
+    const double g2 = __builtin_fma(d0, h1, g1);
+    const double d1 = __builtin_fma(-g2, g2, x);
+    return __builtin_fma(d1, h1, g2);
+}
+DEVI double sqrt_wave(double x) {
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!sqrt_bare_ok(f64_hi(x))) == 0ull, 1)) return sqrt_bare(x); // (wave-uniform)
+    return sqrt(x);
+}
+// Where the flat k_trace kernels and the binning kernel take it: a mask of sites, 0 = plain sqrt everywhere, the code as it
+// was (kept for the A/B).
+//   1  the square root inside vnormalize_wave (ray generation, shadow_ray, shape_normal[_of]): one guard for the function
+//   2  the sphere's discriminant root of the primary pass (closest_update)
+//   4  the sphere's discriminant root of the shadow pass (occludes)
+//   8  the ring pattern's root (pattern_color)
+//  16  vnormalize_shared as the binning kernel calls it (primary_dir): per lane, joined to that function's own condition;
+//      not in the default: alone it measured no gain on the north star (profiles/bare_sqrt_ab.log)
+// trace_bare_sqrt: the instantiations that take sites 1 to 8 — trace_wave_normalize's family, the render flavour of SRC_CULL
+// and SRC_CULL2 without a frame stack, one light, pinhole camera (with ONE and WHOLE and without). Every other kernel is the
+// parent's code (tools/isa_compare.py; profiles/bare_sqrt_*).
+#ifndef RTC_BARE_SQRT
+#define RTC_BARE_SQRT 15
+#endif
+enum { BS_NORMALIZE = 1, BS_PRIMARY = 2, BS_SHADOW = 4, BS_RING = 8, BS_BIN = 16 };
+constexpr bool trace_bare_sqrt(int site, int src, bool refl, bool probe, bool alt, bool multi) {
+    return (RTC_BARE_SQRT & site) != 0 && IS_CULL(src) && !refl && !probe && !alt && !multi;
+}
+// The shared-divisor form of a / mag (vnormalize_shared's and vnormalize_wave's, see there) for a caller that has checked
+// their guard: the callers that take the magnitude's root through sqrt_bare.
+DEVI V3 vdivide_shared(V3 a, double mag) {
+    const double r0 = __builtin_amdgcn_rcp(mag);
+    const double e0 = __builtin_fma(-mag, r0, 1.0);
+    const double r1 = __builtin_fma(r0, e0, r0);
+    const double e1 = __builtin_fma(-mag, r1, 1.0);
+    const double r = __builtin_fma(r1, e1, r1);
+    auto quot = [&](double x) {
+        const double q = x * r;
+        const double rem = __builtin_fma(-mag, q, x);
+        return __builtin_amdgcn_div_fixup(__builtin_fma(rem, r, q), mag, x);
+    };
+    return mk(quot(a.x), quot(a.y), quot(a.z));
+}
 // The three IEEE divisions share their divisor. hipcc expands x / y (f64) into v_div_scale x2, v_rcp, four v_fma refining
 // 1/y, v_mul, v_fma, v_div_fmas, v_div_fixup (11 instructions); everything up to the refined reciprocal depends on y alone
 // as long as v_div_scale leaves y unscaled, which it does unless y, 1/y or x/y leave the normal range or x is tiny
@@ -103,7 +174,18 @@ DEVI V3 vnormalize_plain(V3 a) {
 // vs the host, 2 M triples). The binning kernel uses it (primary_dir). In k_trace this per-lane form measured no gain (north
 // star equal, C4 +1 %, profiles/r03_exp_shared_normalize.log: both paths compiled in line and blended per lane); the flat
 // k_trace kernels take vnormalize_wave below, every other kernel keeps vnormalize_plain.
-DEVI V3 vnormalize_shared(V3 a) {
+// BARE (RTC_BARE_SQRT's site 16): the magnitude's root through sqrt_bare under the same per-lane condition, whose term on
+// `mag` becomes vnormalize_wave's term on the sum of squares — in [2^-767, 2^799), which implies it (see there).
+template <bool BARE = false> DEVI V3 vnormalize_shared(V3 a) {
+    if constexpr (BARE) {
+        const double s = a.x * a.x + a.y * a.y + a.z * a.z;
+        auto in_range = [](double v) { return __builtin_amdgcn_class(v, 0x060 /* +-0 */) || fabs(v) >= 0x1p-500; };
+        if (f64_hi(s) - (256u << 20) < ((1023u + 799u - 256u) << 20) && in_range(a.x) && in_range(a.y) && in_range(a.z)) {
+            return vdivide_shared(a, sqrt_bare(s));
+        }
+        const double mag = sqrt(s);
+        return mk(a.x / mag, a.y / mag, a.z / mag);
+    }
     const double mag = sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
     auto in_range = [](double v) { return __builtin_amdgcn_class(v, 0x060 /* +-0 */) || fabs(v) >= 0x1p-500; };
     if (fabs(mag) >= 0x1p-400 && fabs(mag) <= 0x1p400 && in_range(a.x) && in_range(a.y) && in_range(a.z)) {
@@ -136,7 +218,27 @@ DEVI V3 vnormalize_shared(V3 a) {
 // denominator — decides every quotient with a NaN, an infinity or a zero among the two from those two operands alone,
 // whatever the refined quotient it is handed. tests/test_gpu_shared_normalize_flat.py (rtc_device_arith op 8 vs op 6 vs
 // the host) pins all of it, waves with lanes on both sides of the guard included.
+// RTC_BARE_SQRT's site 1: the root through sqrt_bare in the same wave-level choice, under ONE guard. The term on mag is
+// replaced by one on the sum of squares s, read off ITS upper word: biased exponent field in [256, 1023 + 799), that is s in
+// [2^-767, 2^799), sign clear. It is sqrt_bare_ok with a lower upper bound, so the bare root is the root; and it implies the
+// term on mag it replaces: sqrt is monotone and correctly rounded, so mag >= sqrt(2^-767) > 2^-400, and s < 2^799 gives
+// sqrt(s) < 2^399.5, which rounds to at most the double nearest 2^399.5, below 2^400. (s < 2^800 would not do: the root of the
+// double just below 2^800 rounds UP to 2^400.) Waves with a magnitude in [2^-400, 2^-383.5) or [2^399.5, 2^400) now take the
+// plain form, where they took the shared one: the same bits. The term on the components' exponents stays as it is.
 DEVI V3 vnormalize_wave(V3 a, double &mag_out) {
+    if constexpr ((RTC_BARE_SQRT & BS_NORMALIZE) != 0) {
+        const double s = a.x * a.x + a.y * a.y + a.z * a.z;
+        const int emin = min(min(__builtin_amdgcn_frexp_exp(a.x), __builtin_amdgcn_frexp_exp(a.y)), __builtin_amdgcn_frexp_exp(a.z));
+        const bool fits = emin >= -499 && f64_hi(s) - (256u << 20) < ((1023u + 799u - 256u) << 20);
+        static_assert(1023u + 799u < 2047u, "the guard on s is sqrt_bare_ok's with a lower upper bound");
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fits) == 0ull, 1)) { // (wave-uniform)
+            mag_out = sqrt_bare(s);
+            return vdivide_shared(a, mag_out);
+        }
+        const double mag = sqrt(s);
+        mag_out = mag;
+        return mk(a.x / mag, a.y / mag, a.z / mag);
+    }
     const double mag = sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
     mag_out = mag;
     const int emin = min(min(__builtin_amdgcn_frexp_exp(a.x), __builtin_amdgcn_frexp_exp(a.y)), __builtin_amdgcn_frexp_exp(a.z));
@@ -258,10 +360,11 @@ DEVI bool plane_t_certainly_negative(double oy, double dy) {
 }
 
 // World-space ray in, per-kind transform inside (a plane only needs the y row of the inverse).
-template <class P> DEVI void closest_world(uint32_t kind, P m, V3 ro, V3 rd, int j, double &best, int &hidx, int &hroot);
-template <class P> DEVI bool occludes_world(uint32_t kind, P m, V3 ro, V3 rd, double dist);
+template <bool BARE = false, class P> DEVI void closest_world(uint32_t kind, P m, V3 ro, V3 rd, int j, double &best, int &hidx, int &hroot);
+template <bool BARE = false, class P> DEVI bool occludes_world(uint32_t kind, P m, V3 ro, V3 rd, double dist);
 
-template <bool HAVE_C>
+// BARE (here, in occludes and in pattern_color): the root through sqrt_wave — RTC_BARE_SQRT's sites 2, 4 and 8.
+template <bool HAVE_C, bool BARE = false>
 DEVI void closest_update(uint32_t kind, V3 o, V3 d, double c_pre, int j, double &best, int &hidx, int &hroot) {
     if (kind == RTC_SPHERE) {
         const double a = vdot(d, d);
@@ -269,7 +372,7 @@ DEVI void closest_update(uint32_t kind, V3 o, V3 d, double c_pre, int j, double 
         const double c = HAVE_C ? c_pre : (vdot(o, o) - 1.);
         const double disc = (b * b) - 4. * a * c;
         if (!(disc < 0.)) {
-            const double sq = sqrt(disc);
+            const double sq = BARE ? sqrt_wave(disc) : sqrt(disc);
             const double den = 2. * a;
             const double t1 = (-b - sq) / den;
             if (t1 >= 0.0) {
@@ -288,14 +391,14 @@ DEVI void closest_update(uint32_t kind, V3 o, V3 d, double c_pre, int j, double 
 }
 
 // is_shadowed_by_light (shape.rs:716-727): hit.t < distance  <=>  some entry has 0 <= t < distance.
-DEVI bool occludes(uint32_t kind, V3 o, V3 d, double dist) {
+template <bool BARE = false> DEVI bool occludes(uint32_t kind, V3 o, V3 d, double dist) {
     if (kind == RTC_SPHERE) {
         const double a = vdot(d, d);
         const double b = 2. * vdot(d, o);
         const double c = vdot(o, o) - 1.;
         const double disc = (b * b) - 4. * a * c;
         if (disc < 0.) return false;
-        const double sq = sqrt(disc);
+        const double sq = BARE ? sqrt_wave(disc) : sqrt(disc);
         const double den = 2. * a;
         const double t1 = (-b - sq) / den;
         if (t1 >= 0.0) return t1 < dist;
@@ -309,7 +412,7 @@ DEVI bool occludes(uint32_t kind, V3 o, V3 d, double dist) {
     return false;
 }
 
-template <class P> DEVI void closest_world(uint32_t kind, P m, V3 ro, V3 rd, int j, double &best, int &hidx, int &hroot) {
+template <bool BARE, class P> DEVI void closest_world(uint32_t kind, P m, V3 ro, V3 rd, int j, double &best, int &hidx, int &hroot) {
     if (kind == RTC_PLANE) { // shape.rs:462-471
         const double oy = xpoint_y(m, ro), dy = xvector_y(m, rd);
         if (!(fabs(dy) < RTC_EPSILON) && !plane_t_certainly_negative(oy, dy)) {
@@ -317,23 +420,23 @@ template <class P> DEVI void closest_world(uint32_t kind, P m, V3 ro, V3 rd, int
             if (t >= 0.0 && closer(t, j, best, hidx)) { best = t; hidx = j; hroot = 0; }
         }
     } else {
-        closest_update<false>(kind, xpoint(m, ro), xvector(m, rd), 0., j, best, hidx, hroot);
+        closest_update<false, BARE>(kind, xpoint(m, ro), xvector(m, rd), 0., j, best, hidx, hroot);
     }
 }
-template <class P> DEVI bool occludes_world(uint32_t kind, P m, V3 ro, V3 rd, double dist) {
+template <bool BARE, class P> DEVI bool occludes_world(uint32_t kind, P m, V3 ro, V3 rd, double dist) {
     if (kind == RTC_PLANE) {
         const double oy = xpoint_y(m, ro), dy = xvector_y(m, rd);
         if (fabs(dy) < RTC_EPSILON || plane_t_certainly_negative(oy, dy)) return false;
         const double t = -oy / dy;
         return t >= 0.0 && t < dist;
     }
-    return occludes(kind, xpoint(m, ro), xvector(m, rd), dist);
+    return occludes<BARE>(kind, xpoint(m, ro), xvector(m, rd), dist);
 }
 
 // Primary rays: the object-space origin `po` (= transform_point(inv, camera origin)) and the sphere's
 // c = po.po - 1 are the same for every pixel; they come from the per-render table `prim`
 // (k_prep_primary, same arithmetic), so only the direction is transformed here.
-template <class P, class Q> DEVI void closest_prim(uint32_t kind, P m, Q pr, V3 rd, int j, double &best, int &hidx, int &hroot) {
+template <bool BARE = false, class P, class Q> DEVI void closest_prim(uint32_t kind, P m, Q pr, V3 rd, int j, double &best, int &hidx, int &hroot) {
     if (kind == RTC_PLANE) {
         const double oy = pr[1], dy = xvector_y(m, rd);
         if (!(fabs(dy) < RTC_EPSILON) && !plane_t_certainly_negative(oy, dy)) {
@@ -341,7 +444,7 @@ template <class P, class Q> DEVI void closest_prim(uint32_t kind, P m, Q pr, V3 
             if (t >= 0.0 && closer(t, j, best, hidx)) { best = t; hidx = j; hroot = 0; }
         }
     } else {
-        closest_update<true>(kind, mk(pr[0], pr[1], pr[2]), xvector(m, rd), pr[3], j, best, hidx, hroot);
+        closest_update<true, BARE>(kind, mk(pr[0], pr[1], pr[2]), xvector(m, rd), pr[3], j, best, hidx, hroot);
     }
 }
 
@@ -986,35 +1089,37 @@ template <bool WAVE_NORM = false> DEVI void shadow_ray(V3 light_pos, V3 over, bo
 
 // The closest-hit walk's body (World::intersect + get_hit, streaming form): the exact test of object j for the lanes still
 // tracing, folded into (best, hidx, hroot). Never stops the walk. Holds references, as a [&] lambda would.
-struct ClosestHit {
+template <bool BARE> struct ClosestHitT {
     const bool &tracing;
     const V3 &ro, &rd;
     double &best;
     int &hidx, &hroot;
     template <class M, class Q> DEVI bool operator()(int j, M m, uint32_t kind, Q) const {
-        if (tracing) closest_world(kind, m, ro, rd, j, best, hidx, hroot);
+        if (tracing) closest_world<BARE>(kind, m, ro, rd, j, best, hidx, hroot);
         return true;
     }
 };
+using ClosestHit = ClosestHitT<false>;
 
 // The any-hit walk's body (is_shadowed shape.rs:721-726): the exact test of one object for the lanes still pending — the
 // first object in the way settles a lane — and the walk goes on while some lane is pending. Holds references, as a [&]
 // lambda would.
-struct AnyHit {
+template <bool BARE> struct AnyHitT {
     bool &pending;
     const V3 &over, &dir;
     const double &dist;
     bool &shadowed;
     template <class M, class Q> DEVI bool operator()(int, M m, uint32_t kind, Q) const {
         if (pending) {
-            if (occludes_world(kind, m, over, dir, dist)) { shadowed = true; pending = false; }
+            if (occludes_world<BARE>(kind, m, over, dir, dist)) { shadowed = true; pending = false; }
         }
         return ballot(pending) != 0ull; // stop as soon as no lane is pending
     }
 };
+using AnyHit = AnyHitT<false>;
 
 // ---- patterns (material.rs:41-45 and the six pattern_at bodies) --------------------------
-DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
+template <bool BARE = false> DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
     const V3 op = xpoint(m_obj, world_point);
     const V3 pp = xpoint(S->pat_inv, op);
     const V3 a = mk(S->pat_a[0], S->pat_a[1], S->pat_a[2]);
@@ -1026,7 +1131,7 @@ DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
         const V3 diff = vsub(b, a); // GradientPattern::new: _diff = b.sub(a)
         return vadd(a, vmul(diff, pp.x - floor(pp.x)));
     }
-    case RTC_PATTERN_RING: return rtc_even_f64(floor(sqrt(pp.x * pp.x + pp.y * pp.y))) ? a : b;
+    case RTC_PATTERN_RING: return rtc_even_f64(floor(BARE ? sqrt_wave(pp.x * pp.x + pp.y * pp.y) : sqrt(pp.x * pp.x + pp.y * pp.y))) ? a : b;
     case RTC_PATTERN_CHECKER: return rtc_even_f64(floor(pp.x) + floor(pp.y) + floor(pp.z)) ? a : b;
     case RTC_PATTERN_GRID:
         return (fabs(pp.x - floor(pp.x)) < 0.01 || fabs(pp.z - floor(pp.z)) < 0.01) ? b : a;
@@ -1036,7 +1141,7 @@ DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
 
 // Material::lighting material.rs:319-361. lightv = (light.position - point).normalize() is
 // the shadow ray's direction (same expression, shape.rs:717-719), passed in.
-template <class PP>
+template <bool BARE = false, class PP>
 DEVI V3 lighting(const PP &P, const DevShade *S, const double *m_obj, V3 point, V3 eyev, V3 normal,
                  V3 lightv, bool in_shadow) {
     // The reference's statement order is effective_color, lightv, ambient, [shadow?] light_dot_normal,
@@ -1065,7 +1170,7 @@ DEVI V3 lighting(const PP &P, const DevShade *S, const double *m_obj, V3 point, 
     }
     asm volatile("" ::: "memory"); // the material colour / pattern loads start here, not above the pow
     const V3 I = mk(P.light_int[0], P.light_int[1], P.light_int[2]);
-    const V3 base = (S->pattern_kind != RTC_PATTERN_NONE) ? pattern_color(S, m_obj, point)
+    const V3 base = (S->pattern_kind != RTC_PATTERN_NONE) ? pattern_color<BARE>(S, m_obj, point)
                                                           : mk(S->color[0], S->color[1], S->color[2]);
     const V3 eff = vmulv(base, I);
     const V3 ambient = vmul(eff, S->ambient);
@@ -1402,6 +1507,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     // rtc_shape::kind as kind[] and kind_s[] (flatten_shapes, for rtc_world_create and rtc_world_update alike). The walks
     // that are not the binned pass (no lists, an overflowing list) read DevShade::kind as before.
     constexpr bool CARRY_KIND = trace_short_chains(SC_KIND, SRC, REFL, ONE, MULTI);
+    // RTC_BARE_SQRT's sites in this kernel (vnormalize_wave has site 1 in itself)
+    constexpr bool BARE_PRIMARY = trace_bare_sqrt(BS_PRIMARY, SRC, REFL, PROBE, ALT, MULTI), BARE_SHADOW = trace_bare_sqrt(BS_SHADOW, SRC, REFL, PROBE, ALT, MULTI),
+                   BARE_RING = trace_bare_sqrt(BS_RING, SRC, REFL, PROBE, ALT, MULTI);
     if constexpr (IS_CULL(SRC) && !PROBE && !ALT && !HEADER_LOOKUP) { // (the proof is for rays from the camera origin)
         const auto &Pt = KP(P_arg);
         if (Pt.tile_rows != nullptr && (ONE || Pt.samples == 1u)) {
@@ -1645,7 +1753,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 // closest_prim: the camera origin in object space and the sphere's c from that table, 24 VALU instructions
                 // fewer per sphere test than transforming the origin again (closest_world)
                 auto binned_test = [&](uint32_t kind, const double *m, uint32_t j) {
-                    closest_prim(kind, m, reinterpret_cast<const double *>(vprim + j), rd, (int)j, best, hidx, hroot);
+                    closest_prim<BARE_PRIMARY>(kind, m, reinterpret_cast<const double *>(vprim + j), rd, (int)j, best, hidx, hroot);
                     // CARRY_KIND: object j is a lane's closest hit exactly when hidx names it after its test; its kind goes above
                     // the root bit of hroot (0 or 1, and read by the refractive kernels only): no further value beside hidx
                     if constexpr (CARRY_KIND) {
@@ -1671,7 +1779,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                         asm volatile("" : "+s"(kd), "+s"(rec.m[0]), "+s"(rec.m[1]), "+s"(rec.m[2]), "+s"(rec.m[4]), "+s"(rec.m[5]), "+s"(rec.m[6]),
                                      "+s"(rec.m[8]), "+s"(rec.m[9]), "+s"(rec.m[10]), "+s"(pr.ox), "+s"(pr.oy), "+s"(pr.oz), "+s"(pr.c));
                     const double prv[4] = {pr.ox, pr.oy, pr.oz, pr.c};
-                    closest_prim(kd, rec.m, prv, rd, (int)j, best, hidx, hroot);
+                    closest_prim<BARE_PRIMARY>(kd, rec.m, prv, rd, (int)j, best, hidx, hroot);
                     if constexpr (CARRY_KIND) {
                         if (hidx == (int)j) hroot = (hroot & 1) | (int)(kd << 1);
                     }
@@ -1761,9 +1869,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 }
             } else if (SRC == SRC_CULL2 && !PROBE && shared_origin && first) {
                 // primary rays of a large world: start at the apex, unit direction -> ordered walk with early stop
-                for_each_object<SRC, false>(P, T, L, tracing, B, ClosestHit{tracing, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(tracing && !(best < (double)key)) == 0ull; });
+                for_each_object<SRC, false>(P, T, L, tracing, B, ClosestHitT<BARE_PRIMARY>{tracing, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(tracing && !(best < (double)key)) == 0ull; });
             } else {
-                for_each_object<SRC>(P, T, L, tracing, B, ClosestHit{tracing, ro, rd, best, hidx, hroot}, ro, rd);
+                for_each_object<SRC>(P, T, L, tracing, B, ClosestHitT<BARE_PRIMARY>{tracing, ro, rd, best, hidx, hroot}, ro, rd);
             }
             const bool hit = tracing && hidx >= 0;
             const auto &Ph = KP(P_arg); // shading view: light
@@ -1920,7 +2028,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     listed = ballot(ccnt > Pl.light_cap) == 0ull;      // a cell whose list overflowed is incomplete: fall back
                     if (listed) {
                         for (uint32_t k = 0; k < Pl.n_unb && ballot(sh_pending) != 0ull; ++k) { // unbounded objects: never listed
-                            if (sh_pending && occludes_world(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                            if (sh_pending && occludes_world<BARE_SHADOW>(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                         }
                         // pre-inflated prefilter records hold while every origin is within their limit (DevPre)
                         bool pre_ok;
@@ -1980,7 +2088,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                                 for (uint32_t b = 0; b < LB; ++b) {
                                     if (todo[b] && ent[b] == j) { sel = true; todo[b] = false; }
                                 }
-                                if (sel && sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                                if (sel && sh_pending && occludes_world<BARE_SHADOW>(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                             }
                         }
                     }
@@ -2000,7 +2108,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                     listed = ballot(hit && ccnt > Pl.light_cap) == 0ull;       // a cell whose list overflowed is incomplete: walk instead
                     if (listed) {
                         for (uint32_t k = 0; k < Pl.n_unb && ballot(sh_pending) != 0ull; ++k) { // unbounded objects: never listed
-                            if (sh_pending && occludes_world(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                            if (sh_pending && occludes_world<BARE_SHADOW>(T.kind_s[k], T.isect_s[k].m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                         }
                         bool pre_ok; // pre-inflated prefilter records hold while every origin is within their limit (DevPre)
                         double sdd;
@@ -2040,12 +2148,12 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                                     if (b0 != 0ull) {
                                         const DevIsect rec = T.isect[j0];
                                         const uint32_t kd = T.kind[j0];
-                                        if (sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                                        if (sh_pending && occludes_world<BARE_SHADOW>(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                                     }
                                     if (b1 != 0ull && ballot(sh_pending) != 0ull) {
                                         const DevIsect rec = T.isect[j1];
                                         const uint32_t kd = T.kind[j1];
-                                        if (sh_pending && occludes_world(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
+                                        if (sh_pending && occludes_world<BARE_SHADOW>(kd, rec.m, over, sdir, sdist)) { shadowed = true; sh_pending = false; }
                                     }
                                 }
                             }
@@ -2054,7 +2162,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
                 }
             }
             if (!listed)
-            for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, sh_pending, Bs, AnyHit{sh_pending, over, sdir, sdist, shadowed}, over, sdir);
+            for_each_object<SRC, SHADOW_LANE_FILTER>(P, T, L, sh_pending, Bs, AnyHitT<BARE_SHADOW>{sh_pending, over, sdir, sdist, shadowed}, over, sdir);
 
             // keep the material / pattern loads of the lighting stage BELOW the shadow loop: hoisted
             // above it they stay live through the loop and cost a wave per SIMD in occupancy
@@ -2116,7 +2224,7 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             } else if (hit) {
                 V3 surface;
                 if constexpr (MULTI) surface = surface_all;
-                else surface = lighting(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
+                else surface = lighting<BARE_RING>(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
                 bool want_refl = false, want_refr = false;
                 V3 fr_o = mk(0, 0, 0), fr_d = mk(0, 0, 0);
                 if constexpr (REFL) want_refl = (rem != 0) && !(m_kr <= 0.); // reflected_color shape.rs:730 (NaN: cast)
@@ -2465,7 +2573,7 @@ __global__ void k_arith(uint32_t op, const double *a, const double *b, uint32_t 
     if (op == 5u || op == 6u) { // Vector::normalize of the triple (a[3t], a[3t+1], a[3t+2]): 5 = the shared-divisor form, 6 = three divisions
         if (i % 3u == 0u && i + 2u < n) {
             const V3 v = mk(a[i], a[i + 1], a[i + 2]);
-            const V3 r3 = op == 5u ? vnormalize_shared(v) : vnormalize_plain(v);
+            const V3 r3 = op == 5u ? vnormalize_shared<(RTC_BARE_SQRT & BS_BIN) != 0>(v) : vnormalize_plain(v); // (5: as primary_dir calls it)
             out[i] = r3.x; out[i + 1] = r3.y; out[i + 2] = r3.z;
         }
         return;
@@ -2482,6 +2590,7 @@ __global__ void k_arith(uint32_t op, const double *a, const double *b, uint32_t 
     double r;
     switch (op) {
     case 0: r = sqrt(a[i]); break;
+    case 9: r = sqrt_wave(a[i]); break; // sqrt as the flat k_trace kernels call it: thread t takes element t, a wave holds 64 consecutive values
     case 1: r = a[i] / b[i]; break;
     case 2: r = pow(a[i], b[i]); break;
     case 3: r = floor(a[i]); break;
@@ -2494,7 +2603,7 @@ __global__ void k_arith(uint32_t op, const double *a, const double *b, uint32_t 
 // ---- binned primary pass: per-view tile lists (DevTileBundle, rtc_device.h) ---------------------------------------
 // Primary ray of pixel (px, py) of one camera: Camera::ray_for_pixel_offset(x, 0.5, y, 0.5) camera.rs:64-76, the
 // expression k_trace evaluates.
-DEVI V3 primary_dir(const DevCamera &C, V3 cam_origin, uint32_t px, uint32_t py, double xo = 0.5, double yo = 0.5) {
+template <bool BARE = false> DEVI V3 primary_dir(const DevCamera &C, V3 cam_origin, uint32_t px, uint32_t py, double xo = 0.5, double yo = 0.5) {
     const double xoffset = ((double)px + xo) * C.pixel_size;
     const double yoffset = ((double)py + yo) * C.pixel_size;
     const double world_x = C.half_width - xoffset;
@@ -2502,7 +2611,7 @@ DEVI V3 primary_dir(const DevCamera &C, V3 cam_origin, uint32_t px, uint32_t py,
     const V3 pixel = xpoint(C.vinv, mk(world_x, world_y, -1.));
     // the shared-divisor form (bit-identical, and a cone does not even need that): the binning kernel's lanes normalise ten
     // corner rays each on one latency-bound chain — C3's pipelined frame -7 % (profiles/r03_exp_shared_normalize.log)
-    return vnormalize_shared(vsub(pixel, cam_origin));
+    return vnormalize_shared<BARE>(vsub(pixel, cam_origin)); // (BARE: RTC_BARE_SQRT's site 16, the binning kernel's cones only)
 }
 
 struct BinParams {
@@ -2544,7 +2653,7 @@ DEVI DevTileBundle cell_cone(const BinParams &Q, uint32_t view, uint32_t x0, uin
     const DevCamera &C = Q.views[view];
     const V3 o = xpoint(C.vinv, mk(0., 0., 0.));
     float ax, ay, az;
-    bool good = finite3(o) && dir_f32(primary_dir(C, o, min(x0 + cell / 2u - 1u, x1), min(y0 + cell / 2u - 1u, y1)), ax, ay, az);
+    bool good = finite3(o) && dir_f32(primary_dir<(RTC_BARE_SQRT & BS_BIN) != 0>(C, o, min(x0 + cell / 2u - 1u, x1), min(y0 + cell / 2u - 1u, y1)), ax, ay, az);
     float q2max = 0.f;
     bool narrow = true;
     // corners of the cell's pixel AREA (offsets 0 and 1, not the pixel centres): the cone then also holds every
@@ -2552,7 +2661,7 @@ DEVI DevTileBundle cell_cone(const BinParams &Q, uint32_t view, uint32_t x0, uin
     const uint32_t cx[4] = {x0, x1, x0, x1}, cy[4] = {y0, y0, y1, y1};
     for (int k = 0; k < 4; ++k) {
         float fx, fy, fz;
-        good = dir_f32(primary_dir(C, o, cx[k], cy[k], (k & 1) ? 1.0 : 0.0, (k & 2) ? 1.0 : 0.0), fx, fy, fz) && good;
+        good = dir_f32(primary_dir<(RTC_BARE_SQRT & BS_BIN) != 0>(C, o, cx[k], cy[k], (k & 1) ? 1.0 : 0.0, (k & 2) ? 1.0 : 0.0), fx, fy, fz) && good;
         const float dotv = ax * fx + ay * fy + az * fz;
         const float ux = ay * fz - az * fy, uy = az * fx - ax * fz, uz = ax * fy - ay * fx;
         q2max = fmaxf(q2max, ux * ux + uy * uy + uz * uz);
