@@ -687,16 +687,18 @@ def _copy_lights(arr, n: int) -> list:
     return out
 
 
-def _load_scene(entry: str, text: str | None, path: str | None, *extra, where: str | None = None):
-    """What the load_yaml* functions share: `entry` (its `_file` twin when `path` is given) called with the common buffers and
-    then `extra`, the entry point's further out-arguments, each by reference; failures raise under `where` (default: `entry`).
-    -> (World with every `add: light` of the file and the shapes copied out of the library's array, RtcCamera)."""
+def _load_scene(entry: str, text: str | None, path: str | None, records=(), extra=(), where: str | None = None) -> tuple:
+    """What the load_yaml* functions share: `entry` (its `_file` twin when `path` is given) called with the common buffers, then a
+    (record, has) pair for each ctypes type of `records`, then `extra`, the entry point's further out-arguments, each by
+    reference; failures raise under `where` (default: `entry`). -> (World with every `add: light` of the file and the shapes
+    copied out of the library's array, RtcCamera, then for each of `records` the record, or None where the camera lacks its keys)."""
     shapes, n = C.POINTER(RtcShape)(), C.c_uint32(0)
     lgts, nl, cam = (RtcAreaLight * MAX_LIGHT_SAMPLES)(), C.c_uint32(0), RtcCamera()
     err = C.create_string_buffer(512)
+    pairs = [(ctype(), C.c_uint32(0)) for ctype in records]
     fn = getattr(lib(), entry + "_file" if path is not None else entry)
     st = fn(str(path).encode() if path is not None else text.encode(), C.byref(shapes), C.byref(n), lgts, MAX_LIGHT_SAMPLES, C.byref(nl), C.byref(cam),
-            err, 512, *map(C.byref, extra))
+            err, 512, *[C.byref(x) for pair in pairs for x in pair], *map(C.byref, extra))
     _check(st, where or entry, err.value.decode(errors="replace"))
     w = World([_copy_light(lgts[i]) for i in range(nl.value)])
     for i in range(n.value):
@@ -704,7 +706,7 @@ def _load_scene(entry: str, text: str | None, path: str | None, *extra, where: s
         C.memmove(C.byref(s), C.byref(shapes[i]), C.sizeof(RtcShape))
         w.shapes.append(s)
     lib().rtc_free(shapes)
-    return w, cam
+    return (w, cam, *[record if has.value else None for record, has in pairs])
 
 
 def load_yaml(text: str | None = None, path: str | None = None):
@@ -715,83 +717,67 @@ def load_yaml(text: str | None = None, path: str | None = None):
 def load_yaml_lens(text: str | None = None, path: str | None = None):
     """load_yaml for scenes whose camera may have a thin lens (aperture / focal-distance / lens-usteps / lens-vsteps):
     -> (World, RtcCamera, RtcLens or None)."""
-    ln, has = RtcLens(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_lens", text, path, ln, has)
-    return w, cam, (ln if has.value else None)
+    return _load_scene("rtc_scene_load_yaml_lens", text, path, [RtcLens])
 
 
 def load_yaml_ao(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes whose camera may ask for ambient occlusion (ao-radius / ao-usteps / ao-vsteps):
     -> (World, RtcCamera, RtcLens or None, RtcAo or None)."""
-    ln, has, a, has_a = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_ao", text, path, ln, has, a, has_a)
-    return w, cam, (ln if has.value else None), (a if has_a.value else None)
+    return _load_scene("rtc_scene_load_yaml_ao", text, path, [RtcLens, RtcAo])
 
 
 def load_yaml_gather(text: str | None = None, path: str | None = None):
     """load_yaml_ao for scenes whose camera may also ask for a gather pass (gather-radius / gather-usteps / gather-vsteps):
     -> (World, RtcCamera, RtcLens or None, RtcAo or None, RtcAo or None), the last the gather pass."""
-    ln, has, a, has_a, g, has_g = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_gather", text, path, ln, has, a, has_a, g, has_g)
-    return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None)
+    return _load_scene("rtc_scene_load_yaml_gather", text, path, [RtcLens, RtcAo, RtcAo])
 
 
 def load_yaml_filter(text: str | None = None, path: str | None = None):
     """load_yaml_gather for scenes whose camera may also ask for the edge-aware filter (filter-plane-sigma / filter-passes /
     filter-normal-squarings): -> (World, RtcCamera, RtcLens or None, RtcAo or None, RtcAo or None, RtcFilter or None)."""
-    ln, has, a, has_a, g, has_g, f, has_f = RtcLens(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcAo(), C.c_uint32(0), RtcFilter(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_filter", text, path, ln, has, a, has_a, g, has_g, f, has_f)
-    return w, cam, (ln if has.value else None), (a if has_a.value else None), (g if has_g.value else None), (f if has_f.value else None)
+    return _load_scene("rtc_scene_load_yaml_filter", text, path, [RtcLens, RtcAo, RtcAo, RtcFilter])
 
 
 def load_yaml_adaptive(text: str | None = None, path: str | None = None):
     """load_yaml for scenes whose camera may ask for adaptive anti-aliasing (aa-threshold / aa-usteps / aa-vsteps):
     -> (World, RtcCamera, RtcAdaptive or None)."""
-    a, has = RtcAdaptive(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_adaptive", text, path, a, has)
-    return w, cam, (a if has.value else None)
+    return _load_scene("rtc_scene_load_yaml_adaptive", text, path, [RtcAdaptive])
 
 
 def load_yaml_post(text: str | None = None, path: str | None = None):
     """load_yaml for scenes whose camera may ask for post-processing (tonemap-curve / tonemap-exposure / tonemap-key /
     tonemap-white, bloom-threshold / bloom-strength / bloom-sigma / bloom-radius): -> (World, RtcCamera, RtcTonemap or None,
     RtcBloom or None)."""
-    t, has_t, b, has_b = RtcTonemap(), C.c_uint32(0), RtcBloom(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_post", text, path, t, has_t, b, has_b)
-    return w, cam, (t if has_t.value else None), (b if has_b.value else None)
+    return _load_scene("rtc_scene_load_yaml_post", text, path, [RtcTonemap, RtcBloom])
 
 
 def load_yaml_resize(text: str | None = None, path: str | None = None):
     """load_yaml_projection for scenes whose camera may ask for a delivered size (output-width / output-height / output-filter):
     -> (World, RtcCamera, RtcLens or None, RtcProjection or None, RtcResize or None, out_width, out_height); without the keys
     the size is the camera's own."""
-    ln, has, pj, has_pj = RtcLens(), C.c_uint32(0), RtcProjection(), C.c_uint32(0)
-    rs, ow, oh, has_rs = RtcResize(), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_resize", text, path, ln, has, pj, has_pj, rs, ow, oh, has_rs)
-    return w, cam, (ln if has.value else None), (pj if has_pj.value else None), (rs if has_rs.value else None), ow.value, oh.value
+    rs, ow, oh, has_rs = RtcResize(), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)  # (the sizes sit between the record and its flag)
+    w, cam, ln, pj = _load_scene("rtc_scene_load_yaml_resize", text, path, [RtcLens, RtcProjection], extra=(rs, ow, oh, has_rs))
+    return w, cam, ln, pj, (rs if has_rs.value else None), ow.value, oh.value
 
 
 def load_yaml_projection(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes whose camera may have a projection (projection: orthographic | panorama, ortho-width,
     pano-h-span, pano-v-span): -> (World, RtcCamera, RtcLens or None, RtcProjection or None)."""
-    ln, has, pj, has_pj = RtcLens(), C.c_uint32(0), RtcProjection(), C.c_uint32(0)
-    w, cam = _load_scene("rtc_scene_load_yaml_projection", text, path, ln, has, pj, has_pj)
-    return w, cam, (ln if has.value else None), (pj if has_pj.value else None)
+    return _load_scene("rtc_scene_load_yaml_projection", text, path, [RtcLens, RtcProjection])
 
 
 def load_yaml_motion(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes with motion blur (a shape's `motion:` transform list, the camera's `shutter-samples`):
     -> (World, RtcCamera, RtcLens or None, [RtcMotion], samples) — what Shutter.render takes."""
-    ln, has = RtcLens(), C.c_uint32(0)
     mots, nm, samples = C.POINTER(RtcMotion)(), C.c_uint32(0), C.c_uint32(1)
-    w, cam = _load_scene("rtc_scene_load_yaml_motion", text, path, ln, has, mots, nm, samples)
+    w, cam, ln = _load_scene("rtc_scene_load_yaml_motion", text, path, [RtcLens], extra=(mots, nm, samples))
     motions = []
     for i in range(nm.value):
         m = RtcMotion()
         C.memmove(C.byref(m), C.byref(mots[i]), C.sizeof(RtcMotion))
         motions.append(m)
     lib().rtc_free(mots)
-    return w, cam, (ln if has.value else None), motions, samples.value
+    return w, cam, ln, motions, samples.value
 
 
 class LuaJob:

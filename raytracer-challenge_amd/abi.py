@@ -218,10 +218,6 @@ PROTOTYPES = {
     "rtc_shape_init": (C.c_int32, [U32, Mat16, C.POINTER(RtcMaterial), C.POINTER(RtcShape)]),
     "rtc_material_set_pattern": (C.c_int32, [C.POINTER(RtcMaterial), U32, Vec3, Vec3, Mat16]),
     "rtc_light_default": (None, [C.POINTER(RtcLight)]),
-    "rtc_scene_load_yaml": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
-                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_yaml_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
-                                             C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
     "rtc_canvas_write_png8": (C.c_int32, [C.c_char_p, C.POINTER(C.c_uint8), U32, U32, U32]),
     "rtc_canvas_format_png8": (C.c_size_t, [C.POINTER(C.c_uint8), U32, U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
     "rtc_lua_run": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
@@ -273,45 +269,9 @@ PROTOTYPES = {
     "rtc_image_encoder_write": (C.c_int32, [VP, C.c_char_p]),
     "rtc_image_encoder_destroy": (None, [VP]),
     "rtc_lua_program_render_saved": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, LUA_FILE_FN, C.c_void_p, C.POINTER(RtcStats)]),
-    "rtc_scene_load_lua": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
-                                       C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_lua_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight),
-                                            C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_yaml_lights": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
-                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_yaml_lights_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
-                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_lua_lights": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
-                                              C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_lua_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcLight), U32, C.POINTER(U32),
-                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
     "rtc_lua_program_job_lights": (C.c_int32, [C.c_void_p, U32, C.POINTER(RtcLight), U32, C.POINTER(U32)]),
     "rtc_area_light_from_point": (C.c_int32, [C.POINTER(RtcLight), C.POINTER(RtcAreaLight)]),
     "rtc_area_light_expand": (C.c_int32, [C.POINTER(RtcAreaLight), U32, C.POINTER(RtcLight), U32, C.POINTER(U32)]),
-    "rtc_scene_load_yaml_area_lights": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_yaml_area_lights_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                         C.POINTER(RtcCamera), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_lua_area_lights": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_lua_area_lights_file": (C.c_int32, [C.c_char_p, U32, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(U32), C.c_char_p, C.c_size_t]),
-    "rtc_scene_load_yaml_projection": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                   C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                   C.POINTER(RtcProjection), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_projection_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                        C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                        C.POINTER(RtcProjection), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_lens": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                             C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_lens_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                  C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_motion": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                               C.POINTER(C.POINTER(RtcMotion)), C.POINTER(U32), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_motion_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                    C.POINTER(C.POINTER(RtcMotion)), C.POINTER(U32), C.POINTER(U32)]),
     "rtc_shutter_time": (D, [U32, U32]),
     "rtc_shutter_shapes": (C.c_int32, [C.POINTER(RtcShape), U32, C.POINTER(RtcMotion), U32, U32, U32, C.POINTER(RtcShape)]),
     "rtc_shutter_camera": (C.c_int32, [C.POINTER(RtcCamera), C.POINTER(RtcCamera), U32, U32, C.POINTER(RtcCamera)]),
@@ -408,23 +368,11 @@ PROTOTYPES = {
     "rtc_render_ao": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(C.c_uint16)]),
     "rtc_canvas_apply_ao": (C.c_int32, [PD, C.POINTER(C.c_uint16), U32, D, U32, U32]),
     "rtc_canvas_apply_ao_device": (C.c_int32, [VP, VP, VP, U32, D, U32, U32]),
-    "rtc_scene_load_yaml_ao": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                           C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                           C.POINTER(RtcAo), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_ao_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                C.POINTER(RtcAo), C.POINTER(U32)]),
     "rtc_gather_from_hits": (C.c_int32, [C.POINTER(RtcHit), C.POINTER(RtcHit), PD, PD, U32, D, U32, U32, U32, C.POINTER(RtcGatherBuffers)]),
     "rtc_render_gather_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
     "rtc_render_gather": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
     "rtc_canvas_add_scaled": (C.c_int32, [PD, PD, D, U32, U32]),
     "rtc_canvas_add_scaled_device": (C.c_int32, [VP, VP, VP, D, U32, U32]),
-    "rtc_scene_load_yaml_gather": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                               C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_gather_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                    C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32)]),
     "rtc_float_format_for_name": (C.c_int32, [C.c_char_p, C.POINTER(U32)]),
     "rtc_float_format": (C.c_size_t, [U32, C.POINTER(RtcFloatPlanes), U32, U32, C.POINTER(C.c_uint8), C.c_size_t]),
     "rtc_canvas_save_f64": (C.c_int32, [C.c_char_p, PD, U32, U32]),
@@ -443,12 +391,6 @@ PROTOTYPES = {
     "rtc_counts_to_fraction_device": (C.c_int32, [VP, VP, U32, U32, U32, VP]),
     "rtc_canvas_apply_occlusion": (C.c_int32, [PD, PD, D, U32, U32]),
     "rtc_canvas_apply_occlusion_device": (C.c_int32, [VP, VP, VP, D, U32, U32]),
-    "rtc_scene_load_yaml_filter": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                               C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcFilter), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_filter_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                    C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcAo), C.POINTER(U32), C.POINTER(RtcFilter), C.POINTER(U32)]),
     "rtc_adaptive_validate": (C.c_int32, [C.POINTER(RtcAdaptive)]),
     "rtc_adaptive_offset": (C.c_int32, [C.POINTER(RtcAdaptive), U32, PD, PD]),
     "rtc_adaptive_mask": (C.c_int32, [PD, U32, U32, U32, D, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]),
@@ -456,10 +398,6 @@ PROTOTYPES = {
     "rtc_render_adaptive_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAdaptive), U32, U32, VP, VP, C.POINTER(RtcAdaptiveInfo)]),
     "rtc_render_adaptive": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAdaptive), U32, U32, PD, C.POINTER(C.c_uint8),
                                         C.POINTER(RtcAdaptiveInfo), C.POINTER(RtcStats)]),
-    "rtc_scene_load_yaml_adaptive": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                 C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcAdaptive), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_adaptive_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                      C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcAdaptive), C.POINTER(U32)]),
     "rtc_canvas_luminance": (C.c_int32, [PD, U32, U32, C.POINTER(RtcLuminance)]),
     "rtc_canvas_luminance_device": (C.c_int32, [VP, VP, U32, U32, VP]),
     "rtc_tonemap_validate": (C.c_int32, [C.POINTER(RtcTonemap)]),
@@ -470,24 +408,40 @@ PROTOTYPES = {
     "rtc_bloom_weights": (C.c_int32, [C.POINTER(RtcBloom), PD]),
     "rtc_canvas_bloom": (C.c_int32, [PD, U32, U32, C.POINTER(RtcBloom), PD]),
     "rtc_canvas_bloom_device": (C.c_int32, [VP, VP, U32, U32, C.POINTER(RtcBloom), VP]),
-    "rtc_scene_load_yaml_post": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                             C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcTonemap), C.POINTER(U32),
-                                             C.POINTER(RtcBloom), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_post_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                  C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcTonemap), C.POINTER(U32),
-                                                  C.POINTER(RtcBloom), C.POINTER(U32)]),
     "rtc_resize_validate": (C.c_int32, [C.POINTER(RtcResize)]),
     "rtc_resize_taps": (U32, [U32, U32, U32]),
     "rtc_resize_weights": (C.c_int32, [U32, U32, C.POINTER(RtcResize), C.POINTER(U32), C.POINTER(U32), PD]),
     "rtc_canvas_resize": (C.c_int32, [PD, U32, U32, C.POINTER(RtcResize), PD, U32, U32]),
     "rtc_canvas_resize_device": (C.c_int32, [VP, VP, U32, U32, C.POINTER(RtcResize), VP, U32, U32]),
-    "rtc_scene_load_yaml_resize": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                               C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                               C.POINTER(RtcProjection), C.POINTER(U32), C.POINTER(RtcResize), C.POINTER(U32), C.POINTER(U32), C.POINTER(U32)]),
-    "rtc_scene_load_yaml_resize_file": (C.c_int32, [C.c_char_p, C.POINTER(C.POINTER(RtcShape)), C.POINTER(U32), C.POINTER(RtcAreaLight), U32, C.POINTER(U32),
-                                                    C.POINTER(RtcCamera), C.c_char_p, C.c_size_t, C.POINTER(RtcLens), C.POINTER(U32),
-                                                    C.POINTER(RtcProjection), C.POINTER(U32), C.POINTER(RtcResize), C.POINTER(U32), C.POINTER(U32), C.POINTER(U32)]),
 }
+
+# The scene loaders (include/rtc.h): one common argument list per family, then the entry's own out-arguments. Each `_file`
+# twin takes a path where the text entry takes the text: the same list by construction.
+P = C.POINTER
+
+
+def _loader(lights, capped=True, lua=False, extra=()):
+    return ([C.c_char_p] + ([U32] if lua else []) + [P(P(RtcShape)), P(U32), P(lights)] + ([U32, P(U32)] if capped else []) + [P(RtcCamera)]
+            + ([C.c_char_p, C.c_size_t, P(U32)] if lua else []) + [C.c_char_p, C.c_size_t] + list(extra))
+
+
+def _record(ctype):  # an optional record and its "the camera has the keys" flag
+    return [P(ctype), P(U32)]
+
+
+_LENS, _AO = _record(RtcLens), _record(RtcAo)
+_YAML_EXTRA = {  # entry -> what follows errbuf_len
+    "lens": _LENS, "motion": _LENS + [P(P(RtcMotion)), P(U32), P(U32)], "projection": _LENS + _record(RtcProjection), "ao": _LENS + _AO,
+    "gather": _LENS + _AO + _AO, "filter": _LENS + _AO + _AO + _record(RtcFilter), "adaptive": _record(RtcAdaptive),
+    "post": _record(RtcTonemap) + _record(RtcBloom), "resize": _LENS + _record(RtcProjection) + [P(RtcResize), P(U32), P(U32), P(U32)],
+}
+_LOADERS = {"rtc_scene_load_yaml": _loader(RtcLight, capped=False), "rtc_scene_load_yaml_lights": _loader(RtcLight),
+            "rtc_scene_load_yaml_area_lights": _loader(RtcAreaLight),
+            **{"rtc_scene_load_yaml_" + entry: _loader(RtcAreaLight, extra=extra) for entry, extra in _YAML_EXTRA.items()},
+            "rtc_scene_load_lua": _loader(RtcLight, capped=False, lua=True), "rtc_scene_load_lua_lights": _loader(RtcLight, lua=True),
+            "rtc_scene_load_lua_area_lights": _loader(RtcAreaLight, lua=True)}
+for _name, _args in _LOADERS.items():
+    PROTOTYPES[_name] = PROTOTYPES[_name + "_file"] = (C.c_int32, _args)
 
 
 def declare(lib: C.CDLL) -> None:

@@ -2232,11 +2232,30 @@ const char *rtc_lua_program_output(const rtc_lua_program *prog) { return prog ? 
 
 void rtc_lua_program_free(rtc_lua_program *prog) { delete prog; }
 
-// The single-scene form: run the script, hand out one of its jobs as malloc'ed arrays.
-// lights_cap == 0: the single-light form, *light_out = lights[1]. area_out (instead of light_out): every light as an rtc_area_light
-static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *light_out,
-                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len,
-                           rtc_area_light *area_out = nullptr) {
+// Where a rtc_scene_load_lua* entry wants the lights. Every entry fills the fields it has, by name.
+struct LightsWanted {
+    rtc_light *point = nullptr;     // exactly one of these two: point lights (a world with an area light is refused) ...
+    rtc_area_light *area = nullptr; // ... or every light as an rtc_area_light
+    bool first_only = false;        // the single-light form: *point = lights[1], no cap and no count
+    uint32_t cap = 0;
+    uint32_t *n_out = nullptr;
+};
+
+// The single-scene form, behind all six entries: run the script (`source`: its text, or its path), hand out one of its jobs
+// as malloc'ed arrays. An RTC_ERR_ARG from the pointer checks writes nothing at all.
+static rtc_status load_lua(const char *source, bool is_path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
+                           rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len,
+                           const LightsWanted &lights) {
+    if (!source || !shapes_out || !n_out || (!lights.point && !lights.area) || !camera_out) return RTC_ERR_ARG;
+    if (!lights.first_only && (!lights.cap || !lights.n_out)) return RTC_ERR_ARG;
+    *shapes_out = nullptr;
+    *n_out = 0;
+    if (!lights.first_only) *lights.n_out = 0;
+    if (renders_out) *renders_out = 0;
+    if (outfile && outfile_len) outfile[0] = 0;
+    rtc_lua_program *prog = nullptr;
+    const rtc_status run = is_path ? rtc_lua_run_file(source, 0, &prog, errbuf, errbuf_len) : rtc_lua_run(source, nullptr, 0, &prog, errbuf, errbuf_len);
+    if (run != RTC_OK) return run;
     std::unique_ptr<rtc_lua_program> own(prog);
     Interp &in = prog->in;
     try {
@@ -2250,23 +2269,23 @@ static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_sha
             fail(0, "the script calls Render / AddFrame " + std::to_string(in.jobs.size()) + " time(s)");
         }
         const Job &j = in.jobs[render_index];
-        if (outfile && outfile_len) std::snprintf(outfile, outfile_len, "%s", j.outfile.c_str());
-        if (j.scene->any_area && !area_out) fail(j.line, "the world has an area light: load it with rtc_scene_load_lua_area_lights");
-        if (lights_cap && j.scene->lights.size() > lights_cap) return RTC_ERR_ARG;
+        if (outfile && outfile_len) std::snprintf(outfile, outfile_len, "%s", j.outfile.c_str()); // (truncated to outfile_len; before the refusals)
+        if (j.scene->any_area && !lights.area) fail(j.line, "the world has an area light: load it with rtc_scene_load_lua_area_lights");
+        if (!lights.first_only && j.scene->lights.size() > lights.cap) return RTC_ERR_ARG; // (no message)
         const size_t count = j.scene->shapes.size();
         rtc_shape *arr = static_cast<rtc_shape *>(std::malloc(sizeof(rtc_shape) * (count ? count : 1)));
         if (!arr) return RTC_ERR_NOMEM;
         if (count) std::memcpy(arr, j.scene->shapes.data(), sizeof(rtc_shape) * count);
         *shapes_out = arr;
         *n_out = static_cast<uint32_t>(count);
-        if (lights_cap) {
-            for (size_t i = 0; i < j.scene->lights.size(); ++i) {
-                if (area_out) area_out[i] = j.scene->lights[i];
-                else light_out[i] = point_of(j.scene->lights[i]);
-            }
-            *n_lights_out = static_cast<uint32_t>(j.scene->lights.size());
+        if (lights.first_only) {
+            *lights.point = j.scene->light;
         } else {
-            *light_out = j.scene->light;
+            for (size_t i = 0; i < j.scene->lights.size(); ++i) {
+                if (lights.area) lights.area[i] = j.scene->lights[i];
+                else lights.point[i] = point_of(j.scene->lights[i]);
+            }
+            *lights.n_out = static_cast<uint32_t>(j.scene->lights.size());
         }
         *camera_out = j.camera;
         return RTC_OK;
@@ -2278,94 +2297,62 @@ static rtc_status load_one(rtc_lua_program *prog, uint32_t render_index, rtc_sha
     }
 }
 
+static LightsWanted first_light(rtc_light *light_out) {
+    LightsWanted l;
+    l.point = light_out;
+    l.first_only = true;
+    return l;
+}
+
+static LightsWanted every_light(uint32_t lights_cap, uint32_t *n_lights_out) { // the caller adds where they go: `point` or `area`
+    LightsWanted l;
+    l.cap = lights_cap;
+    l.n_out = n_lights_out;
+    return l;
+}
+
 rtc_status rtc_scene_load_lua(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *light_out,
                               rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf,
                               size_t errbuf_len) {
-    if (!text || !shapes_out || !n_out || !light_out || !camera_out) return RTC_ERR_ARG;
-    *shapes_out = nullptr;
-    *n_out = 0;
-    if (renders_out) *renders_out = 0;
-    if (outfile && outfile_len) outfile[0] = 0;
-    rtc_lua_program *prog = nullptr;
-    const rtc_status st = rtc_lua_run(text, nullptr, 0, &prog, errbuf, errbuf_len);
-    if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, light_out, 0u, nullptr, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+    return load_lua(text, false, render_index, shapes_out, n_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len, first_light(light_out));
 }
 
 rtc_status rtc_scene_load_lua_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *light_out,
                                    rtc_camera *camera_out, char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf,
                                    size_t errbuf_len) {
-    if (!path || !shapes_out || !n_out || !light_out || !camera_out) return RTC_ERR_ARG;
-    *shapes_out = nullptr;
-    *n_out = 0;
-    if (renders_out) *renders_out = 0;
-    if (outfile && outfile_len) outfile[0] = 0;
-    rtc_lua_program *prog = nullptr;
-    const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
-    if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, light_out, 0u, nullptr, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+    return load_lua(path, true, render_index, shapes_out, n_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len, first_light(light_out));
 }
 
 rtc_status rtc_scene_load_lua_lights(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out,
                                      uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len,
                                      uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
-    if (!text || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
-    *shapes_out = nullptr;
-    *n_out = 0;
-    *n_lights_out = 0;
-    if (renders_out) *renders_out = 0;
-    if (outfile && outfile_len) outfile[0] = 0;
-    rtc_lua_program *prog = nullptr;
-    const rtc_status st = rtc_lua_run(text, nullptr, 0, &prog, errbuf, errbuf_len);
-    if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+    LightsWanted l = every_light(lights_cap, n_lights_out);
+    l.point = lights_out;
+    return load_lua(text, false, render_index, shapes_out, n_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len, l);
 }
 
 rtc_status rtc_scene_load_lua_lights_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out, rtc_light *lights_out,
                                           uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *outfile, size_t outfile_len,
                                           uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
-    if (!path || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
-    *shapes_out = nullptr;
-    *n_out = 0;
-    *n_lights_out = 0;
-    if (renders_out) *renders_out = 0;
-    if (outfile && outfile_len) outfile[0] = 0;
-    rtc_lua_program *prog = nullptr;
-    const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
-    if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len);
+    LightsWanted l = every_light(lights_cap, n_lights_out);
+    l.point = lights_out;
+    return load_lua(path, true, render_index, shapes_out, n_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len, l);
 }
 
 rtc_status rtc_scene_load_lua_area_lights(const char *text, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
                                           rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out,
                                           char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
-    if (!text || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
-    *shapes_out = nullptr;
-    *n_out = 0;
-    *n_lights_out = 0;
-    if (renders_out) *renders_out = 0;
-    if (outfile && outfile_len) outfile[0] = 0;
-    rtc_lua_program *prog = nullptr;
-    const rtc_status st = rtc_lua_run(text, nullptr, 0, &prog, errbuf, errbuf_len);
-    if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len,
-                    lights_out);
+    LightsWanted l = every_light(lights_cap, n_lights_out);
+    l.area = lights_out;
+    return load_lua(text, false, render_index, shapes_out, n_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len, l);
 }
 
 rtc_status rtc_scene_load_lua_area_lights_file(const char *path, uint32_t render_index, rtc_shape **shapes_out, uint32_t *n_out,
                                                rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out,
                                                char *outfile, size_t outfile_len, uint32_t *renders_out, char *errbuf, size_t errbuf_len) {
-    if (!path || !shapes_out || !n_out || !lights_out || !lights_cap || !n_lights_out || !camera_out) return RTC_ERR_ARG;
-    *shapes_out = nullptr;
-    *n_out = 0;
-    *n_lights_out = 0;
-    if (renders_out) *renders_out = 0;
-    if (outfile && outfile_len) outfile[0] = 0;
-    rtc_lua_program *prog = nullptr;
-    const rtc_status st = rtc_lua_run_file(path, 0, &prog, errbuf, errbuf_len);
-    if (st != RTC_OK) return st;
-    return load_one(prog, render_index, shapes_out, n_out, nullptr, lights_cap, n_lights_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len,
-                    lights_out);
+    LightsWanted l = every_light(lights_cap, n_lights_out);
+    l.area = lights_out;
+    return load_lua(path, true, render_index, shapes_out, n_out, camera_out, outfile, outfile_len, renders_out, errbuf, errbuf_len, l);
 }
 
 } // extern "C"

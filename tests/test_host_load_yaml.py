@@ -1,40 +1,9 @@
 """The six load_yaml* functions of the package over their one private loader: each one's return tuple, the name its errors
-carry, and that `path` loads what `text` loads. The keys themselves are pinned by the test_host_* file of each feature. No GPU."""
+carry, and that `path` loads what `text` loads. The keys themselves are pinned by the test_host_* file of each feature; what
+every entry point of the library answers for the corpus of tests/yaml_loader_cases.py is pinned by a recorded file. No GPU."""
 import pytest
 
-SCENE = """
-- add: camera
-  width: 40
-  height: 30
-  field-of-view: 0.8
-  from: [0, 2, -6]
-  to: [0, 1, 0]
-  up: [0, 1, 0]
-%s
-- add: light
-  at: [-5, 8, -5]
-  intensity: [1, 1, 1]
-- add: light
-  at: [5, 8, -5]
-  intensity: [0.5, 0.5, 0.5]
-- add: sphere
-  transform:
-    - [translate, 0, 1, 0]
-%s
-- add: plane
-"""
-LENS = "  aperture: 0.1\n  focal-distance: 7\n"
-MOTION = "  motion:\n    - [translate, 1, 0, 0]"
-
-# function -> (the name its errors carry, the camera keys of the scene it is given, what follows (World, camera) in its tuple)
-LOADERS = {
-    "load_yaml": ("rtc_scene_load_yaml", "", ()),
-    "load_yaml_lens": ("rtc_scene_load_yaml_lens", LENS, ("lens",)),
-    "load_yaml_ao": ("rtc_scene_load_yaml_ao", LENS + "  ao-radius: 0.75", ("lens", "ao")),
-    "load_yaml_gather": ("rtc_scene_load_yaml_gather", LENS + "  ao-radius: 0.75\n  gather-radius: 2", ("lens", "ao", "gather")),
-    "load_yaml_projection": ("rtc_scene_load_yaml_projection", "  projection: orthographic\n  ortho-width: 4", ("no lens", "projection")),
-    "load_yaml_motion": ("rtc_scene_load_yaml_motion", LENS + "  shutter-samples: 3", ("lens", "motions", "samples")),
-}
+from yaml_loader_cases import GOLDEN, LOADERS, MOTION, SCENE, parse, run_corpus, serialize
 
 
 def _describe(rtc, name, result):
@@ -82,3 +51,20 @@ def test_tuple_path_and_error_name(rtc, name, tmp_path):
         with pytest.raises(rtc.RtcError) as e:
             load(**kwargs)
         assert e.value.status != 0 and str(e.value).startswith(where + ": ") and detail in str(e.value), (name, str(e.value))
+
+
+def test_recorded_corpus_through_every_entry_point(rtc, tmp_path):
+    """Every document of tests/yaml_loader_cases.py through the 24 YAML and the 6 Lua entry points of rtc.lib(): status,
+    message and a hash of every out-argument (buffers filled with 0xA5 before the call), against the answers recorded from
+    the loader as it stood before its entry points shared one request record (tests/golden/scene_loader_results.txt)."""
+    import sys
+    want = parse(GOLDEN.read_text())
+    got = run_corpus(rtc.lib(), sys.modules[rtc.__name__ + ".abi"], tmp_path)
+    assert [name for name, _ in got] == list(want), "the corpus itself changed: its documents are not the recorded ones"
+    calls = [answer for _, rows in got for _, answer in rows]
+    # most of the equality would be vacuous if the corpus were mostly refused, or mostly accepted
+    assert 3 * sum(st == 0 for st, _, _ in calls) >= len(calls) and 3 * sum(st == 5 for st, _, _ in calls) >= len(calls)
+    differ = [f"{name!r} through {fn}: (status, message, hash) {answer}, recorded {rec}"
+              for name, rows in got for (fn, answer), rec in zip(rows, want[name]) if answer != rec]
+    assert not differ and all(len(rows) == len(want[name]) for name, rows in got), f"{len(differ)} calls differ:\n" + "\n".join(differ[:20])
+    assert serialize(got) == GOLDEN.read_text()
