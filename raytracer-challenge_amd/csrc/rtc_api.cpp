@@ -26,7 +26,7 @@
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
                                        const DevLightTable *lt, const DevLens *lens, const DevProjection *proj, int one_sample,
-                                       int whole_tiles);
+                                       int whole_tiles, int uniform_shade);
 extern "C" hipError_t rtc_launch_prep(const DevIsect *isect, DevPrim *prim, uint32_t n, const double vinv[12],
                                       hipStream_t stream);
 extern "C" hipError_t rtc_launch_arith(uint32_t op, const double *a, const double *b, uint32_t n, double *out,
@@ -545,6 +545,7 @@ rtc_status rtc_context_create(int32_t device, void *stream, rtc_context **out) {
     if (const char *e = std::getenv("RTC_BIN_SORT")) ctx->bin_sort = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_ONE_SAMPLE")) ctx->one_sample = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_WHOLE_TILES")) ctx->whole_tiles = std::atoi(e) != 0;
+    if (const char *e = std::getenv("RTC_UNIFORM_SHADE")) ctx->uniform_shade = std::atoi(e) != 0;
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS")) ctx->bin_small_pixels = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("RTC_BIN_SMALL_PIXELS_PIPELINED")) ctx->bin_small_pixels_pipelined = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("RTC_TILES_PER_WG")) {
@@ -1144,7 +1145,7 @@ static void planned_params(const rtc_context *ctx, const rtc_world *w, const rtc
 static hipError_t trace_planned(const rtc_context *ctx, const RenderParams &P, const LaunchPlan &plan, const LaunchLights &LL, hipStream_t stream,
                                 hipEvent_t e0, hipEvent_t e1, const DevLens *lens, const DevProjection *proj) {
     return rtc_launch_trace(&P, plan.src, (int)plan.refl, (int)plan.refr, plan.grid_wgs, plan.lds_bytes, stream, e0, e1, LL.xl, LL.lt, lens,
-                            proj, ctx->one_sample ? 1 : 0, ctx->whole_tiles ? 1 : 0);
+                            proj, ctx->one_sample ? 1 : 0, ctx->whole_tiles ? 1 : 0, ctx->uniform_shade ? 1 : 0);
 }
 
 // The panorama tables of (cam, proj) in the context's two buffers (include/rtc.h: rtc_projection_tables, keyed by size and

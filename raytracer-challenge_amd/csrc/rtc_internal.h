@@ -104,6 +104,7 @@ struct rtc_context {
     bool bin_sort = true;
     bool one_sample = true; // RTC_ONE_SAMPLE=0: launches of cameras with samples == 1 take the generic render kernel (A/B, parity tests)
     bool whole_tiles = true; // RTC_WHOLE_TILES=0: no launch takes the whole-tile render kernels (A/B, parity tests); RTC_ONE_SAMPLE=0 implies it
+    bool uniform_shade = true; // RTC_UNIFORM_SHADE=0: the flat one-sample kernels shade every tile per lane, one-object tiles too (A/B, parity tests)
     // one-level worlds (<= 256 objects) are binned only in launches of at least this many views (RTC_BIN_SMALL_VIEWS): the
     // binning kernels run on the side stream beside the previous launch's render, which hides them when launches follow each
     // other (north star, 8 views per launch: 0.0745 -> 0.0685 ms per frame; 4 views: 0.0732 -> 0.0704; C4 1.48 -> 1.42;

@@ -273,7 +273,7 @@ template <class P> DEVI V3 xvector(P m, V3 v) {
               m[8] * v.x + m[9] * v.y + m[10] * v.z);
 }
 // transform_vector with a packed 3x3
-DEVI V3 xvector3(const double *m, V3 v) {
+template <class P> DEVI V3 xvector3(P m, V3 v) {
     return mk(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z,
               m[6] * v.x + m[7] * v.y + m[8] * v.z);
 }
@@ -1044,7 +1044,10 @@ template <bool WAVE_NORM = false> DEVI V3 shape_normal(const DevShade *S, const 
 // DevShade::kind's load) and, GROUPED, with the two records a sphere's or a cube's normal reads — rows 0..2 of the inverse and
 // DevShade::nt, both at addresses the hit index alone decides — requested together, ahead of the arithmetic (SC_NORMAL). The
 // operations and their operands are shape_normal's.
-template <bool WAVE_NORM, bool GROUPED> DEVI V3 shape_normal_of(uint32_t kind, const DevShade *S, const double *m_obj, V3 point) {
+// SP, MP: the two records' pointer types — per-lane global pointers, or the constant address space's for a tile whose hit lanes
+// all name one object (trace_uniform_shade): `kind` is then wave-uniform too, the switch is a scalar branch and the records
+// arrive in SGPRs.
+template <bool WAVE_NORM, bool GROUPED, class SP, class MP> DEVI V3 shape_normal_of(uint32_t kind, SP S, MP m_obj, V3 point) {
     if (kind == RTC_PLANE) return mk(S->plane_n[0], S->plane_n[1], S->plane_n[2]);
     double mi[12], nt[9];
     if constexpr (GROUPED) {
@@ -1119,7 +1122,7 @@ template <bool BARE> struct AnyHitT {
 using AnyHit = AnyHitT<false>;
 
 // ---- patterns (material.rs:41-45 and the six pattern_at bodies) --------------------------
-template <bool BARE = false> DEVI V3 pattern_color(const DevShade *S, const double *m_obj, V3 world_point) {
+template <bool BARE = false, class SP, class MP> DEVI V3 pattern_color(SP S, MP m_obj, V3 world_point) {
     const V3 op = xpoint(m_obj, world_point);
     const V3 pp = xpoint(S->pat_inv, op);
     const V3 a = mk(S->pat_a[0], S->pat_a[1], S->pat_a[2]);
@@ -1141,8 +1144,10 @@ template <bool BARE = false> DEVI V3 pattern_color(const DevShade *S, const doub
 
 // Material::lighting material.rs:319-361. lightv = (light.position - point).normalize() is
 // the shadow ray's direction (same expression, shape.rs:717-719), passed in.
-template <bool BARE = false, class PP>
-DEVI V3 lighting(const PP &P, const DevShade *S, const double *m_obj, V3 point, V3 eyev, V3 normal,
+// SP, MP: as shape_normal_of's — with the constant address space's pointers the material's scalars and the pattern record are
+// scalar operands and the pattern switch is a scalar branch.
+template <bool BARE = false, class PP, class SP, class MP>
+DEVI V3 lighting(const PP &P, SP S, MP m_obj, V3 point, V3 eyev, V3 normal,
                  V3 lightv, bool in_shadow) {
     // The reference's statement order is effective_color, lightv, ambient, [shadow?] light_dot_normal,
     // diffuse, reflectv, reflect_dot_eye, factor, specular. The values do not depend on that order
@@ -1288,6 +1293,29 @@ enum { SC_ROWS = 1, SC_LOOKUP = 2, SC_UNBOUNDED = 4, SC_WALK = 8, SC_KIND = 16, 
 constexpr bool trace_short_chains(int item, int src, bool refl, bool one, bool multi) {
     return (RTC_SHORT_CHAINS & item) != 0 && src == SRC_CULL && !refl && one && !multi;
 }
+// One-object tiles shaded from scalar registers in the flat one-sample k_trace kernels. After the closest-hit pass a wave
+// asks whether every lane that hit something hit the SAME object (one ballot, one lane read, one compare; lanes that hit
+// nothing do not count). If so, the hit's DevShade and the rows of its inverse are read through the constant address space at
+// that wave-uniform index — scalar loads into SGPRs, scalar operands of the VALU, scalar branches on the kind and the pattern —
+// by the very functions the per-lane path calls (shape_normal_of, lighting, pattern_color, instantiated for the other pointer
+// type): the operations, their order and their operands' values are the same, only where an operand comes from differs. Mixed
+// tiles take the per-lane path as before. A mask, 0 = the code as it was in every kernel (kept for the A/B):
+//   1  SRC_CULL's flat one-sample kernels, one light (trace_short_chains' family: whole-tile, one-sample, its RGBA form)
+//   2  SRC_CULL2's flat one-sample kernel, one light
+// The run-time switch RTC_UNIFORM_SHADE=0 sends a launch to an instantiation without the path (DevPerLaneShade), as
+// RTC_ONE_SAMPLE=0 sends it to the generic kernel: the host's choice, no branch per tile.
+#ifndef RTC_UNIFORM_SHADE
+#define RTC_UNIFORM_SHADE 3
+#endif
+constexpr bool trace_uniform_shade(int src, bool refl, bool one, bool multi) {
+    return (((RTC_UNIFORM_SHADE & 1) != 0 && src == SRC_CULL) || ((RTC_UNIFORM_SHADE & 2) != 0 && src == SRC_CULL2)) && !refl && one && !multi;
+}
+// k_trace's trailing argument of the instantiations RTC_UNIFORM_SHADE=0 selects: a tag, nothing is read from it.
+struct DevPerLaneShade {
+    uint32_t unused;
+};
+typedef const __attribute__((address_space(4))) DevShade *ConstShade;
+typedef const __attribute__((address_space(4))) double *ConstDoubles;
 
 // One suspended shade_hit call (shape.rs:685-700) on a lane's stack. The stack lives in scratch
 // (dynamic index), so its size is HBM/L2 traffic: Worlds without transparent materials (REFR ==
@@ -1403,7 +1431,9 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
     constexpr bool LENS = has_lens_v<XL...>;
     constexpr bool PROJ = has_projection_v<XL...>;
     constexpr bool ALT = LENS || PROJ; // primary rays that are not the pinhole's: whatever assumes the camera origin is compiled out
-    constexpr bool MULTI = sizeof...(XL) - (ALT ? 1 : 0) != 0;
+    constexpr bool PER_LANE = (false || ... || __is_same(XL, DevPerLaneShade)); // RTC_UNIFORM_SHADE=0's instantiation: the tag alone
+    constexpr bool MULTI = sizeof...(XL) - (ALT ? 1 : 0) - (PER_LANE ? 1 : 0) != 0;
+    static_assert(!PER_LANE || (sizeof...(XL) == 1 && trace_uniform_shade(SRC, REFL, ONE, false)), "the per-lane twin of a kernel that has the uniform path");
     static_assert(!(LENS && PROJ), "a lens or a projection, never both");
     static_assert(sizeof...(XL) <= (ALT ? 2 : 1), "at most one block of further lights, then at most one lens or projection");
     static_assert(!ALT || ((SRC == SRC_SMEM || IS_CULL(SRC)) && !PROBE && !RGBA), "lens and projection launches take SRC_SMEM, SRC_CULL or SRC_CULL2, f64 / RGB output");
@@ -1884,9 +1914,29 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             bool inside = false;
             const DevShade *S = T.shade + (hit ? hidx : 0);
             const double *m_obj = T.isect[hit ? hidx : 0].m;
+            // trace_uniform_shade's test, where `hit` and `hidx` are final: does every lane that hit something name the object
+            // the lowest hit lane names? Then `u_obj` is that object, else — and for a tile without a hit, where nothing is
+            // shaded — NOT_UNIFORM, which is no object's index (the tables hold fewer than 2^31 objects: hidx is an int).
+            constexpr bool UNIFORM_SHADE = !PER_LANE && trace_uniform_shade(SRC, REFL, ONE, MULTI);
+            constexpr uint32_t NOT_UNIFORM = 0xffffffffu;
+            uint32_t u_obj = NOT_UNIFORM, u_lane = 0u; // wave-uniform
+            if constexpr (UNIFORM_SHADE) {
+                const unsigned long long hit_mask = ballot(hit);
+                if (hit_mask != 0ull) {
+                    u_lane = (uint32_t)__builtin_ctzll(hit_mask);
+                    const uint32_t named = (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane(hidx, (int)u_lane));
+                    if (ballot(hit && hidx != (int)named) == 0ull) u_obj = named;
+                }
+            }
             if (hit) {
                 point = vadd(ro, vmul(rd, best)); // Ray::position vec.rs:207-209
                 eyev = vneg(rd);
+                if (UNIFORM_SHADE && u_obj != NOT_UNIFORM) { // (wave-uniform) the kind, then plane_n or the inverse's rows and nt: scalar loads
+                    const ConstShade Su = (ConstShade)(T.shade + u_obj);
+                    const ConstDoubles mu = (ConstDoubles)T.isect[u_obj].m;
+                    const uint32_t ukind = (CARRY_KIND && use_bins) ? (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane(hroot, (int)u_lane)) >> 1 : Su->kind;
+                    normal = shape_normal_of<trace_wave_normalize(4, SRC, REFL, PROBE, ALT, MULTI), trace_short_chains(SC_NORMAL, SRC, REFL, ONE, MULTI)>(ukind, Su, mu, point);
+                } else // (a mixed tile, and every kernel without the path: per lane)
                 if constexpr (CARRY_KIND || trace_short_chains(SC_NORMAL, SRC, REFL, ONE, MULTI)) {
                     const uint32_t nkind = (CARRY_KIND && use_bins) ? (uint32_t)hroot >> 1 : S->kind; // (use_bins is wave-uniform)
                     normal = shape_normal_of<trace_wave_normalize(4, SRC, REFL, PROBE, ALT, MULTI), trace_short_chains(SC_NORMAL, SRC, REFL, ONE, MULTI)>(nkind, S, m_obj, point);
@@ -2224,7 +2274,15 @@ k_trace(const RenderParams P_arg, const DevIsect *__restrict__ t_isect, const ui
             } else if (hit) {
                 V3 surface;
                 if constexpr (MULTI) surface = surface_all;
-                else surface = lighting<BARE_RING>(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
+                else if (UNIFORM_SHADE && u_obj != NOT_UNIFORM) { // (wave-uniform) the material's scalars and the pattern record: scalar loads
+                    // (the index as operand of an empty statement: the loads at the addresses made from it start here, below
+                    // the shadow pass, as the fence above keeps the per-lane ones — nothing of the normal's records is held across it)
+                    uint32_t u_here = u_obj;
+                    asm volatile("" : "+s"(u_here));
+                    const ConstShade Su = (ConstShade)(T.shade + u_here);
+                    const ConstDoubles mu = (ConstDoubles)T.isect[u_here].m;
+                    surface = lighting<BARE_RING>(KP(P_arg), Su, mu, over, eyev, normal, sdir, shadowed);
+                } else surface = lighting<BARE_RING>(KP(P_arg), S, m_obj, over, eyev, normal, sdir, shadowed);
                 bool want_refl = false, want_refr = false;
                 V3 fr_o = mk(0, 0, 0), fr_d = mk(0, 0, 0);
                 if constexpr (REFL) want_refl = (rem != 0) && !(m_kr <= 0.); // reflected_color shape.rs:730 (NaN: cast)
@@ -3607,12 +3665,25 @@ extern "C" int rtc_debug_whole_tile_launch(const WholeTileQuery *q) {
 // `one_sample`: a render launch of a camera with samples == 1 takes the one-sample instantiation (ONE), which exists for the
 // product sources SRC_CULL and SRC_CULL2 only; the measurement-only sources keep the generic kernel.
 // `whole_tiles`: such a launch of one light for which whole_tile_launch holds takes the whole-tile instantiation (WHOLE) on top.
+// `uniform_shade`: false sends a launch whose kernel has the uniform shading path (trace_uniform_shade) to that kernel's
+// per-lane twin, the same template with DevPerLaneShade as its trailing argument.
 template <int SRC, bool REFL, bool REFR, class... XL>
-static hipError_t launch_one(const RenderParams &P, bool one_sample, bool whole_tiles, dim3 grid, size_t lds_bytes, hipStream_t stream,
-                             hipEvent_t e0, hipEvent_t e1, const XL &...xl) {
+static hipError_t launch_one(const RenderParams &P, bool one_sample, bool whole_tiles, bool uniform_shade, dim3 grid, size_t lds_bytes,
+                             hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const XL &...xl) {
     if (P.rays != nullptr) return launch_kernel<SRC, REFL, REFR, true, false, false>(P, grid, lds_bytes, stream, e0, e1, xl...);
     if constexpr (IS_CULL(SRC)) {
         if (one_sample && P.samples == 1u) {
+            if constexpr (trace_uniform_shade(SRC, REFL, true, sizeof...(XL) != 0)) {
+                if (!uniform_shade) {
+                    const DevPerLaneShade tag{0u};
+                    if constexpr (whole_tile_kernel(SRC, REFL)) {
+                        if (whole_tiles && whole_tile_launch(P, SRC, REFL, REFR, false))
+                            return launch_kernel<SRC, REFL, REFR, false, false, true, true>(P, grid, lds_bytes, stream, e0, e1, tag);
+                    }
+                    if (P.gamma != nullptr) return launch_kernel<SRC, REFL, REFR, false, true, true>(P, grid, lds_bytes, stream, e0, e1, tag);
+                    return launch_kernel<SRC, REFL, REFR, false, false, true>(P, grid, lds_bytes, stream, e0, e1, tag);
+                }
+            }
             if constexpr (sizeof...(XL) == 0 && whole_tile_kernel(SRC, REFL)) {
                 if (whole_tiles && whole_tile_launch(P, SRC, REFL, REFR, false))
                     return launch_kernel<SRC, REFL, REFR, false, false, true, true>(P, grid, lds_bytes, stream, e0, e1);
@@ -3633,10 +3704,11 @@ static hipError_t launch_one(const RenderParams &P, bool one_sample, bool whole_
 // RTC_ONE_SAMPLE switch); zero keeps every launch on the generic kernel.
 // `whole_tiles`: non-zero lets such a launch take the whole-tile instantiation where it qualifies (whole_tile_launch; the
 // context's RTC_WHOLE_TILES switch); zero, or one_sample zero, keeps every launch on the kernels it had without the flavour.
+// `uniform_shade`: zero keeps every launch off the uniform shading path (the context's RTC_UNIFORM_SHADE switch).
 extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl, int refr, uint32_t nblocks,
                                        size_t lds_bytes, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const DevExtraLights *xl,
                                        const DevLightTable *lt, const DevLens *lens, const DevProjection *proj, int one_sample,
-                                       int whole_tiles) {
+                                       int whole_tiles, int uniform_shade) {
     const dim3 grid(nblocks);
     // the recursion flavour: refractive Worlds carry the full frame stack, reflective ones the LDS stack, the others none
     auto with_depth = [&](auto &&launch) {
@@ -3663,7 +3735,7 @@ extern "C" hipError_t rtc_launch_trace(const RenderParams *P, int src, int refl,
             });
         }
         auto flavours = [&](auto S) {
-            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, one_sample != 0, whole_tiles != 0, grid, lds_bytes, stream, e0, e1, x...); });
+            return with_depth([&](auto RL, auto RR) { return launch_one<S(), RL(), RR()>(*P, one_sample != 0, whole_tiles != 0, uniform_shade != 0, grid, lds_bytes, stream, e0, e1, x...); });
         };
         // the LDS-staged sources exist for one-light pinhole launches only
         if constexpr (sizeof...(x) == 0) return with_src<SRC_SMEM, SRC_LDS1, SRC_LDSN, SRC_CULL, SRC_CULL2>(src, flavours);

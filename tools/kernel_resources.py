@@ -51,6 +51,8 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         tag += ",whole" if m.group(7) == "1" else ""  # the whole-tile flavour on top of it (one camera, whole tiles, f64 output)
         # the instantiations for Worlds with several lights: in the kernel arguments, or in the World's device table
         tag += ",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else ""
+        # the per-lane twin of a kernel with the uniform shading path (RTC_UNIFORM_SHADE=0 at run time)
+        tag += ",perlane" if "DevPerLaneShade" in name else ""
         # the thin-lens flavour (rtc_render_lens*) and the projection flavour (rtc_render_projection*)
         tag += ",lens>" if "DevLens" in name else ",proj>" if "DevProjection" in name else ">"
     elif (a := re.search(r"k_aovILi(\d)ELb(\d)E", name)):  # the AOV kernel: source, shadow passes, where the further lights come from
