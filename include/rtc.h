@@ -1518,6 +1518,43 @@ rtc_status  rtc_scene_load_yaml_gather_file(const char *path, rtc_shape **shapes
                                             struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
                                             rtc_ao *gather_out, uint32_t *has_gather_out);
 
+/* ==== the three passes under an orthographic or panorama camera ======================== */
+/* rtc_render_aov*, rtc_render_ao* and rtc_render_gather* with the rays of a projection (rtc_projection, above) in place of
+ * the pinhole's centre rays: each entry has its pinhole twin's signature with `proj` after `cam`, and everything the twin's
+ * text says holds with ONE substitution — the pixel's ray. Normative:
+ *   - the ray of pixel (x, y) is rtc_projection_ray(cam, proj, x, y); Hit is World::intersect + get_hit of that ray with
+ *     Intersection::compute_vectors, as rtc_color_at reports it; the AOV planes are rtc_aov_from_hits of those records, the
+ *     gather planes rtc_gather_from_hits;
+ *   - the fan of the AO and gather passes is rtc_ao_ray about that Hit (its over_point, its flipped normal);
+ *   - `depth` is t along the UNIT direction. For an orthographic ray that is the distance from the camera's z = 0 plane,
+ *     where the ray starts — not from a point. The plane may cut a surface: the rays that start inside it hit it from
+ *     inside (flags bit 1, the normal flipped), and what lies wholly behind the plane is not seen;
+ *   - modes, flags, NULL planes, Worlds and ordering: the twin's. RTC_FLAG_NO_CULL gives the same bytes;
+ *     RTC_FLAG_LDS_TABLE answers what it answers the twin.
+ * Arguments are checked in this order: rtc_render_projection's checks first — a NULL context, World, camera or output, a
+ * World of another context, a mode that does not exist, a canvas without pixels; then a NULL or invalid projection
+ * (rtc_projection_validate) and cam->samples != 1 — then the pinhole pass's own (all planes NULL, an invalid rtc_ao, a
+ * misaligned device pointer). Each of them is RTC_ERR_ARG, and nothing has been launched.
+ * The launches stay uncounted in rtc_stats, as the twins'. rtc_context_last_launch_projection reports the kind after them
+ * and rtc_context_last_launch_info the object loop (source) they took; a pinhole pass leaves both records alone.
+ * A panorama's tables are rtc_render_projection's: the same two buffers under the same key, so a colour launch and a pass of
+ * one panorama size upload them once, and a change of key waits for every stream of the context first.
+ * Kernels: the projection instantiations of k_aov, k_ao and k_gather (a trailing DevProjection; csrc/rtc_kernels.hip). A
+ * panorama tile's primary bundle has the camera origin as its shared apex (two-level Worlds: the ordered walk with early
+ * stop); an orthographic tile's has its apex at one lane's origin and its spread measured, and every candidate is visited. */
+rtc_status  rtc_render_aov_projection_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                             uint32_t mode, uint32_t flags, const rtc_aov_buffers *d);
+rtc_status  rtc_render_aov_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                      uint32_t mode, uint32_t flags, const rtc_aov_buffers *host);
+rtc_status  rtc_render_ao_projection_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                            const rtc_ao *ao, uint32_t mode, uint32_t flags, uint16_t *d_ao);
+rtc_status  rtc_render_ao_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                     const rtc_ao *ao, uint32_t mode, uint32_t flags, uint16_t *ao_out);
+rtc_status  rtc_render_gather_projection_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                                const rtc_ao *ao, uint32_t mode, uint32_t flags, const rtc_gather_buffers *d);
+rtc_status  rtc_render_gather_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                         const rtc_ao *ao, uint32_t mode, uint32_t flags, const rtc_gather_buffers *host);
+
 /* ==== float files: the f64 canvas and the AOV planes saved as data ==================== */
 /* Every writer above takes Color::scale'd 8-bit rows: components above 1.0 are clipped and a depth plane becomes a picture.
  * These three keep the numbers. Input: the f64 canvas, `rgb` = height*width*3 doubles, top row first (what rtc_render,
@@ -1690,6 +1727,26 @@ rtc_status  rtc_scene_load_yaml_filter_file(const char *path, rtc_shape **shapes
                                             rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
                                             struct rtc_lens *lens_out, uint32_t *has_lens_out, rtc_ao *ao_out, uint32_t *has_ao_out,
                                             rtc_ao *gather_out, uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out);
+/* Scenes whose camera has a projection AND asks for passes (data/orthographic_passes.yml): rtc_scene_load_yaml_filter plus
+ * rtc_scene_load_yaml_projection's record — the lens, the projection, and the ao-*, gather-* and filter-* records of the
+ * camera, each with its has-flag, under the rules of the entries that introduced them. What the records are for:
+ * rtc_render_aov_projection, rtc_render_ao_projection, rtc_render_gather_projection and rtc_plane_filter. Every other entry
+ * refuses or ignores what it refused or ignored before: the entries without a projection record still refuse such a scene,
+ * naming rtc_scene_load_yaml_projection. */
+rtc_status  rtc_scene_load_yaml_projection_passes(const char *text, rtc_shape **shapes_out, uint32_t *n_out,
+                                                  struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                                  rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                                  struct rtc_lens *lens_out, uint32_t *has_lens_out,
+                                                  struct rtc_projection *proj_out, uint32_t *has_projection_out,
+                                                  rtc_ao *ao_out, uint32_t *has_ao_out, rtc_ao *gather_out, uint32_t *has_gather_out,
+                                                  rtc_filter *filter_out, uint32_t *has_filter_out);
+rtc_status  rtc_scene_load_yaml_projection_passes_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out,
+                                                       struct rtc_area_light *lights_out, uint32_t lights_cap, uint32_t *n_lights_out,
+                                                       rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                                       struct rtc_lens *lens_out, uint32_t *has_lens_out,
+                                                       struct rtc_projection *proj_out, uint32_t *has_projection_out,
+                                                       rtc_ao *ao_out, uint32_t *has_ao_out, rtc_ao *gather_out, uint32_t *has_gather_out,
+                                                       rtc_filter *filter_out, uint32_t *has_filter_out);
 
 /* ==== edge-adaptive anti-aliasing: extra rays only where the frame has contrast ====================== */
 /* A one-sample frame is fast and stair-stepped; cam->samples != 1 pays four or more rays for every pixel, sky and flat floor

@@ -766,6 +766,14 @@ def load_yaml_projection(text: str | None = None, path: str | None = None):
     return _load_scene("rtc_scene_load_yaml_projection", text, path, [RtcLens, RtcProjection])
 
 
+def load_yaml_projection_passes(text: str | None = None, path: str | None = None):
+    """load_yaml_projection and load_yaml_filter in one: scenes whose camera has a projection and asks for passes under it (ao-*,
+    gather-*, filter-* keys; data/orthographic_passes.yml): -> (World, RtcCamera, RtcLens or None, RtcProjection or None,
+    RtcAo or None, RtcAo or None, RtcFilter or None) — what DeviceWorld.render_aov / render_ao / render_gather take as
+    `projection` and `ao`, and plane_filter as `flt`."""
+    return _load_scene("rtc_scene_load_yaml_projection_passes", text, path, [RtcLens, RtcProjection, RtcAo, RtcAo, RtcFilter])
+
+
 def load_yaml_motion(text: str | None = None, path: str | None = None):
     """load_yaml_lens for scenes with motion blur (a shape's `motion:` transform list, the camera's `shutter-samples`):
     -> (World, RtcCamera, RtcLens or None, [RtcMotion], samples) — what Shutter.render takes."""
@@ -1897,39 +1905,53 @@ class DeviceWorld:
         if st != 0:
             raise RtcError(st, "rtc_render_views")
 
+    def _tile_pass(self, entry: str, cam: RtcCamera, projection, *rest) -> None:
+        """rtc_render_<entry>(ctx, world, cam, ...), or with `projection` (an RtcProjection: the orthographic or panorama
+        camera's rays in place of the pinhole's centre rays) rtc_render_<entry with _projection>(ctx, world, cam, proj, ...)."""
+        if projection is None:
+            _check(getattr(lib(), "rtc_render_" + entry)(self.ctx._h, self._h, C.byref(cam), *rest), "rtc_render_" + entry)
+            return
+        head, dev, _ = entry.partition("_device")
+        name = "rtc_render_" + head + "_projection" + dev
+        _check(getattr(lib(), name)(self.ctx._h, self._h, C.byref(cam), C.byref(projection), *rest), name)
+
     def render_aov(self, cam: RtcCamera, planes=("index", "depth", "point", "normal", "flags", "shadow"), mode: int = MODE_RENDER_ASYNC,
-                   flags: int = 0) -> dict:
+                   flags: int = 0, projection: RtcProjection | None = None) -> dict:
         """What each pixel's centre ray saw (rtc_render_aov): {plane: array} for the planes asked for — index int32 (H, W),
         depth float64 (H, W), point / normal float64 (H, W, 3), flags uint8 (H, W), shadow uint16 (H, W). A plane that is
-        not named is neither computed nor copied; without "shadow" no shadow ray is cast."""
+        not named is neither computed nor copied; without "shadow" no shadow ray is cast. With `projection` the pixel's ray
+        is that camera's (rtc_render_aov_projection); so for the five passes below."""
         out = _aov_arrays(planes, cam.vsize, cam.hsize)
         b = _aov_host_buffers(out)
-        _check(lib().rtc_render_aov(self.ctx._h, self._h, C.byref(cam), mode, flags, C.byref(b)), "rtc_render_aov")
+        self._tile_pass("aov", cam, projection, mode, flags, C.byref(b))
         return out
 
-    def render_aov_device(self, cam: RtcCamera, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+    def render_aov_device(self, cam: RtcCamera, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
+                          projection: RtcProjection | None = None) -> None:
         """The same into DEVICE buffers ({plane: address}; rtc_render_aov_device): enqueued on the context's stream."""
         b = _aov_buffers(pointers)
-        _check(lib().rtc_render_aov_device(self.ctx._h, self._h, C.byref(cam), mode, flags, C.byref(b)), "rtc_render_aov_device")
+        self._tile_pass("aov_device", cam, projection, mode, flags, C.byref(b))
 
-    def render_ao(self, cam: RtcCamera, ao: RtcAo, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> np.ndarray:
+    def render_ao(self, cam: RtcCamera, ao: RtcAo, mode: int = MODE_RENDER_ASYNC, flags: int = 0, projection: RtcProjection | None = None) -> np.ndarray:
         """The ambient-occlusion plane (rtc_render_ao): a (vsize, hsize) uint16 array, per pixel the number of the pass's
         samples that meet something within its radius; 0 where the centre ray misses."""
         out = np.empty((cam.vsize, cam.hsize), dtype=np.uint16)
-        _check(lib().rtc_render_ao(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, out.ctypes.data_as(C.POINTER(C.c_uint16))), "rtc_render_ao")
+        self._tile_pass("ao", cam, projection, C.byref(ao), mode, flags, out.ctypes.data_as(C.POINTER(C.c_uint16)))
         return out
 
-    def render_ao_device(self, cam: RtcCamera, ao: RtcAo, d_ao: int, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+    def render_ao_device(self, cam: RtcCamera, ao: RtcAo, d_ao: int, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
+                         projection: RtcProjection | None = None) -> None:
         """The same into a DEVICE buffer of vsize * hsize uint16 (rtc_render_ao_device): enqueued on the context's stream."""
-        _check(lib().rtc_render_ao_device(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.c_void_p(d_ao)), "rtc_render_ao_device")
+        self._tile_pass("ao_device", cam, projection, C.byref(ao), mode, flags, C.c_void_p(d_ao))
 
-    def render_gather(self, cam: RtcCamera, ao: RtcAo, mode: int = MODE_RENDER_ASYNC, flags: int = 0, planes=("radiance", "bounce")) -> dict:
+    def render_gather(self, cam: RtcCamera, ao: RtcAo, mode: int = MODE_RENDER_ASYNC, flags: int = 0, planes=("radiance", "bounce"),
+                      projection: RtcProjection | None = None) -> dict:
         """The one-bounce gather pass (rtc_render_gather): {"radiance": (vsize, hsize, 3), "bounce": (vsize, hsize, 3)} f64 for
         the planes asked for — the mean colour the fan `ao` sees from the centre ray's hit within its radius, and that mean
         times the hit's own base colour and diffuse coefficient, ready for add_scaled. Zeros where the centre ray misses."""
         out = {name: np.empty((cam.vsize, cam.hsize, 3)) for name in planes}
         b = RtcGatherBuffers(**{name: a.ctypes.data for name, a in out.items()})
-        _check(lib().rtc_render_gather(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.byref(b)), "rtc_render_gather")
+        self._tile_pass("gather", cam, projection, C.byref(ao), mode, flags, C.byref(b))
         return out
 
     def render_adaptive(self, cam: RtcCamera, spec: RtcAdaptive, mode: int = MODE_RENDER_ASYNC, flags: int = 0, with_mask: bool = False,
@@ -1961,11 +1983,12 @@ class DeviceWorld:
                                                 C.c_void_p(d_mask) if d_mask else None, C.byref(info)), "rtc_render_adaptive_device")
         return _adaptive_info_dict(info)
 
-    def render_gather_device(self, cam: RtcCamera, ao: RtcAo, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0) -> None:
+    def render_gather_device(self, cam: RtcCamera, ao: RtcAo, pointers: dict, mode: int = MODE_RENDER_ASYNC, flags: int = 0,
+                             projection: RtcProjection | None = None) -> None:
         """The same into DEVICE buffers of vsize * hsize * 3 doubles, {"radiance": pointer, "bounce": pointer} with either left
         out (rtc_render_gather_device): enqueued on the context's stream."""
         b = RtcGatherBuffers(**{name: int(p) for name, p in pointers.items()})
-        _check(lib().rtc_render_gather_device(self.ctx._h, self._h, C.byref(cam), C.byref(ao), mode, flags, C.byref(b)), "rtc_render_gather_device")
+        self._tile_pass("gather_device", cam, projection, C.byref(ao), mode, flags, C.byref(b))
 
     def color_at(self, rays: np.ndarray, remaining: int = 5, want_hits: bool = False, flags: int = 0):
         """World::color_at for an (n, 6) array of rays; returns rgb (n,3) [and the rtc_hit array]."""
@@ -2352,7 +2375,7 @@ def group_undeal_host(staging: np.ndarray, nranks: int, nframes: int, vsize: int
 
 
 __all__ = ["lib", "RtcError", "Matrix", "material", "sphere", "plane", "cube", "light", "area_light", "World", "camera", "ray_for_pixel", "lens", "lens_ray", "ao", "ao_expand", "ao_ray", "ao_from_hits", "apply_ao", "load_yaml_ao", "RtcAo", "MAX_AO_SAMPLES", "gather_from_hits", "add_scaled", "load_yaml_gather", "RtcGatherBuffers", "tonemap_spec", "bloom_spec", "luminance", "tonemap_resolve", "tonemap", "bloom", "bloom_weights", "load_yaml_post", "resize_spec", "resize_weights", "resize", "load_yaml_resize", "RtcResize", "RESIZE_BOX", "RESIZE_TRIANGLE", "RESIZE_CATMULL_ROM", "RESIZE_MITCHELL", "RESIZE_LANCZOS3", "MAX_RESIZE_TAPS", "RtcLuminance", "RtcTonemap", "RtcBloom", "TONEMAP_LINEAR", "TONEMAP_REINHARD", "TONEMAP_ACES", "TONEMAP_AUTO_EXPOSURE", "TONEMAP_AUTO_WHITE", "MAX_BLOOM_RADIUS", "adaptive", "adaptive_offset", "adaptive_mask", "load_yaml_adaptive", "RtcAdaptive", "RtcAdaptiveInfo", "MAX_AA_SAMPLES", "AA_DEFAULT_THRESHOLD", "AA_DEFAULT_STEPS", "AA_DEFAULT_MAX_RAYS", "filter_spec", "plane_filter", "counts_to_fraction", "apply_occlusion", "load_yaml_filter", "RtcFilter", "FILTER_SAME_OBJECT", "MAX_FILTER_PASSES", "FILTER_DEFAULT_PLANE_SIGMA", "FILTER_DEFAULT_PASSES", "FILTER_DEFAULT_NORMAL_SQUARINGS", "projection", "projection_ray", "projection_tables", "PROJ_ORTHOGRAPHIC", "PROJ_PANORAMA", "motion", "shutter_time", "shutter_shapes", "shutter_camera", "canvas_average", "Shutter",
-           "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
+           "load_yaml", "load_yaml_lens", "load_yaml_projection", "load_yaml_projection_passes", "load_yaml_motion", "load_lua", "LuaProgram", "LuaJob", "format_ppm", "write_ppm", "format_png", "write_png", "color_scale255", "to_rgba8", "gamma_thresholds", "Context", "DeviceWorld", "MODE_RENDER", "MODE_RENDER_ASYNC", "FLAG_NONE", "FLAG_NO_CULL", "FLAG_AA_RESAMPLE", "Group", "GroupWorld", "group_unique_id",
            "host_register", "host_unregister", "host_canvas", "host_canvas_rgb8", "host_canvas_rgba8", "format_ppm_rgb8", "write_ppm_rgb8",
            "group_packed_rows", "group_bands_owned", "group_row_owner", "group_packed_row_to_image", "group_undeal_host", "EXCHANGE_RCCL", "EXCHANGE_P2P", "GATHER_NONE", "GATHER_F64", "GATHER_U8",
            "SPHERE", "PLANE", "CUBE", "RtcCamera", "RtcHit", "RtcLight", "RtcAreaLight", "RtcLens", "RtcMotion", "RtcMaterial", "RtcShape", "RtcStats"]

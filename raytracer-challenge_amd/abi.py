@@ -371,6 +371,13 @@ PROTOTYPES = {
     "rtc_gather_from_hits": (C.c_int32, [C.POINTER(RtcHit), C.POINTER(RtcHit), PD, PD, U32, D, U32, U32, U32, C.POINTER(RtcGatherBuffers)]),
     "rtc_render_gather_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
     "rtc_render_gather": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
+    # the three passes with a projection's rays: the pinhole entry's signature with the projection after the camera
+    "rtc_render_aov_projection_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), U32, U32, C.POINTER(RtcAovBuffers)]),
+    "rtc_render_aov_projection": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), U32, U32, C.POINTER(RtcAovBuffers)]),
+    "rtc_render_ao_projection_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), C.POINTER(RtcAo), U32, U32, VP]),
+    "rtc_render_ao_projection": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), C.POINTER(RtcAo), U32, U32, C.POINTER(C.c_uint16)]),
+    "rtc_render_gather_projection_device": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
+    "rtc_render_gather_projection": (C.c_int32, [VP, VP, C.POINTER(RtcCamera), C.POINTER(RtcProjection), C.POINTER(RtcAo), U32, U32, C.POINTER(RtcGatherBuffers)]),
     "rtc_canvas_add_scaled": (C.c_int32, [PD, PD, D, U32, U32]),
     "rtc_canvas_add_scaled_device": (C.c_int32, [VP, VP, VP, D, U32, U32]),
     "rtc_float_format_for_name": (C.c_int32, [C.c_char_p, C.POINTER(U32)]),
@@ -434,6 +441,7 @@ _YAML_EXTRA = {  # entry -> what follows errbuf_len
     "lens": _LENS, "motion": _LENS + [P(P(RtcMotion)), P(U32), P(U32)], "projection": _LENS + _record(RtcProjection), "ao": _LENS + _AO,
     "gather": _LENS + _AO + _AO, "filter": _LENS + _AO + _AO + _record(RtcFilter), "adaptive": _record(RtcAdaptive),
     "post": _record(RtcTonemap) + _record(RtcBloom), "resize": _LENS + _record(RtcProjection) + [P(RtcResize), P(U32), P(U32), P(U32)],
+    "projection_passes": _LENS + _record(RtcProjection) + _AO + _AO + _record(RtcFilter),
 }
 _LOADERS = {"rtc_scene_load_yaml": _loader(RtcLight, capped=False), "rtc_scene_load_yaml_lights": _loader(RtcLight),
             "rtc_scene_load_yaml_area_lights": _loader(RtcAreaLight),

@@ -110,7 +110,7 @@ def _build_facade(name: str, force: bool = False) -> Path:
     return exe
 
 
-# the fourteen programs, each callable as f(force=False) -> Path
+# the fifteen programs, each callable as f(force=False) -> Path
 build_facade_tests = partial(_build_facade, "test_facade")  # the C++ mirror of the reference API
 build_facade_update_test = partial(_build_facade, "test_facade_update")  # the resident World updated in place
 build_facade_area_light_test = partial(_build_facade, "test_facade_area_light")  # World::add_area_light
@@ -125,6 +125,7 @@ build_facade_filter_test = partial(_build_facade, "test_facade_filter")  # Aov::
 build_facade_adaptive_test = partial(_build_facade, "test_facade_adaptive")  # Camera::set_adaptive
 build_facade_post_test = partial(_build_facade, "test_facade_post")  # Canvas::bloom and Canvas::tonemap
 build_facade_resize_test = partial(_build_facade, "test_facade_resize")  # Canvas::resized
+build_facade_projection_passes_test = partial(_build_facade, "test_facade_projection_passes")  # Camera::render_aov / render_ao / render_gather with a projection
 
 
 if __name__ == "__main__":

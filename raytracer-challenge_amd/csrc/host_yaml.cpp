@@ -944,6 +944,23 @@ rtc_status rtc_scene_load_yaml_filter(const char *text, rtc_shape **shapes_out, 
     return load_yaml(text, shapes_out, n_out, camera_out, errbuf, errbuf_len, w);
 }
 
+rtc_status rtc_scene_load_yaml_projection_passes(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                                 uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len,
+                                                 rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out, uint32_t *has_projection_out,
+                                                 rtc_ao *ao_out, uint32_t *has_ao_out, rtc_ao *gather_out, uint32_t *has_gather_out,
+                                                 rtc_filter *filter_out, uint32_t *has_filter_out) {
+    if (!lens_out || !has_lens_out || !proj_out || !has_projection_out || !ao_out || !has_ao_out || !gather_out || !has_gather_out || !filter_out ||
+        !has_filter_out)
+        return RTC_ERR_ARG;
+    Wanted w = area_lights(lights_out, lights_cap, n_lights_out);
+    w.lens = {lens_out, has_lens_out};
+    w.projection = {proj_out, has_projection_out};
+    w.ao = {ao_out, has_ao_out};
+    w.gather = {gather_out, has_gather_out};
+    w.filter = {filter_out, has_filter_out};
+    return load_yaml(text, shapes_out, n_out, camera_out, errbuf, errbuf_len, w);
+}
+
 rtc_status rtc_scene_load_yaml_adaptive(const char *text, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out, uint32_t lights_cap,
                                         uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf, size_t errbuf_len, rtc_adaptive *adaptive_out,
                                         uint32_t *has_adaptive_out) {
@@ -1035,6 +1052,16 @@ rtc_status rtc_scene_load_yaml_filter_file(const char *path, rtc_shape **shapes_
                                            rtc_filter *filter_out, uint32_t *has_filter_out) {
     return from_file(rtc_scene_load_yaml_filter, errbuf, errbuf_len, path, shapes_out, n_out, lights_out, lights_cap, n_lights_out, camera_out,
                      errbuf, errbuf_len, lens_out, has_lens_out, ao_out, has_ao_out, gather_out, has_gather_out, filter_out, has_filter_out);
+}
+
+rtc_status rtc_scene_load_yaml_projection_passes_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,
+                                                      uint32_t lights_cap, uint32_t *n_lights_out, rtc_camera *camera_out, char *errbuf,
+                                                      size_t errbuf_len, rtc_lens *lens_out, uint32_t *has_lens_out, rtc_projection *proj_out,
+                                                      uint32_t *has_projection_out, rtc_ao *ao_out, uint32_t *has_ao_out, rtc_ao *gather_out,
+                                                      uint32_t *has_gather_out, rtc_filter *filter_out, uint32_t *has_filter_out) {
+    return from_file(rtc_scene_load_yaml_projection_passes, errbuf, errbuf_len, path, shapes_out, n_out, lights_out, lights_cap, n_lights_out,
+                     camera_out, errbuf, errbuf_len, lens_out, has_lens_out, proj_out, has_projection_out, ao_out, has_ao_out, gather_out,
+                     has_gather_out, filter_out, has_filter_out);
 }
 
 rtc_status rtc_scene_load_yaml_adaptive_file(const char *path, rtc_shape **shapes_out, uint32_t *n_out, rtc_area_light *lights_out,

@@ -1708,11 +1708,17 @@ extern "C++" { // (two templates: the entry points around them have C linkage)
 // What the device entry points of the three tile passes (k_aov, k_ao, k_gather: one workgroup per 8x8 tile) share behind
 // their own argument checks: the tile-count limit, the World's current generation, k_aov's plan (the same grid for all three,
 // no dynamic LDS), the World's tables in `P` and the common fields of the pass's zeroed parameter block `A`; then
-// fill(G) -> rtc_status, the pass's own set-up and fields, and launch(P, src) -> hipError_t, its rtc_launch_* call, between
+// fill(G) -> rtc_status, the pass's own set-up and fields, and launch(P, src, proj) -> hipError_t, its rtc_launch_* call, between
 // order_behind_build and record_read.
+// `proj`: NULL for the pinhole's centre rays, which changes nothing of the above; otherwise the (validated) projection whose
+// rays the pass casts (rtc_render_*_projection*): its device block is filled as launch_planned fills k_trace's — the
+// orthographic terms, or the panorama's tables through pano_tables, under the same key and the same wait — and handed to
+// launch(); the plan, and with it what RTC_FLAG_LDS_TABLE answers, is the pinhole pass's. Such a launch is also the
+// context's last one (rtc_context_last_launch_info, rtc_context_last_launch_projection; `LL`: the lights it read, or
+// NULL); a pinhole pass leaves that record alone, as it always has.
 template <class FILL, class LAUNCH>
-static rtc_status tile_pass(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags, TileParams &A,
-                            FILL &&fill, LAUNCH &&launch) {
+static rtc_status tile_pass(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode, uint32_t flags,
+                            TileParams &A, const LaunchLights *LL, FILL &&fill, LAUNCH &&launch) {
     if ((unsigned long long)((cam->hsize + 7u) / 8u) * ((cam->vsize + 7u) / 8u) > 0x7fffffffull) return RTC_ERR_ARG; // one workgroup per tile
     HIP_TRY(hipSetDevice(ctx->device));
     rtc_world::Gen *gen = nullptr;
@@ -1737,9 +1743,28 @@ static rtc_status tile_pass(rtc_context *ctx, const rtc_world *w, const rtc_came
     A.pre_limit = G.pre_limit;
     const rtc_status fs = fill(G);
     if (fs != RTC_OK) return fs;
+    DevProjection dproj{};
+    if (proj) {
+        dproj.kind = proj->kind;
+        if (proj->kind == RTC_PROJ_ORTHOGRAPHIC) {
+            double t[3];
+            rtc_projection_ortho_terms(cam->hsize, cam->vsize, proj->width, t);
+            dproj.half_w = t[0]; dproj.half_h = t[1]; dproj.pixel = t[2];
+        } else {
+            const rtc_status ts = pano_tables(ctx, cam, proj);
+            if (ts != RTC_OK) return ts;
+            dproj.col = ctx->d_pano_col.get();
+            dproj.row = ctx->d_pano_row.get();
+        }
+    }
     HIP_TRY(order_behind_build(G, ctx->stream, BIT_STREAM));
-    HIP_TRY(launch(P, plan.src));
+    HIP_TRY(launch(P, plan.src, proj ? &dproj : nullptr));
     HIP_TRY(record_read(w, G, ctx->stream, BIT_STREAM));
+    if (proj) { // (uncounted in rtc_stats, as every tile pass: no pixels, no rays)
+        ctx->last = rtc_launch_info{(uint32_t)plan.src, 0u, 0u, 0u, 0u, 0u, 64u, 0u, 1u, 0u, (LL && LL->lt) ? 1u : 0u, 0u};
+        ctx->last_projection = proj->kind;
+        ++ctx->launches_total;
+    }
     return RTC_OK;
 }
 
@@ -1759,26 +1784,48 @@ template <size_t N> static rtc_status copy_planes_back(rtc_context *ctx, const P
 }
 } // extern "C++"
 
-rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
-                                 const rtc_aov_buffers *d) {
+// The three device entry points, each behind its two public forms: `proj` NULL is the pinhole entry, whose checks these are;
+// the projection entry has made rtc_render_projection's checks (projection_pass_args) first.
+static rtc_status aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode, uint32_t flags,
+                             const rtc_aov_buffers *d) {
     if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || !aov_any(d)) return RTC_ERR_ARG;
     if (((size_t)d->depth | (size_t)d->point | (size_t)d->normal) % sizeof(double) != 0 || (size_t)d->index % 4u != 0 || (size_t)d->shadow % 2u != 0)
         return RTC_ERR_ARG;
     AovParams A;
     std::memset(&A, 0, sizeof A);
     LaunchLights LL;
-    return tile_pass(ctx, w, cam, mode, flags, A,
+    return tile_pass(ctx, w, cam, proj, mode, flags, A, &LL,
         [&](rtc_world::Gen &G) {
             if (d->shadow) lights_of(G, LL);
             for (int k = 0; k < 3; ++k) A.light_pos[k] = G.light.position[k];
             A.index = d->index; A.depth = d->depth; A.point = d->point; A.normal = d->normal; A.flags = d->flags; A.shadow = d->shadow;
             return RTC_OK;
         },
-        [&](const RenderParams &P, int src) { return rtc_launch_aov(&A, &P, src, LL.xl, LL.lt, ctx->stream); });
+        [&](const RenderParams &P, int src, const DevProjection *dp) { return rtc_launch_aov(&A, &P, src, LL.xl, LL.lt, dp, ctx->stream); });
 }
 
-rtc_status rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
-                          const rtc_aov_buffers *host) {
+// What the projection forms of the tile passes check first, in this order (include/rtc.h): rtc_render_projection's own —
+// a context with its own World, a camera with a canvas, somewhere to write, a known mode; a valid projection, one ray per
+// pixel — and then the pinhole pass's.
+static rtc_status projection_pass_args(const rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode,
+                                       const void *out) {
+    if (check_render_args(ctx, w, cam, mode, out, nullptr) != RTC_OK) return RTC_ERR_ARG;
+    return check_projection(cam, proj);
+}
+
+rtc_status rtc_render_aov_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                                 const rtc_aov_buffers *d) {
+    return aov_device(ctx, w, cam, nullptr, mode, flags, d);
+}
+
+rtc_status rtc_render_aov_projection_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode,
+                                            uint32_t flags, const rtc_aov_buffers *d) {
+    const rtc_status ps = projection_pass_args(ctx, w, cam, proj, mode, d);
+    return ps != RTC_OK ? ps : aov_device(ctx, w, cam, proj, mode, flags, d);
+}
+
+static rtc_status aov_host(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode, uint32_t flags,
+                           const rtc_aov_buffers *host) {
     if (!ctx || !w || !cam || !host || w->ctx != ctx || !aov_any(host)) return RTC_ERR_ARG;
     if (cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1802,11 +1849,22 @@ rtc_status rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera
     d.index = host->index ? reinterpret_cast<int32_t *>(base + off[3]) : nullptr;
     d.shadow = host->shadow ? reinterpret_cast<uint16_t *>(base + off[4]) : nullptr;
     d.flags = host->flags ? base + off[5] : nullptr;
-    const rtc_status ls = rtc_render_aov_device(ctx, w, cam, mode, flags, &d);
+    const rtc_status ls = aov_device(ctx, w, cam, proj, mode, flags, &d);
     if (ls != RTC_OK) return ls;
     PlaneCopy back[6];
     for (int k = 0; k < 6; ++k) back[k] = PlaneCopy{dst[k], base + off[k], sizes[k]};
     return copy_planes_back(ctx, back);
+}
+
+rtc_status rtc_render_aov(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, uint32_t mode, uint32_t flags,
+                          const rtc_aov_buffers *host) {
+    return aov_host(ctx, w, cam, nullptr, mode, flags, host);
+}
+
+rtc_status rtc_render_aov_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, uint32_t mode,
+                                     uint32_t flags, const rtc_aov_buffers *host) {
+    const rtc_status ps = projection_pass_args(ctx, w, cam, proj, mode, host);
+    return ps != RTC_OK ? ps : aov_host(ctx, w, cam, proj, mode, flags, host);
 }
 
 rtc_status rtc_aov_view_rgb8_device(rtc_context *ctx, uint32_t view, const rtc_aov_buffers *d, uint32_t width, uint32_t height, double near,
@@ -1848,33 +1906,55 @@ static rtc_status ao_table(rtc_context *ctx, const rtc_ao *ao) {
     return RTC_OK;
 }
 
-rtc_status rtc_render_ao_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
-                                uint32_t flags, uint16_t *d_ao) {
+static rtc_status ao_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao, uint32_t mode,
+                            uint32_t flags, uint16_t *d_ao) {
     if (check_render_args(ctx, w, cam, mode, d_ao, nullptr) != RTC_OK || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
     if ((size_t)d_ao % 2u != 0) return RTC_ERR_ARG;
     AoParams A;
     std::memset(&A, 0, sizeof A);
-    return tile_pass(ctx, w, cam, mode, flags, A,
+    return tile_pass(ctx, w, cam, proj, mode, flags, A, nullptr,
         [&](rtc_world::Gen &) {
             A.radius = ao->radius;
             A.nsamples = ao->usteps * ao->vsteps;
             A.out = d_ao;
             return ao_table(ctx, ao);
         },
-        [&](const RenderParams &P, int src) { return rtc_launch_ao(&A, ctx->d_ao_dirs.get(), &P, src, ctx->stream); });
+        [&](const RenderParams &P, int src, const DevProjection *dp) { return rtc_launch_ao(&A, ctx->d_ao_dirs.get(), &P, src, dp, ctx->stream); });
 }
 
-rtc_status rtc_render_ao(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
-                         uint16_t *ao_out) {
+rtc_status rtc_render_ao_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                                uint32_t flags, uint16_t *d_ao) {
+    return ao_device(ctx, w, cam, nullptr, ao, mode, flags, d_ao);
+}
+
+rtc_status rtc_render_ao_projection_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao,
+                                           uint32_t mode, uint32_t flags, uint16_t *d_ao) {
+    const rtc_status ps = projection_pass_args(ctx, w, cam, proj, mode, d_ao);
+    return ps != RTC_OK ? ps : ao_device(ctx, w, cam, proj, ao, mode, flags, d_ao);
+}
+
+static rtc_status ao_host(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao, uint32_t mode,
+                          uint32_t flags, uint16_t *ao_out) {
     if (!ctx || !w || !cam || !ao_out || w->ctx != ctx || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
     if (cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)cam->hsize * cam->vsize;
     const rtc_status st = ctx->d_ao.reserve(px, &ctx->render_allocs);
     if (st != RTC_OK) return st;
-    const rtc_status ls = rtc_render_ao_device(ctx, w, cam, ao, mode, flags, ctx->d_ao.get());
+    const rtc_status ls = ao_device(ctx, w, cam, proj, ao, mode, flags, ctx->d_ao.get());
     if (ls != RTC_OK) return ls;
     return copy_planes_back(ctx, {{ao_out, ctx->d_ao.get(), sizeof(uint16_t) * px}});
+}
+
+rtc_status rtc_render_ao(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
+                         uint16_t *ao_out) {
+    return ao_host(ctx, w, cam, nullptr, ao, mode, flags, ao_out);
+}
+
+rtc_status rtc_render_ao_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao,
+                                    uint32_t mode, uint32_t flags, uint16_t *ao_out) {
+    const rtc_status ps = projection_pass_args(ctx, w, cam, proj, mode, ao_out);
+    return ps != RTC_OK ? ps : ao_host(ctx, w, cam, proj, ao, mode, flags, ao_out);
 }
 
 rtc_status rtc_canvas_apply_ao_device(rtc_context *ctx, void *d_rgb, const void *d_ao, uint32_t n_samples, double strength, uint32_t width,
@@ -1889,15 +1969,15 @@ rtc_status rtc_canvas_apply_ao_device(rtc_context *ctx, void *d_rgb, const void 
 }
 
 // ---- colour bleeding: the one-bounce gather pass (include/rtc.h) ----------------------------------------------------------
-rtc_status rtc_render_gather_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
-                                    uint32_t flags, const rtc_gather_buffers *d) {
+static rtc_status gather_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao,
+                                uint32_t mode, uint32_t flags, const rtc_gather_buffers *d) {
     if (check_render_args(ctx, w, cam, mode, d, nullptr) != RTC_OK || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
     if (!d->radiance && !d->bounce) return RTC_ERR_ARG;
     if (((size_t)d->radiance | (size_t)d->bounce) % sizeof(double) != 0) return RTC_ERR_ARG;
     GatherParams A;
     std::memset(&A, 0, sizeof A);
     LaunchLights LL;
-    return tile_pass(ctx, w, cam, mode, flags, A,
+    return tile_pass(ctx, w, cam, proj, mode, flags, A, &LL,
         [&](rtc_world::Gen &G) {
             lights_of(G, LL);
             A.radius = ao->radius;
@@ -1910,11 +1990,24 @@ rtc_status rtc_render_gather_device(rtc_context *ctx, const rtc_world *w, const 
             A.bounce = d->bounce;
             return ao_table(ctx, ao); // the fan is the AO pass's: one table per context, whichever pass filled it
         },
-        [&](const RenderParams &P, int src) { return rtc_launch_gather(&A, ctx->d_ao_dirs.get(), &P, src, LL.xl, LL.lt, ctx->stream); });
+        [&](const RenderParams &P, int src, const DevProjection *dp) {
+            return rtc_launch_gather(&A, ctx->d_ao_dirs.get(), &P, src, LL.xl, LL.lt, dp, ctx->stream);
+        });
 }
 
-rtc_status rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
-                             const rtc_gather_buffers *host) {
+rtc_status rtc_render_gather_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode,
+                                    uint32_t flags, const rtc_gather_buffers *d) {
+    return gather_device(ctx, w, cam, nullptr, ao, mode, flags, d);
+}
+
+rtc_status rtc_render_gather_projection_device(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj,
+                                               const rtc_ao *ao, uint32_t mode, uint32_t flags, const rtc_gather_buffers *d) {
+    const rtc_status ps = projection_pass_args(ctx, w, cam, proj, mode, d);
+    return ps != RTC_OK ? ps : gather_device(ctx, w, cam, proj, ao, mode, flags, d);
+}
+
+static rtc_status gather_host(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao, uint32_t mode,
+                              uint32_t flags, const rtc_gather_buffers *host) {
     if (!ctx || !w || !cam || !host || (!host->radiance && !host->bounce) || w->ctx != ctx || rtc_ao_validate(ao) != RTC_OK) return RTC_ERR_ARG;
     if (cam->hsize == 0 || cam->vsize == 0) return RTC_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1924,10 +2017,21 @@ rtc_status rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_cam
     rtc_gather_buffers d;
     d.radiance = host->radiance ? ctx->d_gather.get() : nullptr;
     d.bounce = host->bounce ? ctx->d_gather.get() + plane : nullptr;
-    const rtc_status ls = rtc_render_gather_device(ctx, w, cam, ao, mode, flags, &d);
+    const rtc_status ls = gather_device(ctx, w, cam, proj, ao, mode, flags, &d);
     if (ls != RTC_OK) return ls;
     return copy_planes_back(ctx, {{host->radiance, d.radiance, d.radiance ? sizeof(double) * plane : 0u},
                                   {host->bounce, d.bounce, d.bounce ? sizeof(double) * plane : 0u}});
+}
+
+rtc_status rtc_render_gather(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_ao *ao, uint32_t mode, uint32_t flags,
+                             const rtc_gather_buffers *host) {
+    return gather_host(ctx, w, cam, nullptr, ao, mode, flags, host);
+}
+
+rtc_status rtc_render_gather_projection(rtc_context *ctx, const rtc_world *w, const rtc_camera *cam, const rtc_projection *proj, const rtc_ao *ao,
+                                        uint32_t mode, uint32_t flags, const rtc_gather_buffers *host) {
+    const rtc_status ps = projection_pass_args(ctx, w, cam, proj, mode, host);
+    return ps != RTC_OK ? ps : gather_host(ctx, w, cam, proj, ao, mode, flags, host);
 }
 
 rtc_status rtc_canvas_add_scaled_device(rtc_context *ctx, void *d_rgb, const void *d_plane, double strength, uint32_t width, uint32_t height) {

@@ -201,7 +201,8 @@ struct DevLens {
 
 // Projection launches (rtc_render_projection*, include/rtc.h): the projection instantiations of k_trace take this block as
 // their LAST argument, exactly where the lens instantiations have their DevLens (never both); every other kernel has no such
-// argument. One flavour for both kinds: `kind` is wave-uniform and read in the ray generation only.
+// argument. One flavour for both kinds: `kind` is wave-uniform and read in the ray generation only. The tile passes take the
+// same block in the same place (rtc_render_aov_projection* and its kin): the projection instantiations of k_aov, k_ao, k_gather.
 //   orthographic: half_w, half_h, pixel as the host derived them (rtc_projection_ortho_terms) — per-lane origins on the
 //                 camera's z = 0 plane, one direction; the primary bundle is make_bundle's general form;
 //   panorama:     col[W][2] and row[H][2], {sin, cos} of the pixel's longitude and latitude, evaluated by the HOST

@@ -237,16 +237,18 @@ extern "C" hipError_t rtc_launch_light_lists_built(uint32_t n, uint32_t cap, con
                                                    hipStream_t stream);
 extern "C" rtc_status rtc_gamma_build_table(float gamma, DevGamma *g); // host_ppm.cpp
 extern "C" void rtc_projection_ortho_terms(uint32_t hsize, uint32_t vsize, double width, double out[3]); // host_math.cpp: half_w, half_h, pixel
-// k_aov / k_aov_view (rtc_kernels.hip). `P`: the World's tables only (fill_world); xl / lt: lights_of, read with A->shadow.
+// k_aov / k_aov_view (rtc_kernels.hip). `P`: the World's tables only (fill_world); xl / lt: lights_of, read with A->shadow;
+// `proj`: NULL (the pinhole's centre rays) or the projection whose rays the pass casts (tile_pass fills it).
 extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
-                                     hipStream_t stream);
+                                     const DevProjection *proj, hipStream_t stream);
 extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t stream);
 // k_ao / k_apply_ao (rtc_kernels.hip). `P`: the World's tables only (fill_world); `dirs`: the sample table in device memory.
-extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, hipStream_t stream);
+extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, const DevProjection *proj,
+                                    hipStream_t stream);
 extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_t n, uint32_t n_samples, double strength, hipStream_t stream);
-// k_gather / k_add_scaled (rtc_kernels.hip). `P`, `dirs`: as rtc_launch_ao; `xl` / `lt`: as rtc_launch_aov.
+// k_gather / k_add_scaled (rtc_kernels.hip). `P`, `dirs`: as rtc_launch_ao; `xl` / `lt` / `proj`: as rtc_launch_aov.
 extern "C" hipError_t rtc_launch_gather(const GatherParams *A, const double *dirs, const RenderParams *P, int src, const DevExtraLights *xl,
-                                        const DevLightTable *lt, hipStream_t stream);
+                                        const DevLightTable *lt, const DevProjection *proj, hipStream_t stream);
 extern "C" hipError_t rtc_launch_add_scaled(double *rgb, const double *plane, size_t n, double strength, hipStream_t stream);
 extern "C" hipError_t rtc_launch_canvas_to_rgba8(const double *rgb, size_t n, const DevGamma *g, unsigned char *out, hipStream_t stream);
 // k_average_over (rtc_shutter.hip): one pass of Color::average_over over whole canvases. Adds frames[f * stride + i], f = 0..nf-1

@@ -3119,6 +3119,49 @@ DEVI PrimaryRay primary_ray(const DevCamera &C, uint32_t px, uint32_t py) {
     return PrimaryRay{cam_origin, primary_dir(C, cam_origin, px, py)};
 }
 
+// The projection flavour of the tile passes (a trailing DevProjection, as k_trace's; rtc_render_aov_projection* and its
+// kin): the two stages that differ from the pinhole's, chosen with `if constexpr` — a pinhole instantiation sees neither.
+// rtc_projection_ray(x, y) (include/rtc.h) in k_trace's PROJ block's order, operation for operation. `kind` is wave-uniform
+// and read here only; what follows asks `shared`: every ray leaves the camera origin (panorama) or each its own point of the
+// camera's z = 0 plane (orthographic). The panorama's {sin, cos} come from the host's tables, one 16-byte load each; lanes
+// outside the canvas read entry 0.
+struct ProjectionRay { V3 ro, rd; bool shared; };
+DEVI ProjectionRay projection_ray(const DevCamera &C, const DevProjection &PJ, uint32_t px, uint32_t py, bool in_range) {
+    if (PJ.kind == RTC_PROJ_ORTHOGRAPHIC) {
+        const double ox = PJ.half_w - ((double)px + 0.5) * PJ.pixel;
+        const double oy = PJ.half_h - ((double)py + 0.5) * PJ.pixel;
+        const V3 ro = xpoint(C.vinv, mk(ox, oy, 0.));
+        return ProjectionRay{ro, vnormalize_plain(vsub(xpoint(C.vinv, mk(ox, oy, -1.)), ro)), false};
+    }
+    typedef double SinCos __attribute__((ext_vector_type(2)));
+    V3 cam_origin = xpoint(C.vinv, mk(0., 0., 0.));
+    cam_origin = mk(uniform_f64(cam_origin.x), uniform_f64(cam_origin.y), uniform_f64(cam_origin.z));
+    const SinCos c = *reinterpret_cast<const SinCos *>(PJ.col + 2u * (size_t)(in_range ? px : 0u));
+    const SinCos r = *reinterpret_cast<const SinCos *>(PJ.row + 2u * (size_t)(in_range ? py : 0u));
+    const V3 target = xpoint(C.vinv, mk(r.y * c.x, r.x, -(r.y * c.y)));
+    return ProjectionRay{cam_origin, vnormalize_plain(vsub(target, cam_origin)), true};
+}
+// World::intersect + get_hit of those rays, k_trace's PROJ flavour: a panorama's bundle has the camera origin as its shared
+// apex, and a two-level World takes the ordered walk with early stop; an orthographic tile's bundle is the general form
+// (apex = the axis lane's origin, rho the spread of the others), and without a shared origin there is no ordered walk: every
+// candidate is visited, behind the per-lane prefilter in two-level Worlds.
+template <int SRC, class PP>
+DEVI void projection_closest_hit(const PP &A, const Tables &T, const LdsView &L, bool traced, bool shared, V3 ro, V3 rd, double &best, int &hidx,
+                                 int &hroot) {
+    Bundle B{};
+    B.off = true;
+    if constexpr (IS_CULL(SRC)) {
+        if (ballot(traced) != 0ull) {
+            if (shared) B = make_bundle<true, false>(traced, ro, ro, rd, 0.);
+            else B = make_bundle<false, false>(traced, ro, ro, rd, 0.);
+        }
+    }
+    if (SRC == SRC_CULL2 && shared)
+        for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
+    else
+        for_each_object<SRC, SRC == SRC_CULL2>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
+}
+
 // The hit frame of k_ao and k_gather, in two parts. Intersection::compute_vectors' normal (shape.rs:144-152, 75-96) of object
 // `hidx` at `point`, flipped to face a ray of direction rd; and rtc_ao.h's tangent frame about it, built once per pixel, in
 // front of the sample loop (its one division).
@@ -3153,6 +3196,8 @@ DEVI void limit_reach(Bundle &Bk, double radius) {
 // primary pass). There is no binning kernel, no per-launch DevPrim table: closest_world transforms the origin itself, with
 // the arithmetic k_prep_primary has. XL: empty for one light, or the World's further lights (DevExtraLights / DevLightTable),
 // SHADOW instantiations only. Results do not depend on SRC: closer() orders by (t, insertion index), the cull is conservative.
+// A DevProjection as the pack's last element (both SHADOW forms): the projection flavour, one for both kinds — projection_ray
+// and projection_closest_hit in the place of primary_ray and the primary pass, everything behind the hit as it stands.
 template <int SRC, bool SHADOW, class... XL>
 __global__ void __launch_bounds__(64, RTC_WAVES_PER_SIMD)
 k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind, const DevShade *__restrict__ t_shade,
@@ -3160,19 +3205,32 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
       const DevBound *__restrict__ t_bound_s, const uint32_t *__restrict__ t_orig_s, const DevBound *__restrict__ t_gbound,
       const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
     static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "AOV launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
-    static_assert(sizeof...(XL) <= (SHADOW ? 1 : 0), "further lights only where shadow rays are cast, one block at most");
+    constexpr bool PROJ = has_projection_v<XL...>; // (the pack's last element, behind the further lights)
+    constexpr size_t LIGHT_BLOCKS = sizeof...(XL) - (PROJ ? 1 : 0);
+    static_assert(LIGHT_BLOCKS <= (SHADOW ? 1 : 0), "further lights only where shadow rays are cast, one block at most");
     Tables T{};
     tile_tables(T, t_isect, t_kind, t_shade, t_bound, t_isect_s, t_kind_s, t_bound_s, t_orig_s, t_gbound, t_pre, t_pre_s);
     const LdsView L{};
     const TileLane lane = tile_lane(A);
     const uint32_t px = lane.px, py = lane.py;
     const bool in_range = lane.in_range, traced = lane.traced;
-    const PrimaryRay pr = primary_ray(A.cam, px, py);
+    PrimaryRay pr;
+    bool shared_origin = true; // (a pinhole's rays; a projection's: projection_ray)
+    if constexpr (PROJ) {
+        const ProjectionRay q = projection_ray(A.cam, last_of(xl_arg...), px, py, in_range);
+        pr = PrimaryRay{q.ro, q.rd};
+        shared_origin = q.shared;
+    } else {
+        pr = primary_ray(A.cam, px, py);
+    }
     const V3 ro = pr.ro, rd = pr.rd;
 
     // ---- World::intersect + get_hit, streaming form (k_trace's primary pass without the tile lists) ----
     double best = __builtin_inf();
     int hidx = -1, hroot = 0;
+    if constexpr (PROJ) {
+        projection_closest_hit<SRC>(A, T, L, traced, shared_origin, ro, rd, best, hidx, hroot);
+    } else {
     Bundle B{};
     B.off = true;
     if constexpr (IS_CULL(SRC)) {
@@ -3182,6 +3240,7 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
         for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
     else
         for_each_object<SRC>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
+    }
     const bool hit = traced && hidx >= 0;
 
     // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96), the part the planes hold ----
@@ -3218,7 +3277,7 @@ k_aov(const AovParams A, const DevIsect *__restrict__ t_isect, const uint32_t *_
             if (shadowed) ++count;
         };
         one_light(mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]));
-        if constexpr (sizeof...(XL) == 1) {
+        if constexpr (LIGHT_BLOCKS == 1) {
             const auto &X = first_of(xl_arg...); // DevExtraLights (kernel arguments) or DevLightTable (HBM)
             const uint32_t n_extra = further_light_count(X);
             for (uint32_t li = 0; li < n_extra; ++li) one_light(further_light_position(X, li));
@@ -3273,25 +3332,39 @@ __global__ void __launch_bounds__(256) k_aov_view(const AovViewParams V) {
 #define RTC_AO_LANE_FILTER_ONE_LEVEL 1
 #endif
 template <int SRC> constexpr bool SAMPLE_LANE_FILTER = SRC == SRC_CULL2 || (SRC == SRC_CULL && RTC_AO_LANE_FILTER_ONE_LEVEL); // the sample walks of k_ao and k_gather
-template <int SRC>
+// XP: nothing, or a DevProjection (the projection flavour, as k_aov's; facing_normal then takes a direction per lane)
+template <int SRC, class... XP>
 __global__ void __launch_bounds__(64, RTC_WAVES_PER_SIMD)
 k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__restrict__ t_isect, const uint32_t *__restrict__ t_kind,
      const DevShade *__restrict__ t_shade, const DevBound *__restrict__ t_bound, const DevIsect *__restrict__ t_isect_s,
      const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s, const uint32_t *__restrict__ t_orig_s,
-     const DevBound *__restrict__ t_gbound, const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s) {
+     const DevBound *__restrict__ t_gbound, const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XP... xp_arg) {
     static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "AO launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
+    constexpr bool PROJ = has_projection_v<XP...>;
+    static_assert(sizeof...(XP) == (PROJ ? 1 : 0), "nothing, or the projection");
     Tables T{};
     tile_tables(T, t_isect, t_kind, t_shade, t_bound, t_isect_s, t_kind_s, t_bound_s, t_orig_s, t_gbound, t_pre, t_pre_s);
     const LdsView L{};
     const TileLane lane = tile_lane(A);
     const uint32_t px = lane.px, py = lane.py;
     const bool in_range = lane.in_range, traced = lane.traced;
-    const PrimaryRay pr = primary_ray(A.cam, px, py);
+    PrimaryRay pr;
+    bool shared_origin = true; // (a pinhole's rays; a projection's: projection_ray)
+    if constexpr (PROJ) {
+        const ProjectionRay q = projection_ray(A.cam, last_of(xp_arg...), px, py, in_range);
+        pr = PrimaryRay{q.ro, q.rd};
+        shared_origin = q.shared;
+    } else {
+        pr = primary_ray(A.cam, px, py);
+    }
     const V3 ro = pr.ro, rd = pr.rd;
 
     // ---- World::intersect + get_hit, streaming form (k_aov's primary pass) ----
     double best = __builtin_inf();
     int hidx = -1, hroot = 0;
+    if constexpr (PROJ) {
+        projection_closest_hit<SRC>(A, T, L, traced, shared_origin, ro, rd, best, hidx, hroot);
+    } else {
     Bundle B{};
     B.off = true;
     if constexpr (IS_CULL(SRC)) {
@@ -3301,6 +3374,7 @@ k_ao(const AoParams A, const double *__restrict__ t_dirs, const DevIsect *__rest
         for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
     else
         for_each_object<SRC>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
+    }
     const bool hit = traced && hidx >= 0;
 
     // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96): normal and over_point; then the tangent frame ----
@@ -3363,7 +3437,8 @@ __global__ void __launch_bounds__(256) k_apply_ao(double *__restrict__ rgb, cons
 //   4. the sample's colour added to three doubles per lane (a lane without a counted hit adds 0.0).
 // Lanes without work carry pending = false; every walk is reached by the whole wave. Whether `bounce` is wanted is a
 // wave-uniform argument (A.bounce): one `base` evaluation per pixel behind the loop, from the primary hit's index and
-// over-point, which are live through the loop anyway. XL: as k_aov's (nothing, DevExtraLights or DevLightTable).
+// over-point, which are live through the loop anyway. XL: as k_aov's (nothing, DevExtraLights or DevLightTable, and behind them
+// a DevProjection for the projection flavour).
 // Registers: the loop carries the primary hit's frame (normal, over, t, s: 24 VGPRs), the accumulator (6) and, across the
 // light loop, the secondary hit (normal, over, direction: 18) on top of what a walk needs, which is more than k_ao's 90; the
 // bound is four waves per SIMD (128 VGPRs), the step at which no instantiation spills (profiles/gather_kernel_resources.txt).
@@ -3377,19 +3452,32 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
          const uint32_t *__restrict__ t_kind_s, const DevBound *__restrict__ t_bound_s, const uint32_t *__restrict__ t_orig_s,
          const DevBound *__restrict__ t_gbound, const DevPre *__restrict__ t_pre, const DevPre *__restrict__ t_pre_s, const XL... xl_arg) {
     static_assert(SRC == SRC_SMEM || IS_CULL(SRC), "gather launches take SRC_SMEM, SRC_CULL or SRC_CULL2");
-    static_assert(sizeof...(XL) <= 1, "the further lights: one block at most");
+    constexpr bool PROJ = has_projection_v<XL...>; // (the pack's last element, behind the further lights)
+    constexpr size_t LIGHT_BLOCKS = sizeof...(XL) - (PROJ ? 1 : 0);
+    static_assert(LIGHT_BLOCKS <= 1, "the further lights: one block at most");
     Tables T{};
     tile_tables(T, t_isect, t_kind, t_shade, t_bound, t_isect_s, t_kind_s, t_bound_s, t_orig_s, t_gbound, t_pre, t_pre_s);
     const LdsView L{};
     const TileLane lane = tile_lane(A);
     const uint32_t px = lane.px, py = lane.py;
     const bool in_range = lane.in_range, traced = lane.traced;
-    const PrimaryRay pr = primary_ray(A.cam, px, py);
+    PrimaryRay pr;
+    bool shared_origin = true; // (a pinhole's rays; a projection's: projection_ray)
+    if constexpr (PROJ) {
+        const ProjectionRay q = projection_ray(A.cam, last_of(xl_arg...), px, py, in_range);
+        pr = PrimaryRay{q.ro, q.rd};
+        shared_origin = q.shared;
+    } else {
+        pr = primary_ray(A.cam, px, py);
+    }
     const V3 ro = pr.ro, rd = pr.rd;
 
     // ---- World::intersect + get_hit, streaming form (k_aov's primary pass) ----
     double best = __builtin_inf();
     int hidx = -1, hroot = 0;
+    if constexpr (PROJ) {
+        projection_closest_hit<SRC>(A, T, L, traced, shared_origin, ro, rd, best, hidx, hroot);
+    } else {
     Bundle B{};
     B.off = true;
     if constexpr (IS_CULL(SRC)) {
@@ -3399,6 +3487,7 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
         for_each_object<SRC, false>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd, [&](float key) { return ballot(traced && !(best < (double)key)) == 0ull; });
     else
         for_each_object<SRC>(A, T, L, traced, B, ClosestHit{traced, ro, rd, best, hidx, hroot}, ro, rd);
+    }
     const bool hit = traced && hidx >= 0;
 
     // ---- Intersection::compute_vectors (shape.rs:144-152, 75-96): normal and over_point; then the tangent frame ----
@@ -3464,7 +3553,7 @@ k_gather(const GatherParams A, const double *__restrict__ t_dirs, const DevIsect
             return term;
         };
         V3 surface = one_light(mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]), A);
-        if constexpr (sizeof...(XL) == 1) {
+        if constexpr (LIGHT_BLOCKS == 1) {
             const auto &X = first_of(xl_arg...); // DevExtraLights (kernel arguments) or DevLightTable (HBM)
             const uint32_t n_extra = further_light_count(X);
             for (uint32_t li = 0; li < n_extra; ++li) surface = vadd(surface, one_light(further_light_position(X, li), further_light_intensity(X, li)));
@@ -3531,18 +3620,32 @@ template <class F> static hipError_t with_tables(const RenderParams &P, F &&f) {
     return f(P.isect, P.kind, P.shade, P.bound, P.isect_s, P.kind_s, P.bound_s, P.orig_s, P.gbound, P.pre, P.pre_s);
 }
 
+// A tile pass's projection as the kernel's last argument: f() for a pinhole launch (proj == NULL), f(*proj) for an
+// orthographic or panorama one — rtc_launch_trace's checks: a known kind, and both tables for a panorama (they hold the
+// pass's W and H entries: the host's pano_tables).
+template <class F> static hipError_t with_projection(const DevProjection *proj, F &&f) {
+    if (proj == nullptr) return f();
+    if (proj->kind != RTC_PROJ_ORTHOGRAPHIC && (proj->kind != RTC_PROJ_PANORAMA || proj->col == nullptr || proj->row == nullptr))
+        return hipErrorInvalidValue;
+    return f(*proj);
+}
+
 // `P`: the World's tables only (fill_world). `xl` / `lt` (never both): the further lights of a World with several, read only when
-// A->shadow is set. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
+// A->shadow is set. src: SRC_SMEM, SRC_CULL or SRC_CULL2. `proj`: NULL, or the projection whose rays the pass casts.
 extern "C" hipError_t rtc_launch_aov(const AovParams *A, const RenderParams *P, int src, const DevExtraLights *xl, const DevLightTable *lt,
-                                     hipStream_t stream) {
+                                     const DevProjection *proj, hipStream_t stream) {
     const uint32_t tiles = tile_count(*A);
     if (tiles == 0u) return hipErrorInvalidValue;
-    return with_further_lights(xl, lt, [&](const auto &...x) {
-        return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-            return with_tables(*P, [&](auto... t) {
-                if (A->shadow == nullptr) hipLaunchKernelGGL((k_aov<S(), false>), dim3(tiles), dim3(64), 0, stream, *A, t...); // no shadow rays: the further lights are not read
-                else hipLaunchKernelGGL((k_aov<S(), true, std::decay_t<decltype(x)>...>), dim3(tiles), dim3(64), 0, stream, *A, t..., x...);
-                return hipGetLastError();
+    return with_projection(proj, [&](const auto &...pj) {
+        return with_further_lights(xl, lt, [&](const auto &...x) {
+            return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+                return with_tables(*P, [&](auto... t) {
+                    if (A->shadow == nullptr) // no shadow rays: the further lights are not read
+                        hipLaunchKernelGGL((k_aov<S(), false, std::decay_t<decltype(pj)>...>), dim3(tiles), dim3(64), 0, stream, *A, t..., pj...);
+                    else
+                        hipLaunchKernelGGL((k_aov<S(), true, std::decay_t<decltype(x)>..., std::decay_t<decltype(pj)>...>), dim3(tiles), dim3(64), 0, stream, *A, t..., x..., pj...);
+                    return hipGetLastError();
+                });
             });
         });
     });
@@ -3557,14 +3660,18 @@ extern "C" hipError_t rtc_launch_aov_view(const AovViewParams *V, hipStream_t st
 }
 
 // `P`: the World's tables only (fill_world). `dirs`: A->nsamples directions in device memory. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
-extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, hipStream_t stream) {
+// `proj`: as rtc_launch_aov's.
+extern "C" hipError_t rtc_launch_ao(const AoParams *A, const double *dirs, const RenderParams *P, int src, const DevProjection *proj,
+                                    hipStream_t stream) {
     const uint32_t tiles = tile_count(*A);
     if (tiles == 0u || A->out == nullptr || dirs == nullptr) return hipErrorInvalidValue;
     if (A->nsamples == 0u || A->nsamples > RTC_MAX_AO_SAMPLES) return hipErrorInvalidValue;
-    return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-        return with_tables(*P, [&](auto... t) {
-            hipLaunchKernelGGL((k_ao<S()>), dim3(tiles), dim3(64), 0, stream, *A, dirs, t...);
-            return hipGetLastError();
+    return with_projection(proj, [&](const auto &...pj) {
+        return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+            return with_tables(*P, [&](auto... t) {
+                hipLaunchKernelGGL((k_ao<S(), std::decay_t<decltype(pj)>...>), dim3(tiles), dim3(64), 0, stream, *A, dirs, t..., pj...);
+                return hipGetLastError();
+            });
         });
     });
 }
@@ -3578,17 +3685,19 @@ extern "C" hipError_t rtc_launch_apply_ao(double *rgb, const uint16_t *ao, size_
 }
 
 // `P`: the World's tables only (fill_world). `dirs`: A->nsamples directions in device memory. `xl` / `lt` (never both): the
-// further lights of a World with several. src: SRC_SMEM, SRC_CULL or SRC_CULL2.
+// further lights of a World with several. src: SRC_SMEM, SRC_CULL or SRC_CULL2. `proj`: as rtc_launch_aov's.
 extern "C" hipError_t rtc_launch_gather(const GatherParams *A, const double *dirs, const RenderParams *P, int src, const DevExtraLights *xl,
-                                        const DevLightTable *lt, hipStream_t stream) {
+                                        const DevLightTable *lt, const DevProjection *proj, hipStream_t stream) {
     const uint32_t tiles = tile_count(*A);
     if (tiles == 0u || (A->radiance == nullptr && A->bounce == nullptr) || dirs == nullptr) return hipErrorInvalidValue;
     if (A->nsamples == 0u || A->nsamples > RTC_MAX_AO_SAMPLES) return hipErrorInvalidValue;
-    return with_further_lights(xl, lt, [&](const auto &...x) {
-        return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
-            return with_tables(*P, [&](auto... t) {
-                hipLaunchKernelGGL((k_gather<S(), std::decay_t<decltype(x)>...>), dim3(tiles), dim3(64), 0, stream, *A, dirs, t..., x...);
-                return hipGetLastError();
+    return with_projection(proj, [&](const auto &...pj) {
+        return with_further_lights(xl, lt, [&](const auto &...x) {
+            return with_src<SRC_SMEM, SRC_CULL, SRC_CULL2>(src, [&](auto S) {
+                return with_tables(*P, [&](auto... t) {
+                    hipLaunchKernelGGL((k_gather<S(), std::decay_t<decltype(x)>..., std::decay_t<decltype(pj)>...>), dim3(tiles), dim3(64), 0, stream, *A, dirs, t..., x..., pj...);
+                    return hipGetLastError();
+                });
             });
         });
     });

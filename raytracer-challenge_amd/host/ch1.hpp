@@ -587,7 +587,10 @@ class Camera { // camera.rs:17-160
     // Orthographic and panorama cameras (rtc_projection, include/rtc.h). With a projection set, render / render_async and
     // their rgb8 forms go through rtc_render_projection / rtc_render_projection_rgb8: this camera's size and view, the
     // projection's rays (antialiasing_samples must be 1). A lens and a projection exclude each other (whichever is set second
-    // throws); the rgba8 forms, render_aov and a shutter have no projection entry and throw. Not part of the reference's Camera.
+    // throws); the rgba8 forms and a shutter have no projection entry and throw. The passes — render_aov, render_ao,
+    // render_gather — do not read the camera's projection and throw while one is set: a caller who wants the planes of a
+    // projection's rays says so, with the overloads below that take the rtc_projection explicitly (projection() hands the
+    // camera's own back). Not part of the reference's Camera.
     void set_projection(const rtc_projection &p) {
         check(rtc_projection_validate(&p), "Camera::set_projection");
         if (has_lens_) check(RTC_ERR_UNSUPPORTED, "Camera::set_projection on a camera with a lens");
@@ -598,6 +601,10 @@ class Camera { // camera.rs:17-160
     void set_panorama(double h_span = 6.283185307179586 /* 2 pi */, double v_span = 3.141592653589793 /* pi */) { set_projection(rtc_projection{RTC_PROJ_PANORAMA, 0., h_span, v_span}); }
     void clear_projection() { has_projection_ = false; }
     bool has_projection() const { return has_projection_; }
+    const rtc_projection &projection() const { // the projection set_projection stored; throws when none is set
+        if (!has_projection_) check(RTC_ERR_ARG, "Camera::projection without a projection set");
+        return proj_;
+    }
     // Motion blur (rtc_shutter, include/rtc.h): with a shutter set, every render form — the lens and render_rgba8 with a
     // lens included — is the mean of `samples` frames (1..RTC_MAX_SHUTTER_SAMPLES) of the World at the cell centres of the
     // shutter interval, its shapes moved as World::set_shape_motion says, rendered and averaged on the device by one
@@ -653,11 +660,20 @@ class Camera { // camera.rs:17-160
     // shaded under the World's lights. A lens, a shutter or a projection has no gather form (RTC_ERR_UNSUPPORTED).
     Gather render_gather(const World &w, const rtc_ao &ao) const { return run_gather(w, ao, RTC_MODE_RENDER); }
     Gather render_async_gather(const World &w, const rtc_ao &ao) const { return run_gather(w, ao, RTC_MODE_RENDER_ASYNC); }
+    // The same passes under an orthographic or panorama camera (rtc_render_aov_projection, rtc_render_ao_projection,
+    // rtc_render_gather_projection): this camera's size and view, the rays of `p`, whether or not the camera has a
+    // projection of its own set (antialiasing_samples must be 1). The planes are the C-ABI's; the Aov filters, views and
+    // saves to EXR as any other. A lens or a shutter is refused, as by the forms above.
+    Aov render_aov(const World &w, const rtc_projection &p) const { return run_aov(w, RTC_MODE_RENDER, &p); }
+    Aov render_async_aov(const World &w, const rtc_projection &p) const { return run_aov(w, RTC_MODE_RENDER_ASYNC, &p); }
+    Aov render_ao(const World &w, const rtc_ao &ao, const rtc_projection &p) const { return run_ao(w, ao, RTC_MODE_RENDER, &p); }
+    Gather render_gather(const World &w, const rtc_ao &ao, const rtc_projection &p) const { return run_gather(w, ao, RTC_MODE_RENDER, &p); }
 
   private:
-    Aov run_aov(const World &w, uint32_t mode) const {
+    // (`p`: the explicit projection of the overloads above; NULL: the pinhole forms, which refuse a camera with one set)
+    Aov run_aov(const World &w, uint32_t mode, const rtc_projection *p = nullptr) const {
         if (has_lens_ || shutter_) check(RTC_ERR_UNSUPPORTED, "Camera::render_aov with a lens or a shutter");
-        if (has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_aov with a projection");
+        if (!p && has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_aov with a projection");
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
         Aov a;
@@ -668,11 +684,12 @@ class Camera { // camera.rs:17-160
         World::Uploaded up(w);
         a.n_lights = rtc_world_light_count(up.w);
         const rtc_aov_buffers b = a.buffers();
-        check(rtc_render_aov(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, &b), "Camera::render_aov");
+        if (p) check(rtc_render_aov_projection(Device::get(), up.w, &c, p, mode, RTC_FLAG_NONE, &b), "Camera::render_aov");
+        else check(rtc_render_aov(Device::get(), up.w, &c, mode, RTC_FLAG_NONE, &b), "Camera::render_aov");
         return a;
     }
-    Aov run_ao(const World &w, const rtc_ao &ao, uint32_t mode) const {
-        if (has_lens_ || shutter_ || has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_ao with a lens, a shutter or a projection");
+    Aov run_ao(const World &w, const rtc_ao &ao, uint32_t mode, const rtc_projection *p = nullptr) const {
+        if (has_lens_ || shutter_ || (!p && has_projection_)) check(RTC_ERR_UNSUPPORTED, "Camera::render_ao with a lens, a shutter or a projection");
         check(rtc_ao_validate(&ao), "Camera::render_ao");
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
@@ -681,11 +698,12 @@ class Camera { // camera.rs:17-160
         a.n_lights = ao.usteps * ao.vsteps;
         a.shadow.assign(static_cast<size_t>(hsize) * vsize, 0);
         World::Uploaded up(w);
-        check(rtc_render_ao(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, a.shadow.data()), "Camera::render_ao");
+        if (p) check(rtc_render_ao_projection(Device::get(), up.w, &c, p, &ao, mode, RTC_FLAG_NONE, a.shadow.data()), "Camera::render_ao");
+        else check(rtc_render_ao(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, a.shadow.data()), "Camera::render_ao");
         return a;
     }
-    Gather run_gather(const World &w, const rtc_ao &ao, uint32_t mode) const {
-        if (has_lens_ || shutter_ || has_projection_) check(RTC_ERR_UNSUPPORTED, "Camera::render_gather with a lens, a shutter or a projection");
+    Gather run_gather(const World &w, const rtc_ao &ao, uint32_t mode, const rtc_projection *p = nullptr) const {
+        if (has_lens_ || shutter_ || (!p && has_projection_)) check(RTC_ERR_UNSUPPORTED, "Camera::render_gather with a lens, a shutter or a projection");
         check(rtc_ao_validate(&ao), "Camera::render_gather");
         rtc_camera c = flat_;
         c.samples = antialiasing_samples;
@@ -695,7 +713,8 @@ class Camera { // camera.rs:17-160
         g.bounce.assign(static_cast<size_t>(hsize) * vsize * 3, 0.0);
         const rtc_gather_buffers b{g.radiance.data(), g.bounce.data()};
         World::Uploaded up(w);
-        check(rtc_render_gather(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, &b), "Camera::render_gather");
+        if (p) check(rtc_render_gather_projection(Device::get(), up.w, &c, p, &ao, mode, RTC_FLAG_NONE, &b), "Camera::render_gather");
+        else check(rtc_render_gather(Device::get(), up.w, &c, &ao, mode, RTC_FLAG_NONE, &b), "Camera::render_gather");
         return g;
     }
     Canvas run(const World &w, uint32_t mode) const {

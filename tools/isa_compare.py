@@ -1,5 +1,5 @@
 """Per-kernel comparison of two sets of device-only assembly listings of the kernel units; CPU only.
-usage: python tools/isa_compare.py A B
+usage: python tools/isa_compare.py A B [--rename PATTERN REPLACEMENT]...
 
 A / B: one side each, as a listing, several joined by commas (A1.s,A2.s) or a directory of *.s files. A listing is
 `hipcc <build.py's kernel compile line> --cuda-device-only -S` of one unit of build.KERNEL_SOURCES; a side is one version
@@ -8,7 +8,9 @@ one side compiles twice (the same symbol in two of its listings: each kernel bel
 one side has, the kernels whose instruction stream differs (with both lengths), and a one-line total. A
 stream is the kernel's instructions and local labels: directives, comments and everything after ';' are dropped, and a
 label's function number (.LBB<n>_<k>) is masked, since it only counts the kernels in front of this one. Streams are hashed
-and compared whole; no instruction is looked for. Exit status 1 when anything differs or is compiled twice."""
+and compared whole; no instruction is looked for. Exit status 1 when anything differs or is compiled twice.
+--rename: side A's symbols go through re.sub(PATTERN, REPLACEMENT) before the comparison, for a kernel whose mangled name
+changed while its code should not have (a template parameter added to it); every symbol renamed is printed with its new name."""
 import hashlib
 import re
 import sys
@@ -50,8 +52,14 @@ def side(arg):
     return out, twice
 
 
-def main(a_arg, b_arg):
+def main(a_arg, b_arg, renames=()):
     (a, a_twice), (b, b_twice) = side(a_arg), side(b_arg)
+    for pattern, repl in renames:
+        for name in sorted(a):
+            new = re.sub(pattern, repl, name)
+            if new != name:
+                print(f"renamed: {name}\n     ->  {new}")
+                a[new] = a.pop(name)
     for name in sorted(set(a) - set(b)):
         print(f"only in {a_arg}: {name}")
     for name in sorted(set(b) - set(a)):
@@ -67,6 +75,7 @@ def main(a_arg, b_arg):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    rest = sys.argv[3:]
+    if len(sys.argv) < 3 or len(rest) % 3 or any(rest[k] != "--rename" for k in range(0, len(rest), 3)):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], [(rest[k + 1], rest[k + 2]) for k in range(0, len(rest), 3)]))

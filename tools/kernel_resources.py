@@ -34,6 +34,7 @@ with ThreadPoolExecutor(max_workers=build.jobs()) as pool:
     t = "".join(pool.map(remarks, build.FILTER_KERNEL_SOURCES if FILTER else [n for n in build.ADAPTIVE_SOURCES if n.endswith(".hip")] if ADAPTIVE
                          else [n for n in build.POST_SOURCES if n.endswith(".hip")] if POST
                          else [n for n in build.RESIZE_SOURCES if n.endswith(".hip")] if RESIZE else build.KERNEL_SOURCES))
+PROJ = lambda name: ",proj>" if "DevProjection" in name else ">"  # the projection flavour of a tile pass (rtc_render_*_projection*)
 rows = []
 for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = blk.split("\n")[0].strip()
@@ -56,15 +57,15 @@ for blk in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         # the thin-lens flavour (rtc_render_lens*) and the projection flavour (rtc_render_projection*)
         tag += ",lens>" if "DevLens" in name else ",proj>" if "DevProjection" in name else ">"
     elif (a := re.search(r"k_aovILi(\d)ELb(\d)E", name)):  # the AOV kernel: source, shadow passes, where the further lights come from
-        tag = "k_aov<%s,shadow=%s" % a.groups() + (",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">")
+        tag = "k_aov<%s,shadow=%s" % a.groups() + (",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else "") + PROJ(name)
     elif "k_aov_view" in name:
         tag = "k_aov_view"
     elif (a := re.search(r"k_aoILi(\d)E", name)):  # the ambient-occlusion kernel: source
-        tag = "k_ao<%s>" % a.group(1)
+        tag = "k_ao<%s" % a.group(1) + PROJ(name)
     elif "k_apply_ao" in name:
         tag = "k_apply_ao"
     elif (a := re.search(r"k_gatherILi(\d)E", name)):  # the gather kernel: source, where the further lights come from
-        tag = "k_gather<%s" % a.group(1) + (",multi>" if "DevExtraLights" in name else ",table>" if "DevLightTable" in name else ">")
+        tag = "k_gather<%s" % a.group(1) + (",multi" if "DevExtraLights" in name else ",table" if "DevLightTable" in name else "") + PROJ(name)
     elif "k_add_scaled" in name:
         tag = "k_add_scaled"
     elif (a := re.search(r"k_atrousILj(\d)ELb(\d)E", name)):  # the filter kernel: channels, RTC_FILTER_SAME_OBJECT

@@ -21,7 +21,10 @@ point and normal planes of the same frame — with the filter the scene's camera
 filter-normal-squarings), the one given here, or rtc.h's defaults — and writes OUTDIR/ao_filtered.png and
 beauty_ao_filtered.png (rtc_counts_to_fraction_device, rtc_plane_filter_device, rtc_canvas_apply_occlusion_device),
 OUTDIR/bounce_filtered.png and frame_bounce_filtered.png, and, with both passes, OUTDIR/frame_filtered.png: the colour frame times
-the filtered occlusion plus the filtered bounce. Needs an MI355X (there is no CPU path)."""
+the filtered occlusion plus the filtered bounce. A scene whose camera has a projection (projection: orthographic | panorama,
+data/passes/orthographic_passes.yml) gives the same files under that camera's rays: the colour frame by
+rtc_render_projection_rows, the planes by rtc_render_aov_projection_device and its kin. Needs an MI355X (there is no CPU
+path)."""
 import argparse
 import sys
 from pathlib import Path
@@ -48,14 +51,20 @@ def main(argv):
     abi = __import__("importlib").import_module(rtc.__name__ + ".abi")
     import numpy as np
     import torch
-    world, cam = rtc.load_yaml(path=args.scene)
+    proj = scene_ao = scene_gather = scene_filter = None
+    try:
+        world, cam = rtc.load_yaml(path=args.scene)
+    except rtc.RtcError as refused:   # a camera with a projection: the entry that hands it out with the camera's passes
+        world, cam, lens, proj, scene_ao, scene_gather, scene_filter = rtc.load_yaml_projection_passes(path=args.scene)
+        if proj is None or lens is not None:
+            raise refused
     ao = None
     if args.ao is not None:
         if args.ao:
             radius, usteps, vsteps = args.ao.split(",")
             ao = rtc.ao(float(radius), int(usteps), int(vsteps))
         else:
-            ao = rtc.load_yaml_ao(path=args.scene)[3]
+            ao = scene_ao if proj is not None else rtc.load_yaml_ao(path=args.scene)[3]
             if ao is None:
                 ap.error("--ao: the scene's camera has no ao-radius; give RADIUS,USTEPS,VSTEPS")
     gather = None
@@ -64,7 +73,7 @@ def main(argv):
             radius, usteps, vsteps = args.gather.split(",")
             gather = rtc.ao(float(radius), int(usteps), int(vsteps))
         else:
-            gather = rtc.load_yaml_gather(path=args.scene)[4]
+            gather = scene_gather if proj is not None else rtc.load_yaml_gather(path=args.scene)[4]
             if gather is None:
                 ap.error("--gather: the scene's camera has no gather-radius; give RADIUS,USTEPS,VSTEPS")
     flt = None
@@ -75,7 +84,7 @@ def main(argv):
             sigma, passes, squarings = args.filter.split(",")
             flt = rtc.filter_spec(float(sigma), passes=int(passes), normal_squarings=int(squarings))
         else:
-            flt = rtc.load_yaml_filter(path=args.scene)[5] or rtc.filter_spec()
+            flt = (scene_filter if proj is not None else rtc.load_yaml_filter(path=args.scene)[5]) or rtc.filter_spec()
     width, height = cam.hsize, cam.vsize
     out = Path(args.outdir)
     out.mkdir(parents=True, exist_ok=True)
@@ -86,9 +95,16 @@ def main(argv):
     pic = torch.zeros(width * height * 3, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
     sizes = {}
-    dw.render_rows(cam, 0, height, None, d_ptr8=pic.data_ptr())   # 8-bit rows only
+
+    def render_rows(d_ptr, d_ptr8=None):   # the colour frame: the pinhole's, or the projection's
+        if proj is None:
+            dw.render_rows(cam, 0, height, d_ptr, d_ptr8=d_ptr8)
+        else:
+            dw.render_projection_rows(cam, proj, 0, height, d_ptr, d_ptr8=d_ptr8)
+
+    render_rows(None, d_ptr8=pic.data_ptr())   # 8-bit rows only
     sizes["beauty"] = (out / "beauty.png").write_bytes(enc.encode_device("png", pic.data_ptr(), width, height, 3))
-    dw.render_aov_device(cam, {p: t.data_ptr() for p, t in dev.items()})
+    dw.render_aov_device(cam, {p: t.data_ptr() for p, t in dev.items()}, projection=proj)
     near, far = args.near, args.far
     if near is None or far is None:
         ctx.synchronize()
@@ -109,7 +125,7 @@ def main(argv):
             ap.error(f"--exr: not a plane of the file: {', '.join(unknown)}")
         rgb = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
         torch.cuda.synchronize()
-        dw.render_rows(cam, 0, height, rgb.data_ptr())
+        render_rows(rgb.data_ptr())
         fenc = rtc.FloatEncoder(ctx)
         sizes["frame.exr"] = (out / "frame.exr").write_bytes(
             fenc.encode_device("exr", rgb.data_ptr(), width, height, {p: dev[p].data_ptr() for p in wanted}, "half"))
@@ -121,10 +137,10 @@ def main(argv):
         rgb = torch.zeros(width * height * 3, dtype=torch.float64, device="cuda:0")
         rgba = torch.zeros(width * height * 4, dtype=torch.uint8, device="cuda:0")
         torch.cuda.synchronize()
-        dw.render_ao_device(cam, ao, dev["shadow"].data_ptr())   # (the shadow plane's pictures are written: its buffer is free)
+        dw.render_ao_device(cam, ao, dev["shadow"].data_ptr(), projection=proj)   # (the shadow plane's pictures are written: its buffer is free)
         ctx.aov_view_device("shadow", {"shadow": dev["shadow"].data_ptr()}, width, height, pic.data_ptr(), n_lights=n)
         sizes["ao"] = (out / "ao.png").write_bytes(enc.encode_device("png", pic.data_ptr(), width, height, 3))
-        dw.render_rows(cam, 0, height, rgb.data_ptr())
+        render_rows(rgb.data_ptr())
         ctx.apply_ao_device(rgb.data_ptr(), dev["shadow"].data_ptr(), n, args.ao_strength, width, height)
         ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
         sizes["beauty_ao"] = (out / "beauty_ao.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
@@ -138,7 +154,7 @@ def main(argv):
             ctx.apply_occlusion_device(rgb.data_ptr(), occ_f.data_ptr(), 1.0, width, height)
             ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
             sizes["ao_filtered"] = (out / "ao_filtered.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
-            dw.render_rows(cam, 0, height, rgb.data_ptr())
+            render_rows(rgb.data_ptr())
             ctx.apply_occlusion_device(rgb.data_ptr(), occ_f.data_ptr(), args.ao_strength, width, height)
             ctx.canvas_to_rgba8_device(rgb.data_ptr(), width, height, 1.0, rgba.data_ptr())
             sizes["beauty_ao_filtered"] = (out / "beauty_ao_filtered.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
@@ -153,8 +169,8 @@ def main(argv):
             ctx.canvas_to_rgba8_device(d_canvas, width, height, 1.0, rgba.data_ptr())
             sizes[name] = (out / f"{name}.png").write_bytes(enc.encode_device("png", rgba.data_ptr(), width, height, 4))
 
-        dw.render_rows(cam, 0, height, rgb.data_ptr())
-        dw.render_gather_device(cam, gather, {"bounce": bounce.data_ptr()})
+        render_rows(rgb.data_ptr())
+        dw.render_gather_device(cam, gather, {"bounce": bounce.data_ptr()}, projection=proj)
         save("frame", rgb.data_ptr())
         save("bounce", bounce.data_ptr())
         ctx.add_scaled_device(rgb.data_ptr(), bounce.data_ptr(), args.gather_strength, width, height)
@@ -164,14 +180,14 @@ def main(argv):
             torch.cuda.synchronize()
             ctx.plane_filter_device(bounce.data_ptr(), 3, guides, width, height, flt, bounce_f.data_ptr())
             save("bounce_filtered", bounce_f.data_ptr())
-            dw.render_rows(cam, 0, height, rgb.data_ptr())
+            render_rows(rgb.data_ptr())
             ctx.add_scaled_device(rgb.data_ptr(), bounce_f.data_ptr(), args.gather_strength, width, height)
             save("frame_bounce_filtered", rgb.data_ptr())
             if filtered_frame is not None:
                 ctx.add_scaled_device(filtered_frame.data_ptr(), bounce_f.data_ptr(), args.gather_strength, width, height)
                 save("frame_filtered", filtered_frame.data_ptr())
     hits = int((dev["index"] >= 0).sum().item())
-    print(f"{out}: {width}x{height}, {len(world)} shapes, {n_lights} light sample(s), {hits} of {width * height} pixels hit, "
+    print(f"{out}: {width}x{height}{'' if proj is None else ', ' + ('orthographic' if proj.kind == rtc.PROJ_ORTHOGRAPHIC else 'panorama')}, {len(world)} shapes, {n_lights} light sample(s), {hits} of {width * height} pixels hit, "
           f"depth {near:.6g} .. {far:.6g}; bytes: " + ", ".join(f"{k if '.' in k else k + '.png'} {v}" for k, v in sizes.items()))
     enc.close()
     dw.close()
